@@ -757,6 +757,36 @@ class Watchdog:
                 os._exit(0 if self.rank == 0 else 3)
 
 
+DUMP_SAMPLE_ROWS = 1 << 18   # states of the last timed batch written by --dump-outputs (all of them in smaller batches)
+DUMP_BLOCK = 4096            # candidates per entry of the whole-batch accepted counts
+
+
+def dump_outputs(out_dir, se3, valid):
+    """What the timed path handed its caller in the last timed step, as .npy files for comparing two builds:
+    sample_rows.npy  the rows written (float64): a fixed, seeded sample of the batch (every row when it is small)
+    se3.npy          the sampled states at those rows, [rows, 7] float64 (x y z qx qy qz qw)
+    valid.npy        the validity labels at those rows, float32 0 / 1
+    valid_count_per_4096.npy  accepted states per 4096-candidate block of the WHOLE batch, float64
+    About 17 MB at the default batch of 2^22 states, never more than 64 MB."""
+    S = valid.shape[0]
+    if S <= DUMP_SAMPLE_ROWS:
+        rows = np.arange(S, dtype=np.int64)
+    else:
+        rows = np.sort(np.random.default_rng(20240229).choice(S, DUMP_SAMPLE_ROWS, replace=False))
+    rows_t = torch.from_numpy(rows).to(valid.device)
+    nb = (S + DUMP_BLOCK - 1) // DUMP_BLOCK
+    counts = torch.zeros(nb * DUMP_BLOCK, dtype=torch.float64, device=valid.device)
+    counts[:S] = valid.to(torch.float64)
+    out = {"sample_rows": rows.astype(np.float64),
+           "se3": se3[rows_t].cpu().numpy().astype(np.float64),
+           "valid": valid[rows_t].cpu().numpy().astype(np.float32),
+           "valid_count_per_4096": counts.view(nb, DUMP_BLOCK).sum(1).cpu().numpy()}
+    assert sum(a.nbytes for a in out.values()) <= 64 << 20
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def self_launch(n_gpus, argv):
     """`python bench.py --gpus N` with no launcher around it: re-exec under torch.distributed.run, one rank per GPU
     of this node over RCCL (what the driver's `python -m torch.distributed.run --nnodes=1 --nproc-per-node N
@@ -813,6 +843,9 @@ def main():
                     help="N>1: seconds a multi-GPU stage may take before rank 0 prints the line with what it has")
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise torch.distributed and run the all-gather path even with one rank (self-test)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (a seeded sample of its states and "
+                         "labels + whole-batch accepted counts) as DIR/<name>.npy; one GPU only (see dump_outputs)")
     args = ap.parse_args()
     if args.pmc_child:
         return pmc_child(args)
@@ -820,6 +853,10 @@ def main():
     N = args.gpus
     if N < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
+    if args.dump_outputs and (N > 1 or args.force_dist):
+        raise SystemExit("--dump-outputs needs --gpus 1 without --force-dist (the exchange path keeps its states in the group)")
     if N > 1 and "WORLD_SIZE" not in os.environ:
         # no launcher: spawn the N ranks ourselves (rank 0 of the child job prints the JSON line on our stdout)
         raise SystemExit(self_launch(N, sys.argv[1:]))
@@ -1134,6 +1171,8 @@ def main():
     mat_cap = (cap if args.materialise < 0 else min(cap, args.materialise)) if do_gather else 0
     dt = timed_region(K)
     value = N * S * K / dt
+    if args.dump_outputs:   # before anything else reuses se3 / valid
+        dump_outputs(args.dump_outputs, se3, valid)
     if multi:
         wd.partial = dict(base_line, value=value, ms_per_step=dt / K * 1e3, headline_includes_exchange=bool(do_gather),
                           distributed={"world_size": world, "rccl_ranks_seen": rccl_ranks_seen, "no_exchange": no_exchange,

@@ -1,15 +1,21 @@
 #!/usr/bin/env python3
-"""Build container only: torch.save()s the state_dict of the REFERENCE network class
-(art_planner_motion_cost/.../predictor/network_light.py, imported where it lies) loaded with the seeded
-parameters of tools/convert_weights.random_params(seed) -- the file format predictor.py:20 torch.load()s
-(`self.network.load_state_dict(torch.load(modelFile))`).  Used by tests/test_motion_cost.py to exercise
-tools/convert_weights.py main() on a real torch-saved checkpoint (the repository's trained checkpoints are
-git-LFS stubs).  Usage: make_reference_state_dict.py out.pt [seed]"""
+"""Build container only: the layout of the REFERENCE network's state_dict
+(art_planner_motion_cost/.../predictor/network_light.py, imported where it lies) -- the file format
+predictor.py:20 torch.load()s (`self.network.load_state_dict(torch.load(modelFile))`).
+
+Writes tests/golden/reference_state_dict.json: every entry of network_light.network().state_dict() in the
+class's own order with its shape and dtype (and the value of the BatchNorm num_batches_tracked counters), after
+loading the seeded parameters of tools/convert_weights.random_params(0) into the class.  Data only, no reference
+source text.  tests/test_motion_cost.py rebuilds that checkpoint from the manifest and the seeded parameters, so
+tools/convert_weights.py main() is exercised on a real torch-saved checkpoint of the reference's layout (the
+repository's trained checkpoints are git-LFS stubs).  Usage: make_reference_state_dict.py [out.json]"""
+import json
 import os
 import sys
 
 import torch
 
+sys.dont_write_bytecode = True  # the reference tree is read-only: no __pycache__ next to its sources
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -33,5 +39,20 @@ def build_state_dict(seed=0):
     return net.state_dict()
 
 
+def manifest(sd):
+    out = []
+    for k, v in sd.items():
+        e = {"key": k, "shape": list(v.shape), "dtype": str(v.dtype).replace("torch.", "")}
+        if k.endswith("num_batches_tracked"):
+            e["value"] = int(v.item())
+        out.append(e)
+    return {"what": "network_light.network().state_dict() of the reference, seeded parameters random_params(0) "
+                    "loaded: entries in the class's order (tests/golden/make_reference_state_dict.py)",
+            "entries": out}
+
+
 if __name__ == "__main__":
-    torch.save(build_state_dict(int(sys.argv[2]) if len(sys.argv) > 2 else 0), sys.argv[1])
+    path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(HERE, "reference_state_dict.json")
+    with open(path, "w") as f:
+        json.dump(manifest(build_state_dict(0)), f, indent=1)
+        f.write("\n")

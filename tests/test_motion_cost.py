@@ -121,14 +121,27 @@ def test_convert_weights_main_on_a_torch_saved_state_dict(tmp_path, monkeypatch)
     _check_blob_from_checkpoint(ck, tmp_path, monkeypatch)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/art_planner_motion_cost"),
-                    reason="the reference network class only exists in the build container")
 def test_convert_weights_main_on_the_reference_networks_checkpoint(tmp_path, monkeypatch):
-    """The same through the REFERENCE class: network_light.network().state_dict() torch.save()d by
-    tests/golden/make_reference_state_dict.py (the format predictor.py:20 loads)."""
-    import subprocess
+    """The same in the REFERENCE class's layout: the entries of network_light.network().state_dict() in the class's
+    order, shapes, dtypes and num_batches_tracked values, as tests/golden/make_reference_state_dict.py recorded them
+    (tests/golden/reference_state_dict.json), filled with the seeded parameters and torch.save()d (the format
+    predictor.py:20 loads)."""
+    import torch
+    p = mo.random_params(0)
+    entries = json.load(open(os.path.join(common.GOLDEN_DIR, "reference_state_dict.json")))["entries"]
+    sd = {}
+    for e in entries:
+        k = e["key"]
+        if k.endswith("num_batches_tracked"):
+            t = torch.tensor(e["value"], dtype=getattr(torch, e["dtype"]))
+        else:
+            t = torch.from_numpy(p[k].copy()).to(getattr(torch, e["dtype"]))
+        assert list(t.shape) == e["shape"], (k, list(t.shape), e["shape"])
+        sd[k] = t
+    # every parameter of the blob is in the reference's key set, and nothing else but the BatchNorm counters is
+    assert sorted(k for k in sd if not k.endswith("num_batches_tracked")) == sorted(p), "key sets differ"
     ck = tmp_path / "ref_model.pt"
-    subprocess.check_call([sys.executable, os.path.join(common.GOLDEN_DIR, "make_reference_state_dict.py"), str(ck)])
+    torch.save(sd, ck)
     _check_blob_from_checkpoint(ck, tmp_path, monkeypatch)
 
 

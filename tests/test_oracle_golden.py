@@ -143,14 +143,16 @@ def test_sampler_oracle_properties(big_map):
     assert np.abs(q - qe).max() < 0.03
 
 
-@pytest.mark.skipif(not O.have_ref(), reason="oracle/_ref (real ODE) only exists in the build container")
-def test_oracle_vs_real_ode_random(big_map):
-    rng = np.random.default_rng(7)
+def test_oracle_vs_real_ode_random():
+    """20 000 torso and 60 000 foot dPoses on the C2 map (tests/golden/ode_c2.npz): the oracle's hits are the real
+    ODE's, stored by tests/golden/make_golden_ode_c2.py -- and, where oracle/_ref was built, the live ODE's too."""
+    gm, cases = golden_io.load_ode_c2()
     rob = O.robot("yaml")
-    for side, layer, zoff, n in [(rob.torso, "elevation", (0.42, 0.12), 20000),
-                                 (rob.foot, "elevation_masked", (0.0, 0.08), 60000)]:
-        P = common.random_dposes(big_map, n, rng, zoff, tilt=0.3)
-        of = O.OracleField(big_map[layer], big_map.len_x, big_map.len_y)
-        ref = O.RefChecker(side, big_map[layer], big_map.len_x, big_map.len_y)
-        assert np.array_equal(of.check_boxes(side, P), ref.check(P))
-        ref.close()
+    for part, c in cases.items():
+        side, layer, P = getattr(rob, part), c["layer"], c["poses"]
+        hit = O.OracleField(gm[layer], gm.len_x, gm.len_y, gm.pos_x, gm.pos_y).check_boxes(side, P)
+        assert np.array_equal(hit, c["hit"]), f"{part}: {int((hit != c['hit']).sum())} label mismatches"
+        if O.have_ref():
+            ref = O.RefChecker(side, gm[layer], gm.len_x, gm.len_y, gm.pos_x, gm.pos_y)
+            assert np.array_equal(ref.check(P), c["hit"]), f"{part}: the live ODE disagrees with the stored hits"
+            ref.close()
