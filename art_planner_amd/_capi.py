@@ -39,6 +39,9 @@ SYMBOLS = [
     "artp_inpaint_layer", "artp_cost_set_hole_filling", "artp_cost_set_external_query",
     "artp_cost_blob_bytes", "artp_cost_load_weights", "artp_cost_update_map_layer",
     "artp_cost_update_map", "artp_cost_query", "artp_cost_query_dev", "artp_cost_get_features", "artp_cost_debug_query_cells", "artp_cost_fc_path", "artp_set_r3_extent", "artp_telea_inpaint_u8",
+    "artp_tree_params_defaults", "artp_tree_create", "artp_tree_grow", "artp_tree_solve", "artp_tree_stats",
+    "artp_tree_export", "artp_tree_export_checked", "artp_tree_simplify_path", "artp_tree_stage_times",
+    "artp_tree_destroy",
 ]
 
 
@@ -90,6 +93,14 @@ class RoadmapParams(C.Structure):  # artp_roadmap_params (include/artp_c.h)
                 ("max_n_edges", C.c_uint32), ("recompute_density_after_n_samples", C.c_uint32),
                 ("max_sample_time", C.c_double), ("density_map", C.c_void_p), ("density_params", C.c_void_p),
                 ("construction", C.c_int32), ("max_query_edge_length", C.c_double)]
+
+
+class TreeParams(C.Structure):  # artp_tree_params (include/artp_c.h)
+    _fields_ = [("seed", C.c_uint64), ("first_index", C.c_uint64), ("variant", C.c_int32), ("objective", C.c_int32),
+                ("max_lon_vel", C.c_double), ("max_lat_vel", C.c_double), ("max_ang_vel", C.c_double),
+                ("batch", C.c_uint32), ("max_vertices", C.c_uint32), ("max_batches", C.c_uint32),
+                ("plan_time", C.c_double), ("range", C.c_double), ("rewire_factor", C.c_double),
+                ("profile", C.c_int32)]
 
 
 VARIANTS_LIB_PATH = os.path.join(_HERE, "csrc", "libartp_variants.so")   # make -C art_planner_amd/csrc variants
@@ -213,6 +224,18 @@ def _load_path(LIB_PATH):
     L.artp_preprocessed_reweight_dev.argtypes = [vp, vp, C.POINTER(PreprocessParams), vp, sz, i32]
     L.artp_roadmap_destroy.argtypes = [vp]
     L.artp_roadmap_destroy.restype = None
+    L.artp_tree_params_defaults.argtypes = [C.POINTER(TreeParams)]
+    L.artp_tree_params_defaults.restype = None
+    L.artp_tree_create.argtypes = [vp, C.POINTER(TreeParams), vp, vp, C.POINTER(vp)]
+    L.artp_tree_grow.argtypes = [vp, C.c_uint64, vp]
+    L.artp_tree_solve.argtypes = [vp, vp, sz, C.POINTER(sz), C.POINTER(dbl)]
+    L.artp_tree_stats.argtypes = [vp, C.POINTER(u64 * 8)]
+    L.artp_tree_export.argtypes = [vp] + [vp] * 6
+    L.artp_tree_export_checked.argtypes = [vp, vp, vp, vp, vp, sz, C.POINTER(sz)]
+    L.artp_tree_simplify_path.argtypes = [vp, vp, sz, vp, C.POINTER(sz), C.POINTER(dbl)]
+    L.artp_tree_stage_times.argtypes = [vp, C.POINTER(dbl * 10)]
+    L.artp_tree_destroy.argtypes = [vp]
+    L.artp_tree_destroy.restype = None
     for name in ("artp_preprocess_params_defaults", "artp_preprocess_params_yaml"):
         getattr(L, name).argtypes = [C.POINTER(PreprocessParams)]
         getattr(L, name).restype = None
@@ -245,7 +268,8 @@ def _load_path(LIB_PATH):
         if fn.restype is C.c_int and name not in ("artp_destroy", "artp_cost_blob_bytes", "artp_roadmap_destroy",
                                                   "artp_roadmap_params_defaults", "artp_preprocess_params_defaults",
                                                   "artp_preprocess_params_yaml", "artp_preprocessed_destroy",
-                                                  "artp_group_destroy"):
+                                                  "artp_group_destroy", "artp_tree_params_defaults",
+                                                  "artp_tree_destroy"):
             fn.restype = C.c_int
     return L
 

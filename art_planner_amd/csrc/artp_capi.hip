@@ -3452,6 +3452,7 @@ int artp_cost_get_features(artp_ctx* c, float* out, int* fh, int* fw) {
 }  // extern "C"
 
 #include "roadmap.h"
+#include "tree.h"
 #include "preprocess.h"
 #include "group.h"
 

@@ -1867,10 +1867,12 @@ int artp_roadmap_set_query(artp_roadmap* rm, const double* start7, const double*
 // (i, j) of path states is tried as a shortcut in one batch -- the 0.5 m interpolation rule, the discrete
 // motion validator and the objective's cost -- and the cheapest chain of valid shortcuts from the first to the
 // last state is taken (a shortest path in a DAG).  Never worse than the input path under the objective.
-int artp_roadmap_simplify_path(artp_roadmap* rm, const double* path_se3, size_t n, double* out_se3, size_t* n_out,
-                               double* cost) {
-  if (!rm || !path_se3 || !out_se3 || !n_out || n < 1) return ARTP_ERR_INVALID_ARG;
-  artp_ctx* c = rm->ctx;
+// The core takes the objective's parameters only: the tree planners share it (artp_tree_simplify_path).
+}  // extern "C"
+namespace {
+int roadmap_simplify_path_impl(artp_ctx* c, const artp_roadmap_params* prm, const double* path_se3, size_t n,
+                               double* out_se3, size_t* n_out, double* cost) {
+  if (!c || !path_se3 || !out_se3 || !n_out || n < 1) return ARTP_ERR_INVALID_ARG;
   if (n <= 2) {
     std::memcpy(out_se3, path_se3, n * 7 * sizeof(double));
     *n_out = n;
@@ -1889,9 +1891,9 @@ int artp_roadmap_simplify_path(artp_roadmap* rm, const double* path_se3, size_t 
   if (ne) {
     // shortcut candidates are path segments: the learned objective prices them the way motionCost does
     // (max_query_edge_length, motion_cost_objective.cpp:41-42); the 0.5 m rule still decides their validity
-    const double mq = rm->params.max_query_edge_length > 0.0 ? rm->params.max_query_edge_length : 0.5;
-    int rc = roadmap_eval_edges_host(c, &rm->params, verts, eu.data(), ev.data(), ne, ok1.data(), ni.data(), ec.data(), false,
-                                     nullptr, rm->params.objective == 2 ? mq : 0.0);
+    const double mq = prm->max_query_edge_length > 0.0 ? prm->max_query_edge_length : 0.5;
+    int rc = roadmap_eval_edges_host(c, prm, verts, eu.data(), ev.data(), ne, ok1.data(), ni.data(), ec.data(), false,
+                                     nullptr, prm->objective == 2 ? mq : 0.0);
     if (rc != ARTP_OK) return rc;
     std::vector<double> s1(ne * 7), s2(ne * 7);
     for (size_t e = 0; e < ne; ++e) {
@@ -1928,6 +1930,14 @@ int artp_roadmap_simplify_path(artp_roadmap* rm, const double* path_se3, size_t 
   *n_out = keep.size();
   if (cost) *cost = best[n - 1];
   return ARTP_OK;
+}
+}  // namespace
+extern "C" {
+
+int artp_roadmap_simplify_path(artp_roadmap* rm, const double* path_se3, size_t n, double* out_se3, size_t* n_out,
+                               double* cost) {
+  if (!rm) return ARTP_ERR_INVALID_ARG;
+  return roadmap_simplify_path_impl(rm->ctx, &rm->params, path_se3, n, out_se3, n_out, cost);
 }
 
 int artp_roadmap_stats(const artp_roadmap* rm, uint64_t out[8]) {

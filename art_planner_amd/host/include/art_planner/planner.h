@@ -28,6 +28,7 @@
 #include "art_planner/params.h"
 #include "art_planner/planner_status.h"
 #include "art_planner/planners/batch_prm.h"
+#include "art_planner/planners/batch_tree.h"
 
 // With BOTH real libraries available the class also carries the reference's EXACT public signatures and the protected
 // members a subclass like PlannerRos reaches into (planner.h:41-70, planner_ros.h:24):
@@ -42,6 +43,7 @@
 #include <ompl/base/ScopedState.h>
 #include <ompl/geometric/PathGeometric.h>
 #include <ompl/geometric/SimpleSetup.h>
+#include "art_planner/planners/batch_tree_planner.h"
 #include "art_planner/planners/lazy_prm_star_min_update.h"
 #include "art_planner/planners/prm_motion_cost.h"
 #include "art_planner/sampler.h"
@@ -83,7 +85,7 @@ class Planner {
   // checker, the batched motion validator (in place of OMPL's DiscreteMotionValidator) and the sampler allocator
   explicit Planner(const ParamsConstPtr& params = std::make_shared<const Params>(), int device = 0)
       : params_(params), gpu_(std::make_shared<GpuContext>(params, device)),
-        prm_(std::make_shared<BatchPRM>(params, gpu_)), sampler_allocator_(params, gpu_) {
+        prm_(std::make_shared<BatchPRM>(params, gpu_)), tree_(makeTree(params, gpu_)), sampler_allocator_(params, gpu_) {
     rb_->prm = prm_;
     rb_->params = params_;
     space_ = std::make_shared<StateSpace>();
@@ -92,8 +94,8 @@ class Planner {
     // planner.cpp:90-117: the planner by name, set as ss_'s planner, its maintainer.  The PRM planners are the shells over
     // the batched roadmap (planners/*.h).  "lazy_prm_star" (the reference: OMPL's own og::LazyPRMstar, no maintainer,
     // :98-99) is SUBSTITUTED by the LazyPRMStarMinUpdate shell without a maintainer -- the same LazyPRM* graph and lazy
-    // edge checks, no min-update upkeep.  The tree planners of the reference (rrt_star, inf_rrt_star, rrt_sharp: OMPL's own,
-    // one isValid per state) have no batched counterpart and THROW here like an unknown name.
+    // edge checks, no min-update upkeep.  The tree planners of the reference (rrt_star, inf_rrt_star, rrt_sharp: OMPL's
+    // RRTstar / InformedRRTstar / RRTsharp) are the BatchTreePlanner shell over the batch-synchronous tree (artp_tree_*).
     ob::PlannerPtr planner;
     if (params_->planner.name == "lazy_prm_star_min_update" || params_->planner.name == "lazy_prm_star") {
       auto p = std::make_shared<LazyPRMStarMinUpdate>(si);
@@ -106,6 +108,10 @@ class Planner {
     } else if (params_->planner.name == "prm_motion_cost") {
       auto p = std::make_shared<PRMMotionCost>(si);
       p->bindRoadmap(rb_);
+      planner = p;
+    } else if (tree_) {
+      auto p = std::make_shared<BatchTreePlanner>(si, params_->planner.name);
+      p->bindTree(tree_, params_);
       planner = p;
     } else {
       throw std::runtime_error("Unknown planner requested: " + params_->planner.name);
@@ -121,7 +127,7 @@ class Planner {
 #else
   explicit Planner(const ParamsConstPtr& params = std::make_shared<const Params>(), int device = 0)
       : params_(params), gpu_(std::make_shared<GpuContext>(params, device)),
-        prm_(std::make_shared<BatchPRM>(params, gpu_)) {
+        prm_(std::make_shared<BatchPRM>(params, gpu_)), tree_(makeTree(params, gpu_)) {
     rb_->prm = prm_;
     rb_->params = params_;
   }
@@ -328,6 +334,7 @@ class Planner {
   void setSeed(uint64_t seed) {
     seed_ = seed;
     prm_->setSeed(seed);
+    if (tree_) tree_->setSeed(seed);
   }
 
   // Build the roadmap in the reference planners' own insertion order instead of the batched front end:
@@ -365,6 +372,15 @@ class Planner {
     const auto& sg = params_->planner.start_goal_search;
     if (!searchValid(start_flat, sg.start_radius, sg.n_iter, 0x5741u, &start_valid)) return PlannerStatus::INVALID_START;
     if (!searchValid(goal_clipped, sg.goal_radius, sg.n_iter, 0x474fu, &goal_valid)) return PlannerStatus::INVALID_GOAL;
+    if (tree_) {  // rrt_star / inf_rrt_star / rrt_sharp: a fresh tree per call, grown for plan_time
+      try {
+        solved_ = tree_->plan(start_valid, goal_valid, params_->planner.plan_time, &path_, &cost_);
+      } catch (const std::exception& e) {
+        std::cout << e.what() << std::endl;
+        solved_ = false;
+      }
+      return solved_ ? PlannerStatus::SOLVED : PlannerStatus::NOT_SOLVED;
+    }
     try {
       if (rb_->built) {
         prm_->setQuery(start_valid, goal_valid);  // clearQuery + new start / goal on the kept graph (:241-242)
@@ -398,7 +414,10 @@ class Planner {
     Path simple = path_;
     double cost_simple = cost_;
     try {
-      prm_->simplify(&simple, &cost_simple);
+      if (tree_)
+        tree_->simplify(&simple, &cost_simple);
+      else
+        prm_->simplify(&simple, &cost_simple);
     } catch (const MotionCostCallFailed&) {
       throw;   // not ours to absorb (planner.cpp:247 catches ompl::Exception only)
     } catch (const std::exception&) {
@@ -419,11 +438,14 @@ class Planner {
   double getSolutionCost() const { return cost_; }
   const GpuContextPtr& gpu() const { return gpu_; }
   const std::shared_ptr<BatchPRM>& roadmap() const { return prm_; }
+  // the tree of the tree planners' last plan() (null for the roadmap planners)
+  const std::shared_ptr<BatchTree>& tree() const { return tree_; }
 
  protected:
   ParamsConstPtr params_;
   GpuContextPtr gpu_;
   std::shared_ptr<BatchPRM> prm_;
+  std::shared_ptr<BatchTree> tree_;   // rrt_star, inf_rrt_star, rrt_sharp only
   std::shared_ptr<RoadmapHandle> rb_{std::make_shared<RoadmapHandle>()};   // prm_ + "sampleGraph has run", shared with ss_'s planner
   std::shared_ptr<Map> map_;
   mutable std::mutex map_mutex_;
@@ -439,6 +461,11 @@ class Planner {
 #endif
 
  private:
+  static std::shared_ptr<BatchTree> makeTree(const ParamsConstPtr& params, const GpuContextPtr& gpu) {
+    const int variant = BatchTree::variantOf(params->planner.name);
+    return variant < 0 ? nullptr : std::make_shared<BatchTree>(params, gpu, variant);
+  }
+
   double clamp(double v, int axis) const { return v < low_[axis] ? low_[axis] : (v > high_[axis] ? high_[axis] : v); }
 
   // Map::get3DPoseFrom2D (map.cpp:77-90): cell of the position (same arithmetic as the sampler's

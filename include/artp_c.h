@@ -456,6 +456,62 @@ int artp_roadmap_set_density_map(artp_roadmap* rm, struct artp_preprocessed* pp,
                                  const struct artp_preprocess_params* params);
 void artp_roadmap_destroy(artp_roadmap* rm);
 
+/* ---- tree planners: rrt_star, inf_rrt_star, rrt_sharp (art_planner/src/planner.cpp:92-105) ---------------------------
+ * OMPL's RRTstar::solve (and InformedRRTstar / RRTsharp) in batch-synchronous form: every batch of `batch` samples is
+ * steered, checked, connected and rewired as ONE device batch per stage (DESIGN.md "Tree planners").  The tree's vertex 0
+ * is the start; while the goal is not a vertex, slot 0 of each batch is the goal state itself (GoalState's threshold is
+ * machine epsilon: it is only reached by steering onto it).  Objectives: PathLengthObjective only (the reference's
+ * getObjective, planner.cpp:27-35, never gives the tree planners the learned cost).  Needs both height layers, the
+ * sampler layers and artp_set_z_bounds.  The tree is a pure function of the parameters (bit for bit). */
+typedef struct artp_tree artp_tree;
+typedef struct artp_tree_params {
+  uint64_t seed, first_index;  /* sample stream: slot i of batch b is index first_index + b * batch + i */
+  int32_t variant;             /* 0 = rrt_star, 1 = inf_rrt_star, 2 = rrt_sharp */
+  int32_t objective;           /* 0 = PathLengthObjective::motionCostHeuristic (Euclidean / max_lon_vel),
+                                  1 = directional time cost (use_directional_cost, params.h:70); 2 is refused */
+  double max_lon_vel, max_lat_vel, max_ang_vel; /* params.h:71-73 */
+  uint32_t batch;              /* samples per batch (1 .. 65536; default 1024) */
+  uint32_t max_vertices;       /* vertex capacity of the tree (default 100000) */
+  uint32_t max_batches;        /* 0 = no limit */
+  double plan_time;            /* seconds of artp_tree_grow; 0 = no time budget */
+  double range;                /* steering distance; 0 = OMPL's 0.2 x maxExtent (R^3 bounds of planner.cpp:146-156 + pi/2) */
+  double rewire_factor;        /* RRTstar's rewireFactor_ (1.1): k = ceil(rewire_factor (e + e/6) ln (n + 1)) <= 64 */
+  int32_t profile;             /* != 0: per-stage device times for artp_tree_stage_times (one stream sync per batch) */
+} artp_tree_params;
+void artp_tree_params_defaults(artp_tree_params* p);
+/* ARTP_ERR_INVALID_ARG (artp_last_error says which) when start or goal is not a valid state or a parameter is out of
+ * range (objective 2 included).  Creating a tree draws no samples. */
+int artp_tree_create(artp_ctx* ctx, const artp_tree_params* params, const double* start_se3, const double* goal_se3,
+                     artp_tree** out);
+/* Grows by up to n_batches batches (0 = no count limit), stopping early at max_vertices, max_batches or plan_time seconds
+ * of this call, whichever comes first (at least one of n_batches, max_batches, plan_time must be set).
+ * out (may be NULL): [0] batches run by this call, [1] vertices now. */
+int artp_tree_grow(artp_tree* tree, uint64_t n_batches, uint64_t out[2]);
+/* The root -> goal chain (n_path states) at cost(goal); *n_path = 0 and *cost = +inf while the goal is not a vertex.
+ * Capacity as artp_roadmap_solve: ARTP_ERR_CAPACITY with *n_path = the states needed when cap_states is too small. */
+int artp_tree_solve(const artp_tree* tree, double* path_se3, size_t cap_states, size_t* n_path, double* cost);
+/* out: [0] vertices, [1] batches, [2] samples drawn, [3] motions checked, [4] rewires, [5] pruned vertices,
+ * [6] goal vertex id (~0 = none yet), [7] batch of the first solution (~0 = none yet). */
+int artp_tree_stats(const artp_tree* tree, uint64_t out[8]);
+/* Any pointer may be NULL.  verts: n x 7; parent (vertex 0: 0xffffffff), cost-to-come, cost of the edge from the parent,
+ * batch the vertex was born in, pruned flag: n each.  cost[v] is the left fold from the root of the edge costs along the
+ * parent chain: ((0 + w1) + w2) + ... */
+int artp_tree_export(const artp_tree* tree, double* verts, uint32_t* parent, double* cost, double* edge_cost,
+                     uint32_t* born_batch, uint8_t* pruned);
+/* Every motion checkMotion(u, v) checked since creation, in check order: u a vertex, v the vertex id of the new state
+ * (0xffffffff when the state did not become one), the verdict, the batch.  *n = the number of motions; the arrays
+ * (any may be NULL) take the first cap of them, ARTP_ERR_CAPACITY when they do not hold all. */
+int artp_tree_export_checked(const artp_tree* tree, uint32_t* u, uint32_t* v, uint8_t* valid, uint32_t* batch, size_t cap,
+                             size_t* n);
+/* Planner::getSolutionPath(true): artp_roadmap_simplify_path's all-pairs shortcut search with the tree's objective */
+int artp_tree_simplify_path(artp_tree* tree, const double* path_se3, size_t n, double* out_se3, size_t* n_out,
+                            double* cost);
+/* Device microseconds per stage summed over the batches grown with params.profile != 0: [0] sample, [1] nearest,
+ * [2] steer + survivor count, [3] first motion + survivor count, [4] near set, [5] near motions, [6] parent choice,
+ * [7] rewire, [8] rrt_sharp shortest paths, [9] cost-to-come (+ pruning). */
+int artp_tree_stage_times(const artp_tree* tree, double us[10]);
+void artp_tree_destroy(artp_tree* tree);
+
 /* ---- "next" row N2: the per-map preprocessing chain on the device -----------------------
  * Replaces processors::Basic (art_planner/src/map/processors/basic.cpp:42-143: traversability threshold,
  * safety morphology, elevation_masked, sample filter), estimateNormals (art_planner/src/utils.cpp:213-326)
