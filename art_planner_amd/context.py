@@ -393,12 +393,20 @@ class Context:
         self._chk(self.L.artp_cost_query_dev(self.h, edges_t.data_ptr(), edges_t.shape[0], cost_t.data_ptr()),
                   "artp_cost_query_dev")
 
+    def cost_feature_channels(self):
+        """48 (the light network, blob version 1) or 64 (the full-width network, version 2)."""
+        ch = C.c_int(0)
+        self._chk(self.L.artp_cost_feature_channels(self.h, C.byref(ch)), "artp_cost_feature_channels")
+        return int(ch.value)
+
     def cost_features(self):
+        """The feature map as float32 [F][F][channels] (channels = cost_feature_channels())."""
+        ch = self.cost_feature_channels()
         fh, fw = C.c_int(0), C.c_int(0)
-        self._chk(self.L.artp_cost_get_features(self.h, None, C.byref(fh), C.byref(fw)), "artp_cost_get_features")
-        out = np.empty((fh.value, fw.value, 48), np.float32)
-        self._chk(self.L.artp_cost_get_features(self.h, out.ctypes.data, C.byref(fh), C.byref(fw)),
-                  "artp_cost_get_features")
+        self._chk(self.L.artp_cost_get_features_c(self.h, None, ch, C.byref(fh), C.byref(fw)), "artp_cost_get_features_c")
+        out = np.empty((fh.value, fw.value, ch), np.float32)
+        self._chk(self.L.artp_cost_get_features_c(self.h, out.ctypes.data, ch, C.byref(fh), C.byref(fw)),
+                  "artp_cost_get_features_c")
         return out
 
     def compact_valid_indices_dev(self, valid_t, idx_t, count_t):

@@ -152,6 +152,7 @@ struct artp_ctx {
   int cur_lane = 0;
   // motion cost (R8/R9)
   bool have_weights = false;
+  int cost_net = 0;                    // blob version of the loaded network: 1 light (network_light.py), 2 full width (network.py)
   half8* d_convw[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // [4]: the 15 x 15 layer's B fragments, per-row packing
   float* d_convb[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   float* d_c12 = nullptr;              // conv1 o conv2 composed: [24][25] + [24] (conv12_pool_kernel)
@@ -169,7 +170,7 @@ struct artp_ctx {
   float fc_selfcheck_err = 0.f;        // largest |MFMA - fp32| of the probe batch
   half_t* d_act[2] = {nullptr, nullptr};
   size_t act_cap = 0;
-  half_t* d_feat = nullptr;            // NHWC [Fh][Fw][48]
+  half_t* d_feat = nullptr;            // NHWC [Fh][Fw][48 | 64] (the loaded network's feature channels)
   size_t feat_cap = 0;
   float* d_map_f32 = nullptr;
   size_t map_cap = 0;
@@ -2659,11 +2660,28 @@ namespace {
 struct ConvSpec { int cout, cin, kh, kw, nt; };
 // layers 2..6 of network.CNNpart (network_light.py:23-36)
 const ConvSpec kConv[5] = {{24, 24, 3, 3, 2}, {48, 24, 3, 3, 3}, {48, 48, 3, 3, 3}, {48, 48, 3, 3, 3}, {48, 48, 15, 15, 3}};
+// the same layers of the full-width network (network.py:23-36)
+const ConvSpec kConvFull[5] = {{32, 32, 3, 3, 2}, {64, 32, 3, 3, 4}, {64, 64, 3, 3, 4}, {64, 64, 3, 3, 4}, {64, 64, 15, 15, 4}};
 
-size_t cost_blob_floats() {
-  size_t n = 24 * 9 + 24;
-  for (const ConvSpec& s : kConv) n += (size_t)s.cout * s.cin * s.kh * s.kw + s.cout;
-  return n + FcWeights::TOTAL;
+// what differs between the two networks the blob versions describe
+struct CostNet {
+  int version;
+  int c1, c;        // conv1 / conv2 channels, feature channels (conv3 .. the 15 x 15 layer)
+  const ConvSpec* conv;
+  int fc_floats;    // FcWeights::TOTAL / FcWeightsFull::TOTAL
+  int fc_mfma_bytes;
+};
+const CostNet kNetLight = {1, 24, 48, kConv, FcWeights::TOTAL, FcMfma::TOTAL};
+const CostNet kNetFull = {2, 32, 64, kConvFull, FcWeightsFull::TOTAL, FcMfmaFull::TOTAL};
+const CostNet* cost_net_of_version(int v) { return v == 1 ? &kNetLight : v == 2 ? &kNetFull : nullptr; }
+
+size_t cost_blob_floats(const CostNet& net = kNetLight) {
+  size_t n = (size_t)net.c1 * 9 + net.c1;
+  for (int l = 0; l < 5; ++l) {
+    const ConvSpec& s = net.conv[l];
+    n += (size_t)s.cout * s.cin * s.kh * s.kw + s.cout;
+  }
+  return n + net.fc_floats;
 }
 
 inline uint16_t f32_to_f16_bits(float f) {  // round-to-nearest-even, host side
@@ -2758,6 +2776,60 @@ inline void fc_mfma_pack(const float* w, std::vector<unsigned char>* out) {
   ob[2] = w[FcWeights::O3_B];
 }
 
+// The full-width network's FC part (FcWeightsFull) in the fragment order fc_cost_mfma_full_kernel reads: tar0 composed into
+// out0 in double (k < 64 the map features, 64 .. 73 the ten geometric inputs, 74 the bias), hi / lo half-float pairs.
+inline void fc_mfma_pack_full(const float* w, std::vector<unsigned char>* out) {
+  using W = FcWeightsFull;
+  out->assign(FcMfmaFull::TOTAL, 0);
+  auto put16 = [&](size_t byte_off, double v) {
+    const _Float16 hi = (_Float16)(float)v;
+    const _Float16 lo = (_Float16)(float)(v - (double)hi);
+    std::memcpy(out->data() + byte_off, &hi, 2);
+    std::memcpy(out->data() + byte_off + 1024, &lo, 2);   // the lo fragment follows its hi fragment
+  };
+  std::vector<double> w0c((size_t)64 * 96, 0.0);   // [hidden unit][k]
+  for (int o = 0; o < 64; ++o) {
+    for (int k = 0; k < 64; ++k) w0c[o * 96 + k] = w[W::OUT0_W + o * 80 + k];
+    double bias = w[W::OUT0_B + o];
+    for (int m = 0; m < 16; ++m) {
+      const double a = w[W::OUT0_W + o * 80 + 64 + m];
+      for (int k = 0; k < 10; ++k) w0c[o * 96 + 64 + k] += a * (double)w[W::TAR0_W + m * 10 + k];
+      bias += a * (double)w[W::TAR0_B + m];
+    }
+    w0c[o * 96 + 74] = bias;
+  }
+  auto hidden_of_row = [](int r) {  // accumulator row 16 t + 4 g + i of the first GEMM -> hidden unit (see the kernel's header)
+    const int t = r / 16, g = (r % 16) / 4, i = r % 4;
+    return 32 * (t / 2) + 8 * g + 4 * (t % 2) + i;
+  };
+  for (int s = 0; s < 3; ++s)
+    for (int t = 0; t < 4; ++t)
+      for (int l = 0; l < 64; ++l)
+        for (int j = 0; j < 8; ++j)
+          put16(FcMfmaFull::G1 + (size_t)((s * 4 + t) * 2) * 1024 + l * 16 + j * 2,
+                w0c[(size_t)hidden_of_row(16 * t + (l & 15)) * 96 + 32 * s + 8 * (l >> 4) + j]);
+  // head unit u = 32 h + m: head h (out1_conv1 / 2 / 3), its unit m; k = hidden unit
+  const int hw[3] = {W::H1_W, W::H2_W, W::H3_W}, hb[3] = {W::H1_B, W::H2_B, W::H3_B}, ow[3] = {W::O1_W, W::O2_W, W::O3_W};
+  for (int s = 0; s < 2; ++s)
+    for (int t = 0; t < 6; ++t)
+      for (int l = 0; l < 64; ++l) {
+        const int u = 16 * t + (l & 15);
+        for (int j = 0; j < 8; ++j)
+          put16(FcMfmaFull::G2 + (size_t)((s * 6 + t) * 2) * 1024 + l * 16 + j * 2,
+                w[hw[u / 32] + (u % 32) * 64 + 32 * s + 8 * (l >> 4) + j]);
+      }
+  float* bias2 = reinterpret_cast<float*>(out->data() + FcMfmaFull::BIAS2);
+  float* outw = reinterpret_cast<float*>(out->data() + FcMfmaFull::OUT);
+  float* ob = reinterpret_cast<float*>(out->data() + FcMfmaFull::OB);
+  for (int u = 0; u < 96; ++u) {
+    bias2[u] = w[hb[u / 32] + u % 32];
+    outw[u] = w[ow[u / 32] + u % 32];
+  }
+  ob[0] = w[W::O1_B];
+  ob[1] = w[W::O2_B];
+  ob[2] = w[W::O3_B];
+}
+
 }  // namespace
 
 // A 512-edge probe batch on a 6 x 6 pseudo-random feature map through fc_cost_mfma_kernel and fc_cost_kernel (same
@@ -2765,7 +2837,8 @@ inline void fc_mfma_pack(const float* w, std::vector<unsigned char>* out) {
 // split's own error (a few 1e-6 in practice; 1e-4 absolute + 1e-4 relative allowed).
 static int cost_fc_selfcheck(artp_ctx* c) {
   constexpr int F = 6, B = 512;
-  std::vector<uint16_t> feat((size_t)F * F * 48);
+  const bool full = c->cost_net == 2;   // the full-width network's pair: fc_cost_mfma_full_kernel, fc_cost_kernel<FcWeightsFull>
+  std::vector<uint16_t> feat((size_t)F * F * (full ? 64 : 48));
   std::vector<float> edges((size_t)B * 6);
   uint32_t s = 0x9E3779B9u;
   auto rnd = [&]() {
@@ -2797,10 +2870,16 @@ static int cost_fc_selfcheck(artp_ctx* c) {
   hipError_t e1 = hipMemcpyAsync(d_feat, feat.data(), fb, hipMemcpyHostToDevice, c->stream);
   if (e1 == hipSuccess) e1 = hipMemcpyAsync(d_edges, edges.data(), eb, hipMemcpyHostToDevice, c->stream);
   std::vector<float> c0((size_t)B * 3), c1((size_t)B * 3);
-  if (e1 == hipSuccess) {
+  if (e1 == hipSuccess && !full) {
     hipLaunchKernelGGL(fc_cost_mfma_kernel, dim3(2), dim3(256), 0, c->stream, (const float*)d_edges, (size_t)B, (const half_t*)d_feat, g,
                        (const char*)c->d_fc_mfma, d_c0);
-    hipLaunchKernelGGL(fc_cost_kernel, dim3((B + 255) / 256), dim3(256), 0, c->stream, (const float*)d_edges, (size_t)B,
+    hipLaunchKernelGGL(fc_cost_kernel<FcWeights>, dim3((B + 255) / 256), dim3(256), 0, c->stream, (const float*)d_edges, (size_t)B,
+                       (const half_t*)d_feat, g, (const float*)c->d_fc, d_c1);
+    e1 = hipGetLastError();
+  } else if (e1 == hipSuccess) {
+    hipLaunchKernelGGL(fc_cost_mfma_full_kernel, dim3(2), dim3(256), 0, c->stream, (const float*)d_edges, (size_t)B,
+                       (const half_t*)d_feat, g, (const char*)c->d_fc_mfma, d_c0);
+    hipLaunchKernelGGL(fc_cost_kernel<FcWeightsFull>, dim3((B + 255) / 256), dim3(256), 0, c->stream, (const float*)d_edges, (size_t)B,
                        (const half_t*)d_feat, g, (const float*)c->d_fc, d_c1);
     e1 = hipGetLastError();
   }
@@ -2830,19 +2909,33 @@ extern "C" {
 
 size_t artp_cost_blob_bytes(void) { return 8 + cost_blob_floats() * sizeof(float); }
 
+size_t artp_cost_blob_bytes_version(int version) {
+  const CostNet* net = cost_net_of_version(version);
+  return net ? 8 + cost_blob_floats(*net) * sizeof(float) : 0;
+}
+
 int artp_cost_load_weights(artp_ctx* c, const void* blob, size_t bytes) {
   if (!c || !blob) return ARTP_ERR_INVALID_ARG;
   std::lock_guard<std::recursive_mutex> lock(c->mu);
   const unsigned char* p = static_cast<const unsigned char*>(blob);
-  if (bytes != artp_cost_blob_bytes() || std::memcmp(p, "ARMC", 4) != 0 || p[4] != 1) {
+  const CostNet* netp = bytes >= 8 ? cost_net_of_version(p[4]) : nullptr;
+  if (!netp || bytes != artp_cost_blob_bytes_version(p[4]) || std::memcmp(p, "ARMC", 4) != 0) {
     c->last_error = "motion-cost blob: bad magic, version or size";
     return ARTP_ERR_INVALID_ARG;
   }
+  const CostNet& net = *netp;
   HIP_TRY(c, hipSetDevice(c->device));
+  // a switch between the networks drops the feature map (the other network's features, another channel count):
+  // queries answer ARTP_ERR_NO_MAP until the next artp_cost_update_map*
+  if (c->cost_net != net.version) {
+    c->have_features = false;
+    c->have_weights = false;
+  }
+  c->cost_net = net.version;
   const float* w = reinterpret_cast<const float*>(p + 8);
-  w += 216 + 24;  // conv1 (composed with conv2 below)
+  w += net.c1 * 9 + net.c1;  // conv1 (composed with conv2 below)
   for (int l = 0; l < 5; ++l) {
-    const ConvSpec& s = kConv[l];
+    const ConvSpec& s = net.conv[l];
     const int krow = s.kw * s.cin, ksteps = (krow + 31) / 32;
     const size_t nfrag = l == 4 ? (size_t)s.kh * ksteps * s.nt * 64 : 0;  // per-row packing: the 15 x 15 layer only
     std::vector<uint16_t> packed(nfrag * 8, 0);
@@ -2862,7 +2955,7 @@ int artp_cost_load_weights(artp_ctx* c, const void* blob, size_t bytes) {
               packed[((((size_t)kh * ksteps + ks) * s.nt + nt) * 64 + l) * 8 + j] = f32_to_f16_bits(v);
             }
 #ifdef ARTP_VARIANTS
-    if (l == 4) {
+    if (l == 4 && net.version == 1) {
       // the same layer for conv15_pair32_kernel: [kernel row -1 .. 15][k-step][k-half][channel][k-quad][8], kernel rows
       // -1 and 15 all zero (Conv15P32Cfg); element j of (channel co, quad kq) = W[co][k = 32 ks + 16 sh + 8 kq + j]
       using P32 = Conv15P32Cfg<6>;
@@ -2904,31 +2997,35 @@ int artp_cost_load_weights(artp_ctx* c, const void* blob, size_t bytes) {
   {
     // conv1 (+BN) followed by conv2 (+BN) without an activation in between (network_light.py:84-87) is one 5 x 5
     // convolution: Wc[co][a+c][b+d] += W2[co][ci][a][b] * W1[ci][c][d], bias b2[co] + sum W2[co][ci][a][b] * b1[ci]
+    // (C1 = 24 channels for the light network, 32 for the full one)
+    const int C1 = net.c1;
     const float* base = reinterpret_cast<const float*>(p + 8);
-    const float* w1 = base;            // [24][3][3]
-    const float* b1 = base + 216;      // [24]
-    const float* w2 = base + 240;      // [24][24][3][3]
-    const float* b2 = w2 + 24 * 24 * 9;
-    double wc[24][25], bc[24];
-    for (int co = 0; co < 24; ++co) {
+    const float* w1 = base;            // [C1][3][3]
+    const float* b1 = base + C1 * 9;   // [C1]
+    const float* w2 = b1 + C1;         // [C1][C1][3][3]
+    const float* b2 = w2 + C1 * C1 * 9;
+    double wc[32][25], bc[32];
+    for (int co = 0; co < C1; ++co) {
       for (int k = 0; k < 25; ++k) wc[co][k] = 0.0;
       bc[co] = b2[co];
-      for (int ci = 0; ci < 24; ++ci)
+      for (int ci = 0; ci < C1; ++ci)
         for (int a = 0; a < 3; ++a)
           for (int b = 0; b < 3; ++b) {
-            const double v2 = w2[((co * 24 + ci) * 3 + a) * 3 + b];
+            const double v2 = w2[((co * C1 + ci) * 3 + a) * 3 + b];
             bc[co] += v2 * b1[ci];
             for (int cc = 0; cc < 3; ++cc)
               for (int d = 0; d < 3; ++d) wc[co][(a + cc) * 5 + (b + d)] += v2 * (double)w1[ci * 9 + cc * 3 + d];
           }
     }
-    float h12[24 * 25 + 24];
-    for (int co = 0; co < 24; ++co) {
-      for (int k = 0; k < 25; ++k) h12[co * 25 + k] = (float)wc[co][k];
-      h12[600 + co] = (float)bc[co];
+    if (net.version == 1) {   // conv12_pool_kernel's operand (variants build; the light network only)
+      float h12[24 * 25 + 24];
+      for (int co = 0; co < 24; ++co) {
+        for (int k = 0; k < 25; ++k) h12[co * 25 + k] = (float)wc[co][k];
+        h12[600 + co] = (float)bc[co];
+      }
+      if (!c->d_c12) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_c12), sizeof(h12)));
+      HIP_TRY(c, hipMemcpy(c->d_c12, h12, sizeof(h12), hipMemcpyHostToDevice));
     }
-    if (!c->d_c12) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_c12), sizeof(h12)));
-    HIP_TRY(c, hipMemcpy(c->d_c12, h12, sizeof(h12), hipMemcpyHostToDevice));
     {
       // conv12_mfma_kernel's operand: [channel tile t][hi, lo][lane][8 half floats] + bias[32].  Lane l = (m = l & 15, g = l >> 4)
       // holds channel 16 t + m, K slots 8 g .. 8 g + 7; slot s < 30 = window row s / 6, tap s % 6 (tap 5 and slots 30, 31: 0).
@@ -2939,27 +3036,27 @@ int artp_cost_load_weights(artp_ctx* c, const void* blob, size_t bytes) {
           for (int j = 0; j < 8; ++j) {
             const int ch = 16 * t + (l & 15), sl = 8 * (l >> 4) + j;
             double v = 0.0;
-            if (ch < 24 && sl < 30 && sl % 6 < 5) v = wc[ch][(sl / 6) * 5 + sl % 6];
+            if (ch < C1 && sl < 30 && sl % 6 < 5) v = wc[ch][(sl / 6) * 5 + sl % 6];
             const _Float16 hi = (_Float16)v;
             const _Float16 lo = (_Float16)(v - (double)hi);
             std::memcpy(blob.data() + ((((size_t)t * 2 + 0) * 64 + l) * 8 + j) * 2, &hi, 2);
             std::memcpy(blob.data() + ((((size_t)t * 2 + 1) * 64 + l) * 8 + j) * 2, &lo, 2);
           }
       float b32[32] = {0};
-      for (int co = 0; co < 24; ++co) b32[co] = (float)bc[co];
+      for (int co = 0; co < C1; ++co) b32[co] = (float)bc[co];
       std::memcpy(blob.data() + (size_t)C12M_FRAG_HALFS * 2, b32, sizeof(b32));
       if (!c->d_c12m) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_c12m), blob.size()));
       HIP_TRY(c, hipMemcpy(c->d_c12m, blob.data(), blob.size(), hipMemcpyHostToDevice));
     }
     // conv3..5 for conv345_kernel: K walked in 16-byte chunks over the whole (kh, kw, cin) window; fragment
     // [ks][nt][lane][8]: lane l, element j holds B[k][n] with chunk q = 4 ks + (l >> 4), k = 8 q + j, n = 16 nt + (l & 15)
-    const float* wl = w2 + 24 * 24 * 9 + 24;
+    const float* wl = w2 + C1 * C1 * 9 + C1;
     for (int l = 0; l < 3; ++l) {
-      const ConvSpec& s = kConv[l + 1];
+      const ConvSpec& s = net.conv[l + 1];
       const int cpr = 3 * s.cin / 8, q_tot = 3 * cpr, ks_tot = (q_tot + 3) / 4;
-      std::vector<uint16_t> packed((size_t)ks_tot * 3 * 64 * 8, 0);
+      std::vector<uint16_t> packed((size_t)ks_tot * s.nt * 64 * 8, 0);
       for (int ks = 0; ks < ks_tot; ++ks)
-        for (int nt = 0; nt < 3; ++nt)
+        for (int nt = 0; nt < s.nt; ++nt)
           for (int ln = 0; ln < 64; ++ln)
             for (int j = 0; j < 8; ++j) {
               const int q = ks * 4 + (ln >> 4), co = nt * 16 + (ln & 15);
@@ -2968,7 +3065,7 @@ int artp_cost_load_weights(artp_ctx* c, const void* blob, size_t bytes) {
                 const int kh = q / cpr, i = (q % cpr) * 8 + j, kw = i / s.cin, ci = i % s.cin;
                 v = wl[(((size_t)co * s.cin + ci) * 3 + kh) * 3 + kw];
               }
-              packed[(((size_t)ks * 3 + nt) * 64 + ln) * 8 + j] = f32_to_f16_bits(v);
+              packed[(((size_t)ks * s.nt + nt) * 64 + ln) * 8 + j] = f32_to_f16_bits(v);
             }
       if (c->d_convw_chunk[l]) HIP_TRY(c, hipFree(c->d_convw_chunk[l]));
       c->d_convw_chunk[l] = nullptr;
@@ -2977,12 +3074,17 @@ int artp_cost_load_weights(artp_ctx* c, const void* blob, size_t bytes) {
       wl += (size_t)s.cout * s.cin * 9 + s.cout;
     }
   }
-  if (!c->d_fc) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_fc), FcWeights::TOTAL * sizeof(float)));
-  HIP_TRY(c, hipMemcpy(c->d_fc, w, FcWeights::TOTAL * sizeof(float), hipMemcpyHostToDevice));
+  // the FC blobs are sized for the larger (full-width) network: a switch reuses them
+  if (!c->d_fc) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_fc), FcWeightsFull::TOTAL * sizeof(float)));
+  HIP_TRY(c, hipMemcpy(c->d_fc, w, (size_t)net.fc_floats * sizeof(float), hipMemcpyHostToDevice));
   {
     std::vector<unsigned char> blob;
-    fc_mfma_pack(w, &blob);
-    if (!c->d_fc_mfma) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_fc_mfma), blob.size()));
+    if (net.version == 1)
+      fc_mfma_pack(w, &blob);
+    else
+      fc_mfma_pack_full(w, &blob);
+    static_assert(FcMfmaFull::TOTAL >= FcMfma::TOTAL, "one allocation for both");
+    if (!c->d_fc_mfma) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_fc_mfma), FcMfmaFull::TOTAL));
     HIP_TRY(c, hipMemcpy(c->d_fc_mfma, blob.data(), blob.size(), hipMemcpyHostToDevice));
     c->fc_mfma = c->fc_mfma_wanted;   // artp_cost_set_fc_path
   }
@@ -3019,7 +3121,75 @@ int artp_cost_fc_path(artp_ctx* c, int* mfma, int* selfcheck, float* max_abs_dif
   return ARTP_OK;
 }
 
+// The full-width network (network.py, blob version 2): the light path's two launches at 32 / 64 channels.
+//  (B) conv345_kernel<12, true, true, 32, 64>: conv1 o conv2 composed (5 x 5, 1 -> 32: the two 16-channel MFMA tiles the light
+//      network pads to 24 are full) + pool inside the patch phase, then conv3 32 -> 64, conv4, pool3, conv5 64 -> 64.  12 x 12
+//      tiles: 145 KB of LDS (C345Cfg; a 16 x 16 tile would need 183 KB).
+//  (C) conv_ksplit_kernel at Cin = Cout = 64: K per kernel row = 960 = 30 k-steps, four 16-channel n-tiles.  8-row tiles with
+//      eight wavefronts (144 KB of LDS, one workgroup per CU) where they are no more than the CUs, else 6-row tiles with four
+//      wavefronts (76 KB, two per CU).
+static int cost_run_cnn_full(artp_ctx* c, const float* d_map, int H, int W) {
+  constexpr int C = 64, T = 12;
+  const int h2 = H - 4, w2 = W - 4, hp = h2 / 2, wpp = w2 / 2;
+  const int h5 = hp - 8, w5 = wpp - 8, hf = h5 - 14, wf = w5 - 14;
+  if (hf < 3 || wf < 3) {
+    c->last_error = "map too small for the motion-cost feature extractor";
+    return ARTP_ERR_INVALID_ARG;
+  }
+  // conv5's output [h5][w5][64] halfs; (H-2)(W-2) * 48 bytes (the light path's sizing) is more whenever hf >= 3
+  const size_t act_bytes = std::max((size_t)(H - 2) * (W - 2) * 24 * 2, (size_t)h5 * w5 * C * 2) + 8192;
+  if (c->act_cap < act_bytes) {
+    for (int l = 0; l < 2; ++l) {
+      if (c->d_act[l]) HIP_TRY(c, hipFree(c->d_act[l]));
+      c->d_act[l] = nullptr;
+      HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_act[l]), act_bytes));
+      HIP_TRY(c, hipMemset(c->d_act[l], 0, act_bytes));
+    }
+    c->act_cap = act_bytes;
+  }
+  const size_t feat_bytes = (size_t)hf * wf * C * 2 + 256;
+  if (c->feat_cap < feat_bytes) {
+    if (c->d_feat) HIP_TRY(c, hipFree(c->d_feat));
+    c->d_feat = nullptr;
+    HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_feat), feat_bytes));
+    c->feat_cap = feat_bytes;
+  }
+  half_t* Bf = c->d_act[1];
+  hipStream_t st = c->stream;
+  {
+    auto k345 = conv345_kernel<T, true, true, 32, C>;
+    const int lds = C345Cfg<T, 32, C>::LDS_BYTES;
+    HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k345), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    const unsigned blocks = (unsigned)(((w5 + T - 1) / T) * ((h5 + T - 1) / T));
+    // `in` is not read by the fused form (F12): the patch comes from the map
+    hipLaunchKernelGGL(k345, dim3(blocks), dim3(C345_NT), lds, st, (const half_t*)Bf, hp, wpp,
+                       (const half8*)c->d_convw_chunk[0], (const float*)c->d_convb[1], (const half8*)c->d_convw_chunk[1],
+                       (const float*)c->d_convb[2], (const half8*)c->d_convw_chunk[2], (const float*)c->d_convb[3], Bf,
+                       d_map, H, W, (const half8*)c->d_c12m, (const float*)(c->d_c12m + (size_t)C12M_FRAG_HALFS * 2));
+    HIP_TRY(c, hipGetLastError());
+  }
+  {
+    auto launch = [&](auto kfn, int lds, int tr, int threads) -> int {
+      HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+      const unsigned blocks = (unsigned)(((wf + 15) / 16) * ((hf + tr - 1) / tr));
+      hipLaunchKernelGGL(kfn, dim3(blocks), dim3(threads), lds, st, (const half_t*)Bf, h5, w5, (const half8*)c->d_convw[4],
+                         (const float*)c->d_convb[4], c->d_feat);
+      return ARTP_OK;
+    };
+    const long tiles8 = (long)((wf + 15) / 16) * ((hf + 7) / 8);
+    const int rcl = tiles8 <= c->n_cus
+                        ? launch(conv_ksplit_kernel<15, 15, C, C, 4, true, 8, 8>, ConvKsplitCfg<15, 15, C, C, 4, true, 8, 8>::LDS_BYTES, 8, 512)
+                        : launch(conv_ksplit_kernel<15, 15, C, C, 4, true, 6>, ConvKsplitCfg<15, 15, C, C, 4, true, 6>::LDS_BYTES, 6, 256);
+    if (rcl != ARTP_OK) return rcl;
+  }
+  HIP_TRY(c, hipGetLastError());
+  c->feat_h = hf;
+  c->feat_w = wf;
+  return ARTP_OK;
+}
+
 static int cost_run_cnn(artp_ctx* c, const float* d_map, int H, int W) {
+  if (c->cost_net == 2) return cost_run_cnn_full(c, d_map, H, W);
   // shapes: network_light.py:84-107
   const int h1 = H - 2, w1 = W - 2, h2 = h1 - 2, w2 = w1 - 2, hp = h2 / 2, wpp = w2 / 2;
   const int h3 = hp - 2, w3 = wpp - 2, h4 = h3 - 2, w4 = w3 - 2, hq = h4 - 2, wq = w4 - 2;
@@ -3347,7 +3517,18 @@ int artp_cost_query_dev(artp_ctx* c, const float* edges, size_t b, float* cost) 
   HIP_TRY(c, hipSetDevice(c->device));
   // up to 2^16 edges (a roadmap update's query): four lanes per edge; above that a lane per edge fills the GPU.  Both
   // kernels accumulate every unit in the same order: the same bits
-  if (c->fc_mfma) {
+  if (c->cost_net == 2) {
+    // the full-width network: fc_cost_mfma_full_kernel (67 KB of LDS: two workgroups per CU), or its fp32 VALU form
+    if (c->fc_mfma) {
+      size_t blocks = (b + 255) / 256;
+      if (blocks > (size_t)c->n_cus * 2) blocks = (size_t)c->n_cus * 2;
+      hipLaunchKernelGGL(fc_cost_mfma_full_kernel, dim3((unsigned)blocks), dim3(256), 0, c->stream, edges, b,
+                         (const half_t*)c->d_feat, c->cost_geom, (const char*)c->d_fc_mfma, cost);
+    } else {
+      hipLaunchKernelGGL(fc_cost_kernel<FcWeightsFull>, dim3((unsigned)((b + 255) / 256)), dim3(256), 0, c->stream, edges, b,
+                         (const half_t*)c->d_feat, c->cost_geom, (const float*)c->d_fc, cost);
+    }
+  } else if (c->fc_mfma) {
     // the MLP as MFMA tiles (cost_kernels.h fc_cost_mfma_kernel): 64 edges per wavefront, 256 per workgroup
     size_t blocks = (b + 255) / 256;
     if (blocks > (size_t)c->n_cus * 3) blocks = (size_t)c->n_cus * 3;  // three workgroups per CU fit (50 KB of LDS each)
@@ -3357,7 +3538,7 @@ int artp_cost_query_dev(artp_ctx* c, const float* edges, size_t b, float* cost) 
     hipLaunchKernelGGL(fc_cost_split_kernel, dim3((unsigned)((b + FC_SPLIT_EDGES - 1) / FC_SPLIT_EDGES)), dim3(256), 0, c->stream,
                        edges, b, (const half_t*)c->d_feat, c->cost_geom, (const float*)c->d_fc, cost);
   else
-    hipLaunchKernelGGL(fc_cost_kernel, dim3((unsigned)((b + 255) / 256)), dim3(256), 0, c->stream, edges, b,
+    hipLaunchKernelGGL(fc_cost_kernel<FcWeights>, dim3((unsigned)((b + 255) / 256)), dim3(256), 0, c->stream, edges, b,
                        (const half_t*)c->d_feat, c->cost_geom, (const float*)c->d_fc, cost);
   HIP_TRY(c, hipGetLastError());
   return ARTP_OK;
@@ -3429,16 +3610,29 @@ int artp_cost_query(artp_ctx* c, const float* edges, size_t b, float* cost) {
   return ARTP_OK;
 }
 
-// Copy the feature map out (tests / diagnostics): NHWC fp16 -> float [F][F][48]
-int artp_cost_get_features(artp_ctx* c, float* out, int* fh, int* fw) {
+int artp_cost_feature_channels(artp_ctx* c, int* channels) {
+  if (!c || !channels) return ARTP_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> lock(c->mu);
+  if (!c->have_weights) return ARTP_ERR_NO_WEIGHTS;
+  *channels = c->cost_net == 2 ? 64 : 48;
+  return ARTP_OK;
+}
+
+// Copy the feature map out (tests / diagnostics): NHWC fp16 -> float [F][F][channels]
+int artp_cost_get_features_c(artp_ctx* c, float* out, int channels, int* fh, int* fw) {
   if (!c || !fh || !fw) return ARTP_ERR_INVALID_ARG;
   std::lock_guard<std::recursive_mutex> lock(c->mu);
+  const int nc = c->cost_net == 2 ? 64 : 48;
+  if (c->have_weights && channels != nc) {
+    c->last_error = "artp_cost_get_features: the loaded network's feature maps have " + std::to_string(nc) + " channels";
+    return ARTP_ERR_INVALID_ARG;
+  }
   if (!c->have_features) return ARTP_ERR_NO_MAP;
   *fh = c->feat_h;
   *fw = c->feat_w;
   if (!out) return ARTP_OK;
   HIP_TRY(c, hipSetDevice(c->device));
-  const size_t n = (size_t)c->feat_h * c->feat_w * 48;
+  const size_t n = (size_t)c->feat_h * c->feat_w * nc;
   std::vector<uint16_t> tmp(n);
   HIP_TRY(c, hipMemcpy(tmp.data(), c->d_feat, n * 2, hipMemcpyDeviceToHost));
   for (size_t i = 0; i < n; ++i) {
@@ -3447,6 +3641,11 @@ int artp_cost_get_features(artp_ctx* c, float* out, int* fh, int* fw) {
     out[i] = (float)h;
   }
   return ARTP_OK;
+}
+
+// the light network's 48 channels only: refused while the full-width network is loaded (an old caller's buffer)
+int artp_cost_get_features(artp_ctx* c, float* out, int* fh, int* fw) {
+  return artp_cost_get_features_c(c, out, 48, fh, fw);
 }
 
 }  // extern "C"

@@ -426,18 +426,23 @@ __device__ __forceinline__ void conv12_pooled16(const unsigned* __restrict__ pat
 // (conv12_mfma_kernel, (A') as a launch of its own: cost_kernels_variants.h)
 
 // ---- (B) conv3 -> conv4 -> pool3 -> conv5 ------------------------------------------------------------------
-template <int T>
+// C1 = the channels of conv1 / conv2 (the patch), C = those of conv3 .. conv5: 24 / 48 for the light network
+// (network_light.py), 32 / 64 for the full-width one (network.py).  NT = C / 16 channel tiles, KS3 / KS = the k-steps of
+// conv3 / conv4 and conv5 (27 / 54 chunks -> 7 / 14 for the light network, 36 / 72 -> 9 / 18 for the full one).
+// At full width a tile needs (T+4)^2 + (T+6)^2 pixels of 128 bytes + 72 KB of weights: T = 12 is 145 KB, T = 16 would be 183.
+template <int T, int C1 = 24, int C = 48>
 struct C345Cfg {
+  static constexpr int NT = C / 16, KS3 = (9 * C1 / 8 + 3) / 4, KS = (9 * C / 8 + 3) / 4;
   static constexpr int RI = T + 8, R3 = T + 6, R4 = T + 4, RP = T + 2;
-  static constexpr int IN_B = RI * RI * 48, C3_B = R3 * R3 * 96, C4_B = R4 * R4 * 96, P_B = RP * RP * 96,
-                       OUT_B = T * T * 96;
+  static constexpr int IN_B = RI * RI * C1 * 2, C3_B = R3 * R3 * C * 2, C4_B = R4 * R4 * C * 2, P_B = RP * RP * C * 2,
+                       OUT_B = T * T * C * 2;
   static constexpr int X_B = ((IN_B > C4_B ? IN_B : C4_B) + 255) & ~255;   // input patch, then conv4's region, then the out tile
   static constexpr int Y_B = ((C3_B > P_B ? C3_B : P_B) + 255) & ~255;     // conv3's region, then the pooled region
-  static constexpr int W_B = 14 * 3 * 1024;   // conv4's, then conv5's B fragments (14 k-steps x 3 x 64 lanes x 16 bytes)
+  static constexpr int W_B = KS * NT * 1024;  // conv4's, then conv5's B fragments (14 k-steps x 3 x 64 lanes x 16 bytes)
   // conv3's (7 k-steps) get a region of their own when it fits: conv4's weights can then be committed without
   // waiting for every wavefront to leave conv3 (one barrier less); T = 18 shares the region
-  static constexpr bool SEP_W3 = X_B + Y_B + W_B + 7 * 3 * 1024 <= 160 * 1024;
-  static constexpr int W3_B = SEP_W3 ? 7 * 3 * 1024 : 0;
+  static constexpr bool SEP_W3 = X_B + Y_B + W_B + KS3 * NT * 1024 <= 160 * 1024;
+  static constexpr int W3_B = SEP_W3 ? KS3 * NT * 1024 : 0;
   static constexpr int LDS_BYTES = X_B + Y_B + W3_B + W_B;
   static_assert(LDS_BYTES <= 160 * 1024, "one workgroup per CU");
   static_assert(OUT_B <= X_B, "the finished tile is staged over conv4's region");
@@ -452,20 +457,20 @@ constexpr int C345_NT = 64 * C345_NW;    // latencies run under the other's MFMA
 // their use (w_prefetch), registers -> LDS once the previous layer is done with the region (w_commit) -- and every
 // wavefront reads its fragments from LDS.  (Each wavefront fetching them itself moved 420 KB per tile through the
 // L1 against 27 KB of input.)
-template <int KS>
-struct WRegs { half8 v[(KS * 192 + C345_NT - 1) / C345_NT]; };
-template <int KS>
-__device__ __forceinline__ void w_prefetch(const half8* __restrict__ wp, WRegs<KS>& r, int tid) {
-  constexpr int NCH = KS * 192, NIT = (NCH + C345_NT - 1) / C345_NT;
+template <int KS, int NT = 3>
+struct WRegs { half8 v[(KS * NT * 64 + C345_NT - 1) / C345_NT]; };
+template <int KS, int NT = 3>
+__device__ __forceinline__ void w_prefetch(const half8* __restrict__ wp, WRegs<KS, NT>& r, int tid) {
+  constexpr int NCH = KS * NT * 64, NIT = (NCH + C345_NT - 1) / C345_NT;
 #pragma unroll
   for (int it = 0; it < NIT; ++it) {
     const int c = tid + it * C345_NT;
     r.v[it] = wp[c < NCH ? c : NCH - 1];
   }
 }
-template <int KS>
-__device__ __forceinline__ void w_commit(char* __restrict__ W, const WRegs<KS>& r, int tid) {
-  constexpr int NCH = KS * 192, NIT = (NCH + C345_NT - 1) / C345_NT;
+template <int KS, int NT = 3>
+__device__ __forceinline__ void w_commit(char* __restrict__ W, const WRegs<KS, NT>& r, int tid) {
+  constexpr int NCH = KS * NT * 64, NIT = (NCH + C345_NT - 1) / C345_NT;
 #pragma unroll
   for (int it = 0; it < NIT; ++it) {
     const int c = tid + it * C345_NT;
@@ -480,11 +485,11 @@ __device__ __forceinline__ void w_commit(char* __restrict__ W, const WRegs<KS>& 
 // column (lane & 15) = pixel, row ((lane >> 4) * 4 + r) = channel, so a lane ends up with FOUR CONSECUTIVE CHANNELS
 // of one pixel -- one 8-byte store into the NHWC region instead of four 2-byte stores that collide 8-fold on the
 // LDS banks (first version: the three epilogues cost more cycles than the three MFMA loops).
-// W: the layer's B fragments [KS][3][64] in LDS, chunk order (packed by artp_cost_load_weights).
+// W: the layer's B fragments [KS][NT][64] in LDS, chunk order (packed by artp_cost_load_weights).
 // bv: the layer's bias, bv[n][r] = channel 16 n + 4 (lane >> 4) + r; it rides in the accumulator.
-template <int CIN, int RWI, int RWO, int MTW, int KS>
+template <int CIN, int RWI, int RWO, int MTW, int KS, int NT = 3>
 __device__ __forceinline__ void conv3x3_lds_mfma(const char* __restrict__ in, const char* __restrict__ W,
-                                                 const floatx4 (&bv)[3], floatx4 (&acc)[MTW][3], int wave, int lane) {
+                                                 const floatx4 (&bv)[NT], floatx4 (&acc)[MTW][NT], int wave, int lane) {
   constexpr int PIXB = CIN * 2;
   constexpr int CPR = 3 * CIN / 8;      // 16-byte chunks per kernel row (kw, cin)
   constexpr int Q = 3 * CPR;            // chunks of the whole window
@@ -499,7 +504,7 @@ __device__ __forceinline__ void conv3x3_lds_mfma(const char* __restrict__ in, co
     const int y = p / RWO, x = p - y * RWO;
     base[m] = (y * RWI + x) * PIXB;
 #pragma unroll
-    for (int n = 0; n < 3; ++n) acc[m][n] = bv[n];
+    for (int n = 0; n < NT; ++n) acc[m][n] = bv[n];
   }
   auto chunk_off = [&](int ks) {
     int q = ks * 4 + kg;
@@ -507,12 +512,12 @@ __device__ __forceinline__ void conv3x3_lds_mfma(const char* __restrict__ in, co
     const int r = (q >= CPR) + (q >= 2 * CPR);
     return r * (RWI * PIXB - CPR * 16) + q * 16;   // r * RWI * PIXB + (q - r * CPR) * 16
   };
-  half8 a[2][MTW], b[2][3];
+  half8 a[2][MTW], b[2][NT];
   const char* wl = W + lane * 16;
   {
     const int off = chunk_off(0);
 #pragma unroll
-    for (int n = 0; n < 3; ++n) b[0][n] = *reinterpret_cast<const half8*>(wl + n * 1024);
+    for (int n = 0; n < NT; ++n) b[0][n] = *reinterpret_cast<const half8*>(wl + n * 1024);
 #pragma unroll
     for (int m = 0; m < MTW; ++m) a[0][m] = *reinterpret_cast<const half8*>(in + base[m] + off);
   }
@@ -522,7 +527,7 @@ __device__ __forceinline__ void conv3x3_lds_mfma(const char* __restrict__ in, co
     if (ks + 1 < KS) {
       const int off = chunk_off(ks + 1);
 #pragma unroll
-      for (int n = 0; n < 3; ++n) b[nxt][n] = *reinterpret_cast<const half8*>(wl + ((ks + 1) * 3 + n) * 1024);
+      for (int n = 0; n < NT; ++n) b[nxt][n] = *reinterpret_cast<const half8*>(wl + ((ks + 1) * NT + n) * 1024);
 #pragma unroll
       for (int m = 0; m < MTW; ++m) a[nxt][m] = *reinterpret_cast<const half8*>(in + base[m] + off);
     }
@@ -530,16 +535,16 @@ __device__ __forceinline__ void conv3x3_lds_mfma(const char* __restrict__ in, co
     for (int m = 0; m < MTW; ++m)
       if (m < MTW - 1 || (m * C345_NW + wave) * 16 < NPO) {  // wave-uniform: a wavefront without a last m-tile skips it
 #pragma unroll
-        for (int n = 0; n < 3; ++n)
+        for (int n = 0; n < NT; ++n)
           acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(b[cur][n], a[cur][m], acc[m][n], 0, 0, 0);
       }
   }
 }
 
-// leaky-ReLU + fp16 of a layer's accumulators (bias included) into an LDS region (linear pixel index, 96 bytes per
+// leaky-ReLU + fp16 of a layer's accumulators (bias included) into an LDS region (linear pixel index, NT * 32 bytes per
 // pixel).  Transposed product (see above): lane = pixel (lane & 15) of the m-tile, acc[m][n][r] = channel 16 n + 4 (lane >> 4) + r.
-template <int NPO, int MTW>
-__device__ __forceinline__ void store_region_lds(char* __restrict__ out, const floatx4 (&acc)[MTW][3], int wave,
+template <int NPO, int MTW, int NT = 3>
+__device__ __forceinline__ void store_region_lds(char* __restrict__ out, const floatx4 (&acc)[MTW][NT], int wave,
                                                  int lane) {
   typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
   const int li = lane & 15, kg = lane >> 4;
@@ -548,11 +553,11 @@ __device__ __forceinline__ void store_region_lds(char* __restrict__ out, const f
     const int p = (m * C345_NW + wave) * 16 + li;
     if (p < NPO) {
 #pragma unroll
-      for (int n = 0; n < 3; ++n) {
+      for (int n = 0; n < NT; ++n) {
         half4_t h;
 #pragma unroll
         for (int r = 0; r < 4; ++r) h[r] = (half_t)fmaxf(acc[m][n][r], 0.3f * acc[m][n][r]);  // lrelu(v) = max(v, 0.3 v)
-        *reinterpret_cast<half4_t*>(out + p * 96 + (n * 16 + kg * 4) * 2) = h;
+        *reinterpret_cast<half4_t*>(out + p * NT * 32 + (n * 16 + kg * 4) * 2) = h;
       }
     }
   }
@@ -574,15 +579,17 @@ __device__ unsigned long long g_cnn_cycles[16];  // conv345 phases (cycles of wa
 // (conv12_pooled16, the arithmetic of conv12_mfma_kernel: the same bits): `in` is not read, no 24-channel image exists, and
 // the launch in front is gone.  The window of a (T+8)^2 patch is (2 T + 20)^2 floats -- fewer bytes than the patch itself --,
 // kept as half floats (twice, see conv12_mfma_kernel) in conv3's still unused output region.
-template <int T, bool XCD = true, bool F12 = false>
+// C1 / C: the network's widths (C345Cfg): 24 / 48 the light network, 32 / 64 the full one (F12 only; its 32 channels fill the
+// composed layer's two 16-channel MFMA tiles that the light network's 24 pad).
+template <int T, bool XCD = true, bool F12 = false, int C1 = 24, int C = 48>
 __global__ void __launch_bounds__(C345_NT)
-conv345_kernel(const half_t* __restrict__ in /*[Hin][Win][24]*/, int Hin, int Win,
+conv345_kernel(const half_t* __restrict__ in /*[Hin][Win][C1]*/, int Hin, int Win,
                const half8* __restrict__ w3, const float* __restrict__ b3, const half8* __restrict__ w4,
                const float* __restrict__ b4, const half8* __restrict__ w5, const float* __restrict__ b5,
-               half_t* __restrict__ out /*[Hin-8][Win-8][48]*/, const float* __restrict__ raw = nullptr /*[H][W]*/, int H = 0,
+               half_t* __restrict__ out /*[Hin-8][Win-8][C]*/, const float* __restrict__ raw = nullptr /*[H][W]*/, int H = 0,
                int W = 0, const half8* __restrict__ w12 = nullptr, const float* __restrict__ b12 = nullptr) {
-  using Cfg = C345Cfg<T>;
-  constexpr int NW = C345_NW, NT_ = C345_NT;
+  using Cfg = C345Cfg<T, C1, C>;
+  constexpr int NW = C345_NW, NT_ = C345_NT, NT = Cfg::NT, KS3 = Cfg::KS3, KS = Cfg::KS, PXB = C * 2;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* X = smem;
   char* Y = smem + Cfg::X_B;
@@ -600,9 +607,9 @@ conv345_kernel(const half_t* __restrict__ in /*[Hin][Win][24]*/, int Hin, int Wi
 #endif
   // the three layers' biases (transposed product: four consecutive channels per lane) up front: a global load in
   // front of a layer's first MFMA would sit in its critical path
-  floatx4 bv3[3], bv4[3], bv5[3];
+  floatx4 bv3[NT], bv4[NT], bv5[NT];
 #pragma unroll
-  for (int n = 0; n < 3; ++n) {
+  for (int n = 0; n < NT; ++n) {
     bv3[n] = *reinterpret_cast<const floatx4*>(b3 + n * 16 + (lane >> 4) * 4);
     bv4[n] = *reinterpret_cast<const floatx4*>(b4 + n * 16 + (lane >> 4) * 4);
     bv5[n] = *reinterpret_cast<const floatx4*>(b5 + n * 16 + (lane >> 4) * 4);
@@ -611,9 +618,9 @@ conv345_kernel(const half_t* __restrict__ in /*[Hin][Win][24]*/, int Hin, int Wi
   // and conv3's weights (requested first) does not wait for the others -- conv4's have the whole of conv3 to arrive and
   // conv5's the whole of conv3 and conv4 (requested a phase ahead, 256 workgroups fetching the same 43 KB at the same
   // moment waited 4-6 k cycles at each commit).  60 registers until the commits.
-  WRegs<7> rw3;
-  WRegs<14> rw, rw5;
-  w_prefetch<7>(w3, rw3, tid);  // conv3's weights travel with the patch
+  WRegs<KS3, NT> rw3;
+  WRegs<KS, NT> rw, rw5;
+  w_prefetch<KS3, NT>(w3, rw3, tid);  // conv3's weights travel with the patch
   if constexpr (F12) {
     // the tile's window of the map -> half floats in Y, twice (copy 1 shifted by one pixel); zeros outside the map
     constexpr int RI = Cfg::RI, WIN = 2 * RI + 4, RSD = RI + 3, COPY = WIN * RSD;
@@ -645,9 +652,9 @@ conv345_kernel(const half_t* __restrict__ in /*[Hin][Win][24]*/, int Hin, int Wi
         if (c > 0) p1[r * 2 * RSD + c - 1] = h;
       }
     }
-    w_prefetch<14>(w4, rw, tid);
-    w_prefetch<14>(w5, rw5, tid);
-    w_commit<7>(W3, rw3, tid);
+    w_prefetch<KS, NT>(w4, rw, tid);
+    w_prefetch<KS, NT>(w5, rw5, tid);
+    w_commit<KS3, NT>(W3, rw3, tid);
     __syncthreads();
     ARTP_CNN_MARK(11);
     // the patch: 16 pooled pixels per step and wavefront, linear pixel index over the RI x RI patch
@@ -668,24 +675,24 @@ conv345_kernel(const half_t* __restrict__ in /*[Hin][Win][24]*/, int Hin, int Wi
       }
       if (live) {
         const int g = lane >> 4;
-        *reinterpret_cast<half4_t*>(X + pp * 48 + 8 * g) = o0;
-        if (g < 2) *reinterpret_cast<half4_t*>(X + pp * 48 + 32 + 8 * g) = o1;
+        *reinterpret_cast<half4_t*>(X + pp * C1 * 2 + 8 * g) = o0;
+        if (C1 == 32 || g < 2) *reinterpret_cast<half4_t*>(X + pp * C1 * 2 + 32 + 8 * g) = o1;
       }
     }
     ARTP_CNN_MARK(12);
   } else {
   // input patch (T+8)^2 x 24 channels -> X; rows are contiguous byte runs of the NHWC image, zeros outside it
   {
-    constexpr int CPR = Cfg::RI * 48 / 16;  // 16-byte chunks per patch row
+    constexpr int CPR = Cfg::RI * C1 * 2 / 16;  // 16-byte chunks per patch row
     constexpr int NCH = Cfg::RI * CPR;
     constexpr int NIT = (NCH + NT_ - 1) / NT_;
-    const long row_bytes = (long)Win * 48;
+    const long row_bytes = (long)Win * C1 * 2;
     half8 v[NIT];
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
       const int c = tid + it * NT_;
       const int r = c / CPR, cc = c - r * CPR;
-      const long off = (long)ox0 * 48 + (long)cc * 16;
+      const long off = (long)ox0 * C1 * 2 + (long)cc * 16;
       // unconditional load from a clamped address (see the fused branch above: conditional loads are serialised)
       const bool ok = c < NCH && oy0 + r < Hin && off + 16 <= row_bytes;
       const half8 t = *reinterpret_cast<const half8*>(reinterpret_cast<const char*>(in) + (ok ? (long)(oy0 + r) * row_bytes + off : 0l));
@@ -698,51 +705,52 @@ conv345_kernel(const half_t* __restrict__ in /*[Hin][Win][24]*/, int Hin, int Wi
       if (c < NCH) *reinterpret_cast<half8*>(X + c * 16) = v[it];
     }
   }
-  w_prefetch<14>(w4, rw, tid);
-  w_prefetch<14>(w5, rw5, tid);
-  w_commit<7>(W3, rw3, tid);
+  w_prefetch<KS, NT>(w4, rw, tid);
+  w_prefetch<KS, NT>(w5, rw5, tid);
+  w_commit<KS3, NT>(W3, rw3, tid);
   }
   __syncthreads();
   ARTP_CNN_MARK(0);
   {  // conv3: X (24 ch) -> Y
     constexpr int MTW = (Cfg::R3 * Cfg::R3 + 16 * NW - 1) / (16 * NW);
-    floatx4 acc[MTW][3];
-    conv3x3_lds_mfma<24, Cfg::RI, Cfg::R3, MTW, 7>(X, W3, bv3, acc, wave, lane);
+    floatx4 acc[MTW][NT];
+    conv3x3_lds_mfma<C1, Cfg::RI, Cfg::R3, MTW, KS3, NT>(X, W3, bv3, acc, wave, lane);
     ARTP_CNN_MARK(1);
-    store_region_lds<Cfg::R3 * Cfg::R3, MTW>(Y, acc, wave, lane);
+    store_region_lds<Cfg::R3 * Cfg::R3, MTW, NT>(Y, acc, wave, lane);
     ARTP_CNN_MARK(2);
   }
   if (!Cfg::SEP_W3) __syncthreads();  // shared region: every wavefront must be done with conv3's weights
-  w_commit<14>(Wl, rw, tid);          // (own region: no wavefront reads it before the barrier)
+  w_commit<KS, NT>(Wl, rw, tid);      // (own region: no wavefront reads it before the barrier)
   __syncthreads();
   ARTP_CNN_MARK(3);
   {  // conv4: Y -> X (the patch is dead)
     constexpr int MTW = (Cfg::R4 * Cfg::R4 + 16 * NW - 1) / (16 * NW);
-    floatx4 acc[MTW][3];
-    conv3x3_lds_mfma<48, Cfg::R3, Cfg::R4, MTW, 14>(Y, Wl, bv4, acc, wave, lane);
+    floatx4 acc[MTW][NT];
+    conv3x3_lds_mfma<C, Cfg::R3, Cfg::R4, MTW, KS, NT>(Y, Wl, bv4, acc, wave, lane);
     ARTP_CNN_MARK(4);
-    store_region_lds<Cfg::R4 * Cfg::R4, MTW>(X, acc, wave, lane);
+    store_region_lds<Cfg::R4 * Cfg::R4, MTW, NT>(X, acc, wave, lane);
     ARTP_CNN_MARK(5);
   }
   __syncthreads();               // conv4's weights are dead, X is complete
-  w_commit<14>(Wl, rw5, tid);
+  w_commit<KS, NT>(Wl, rw5, tid);
   ARTP_CNN_MARK(6);
   {  // max_pool 3 / 1: X -> Y.  An item = (pooled pixel, 8-channel chunk): nine independent 16-byte reads, a max tree, one
      // store; the items are dealt out thread by thread, fully unrolled (round 5: the column walk with three rows in
      // registers read a third as much but as a chain of dependent LDS round trips -- 6 k cycles for 1.2 k of LDS time).
-    constexpr int RP = Cfg::RP, R4 = Cfg::R4, NITEM = RP * RP * 6, NIT = (NITEM + NT_ - 1) / NT_;
+    constexpr int CPP = C / 8;   // 16-byte chunks per pixel
+    constexpr int RP = Cfg::RP, R4 = Cfg::R4, NITEM = RP * RP * CPP, NIT = (NITEM + NT_ - 1) / NT_;
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
       const int item = tid + it * NT_;
       if (item < NITEM) {
-        const int p = item / 6, c = item - p * 6;
+        const int p = item / CPP, c = item - p * CPP;
         const int y = p / RP, x = p - y * RP;
-        const char* src = X + ((y * R4 + x) * 96 + c * 16);
+        const char* src = X + ((y * R4 + x) * PXB + c * 16);
         half8 m = *reinterpret_cast<const half8*>(src);
 #pragma unroll
         for (int k = 1; k < 9; ++k)
-          m = __builtin_elementwise_max(m, *reinterpret_cast<const half8*>(src + ((k / 3) * R4 + (k % 3)) * 96));
-        *reinterpret_cast<half8*>(Y + p * 96 + c * 16) = m;
+          m = __builtin_elementwise_max(m, *reinterpret_cast<const half8*>(src + ((k / 3) * R4 + (k % 3)) * PXB));
+        *reinterpret_cast<half8*>(Y + p * PXB + c * 16) = m;
       }
     }
   }
@@ -750,20 +758,20 @@ conv345_kernel(const half_t* __restrict__ in /*[Hin][Win][24]*/, int Hin, int Wi
   ARTP_CNN_MARK(7);
   {  // conv5: Y -> the finished tile, staged in X, then whole 16-byte lanes to the NHWC image
     constexpr int MTW = (T * T + 16 * NW - 1) / (16 * NW);
-    floatx4 acc[MTW][3];
-    conv3x3_lds_mfma<48, Cfg::RP, T, MTW, 14>(Y, Wl, bv5, acc, wave, lane);
+    floatx4 acc[MTW][NT];
+    conv3x3_lds_mfma<C, Cfg::RP, T, MTW, KS, NT>(Y, Wl, bv5, acc, wave, lane);
     ARTP_CNN_MARK(8);
-    store_region_lds<T * T, MTW>(X, acc, wave, lane);
+    store_region_lds<T * T, MTW, NT>(X, acc, wave, lane);
   }
   __syncthreads();
   ARTP_CNN_MARK(9);
   {
-    constexpr int CPR = T * 96 / 16;  // chunks per tile row
+    constexpr int CPR = T * PXB / 16;  // chunks per tile row
     for (int c = tid; c < T * CPR; c += NT_) {
       const int r = c / CPR, cc = c - r * CPR;
-      const int px = (cc * 16) / 96;
+      const int px = (cc * 16) / PXB;
       if (oy0 + r < Hout && ox0 + px < Wout)
-        *reinterpret_cast<half8*>(reinterpret_cast<char*>(out) + ((size_t)(oy0 + r) * Wout + ox0) * 96 + cc * 16) =
+        *reinterpret_cast<half8*>(reinterpret_cast<char*>(out) + ((size_t)(oy0 + r) * Wout + ox0) * PXB + cc * 16) =
             *reinterpret_cast<const half8*>(X + c * 16);
     }
   }
@@ -784,6 +792,17 @@ struct FcWeights {  // BN folded; fp32; offsets into one LDS/global array
     H3_W = H2_B + 24, H3_B = H3_W + 36 * 48, O1_W = H3_B + 36, O1_B = O1_W + 24, O2_W = O1_B + 1,
     O2_B = O2_W + 24, O3_W = O2_B + 1, O3_B = O3_W + 36, TOTAL = O3_B + 1
   };
+  static constexpr int C = 48, HID = 48, N12 = 24, N3 = 36;   // map features, out0 units, units of heads 1 / 2 and of head 3
+};
+// the full-width network (network.py): 64 features, out0 80 -> 64, three heads of 32
+struct FcWeightsFull {
+  enum {
+    TAR0_W = 0, TAR0_B = TAR0_W + 160, OUT0_W = TAR0_B + 16, OUT0_B = OUT0_W + 64 * 80,
+    H1_W = OUT0_B + 64, H1_B = H1_W + 32 * 64, H2_W = H1_B + 32, H2_B = H2_W + 32 * 64,
+    H3_W = H2_B + 32, H3_B = H3_W + 32 * 64, O1_W = H3_B + 32, O1_B = O1_W + 32, O2_W = O1_B + 1,
+    O2_B = O2_W + 32, O3_W = O2_B + 1, O3_B = O3_W + 32, TOTAL = O3_B + 1
+  };
+  static constexpr int C = 64, HID = 64, N12 = 32, N3 = 32;
 };
 
 struct CostMapGeom {
@@ -816,11 +835,15 @@ cost_query_cells_kernel(const float* __restrict__ edges, size_t B, CostMapGeom g
 }
 
 // edges: [B][6] = tx ty tyaw sx sy syaw (motion_cost_objective.h:22, prm_motion_cost.cpp:41-52)
-// feat : NHWC fp16 [F][F][48], index [row][col] with row growing along world x (cost_query_server.py:74)
+// feat : NHWC fp16 [F][F][FW::C], index [row][col] with row growing along world x (cost_query_server.py:74)
 // cost : [B][3] = energy, time, 1 - prob
+// FW: FcWeights (the light network) or FcWeightsFull
+template <class FW = FcWeights>
 __global__ void __launch_bounds__(256)
 fc_cost_kernel(const float* __restrict__ edges, size_t B, const half_t* __restrict__ feat, CostMapGeom g,
                const float* __restrict__ wts, float* __restrict__ cost) {
+  using FcWeights = FW;
+  constexpr int NF = FW::C, NH = FW::HID;
   // the weights are wave-uniform operands: read straight from the (scalar-cached) blob, they arrive in SGPRs
   const float* __restrict__ sw = wts;
   const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -829,10 +852,10 @@ fc_cost_kernel(const float* __restrict__ edges, size_t B, const half_t* __restri
   const double tx = ed[0], ty = ed[1], tyaw = ed[2], sx = ed[3], sy = ed[4], syaw = ed[5];
   int row, col;
   cost_query_cell(g, sx, sy, &row, &col);  // cost_query.py:51-55
-  const half_t* fp = feat + ((size_t)row * g.Fw + col) * 48;
-  float x[64];
+  const half_t* fp = feat + ((size_t)row * g.Fw + col) * NF;
+  float x[NF + 16];
 #pragma unroll
-  for (int v = 0; v < 6; ++v) {
+  for (int v = 0; v < NF / 8; ++v) {
     const half8 t = reinterpret_cast<const half8*>(fp)[v];
 #pragma unroll
     for (int j = 0; j < 8; ++j) x[v * 8 + j] = (float)t[j];
@@ -861,24 +884,24 @@ fc_cost_kernel(const float* __restrict__ edges, size_t B, const half_t* __restri
     float a = sw[FcWeights::TAR0_B + o];
 #pragma unroll
     for (int k = 0; k < 10; ++k) a = fmaf(t[k], sw[FcWeights::TAR0_W + o * 10 + k], a);
-    x[48 + o] = a;
+    x[NF + o] = a;
   }
-  float h[48];
+  float h[NH];
 #pragma unroll
-  for (int o = 0; o < 48; ++o) {
+  for (int o = 0; o < NH; ++o) {
     float a = sw[FcWeights::OUT0_B + o];
 #pragma unroll
-    for (int k = 0; k < 64; ++k) a = fmaf(x[k], sw[FcWeights::OUT0_W + o * 64 + k], a);
+    for (int k = 0; k < NF + 16; ++k) a = fmaf(x[k], sw[FcWeights::OUT0_W + o * (NF + 16) + k], a);
     h[o] = a > 0.f ? a : 0.3f * a;
   }
   float power = sw[FcWeights::O1_B], tim = sw[FcWeights::O2_B], prob = sw[FcWeights::O3_B];
 #pragma unroll 4
-  for (int o = 0; o < 24; ++o) {
+  for (int o = 0; o < FW::N12; ++o) {
     float a = sw[FcWeights::H1_B + o], c = sw[FcWeights::H2_B + o];
 #pragma unroll
-    for (int k = 0; k < 48; ++k) {
-      a = fmaf(h[k], sw[FcWeights::H1_W + o * 48 + k], a);
-      c = fmaf(h[k], sw[FcWeights::H2_W + o * 48 + k], c);
+    for (int k = 0; k < NH; ++k) {
+      a = fmaf(h[k], sw[FcWeights::H1_W + o * NH + k], a);
+      c = fmaf(h[k], sw[FcWeights::H2_W + o * NH + k], c);
     }
     a = a > 0.f ? a : 0.3f * a;
     c = c > 0.f ? c : 0.3f * c;
@@ -886,10 +909,10 @@ fc_cost_kernel(const float* __restrict__ edges, size_t B, const half_t* __restri
     tim = fmaf(c, sw[FcWeights::O2_W + o], tim);
   }
 #pragma unroll 4
-  for (int o = 0; o < 36; ++o) {
+  for (int o = 0; o < FW::N3; ++o) {
     float a = sw[FcWeights::H3_B + o];
 #pragma unroll
-    for (int k = 0; k < 48; ++k) a = fmaf(h[k], sw[FcWeights::H3_W + o * 48 + k], a);
+    for (int k = 0; k < NH; ++k) a = fmaf(h[k], sw[FcWeights::H3_W + o * NH + k], a);
     a = a > 0.f ? a : 0.3f * a;
     prob = fmaf(a, sw[FcWeights::O3_W + o], prob);
   }
@@ -1127,6 +1150,193 @@ fc_cost_mfma_kernel(const float* __restrict__ edges, size_t B, const half_t* __r
         const size_t e = chunk * 64 + el[u];
         if (kg == 0 && e < B) {
           const float* ob = reinterpret_cast<const float*>(sw + FcMfma::OB);
+          float power = pp + ob[0], tim = qq + ob[1], prob = rr + ob[2];
+          power = power > 0.f ? power : 0.f;
+          tim = tim > 0.f ? tim : 0.f;
+          prob = 1.0f / (1.0f + expf(-prob));
+          cost[3 * e + 0] = power;
+          cost[3 * e + 1] = tim;
+          cost[3 * e + 2] = 1.0f - prob;  // cost_query.py:65-69 returns cost[3] = 1 - prob
+        }
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();   // the staging area is rewritten by the next chunk
+  }
+}
+
+// ---- the full-width network's MLP on the matrix cores (network.py: 64 features + tar0's 16 -> 64 hidden -> 3 x 32 head units) -----
+// fc_cost_mfma_kernel's scheme at the other widths: the transposed product over 16-edge tiles, every fp32 operand as a half-float
+// hi / lo pair, tar0 composed into out0 on the host (K = 64 features + 10 inputs + 1 bias = 75 of 96: three 32-wide steps).
+// Both GEMMs are whole 32-wide steps here -- 64 hidden units = two steps of the second GEMM --, so there is no 16-wide step and
+// no mixed-shape accumulation (no FCM_SHAPE_CHANGE).  Hidden unit 32 s + 8 g + 4 u + i sits in accumulator row 4 g + i of
+// tile 2 s + u: the four tiles of the first GEMM are, pairwise, the second's operands for step s.  Head units 32 h .. 32 h + 31 =
+// head h (energy, time, prob): tiles 2 h and 2 h + 1.
+// Blob (fc_mfma_pack_full on the host): [s 3][t 4][hi|lo] 1 KB fragments of the first GEMM, [s 2][t 6][hi|lo] of the second,
+// head biases [96], output weights [96] (unit u belongs to head u / 32), output biases [3].
+struct FcMfmaFull {
+  enum {
+    G1 = 0, G2 = G1 + 24 * 1024, BIAS2 = G2 + 24 * 1024, OUT = BIAS2 + 96 * 4, OB = OUT + 96 * 4, TOTAL = OB + 16,
+    STAGE = FcMfma::STAGE
+  };
+  static_assert(TOTAL % 16 == 0, "16-byte copies");
+};
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2)))
+fc_cost_mfma_full_kernel(const float* __restrict__ edges, size_t B, const half_t* __restrict__ feat, CostMapGeom g,
+                         const char* __restrict__ blob, float* __restrict__ cost) {
+  __shared__ __attribute__((aligned(16))) char sw[FcMfmaFull::TOTAL];
+  __shared__ __attribute__((aligned(16))) char stage_all[4][FcMfmaFull::STAGE];
+  for (int i = threadIdx.x; i < FcMfmaFull::TOTAL / 16; i += blockDim.x)
+    reinterpret_cast<uint4*>(sw)[i] = reinterpret_cast<const uint4*>(blob)[i];
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int li = lane & 15, kg = lane >> 4;
+  char* st = stage_all[wave];
+  int* s_off = reinterpret_cast<int*>(st);
+  half_t* s_hi = reinterpret_cast<half_t*>(st + 256);
+  half_t* s_lo = reinterpret_cast<half_t*>(st + 256 + 64 * 32);
+  const size_t n_chunks = (B + 63) / 64;
+  for (size_t chunk = (size_t)blockIdx.x * 4 + wave; chunk < n_chunks; chunk += (size_t)gridDim.x * 4) {
+    {  // one lane per edge: gather offset and the ten geometric inputs (network.py:118-132), hi / lo halves
+      const size_t e_raw = chunk * 64 + lane;
+      const size_t e = e_raw < B ? e_raw : B - 1;
+      const float* ed = edges + 6 * e;
+      const double tx = ed[0], ty = ed[1], tyaw = ed[2], sx = ed[3], sy = ed[4], syaw = ed[5];
+      int row, col;
+      cost_query_cell(g, sx, sy, &row, &col);  // cost_query.py:51-55
+      s_off[lane] = (row * g.Fw + col) * 64;
+      const float dx = (float)(tx - sx), dy = (float)(ty - sy);
+      float dyaw = (float)(tyaw - syaw);
+      const float PI = 3.14159265358979323846f;
+      if (dyaw > PI) dyaw -= 2.0f * PI;
+      if (dyaw < -PI) dyaw += 2.0f * PI;
+      const float sya = (float)syaw;
+      float t[16];
+      t[0] = dx;
+      t[1] = dy;
+      t[2] = sqrtf(dx * dx + dy * dy);
+      t[3] = atan2f(dy, dx);
+      t[4] = dyaw;
+      t[5] = cosf(dyaw);
+      t[6] = sinf(dyaw);
+      t[7] = sya;
+      t[8] = cosf(sya);
+      t[9] = sinf(sya);
+      t[10] = 1.0f;  // the composed bias rides on this input
+      t[11] = t[12] = t[13] = t[14] = t[15] = 0.0f;
+      half8 h0, h1, l0, l1;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        h0[k] = (half_t)t[k];
+        l0[k] = (half_t)(t[k] - (float)h0[k]);
+        h1[k] = (half_t)t[8 + k];
+        l1[k] = (half_t)(t[8 + k] - (float)h1[k]);
+      }
+      reinterpret_cast<half8*>(s_hi + lane * 16)[0] = h0;
+      reinterpret_cast<half8*>(s_hi + lane * 16)[1] = h1;
+      reinterpret_cast<half8*>(s_lo + lane * 16)[0] = l0;
+      reinterpret_cast<half8*>(s_lo + lane * 16)[1] = l1;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll 1
+    for (int pair = 0; pair < 2; ++pair) {
+      // two 16-edge tiles per pass; the weight fragments are read from LDS in every pass (see fc_cost_mfma_kernel)
+      int woff = lane * 16;
+      asm volatile("" : "+v"(woff));
+      const char* wl = sw + woff;
+      int el[2];
+      half8 x0[2], x1[2], x2[2], x2lo[2];
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        el[u] = (pair * 2 + u) * 16 + li;
+        const half_t* fp = feat + s_off[el[u]];
+        // operands of the first GEMM: lane = edge li, k = 32 s + 8 kg + j
+        x0[u] = *reinterpret_cast<const half8*>(fp + 8 * kg);
+        x1[u] = *reinterpret_cast<const half8*>(fp + 32 + 8 * kg);
+        if (kg < 2) {
+          x2[u] = *reinterpret_cast<const half8*>(s_hi + el[u] * 16 + 8 * kg);
+          x2lo[u] = *reinterpret_cast<const half8*>(s_lo + el[u] * 16 + 8 * kg);
+        } else {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) x2[u][j] = x2lo[u][j] = (half_t)0.0f;
+        }
+      }
+      floatx4 a1[2][4];
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        floatx4 c0 = {0.0f, 0.0f, 0.0f, 0.0f}, c1 = {0.0f, 0.0f, 0.0f, 0.0f};
+        half8 wh[3], wlo[3];
+#pragma unroll
+        for (int s = 0; s < 3; ++s) {
+          wh[s] = *reinterpret_cast<const half8*>(wl + FcMfmaFull::G1 + ((s * 4 + t) * 2 + 0) * 1024);
+          wlo[s] = *reinterpret_cast<const half8*>(wl + FcMfmaFull::G1 + ((s * 4 + t) * 2 + 1) * 1024);
+        }
+        // small terms first (lo x hi, hi x lo), then hi x hi; the map features are half floats (their lo is 0)
+        FCM_MFMA32X2(c0, c1, wlo[0], x0[0], x0[1]);
+        FCM_MFMA32X2(c0, c1, wlo[1], x1[0], x1[1]);
+        FCM_MFMA32X2(c0, c1, wlo[2], x2[0], x2[1]);
+        FCM_MFMA32X2(c0, c1, wh[2], x2lo[0], x2lo[1]);
+        FCM_MFMA32X2(c0, c1, wh[0], x0[0], x0[1]);
+        FCM_MFMA32X2(c0, c1, wh[1], x1[0], x1[1]);
+        FCM_MFMA32X2(c0, c1, wh[2], x2[0], x2[1]);
+        a1[0][t] = c0;
+        a1[1][t] = c1;
+      }
+      // leaky-ReLU (0.3), hi / lo halves: tiles 2 s and 2 s + 1 are step s of the second GEMM
+      half8 hA[2][2], hAlo[2][2];   // [edge tile][step]
+#pragma unroll
+      for (int u = 0; u < 2; ++u)
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            float v = a1[u][2 * s + j / 4][j % 4];
+            v = v > 0.f ? v : 0.3f * v;
+            hA[u][s][j] = (half_t)v;
+            hAlo[u][s][j] = (half_t)(v - (float)hA[u][s][j]);
+          }
+      float p[2] = {0.f, 0.f}, q[2] = {0.f, 0.f}, r[2] = {0.f, 0.f};
+#pragma unroll
+      for (int t = 0; t < 6; ++t) {
+        const floatx4 bias = *reinterpret_cast<const floatx4*>(sw + FcMfmaFull::BIAS2 + (16 * t + 4 * kg) * 4);
+        floatx4 c0 = bias, c1 = bias;
+        const half8 w0h = *reinterpret_cast<const half8*>(wl + FcMfmaFull::G2 + ((0 * 6 + t) * 2 + 0) * 1024);
+        const half8 w0l = *reinterpret_cast<const half8*>(wl + FcMfmaFull::G2 + ((0 * 6 + t) * 2 + 1) * 1024);
+        const half8 w1h = *reinterpret_cast<const half8*>(wl + FcMfmaFull::G2 + ((1 * 6 + t) * 2 + 0) * 1024);
+        const half8 w1l = *reinterpret_cast<const half8*>(wl + FcMfmaFull::G2 + ((1 * 6 + t) * 2 + 1) * 1024);
+        FCM_MFMA32X2(c0, c1, w0l, hA[0][0], hA[1][0]);
+        FCM_MFMA32X2(c0, c1, w1l, hA[0][1], hA[1][1]);
+        FCM_MFMA32X2(c0, c1, w0h, hAlo[0][0], hAlo[1][0]);
+        FCM_MFMA32X2(c0, c1, w1h, hAlo[0][1], hAlo[1][1]);
+        FCM_MFMA32X2(c0, c1, w0h, hA[0][0], hA[1][0]);
+        FCM_MFMA32X2(c0, c1, w1h, hA[0][1], hA[1][1]);
+        // head units 16 t + 4 kg + i: leaky-ReLU, then their share of their head's output dot product
+        const floatx4 o = *reinterpret_cast<const floatx4*>(sw + FcMfmaFull::OUT + (16 * t + 4 * kg) * 4);
+        floatx4 cc[2] = {c0, c1};
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) cc[u][i] = cc[u][i] > 0.f ? cc[u][i] : 0.3f * cc[u][i];
+          const float d = cc[u][0] * o[0] + cc[u][1] * o[1] + cc[u][2] * o[2] + cc[u][3] * o[3];
+          if (t < 2) p[u] += d;
+          else if (t < 4) q[u] += d;
+          else r[u] += d;
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        float pp = p[u], qq = q[u], rr = r[u];
+        pp += __shfl_xor(pp, 16, 64);
+        qq += __shfl_xor(qq, 16, 64);
+        rr += __shfl_xor(rr, 16, 64);
+        pp += __shfl_xor(pp, 32, 64);
+        qq += __shfl_xor(qq, 32, 64);
+        rr += __shfl_xor(rr, 32, 64);
+        const size_t e = chunk * 64 + el[u];
+        if (kg == 0 && e < B) {
+          const float* ob = reinterpret_cast<const float*>(sw + FcMfmaFull::OB);
           float power = pp + ob[0], tim = qq + ob[1], prob = rr + ob[2];
           power = power > 0.f ? power : 0.f;
           tim = tim > 0.f ? tim : 0.f;

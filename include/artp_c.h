@@ -599,13 +599,22 @@ void artp_preprocessed_destroy(artp_preprocessed* pp);
  *      (art_planner/include/art_planner/objectives/motion_cost_objective.h:22-23; the reference
  *      implements it as a ROS service to the Python/CUDA node, art_planner_ros/src/planner_ros.cpp:
  *      283-318 -> art_planner_motion_cost/scripts/cost_query_server.py:145-169) ----------------------
- * Weights: a flat float32 blob of the n48convNetwork3LR network (network_light.py:19-62) with eval-mode
- * BatchNorm folded into every convolution: "ARMC", version byte 1, 3 pad bytes, then for the six
- * convolutions [Cout][Cin][KH][KW] weights + [Cout] bias, then the 1x1 layers tar0, out0, out1_conv1..3
- * ([Cout][Cin] + [Cout]) and out2_conv1..3 ([Cin] + 1).  tools/convert_weights.py writes it from a
- * torch state_dict. */
-size_t artp_cost_blob_bytes(void);
+ * Weights: a flat float32 blob of the network with eval-mode BatchNorm folded into every convolution:
+ * "ARMC", a version byte, 3 pad bytes, then for the six convolutions [Cout][Cin][KH][KW] weights + [Cout] bias,
+ * then the 1x1 layers tar0, out0, out1_conv1..3 ([Cout][Cin] + [Cout]) and out2_conv1..3 ([Cin] + 1).
+ *   version 1: the light n48convNetwork3LR (network_light.py:19-62): conv1/2 24, conv3..5 and the 15x15 layer 48
+ *              channels, out0 64 -> 48, heads 24 / 24 / 36; 583 379 floats (2 333 524 bytes).
+ *   version 2: the full-width n9convNetwork3LR (network.py: grid-1563-blind, grid-1975-blind, grid-1992-perceptive):
+ *              conv1/2 32, then 64 channels, out0 80 -> 64, heads 32 / 32 / 32; 1 035 283 floats (4 141 140 bytes).
+ * tools/convert_weights.py writes either from a torch state_dict (init_conv1's width picks the version). */
+size_t artp_cost_blob_bytes(void);                 /* the version-1 (light) size */
+size_t artp_cost_blob_bytes_version(int version);  /* the size of a version-1 or -2 blob; 0 for any other version */
+/* Either version; a context switches networks in either direction.  A load that changes the network drops the
+ * feature map: artp_cost_query* answer ARTP_ERR_NO_MAP until the next artp_cost_update_map* (no query is ever answered
+ * from the other network's features).  Reloading the same network keeps it, as before. */
 int artp_cost_load_weights(artp_ctx* ctx, const void* blob, size_t bytes);
+/* *channels = the feature channels of the loaded network: 48 (version 1) or 64 (version 2); ARTP_ERR_NO_WEIGHTS before a load. */
+int artp_cost_feature_channels(artp_ctx* ctx, int* channels);
 /* Which kernel answers artp_cost_query: *mfma = 1 the MFMA form of FCpart (network_light.py:113-165), 0 the fp32 VALU kernels.
  * artp_cost_load_weights runs a probe batch through both and falls back to fp32 if they disagree (*selfcheck: 1 agreed,
  * 0 disagreed, -1 not run; *max_abs_diff = the probe's largest difference).  Any pointer may be NULL. */
@@ -647,8 +656,12 @@ int artp_cost_set_external_query(artp_ctx* ctx, artp_cost_query_fn fn, void* use
  * (cost_query.py:54-55: float64 arithmetic, clamp to [1, shape - 2], .long()) -- computed by the device function the
  * cost kernels use; the tests compare it with the reference's own CostQuery.  Host buffers. */
 int artp_cost_debug_query_cells(artp_ctx* ctx, const float* edges, size_t b, int32_t* rows_out, int32_t* cols_out);
-/* diagnostics: feature map as float [fh][fw][48]; out may be NULL to query the size */
+/* diagnostics: feature map as float [fh][fw][48]; out may be NULL to query the size.  The light network's 48 channels
+ * only: ARTP_ERR_INVALID_ARG while a version-2 network is loaded (use artp_cost_get_features_c). */
 int artp_cost_get_features(artp_ctx* ctx, float* out, int* fh, int* fw);
+/* the same for either network: float [fh][fw][channels]; channels must be artp_cost_feature_channels' value
+ * (ARTP_ERR_INVALID_ARG otherwise) */
+int artp_cost_get_features_c(artp_ctx* ctx, float* out, int channels, int* fh, int* fw);
 
 #ifdef __cplusplus
 }

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""Convert a motion-cost network state_dict (art_planner_motion_cost/.../network_light.py:19-62) into the
-flat float32 blob artp_cost_load_weights() expects (include/artp_c.h): eval-mode BatchNorm folded into
-every convolution.
+"""Convert a motion-cost network state_dict into the flat float32 blob artp_cost_load_weights() expects
+(include/artp_c.h): eval-mode BatchNorm folded into every convolution.  Both networks the reference ships
+checkpoints for convert: the light one (network_light.py:19-62, n48convNetwork3LR -> blob version 1) and the
+full-width one (network.py, n9convNetwork3LR -> blob version 2); init_conv1's width tells them apart.
 
     python tools/convert_weights.py model.pt model.armc       # needs torch + the real (git-LFS) weights
 
@@ -24,14 +25,23 @@ SHAPES = {  # network_light.py:19-62
     "out1_conv2": (24, 48, 1, 1), "out1_conv3": (36, 48, 1, 1),
     "out2_conv1": (1, 24, 1, 1), "out2_conv2": (1, 24, 1, 1), "out2_conv3": (1, 36, 1, 1),
 }
+SHAPES_FULL = {  # network.py: the same layers, wider
+    "init_conv1": (32, 1, 3, 3), "init_conv2": (32, 32, 3, 3), "init_conv3": (64, 32, 3, 3),
+    "init_conv4": (64, 64, 3, 3), "init_conv5": (64, 64, 3, 3), "init_flatten": (64, 64, 15, 15),
+    "tar0_conv1": (16, 10, 1, 1), "out0_conv1": (64, 80, 1, 1), "out1_conv1": (32, 64, 1, 1),
+    "out1_conv2": (32, 64, 1, 1), "out1_conv3": (32, 64, 1, 1),
+    "out2_conv1": (1, 32, 1, 1), "out2_conv2": (1, 32, 1, 1), "out2_conv3": (1, 32, 1, 1),
+}
 WITH_BIAS = ("out2_conv1", "out2_conv2", "out2_conv3")
+BLOB_VERSION = {24: 1, 32: 2}  # init_conv1's output channels -> blob version
 
 
-def random_params(seed=0):
-    """Seeded, well-conditioned parameters with the reference state_dict's names and shapes."""
+def random_params(seed=0, shapes=None):
+    """Seeded, well-conditioned parameters with the reference state_dict's names and shapes (SHAPES unless
+    `shapes` is given, e.g. SHAPES_FULL)."""
     rng = np.random.default_rng(seed)
     p = {}
-    for name, shp in SHAPES.items():
+    for name, shp in (SHAPES if shapes is None else shapes).items():
         fan_in = shp[1] * shp[2] * shp[3]
         p[name + ".weight"] = (rng.standard_normal(shp) * np.sqrt(2.0 / fan_in)).astype(np.float32)
         if name in WITH_BIAS:
@@ -59,6 +69,9 @@ def fold(params, name):
 
 
 def to_blob(params) -> bytes:
+    width = int(np.shape(params["init_conv1.weight"])[0])
+    if width not in BLOB_VERSION:
+        raise ValueError(f"init_conv1 has {width} output channels: neither the light (24) nor the full (32) network")
     parts = []
     for n in CONVS:
         w, b = fold(params, n)
@@ -70,7 +83,7 @@ def to_blob(params) -> bytes:
         parts += [np.asarray(params[n + ".weight"], np.float32).ravel(),
                   np.asarray(params[n + ".bias"], np.float32).ravel()]
     body = np.concatenate(parts).astype("<f4").tobytes()
-    return b"ARMC" + struct.pack("<B3x", 1) + body
+    return b"ARMC" + struct.pack("<B3x", BLOB_VERSION[width]) + body
 
 
 def main():
