@@ -32,7 +32,8 @@ SYMBOLS = [
     "artp_debug_pipeline_counters", "artp_debug_partner_table", "artp_roadmap_params_defaults",
     "artp_roadmap_build", "artp_roadmap_stats", "artp_roadmap_export", "artp_roadmap_solve", "artp_roadmap_destroy",
     "artp_roadmap_revalidate", "artp_roadmap_set_query", "artp_roadmap_simplify_path", "artp_roadmap_grow",
-    "artp_roadmap_solve_until", "artp_roadmap_set_density_map", "artp_preprocessed_reweight_dev",
+    "artp_roadmap_solve_until", "artp_roadmap_set_density_map", "artp_roadmap_solve_many",
+    "artp_preprocessed_reweight_dev",
     "artp_preprocess_params_defaults", "artp_preprocess_params_yaml", "artp_preprocess_map",
     "artp_preprocess_map_ex", "artp_preprocessed_change",
     "artp_preprocessed_get_layer", "artp_preprocessed_install", "artp_preprocessed_destroy",
@@ -222,6 +223,7 @@ def _load_path(LIB_PATH):
     L.artp_roadmap_grow.argtypes = [vp, C.c_uint64, vp]
     L.artp_roadmap_solve_until.argtypes = [vp, dbl, C.c_uint32, vp, sz, C.POINTER(sz), C.POINTER(dbl), vp]
     L.artp_roadmap_set_density_map.argtypes = [vp, vp, C.POINTER(PreprocessParams)]
+    L.artp_roadmap_solve_many.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp, sz, vp]
     L.artp_preprocessed_reweight_dev.argtypes = [vp, vp, C.POINTER(PreprocessParams), vp, sz, i32]
     L.artp_roadmap_destroy.argtypes = [vp]
     L.artp_roadmap_destroy.restype = None

@@ -7,8 +7,10 @@
 // SE3FromSE2Sampler / BatchMotionValidator::setZBounds exactly as for the per-state interfaces.
 #pragma once
 
+#include <algorithm>
 #include <array>
 #include <cstdint>
+#include <stdexcept>
 #include <vector>
 
 #include "art_planner/gpu_context.h"
@@ -155,6 +157,35 @@ class BatchPRM {
     throwOnError(gpu_->get(), artp_roadmap_set_query(rm_, s.data(), g.data()), "artp_roadmap_set_query");
   }
 
+  // Every goal's answer of setQuery(start, goal) + solve() from one lazy search (artp_roadmap_solve_many): status
+  // ARTP_GOAL_* per goal, cost (+inf without a path), path (empty without one; any output may be null).  The roadmap
+  // keeps its own query.  Returns the goals answered through the exact per-goal fallback.
+  size_t solveMany(const StateArray& start, const std::vector<StateArray>& goals, std::vector<int32_t>* status,
+                   std::vector<double>* cost, std::vector<std::vector<StateArray>>* paths = nullptr) {
+    if (!rm_) throw std::runtime_error("BatchPRM::solveMany before sampleGraph");
+    const size_t n = goals.size();
+    std::vector<int32_t> st(n);
+    std::vector<double> c(n);
+    std::vector<uint64_t> off(n + 1, 0);
+    uint64_t stats[4] = {0, 0, 0, 0};
+    std::vector<StateArray> buf(paths ? std::max<size_t>(64 * n, 1) : 0);
+    const double* g = n ? goals[0].data() : nullptr;
+    int rc = artp_roadmap_solve_many(rm_, start.data(), g, n, st.data(), c.data(), off.data(),
+                                     paths ? buf[0].data() : nullptr, buf.size(), stats);
+    if (rc == ARTP_ERR_CAPACITY && paths && off[n] > buf.size()) {  // longer paths than the buffer: once more with room
+      buf.resize(off[n]);
+      rc = artp_roadmap_solve_many(rm_, start.data(), g, n, st.data(), c.data(), off.data(), buf[0].data(), buf.size(),
+                                   stats);
+    }
+    throwOnError(gpu_->get(), rc, "artp_roadmap_solve_many");
+    if (paths) {
+      paths->assign(n, {});
+      for (size_t i = 0; i < n; ++i) (*paths)[i].assign(buf.begin() + off[i], buf.begin() + off[i + 1]);
+    }
+    if (status) status->swap(st);
+    if (cost) cost->swap(c);
+    return static_cast<size_t>(stats[3]);
+  }
   // Planner::getSolutionPath(simplify = true) (planner.cpp:266-280): deterministic batched shortcutting
   void simplify(std::vector<StateArray>* path, double* cost = nullptr) {
     if (!rm_ || path->empty()) return;

@@ -125,6 +125,42 @@ class Roadmap:
             self.ctx._chk(self.L.artp_roadmap_set_density_map(self.h, density_map.h, C.byref(density_map.params)),
                           "artp_roadmap_set_density_map")
 
+    # per-goal status of solve_many (include/artp_c.h: ARTP_GOAL_*)
+    GOAL_SOLVED, GOAL_INVALID, GOAL_UNREACHABLE, GOAL_TOO_MANY_REMOVALS = 0, 1, 2, 3
+
+    def solve_many(self, start, goals, paths=True, cap_states=None) -> dict:
+        """Every goal's answer of set_query(start, goal) + solve() from one lazy search (artp_roadmap_solve_many).
+        {"status": int32 [n], "cost": float64 [n] (+inf without a path), "paths": list of (m, 7) arrays (None where
+        there is no path; the whole list None with paths=False), "stats": {"rounds", "removed", "motions", "fallback"}}.
+        The roadmap keeps its own query."""
+        s = np.ascontiguousarray(start, np.float64).reshape(7)
+        g = np.ascontiguousarray(goals, np.float64).reshape(-1, 7)
+        n = g.shape[0]
+        status = np.empty(n, np.int32)
+        cost = np.empty(n, np.float64)
+        off = np.zeros(n + 1, np.uint64)
+        st = np.zeros(4, np.uint64)
+        cap = int(cap_states) if cap_states is not None else max(64 * n, 1)
+        buf = np.empty((cap, 7), np.float64) if paths else None
+
+        def call(buf, cap):
+            return self.L.artp_roadmap_solve_many(self.h, s.ctypes.data, g.ctypes.data if n else None, n,
+                                                  status.ctypes.data, cost.ctypes.data,
+                                                  off.ctypes.data if paths else None,
+                                                  buf.ctypes.data if paths else None, cap if paths else 0,
+                                                  st.ctypes.data)
+        rc = call(buf, cap)
+        if paths and rc == -5:  # ARTP_ERR_CAPACITY: once more with the reported size
+            cap = int(off[n])
+            buf = np.empty((cap, 7), np.float64)
+            rc = call(buf, cap)
+        self.ctx._chk(rc, "artp_roadmap_solve_many")
+        out_paths = None
+        if paths:
+            out_paths = [buf[int(off[i]):int(off[i + 1])].copy() if status[i] == 0 else None for i in range(n)]
+        return {"status": status, "cost": cost, "paths": out_paths,
+                "stats": {"rounds": int(st[0]), "removed": int(st[1]), "motions": int(st[2]), "fallback": int(st[3])}}
+
     def solve(self, cap_states=4096) -> Tuple[Optional[np.ndarray], float, int]:
         """(path n x 7 or None when start and goal are not connected, cost, lazy edge removals)."""
         path = np.empty((cap_states, 7), np.float64)

@@ -456,6 +456,23 @@ int artp_roadmap_set_density_map(artp_roadmap* rm, struct artp_preprocessed* pp,
                                  const struct artp_preprocess_params* params);
 void artp_roadmap_destroy(artp_roadmap* rm);
 
+/* ---- batched roadmap: one start, many goals ------------------------------------------------------------------------
+ * For every goal i the answer of artp_roadmap_set_query(rm, start, goal_i) + artp_roadmap_solve on the same roadmap,
+ * from ONE lazy search: the start is attached once, every goal to its own k nearest vertices, and each lazy round is one
+ * shortest-path search from the start, one batched motion check of all unresolved paths and the removal of the invalid
+ * edges.  Equality with the sequential answers assumes direction-symmetric motion verdicts (DESIGN.md "Many goals from
+ * one start").  status[i] / cost[i] (+inf without a path) for every goal; path_offsets (n_goals + 1 entries) and
+ * path_se3 (states of goal i at [path_offsets[i], path_offsets[i + 1]), start first, goal last) may be NULL (costs
+ * only).  ARTP_ERR_CAPACITY when path_se3 holds fewer than path_offsets[n_goals] states (statuses, costs and offsets are
+ * filled).  ARTP_ERR_INVALID_ARG, with nothing changed, when the start is not valid.  The roadmap keeps its query;
+ * lazy removals on roadmap edges persist and the motion verdicts are cached, as artp_roadmap_solve does.
+ * stats (may be NULL): [0] lazy rounds, [1] edges removed, [2] motions checked, [3] goals answered through the exact
+ * set_query + solve fallback (goals that would enter the start's neighbour list or take the start into theirs). */
+enum { ARTP_GOAL_SOLVED = 0, ARTP_GOAL_INVALID = 1, ARTP_GOAL_UNREACHABLE = 2, ARTP_GOAL_TOO_MANY_REMOVALS = 3 };
+int artp_roadmap_solve_many(artp_roadmap* rm, const double* start_se3, const double* goals_se3, size_t n_goals,
+                            int32_t* status, double* cost, uint64_t* path_offsets, double* path_se3,
+                            size_t cap_states, uint64_t stats[4]);
+
 /* ---- tree planners: rrt_star, inf_rrt_star, rrt_sharp (art_planner/src/planner.cpp:92-105) ---------------------------
  * OMPL's RRTstar::solve (and InformedRRTstar / RRTsharp) in batch-synchronous form: every batch of `batch` samples is
  * steered, checked, connected and rewired as ONE device batch per stage (DESIGN.md "Tree planners").  The tree's vertex 0
