@@ -9,8 +9,9 @@ with all inputs (map layers) resident in HBM before the timed region.  With N > 
 owns a disjoint sample-index range (weak scaling) and the accepted states are compacted and
 all-gathered over RCCL on a side stream (the planners need every accepted state on every rank).
 
-Prints ONE JSON line on rank 0 (see the repo prompt's bench contract) incl. `roofline` and
-`cpu_baseline`.  `roofline.pmc` is measured IN THIS RUN: bench.py re-launches itself (`--pmc-child`, a few
+A plain run sets up, warms up, times the steps (writing --dump-outputs) and prints the result line on rank 0.
+`--full` measures everything else after the headline and adds it to the line, incl. `roofline` and `cpu_baseline`.
+`roofline.pmc` is measured IN THAT RUN: bench.py re-launches itself (`--pmc-child`, a few
 sample+validate batches and nothing else) under `rocprofv3 --kernel-trace --pmc ...`, one pass per counter
 group (PMC is never combined with other trace domains), and derives HBM traffic, VALU / LDS busy and L2 hit rate
 per pipeline kernel.  If rocprofv3 is not usable it falls back to the committed profiles/pmc_r03.json -- only
@@ -110,7 +111,7 @@ def contract_line(full):
     out["value_edges"] = full.get("value_edges")
     out["value_edges_interp"] = full.get("value_edges_interp")
     out["unit_edges"] = full.get("unit_edges")
-    out["roofline"] = roof
+    out["roofline"] = roof if r else None      # a plain run has none
     out["cpu_baseline"] = cpu_s
     for k in ("valid_fraction", "label_hash_batch0", "device", "gather_error", "headline_includes_exchange", "detail"):
         if k in full:
@@ -133,8 +134,9 @@ def contract_line(full):
 
 
 def emit(full, stream=None, partial=False):
-    """BENCH_DETAIL line (everything) first, then the contract line LAST.  partial: a run with parts switched off (--no-pmc,
-    --skip-extras, --no-cpu-baseline: the profiler's and the scripts' runs) keeps its record apart from the default run's."""
+    """BENCH_DETAIL line (everything) first, then the contract line LAST.  partial: a plain run or a --full run with parts
+    switched off (--no-pmc, --skip-extras, --no-cpu-baseline: the profiler's and the scripts' runs) keeps its record apart
+    from the complete run's."""
     stream = stream or sys.stdout
     detail_path = None
     try:
@@ -819,13 +821,17 @@ def main():
                     help="REHEARSAL of the N > 1 code path on a one-GPU box, not a measurement: every rank uses GPU 0, "
                          "torch.distributed runs over gloo and the device group over the library $ARTP_RCCL_LIB names "
                          "(tests/cpp/loopback_rccl.cpp: RCCL refuses two ranks on one GPU); the line says so in `rehearsal`")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything besides the headline: the cold step, the exchange under other settings, the "
+                         "roofline and its PMC passes, edges, the C1-C5 / N1-N2 extras and the CPU baseline.  Without it a "
+                         "run sets up, warms up, times the steps, writes --dump-outputs and prints the result line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-gather", action="store_true")
-    ap.add_argument("--no-pmc", action="store_true", help="do not run the rocprofv3 PMC passes")
+    ap.add_argument("--no-pmc", action="store_true", help="--full without the rocprofv3 PMC passes")
     ap.add_argument("--pmc-child", nargs="?", const="states", default=None,
                     choices=["states", "check_motion", "sampler"], help=argparse.SUPPRESS)
     ap.add_argument("--pmc-reps", type=int, default=4, help=argparse.SUPPRESS)
-    ap.add_argument("--skip-extras", action="store_true", help="no edge / motion-cost measurements (profiling)")
+    ap.add_argument("--skip-extras", action="store_true", help="--full without the edge / motion-cost measurements (profiling)")
     ap.add_argument("--lanes", type=int, default=1,
                     help="parts of a step's batch validated side by side on as many streams of the context (1..4); "
                          "2 was worth 6 %% before the stream kernels balanced their own load, -0.7 %% on the final build")
@@ -1099,7 +1105,7 @@ def main():
     # ---- the cold step: the first batches after the device idled (a 10 Hz replanner never reaches the steady state the
     # headline region is measured in; profiles/r04_cold_probe.txt) -- HIP events around 4 batches after 2 s without work
     cold_ms = None
-    if not multi and not args.skip_extras:
+    if args.full and not multi and not args.skip_extras:
         time.sleep(2.0)
         e0c, e1c = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0c.record()
@@ -1120,9 +1126,10 @@ def main():
     no_exchange = None
     if multi:
         wd.partial = dict(base_line, value=None)   # whatever happens from here on, the line has its fixed fields
-    if multi and do_gather:
+    if args.full and multi and do_gather:
         # first the same K steps WITHOUT any exchange (only the barrier and the clock cross ranks): if the exchange hangs
-        # on this node, the watchdog's line still carries a measured aggregate -- flagged as such
+        # on this node, the watchdog's line still carries a measured aggregate -- flagged as such (a plain run's line
+        # then has no value, only the stage that hung)
         do_gather, keep = False, True
         k0 = max(3, min(K, 20))
         dt0 = timed_region(k0, "no_exchange")
@@ -1184,7 +1191,7 @@ def main():
     # without --force-dist a one-rank RCCL group is brought up AFTER the headline so that every N reports the block ----
     headline_gathers = do_gather
     dist_extras = None
-    if N == 1 and dist is None and not args.no_gather and not args.skip_extras:
+    if args.full and N == 1 and dist is None and not args.no_gather and not args.skip_extras:
         try:
             if args.exchange == "group":
                 # a one-member RCCL group of the C ABI (its own context: the map is replicated per member)
@@ -1205,8 +1212,6 @@ def main():
             do_gather = False
             dist = None
     if do_gather:
-        k2 = max(3, min(K, 20))
-        mat_cap = (cap if args.materialise < 0 else min(cap, args.materialise))
         dist_extras = {"world_size": world, "rccl_ranks_seen": rccl_ranks_seen,
                        "exchange": ("artp_group_* of the C ABI (librccl bound by libartp.so; one call per step)"
                                     if use_grp is not None else "torch.distributed " + dist.get_backend()),
@@ -1215,7 +1220,12 @@ def main():
                                      "$ARTP_RCCL_LIB = %s" % (world, os.environ.get("ARTP_RCCL_LIB"))) if args.rehearse_on_one_gpu else None,
                        "materialise_default": args.materialise, "no_exchange": no_exchange,
                        "per_rank_ms_per_step": per_rank_ms,
-                       "states_per_s_default": value if headline_gathers else N * S * k2 / timed_region(k2, "default")}
+                       "states_per_s_default": value if headline_gathers else None}
+    if do_gather and args.full:
+        k2 = max(3, min(K, 20))
+        mat_cap = (cap if args.materialise < 0 else min(cap, args.materialise))
+        if not headline_gathers:
+            dist_extras["states_per_s_default"] = N * S * k2 / timed_region(k2, "default")
         for name, mc in (("states_per_s_materialise_all", cap), ("states_per_s_materialise_none", 0)):
             mat_cap = mc
             dist_extras[name] = N * S * k2 / timed_region(k2, name[13:])
@@ -1312,6 +1322,39 @@ def main():
             if use_grp is not None:
                 use_grp.close()
             dist.destroy_process_group()
+        return
+
+    def report(out, partial):
+        """Rank 0's last act: the result lines (unless the watchdog is printing its own), then the final barrier."""
+        try:  # RCCL prints a version banner through C stdio; push it out BEFORE the JSON so that the line is the last one
+            import ctypes
+            ctypes.CDLL(None).fflush(None)
+        except Exception:
+            pass
+        if wd.fired:   # the watchdog is printing its own line: never two
+            time.sleep(5)
+            return
+        wd.done()
+        emit(out, partial=partial)
+        if dist is not None:
+            wd.line_printed = True
+            wd.stage("final barrier", args.watchdog)
+            try:
+                dist.barrier()
+                if use_grp is not None:
+                    use_grp.close()
+                dist.destroy_process_group()
+            except Exception:  # pragma: no cover
+                pass
+            wd.done()
+
+    if not args.full:
+        # a plain run ends with its headline: the fixed fields, the configuration and, with N > 1, how the exchange ran
+        out = dict(base_line, value=value, ms_per_step=dt / K * 1e3, device=ctx.arch, gather_error=gather_error)
+        out["config"] = dict(base_line["config"], lanes=lanes)
+        if multi:
+            out.update(headline_includes_exchange=bool(headline_gathers), distributed=dist_extras)
+        report(out, partial=True)
         return
     if multi:
         wd.stage("rank 0: roofline timing and report", max(args.watchdog, 600.0))
@@ -1924,27 +1967,7 @@ def main():
         "c4_800_defaults": c4, "per_call_latency": per_call, "distributed": dist_extras,
         "device": ctx.arch, "gather_error": gather_error,
     }
-    try:  # RCCL prints a version banner through C stdio; push it out BEFORE the JSON so that the line is the last one
-        import ctypes
-        ctypes.CDLL(None).fflush(None)
-    except Exception:
-        pass
-    if wd.fired:   # the watchdog is printing its own line: never two
-        time.sleep(5)
-        return
-    wd.done()
-    emit(out, partial=bool(args.no_pmc or args.skip_extras or args.no_cpu_baseline or N > 1))
-    if dist is not None:
-        wd.line_printed = True
-        wd.stage("final barrier", args.watchdog)
-        try:
-            dist.barrier()
-            if use_grp is not None:
-                use_grp.close()
-            dist.destroy_process_group()
-        except Exception:  # pragma: no cover
-            pass
-        wd.done()
+    report(out, partial=bool(args.no_pmc or args.skip_extras or args.no_cpu_baseline or N > 1))
 
 
 if __name__ == "__main__":

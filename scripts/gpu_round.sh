@@ -1,14 +1,15 @@
 #!/bin/bash
-# One GPU-box visit: the -m gpu suite, the default bench (incl. its live PMC passes), a kernel-trace profile.
+# One GPU-box visit: the -m gpu suite, the complete bench (--full, incl. its live PMC passes), a kernel-trace profile.
 #   gpurun --timeout 1500 -- 'bash scripts/gpu_round.sh <tag>'
 TAG=${1:-r02}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)   # the repository
 OUT=$GRAFT_REPO_ROOT/gpurun_out
 mkdir -p $OUT
 cd $GRAFT_REPO_ROOT
 timeout 900 python -m pytest tests -m gpu -q -p no:cacheprovider > $OUT/pytest_gpu_$TAG.log 2>&1
 echo "pytest rc $?" >> $OUT/pytest_gpu_$TAG.log
 tail -15 $OUT/pytest_gpu_$TAG.log
-timeout 600 python bench.py > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err
+timeout 600 python bench.py --full > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err
 echo "bench rc $?"
 python - <<PY
 import json
@@ -36,14 +37,14 @@ PY
 # the multi-GPU code path with ONE rank (torch.distributed / RCCL world size 1: communicator, bitmap all-gather, re-materialisation and
 # the edge exchange are real, the scaling is not): its contract line goes to profiles/ next to the default run's
 cd $GRAFT_REPO_ROOT
-timeout 600 python bench.py --gpus 1 --force-dist --skip-extras --no-pmc --no-cpu-baseline > $OUT/bench_force_dist_$TAG.json 2> $OUT/bench_force_dist_$TAG.err
+timeout 600 python bench.py --gpus 1 --force-dist --full --skip-extras --no-pmc --no-cpu-baseline > $OUT/bench_force_dist_$TAG.json 2> $OUT/bench_force_dist_$TAG.err
 echo "bench --force-dist rc $?"
 tail -1 $OUT/bench_force_dist_$TAG.json | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('force-dist value', d['value'], 'ms/step', d['ms_per_step'], 'distributed', json.dumps(d.get('distributed'))[:600], 'gather_error', d.get('gather_error'))" || tail -5 $OUT/bench_force_dist_$TAG.err
 mkdir -p $OUT/prof_$TAG
 cd /tmp && export TMPDIR=/tmp
 # --lanes 1: one batch at a time on one stream, the configuration of roofline.kernel_ms (rocprofv3 serialises the
 # kernels of concurrent streams anyway)
-rocprofv3 --kernel-trace --stats -d $OUT/prof_$TAG/trace -o trace -- python $GRAFT_REPO_ROOT/bench.py --lanes 1 --steps 3 --warmup 1 --no-cpu-baseline --no-pmc > $OUT/prof_$TAG/trace.log 2>&1
+rocprofv3 --kernel-trace --stats -d $OUT/prof_$TAG/trace -o trace -- python $ROOT/bench.py --lanes 1 --steps 3 --warmup 1 --full --no-cpu-baseline --no-pmc > $OUT/prof_$TAG/trace.log 2>&1
 python $GRAFT_REPO_ROOT/scripts/prof_summary.py $OUT/prof_$TAG > $OUT/prof_$TAG/summary.txt 2>&1
 # the headline workloads ALONE (bench.py --pmc-child <mode>: 4 batches and nothing else), so that a kernel's avg column
 # IS its per-launch time: states = fused sample + validate of 2^22 states; check_motion = 2^18 edges; sampler alone

@@ -3,10 +3,11 @@
 # (never combined with trace domains other than --kernel-trace).  Usage (via gpurun):
 #   bash scripts/prof_run.sh <tag>     -> gpurun_out/prof_<tag>/summary.txt
 TAG=${1:-r01}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)   # the repository
 OUT=$GRAFT_REPO_ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-CMD="python $GRAFT_REPO_ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline"
+CMD="python $ROOT/bench.py --steps 3 --warmup 1 --full --no-cpu-baseline"
 CMDP="$CMD --skip-extras"   # PMC passes: only the 2^22-state launches, so max/dispatch = the bench launch
 rocprofv3 --kernel-trace --stats -d $OUT/trace -o trace -- $CMD > $OUT/trace.log 2>&1
 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY -d $OUT/pmc1 -o pmc1 -- $CMDP > $OUT/pmc1.log 2>&1

@@ -1,6 +1,6 @@
 #!/bin/bash
-# bench.py without the extras / CPU baseline: headline value, per-step time and queue counts
-python $GRAFT_REPO_ROOT/bench.py --steps 10 --warmup 3 --no-cpu-baseline --skip-extras 2>&1 | tail -1 > /tmp/qb.json
+# bench.py --full without the extras / CPU baseline: headline value, per-step time and queue counts (its detail record)
+python "$(dirname "$0")/../bench.py" --steps 10 --warmup 3 --full --no-cpu-baseline --skip-extras 2>&1 | grep '^BENCH_DETAIL ' | cut -d' ' -f2- > /tmp/qb.json
 python - <<'PY'
 import json
 d = json.loads(open("/tmp/qb.json").read())

@@ -2,7 +2,7 @@
 # Tuning loop on the GPU box: headline step time + label hash, then per-kernel times of the pipeline launches
 # (kernel trace of the PMC child workload: only 2^22-state batches).  Optional: ARTP_LIB=<variant .so>
 cd $GRAFT_REPO_ROOT
-python bench.py --steps 20 --warmup 3 --no-cpu-baseline --skip-extras --no-pmc 2>/dev/null | tail -1 > /tmp/qb.json
+python bench.py --steps 20 --warmup 3 --full --no-cpu-baseline --skip-extras --no-pmc 2>/dev/null | grep '^BENCH_DETAIL ' | cut -d' ' -f2- > /tmp/qb.json
 python - <<'PY'
 import json
 d = json.loads(open("/tmp/qb.json").read())

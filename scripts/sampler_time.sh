@@ -1,2 +1,2 @@
 #!/bin/bash
-python $GRAFT_REPO_ROOT/bench.py --steps 5 --warmup 2 --no-cpu-baseline --skip-extras 2>&1 | grep "^{" | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('sampler_ms', d['sampler_ms_per_batch'], 'value', d['value'])"
+python "$(dirname "$0")/../bench.py" --steps 5 --warmup 2 --full --no-cpu-baseline --skip-extras 2>&1 | grep "^BENCH_DETAIL " | cut -d' ' -f2- | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('sampler_ms', d['sampler_ms_per_batch'], 'value', d['value'])"

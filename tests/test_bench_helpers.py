@@ -288,3 +288,23 @@ def test_watchdog_partial_line_is_short_too():
     part = {"metric": "m", "value": 1.0, "unit": "states/s", "n_gpus": 2, "distributed": {"exchange": "x" * 5000, "blob": ["y" * 100] * 100}}
     line = bench.contract_line(part)
     assert len(line) < 6144 and json.loads(line)["value"] == 1.0
+
+
+def test_a_plain_run_line_carries_the_contract_keys_and_nothing_measured_by_full():
+    """A run without --full reports its headline alone: the contract keys as a --full run states them, the configuration,
+    and null where --full would put the roofline and the CPU baseline."""
+    full = _canned_full_result()
+    plain = {k: full[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
+                                  "scaling", "vs_baseline", "dtype", "data", "config", "device", "gather_error")}
+    d = json.loads(bench.contract_line(plain))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup"):
+        assert d[k] == plain[k], k
+    assert d["roofline"] is None and d["cpu_baseline"] is None and d["headline"] is None
+    assert json.loads(bench.contract_line(full))["roofline"]["bound"] == "valu_issue"
+
+
+def test_full_is_an_option_of_the_bench():
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(common.ROOT, "bench.py"), "--help"], capture_output=True, text=True)
+    assert r.returncode == 0 and "--full" in r.stdout, r.stderr
