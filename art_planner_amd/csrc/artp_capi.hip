@@ -372,24 +372,42 @@ size_t lds_few(const artp_ctx* c) {
   return scratch_bytes_per_wave(c->caps_full) + 4 * scratch_bytes_per_wave(c->caps_foot_full);
 }
 
+// Opt-in to `bytes` of dynamic LDS (needed above 64 KiB).  The attribute belongs to the kernel on a device, not to a
+// context: it is only ever raised, so that a context on a coarser map cannot take it away from one on a finer map.
+int opt_in_lds(artp_ctx* c, const void* fn, size_t bytes) {
+  static std::mutex mu;
+  static std::vector<std::pair<std::pair<int, const void*>, int>> set;  // (device, kernel) -> bytes opted in
+  std::lock_guard<std::mutex> lock(mu);
+  int* have = nullptr;
+  for (auto& e : set)
+    if (e.first.first == c->device && e.first.second == fn) have = &e.second;
+  if (have && *have >= (int)bytes) return ARTP_OK;
+  HIP_TRY(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+  if (have)
+    *have = (int)bytes;
+  else
+    set.push_back({{c->device, fn}, (int)bytes});
+  return ARTP_OK;
+}
+
+#define ARTP_OPT_IN(c, kernel, bytes)                                                       \
+  do {                                                                                      \
+    const int _rc = opt_in_lds((c), reinterpret_cast<const void*>(kernel), (bytes));        \
+    if (_rc != ARTP_OK) return _rc;                                                         \
+  } while (0)
+
+// Every kernel's opt-in for the current map, the resident ones included (they are restarted after every map write).
 int set_kernel_lds(artp_ctx* c) {
-  // > 64 KiB of dynamic LDS needs the opt-in attribute
-  HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(check_boxes_kernel<1>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_full(c)));
-  HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(validate_states_kernel<1>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_full(c)));
-  HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(plane_stage_kernel<1>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_full(c)));
-  HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(validate_few_kernel),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_few(c)));
-  HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(check_motions_few_kernel),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_few(c)));
-  HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(resolve_boxes_kernel<ARTP_WAVES_PER_BLOCK, 64, 3>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_scan(c)));
-  HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(resolve_boxes_kernel<ARTP_WAVES_PER_BLOCK, 16, 1>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_feet(c)));
-  HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(resolve_boxes_kernel<ARTP_WAVES_PER_BLOCK, 64, 2>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_feet_wave(c)));
+  ARTP_OPT_IN(c, check_boxes_kernel<1>, lds_full(c));
+  ARTP_OPT_IN(c, validate_states_kernel<1>, lds_full(c));
+  ARTP_OPT_IN(c, plane_stage_kernel<1>, lds_full(c));
+  ARTP_OPT_IN(c, validate_few_kernel, lds_few(c));
+  ARTP_OPT_IN(c, check_motions_few_kernel, lds_few(c));
+  ARTP_OPT_IN(c, validate_service_kernel, lds_few(c));
+  ARTP_OPT_IN(c, check_motions_pool_kernel, lds_few(c));
+  ARTP_OPT_IN(c, (resolve_boxes_kernel<ARTP_WAVES_PER_BLOCK, 64, 3>), lds_scan(c));
+  ARTP_OPT_IN(c, (resolve_boxes_kernel<ARTP_WAVES_PER_BLOCK, 16, 1>), lds_feet(c));
+  ARTP_OPT_IN(c, (resolve_boxes_kernel<ARTP_WAVES_PER_BLOCK, 64, 2>), lds_feet_wave(c));
   return ARTP_OK;
 }
 
@@ -767,8 +785,6 @@ static int svc_start(artp_ctx* c) {
     c->svc_dev = static_cast<SvcMailbox*>(pd);
     HIP_TRY(c, hipStreamCreateWithFlags(&c->svc_stream, hipStreamNonBlocking));
     HIP_TRY(c, hipEventCreateWithFlags(&c->svc_after_map, hipEventDisableTiming));
-    HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(validate_service_kernel),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_few(c)));
   }
   // behind every map write already enqueued on the context's stream: the kernel captures the field arguments of NOW
   HIP_TRY(c, hipEventRecord(c->svc_after_map, c->stream));
@@ -2152,8 +2168,6 @@ static int pool_start(artp_ctx* c) {
     HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->pool_ctl), sizeof(PoolCtl)));
     HIP_TRY(c, hipStreamCreateWithFlags(&c->pool_stream, hipStreamNonBlocking));
     HIP_TRY(c, hipEventCreateWithFlags(&c->pool_after_map, hipEventDisableTiming));
-    HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(check_motions_pool_kernel),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_few(c)));
   }
   if (c->pool_seq >= 0xfffffff0u) {   // the request numbers wrap: every tag back to "never"
     reinterpret_cast<volatile uint64_t*>(&c->pool_mb->line[0])[0] = 0;

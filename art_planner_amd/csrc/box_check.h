@@ -692,6 +692,86 @@ __device__ __forceinline__ bool wave_plane_stage(const FieldDev& f, const BoxHF&
   return false;
 }
 
+// (g) for a window whose kept triangles overflow s.tri (a 64 x 64 window holds up to 7938): the same greedy grouping
+// as wave_plane_stage's, without a list.  Lane `lane` owns the window's triangles v = lane + 64 * sl in buffer order
+// (v = 2 * cell + DBC, cell = cx * cellsZ + cz: the order grp_compact_triangles writes the kept ones in) and keeps
+// its undecided kept ones as a 128-bit mask in registers; planes come from the LDS tile s.h.  The partner fast path of
+// wave_plane_stage only decides singleton groups early; the greedy pass alone gives the same answer.
+__device__ __forceinline__ bool wave_plane_stage_unlisted(const FieldDev& f, const BoxHF& b, const WaveScratch& s,
+                                                       int lane) {
+  const int numX = b.maxX - b.minX + 1;
+  const int cellsX = numX - 1, cellsZ = b.maxZ - b.minZ;
+  const int nv = 2 * cellsX * cellsZ;  // <= 2 * 63 * 63 = 7938 < 64 * 128
+  const int slots = (nv + 63) >> 6;
+  const float minO2 = b.aabb[2];
+  auto tri_plane = [&](int v, float pl[4], int& gx, int& gz, bool& up, bool& kept) {
+    up = !(v & 1);
+    const int c = v >> 1;
+    const int cx = c / cellsZ, cz = c - (c / cellsZ) * cellsZ;
+    const int e = cz * numX + cx;
+    const float hA = s.h[e], hB = s.h[e + 1], hC = s.h[e + numX], hD = s.h[e + numX + 1];
+    const bool fA = is_finite(hA), fB = is_finite(hB), fC = is_finite(hC), fD = is_finite(hD);
+    const bool cA = fA && hA > minO2, cB = fB && hB > minO2, cC = fC && hC > minO2, cD = fD && hD > minO2;
+    kept = up ? ((cA || cB || cC) && (fA && fB && fC)) : ((cB || cC || cD) && (fB && fC && fD));
+    const float xA = (float)(b.minX + cx) * f.sample_w, xB = (float)(b.minX + cx + 1) * f.sample_w;
+    const float zA = (float)(b.minZ + cz) * f.sample_d, zC = (float)(b.minZ + cz + 1) * f.sample_d;
+    if (up)
+      triangle_plane(xA, hA, zA, xB, hB, zA, xA, hC, zC, true, pl);
+    else
+      triangle_plane(xB, hD, zC, xB, hB, zA, xA, hC, zC, false, pl);
+    gx = b.minX + cx + (up ? 0 : 1);
+    gz = b.minZ + cz + (up ? 0 : 1);
+  };
+  unsigned long long open0 = 0ull, open1 = 0ull;  // bit sl (sl - 64): triangle lane + 64 * sl is kept and undecided
+  for (int sl = 0; sl < slots; ++sl) {
+    const int v = lane + 64 * sl;
+    if (v < nv) {
+      float pl[4];
+      int gx, gz;
+      bool up, kept;
+      tri_plane(v, pl, gx, gz, up, kept);
+      if (kept) {
+        if (sl < 64) open0 |= 1ull << sl;
+        else open1 |= 1ull << (sl - 64);
+      }
+    }
+  }
+  for (;;) {
+    const int mine = open0 ? lane + 64 * (__ffsll((long long)open0) - 1)
+                           : (open1 ? lane + 64 * (63 + __ffsll((long long)open1)) : 0x7fffffff);
+    const int k = wave_min_i(mine);
+    if (k == 0x7fffffff) break;
+    float base[4];  // base plane (wave-uniform: every lane computes it from broadcast LDS reads)
+    {
+      int gx, gz;
+      bool up, kept;
+      tri_plane(k, base, gx, gz, up, kept);
+    }
+    float cpos[4][3];
+    const int nc = box_plane_contacts(b, base[0], base[1], base[2], base[3], 10, cpos);
+    bool hit = false;
+    for (int sl = k >> 6; sl < slots; ++sl) {
+      const int v = lane + 64 * sl;
+      const unsigned long long bit = 1ull << (sl & 63);
+      if (v >= k && ((sl < 64 ? open0 : open1) & bit)) {
+        float pl[4];
+        int gx, gz;
+        bool up, kept;
+        tri_plane(v, pl, gx, gz, up, kept);
+        if (v == k || planes_eps_equal(base, pl)) {
+          if (sl < 64) open0 &= ~bit;
+          else open1 &= ~bit;
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+            if (i < nc) hit = hit || is_on_heightfield2(f, gx, gz, cpos[i][0], cpos[i][2], up);
+        }
+      }
+    }
+    if (__any(hit)) return true;
+  }
+  return false;
+}
+
 // (g), common case.  Every contact dCollideBoxPlane produces is a corner of the box (deepest corner,
 // its two neighbours along the smallest-projection sides, and the fourth corner of that face;
 // ode/ode/src/box.cpp:789-861), and a contact is only accepted by a group triangle whose CELL contains
@@ -956,7 +1036,8 @@ __device__ __forceinline__ int wave_plane_stage_corners(const FieldDev& f, const
 // The whole zone test in one call (used at the HeightMapBoxChecker boundary, artp_check_boxes).
 // Returns 0/1 like dCollide(box, field, 1, ...) != 0.  All 64 lanes must call it with identical
 // arguments; the result and *exit_code are wave-uniform.  Returns -1 when the window does not fit the
-// LDS scratch (the host sizes the scratch from the box diagonal).
+// LDS tile (the host sizes the tile from the box diagonal); a kept-triangle list longer than s.tri is
+// no error.
 __device__ __forceinline__ int wave_check_box(const FieldDev& f, const BoxHF& b, const WaveScratch& s,
                                               int lane, int* exit_code) {
   if (!b.on_field) {
@@ -977,13 +1058,14 @@ __device__ __forceinline__ int wave_check_box(const FieldDev& f, const BoxHF& b,
     return 1;
   }
   const int T = wave_compact_triangles<true>(b, s, lane);
-  if (T < 0) {
-    *exit_code = -1;
-    return -1;
-  }
-  if (T > 0) {
-    int r = s.cand ? wave_plane_stage_corners(f, b, s, lane, T) : 2;
-    if (r == 2) r = wave_plane_stage(f, b, s, lane, T) ? 1 : 0;
+  if (T != 0) {
+    int r;
+    if (T < 0) {  // more kept triangles than s.tri holds: the exact grouping without the list
+      r = wave_plane_stage_unlisted(f, b, s, lane) ? 1 : 0;
+    } else {
+      r = s.cand ? wave_plane_stage_corners(f, b, s, lane, T) : 2;
+      if (r == 2) r = wave_plane_stage(f, b, s, lane, T) ? 1 : 0;
+    }
     if (r) {
       *exit_code = EXIT_PLANE;
       return 1;

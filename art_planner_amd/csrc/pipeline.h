@@ -1316,11 +1316,11 @@ plane_stage_kernel(FieldDev fb, FieldDev ff, RobotDev rb, PipelineQueues q, uint
     else
       wave_scan_window(fb, b, s, lane, w);
     const int T = wave_compact_triangles<true>(b, s, lane);
-    if (T < 0) {
-      if (lane == 0) atomicExch(error_flag, 1);
-      continue;
-    }
-    const int result = (T > 0 && (foot ? wave_plane_stage(ff, b, s, lane, T) : wave_plane_stage(fb, b, s, lane, T))) ? 1 : 0;
+    int result;
+    if (T < 0)  // more kept triangles than the list holds: the same grouping without the list
+      result = (foot ? wave_plane_stage_unlisted(ff, b, s, lane) : wave_plane_stage_unlisted(fb, b, s, lane)) ? 1 : 0;
+    else
+      result = (T > 0 && (foot ? wave_plane_stage(ff, b, s, lane, T) : wave_plane_stage(fb, b, s, lane, T))) ? 1 : 0;
     if (lane == 0) {
       const bool ok = (rec.kind & 1u) ? (result != 0) : (result == 0);
       if (!ok) valid[rec.state] = 0;

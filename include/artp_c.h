@@ -37,7 +37,9 @@ typedef enum {
   ARTP_ERR_NO_DEVICE = -2,   /* no HIP device / wrong architecture: the product has NO CPU fallback */
   ARTP_ERR_HIP = -3,         /* a HIP runtime call failed; artp_last_error() has the text */
   ARTP_ERR_NO_MAP = -4,      /* a required layer was not uploaded (reference: hasMap() == false) */
-  ARTP_ERR_CAPACITY = -5,    /* box too large for the LDS window tile of this context */
+  ARTP_ERR_CAPACITY = -5,    /* layer upload: a box window wider than 64 samples (diagonal / spacing + 4 > 64) does not
+                                fit the LDS window tile; once a layer is accepted, no validity call returns it.  Also:
+                                an output buffer too small (the planner calls below) */
   ARTP_ERR_NO_WEIGHTS = -6,
   ARTP_ERR_TIMEOUT = -7,     /* artp_group_synchronize: a member's stream did not finish in time */
   ARTP_ERR_COMM = -8,        /* RCCL missing, or a communicator call failed (artp_group_last_error) */
