@@ -103,10 +103,11 @@ estimate_normals_kernel(const float* __restrict__ elev, PreGeom g, int n_r, int 
 // grey erosion (min) / dilation (max) with the footprint of getCircularKernel(size) (utils.cpp:114-119), anchored at
 // (size/2, size/2) like cv::erode / cv::dilate; replicated borders (for these footprints the same as OpenCV's
 // ignored border: clamping an offset moves it towards the anchor, where the footprint is at least as wide).
-// fp: one 64-bit row mask per footprint row (bit x of row y = kernel(y, x)), `fsize` rows (<= 64).
+// fp: one span per footprint row, fp[2 y] .. fp[2 y + 1] = the columns x with kernel(y, x) set (a row of a filled
+// midpoint circle, or of the 3 x 3 rectangle, is one span; x0 > x1: an empty row), `fsize` rows, any size.
 template <bool DILATE>
 __global__ void __launch_bounds__(256)
-morph_kernel(const float* __restrict__ in, int rows, int cols, int fsize, const unsigned long long* __restrict__ fp,
+morph_kernel(const float* __restrict__ in, int rows, int cols, int fsize, const int* __restrict__ fp,
              float* __restrict__ out) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= rows * cols) return;
@@ -114,10 +115,9 @@ morph_kernel(const float* __restrict__ in, int rows, int cols, int fsize, const 
   const int r = fsize / 2;
   float v = DILATE ? -INFINITY : INFINITY;
   for (int y = 0; y < fsize; ++y) {
-    const unsigned long long m = fp[y];
+    const int x0 = fp[2 * y], x1 = fp[2 * y + 1];
     const int jj = min(max(j + y - r, 0), cols - 1);
-    for (int x = 0; x < fsize; ++x) {
-      if (!((m >> x) & 1ull)) continue;
+    for (int x = x0; x <= x1; ++x) {
       const int ii = min(max(i + x - r, 0), rows - 1);
       const float xv = in[ii + (size_t)jj * rows];
       v = DILATE ? fmaxf(v, xv) : fminf(v, xv);
@@ -530,20 +530,24 @@ namespace {
 // every step the spans of rows centre -+ dy over [centre - dx, centre + dx] and of rows centre -+ dx over
 // [centre - dy, centre + dy]), clipped to the image -- restated from the published OpenCV source, which is not
 // installed here (parity UNPINNED).  size <= 0: cv::Mat() -> cv::erode / cv::dilate use a 3 x 3 rectangle.
-std::vector<unsigned long long> circular_footprint(int size, int* fsize) {
+std::vector<int> circular_footprint(int size, int* fsize) {
   if (size <= 0) {
     *fsize = 3;
-    return {7ull, 7ull, 7ull};
+    return {0, 2, 0, 2, 0, 2};
   }
-  if (size > 64) size = 64;
   *fsize = size;
-  std::vector<unsigned long long> rows(size, 0ull);
+  std::vector<int> spans(2 * (size_t)size);
+  for (int y = 0; y < size; ++y) {
+    spans[2 * y] = size;  // empty until a line covers it
+    spans[2 * y + 1] = -1;
+  }
   const int radius = size / 2, cx = radius, cy = radius;
-  auto hline = [&](int y, int x0, int x1) {
+  auto hline = [&](int y, int x0, int x1) {  // every line holds the centre column: the union of a row's lines is a span
     if (y < 0 || y >= size) return;
     x0 = x0 < 0 ? 0 : x0;
     x1 = x1 >= size ? size - 1 : x1;
-    for (int x = x0; x <= x1; ++x) rows[y] |= 1ull << x;
+    spans[2 * y] = std::min(spans[2 * y], x0);
+    spans[2 * y + 1] = std::max(spans[2 * y + 1], x1);
   };
   int err = 0, dx = radius, dy = 0, plus = 1, minus = (radius << 1) - 1;
   while (dx >= dy) {
@@ -559,7 +563,7 @@ std::vector<unsigned long long> circular_footprint(int size, int* fsize) {
     dx += mask;
     minus -= mask & 2;
   }
-  return rows;
+  return spans;
 }
 
 // The sampling distribution of a preprocessed map (planner.cpp:43-56): [inverse vertex density] * sample filter
@@ -741,38 +745,43 @@ int artp_preprocess_map_ex(artp_ctx* c, const artp_preprocess_inputs* in, const 
                        L(PRE_STD));
   }
   // setMaskedElevationAndTraversability                            basic.cpp:57-106
-  // footprints of this call's morphology sizes, uploaded once each (64 rows of 64 bits at most)
-  unsigned long long* d_fp = nullptr;
-  ok = ok && hipMalloc(reinterpret_cast<void**>(&d_fp), 16 * 64 * sizeof(unsigned long long)) == hipSuccess;
-  int fp_sizes[16], fp_fsize[16], n_fp = 0;
-  auto footprint = [&](int size, int* fsize) -> const unsigned long long* {
-    for (int q = 0; q < n_fp; ++q)
-      if (fp_sizes[q] == size) {
-        *fsize = fp_fsize[q];
-        return d_fp + 64 * q;
-      }
-    const std::vector<unsigned long long> rowsv = circular_footprint(size, fsize);
-    const int q = n_fp < 16 ? n_fp++ : 15;
-    fp_sizes[q] = size;
-    fp_fsize[q] = *fsize;
-    ok = ok && d_fp && hipMemcpyAsync(d_fp + 64 * q, rowsv.data(), rowsv.size() * 8, hipMemcpyHostToDevice, st) == hipSuccess &&
-         hipStreamSynchronize(st) == hipSuccess;  // rowsv dies with this call
-    return d_fp + 64 * q;
-  };
-  auto erode = [&](const float* in, int size, float* o) {
-    int fs = 0;
-    const unsigned long long* fp = footprint(size, &fs);
-    if (ok) hipLaunchKernelGGL(artp::morph_kernel<false>, grid, blk, 0, st, in, rows, cols, fs, fp, o);
-  };
-  auto dilate = [&](const float* in, int size, float* o) {
-    int fs = 0;
-    const unsigned long long* fp = footprint(size, &fs);
-    if (ok) hipLaunchKernelGGL(artp::morph_kernel<true>, grid, blk, 0, st, in, rows, cols, fs, fp, o);
-  };
+  // the footprints of this call's morphology sizes (basic.cpp:57-125), any size, uploaded together
   const int fh = (int)std::ceil(prm->foothold_size / res);
   const int margin = (int)std::ceil(2 * prm->foothold_margin / res);
   const int hole = (int)std::floor(prm->foothold_margin_max_hole_size / res);
   const int search = (int)std::ceil(2 * prm->foothold_margin_max_drop_search_radius / res);
+  const double total_reach = std::sqrt(c->params.reach_x * c->params.reach_x + c->params.reach_y * c->params.reach_y);
+  const double min_wall = std::min((c->params.torso_length - c->params.reach_x) * 0.5,
+                                   (c->params.torso_width - c->params.reach_y) * 0.5);
+  const int reach = (int)(total_reach / res), wall = (int)(min_wall / res);
+  const int fp_sizes[6] = {fh, margin, hole, search, reach, wall};
+  int fp_off[6], fp_fsize[6];
+  std::vector<int> fp_host;
+  for (int q = 0; q < 6; ++q) {
+    fp_off[q] = (int)fp_host.size();
+    const std::vector<int> spans = circular_footprint(fp_sizes[q], &fp_fsize[q]);
+    fp_host.insert(fp_host.end(), spans.begin(), spans.end());
+  }
+  int* d_fp = nullptr;
+  ok = ok && hipMalloc(reinterpret_cast<void**>(&d_fp), fp_host.size() * sizeof(int)) == hipSuccess &&
+       hipMemcpyAsync(d_fp, fp_host.data(), fp_host.size() * sizeof(int), hipMemcpyHostToDevice, st) == hipSuccess &&
+       hipStreamSynchronize(st) == hipSuccess;  // fp_host dies with this call
+  auto footprint = [&](int size, int* fsize) -> const int* {
+    int q = 0;
+    while (q < 5 && fp_sizes[q] != size) ++q;
+    *fsize = fp_fsize[q];
+    return d_fp + fp_off[q];
+  };
+  auto erode = [&](const float* in, int size, float* o) {
+    int fs = 0;
+    const int* fp = footprint(size, &fs);
+    if (ok) hipLaunchKernelGGL(artp::morph_kernel<false>, grid, blk, 0, st, in, rows, cols, fs, fp, o);
+  };
+  auto dilate = [&](const float* in, int size, float* o) {
+    int fs = 0;
+    const int* fp = footprint(size, &fs);
+    if (ok) hipLaunchKernelGGL(artp::morph_kernel<true>, grid, blk, 0, st, in, rows, cols, fs, fp, o);
+  };
   hipLaunchKernelGGL(artp::pre_threshold_kernel, grid, blk, 0, st, (const float*)L(PRE_TRAV), n,
                      prm->traversability_thres, L(PRE_TRAV_FILTER));
   dilate(L(PRE_TRAV_FILTER), hole, L(PRE_T0));
@@ -793,14 +802,9 @@ int artp_preprocess_map_ex(artp_ctx* c, const artp_preprocess_inputs* in, const 
   hipLaunchKernelGGL(artp::pre_masked_elevation_kernel, grid, blk, 0, st, (const float*)L(PRE_ELEV),
                      (const float*)L(PRE_SAFETY), n, L(PRE_MASKED));
   // setTraversabilityFilter                                        basic.cpp:110-125
-  {
-    const double total_reach = std::sqrt(c->params.reach_x * c->params.reach_x + c->params.reach_y * c->params.reach_y);
-    const double min_wall = std::min((c->params.torso_length - c->params.reach_x) * 0.5,
-                                     (c->params.torso_width - c->params.reach_y) * 0.5);
-    dilate(L(PRE_SAFETY), (int)(total_reach / res), L(PRE_T0));
-    erode(L(PRE_T0), (int)(total_reach / res), L(PRE_T1));
-    erode(L(PRE_T1), (int)(min_wall / res), L(PRE_SAMPLE_FILTER));
-  }
+  dilate(L(PRE_SAFETY), reach, L(PRE_T0));
+  erode(L(PRE_T0), reach, L(PRE_T1));
+  erode(L(PRE_T1), wall, L(PRE_SAMPLE_FILTER));
   // the sampling distribution (planner.cpp:43-56): [inverse vertex density] * sample filter [capped unknown share]
   double* d_verts = nullptr;
   if (prm->use_inverse_vertex_density && in->n_vertices > 0)

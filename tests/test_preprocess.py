@@ -6,6 +6,7 @@ import pytest
 
 import common
 import oracle_py as O
+import preprocess_restated as P
 
 pytestmark = pytest.mark.gpu
 
@@ -22,13 +23,12 @@ def test_device_preprocessing_matches_numpy_restatement(n, res, seed):
     for name in ("traversability_thresholded", "elevation_masked", "sample_probability"):
         assert np.array_equal(pp.layer(name), gm[name]), name
     assert np.array_equal(pp.layer("plane_fit_std_dev"), gm["plane_fit_std_dev"])
-    # float sums: same order of accumulation, numpy's norm / division differ in the last bits
-    for name in ("normal_x", "normal_y", "normal_z"):
-        assert np.abs(pp.layer(name) - gm[name]).max() < 2e-6, name
-    with np.errstate(invalid="ignore"):
-        d = np.abs(pp.layer("cum_prob") - gm["cum_prob"])
-        assert np.nanmax(d) < 1e-5 and np.array_equal(np.isnan(pp.layer("cum_prob")), np.isnan(gm["cum_prob"]))
-    assert np.abs(pp.layer("cum_prob_rowwise") - gm["cum_prob_rowwise"]).max() < 1e-5
+    # float sums: bit-equal to the kernel-order restatement (which is within 2e-6 of the oracle's np.cross / norm form,
+    # tests/test_preprocess_restated.py)
+    L = P.preprocess(gm["elevation"], gm.len_x, gm.len_y, gm.pos_x, gm.pos_y, traversability=gm["traversability"])
+    for name in ("normal_x", "normal_y", "normal_z", "cum_prob", "cum_prob_rowwise"):
+        assert np.array_equal(pp.layer(name), L[name], equal_nan=True), name
+    assert np.array_equal(np.isnan(pp.layer("cum_prob")), np.isnan(gm["cum_prob"]))
     pp.close()
     ctx.close()
 
@@ -141,9 +141,10 @@ def _blur_reflect101(a, taps):
 def test_sampling_distribution_processors():
     """The rest of Planner::setUpMapProcessors' new-map chain (planner.cpp:43-56): inverse vertex density
     (sample_density.cpp:12-43), base distribution, capped unknown share (probability_distribution.cpp:50-90),
-    CDF -- against a numpy restatement; and unknown_space_untraversable through the "observed" layer."""
+    CDF -- bit-equal to the kernel-order restatement (tests/preprocess_restated.py), the blur also against numpy's
+    reflect padding; and unknown_space_untraversable through the "observed" layer."""
     from art_planner_amd.context import Context
-    from synthetic import make_map, cumulative_distribution
+    from synthetic import make_map
     gm = make_map(160, 0.05, seed=12)
     ctx = Context(0, "yaml")
     rng = np.random.default_rng(4)
@@ -179,18 +180,17 @@ def test_sampling_distribution_processors():
     blurred = _blur_reflect101(cnt, _gauss_taps(k, radius / res))
     got_blur = pp.layer("n_samples")
     assert np.abs(got_blur - blurred).max() < 1e-5 * max(1.0, blurred.max())
+    # the kernel-order restatement of the whole sampling chain: bit-equal
+    L = P.preprocess(gm["elevation"], gm.len_x, gm.len_y, gm.pos_x, gm.pos_y, traversability=gm["traversability"],
+                     observed=observed, vertices=verts, prm=P.params("yaml", max_prob_unknown_samples=0.05),
+                     rob=P.robot("yaml", unknown_space_untraversable=0))
+    for name in ("n_samples", "sample_probability", "cum_prob", "cum_prob_rowwise"):
+        assert np.array_equal(pp.layer(name), L[name], equal_nan=True), name
     prob = (np.float32(got_blur.max()) - got_blur) * sf
     known, unknown = prob[observed > 0].astype(np.float64).sum(), prob[observed <= 0].astype(np.float64).sum()
     assert unknown / (known + unknown) > 0.05                            # the cap really acts
-    mult = np.where(observed > 0, (1 - 0.05) / known, 0.05 / unknown).astype(np.float32)
-    expect = prob * mult
     got = pp.layer("sample_probability")
-    assert np.abs(got - expect).max() <= 2e-6 * expect.max()
     assert abs(got[observed <= 0].astype(np.float64).sum() / got.astype(np.float64).sum() - 0.05) < 1e-5
-    cp, cr = cumulative_distribution(got)
-    with np.errstate(invalid="ignore"):
-        assert np.nanmax(np.abs(pp.layer("cum_prob") - cp)) < 1e-5
-    assert np.abs(pp.layer("cum_prob_rowwise") - cr).max() < 1e-5
     # unknown_space_untraversable (the default): unobserved cells lose their traversability
     pu = ctx.preprocess_map(gm["elevation"], gm.len_x, gm.len_y, gm.pos_x, gm.pos_y,
                             traversability=gm["traversability"], observed=observed)
