@@ -18,7 +18,8 @@ SYMBOLS = [
     "artp_upload_layer", "artp_update_layer_rect", "artp_update_layer_rects", "artp_check_boxes", "artp_check_boxes_dev",
     "artp_validate_states", "artp_validate_states_dev", "artp_set_persistent_latency", "artp_persistent_latency_stats", "artp_upload_sampler_layers",
     "artp_sample_states", "artp_sample_states_dev", "artp_sample_and_validate_dev",
-    "artp_sample_and_validate", "artp_check_motions_last_valid", "artp_check_motions_last_valid_dev",
+    "artp_sample_and_validate", "artp_reachability_map", "artp_reachability_map_dev", "artp_reachability_poses",
+    "artp_reachability_halo", "artp_check_motions_last_valid", "artp_check_motions_last_valid_dev",
     "artp_set_z_bounds", "artp_set_few_edges", "artp_set_edge_passes", "artp_cost_set_fc_path", "artp_check_motions", "artp_check_motions_dev", "artp_check_edges_interp",
     "artp_check_edges_interp_dev", "artp_compact_valid_dev", "artp_compact_valid_indices_dev", "artp_sample_states_at_dev",
     "artp_pack_edge_results_dev", "artp_cost_update_map_dev", "artp_pack_valid_bits_dev", "artp_indices_from_bits_dev",
@@ -165,6 +166,9 @@ def _load_path(LIB_PATH):
         getattr(L, name).argtypes = [vp, u64, u64, sz, vp]
     L.artp_sample_and_validate_dev.argtypes = [vp, u64, u64, sz, vp, vp, C.POINTER(sz)]
     L.artp_sample_and_validate.argtypes = [vp, u64, u64, sz, vp, vp, vp]
+    for name in ("artp_reachability_map", "artp_reachability_map_dev", "artp_reachability_poses"):
+        getattr(L, name).argtypes = [vp, i32, vp, vp]
+    L.artp_reachability_halo.argtypes = [vp, C.POINTER(i32)]
     L.artp_map_version.argtypes = [vp]
     L.artp_map_version.restype = C.c_uint64
     L.artp_set_z_bounds.argtypes = [vp, dbl, dbl]

@@ -72,6 +72,7 @@ class Context:
         layer = _f32F(layer)
         self._chk(self.L.artp_upload_layer(self.h, slot, layer.ctypes.data, layer.shape[0], layer.shape[1],
                                            len_x, len_y, pos_x, pos_y), "artp_upload_layer")
+        self._grid = layer.shape
 
     def update_layer_rect(self, slot, patch, row0, col0):
         patch = _f32F(patch)
@@ -188,6 +189,50 @@ class Context:
     def map_version(self):
         """artp_map_version: bumped by every call that changes a layer, its tables or the sampler tables."""
         return int(self.L.artp_map_version(self.h))
+
+    # ---- reachability maps (include/artp_c.h artp_reachability_*) ------------------------------------------------
+    def _reach_rect(self, rect):
+        """(rect array for the C call or None, nrows, ncols); rect = (row0, col0, nrows, ncols) or None = the whole map."""
+        if rect is None:
+            grid = getattr(self, "_grid", None)
+            if grid is None:
+                raise _capi.ArtpError("reachability: no map installed through this Context")
+            return None, int(grid[0]), int(grid[1])
+        r = np.ascontiguousarray(rect, np.int32).reshape(4)
+        return r, max(int(r[2]), 0), max(int(r[3]), 0)
+
+    def reachability_map(self, n_yaw=16, rect=None) -> np.ndarray:
+        """(nrows, ncols) uint32: bit k of [r, c] = isValid of the lattice pose of cell (row0 + r, col0 + c) at heading
+        bin k (yaw 2 pi k / n_yaw); 0 where the cell's height or normal is not finite."""
+        r, nr, nc = self._reach_rect(rect)
+        out = np.zeros(nr * nc, np.uint32)
+        self._chk(self.L.artp_reachability_map(self.h, int(n_yaw), r.ctypes.data if r is not None else None,
+                                               out.ctypes.data), "artp_reachability_map")
+        return out.reshape(nc, nr).T
+
+    def reachability_map_dev(self, mask_t, n_yaw, rect=None):
+        """The same into a device tensor of >= nrows * ncols 32-bit words (column-major), asynchronous on the current
+        stream."""
+        r, nr, nc = self._reach_rect(rect)
+        if mask_t.numel() * mask_t.element_size() < nr * nc * 4:
+            raise _capi.ArtpError("reachability_map_dev: mask_t holds fewer than nrows * ncols words")
+        self._chk(self.L.artp_reachability_map_dev(self.h, int(n_yaw), r.ctypes.data if r is not None else None,
+                                                   mask_t.data_ptr()), "artp_reachability_map_dev")
+
+    def reachability_poses(self, n_yaw, rect=None) -> np.ndarray:
+        """(nrows, ncols, n_yaw, 7) float64: the lattice poses (x y z qx qy qz qw); NaN z / quaternion where the cell's
+        height or normal is not finite."""
+        r, nr, nc = self._reach_rect(rect)
+        out = np.empty((nc, nr, max(int(n_yaw), 0), 7), np.float64)
+        self._chk(self.L.artp_reachability_poses(self.h, int(n_yaw), r.ctypes.data if r is not None else None,
+                                                 out.ctypes.data), "artp_reachability_poses")
+        return out.transpose(1, 0, 2, 3)
+
+    def reachability_halo(self) -> int:
+        """Cells around a rectangle written by update_layer_rect(s) whose masks may change (artp_reachability_halo)."""
+        v = C.c_int(0)
+        self._chk(self.L.artp_reachability_halo(self.h, C.byref(v)), "artp_reachability_halo")
+        return v.value
 
     def check_edges_interp(self, s1, s2):
         s1 = np.ascontiguousarray(s1, np.float64).reshape(-1, 7)
@@ -470,6 +515,7 @@ class PreprocessedMap:
 
     def install(self):
         self.ctx._chk(self.ctx.L.artp_preprocessed_install(self.ctx.h, self.h), "artp_preprocessed_install")
+        self.ctx._grid = tuple(self.shape)
 
     def reweight_dev(self, vertices_t=None, install_sampler=True):
         """Map::reApplyPreprocessing for the sampling distribution: inverse density of the given roadmap vertices

@@ -3667,6 +3667,7 @@ int artp_cost_get_features(artp_ctx* c, float* out, int* fh, int* fw) {
 #include "roadmap.h"
 #include "tree.h"
 #include "roadmap_many.h"
+#include "reach.h"
 #include "preprocess.h"
 #include "group.h"
 

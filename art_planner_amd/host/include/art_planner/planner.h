@@ -331,6 +331,32 @@ class Planner {
   // (GpuContext::setPersistentLatency; 17 -> 12 us and 33 -> 25 us per call on an MI355X).
   void setPersistentLatency(bool on) { gpu_->setPersistentLatency(on); }
 
+  // Where on the map the robot can stand, and at which headings (artp_reachability_map, include/artp_c.h): mask[r + c rows]
+  // bit k = isValid of the goal plan() would make of cell (r, c) at yaw 2 pi k / n_yaw.  Also stores the share of valid
+  // headings per cell as the float layer "reachability" of the planner's Map (and of its grid_map where it holds one), so
+  // a PlannerRos-shaped host can publish it with the map.
+  std::vector<uint32_t> computeReachability(unsigned n_yaw) {
+    std::lock_guard<std::mutex> lock(map_mutex_);
+    if (!map_) throw std::runtime_error("computeReachability: the planner does not have a map set");
+    const auto g = map_->getGeometry();
+    std::vector<uint32_t> mask(static_cast<size_t>(g.rows) * g.cols);
+    throwOnError(gpu_->get(), artp_reachability_map(gpu_->get(), static_cast<int>(n_yaw), nullptr, mask.data()),
+                 "artp_reachability_map");
+    std::vector<float> share(mask.size());
+    for (size_t i = 0; i < mask.size(); ++i)
+      share[i] = static_cast<float>(__builtin_popcount(mask[i])) / static_cast<float>(n_yaw);
+    map_->addLayer("reachability", share.data());
+#ifdef ARTP_HAVE_GRID_MAP
+    if (map_->hasGridMap()) {
+      auto& gm = map_->getMap();
+      gm.add("reachability", 0.0f);
+      float* d = gm.get("reachability").data();
+      for (size_t i = 0; i < share.size(); ++i) d[i] = share[i];
+    }
+#endif
+    return mask;
+  }
+
   void setSeed(uint64_t seed) {
     seed_ = seed;
     prm_->setSeed(seed);

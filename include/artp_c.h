@@ -184,6 +184,32 @@ int artp_sample_and_validate_dev(artp_ctx* ctx, uint64_t seed, uint64_t first_in
 int artp_sample_and_validate(artp_ctx* ctx, uint64_t seed, uint64_t first_index, size_t n, double* se3_out,
                              uint8_t* valid_out, uint64_t* map_version);
 
+/* ---- Reachability maps: isValid at every cell and heading of a rectangle of the map -----------------
+ * The lattice pose of cell (r, c) and heading bin k (0 <= k < n_yaw, 1 <= n_yaw <= 32) is the goal Planner::plan makes
+ * of that cell (planner.cpp:224-238, Map::get3DPoseFrom2D, map.cpp:77-90): x, y = the grid_map centre of the cell
+ * (the sampler's arithmetic), yaw_k = (2 pi / n_yaw) k, minus 2 pi where it exceeds pi (heading 0 is bin 0), z = the
+ * cell's height, roll = -atan2(n_b.y, n_b.z) and pitch = atan2(n_b.x, n_b.z) for the cell's normal turned into the yaw
+ * frame, the quaternion from setSO3FromRPY; no perturbation.  Heights and normals are the SAMPLER layers
+ * (artp_upload_sampler_layers / artp_preprocessed_install).  Bit k of mask[cell] = the isValid() label of that pose.
+ * A cell whose height or any normal component is not finite has mask 0 (its pose is never validated).
+ * rect = {row0, col0, nrows, ncols} of the installed map, NULL = the whole map.  mask is column-major nrows x ncols
+ * (grid_map's layout; cell (r, c) of the rectangle at r + c nrows).  ARTP_ERR_NO_MAP without both validity layers and
+ * the sampler layers; ARTP_ERR_INVALID_ARG for n_yaw outside [1, 32], an empty rect, one not inside the map or
+ * nrows * ncols * n_yaw >= 2^32.  The map is validated in chunks of at most 2^22 poses; artp_map_version is unchanged.
+ * Host form: synchronous.  _dev form: mask in device memory, asynchronous on the context's current stream / lane. */
+int artp_reachability_map(artp_ctx* ctx, int n_yaw, const int rect[4], uint32_t* mask);
+int artp_reachability_map_dev(artp_ctx* ctx, int n_yaw, const int rect[4], uint32_t* mask);
+/* The lattice poses themselves (x y z qx qy qz qw), host buffer of nrows * ncols * n_yaw states: pose index
+ * (r + c nrows) n_yaw + k, so the n_yaw headings of a cell are neighbours.  Cells that are not finite give x, y as above
+ * and NaN z and quaternion.  Needs the sampler layers only (ARTP_ERR_NO_MAP otherwise).  Synchronous. */
+int artp_reachability_poses(artp_ctx* ctx, int n_yaw, const int rect[4], double* se3_out);
+/* *cells = a conservative radius, in cells, of what a cell's mask depends on in the VALIDITY layers: the largest
+ * |box offset| + box half-diagonal of the robot (any attitude) over the map resolution, plus the window margin of
+ * "diagonal / spacing + 4".  After artp_update_layer_rect(s), which leave the sampler layers alone, recompute the changed
+ * rectangle grown by the halo (clipped to the map) and paste it into the old mask: the result equals a full recompute.
+ * artp_preprocessed_install (and artp_upload_sampler_layers) change heights and normals too: recompute the whole map. */
+int artp_reachability_halo(artp_ctx* ctx, int* cells);
+
 /* ---- ob::MotionValidator::checkMotion (OMPL DiscreteMotionValidator; call sites
  *      prm_motion_cost.cpp:652, lazy_prm_star_min_update.cpp:725), batched -----------------------
  * valid[i] = isValid(s2_i) && all interior states of the discretised segment are valid.
