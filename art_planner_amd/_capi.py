@@ -41,6 +41,7 @@ SYMBOLS = [
     "artp_inpaint_layer", "artp_cost_set_hole_filling", "artp_cost_set_external_query",
     "artp_cost_blob_bytes", "artp_cost_load_weights", "artp_cost_update_map_layer",
     "artp_cost_update_map", "artp_cost_query", "artp_cost_query_dev", "artp_cost_get_features", "artp_cost_debug_query_cells",
+    "artp_cost_debug_forms",
     "artp_cost_blob_bytes_version", "artp_cost_feature_channels", "artp_cost_get_features_c", "artp_cost_fc_path", "artp_set_r3_extent", "artp_telea_inpaint_u8",
     "artp_tree_params_defaults", "artp_tree_create", "artp_tree_grow", "artp_tree_solve", "artp_tree_stats",
     "artp_tree_export", "artp_tree_export_checked", "artp_tree_simplify_path", "artp_tree_stage_times",
@@ -266,6 +267,7 @@ def _load_path(LIB_PATH):
     L.artp_cost_query.argtypes = [vp, vp, sz, vp]
     L.artp_cost_query_dev.argtypes = [vp, vp, sz, vp]
     L.artp_cost_debug_query_cells.argtypes = [vp, vp, sz, vp, vp]
+    L.artp_cost_debug_forms.argtypes = [vp, C.POINTER(i32)]
     L.artp_cost_get_features.argtypes = [vp, vp, C.POINTER(i32), C.POINTER(i32)]
     L.artp_cost_blob_bytes_version.argtypes = [i32]
     L.artp_cost_blob_bytes_version.restype = sz

@@ -428,6 +428,13 @@ class Context:
                                                      cols.ctypes.data), "artp_cost_debug_query_cells")
         return rows, cols
 
+    def cost_debug_forms(self):
+        """{'net': 1/2, 'c345_tile': 12/16/18, 'conv15_rows': 6/8/9/10, 'conv15_threads': 256/512} -- the kernel forms the last
+        successful cost_update_map* ran (artp_cost_debug_forms; all zero before the first)."""
+        out = (C.c_int32 * 4)()
+        self._chk(self.L.artp_cost_debug_forms(self.h, out), "artp_cost_debug_forms")
+        return dict(zip(("net", "c345_tile", "conv15_rows", "conv15_threads"), (int(v) for v in out)))
+
     def cost_fc_path(self):
         """{'mfma': 0/1, 'selfcheck': -1/0/1, 'max_abs_diff': float} -- which kernel answers cost queries (artp_cost_fc_path)."""
         m, sc, d = C.c_int32(0), C.c_int32(0), C.c_float(0)

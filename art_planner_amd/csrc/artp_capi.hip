@@ -176,6 +176,7 @@ struct artp_ctx {
   size_t map_cap = 0;
   CostMapGeom cost_geom{};
   int feat_h = 0, feat_w = 0;
+  int cost_forms[4] = {0, 0, 0, 0};    // artp_cost_debug_forms: network, conv345 tile edge, 15 x 15 tile rows, its threads
   bool have_features = false;
   bool cost_fill_holes = false;        // artp_cost_set_hole_filling
   bool cost_fill_telea = false;   // artp_cost_set_hole_filling(ctx, 2): Telea's fast-marching fill (telea.h)
@@ -3170,6 +3171,7 @@ static int cost_run_cnn_full(artp_ctx* c, const float* d_map, int H, int W) {
   }
   half_t* Bf = c->d_act[1];
   hipStream_t st = c->stream;
+  bool wide = false;
   {
     auto k345 = conv345_kernel<T, true, true, 32, C>;
     const int lds = C345Cfg<T, 32, C>::LDS_BYTES;
@@ -3191,7 +3193,8 @@ static int cost_run_cnn_full(artp_ctx* c, const float* d_map, int H, int W) {
       return ARTP_OK;
     };
     const long tiles8 = (long)((wf + 15) / 16) * ((hf + 7) / 8);
-    const int rcl = tiles8 <= c->n_cus
+    wide = tiles8 <= c->n_cus;
+    const int rcl = wide
                         ? launch(conv_ksplit_kernel<15, 15, C, C, 4, true, 8, 8>, ConvKsplitCfg<15, 15, C, C, 4, true, 8, 8>::LDS_BYTES, 8, 512)
                         : launch(conv_ksplit_kernel<15, 15, C, C, 4, true, 6>, ConvKsplitCfg<15, 15, C, C, 4, true, 6>::LDS_BYTES, 6, 256);
     if (rcl != ARTP_OK) return rcl;
@@ -3199,6 +3202,10 @@ static int cost_run_cnn_full(artp_ctx* c, const float* d_map, int H, int W) {
   HIP_TRY(c, hipGetLastError());
   c->feat_h = hf;
   c->feat_w = wf;
+  c->cost_forms[0] = 2;
+  c->cost_forms[1] = T;
+  c->cost_forms[2] = wide ? 8 : 6;
+  c->cost_forms[3] = wide ? 512 : 256;
   return ARTP_OK;
 }
 
@@ -3233,6 +3240,7 @@ static int cost_run_cnn(artp_ctx* c, const float* d_map, int H, int W) {
   half_t* Bf = c->d_act[1];
   hipStream_t st = c->stream;
   bool fuse12 = false;
+  int forms[4] = {1, 0, 0, 256};   // -> c->cost_forms once the update has succeeded
   {
     // round 3: three launches.  (A) conv1 o conv2 + lrelu + pool2 straight from the f32 map -> A [hp][wpp][24];
     // (B) conv3 -> conv4 -> pool3 -> conv5 with LDS-resident halo tiles -> Bf [h5][w5][48]; (C) the 15 x 15 layer.
@@ -3283,6 +3291,7 @@ static int cost_run_cnn(artp_ctx* c, const float* d_map, int H, int W) {
 #ifdef ARTP_VARIANTS
     if (const char* ev = std::getenv("ARTP_C345_T")) t_best = std::atoi(ev);  // tuning
 #endif
+    forms[1] = t_best;
     int rcb;
     if (fuse12)
       rcb = t_best == 18   ? launch_b(conv345_kernel<18, true, true>, C345Cfg<18>::LDS_BYTES, 18)
@@ -3332,6 +3341,8 @@ static int cost_run_cnn(artp_ctx* c, const float* d_map, int H, int W) {
     };
     int rcl;
     const long tiles8 = (long)((wf + 15) / 16) * ((hf + 7) / 8);
+    forms[2] = tiles8 <= c->n_cus ? 8 : best;
+    forms[3] = tiles8 <= c->n_cus ? 512 : 256;
     if (tiles8 <= c->n_cus)
       rcl = launch(conv_ksplit_kernel<15, 15, 48, 48, 3, true, 8, 8>, ConvKsplitCfg<15, 15, 48, 48, 3, true, 8, 8>::LDS_BYTES, 8, 512);
     else if (best == 9)
@@ -3443,6 +3454,7 @@ static int cost_run_cnn(artp_ctx* c, const float* d_map, int H, int W) {
   HIP_TRY(c, hipGetLastError());
   c->feat_h = hf;
   c->feat_w = wf;
+  std::memcpy(c->cost_forms, forms, sizeof(forms));
   return ARTP_OK;
 }
 
@@ -3604,6 +3616,14 @@ int artp_cost_debug_query_cells(artp_ctx* c, const float* edges, size_t b, int32
   HIP_TRY(c, hipMemcpyAsync(rows_out, d_rc, b * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipMemcpyAsync(cols_out, d_rc + b, b * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return ARTP_OK;
+}
+
+// diagnostics: which kernel forms the last successful artp_cost_update_map* ran (the tests confirm their shape sweep with it)
+int artp_cost_debug_forms(artp_ctx* c, int out[4]) {
+  if (!c || !out) return ARTP_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> lock(c->mu);
+  std::memcpy(out, c->cost_forms, sizeof(c->cost_forms));
   return ARTP_OK;
 }
 

@@ -669,7 +669,9 @@ int artp_cost_fc_path(artp_ctx* ctx, int* mfma, int* selfcheck, float* max_abs_d
 int artp_cost_set_fc_path(artp_ctx* ctx, int mfma);
 /* CostPredictor.updateFeatures (predictor.py:28-36) + CostQuery.setMapParams (cost_query.py:26-35):
  * elev_xy is the server's map array [rows][cols] row-major with index a growing along world x and b
- * along world y (cost_query_server.py:66-74), holes already inpainted; (cx, cy) = map centre. */
+ * along world y (cost_query_server.py:66-74), holes already inpainted; (cx, cy) = map centre.
+ * A map smaller than 54 x 54 (a feature map under 3 x 3) is refused with ARTP_ERR_INVALID_ARG; a refused update changes
+ * nothing a query sees: the previous map's features and geometry keep answering (as does artp_cost_debug_forms). */
 int artp_cost_update_map(artp_ctx* ctx, const float* elev_xy, int rows, int cols, double res, double len_x,
                          double len_y, double cx, double cy);
 /* The same with the map array already in HBM (asynchronous on the context's stream). */
@@ -701,6 +703,10 @@ int artp_cost_set_external_query(artp_ctx* ctx, artp_cost_query_fn fn, void* use
  * (cost_query.py:54-55: float64 arithmetic, clamp to [1, shape - 2], .long()) -- computed by the device function the
  * cost kernels use; the tests compare it with the reference's own CostQuery.  Host buffers. */
 int artp_cost_debug_query_cells(artp_ctx* ctx, const float* edges, size_t b, int32_t* rows_out, int32_t* cols_out);
+/* diagnostics: the kernel forms the last successful artp_cost_update_map* ran: out[0] the network version (1 / 2),
+ * out[1] conv345_kernel's tile edge (12 / 16 / 18), out[2] the 15 x 15 layer's tile height in rows (6 / 8 / 9 / 10),
+ * out[3] its workgroup size in threads (256 / 512).  All zero before the first successful update. */
+int artp_cost_debug_forms(artp_ctx* ctx, int out[4]);
 /* diagnostics: feature map as float [fh][fw][48]; out may be NULL to query the size.  The light network's 48 channels
  * only: ARTP_ERR_INVALID_ARG while a version-2 network is loaded (use artp_cost_get_features_c). */
 int artp_cost_get_features(artp_ctx* ctx, float* out, int* fh, int* fw);
