@@ -161,7 +161,13 @@ int artp_validate_states_dev(artp_ctx* ctx, const double* se3, size_t n, uint8_t
 /* ---- ob::StateSampler::sampleUniform, batched
  *      (art_planner/src/sampler.cpp:56-131; SE3FromSE2Sampler) ----------------------------------
  * The seven layers the sampler reads (sampler.cpp:61-63,99-103; map.h:64-116), same geometry as the
- * validity layers.  cum_prob_rowwise = column 0 of "cum_prob_rowwise_hack" (rows floats). */
+ * validity layers.  cum_prob_rowwise = column 0 of "cum_prob_rowwise_hack" (rows floats).
+ * A row of cum_prob must be NaN-free or NaN THROUGHOUT.  That is all computeCumulativeProbabilityDistribution can
+ * produce (probability_distribution.cpp:28 divides every entry of a row by the row's sum, so a NaN comes from the
+ * divisor -- 0 / 0 of an all-zero row, or a NaN cell that poisons the sum -- and then fills the row; the processors
+ * only ever multiply finite factors into "sample_probability").  A row that is NaN throughout samples its last column,
+ * as the reference's scan does.  For a row that turns NaN part-way the pivot search is undefined: the scan would
+ * ignore the NaN entries, the search counts them (tests/test_sampler_probe.py pins the scan's answer). */
 int artp_upload_sampler_layers(artp_ctx* ctx, const float* cum_prob, const float* cum_prob_rowwise,
                                const float* elevation, const float* normal_x, const float* normal_y,
                                const float* normal_z, const float* plane_fit_std_dev, int rows,

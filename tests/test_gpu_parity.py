@@ -244,6 +244,8 @@ def test_c4_map_800_defaults_robot_labels():
     ctx.upload_map(gm)
     rob = O.robot("defaults")
     se3 = ctx.sample_states(7, 0, 1 << 18)
+    so, _ = O.OracleSampler(gm).sample(rob, 7, 0, 20000)           # 800 columns: the binary search over the pivots
+    assert np.abs(se3[:20000] - so).max() < 1e-12
     vg = ctx.validate_states(se3)
     om = O.OracleMap(gm)
     vo = common.oracle_states_valid_threaded(gm, rob, se3)           # all 2^18 labels
