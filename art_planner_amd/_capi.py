@@ -19,7 +19,8 @@ SYMBOLS = [
     "artp_validate_states", "artp_validate_states_dev", "artp_set_persistent_latency", "artp_persistent_latency_stats", "artp_upload_sampler_layers",
     "artp_sample_states", "artp_sample_states_dev", "artp_sample_and_validate_dev",
     "artp_sample_and_validate", "artp_reachability_map", "artp_reachability_map_dev", "artp_reachability_poses",
-    "artp_reachability_halo", "artp_check_motions_last_valid", "artp_check_motions_last_valid_dev",
+    "artp_reachability_halo", "artp_field_params_defaults", "artp_field_compute", "artp_field_dist", "artp_field_dist_dev",
+    "artp_field_path", "artp_field_edge_costs", "artp_field_stats", "artp_field_destroy", "artp_check_motions_last_valid", "artp_check_motions_last_valid_dev",
     "artp_set_z_bounds", "artp_set_few_edges", "artp_set_edge_passes", "artp_cost_set_fc_path", "artp_check_motions", "artp_check_motions_dev", "artp_check_edges_interp",
     "artp_check_edges_interp_dev", "artp_compact_valid_dev", "artp_compact_valid_indices_dev", "artp_sample_states_at_dev",
     "artp_pack_edge_results_dev", "artp_cost_update_map_dev", "artp_pack_valid_bits_dev", "artp_indices_from_bits_dev",
@@ -99,6 +100,17 @@ class RoadmapParams(C.Structure):  # artp_roadmap_params (include/artp_c.h)
                 ("construction", C.c_int32), ("max_query_edge_length", C.c_double)]
 
 
+class FieldParams(C.Structure):  # artp_field_params (include/artp_c.h)
+    _fields_ = [("objective", C.c_int32), ("plain_sweeps", C.c_int32), ("max_lon_vel", C.c_double),
+                ("max_lat_vel", C.c_double), ("max_ang_vel", C.c_double), ("inner_sweeps", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class FieldStats(C.Structure):  # artp_field_stats_t
+    _fields_ = [(n, C.c_uint64) for n in ("outer_rounds", "tile_launches", "reached_nodes", "plain_sweeps", "hop_rounds",
+                                          "hop_tile_launches", "nodes", "tiles")]
+
+
 class TreeParams(C.Structure):  # artp_tree_params (include/artp_c.h)
     _fields_ = [("seed", C.c_uint64), ("first_index", C.c_uint64), ("variant", C.c_int32), ("objective", C.c_int32),
                 ("max_lon_vel", C.c_double), ("max_lat_vel", C.c_double), ("max_ang_vel", C.c_double),
@@ -170,6 +182,16 @@ def _load_path(LIB_PATH):
     for name in ("artp_reachability_map", "artp_reachability_map_dev", "artp_reachability_poses"):
         getattr(L, name).argtypes = [vp, i32, vp, vp]
     L.artp_reachability_halo.argtypes = [vp, C.POINTER(i32)]
+    L.artp_field_params_defaults.argtypes = [C.POINTER(FieldParams)]
+    L.artp_field_params_defaults.restype = None
+    L.artp_field_compute.argtypes = [vp, C.POINTER(FieldParams), i32, vp, vp, i32, vp, sz, i32, C.POINTER(vp)]
+    L.artp_field_dist.argtypes = [vp, vp]
+    L.artp_field_dist_dev.argtypes = [vp, C.POINTER(vp)]
+    L.artp_field_path.argtypes = [vp, vp, vp, vp, sz, C.POINTER(sz), C.POINTER(dbl)]
+    L.artp_field_edge_costs.argtypes = [vp, vp, vp, sz, vp]
+    L.artp_field_stats.argtypes = [vp, C.POINTER(FieldStats)]
+    L.artp_field_destroy.argtypes = [vp]
+    L.artp_field_destroy.restype = None
     L.artp_map_version.argtypes = [vp]
     L.artp_map_version.restype = C.c_uint64
     L.artp_set_z_bounds.argtypes = [vp, dbl, dbl]

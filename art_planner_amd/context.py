@@ -234,6 +234,17 @@ class Context:
         self._chk(self.L.artp_reachability_halo(self.h, C.byref(v)), "artp_reachability_halo")
         return v.value
 
+    def cost_field(self, mask, n_yaw, sources, *, rect=None, reverse=False, objective=1, max_lon_vel=0.5,
+                   max_lat_vel=0.1, max_ang_vel=0.5, plain_sweeps=False, inner_sweeps=64):
+        """Cost-to-go field over the lattice of a reachability mask (artp_field_compute): mask = (nrows, ncols) uint32
+        array, or a device tensor in the layout reachability_map_dev writes; sources = (r, c, k) triples local to the
+        rectangle.  reverse=False: cost from the nearest source to every node; True: from every node to the nearest
+        source.  Returns a CostField (.dist(), .dist_dev(), .path(target), .stats(), .close())."""
+        from .field import CostField
+        return CostField(self, mask, n_yaw, sources, rect=rect, reverse=reverse, objective=objective,
+                         max_lon_vel=max_lon_vel, max_lat_vel=max_lat_vel, max_ang_vel=max_ang_vel,
+                         plain_sweeps=plain_sweeps, inner_sweeps=inner_sweeps)
+
     def check_edges_interp(self, s1, s2):
         s1 = np.ascontiguousarray(s1, np.float64).reshape(-1, 7)
         s2 = np.ascontiguousarray(s2, np.float64).reshape(-1, 7)

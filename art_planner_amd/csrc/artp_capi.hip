@@ -3688,6 +3688,7 @@ int artp_cost_get_features(artp_ctx* c, float* out, int* fh, int* fw) {
 #include "tree.h"
 #include "roadmap_many.h"
 #include "reach.h"
+#include "field.h"
 #include "preprocess.h"
 #include "group.h"
 

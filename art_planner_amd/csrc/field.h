@@ -1,0 +1,806 @@
+// field.h -- cost-to-go fields: shortest lattice costs from a set of source poses to every cell and heading of a
+// rectangle of the map (include/artp_c.h artp_field_*).
+//
+// Node (r, c, k) exists iff bit k of mask[r + c nrows] is set; node index = (r + c nrows) n_yaw + k, the pose order of
+// reach.h.  Ten moves per node (eight neighbouring cells at the same heading, two rotations).  dist[] is the least fixed
+// point of dist[v] = min(dist[u] + w(u, v)) with dist[source] = 0: fl(+) is monotone and the weights are non-negative, so
+// that fixed point is unique and does not depend on the order of the relaxations -- every kernel here relaxes IN PLACE and
+// reads neighbours that other lanes or workgroups may be lowering at the same time (an aligned 8-byte load or store is
+// not torn; any value read is the cost of a real path, so it can only delay the fixed point, never miss it).
+//   field_plain_kernel<PHASE>  one lane per node pulls from its <= 10 predecessors; one launch per sweep, a device counter
+//                              of waves that changed something: the stepping stone and the timing yardstick
+//   field_tile_kernel<PHASE>   a workgroup owns 16 x 16 cells x all headings: dist of the tile plus a one-cell halo, the
+//                              mask words, the heights and the weight table go to LDS (heading-major planes: the lanes of
+//                              a wave read neighbouring doubles); it sweeps inside LDS until nothing changes or
+//                              inner_sweeps are spent, writes its own cells back (plain vector stores; the halo is
+//                              read-only) and flags the neighbouring tiles whose halo it changed for the next launch.
+//                              A launch covers every tile; the ones nobody flagged leave at once.
+//   PHASE 0 = distances, PHASE 1 = hop counts: hops[v] = the fewest tight edges (dist[u] + w == dist[v] bit for bit)
+//                              from a source, the rule of roadmap_many_hops_kernel.  Objective 0's rotations cost 0, so
+//                              "tight" holds both ways there; a predecessor one hop closer cannot close a cycle.
+//   field_path_kernel          one wave walks from the target to a source: lane m tests move m, the first tight one wins
+// No launch waits for another workgroup and no kernel stays resident: the host reads one counter per outer round.
+#pragma once
+
+namespace artp {
+
+constexpr int FIELD_T = 16;                            // tile edge in cells
+constexpr int FIELD_HP = FIELD_T + 2;                  // with the halo
+constexpr int FIELD_PLANE = FIELD_HP * FIELD_HP;       // cells of a heading plane in LDS
+constexpr int FIELD_TAB = 8 * 32 + 8;                  // objective 1: w[m][k]; then (dx^2 + dy^2)[m] for objective 0
+constexpr uint32_t FIELD_NONE = 0xffffffffu;
+
+struct FieldGrid {
+  int nrows, ncols, n_yaw;
+  int tiles_r, tiles_c;
+  int objective, reverse;
+  uint32_t yaw_bits;  // the low n_yaw bits
+  double vlon;        // max_lon_vel
+  double wrot;        // cost of a rotation move
+};
+
+__host__ __device__ constexpr int field_dr(int m) { return m < 3 ? -1 : (m < 5 ? 0 : 1); }
+__host__ __device__ constexpr int field_dc(int m) { return (m == 0 || m == 3 || m == 5) ? -1 : ((m == 1 || m == 6) ? 0 : 1); }
+
+// cost of translation move m (0..7) from a cell of height ha to one of height hb at heading k; tab in LDS or global
+__device__ __forceinline__ double field_move_cost(const FieldGrid& G, const double* tab, int m, int k, float ha, float hb) {
+  if (G.objective == 0) {
+    const double dz = (double)hb - (double)ha;
+    return sqrt(tab[8 * 32 + m] + dz * dz) / G.vlon;
+  }
+  return tab[m * 32 + k];
+}
+
+// The edge between node v and its neighbour at offset j that the search pulls along: forward fields use the move
+// neighbour -> v (move 7 - j seen from the neighbour), reverse fields the move v -> neighbour (move j).
+__device__ __forceinline__ double field_pull_cost(const FieldGrid& G, const double* tab, int j, int k, float hv, float hn) {
+  return G.reverse ? field_move_cost(G, tab, j, k, hv, hn) : field_move_cost(G, tab, 7 - j, k, hn, hv);
+}
+
+__global__ void __launch_bounds__(256)
+field_heights_kernel(SamplerDev sm, MapGeom g, ReachRect rc, float* __restrict__ h) {
+  const uint32_t cell = blockIdx.x * blockDim.x + threadIdx.x;
+  if (cell >= (uint32_t)rc.nrows * (uint32_t)rc.ncols) return;
+  const int row = rc.row0 + (int)(cell % (uint32_t)rc.nrows);
+  const int col = rc.col0 + (int)(cell / (uint32_t)rc.nrows);
+  h[cell] = sm.cells[2 * ((size_t)row + (size_t)col * g.rows)].x;
+}
+
+__global__ void __launch_bounds__(256)
+field_init_kernel(size_t n, double* __restrict__ dist, uint32_t* __restrict__ hops) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  dist[i] = INFINITY;
+  hops[i] = FIELD_NONE;
+}
+
+// one lane per source: not a node of the mask -> *bad; else dist = 0, hops = 0
+__global__ void __launch_bounds__(64)
+field_sources_kernel(FieldGrid G, const uint32_t* __restrict__ mask, const int* __restrict__ src, int n_src,
+                     double* __restrict__ dist, uint32_t* __restrict__ hops, unsigned* __restrict__ bad) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_src) return;
+  const int r = src[3 * i], c = src[3 * i + 1], k = src[3 * i + 2];  // inside the rectangle: checked by the host
+  const size_t cell = (size_t)r + (size_t)c * G.nrows;
+  if (!((mask[cell] >> k) & 1u)) {
+    atomicAdd(bad, 1u);
+    return;
+  }
+  dist[cell * G.n_yaw + k] = 0.0;
+  hops[cell * G.n_yaw + k] = 0u;
+}
+
+// The first round's work: the tiles of the sources and the tiles around them (a source in a tile's border row is in
+// its neighbour's halo, and no tile "changed" it).
+__global__ void __launch_bounds__(64)
+field_seed_tiles_kernel(FieldGrid G, const int* __restrict__ src, int n_src, unsigned* __restrict__ active) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_src) return;
+  const int ti = src[3 * i] / FIELD_T, tj = src[3 * i + 1] / FIELD_T;
+  for (int dj = -1; dj <= 1; ++dj)
+    for (int di = -1; di <= 1; ++di)
+      if (ti + di >= 0 && ti + di < G.tiles_r && tj + dj >= 0 && tj + dj < G.tiles_c)
+        active[(ti + di) + (tj + dj) * G.tiles_r] = 1u;
+}
+
+template <int PHASE>
+__global__ void __launch_bounds__(256)
+field_plain_kernel(FieldGrid G, const uint32_t* __restrict__ mask, const float* __restrict__ h,
+                   const double* __restrict__ tab, double* dist, uint32_t* hops, unsigned* __restrict__ changed) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t n = (size_t)G.nrows * G.ncols * G.n_yaw;
+  bool ch = false;
+  if (i < n) {
+    const uint32_t cell = (uint32_t)(i / (uint32_t)G.n_yaw);
+    const int k = (int)(i - (size_t)cell * G.n_yaw);
+    const uint32_t mw = mask[cell] & G.yaw_bits;
+    if ((mw >> k) & 1u) {
+      const int r = (int)(cell % (uint32_t)G.nrows), c = (int)(cell / (uint32_t)G.nrows);
+      const float hv = h[cell];
+      double best = dist[i];
+      uint32_t hb = PHASE ? hops[i] : 0u;
+      const double old = best;
+      const uint32_t hold = hb;
+      if (!PHASE || best < INFINITY) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const int rr = r + field_dr(j), cc = c + field_dc(j);
+          if (rr < 0 || rr >= G.nrows || cc < 0 || cc >= G.ncols) continue;
+          const uint32_t nc = (uint32_t)rr + (uint32_t)cc * (uint32_t)G.nrows;
+          if (!((mask[nc] >> k) & 1u)) continue;
+          const size_t ni = (size_t)nc * G.n_yaw + k;
+          const double du = dist[ni];
+          if (PHASE == 0) {
+            if (!(du < best)) continue;  // w >= 0: no candidate below du
+            const double cand = du + field_pull_cost(G, tab, j, k, hv, h[nc]);
+            if (cand < best) best = cand;
+          } else {
+            const uint32_t hu = hops[ni];
+            if (hu == FIELD_NONE || hu + 1u >= hb) continue;
+            if (du + field_pull_cost(G, tab, j, k, hv, h[nc]) == old) hb = hu + 1u;
+          }
+        }
+        if (G.n_yaw > 1) {
+#pragma unroll
+          for (int s = 0; s < 2; ++s) {
+            const int kk = s == 0 ? (k + 1 == G.n_yaw ? 0 : k + 1) : (k == 0 ? G.n_yaw - 1 : k - 1);
+            if (!((mw >> kk) & 1u)) continue;
+            const size_t ni = (size_t)cell * G.n_yaw + kk;
+            const double du = dist[ni];
+            if (PHASE == 0) {
+              const double cand = du + G.wrot;
+              if (cand < best) best = cand;
+            } else {
+              const uint32_t hu = hops[ni];
+              if (hu == FIELD_NONE || hu + 1u >= hb) continue;
+              if (du + G.wrot == old) hb = hu + 1u;
+            }
+          }
+        }
+      }
+      if (PHASE == 0 && best < old) {
+        dist[i] = best;
+        ch = true;
+      }
+      if (PHASE == 1 && hb < hold) {
+        hops[i] = hb;
+        ch = true;
+      }
+    }
+  }
+  if (__any(ch) && (threadIdx.x & 63) == 0) atomicAdd(changed, 1u);
+}
+
+// LDS of a tile launch: n_yaw distance planes | the table | mask words | heights | (PHASE 1) n_yaw hop planes | 4 words
+inline size_t field_tile_lds(int n_yaw, int phase) {
+  return (size_t)n_yaw * FIELD_PLANE * 8 + FIELD_TAB * 8 + FIELD_PLANE * 4 * 2 + (phase ? (size_t)n_yaw * FIELD_PLANE * 4 : 0) +
+         16;
+}
+
+// counters[0] += flags set for the next round, counters[1] += tiles that ran (both cumulative over the call)
+template <int PHASE>
+__global__ void __launch_bounds__(256)
+field_tile_kernel(FieldGrid G, const uint32_t* __restrict__ mask, const float* __restrict__ h,
+                  const double* __restrict__ tabg, double* dist, uint32_t* hops, unsigned* act_cur, unsigned* act_nxt,
+                  unsigned* __restrict__ counters, int inner_max) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tile = blockIdx.x;
+  if (!act_cur[tile]) return;  // nobody writes act_cur in this launch before the barrier below: uniform
+  const int ny = G.n_yaw;
+  double* sd = reinterpret_cast<double*>(smem);
+  double* stab = sd + (size_t)ny * FIELD_PLANE;
+  uint32_t* smask = reinterpret_cast<uint32_t*>(stab + FIELD_TAB);
+  float* sh = reinterpret_cast<float*>(smask + FIELD_PLANE);
+  uint32_t* shop = reinterpret_cast<uint32_t*>(sh + FIELD_PLANE);
+  unsigned* sflag = reinterpret_cast<unsigned*>(shop + (PHASE ? (size_t)ny * FIELD_PLANE : 0));
+  const int tid = threadIdx.x;
+  const int ti = tile % G.tiles_r, tj = tile / G.tiles_r;
+  const int r0 = ti * FIELD_T, c0 = tj * FIELD_T;
+
+  for (int e = tid; e < FIELD_PLANE; e += 256) {
+    const int r = r0 + e % FIELD_HP - 1, c = c0 + e / FIELD_HP - 1;
+    const bool in = r >= 0 && r < G.nrows && c >= 0 && c < G.ncols;
+    const size_t cell = in ? (size_t)r + (size_t)c * G.nrows : 0;
+    smask[e] = in ? mask[cell] & G.yaw_bits : 0u;
+    sh[e] = in ? h[cell] : 0.f;
+  }
+  for (int e = tid; e < FIELD_PLANE * ny; e += 256) {
+    const int ci = e / ny, k = e - ci * ny;
+    const int r = r0 + ci % FIELD_HP - 1, c = c0 + ci / FIELD_HP - 1;
+    const bool in = r >= 0 && r < G.nrows && c >= 0 && c < G.ncols;
+    const size_t node = in ? ((size_t)r + (size_t)c * G.nrows) * ny + k : 0;
+    sd[k * FIELD_PLANE + ci] = in ? dist[node] : (double)INFINITY;
+    if (PHASE) shop[k * FIELD_PLANE + ci] = in ? hops[node] : FIELD_NONE;
+  }
+  for (int e = tid; e < FIELD_TAB; e += 256) stab[e] = tabg[e];
+  if (tid == 0) sflag[0] = 0u;
+  __syncthreads();
+
+  const int tr = tid & (FIELD_T - 1), tc = tid >> 4;
+  const int me = (tr + 1) + (tc + 1) * FIELD_HP;
+  const uint32_t mw = smask[me];
+  uint32_t nbm[8];
+  double w8[8];  // objective 0: the eight translation costs of this cell
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int nb = me + field_dr(j) + field_dc(j) * FIELD_HP;
+    nbm[j] = smask[nb];
+    w8[j] = G.objective == 0 ? field_pull_cost(G, stab, j, 0, sh[me], sh[nb]) : 0.0;
+  }
+  const int widx0 = G.reverse ? 0 : 7;  // objective 1: table row of offset j = reverse ? j : 7 - j
+  const int wsgn = G.reverse ? 1 : -1;
+  const double wrot = G.wrot;
+  unsigned border = 0u;  // bit 0 / 1: a cell of the first / last row changed, bit 2 / 3: first / last column, bit 4: any
+  const unsigned my_border = (tr == 0 ? 1u : 0u) | (tr == FIELD_T - 1 ? 2u : 0u) | (tc == 0 ? 4u : 0u) |
+                             (tc == FIELD_T - 1 ? 8u : 0u) | 16u;
+  int still = 0;
+  for (int sweep = 0; sweep < inner_max; ++sweep) {
+    bool ch = false;
+    for (int k = 0; k < ny; ++k) {
+      if (!((mw >> k) & 1u)) continue;
+      double* plane = sd + k * FIELD_PLANE;
+      const double old = plane[me];
+      const int kp = k + 1 == ny ? 0 : k + 1, km = k == 0 ? ny - 1 : k - 1;
+      if (PHASE == 0) {
+        double best = old;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          if (!((nbm[j] >> k) & 1u)) continue;
+          const double w = G.objective == 0 ? w8[j] : stab[(widx0 + wsgn * j) * 32 + k];
+          const double cand = plane[me + field_dr(j) + field_dc(j) * FIELD_HP] + w;
+          if (cand < best) best = cand;
+        }
+        if (ny > 1) {
+          if ((mw >> kp) & 1u) {
+            const double cand = sd[kp * FIELD_PLANE + me] + wrot;
+            if (cand < best) best = cand;
+          }
+          if ((mw >> km) & 1u) {
+            const double cand = sd[km * FIELD_PLANE + me] + wrot;
+            if (cand < best) best = cand;
+          }
+        }
+        if (best < old) {
+          plane[me] = best;
+          ch = true;
+        }
+      } else {
+        if (!(old < INFINITY)) continue;
+        uint32_t* hplane = shop + k * FIELD_PLANE;
+        const uint32_t hold = hplane[me];
+        uint32_t hb = hold;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          if (!((nbm[j] >> k) & 1u)) continue;
+          const int nb = me + field_dr(j) + field_dc(j) * FIELD_HP;
+          const uint32_t hu = hplane[nb];
+          if (hu == FIELD_NONE || hu + 1u >= hb) continue;
+          const double w = G.objective == 0 ? w8[j] : stab[(widx0 + wsgn * j) * 32 + k];
+          if (plane[nb] + w == old) hb = hu + 1u;
+        }
+        if (ny > 1) {
+          if ((mw >> kp) & 1u) {
+            const uint32_t hu = shop[kp * FIELD_PLANE + me];
+            if (hu != FIELD_NONE && hu + 1u < hb && sd[kp * FIELD_PLANE + me] + wrot == old) hb = hu + 1u;
+          }
+          if ((mw >> km) & 1u) {
+            const uint32_t hu = shop[km * FIELD_PLANE + me];
+            if (hu != FIELD_NONE && hu + 1u < hb && sd[km * FIELD_PLANE + me] + wrot == old) hb = hu + 1u;
+          }
+        }
+        if (hb < hold) {
+          hplane[me] = hb;
+          ch = true;
+        }
+      }
+    }
+    if (ch) border |= my_border;
+    still = __syncthreads_or(ch ? 1 : 0);
+    if (!still) break;
+  }
+  if (border) atomicOr(&sflag[0], border);
+  __syncthreads();
+  const unsigned bits = sflag[0];
+  if (bits) {  // own cells back; the halo belongs to the neighbours
+    for (int e = tid; e < FIELD_T * FIELD_T * ny; e += 256) {
+      const int ci = e / ny, k = e - ci * ny;
+      const int lr = ci & (FIELD_T - 1), lc = ci >> 4;
+      const int r = r0 + lr, c = c0 + lc;
+      if (r >= G.nrows || c >= G.ncols) continue;
+      const size_t node = ((size_t)r + (size_t)c * G.nrows) * ny + k;
+      const int li = k * FIELD_PLANE + (lr + 1) + (lc + 1) * FIELD_HP;
+      if (PHASE == 0) dist[node] = sd[li];
+      else hops[node] = shop[li];
+    }
+  }
+  if (tid < 8) {
+    const int dr = field_dr(tid), dc = field_dc(tid);
+    const int ni = ti + dr, nj = tj + dc;
+    const bool rows_ok = dr == 0 || (bits & (dr < 0 ? 1u : 2u));
+    const bool cols_ok = dc == 0 || (bits & (dc < 0 ? 4u : 8u));
+    if (rows_ok && cols_ok && (bits & 16u) && ni >= 0 && ni < G.tiles_r && nj >= 0 && nj < G.tiles_c) {
+      act_nxt[ni + nj * G.tiles_r] = 1u;
+      atomicAdd(&counters[0], 1u);
+    }
+  } else if (tid == 8) {
+    if (still) {  // inner_max spent while still changing: this tile goes on in the next round
+      act_nxt[tile] = 1u;
+      atomicAdd(&counters[0], 1u);
+    }
+    atomicAdd(&counters[1], 1u);
+    act_cur[tile] = 0u;  // every lane read it in front of the first barrier
+  }
+}
+
+__global__ void __launch_bounds__(256)
+field_count_kernel(size_t n, const double* __restrict__ dist, unsigned long long* __restrict__ count) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool fin = i < n && dist[i] < INFINITY;
+  const unsigned long long b = __ballot(fin);
+  if ((threadIdx.x & 63) == 0 && b) atomicAdd(count, (unsigned long long)__popcll(b));
+}
+
+// neighbour of (r, c, k) by move m (0..9); false when it leaves the rectangle (or n_yaw == 1 for a rotation)
+__device__ __forceinline__ bool field_neighbour(const FieldGrid& G, int r, int c, int k, int m, int* nr, int* nc, int* nk) {
+  if (m < 8) {
+    *nr = r + field_dr(m);
+    *nc = c + field_dc(m);
+    *nk = k;
+    return *nr >= 0 && *nr < G.nrows && *nc >= 0 && *nc < G.ncols;
+  }
+  *nr = r;
+  *nc = c;
+  *nk = m == 8 ? (k + 1 == G.n_yaw ? 0 : k + 1) : (k == 0 ? G.n_yaw - 1 : k - 1);
+  return G.n_yaw > 1;
+}
+
+// One wave.  out_n: the states of the path (0 = unreachable, -1 = no tight predecessor: cannot happen at the fixed point);
+// nodes (cap triples) in travel order when they fit.
+__global__ void __launch_bounds__(64)
+field_path_kernel(FieldGrid G, const uint32_t* __restrict__ mask, const float* __restrict__ h,
+                  const double* __restrict__ tab, const double* __restrict__ dist, const uint32_t* __restrict__ hops,
+                  int r, int c, int k, long long cap, int* __restrict__ nodes, long long* __restrict__ out_n,
+                  double* __restrict__ out_cost) {
+  const int lane = threadIdx.x;
+  size_t node = ((size_t)r + (size_t)c * G.nrows) * G.n_yaw + k;
+  uint32_t hv = hops[node];
+  double dv = dist[node];
+  if (lane == 0) *out_cost = dv;
+  if (hv == FIELD_NONE) {
+    if (lane == 0) *out_n = 0;
+    return;
+  }
+  const long long n = (long long)hv + 1;
+  if (lane == 0) *out_n = n;
+  if (n > cap) return;
+  for (long long step = 0;; ++step) {
+    if (lane == 0) {
+      int* o = nodes + 3 * (G.reverse ? step : n - 1 - step);
+      o[0] = r;
+      o[1] = c;
+      o[2] = k;
+    }
+    if (hv == 0u) break;
+    bool ok = false;
+    int nr = 0, nc = 0, nk = 0;
+    if (lane < 10 && field_neighbour(G, r, c, k, lane, &nr, &nc, &nk)) {
+      const size_t ncell = (size_t)nr + (size_t)nc * G.nrows;
+      if ((mask[ncell] >> nk) & 1u) {
+        const size_t ni = ncell * G.n_yaw + nk;
+        const double w = lane < 8 ? field_pull_cost(G, tab, lane, k, h[(size_t)r + (size_t)c * G.nrows], h[ncell]) : G.wrot;
+        ok = hops[ni] + 1u == hv && dist[ni] + w == dv;
+      }
+    }
+    const unsigned long long b = __ballot(ok);
+    if (!b) {
+      if (lane == 0) *out_n = -1;
+      return;
+    }
+    const int m = __ffsll((long long)b) - 1;
+    field_neighbour(G, r, c, k, m, &nr, &nc, &nk);
+    r = nr;
+    c = nc;
+    k = nk;
+    node = ((size_t)r + (size_t)c * G.nrows) * G.n_yaw + k;
+    dv = dist[node];
+    hv -= 1u;
+  }
+}
+
+// the lattice poses of n nodes (triples local to the rectangle)
+__global__ void __launch_bounds__(256)
+field_poses_kernel(SamplerDev sm, MapGeom g, ReachRect rc, const int* __restrict__ nodes, size_t n,
+                   double* __restrict__ se3) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t p = ((uint32_t)nodes[3 * i] + (uint32_t)nodes[3 * i + 1] * (uint32_t)rc.nrows) * (uint32_t)rc.n_yaw +
+                     (uint32_t)nodes[3 * i + 2];
+  double st[7];
+  reach_lattice_pose(sm, g, rc, p, st);
+#pragma unroll
+  for (int j = 0; j < 7; ++j) se3[7 * i + j] = st[j];
+}
+
+__global__ void __launch_bounds__(256)
+field_edge_cost_kernel(FieldGrid G, const float* __restrict__ h, const double* __restrict__ tab, const int* __restrict__ a,
+                       const int* __restrict__ b, size_t n, double* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int r = a[3 * i], c = a[3 * i + 1], k = a[3 * i + 2];
+  const int br = b[3 * i], bc = b[3 * i + 1], bk = b[3 * i + 2];
+  double w = __longlong_as_double(0x7ff8000000000000ll);
+  const bool in = r >= 0 && r < G.nrows && c >= 0 && c < G.ncols && k >= 0 && k < G.n_yaw && br >= 0 && br < G.nrows &&
+                  bc >= 0 && bc < G.ncols && bk >= 0 && bk < G.n_yaw;
+  if (in) {
+    for (int m = 0; m < 10; ++m) {
+      int nr, nc, nk;
+      if (!field_neighbour(G, r, c, k, m, &nr, &nc, &nk) || nr != br || nc != bc || nk != bk) continue;
+      w = m < 8 ? field_move_cost(G, tab, m, k, h[(size_t)r + (size_t)c * G.nrows], h[(size_t)br + (size_t)bc * G.nrows])
+                : G.wrot;
+      break;
+    }
+  }
+  out[i] = w;
+}
+
+}  // namespace artp
+
+struct artp_field {
+  artp_ctx* ctx = nullptr;
+  artp_field_params params{};
+  artp::ReachRect rect{};
+  artp::FieldGrid grid{};
+  MapGeom geom{};         // of the map the field was computed on (the poses of artp_field_path)
+  SamplerDev sampler{};
+  uint64_t map_version = 0;
+  size_t n_nodes = 0, n_cells = 0, n_tiles = 0;
+  double* d_dist = nullptr;
+  uint32_t* d_hops = nullptr;
+  uint32_t* d_mask = nullptr;
+  float* d_h = nullptr;
+  double* d_tab = nullptr;
+  unsigned* d_flags = nullptr;   // two flag arrays of n_tiles words | counters[4]
+  int* d_nodes = nullptr;        // sources at compute time; path / edge scratch later
+  size_t nodes_cap = 0;          // ints
+  double* d_out = nullptr;       // path poses / edge costs
+  size_t out_cap = 0;            // doubles
+  artp_field_stats_t stats{};
+};
+
+namespace {
+
+void field_free(artp_field* f) {
+  for (void* p : {(void*)f->d_dist, (void*)f->d_hops, (void*)f->d_mask, (void*)f->d_h, (void*)f->d_tab, (void*)f->d_flags,
+                  (void*)f->d_nodes, (void*)f->d_out})
+    if (p) (void)hipFree(p);
+  delete f;
+}
+
+int field_ensure_scratch(artp_field* f, size_t ints, size_t doubles) {
+  artp_ctx* c = f->ctx;
+  if (f->nodes_cap < ints) {
+    if (f->d_nodes) HIP_TRY(c, hipFree(f->d_nodes));
+    f->d_nodes = nullptr;
+    f->nodes_cap = 0;
+    HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&f->d_nodes), ints * sizeof(int)));
+    f->nodes_cap = ints;
+  }
+  if (f->out_cap < doubles) {
+    if (f->d_out) HIP_TRY(c, hipFree(f->d_out));
+    f->d_out = nullptr;
+    f->out_cap = 0;
+    HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&f->d_out), doubles * sizeof(double)));
+    f->out_cap = doubles;
+  }
+  return ARTP_OK;
+}
+
+// the (m, k) table of objective 1 and the squared planar step lengths of objective 0
+void field_make_table(const artp_field_params& p, const MapGeom& g, int n_yaw, double* tab) {
+  const double pi = 3.14159265358979323846;
+  for (int m = 0; m < 8; ++m) {
+    const double dx = g.res * (double)(-artp::field_dr(m)), dy = g.res * (double)(-artp::field_dc(m));
+    tab[8 * 32 + m] = dx * dx + dy * dy;
+    for (int k = 0; k < 32; ++k) {
+      double yaw = (2.0 * pi / (double)n_yaw) * (double)k;
+      if (yaw > pi) yaw -= 2.0 * pi;
+      const double lon = std::cos(yaw) * dx + std::sin(yaw) * dy;
+      const double lat = -std::sin(yaw) * dx + std::cos(yaw) * dy;
+      const double t_lon = std::fabs(lon) / p.max_lon_vel, t_lat = std::fabs(lat) / p.max_lat_vel;
+      tab[m * 32 + k] = k < n_yaw ? std::max(std::max(t_lon, t_lat), 0.0) : INFINITY;  // t_yaw = 0: a translation
+    }
+  }
+}
+
+// One search (PHASE 0: distances, 1: hop counts) to its fixed point.  The tiles of the sources are flagged in flags[0].
+template <int PHASE>
+int field_search(artp_field* f, const int* d_src, int n_src) {
+  artp_ctx* c = f->ctx;
+  hipStream_t st = c->stream;
+  const artp::FieldGrid& G = f->grid;
+  unsigned* counters = f->d_flags + 2 * f->n_tiles;
+  HIP_TRY(c, hipMemsetAsync(f->d_flags, 0, (2 * f->n_tiles + 4) * sizeof(unsigned), st));
+  const uint64_t cap = (uint64_t)f->n_nodes + 2;  // sweep s settles every node whose best path has <= s edges
+  if (f->params.plain_sweeps) {
+    const unsigned blocks = (unsigned)((f->n_nodes + 255) / 256);
+    unsigned seen = 0;
+    for (uint64_t sweeps = 0;;) {
+      if (sweeps > cap) {
+        c->last_error = "artp_field_compute: more sweeps than nodes";
+        return ARTP_ERR_CAPACITY;
+      }
+      for (int r = 0; r < 16; ++r)
+        hipLaunchKernelGGL(artp::field_plain_kernel<PHASE>, dim3(blocks), dim3(256), 0, st, G, (const uint32_t*)f->d_mask,
+                           (const float*)f->d_h, (const double*)f->d_tab, f->d_dist, f->d_hops, counters);
+      HIP_TRY(c, hipGetLastError());
+      sweeps += 16;
+      (PHASE ? f->stats.hop_rounds : f->stats.plain_sweeps) = sweeps;
+      unsigned now = 0;
+      HIP_TRY(c, hipMemcpyAsync(&now, counters, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+      HIP_TRY(c, hipStreamSynchronize(st));
+      if (now == seen) break;  // sixteen sweeps changed nothing
+      seen = now;
+    }
+    return ARTP_OK;
+  }
+  hipLaunchKernelGGL(artp::field_seed_tiles_kernel, dim3((unsigned)((n_src + 63) / 64)), dim3(64), 0, st, G, d_src, n_src,
+                     f->d_flags);
+  HIP_TRY(c, hipGetLastError());
+  const size_t lds = artp::field_tile_lds(G.n_yaw, PHASE);
+  // a workgroup may ask for more than 64 KB of dynamic LDS once the function says so (32 headings: 88 / 126 KB)
+  if (lds > 64 * 1024)
+    HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&artp::field_tile_kernel<PHASE>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  unsigned seen[2] = {0, 0};
+  for (uint64_t round = 0;; ++round) {
+    if (round > cap) {
+      c->last_error = "artp_field_compute: more outer rounds than nodes";
+      return ARTP_ERR_CAPACITY;
+    }
+    unsigned* cur = f->d_flags + (round & 1) * f->n_tiles;
+    unsigned* nxt = f->d_flags + ((round + 1) & 1) * f->n_tiles;
+    hipLaunchKernelGGL(artp::field_tile_kernel<PHASE>, dim3((unsigned)f->n_tiles), dim3(256), lds, st, G,
+                       (const uint32_t*)f->d_mask, (const float*)f->d_h, (const double*)f->d_tab, f->d_dist, f->d_hops, cur,
+                       nxt, counters, f->params.inner_sweeps);
+    HIP_TRY(c, hipGetLastError());
+    unsigned now[2] = {0, 0};
+    HIP_TRY(c, hipMemcpyAsync(now, counters, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    (PHASE ? f->stats.hop_rounds : f->stats.outer_rounds) = round + 1;
+    (PHASE ? f->stats.hop_tile_launches : f->stats.tile_launches) = now[1];
+    if (now[0] == seen[0]) break;  // nothing flagged for the next round
+    seen[0] = now[0];
+  }
+  return ARTP_OK;
+}
+
+int field_compute_impl(artp_ctx* c, artp_field* f, const uint32_t* mask, int mask_on_device, const int* sources,
+                       size_t n_sources) {
+  hipStream_t st = c->stream;
+  const artp::FieldGrid& G = f->grid;
+  HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&f->d_dist), f->n_nodes * sizeof(double)));
+  HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&f->d_hops), f->n_nodes * sizeof(uint32_t)));
+  HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&f->d_mask), f->n_cells * sizeof(uint32_t)));
+  HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&f->d_h), f->n_cells * sizeof(float)));
+  HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&f->d_tab), artp::FIELD_TAB * sizeof(double)));
+  HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&f->d_flags), (2 * f->n_tiles + 4) * sizeof(unsigned)));
+  int rc = field_ensure_scratch(f, 3 * n_sources, 8);
+  if (rc) return rc;
+  double tab[artp::FIELD_TAB];
+  field_make_table(f->params, f->geom, G.n_yaw, tab);
+  HIP_TRY(c, hipMemcpyAsync(f->d_mask, mask, f->n_cells * sizeof(uint32_t),
+                            mask_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemcpyAsync(f->d_tab, tab, sizeof(tab), hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemcpyAsync(f->d_nodes, sources, 3 * n_sources * sizeof(int), hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemsetAsync(f->d_flags, 0, (2 * f->n_tiles + 4) * sizeof(unsigned), st));
+  hipLaunchKernelGGL(artp::field_heights_kernel, dim3((unsigned)((f->n_cells + 255) / 256)), dim3(256), 0, st, f->sampler,
+                     f->geom, f->rect, f->d_h);
+  hipLaunchKernelGGL(artp::field_init_kernel, dim3((unsigned)((f->n_nodes + 255) / 256)), dim3(256), 0, st, f->n_nodes,
+                     f->d_dist, f->d_hops);
+  unsigned* counters = f->d_flags + 2 * f->n_tiles;
+  hipLaunchKernelGGL(artp::field_sources_kernel, dim3((unsigned)((n_sources + 63) / 64)), dim3(64), 0, st, G,
+                     (const uint32_t*)f->d_mask, (const int*)f->d_nodes, (int)n_sources, f->d_dist, f->d_hops, counters);
+  HIP_TRY(c, hipGetLastError());
+  unsigned bad = 0;
+  HIP_TRY(c, hipMemcpyAsync(&bad, counters, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipStreamSynchronize(st));  // the host copies of mask, table and sources are free from here
+  if (bad) {
+    c->last_error = "artp_field_compute: a source is not a node of the mask";
+    return ARTP_ERR_INVALID_ARG;
+  }
+  rc = field_search<0>(f, f->d_nodes, (int)n_sources);
+  if (rc) return rc;
+  rc = field_search<1>(f, f->d_nodes, (int)n_sources);
+  if (rc) return rc;
+  unsigned long long* d_count = reinterpret_cast<unsigned long long*>(f->d_out);
+  HIP_TRY(c, hipMemsetAsync(d_count, 0, sizeof(unsigned long long), st));
+  hipLaunchKernelGGL(artp::field_count_kernel, dim3((unsigned)((f->n_nodes + 255) / 256)), dim3(256), 0, st, f->n_nodes,
+                     (const double*)f->d_dist, d_count);
+  HIP_TRY(c, hipGetLastError());
+  unsigned long long reached = 0;
+  HIP_TRY(c, hipMemcpyAsync(&reached, d_count, sizeof(reached), hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipStreamSynchronize(st));
+  f->stats.reached_nodes = reached;
+  return ARTP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void artp_field_params_defaults(artp_field_params* p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof(*p));
+  p->objective = 0;       // use_directional_cost{false} (params.h:70)
+  p->plain_sweeps = 0;
+  p->max_lon_vel = 0.5;   // params.h:71-73
+  p->max_lat_vel = 0.1;
+  p->max_ang_vel = 0.5;
+  p->inner_sweeps = 64;
+}
+
+int artp_field_compute(artp_ctx* c, const artp_field_params* params, int n_yaw, const int* rect, const uint32_t* mask,
+                       int mask_on_device, const int* sources, size_t n_sources, int reverse, artp_field** out) {
+  if (out) *out = nullptr;
+  if (!c || !params || !mask || !sources || !out || n_sources < 1) return ARTP_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> lock(c->mu);
+  if (!reach_have_lattice(c)) return ARTP_ERR_NO_MAP;
+  artp::ReachRect r;
+  int rc = reach_resolve(c, n_yaw, rect, &r);
+  if (rc) return rc;
+  if (params->objective != 0 && params->objective != 1) {
+    c->last_error = "artp_field_compute: objective must be 0 or 1 (the learned objective has no lattice form)";
+    return ARTP_ERR_INVALID_ARG;
+  }
+  if (!(params->max_lon_vel > 0.0) || !(params->max_lat_vel > 0.0) || !(params->max_ang_vel > 0.0) ||
+      !std::isfinite(params->max_lon_vel) || !std::isfinite(params->max_lat_vel) || !std::isfinite(params->max_ang_vel) ||
+      params->inner_sweeps < 1 || n_sources > (size_t)1 << 24) {
+    c->last_error = "artp_field_compute: velocities must be positive and finite, inner_sweeps >= 1, n_sources <= 2^24";
+    return ARTP_ERR_INVALID_ARG;
+  }
+  for (size_t i = 0; i < n_sources; ++i) {
+    const int sr = sources[3 * i], sc = sources[3 * i + 1], sk = sources[3 * i + 2];
+    if (sr < 0 || sr >= r.nrows || sc < 0 || sc >= r.ncols || sk < 0 || sk >= n_yaw) {
+      c->last_error = "artp_field_compute: a source lies outside the rectangle or its heading outside [0, n_yaw)";
+      return ARTP_ERR_INVALID_ARG;
+    }
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  artp_field* f = new artp_field;
+  f->ctx = c;
+  f->params = *params;
+  f->rect = r;
+  f->geom = c->geom;
+  f->sampler = c->sampler;
+  f->map_version = c->map_version.load();
+  f->n_cells = (size_t)r.nrows * r.ncols;
+  f->n_nodes = f->n_cells * (size_t)n_yaw;
+  artp::FieldGrid& G = f->grid;
+  G.nrows = r.nrows;
+  G.ncols = r.ncols;
+  G.n_yaw = n_yaw;
+  G.tiles_r = (r.nrows + artp::FIELD_T - 1) / artp::FIELD_T;
+  G.tiles_c = (r.ncols + artp::FIELD_T - 1) / artp::FIELD_T;
+  G.objective = params->objective;
+  G.reverse = reverse ? 1 : 0;
+  G.yaw_bits = n_yaw == 32 ? 0xffffffffu : (1u << n_yaw) - 1u;
+  G.vlon = params->max_lon_vel;
+  G.wrot = params->objective == 0 ? 0.0 : (2.0 * 3.14159265358979323846 / (double)n_yaw) / params->max_ang_vel;
+  f->n_tiles = (size_t)G.tiles_r * G.tiles_c;
+  f->stats.nodes = f->n_nodes;
+  f->stats.tiles = f->n_tiles;
+  rc = field_compute_impl(c, f, mask, mask_on_device, sources, n_sources);
+  if (rc) {
+    (void)hipStreamSynchronize(c->stream);
+    field_free(f);
+    return rc;
+  }
+  *out = f;
+  return ARTP_OK;
+}
+
+int artp_field_dist(artp_field* f, double* dist_out) {
+  if (!f || !dist_out) return ARTP_ERR_INVALID_ARG;
+  artp_ctx* c = f->ctx;
+  std::lock_guard<std::recursive_mutex> lock(c->mu);
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipMemcpyAsync(dist_out, f->d_dist, f->n_nodes * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return ARTP_OK;
+}
+
+int artp_field_dist_dev(artp_field* f, const double** dist_dev) {
+  if (!f || !dist_dev) return ARTP_ERR_INVALID_ARG;
+  *dist_dev = f->d_dist;
+  return ARTP_OK;
+}
+
+int artp_field_path(artp_field* f, const int* target, int* nodes_out, double* se3_out, size_t cap, size_t* n,
+                    double* cost) {
+  if (n) *n = 0;
+  if (!f || !target || !n || !cost) return ARTP_ERR_INVALID_ARG;
+  artp_ctx* c = f->ctx;
+  std::lock_guard<std::recursive_mutex> lock(c->mu);
+  const artp::FieldGrid& G = f->grid;
+  if (target[0] < 0 || target[0] >= G.nrows || target[1] < 0 || target[1] >= G.ncols || target[2] < 0 ||
+      target[2] >= G.n_yaw) {
+    c->last_error = "artp_field_path: the target lies outside the rectangle or its heading outside [0, n_yaw)";
+    return ARTP_ERR_INVALID_ARG;
+  }
+  if (se3_out && f->map_version != c->map_version.load()) {
+    c->last_error = "artp_field_path: the map changed since the field was computed (its poses are gone)";
+    return ARTP_ERR_INVALID_ARG;
+  }
+  if (cap > f->n_nodes) cap = f->n_nodes;
+  HIP_TRY(c, hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  int rc = field_ensure_scratch(f, 3 * cap + 4, 7 * cap + 8);
+  if (rc) return rc;
+  // d_out: [0] = cost, [1] = the count (as long long), [8 ..] = the poses
+  long long* d_n = reinterpret_cast<long long*>(f->d_out + 1);
+  hipLaunchKernelGGL(artp::field_path_kernel, dim3(1), dim3(64), 0, st, G, (const uint32_t*)f->d_mask, (const float*)f->d_h,
+                     (const double*)f->d_tab, (const double*)f->d_dist, (const uint32_t*)f->d_hops, target[0], target[1],
+                     target[2], (long long)cap, f->d_nodes, d_n, f->d_out);
+  HIP_TRY(c, hipGetLastError());
+  double head[2];
+  HIP_TRY(c, hipMemcpyAsync(head, f->d_out, sizeof(head), hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipStreamSynchronize(st));
+  long long cnt;
+  std::memcpy(&cnt, &head[1], sizeof(cnt));
+  *cost = head[0];
+  if (cnt < 0) {
+    c->last_error = "artp_field_path: no tight predecessor (the field is not at its fixed point)";
+    return ARTP_ERR_HIP;
+  }
+  *n = (size_t)cnt;
+  if (cnt == 0) return ARTP_OK;  // unreachable: *cost = +inf
+  if ((size_t)cnt > cap) {
+    c->last_error = "artp_field_path: cap is smaller than the path";
+    return ARTP_ERR_CAPACITY;
+  }
+  if (nodes_out)
+    HIP_TRY(c, hipMemcpyAsync(nodes_out, f->d_nodes, 3 * (size_t)cnt * sizeof(int), hipMemcpyDeviceToHost, st));
+  if (se3_out) {
+    hipLaunchKernelGGL(artp::field_poses_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, f->sampler, f->geom,
+                       f->rect, (const int*)f->d_nodes, (size_t)cnt, f->d_out + 8);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(se3_out, f->d_out + 8, 7 * (size_t)cnt * sizeof(double), hipMemcpyDeviceToHost, st));
+  }
+  HIP_TRY(c, hipStreamSynchronize(st));
+  return ARTP_OK;
+}
+
+int artp_field_edge_costs(artp_field* f, const int* a, const int* b, size_t n, double* cost_out) {
+  if (!f || (n && (!a || !b || !cost_out))) return ARTP_ERR_INVALID_ARG;
+  if (!n) return ARTP_OK;
+  artp_ctx* c = f->ctx;
+  std::lock_guard<std::recursive_mutex> lock(c->mu);
+  HIP_TRY(c, hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  int rc = field_ensure_scratch(f, 6 * n, n + 8);
+  if (rc) return rc;
+  HIP_TRY(c, hipMemcpyAsync(f->d_nodes, a, 3 * n * sizeof(int), hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemcpyAsync(f->d_nodes + 3 * n, b, 3 * n * sizeof(int), hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(artp::field_edge_cost_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, f->grid,
+                     (const float*)f->d_h, (const double*)f->d_tab, (const int*)f->d_nodes, (const int*)(f->d_nodes + 3 * n),
+                     n, f->d_out);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(cost_out, f->d_out, n * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipStreamSynchronize(st));
+  return ARTP_OK;
+}
+
+int artp_field_stats(artp_field* f, artp_field_stats_t* out) {
+  if (!f || !out) return ARTP_ERR_INVALID_ARG;
+  *out = f->stats;
+  return ARTP_OK;
+}
+
+void artp_field_destroy(artp_field* f) {
+  if (!f) return;
+  (void)hipSetDevice(f->ctx->device);
+  (void)hipStreamSynchronize(f->ctx->stream);
+  field_free(f);
+}
+
+}  // extern "C"

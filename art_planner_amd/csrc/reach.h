@@ -27,6 +27,53 @@ __device__ __forceinline__ bool reach_cell_finite(const float4& ca) {
   return is_finite(ca.x) && is_finite(ca.y) && is_finite(ca.z) && is_finite(ca.w);
 }
 
+// The lattice pose (x y z qx qy qz qw) of pose index p of the rectangle; false (NaN z and quaternion) where the cell's
+// height or normal is not finite.
+__device__ __forceinline__ bool reach_lattice_pose(const SamplerDev& sm, const MapGeom& g, const ReachRect& rc, uint32_t p,
+                                                   double* st) {
+  const uint32_t cell = p / (uint32_t)rc.n_yaw;
+  const int k = (int)(p - cell * (uint32_t)rc.n_yaw);
+  const int row = rc.row0 + (int)(cell % (uint32_t)rc.nrows);
+  const int col = rc.col0 + (int)(cell / (uint32_t)rc.nrows);
+  // grid_map getPosition: (c + (L/2 - res/2)) + res * (-i), as the sampler computes it
+  const double px = (g.pos_x + (0.5 * g.len_x - 0.5 * g.res)) + g.res * (double)(-row);
+  const double py = (g.pos_y + (0.5 * g.len_y - 0.5 * g.res)) + g.res * (double)(-col);
+  // the n_yaw lanes of a cell read the same 32-byte record: one request for all of them
+  const float4 ca = sm.cells[2 * ((size_t)row + (size_t)col * g.rows)];
+  const bool fin = reach_cell_finite(ca);
+  const double pi = 3.14159265358979323846;
+  double yaw = (2.0 * pi / (double)rc.n_yaw) * (double)k;
+  if (yaw > pi) yaw -= 2.0 * pi;
+  st[0] = px;
+  st[1] = py;
+  {
+    const double nwx = (double)ca.y, nwy = (double)ca.z, nwz = (double)ca.w;
+    double sy2s, sy2c;
+    sincos_half_angle(0.5 * yaw, &sy2s, &sy2c);
+    // normal_b = Quaterniond(AngleAxisd(yaw, Z)).inverse() * normal_w: the plane rotation by -yaw (as sample_one)
+    const double cyaw = sy2c * sy2c - sy2s * sy2s, syaw = (sy2c + sy2c) * sy2s;
+    const double nbx = cyaw * nwx + syaw * nwy;
+    const double nby = cyaw * nwy - syaw * nwx;
+    const double nbz = nwz;
+    const double roll = -atan2(nby, nbz);
+    const double pitch = atan2(nbx, nbz);
+    double cr, cp, sr, sp;  // setSO3FromRPY (utils.h:101-115)
+    sincos_half_angle(roll * 0.5, &sr, &cr);
+    sincos_half_angle(pitch * 0.5, &sp, &cp);
+    const double cy = sy2c, sy = sy2s;
+    st[2] = (double)ca.x;
+    st[6] = cy * cp * cr + sy * sp * sr;
+    st[3] = cy * cp * sr - sy * sp * cr;
+    st[4] = sy * cp * sr + cy * sp * cr;
+    st[5] = sy * cp * cr - cy * sp * sr;
+  }
+  if (!fin) {
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    for (int j = 2; j < 7; ++j) st[j] = nan;
+  }
+  return fin;
+}
+
 // Poses first_pose .. first_pose + n - 1 of the rectangle; se3_out / recs (either may be null) point at pose first_pose.
 __global__ void __launch_bounds__(256)
 reach_poses_kernel(SamplerDev sm, MapGeom g, ReachRect rc, uint32_t first_pose, uint32_t n, double* __restrict__ se3_out,
@@ -39,48 +86,8 @@ reach_poses_kernel(SamplerDev sm, MapGeom g, ReachRect rc, uint32_t first_pose, 
   const uint32_t i = i0 + lane;
   float4 r[4];
   if (i < n) {
-    const uint32_t p = first_pose + i;
-    const uint32_t cell = p / (uint32_t)rc.n_yaw;
-    const int k = (int)(p - cell * (uint32_t)rc.n_yaw);
-    const int row = rc.row0 + (int)(cell % (uint32_t)rc.nrows);
-    const int col = rc.col0 + (int)(cell / (uint32_t)rc.nrows);
-    // grid_map getPosition: (c + (L/2 - res/2)) + res * (-i), as the sampler computes it
-    const double px = (g.pos_x + (0.5 * g.len_x - 0.5 * g.res)) + g.res * (double)(-row);
-    const double py = (g.pos_y + (0.5 * g.len_y - 0.5 * g.res)) + g.res * (double)(-col);
-    // the n_yaw lanes of a cell read the same 32-byte record: one request for all of them
-    const float4 ca = sm.cells[2 * ((size_t)row + (size_t)col * g.rows)];
-    const bool fin = reach_cell_finite(ca);
-    const double pi = 3.14159265358979323846;
-    double yaw = (2.0 * pi / (double)rc.n_yaw) * (double)k;
-    if (yaw > pi) yaw -= 2.0 * pi;
     double st[7];
-    st[0] = px;
-    st[1] = py;
-    {
-      const double nwx = (double)ca.y, nwy = (double)ca.z, nwz = (double)ca.w;
-      double sy2s, sy2c;
-      sincos_half_angle(0.5 * yaw, &sy2s, &sy2c);
-      // normal_b = Quaterniond(AngleAxisd(yaw, Z)).inverse() * normal_w: the plane rotation by -yaw (as sample_one)
-      const double cyaw = sy2c * sy2c - sy2s * sy2s, syaw = (sy2c + sy2c) * sy2s;
-      const double nbx = cyaw * nwx + syaw * nwy;
-      const double nby = cyaw * nwy - syaw * nwx;
-      const double nbz = nwz;
-      const double roll = -atan2(nby, nbz);
-      const double pitch = atan2(nbx, nbz);
-      double cr, cp, sr, sp;  // setSO3FromRPY (utils.h:101-115)
-      sincos_half_angle(roll * 0.5, &sr, &cr);
-      sincos_half_angle(pitch * 0.5, &sp, &cp);
-      const double cy = sy2c, sy = sy2s;
-      st[2] = (double)ca.x;
-      st[6] = cy * cp * cr + sy * sp * sr;
-      st[3] = cy * cp * sr - sy * sp * cr;
-      st[4] = sy * cp * sr + cy * sp * cr;
-      st[5] = sy * cp * cr - cy * sp * sr;
-    }
-    if (!fin) {
-      const double nan = __longlong_as_double(0x7ff8000000000000ll);
-      for (int j = 2; j < 7; ++j) st[j] = nan;
-    }
+    const bool fin = reach_lattice_pose(sm, g, rc, first_pose + i, st);
     if (se3_out) {
 #pragma unroll
       for (int j = 0; j < 7; ++j) sw[lane * 7 + j] = st[j];

@@ -13,6 +13,8 @@
 // caller (include/artp_c.h, N2): the elevation layer must be hole-free, "observed" marks the cells that were.
 #pragma once
 
+#include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdint>
 #include <iostream>
@@ -355,6 +357,49 @@ class Planner {
     }
 #endif
     return mask;
+  }
+
+  // Cost-to-go field over the lattice of a reachability mask (artp_field_compute, include/artp_c.h): the smallest
+  // PathLengthObjective cost of a lattice path from any source (r, c, k) to every cell and heading, or to the sources for
+  // reverse.  mask = what computeReachability(n_yaw) returned, or an edited copy (keep-out zones).  Returns dist,
+  // index (r + c rows) n_yaw + k, +inf where unreachable, and stores the smallest cost over the headings of each cell
+  // as the float layer "cost_to_go" of the planner's Map.  The objective and its velocities come from
+  // Params::objectives.custom_path_length.  Lattice paths are proposals: their moves' interior states are not checked.
+  std::vector<double> computeCostField(const std::vector<uint32_t>& mask, unsigned n_yaw,
+                                       const std::vector<std::array<int, 3>>& sources, bool reverse = false,
+                                       artp_field** keep = nullptr) {
+    std::lock_guard<std::mutex> lock(map_mutex_);
+    if (!map_) throw std::runtime_error("computeCostField: the planner does not have a map set");
+    const auto g = map_->getGeometry();
+    const size_t cells = static_cast<size_t>(g.rows) * g.cols;
+    if (mask.size() != cells) throw std::runtime_error("computeCostField: the mask does not have rows * cols words");
+    artp_field_params fp;
+    artp_field_params_defaults(&fp);
+    const auto& cpl = params_->objectives.custom_path_length;
+    fp.objective = cpl.use_directional_cost ? 1 : 0;
+    fp.max_lon_vel = cpl.max_lon_vel;
+    fp.max_lat_vel = cpl.max_lat_vel;
+    fp.max_ang_vel = cpl.max_ang_vel;
+    std::vector<int> src;
+    for (const auto& s : sources) src.insert(src.end(), s.begin(), s.end());
+    artp_field* f = nullptr;
+    throwOnError(gpu_->get(),
+                 artp_field_compute(gpu_->get(), &fp, static_cast<int>(n_yaw), nullptr, mask.data(), 0, src.data(),
+                                    sources.size(), reverse ? 1 : 0, &f),
+                 "artp_field_compute");
+    std::vector<double> dist(cells * n_yaw);
+    const int rc = artp_field_dist(f, dist.data());
+    if (rc || !keep) artp_field_destroy(f);
+    throwOnError(gpu_->get(), rc, "artp_field_dist");
+    if (keep) *keep = f;   // the caller asks paths of it (artp_field_path) and destroys it
+    std::vector<float> best(cells);
+    for (size_t i = 0; i < cells; ++i) {
+      double b = std::numeric_limits<double>::infinity();
+      for (unsigned k = 0; k < n_yaw; ++k) b = std::min(b, dist[i * n_yaw + k]);
+      best[i] = static_cast<float>(b);
+    }
+    map_->addLayer("cost_to_go", best.data());
+    return dist;
   }
 
   void setSeed(uint64_t seed) {

@@ -216,6 +216,70 @@ int artp_reachability_poses(artp_ctx* ctx, int n_yaw, const int rect[4], double*
  * artp_preprocessed_install (and artp_upload_sampler_layers) change heights and normals too: recompute the whole map. */
 int artp_reachability_halo(artp_ctx* ctx, int* cells);
 
+/* ---- Cost-to-go fields: shortest lattice costs from a pose to every cell and heading ------------------
+ * The graph: node (r, c, k) of the rectangle at n_yaw headings exists iff bit k of mask[r + c nrows]
+ * is set (the layout artp_reachability_map writes; the call never computes the mask: pass an edited or a synthetic one).
+ * Ten moves per node: m = 0..7 to the neighbouring cells, (dr, dc) = (-1,-1) (-1,0) (-1,1) (0,-1) (0,1) (1,-1) (1,0) (1,1),
+ * heading unchanged; m = 8: k -> (k + 1) mod n_yaw; m = 9: k -> (k - 1) mod n_yaw (none at n_yaw = 1).  An edge exists iff
+ * both ends exist inside the rectangle and its cost is finite.  Cost of a -> b = PathLengthObjective::motionCost(a, b) on
+ * the lattice's nominal numbers: dx = res (-dr), dy = res (-dc) (the difference of the two cell centres), dz = the
+ * difference of the sampler layer's cell heights widened to f64, yaw_k as artp_reachability_map defines it.
+ *   objective 0: sqrt((dx^2 + dy^2) + dz^2) / max_lon_vel, rotations cost 0
+ *   objective 1: max(|lon| / max_lon_vel, |lat| / max_lat_vel, yaw_dif / max_ang_vel), lon = cos(yaw_a) dx + sin(yaw_a) dy,
+ *                lat = -sin(yaw_a) dx + cos(yaw_a) dy, yaw_dif = 2 pi / n_yaw for a rotation and 0 for a translation
+ *   objective 2 (learned): ARTP_ERR_INVALID_ARG.
+ * dist[node] (f64): reverse = 0: the smallest cost of a lattice path from any source to the node; reverse = 1: from the
+ * node to any source.  A path's cost is the left fold ((0 + w1) + w2) + ... of its edge costs counted from the SOURCE end
+ * outwards, in both forms.  +inf where the node does not exist or cannot be reached.  The least fixed point of
+ * dist[v] = min(dist[u] + w) is unique (fl(+) is monotone, w >= 0), so both kernel forms give the same bits.
+ * An edge is usable when both end poses are valid: the interior states of a move are NOT checked.  A lattice path is a
+ * proposal; artp_field_path hands its states out as SE3 so that the caller can run them through artp_check_motions.
+ * Nodes (sources, target, nodes_out) are int triples (r, c, k), r and c LOCAL to the rectangle. */
+typedef struct artp_field artp_field;
+typedef struct artp_field_params {
+  int32_t objective;      /* 0 or 1, as artp_roadmap_params::objective */
+  int32_t plain_sweeps;   /* 0 = the tiled form (default); 1 = the plain form: one lane per node, one launch per sweep */
+  double max_lon_vel, max_lat_vel, max_ang_vel; /* params.h:71-73; the artp_roadmap_params defaults */
+  int32_t inner_sweeps;   /* tiled form: sweeps inside LDS per tile and outer round at most (default 64, >= 1) */
+  int32_t reserved;
+} artp_field_params;
+typedef struct artp_field_stats_t {
+  uint64_t outer_rounds;   /* tiled form: kernel launches of the distance search (one host read each) */
+  uint64_t tile_launches;  /* tiled form: tiles that ran in them (a launch skips the tiles nothing reached) */
+  uint64_t reached_nodes;  /* nodes with a finite distance */
+  uint64_t plain_sweeps;   /* plain form: launches of the distance search */
+  uint64_t hop_rounds;     /* launches of the hop-count search, either form */
+  uint64_t hop_tile_launches;
+  uint64_t nodes;          /* nrows * ncols * n_yaw */
+  uint64_t tiles;          /* tiles of the rectangle (16 x 16 cells each) */
+} artp_field_stats_t;
+void artp_field_params_defaults(artp_field_params* p);
+/* mask: nrows x ncols words, column-major, in host (mask_on_device = 0) or device memory (1); the field keeps a copy.
+ * sources: n_sources >= 1 triples.  Heights are the SAMPLER layers' (ARTP_ERR_NO_MAP without them; the validity layers are
+ * not needed).  ARTP_ERR_INVALID_ARG, with nothing computed: n_yaw or rect as artp_reachability_map refuses them, objective
+ * not 0 or 1, a velocity that is not positive, a source outside the rectangle or not a node of the mask.  Every launch is
+ * bounded; the host reads one count per outer round; more rounds than nodes + 2 (impossible at a fixed point search of
+ * non-negative weights) end the call with ARTP_ERR_CAPACITY.  Synchronous, on the context's current stream. */
+int artp_field_compute(artp_ctx* ctx, const artp_field_params* params, int n_yaw, const int rect[4], const uint32_t* mask,
+                       int mask_on_device, const int* sources, size_t n_sources, int reverse, artp_field** out);
+/* dist: nrows * ncols * n_yaw doubles, index (r + c nrows) n_yaw + k (the pose order of artp_reachability_poses).
+ * artp_field_dist copies to the host; artp_field_dist_dev gives the field's own device buffer (valid until destroy). */
+int artp_field_dist(artp_field* f, double* dist_out);
+int artp_field_dist_dev(artp_field* f, const double** dist_dev);
+/* Descent from the target along tight predecessors (dist[u] + w == dist[v] bit for bit, one hop closer by the hop count
+ * of fewest tight edges, the first such move in the order of the ten moves) to a source.  nodes_out (3 ints per state) and
+ * se3_out (7 doubles per state, the poses of artp_reachability_poses; either may be NULL) hold the states in TRAVEL
+ * order: source -> target for reverse = 0, target -> source for reverse = 1.  *cost = dist[target].  *n = 0, *cost = +inf
+ * and ARTP_OK when the target cannot be reached; ARTP_ERR_CAPACITY with *n = the states needed when cap is too small;
+ * ARTP_ERR_INVALID_ARG for a target outside the rectangle. */
+int artp_field_path(artp_field* f, const int target[3], int* nodes_out, double* se3_out, size_t cap, size_t* n,
+                    double* cost);
+/* cost_out[i] = the device's cost of the move a_i -> b_i (host arrays of n triples); NaN where b_i is not one of the ten
+ * moves from a_i or a node lies outside the rectangle.  The mask is not consulted. */
+int artp_field_edge_costs(artp_field* f, const int* a, const int* b, size_t n, double* cost_out);
+int artp_field_stats(artp_field* f, artp_field_stats_t* out);
+void artp_field_destroy(artp_field* f);
+
 /* ---- ob::MotionValidator::checkMotion (OMPL DiscreteMotionValidator; call sites
  *      prm_motion_cost.cpp:652, lazy_prm_star_min_update.cpp:725), batched -----------------------
  * valid[i] = isValid(s2_i) && all interior states of the discretised segment are valid.
