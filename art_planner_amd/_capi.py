@@ -20,7 +20,8 @@ SYMBOLS = [
     "artp_sample_states", "artp_sample_states_dev", "artp_sample_and_validate_dev",
     "artp_sample_and_validate", "artp_reachability_map", "artp_reachability_map_dev", "artp_reachability_poses",
     "artp_reachability_halo", "artp_field_params_defaults", "artp_field_compute", "artp_field_dist", "artp_field_dist_dev",
-    "artp_field_path", "artp_field_edge_costs", "artp_field_stats", "artp_field_destroy", "artp_check_motions_last_valid", "artp_check_motions_last_valid_dev",
+    "artp_field_path", "artp_field_edge_costs", "artp_field_stats", "artp_field_update", "artp_field_update_stats",
+    "artp_field_destroy", "artp_check_motions_last_valid", "artp_check_motions_last_valid_dev",
     "artp_set_z_bounds", "artp_set_few_edges", "artp_set_edge_passes", "artp_cost_set_fc_path", "artp_check_motions", "artp_check_motions_dev", "artp_check_edges_interp",
     "artp_check_edges_interp_dev", "artp_compact_valid_dev", "artp_compact_valid_indices_dev", "artp_sample_states_at_dev",
     "artp_pack_edge_results_dev", "artp_cost_update_map_dev", "artp_pack_valid_bits_dev", "artp_indices_from_bits_dev",
@@ -111,6 +112,12 @@ class FieldStats(C.Structure):  # artp_field_stats_t
                                           "hop_tile_launches", "nodes", "tiles")]
 
 
+class FieldUpdateStats(C.Structure):  # artp_field_update_stats_t
+    _fields_ = [(n, C.c_uint64) for n in ("changed_words", "removed_nodes", "added_nodes", "dead_nodes", "hop_dead_nodes",
+                                          "unsupport_rounds", "dist_rounds", "hop_rounds", "tile_launches",
+                                          "reached_nodes")]
+
+
 class TreeParams(C.Structure):  # artp_tree_params (include/artp_c.h)
     _fields_ = [("seed", C.c_uint64), ("first_index", C.c_uint64), ("variant", C.c_int32), ("objective", C.c_int32),
                 ("max_lon_vel", C.c_double), ("max_lat_vel", C.c_double), ("max_ang_vel", C.c_double),
@@ -190,6 +197,8 @@ def _load_path(LIB_PATH):
     L.artp_field_path.argtypes = [vp, vp, vp, vp, sz, C.POINTER(sz), C.POINTER(dbl)]
     L.artp_field_edge_costs.argtypes = [vp, vp, vp, sz, vp]
     L.artp_field_stats.argtypes = [vp, C.POINTER(FieldStats)]
+    L.artp_field_update.argtypes = [vp, vp, i32, vp, i32]
+    L.artp_field_update_stats.argtypes = [vp, C.POINTER(FieldUpdateStats)]
     L.artp_field_destroy.argtypes = [vp]
     L.artp_field_destroy.restype = None
     L.artp_map_version.argtypes = [vp]

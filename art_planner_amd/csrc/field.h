@@ -20,6 +20,16 @@
 //                              "tight" holds both ways there; a predecessor one hop closer cannot close a cycle.
 //   field_path_kernel          one wave walks from the target to a source: lane m tests move m, the first tight one wins
 // No launch waits for another workgroup and no kernel stays resident: the host reads one counter per outer round.
+//
+// artp_field_update brings a computed field to the fixed point of an edited mask in place:
+//   field_update_sources_kernel / field_diff_kernel   refuse a removed source; install the changed words (and heights),
+//                              clear the removed nodes, flag the tiles around every changed cell
+//   field_unsupport_*_kernel<PHASE>  a live node stays iff it is a source or a live neighbour u has dist[u] + w == dist[v]
+//                              AND hops[u] + 1 == hops[v]; the others go back to +inf / NONE (PHASE 0) or NONE (PHASE 1:
+//                              hop counts at the settled distances) until nobody dies.  "Dead" is that value itself, and
+//                              dying only spreads, so a stale neighbour read delays a death, never prevents it.
+//   field_hop_reset_kernel     hops = NONE where dist differs from the snapshot taken before the searches
+// and the two searches above run again from the flagged tiles instead of from the sources' tiles.
 #pragma once
 
 namespace artp {
@@ -443,6 +453,271 @@ field_edge_cost_kernel(FieldGrid G, const float* __restrict__ h, const double* _
   out[i] = w;
 }
 
+// ---- artp_field_update ------------------------------------------------------------------------------------------
+
+// the tiles that hold cell (r, c) or one of its eight neighbours: every tile that has the cell in its own cells or halo
+__device__ __forceinline__ void field_flag_around(const FieldGrid& G, int r, int c, unsigned* flags) {
+  for (int dc = -1; dc <= 1; ++dc)
+    for (int dr = -1; dr <= 1; ++dr) {
+      const int rr = r + dr, cc = c + dc;
+      if (rr >= 0 && rr < G.nrows && cc >= 0 && cc < G.ncols) flags[rr / FIELD_T + (cc / FIELD_T) * G.tiles_r] = 1u;
+    }
+}
+
+struct FieldSub {
+  int row0, col0, nrows, ncols;  // local to the field's rectangle
+};
+
+// cnt[0] changed words, [1] removed bits, [2] added bits, [3] changed heights, [4] sources that are no nodes any more
+
+// one lane per source against the merged mask (the new word inside sub, the field's own outside)
+__global__ void __launch_bounds__(64)
+field_update_sources_kernel(FieldGrid G, FieldSub sub, const uint32_t* __restrict__ mask, const uint32_t* __restrict__ new_mask,
+                            const int* __restrict__ src, int n_src, unsigned long long* __restrict__ cnt) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_src) return;
+  const int r = src[3 * i], c = src[3 * i + 1], k = src[3 * i + 2];
+  const size_t cell = (size_t)r + (size_t)c * G.nrows;
+  const bool in = r >= sub.row0 && r < sub.row0 + sub.nrows && c >= sub.col0 && c < sub.col0 + sub.ncols;
+  if (!(((in ? new_mask[cell] : mask[cell]) >> k) & 1u)) atomicAdd(&cnt[4], 1ull);
+}
+
+// One lane per cell of sub, after field_update_sources_kernel in the same stream: nothing is written when cnt[4] != 0.
+__global__ void __launch_bounds__(256)
+field_diff_kernel(FieldGrid G, FieldSub sub, const uint32_t* __restrict__ new_mask, uint32_t* __restrict__ mask, int refresh,
+                  SamplerDev sm, int map_rows, ReachRect rc, float* __restrict__ h, double* __restrict__ dist,
+                  uint32_t* __restrict__ hops, unsigned* acc, unsigned long long* cnt) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (uint32_t)sub.nrows * (uint32_t)sub.ncols) return;
+  if (cnt[4]) return;
+  const int r = sub.row0 + (int)(i % (uint32_t)sub.nrows), c = sub.col0 + (int)(i / (uint32_t)sub.nrows);
+  const size_t cell = (size_t)r + (size_t)c * G.nrows;
+  const uint32_t old = mask[cell], nw = new_mask[cell];
+  const uint32_t diff = (old ^ nw) & G.yaw_bits;
+  bool touched = diff != 0u;
+  if (old != nw) mask[cell] = nw;
+  if (diff) {
+    const uint32_t gone = old & diff;
+    for (int k = 0; k < G.n_yaw; ++k)
+      if ((gone >> k) & 1u) {
+        dist[cell * G.n_yaw + k] = INFINITY;
+        hops[cell * G.n_yaw + k] = FIELD_NONE;
+      }
+    atomicAdd(&cnt[0], 1ull);
+    if (gone) atomicAdd(&cnt[1], (unsigned long long)__popc(gone));
+    if (nw & diff) atomicAdd(&cnt[2], (unsigned long long)__popc(nw & diff));
+  }
+  if (refresh) {
+    const float hn = sm.cells[2 * ((size_t)(rc.row0 + r) + (size_t)(rc.col0 + c) * map_rows)].x;
+    if (__float_as_uint(hn) != __float_as_uint(h[cell])) {  // bit patterns: a NaN height stays "unchanged"
+      h[cell] = hn;
+      touched = true;
+      atomicAdd(&cnt[3], 1ull);
+    }
+  }
+  if (touched) field_flag_around(G, r, c, acc);
+}
+
+// counters[0] += waves in which a node died, counters[2] += nodes that died
+template <int PHASE>
+__global__ void __launch_bounds__(256)
+field_unsupport_plain_kernel(FieldGrid G, const uint32_t* __restrict__ mask, const float* __restrict__ h,
+                             const double* __restrict__ tab, double* dist, uint32_t* hops, unsigned* __restrict__ counters) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t n = (size_t)G.nrows * G.ncols * G.n_yaw;
+  bool die = false;
+  if (i < n) {
+    const uint32_t cell = (uint32_t)(i / (uint32_t)G.n_yaw);
+    const int k = (int)(i - (size_t)cell * G.n_yaw);
+    if ((mask[cell] >> k) & 1u) {
+      const double dv = dist[i];
+      const uint32_t hv = hops[i];
+      // live, and not a source (the only nodes at 0 hops)
+      if (dv < INFINITY && hv != 0u && !(PHASE == 1 && hv == FIELD_NONE)) {
+        bool sup = false;
+        if (hv != FIELD_NONE) {
+          const int r = (int)(cell % (uint32_t)G.nrows), c = (int)(cell / (uint32_t)G.nrows);
+          const float hc = h[cell];
+          for (int m = 0; m < 10 && !sup; ++m) {
+            int nr, nc, nk;
+            if (!field_neighbour(G, r, c, k, m, &nr, &nc, &nk)) continue;
+            const size_t ncell = (size_t)nr + (size_t)nc * G.nrows;
+            if (!((mask[ncell] >> nk) & 1u)) continue;
+            const size_t ni = ncell * G.n_yaw + nk;
+            const uint32_t hu = hops[ni];
+            if (hu == FIELD_NONE || hu + 1u != hv) continue;
+            const double w = m < 8 ? field_pull_cost(G, tab, m, k, hc, h[ncell]) : G.wrot;
+            sup = dist[ni] + w == dv;
+          }
+        }
+        if (!sup) {
+          if (PHASE == 0) dist[i] = INFINITY;
+          hops[i] = FIELD_NONE;
+          die = true;
+        }
+      }
+    }
+  }
+  const unsigned long long b = __ballot(die);
+  if (b && (threadIdx.x & 63) == 0) {
+    atomicAdd(&counters[0], 1u);
+    atomicAdd(&counters[2], (unsigned)__popcll(b));
+  }
+}
+
+// The protocol and the LDS layout of field_tile_kernel<1> (field_tile_lds(n_yaw, 1)); sflag[1] counts the tile's deaths.
+// counters[0] += flags set for the next round, [1] += tiles that ran, [2] += nodes that died.  acc collects, over the
+// whole update, the tiles whose own cells or halo changed: the seeds of the search that follows.
+template <int PHASE>
+__global__ void __launch_bounds__(256)
+field_unsupport_tile_kernel(FieldGrid G, const uint32_t* __restrict__ mask, const float* __restrict__ h,
+                            const double* __restrict__ tabg, double* dist, uint32_t* hops, unsigned* act_cur,
+                            unsigned* act_nxt, unsigned* acc, unsigned* __restrict__ counters, int inner_max) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tile = blockIdx.x;
+  if (!act_cur[tile]) return;  // uniform, as in field_tile_kernel
+  const int ny = G.n_yaw;
+  double* sd = reinterpret_cast<double*>(smem);
+  double* stab = sd + (size_t)ny * FIELD_PLANE;
+  uint32_t* smask = reinterpret_cast<uint32_t*>(stab + FIELD_TAB);
+  float* sh = reinterpret_cast<float*>(smask + FIELD_PLANE);
+  uint32_t* shop = reinterpret_cast<uint32_t*>(sh + FIELD_PLANE);
+  unsigned* sflag = reinterpret_cast<unsigned*>(shop + (size_t)ny * FIELD_PLANE);
+  const int tid = threadIdx.x;
+  const int ti = tile % G.tiles_r, tj = tile / G.tiles_r;
+  const int r0 = ti * FIELD_T, c0 = tj * FIELD_T;
+
+  for (int e = tid; e < FIELD_PLANE; e += 256) {
+    const int r = r0 + e % FIELD_HP - 1, c = c0 + e / FIELD_HP - 1;
+    const bool in = r >= 0 && r < G.nrows && c >= 0 && c < G.ncols;
+    const size_t cell = in ? (size_t)r + (size_t)c * G.nrows : 0;
+    smask[e] = in ? mask[cell] & G.yaw_bits : 0u;
+    sh[e] = in ? h[cell] : 0.f;
+  }
+  for (int e = tid; e < FIELD_PLANE * ny; e += 256) {
+    const int ci = e / ny, k = e - ci * ny;
+    const int r = r0 + ci % FIELD_HP - 1, c = c0 + ci / FIELD_HP - 1;
+    const bool in = r >= 0 && r < G.nrows && c >= 0 && c < G.ncols;
+    const size_t node = in ? ((size_t)r + (size_t)c * G.nrows) * ny + k : 0;
+    sd[k * FIELD_PLANE + ci] = in ? dist[node] : (double)INFINITY;
+    shop[k * FIELD_PLANE + ci] = in ? hops[node] : FIELD_NONE;
+  }
+  for (int e = tid; e < FIELD_TAB; e += 256) stab[e] = tabg[e];
+  if (tid < 2) sflag[tid] = 0u;
+  __syncthreads();
+
+  const int tr = tid & (FIELD_T - 1), tc = tid >> 4;
+  const int me = (tr + 1) + (tc + 1) * FIELD_HP;
+  const uint32_t mw = smask[me];
+  uint32_t nbm[8];
+  double w8[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int nb = me + field_dr(j) + field_dc(j) * FIELD_HP;
+    nbm[j] = smask[nb];
+    w8[j] = G.objective == 0 ? field_pull_cost(G, stab, j, 0, sh[me], sh[nb]) : 0.0;
+  }
+  const int widx0 = G.reverse ? 0 : 7;
+  const int wsgn = G.reverse ? 1 : -1;
+  const double wrot = G.wrot;
+  unsigned border = 0u;
+  const unsigned my_border = (tr == 0 ? 1u : 0u) | (tr == FIELD_T - 1 ? 2u : 0u) | (tc == 0 ? 4u : 0u) |
+                             (tc == FIELD_T - 1 ? 8u : 0u) | 16u;
+  unsigned died = 0u;
+  int still = 0;
+  for (int sweep = 0; sweep < inner_max; ++sweep) {
+    bool ch = false;
+    for (int k = 0; k < ny; ++k) {
+      if (!((mw >> k) & 1u)) continue;
+      double* plane = sd + k * FIELD_PLANE;
+      uint32_t* hplane = shop + k * FIELD_PLANE;
+      const double old = plane[me];
+      const uint32_t hv = hplane[me];
+      if (!(old < INFINITY) || hv == 0u || (PHASE == 1 && hv == FIELD_NONE)) continue;
+      bool sup = false;
+      if (hv != FIELD_NONE) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          if (!((nbm[j] >> k) & 1u)) continue;
+          const int nb = me + field_dr(j) + field_dc(j) * FIELD_HP;
+          const uint32_t hu = hplane[nb];
+          if (hu == FIELD_NONE || hu + 1u != hv) continue;
+          const double w = G.objective == 0 ? w8[j] : stab[(widx0 + wsgn * j) * 32 + k];
+          if (plane[nb] + w == old) sup = true;
+        }
+        if (ny > 1) {
+          const int kp = k + 1 == ny ? 0 : k + 1, km = k == 0 ? ny - 1 : k - 1;
+          if ((mw >> kp) & 1u) {
+            const uint32_t hu = shop[kp * FIELD_PLANE + me];
+            if (hu != FIELD_NONE && hu + 1u == hv && sd[kp * FIELD_PLANE + me] + wrot == old) sup = true;
+          }
+          if ((mw >> km) & 1u) {
+            const uint32_t hu = shop[km * FIELD_PLANE + me];
+            if (hu != FIELD_NONE && hu + 1u == hv && sd[km * FIELD_PLANE + me] + wrot == old) sup = true;
+          }
+        }
+      }
+      if (!sup) {
+        if (PHASE == 0) plane[me] = INFINITY;
+        hplane[me] = FIELD_NONE;
+        ch = true;
+        ++died;
+      }
+    }
+    if (ch) border |= my_border;
+    still = __syncthreads_or(ch ? 1 : 0);
+    if (!still) break;
+  }
+  if (border) atomicOr(&sflag[0], border);
+  if (died) atomicAdd(&sflag[1], died);
+  __syncthreads();
+  const unsigned bits = sflag[0];
+  if (bits) {
+    for (int e = tid; e < FIELD_T * FIELD_T * ny; e += 256) {
+      const int ci = e / ny, k = e - ci * ny;
+      const int lr = ci & (FIELD_T - 1), lc = ci >> 4;
+      const int r = r0 + lr, c = c0 + lc;
+      if (r >= G.nrows || c >= G.ncols) continue;
+      const size_t node = ((size_t)r + (size_t)c * G.nrows) * ny + k;
+      const int li = k * FIELD_PLANE + (lr + 1) + (lc + 1) * FIELD_HP;
+      if (PHASE == 0) dist[node] = sd[li];
+      hops[node] = shop[li];
+    }
+  }
+  if (tid < 8) {
+    const int dr = field_dr(tid), dc = field_dc(tid);
+    const int ni = ti + dr, nj = tj + dc;
+    const bool rows_ok = dr == 0 || (bits & (dr < 0 ? 1u : 2u));
+    const bool cols_ok = dc == 0 || (bits & (dc < 0 ? 4u : 8u));
+    if (rows_ok && cols_ok && (bits & 16u) && ni >= 0 && ni < G.tiles_r && nj >= 0 && nj < G.tiles_c) {
+      act_nxt[ni + nj * G.tiles_r] = 1u;
+      acc[ni + nj * G.tiles_r] = 1u;
+      atomicAdd(&counters[0], 1u);
+    }
+  } else if (tid == 8) {
+    if (still) {
+      act_nxt[tile] = 1u;
+      atomicAdd(&counters[0], 1u);
+    }
+    if (bits) acc[tile] = 1u;
+    atomicAdd(&counters[1], 1u);
+    if (sflag[1]) atomicAdd(&counters[2], sflag[1]);
+    act_cur[tile] = 0u;
+  }
+}
+
+// hops = NONE where the distance is not the one of the snapshot; the tiles around such a node are flagged
+__global__ void __launch_bounds__(256)
+field_hop_reset_kernel(FieldGrid G, const double* __restrict__ dist, const double* __restrict__ snap,
+                       uint32_t* __restrict__ hops, unsigned* acc) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)G.nrows * G.ncols * G.n_yaw) return;
+  if (__double_as_longlong(dist[i]) == __double_as_longlong(snap[i])) return;
+  hops[i] = FIELD_NONE;
+  const uint32_t cell = (uint32_t)(i / (uint32_t)G.n_yaw);
+  field_flag_around(G, (int)(cell % (uint32_t)G.nrows), (int)(cell / (uint32_t)G.nrows), acc);
+}
+
 }  // namespace artp
 
 struct artp_field {
@@ -465,13 +740,22 @@ struct artp_field {
   double* d_out = nullptr;       // path poses / edge costs
   size_t out_cap = 0;            // doubles
   artp_field_stats_t stats{};
+  // artp_field_update: the sources (d_nodes is path scratch after compute) and the scratch of the first update
+  std::vector<int> h_src;
+  int* d_src = nullptr;
+  double* d_snap = nullptr;             // dist in front of the searches of an update
+  unsigned* d_acc = nullptr;            // n_tiles flags: the tiles an update touched so far
+  unsigned long long* d_ucnt = nullptr; // the eight counts of the diff
+  uint32_t* d_stage = nullptr;          // a host mask's sub-rectangle, in the field's layout
+  artp_field_update_stats_t ustats{};
 };
 
 namespace {
 
 void field_free(artp_field* f) {
   for (void* p : {(void*)f->d_dist, (void*)f->d_hops, (void*)f->d_mask, (void*)f->d_h, (void*)f->d_tab, (void*)f->d_flags,
-                  (void*)f->d_nodes, (void*)f->d_out})
+                  (void*)f->d_nodes, (void*)f->d_out, (void*)f->d_src, (void*)f->d_snap, (void*)f->d_acc, (void*)f->d_ucnt,
+                  (void*)f->d_stage})
     if (p) (void)hipFree(p);
   delete f;
 }
@@ -512,9 +796,10 @@ void field_make_table(const artp_field_params& p, const MapGeom& g, int n_yaw, d
   }
 }
 
-// One search (PHASE 0: distances, 1: hop counts) to its fixed point.  The tiles of the sources are flagged in flags[0].
+// One search (PHASE 0: distances, 1: hop counts) to its fixed point.  The first round's tiles are those of the sources, or
+// the n_tiles flags of d_seed (artp_field_update: the tiles that changed) when it is given.
 template <int PHASE>
-int field_search(artp_field* f, const int* d_src, int n_src) {
+int field_search(artp_field* f, const int* d_src, int n_src, const unsigned* d_seed = nullptr) {
   artp_ctx* c = f->ctx;
   hipStream_t st = c->stream;
   const artp::FieldGrid& G = f->grid;
@@ -543,9 +828,13 @@ int field_search(artp_field* f, const int* d_src, int n_src) {
     }
     return ARTP_OK;
   }
-  hipLaunchKernelGGL(artp::field_seed_tiles_kernel, dim3((unsigned)((n_src + 63) / 64)), dim3(64), 0, st, G, d_src, n_src,
-                     f->d_flags);
-  HIP_TRY(c, hipGetLastError());
+  if (d_seed) {
+    HIP_TRY(c, hipMemcpyAsync(f->d_flags, d_seed, f->n_tiles * sizeof(unsigned), hipMemcpyDeviceToDevice, st));
+  } else {
+    hipLaunchKernelGGL(artp::field_seed_tiles_kernel, dim3((unsigned)((n_src + 63) / 64)), dim3(64), 0, st, G, d_src, n_src,
+                       f->d_flags);
+    HIP_TRY(c, hipGetLastError());
+  }
   const size_t lds = artp::field_tile_lds(G.n_yaw, PHASE);
   // a workgroup may ask for more than 64 KB of dynamic LDS once the function says so (32 headings: 88 / 126 KB)
   if (lds > 64 * 1024)
@@ -592,6 +881,7 @@ int field_compute_impl(artp_ctx* c, artp_field* f, const uint32_t* mask, int mas
                             mask_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
   HIP_TRY(c, hipMemcpyAsync(f->d_tab, tab, sizeof(tab), hipMemcpyHostToDevice, st));
   HIP_TRY(c, hipMemcpyAsync(f->d_nodes, sources, 3 * n_sources * sizeof(int), hipMemcpyHostToDevice, st));
+  f->h_src.assign(sources, sources + 3 * n_sources);  // d_nodes becomes path scratch; artp_field_update needs them
   HIP_TRY(c, hipMemsetAsync(f->d_flags, 0, (2 * f->n_tiles + 4) * sizeof(unsigned), st));
   hipLaunchKernelGGL(artp::field_heights_kernel, dim3((unsigned)((f->n_cells + 255) / 256)), dim3(256), 0, st, f->sampler,
                      f->geom, f->rect, f->d_h);
@@ -621,6 +911,111 @@ int field_compute_impl(artp_ctx* c, artp_field* f, const uint32_t* mask, int mas
   HIP_TRY(c, hipMemcpyAsync(&reached, d_count, sizeof(reached), hipMemcpyDeviceToHost, st));
   HIP_TRY(c, hipStreamSynchronize(st));
   f->stats.reached_nodes = reached;
+  return ARTP_OK;
+}
+
+int field_update_scratch(artp_field* f, bool stage) {
+  artp_ctx* c = f->ctx;
+  if (!f->d_src) {
+    HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&f->d_src), f->h_src.size() * sizeof(int)));
+    HIP_TRY(c, hipMemcpyAsync(f->d_src, f->h_src.data(), f->h_src.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  }
+  if (!f->d_snap) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&f->d_snap), f->n_nodes * sizeof(double)));
+  if (!f->d_acc) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&f->d_acc), f->n_tiles * sizeof(unsigned)));
+  if (!f->d_ucnt) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&f->d_ucnt), 8 * sizeof(unsigned long long)));
+  if (stage && !f->d_stage) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&f->d_stage), f->n_cells * sizeof(uint32_t)));
+  return ARTP_OK;
+}
+
+// One unsupport pass (PHASE 0: on distances, 1: on hop counts at the settled distances) until no node dies, over the
+// tiles flagged in d_acc (tiled form) or over every node (plain form).  Each round kills a node or is the last.
+template <int PHASE>
+int field_unsupport(artp_field* f, artp_field_update_stats_t* us, uint64_t* dead) {
+  artp_ctx* c = f->ctx;
+  hipStream_t st = c->stream;
+  const artp::FieldGrid& G = f->grid;
+  unsigned* counters = f->d_flags + 2 * f->n_tiles;
+  HIP_TRY(c, hipMemsetAsync(f->d_flags, 0, (2 * f->n_tiles + 4) * sizeof(unsigned), st));
+  const uint64_t cap = (uint64_t)f->n_nodes + 2;
+  unsigned now[3] = {0, 0, 0};
+  if (f->params.plain_sweeps) {
+    const unsigned blocks = (unsigned)((f->n_nodes + 255) / 256);
+    unsigned seen = 0;
+    for (uint64_t sweeps = 0;;) {
+      if (sweeps > cap) {
+        c->last_error = "artp_field_update: more unsupport sweeps than nodes";
+        return ARTP_ERR_CAPACITY;
+      }
+      for (int r = 0; r < 16; ++r)
+        hipLaunchKernelGGL(artp::field_unsupport_plain_kernel<PHASE>, dim3(blocks), dim3(256), 0, st, G,
+                           (const uint32_t*)f->d_mask, (const float*)f->d_h, (const double*)f->d_tab, f->d_dist, f->d_hops,
+                           counters);
+      HIP_TRY(c, hipGetLastError());
+      sweeps += 16;
+      us->unsupport_rounds += 16;
+      HIP_TRY(c, hipMemcpyAsync(now, counters, sizeof(now), hipMemcpyDeviceToHost, st));
+      HIP_TRY(c, hipStreamSynchronize(st));
+      *dead = now[2];
+      if (now[0] == seen) break;
+      seen = now[0];
+    }
+    return ARTP_OK;
+  }
+  HIP_TRY(c, hipMemcpyAsync(f->d_flags, f->d_acc, f->n_tiles * sizeof(unsigned), hipMemcpyDeviceToDevice, st));
+  const size_t lds = artp::field_tile_lds(G.n_yaw, 1);  // distances and hop counts in both phases: 126 KB at 32 headings
+  if (lds > 64 * 1024)
+    HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&artp::field_unsupport_tile_kernel<PHASE>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  const uint64_t tiles0 = us->tile_launches;
+  unsigned seen = 0;
+  for (uint64_t round = 0;; ++round) {
+    if (round > cap) {
+      c->last_error = "artp_field_update: more unsupport rounds than nodes";
+      return ARTP_ERR_CAPACITY;
+    }
+    unsigned* cur = f->d_flags + (round & 1) * f->n_tiles;
+    unsigned* nxt = f->d_flags + ((round + 1) & 1) * f->n_tiles;
+    hipLaunchKernelGGL(artp::field_unsupport_tile_kernel<PHASE>, dim3((unsigned)f->n_tiles), dim3(256), lds, st, G,
+                       (const uint32_t*)f->d_mask, (const float*)f->d_h, (const double*)f->d_tab, f->d_dist, f->d_hops, cur,
+                       nxt, f->d_acc, counters, f->params.inner_sweeps);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(now, counters, sizeof(now), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    us->unsupport_rounds += 1;
+    us->tile_launches = tiles0 + now[1];
+    *dead = now[2];
+    if (now[0] == seen) break;
+    seen = now[0];
+  }
+  return ARTP_OK;
+}
+
+// The passes of an update after the diff found a change.  f->stats takes the searches' counts on the way; the caller
+// moves them to the update's own numbers.
+int field_update_passes(artp_field* f, artp_field_update_stats_t* us) {
+  artp_ctx* c = f->ctx;
+  hipStream_t st = c->stream;
+  HIP_TRY(c, hipMemcpyAsync(f->d_snap, f->d_dist, f->n_nodes * sizeof(double), hipMemcpyDeviceToDevice, st));
+  const int n_src = (int)(f->h_src.size() / 3);
+  int rc = field_unsupport<0>(f, us, &us->dead_nodes);
+  if (rc) return rc;
+  rc = field_search<0>(f, f->d_src, n_src, f->d_acc);
+  if (rc) return rc;
+  hipLaunchKernelGGL(artp::field_hop_reset_kernel, dim3((unsigned)((f->n_nodes + 255) / 256)), dim3(256), 0, st, f->grid,
+                     (const double*)f->d_dist, (const double*)f->d_snap, f->d_hops, f->d_acc);
+  HIP_TRY(c, hipGetLastError());
+  rc = field_unsupport<1>(f, us, &us->hop_dead_nodes);
+  if (rc) return rc;
+  rc = field_search<1>(f, f->d_src, n_src, f->d_acc);
+  if (rc) return rc;
+  HIP_TRY(c, hipMemsetAsync(f->d_ucnt, 0, sizeof(unsigned long long), st));
+  hipLaunchKernelGGL(artp::field_count_kernel, dim3((unsigned)((f->n_nodes + 255) / 256)), dim3(256), 0, st, f->n_nodes,
+                     (const double*)f->d_dist, f->d_ucnt);
+  HIP_TRY(c, hipGetLastError());
+  unsigned long long reached = 0;
+  HIP_TRY(c, hipMemcpyAsync(&reached, f->d_ucnt, sizeof(reached), hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipStreamSynchronize(st));
+  us->reached_nodes = reached;
   return ARTP_OK;
 }
 
@@ -793,6 +1188,88 @@ int artp_field_edge_costs(artp_field* f, const int* a, const int* b, size_t n, d
 int artp_field_stats(artp_field* f, artp_field_stats_t* out) {
   if (!f || !out) return ARTP_ERR_INVALID_ARG;
   *out = f->stats;
+  return ARTP_OK;
+}
+
+int artp_field_update(artp_field* f, const uint32_t* new_mask, int mask_on_device, const int* sub_rect,
+                      int refresh_heights) {
+  if (!f || !new_mask) return ARTP_ERR_INVALID_ARG;
+  artp_ctx* c = f->ctx;
+  std::lock_guard<std::recursive_mutex> lock(c->mu);
+  const artp::FieldGrid& G = f->grid;
+  artp::FieldSub sub{0, 0, G.nrows, G.ncols};
+  if (sub_rect) sub = artp::FieldSub{sub_rect[0], sub_rect[1], sub_rect[2], sub_rect[3]};
+  if (sub.nrows < 1 || sub.ncols < 1 || sub.row0 < 0 || sub.col0 < 0 || sub.row0 > G.nrows - sub.nrows ||
+      sub.col0 > G.ncols - sub.ncols) {
+    c->last_error = "artp_field_update: sub_rect is empty or not inside the field's rectangle";
+    return ARTP_ERR_INVALID_ARG;
+  }
+  const MapGeom &a = f->geom, &b = c->geom;
+  const bool same_map = reach_have_lattice(c) && a.rows == b.rows && a.cols == b.cols && a.len_x == b.len_x &&
+                        a.len_y == b.len_y && a.pos_x == b.pos_x && a.pos_y == b.pos_y && a.res == b.res;
+  if (refresh_heights && !same_map) {
+    c->last_error = "artp_field_update: refresh_heights needs sampler layers of the geometry the field was computed on";
+    return ARTP_ERR_INVALID_ARG;
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  int rc = field_update_scratch(f, !mask_on_device);
+  if (rc) return rc;
+  HIP_TRY(c, hipMemsetAsync(f->d_acc, 0, f->n_tiles * sizeof(unsigned), st));
+  HIP_TRY(c, hipMemsetAsync(f->d_ucnt, 0, 8 * sizeof(unsigned long long), st));
+  const uint32_t* nm = new_mask;
+  if (!mask_on_device) {  // the columns of sub_rect only, to the same place of a buffer in the field's layout
+    const size_t off = (size_t)sub.row0 + (size_t)sub.col0 * G.nrows, pitch = (size_t)G.nrows * sizeof(uint32_t);
+    HIP_TRY(c, hipMemcpy2DAsync(f->d_stage + off, pitch, new_mask + off, pitch, (size_t)sub.nrows * sizeof(uint32_t),
+                                (size_t)sub.ncols, hipMemcpyHostToDevice, st));
+    nm = f->d_stage;
+  }
+  const int n_src = (int)(f->h_src.size() / 3);
+  hipLaunchKernelGGL(artp::field_update_sources_kernel, dim3((unsigned)((n_src + 63) / 64)), dim3(64), 0, st, G, sub,
+                     (const uint32_t*)f->d_mask, nm, (const int*)f->d_src, n_src, f->d_ucnt);
+  const size_t sub_cells = (size_t)sub.nrows * sub.ncols;
+  hipLaunchKernelGGL(artp::field_diff_kernel, dim3((unsigned)((sub_cells + 255) / 256)), dim3(256), 0, st, G, sub, nm,
+                     f->d_mask, refresh_heights ? 1 : 0, refresh_heights ? c->sampler : f->sampler, f->geom.rows, f->rect,
+                     f->d_h, f->d_dist, f->d_hops, f->d_acc, f->d_ucnt);
+  HIP_TRY(c, hipGetLastError());
+  unsigned long long cnt[5] = {0, 0, 0, 0, 0};
+  HIP_TRY(c, hipMemcpyAsync(cnt, f->d_ucnt, sizeof(cnt), hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipStreamSynchronize(st));  // the host copy of the mask is free from here
+  if (cnt[4]) {
+    c->last_error = "artp_field_update: a source is no longer a node of the mask (the field is unchanged)";
+    return ARTP_ERR_INVALID_ARG;
+  }
+  artp_field_update_stats_t us{};
+  us.changed_words = cnt[0];
+  us.removed_nodes = cnt[1];
+  us.added_nodes = cnt[2];
+  us.reached_nodes = f->stats.reached_nodes;
+  if (cnt[0] || cnt[3]) {
+    const artp_field_stats_t keep = f->stats;
+    f->stats.outer_rounds = f->stats.tile_launches = f->stats.plain_sweeps = f->stats.hop_rounds =
+        f->stats.hop_tile_launches = 0;
+    rc = field_update_passes(f, &us);
+    us.dist_rounds = f->params.plain_sweeps ? f->stats.plain_sweeps : f->stats.outer_rounds;
+    us.hop_rounds = f->stats.hop_rounds;
+    us.tile_launches += f->stats.tile_launches + f->stats.hop_tile_launches;
+    f->stats = keep;  // the numbers of artp_field_compute stay; only reached_nodes follows the field
+    if (rc) {
+      (void)hipStreamSynchronize(st);
+      return rc;
+    }
+    f->stats.reached_nodes = us.reached_nodes;
+  }
+  if (same_map) {  // artp_field_path's poses: the current sampler layers, as a new field would take them
+    f->sampler = c->sampler;
+    f->map_version = c->map_version.load();
+  }
+  f->ustats = us;
+  return ARTP_OK;
+}
+
+int artp_field_update_stats(artp_field* f, artp_field_update_stats_t* out) {
+  if (!f || !out) return ARTP_ERR_INVALID_ARG;
+  *out = f->ustats;
   return ARTP_OK;
 }
 

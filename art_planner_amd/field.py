@@ -22,16 +22,7 @@ class CostField:
         p.max_lon_vel, p.max_lat_vel, p.max_ang_vel = max_lon_vel, max_lat_vel, max_ang_vel
         r, nr, nc = ctx._reach_rect(rect)
         self.nrows, self.ncols, self.n_yaw, self.reverse = nr, nc, int(n_yaw), bool(reverse)
-        if hasattr(mask, "data_ptr"):   # a device tensor of nrows * ncols 32-bit words, column-major
-            if mask.numel() * mask.element_size() < nr * nc * 4:
-                raise _capi.ArtpError("cost_field: the mask tensor holds fewer than nrows * ncols words")
-            mask_ptr, on_device, keep = mask.data_ptr(), 1, mask
-        else:
-            m = np.asarray(mask)
-            if m.shape != (nr, nc):
-                raise _capi.ArtpError(f"cost_field: the mask is {m.shape}, the rectangle ({nr}, {nc})")
-            keep = np.asfortranarray(m, dtype=np.uint32)
-            mask_ptr, on_device = keep.ctypes.data, 0
+        mask_ptr, on_device, keep = self._mask_arg(mask, "cost_field")
         src = np.ascontiguousarray(sources, np.int32).reshape(-1, 3)
         h = C.c_void_p()
         ctx._chk(self.L.artp_field_compute(ctx.h, C.byref(p), int(n_yaw), r.ctypes.data if r is not None else None,
@@ -39,6 +30,19 @@ class CostField:
                                            C.byref(h)), "artp_field_compute")
         del keep
         self.h = h
+
+    def _mask_arg(self, mask, what):
+        """(pointer, on_device, the object that owns the memory) of a mask of the field's rectangle."""
+        nr, nc = self.nrows, self.ncols
+        if hasattr(mask, "data_ptr"):   # a device tensor of nrows * ncols 32-bit words, column-major
+            if mask.numel() * mask.element_size() < nr * nc * 4:
+                raise _capi.ArtpError(f"{what}: the mask tensor holds fewer than nrows * ncols words")
+            return mask.data_ptr(), 1, mask
+        m = np.asarray(mask)
+        if m.shape != (nr, nc):
+            raise _capi.ArtpError(f"{what}: the mask is {m.shape}, the rectangle ({nr}, {nc})")
+        keep = np.asfortranarray(m, dtype=np.uint32)
+        return keep.ctypes.data, 0, keep
 
     def close(self):
         if self.h:
@@ -105,6 +109,20 @@ class CostField:
         self.ctx._chk(self.L.artp_field_edge_costs(self.h, a.ctypes.data, b.ctypes.data, len(a), out.ctypes.data),
                       "artp_field_edge_costs")
         return out
+
+    def update(self, mask, rect=None, refresh_heights=False) -> dict:
+        """Bring the field to the fixed point of an edited mask in place (artp_field_update): the
+        same bits as a new cost_field on it.  mask as in the constructor, over the field's whole rectangle; rect =
+        (row0, col0, nrows, ncols) local to the field: only the words inside it are read (None = all).
+        refresh_heights re-reads the sampler layer's heights inside rect.  Returns the update's stats."""
+        mask_ptr, on_device, keep = self._mask_arg(mask, "CostField.update")
+        r = None if rect is None else np.ascontiguousarray(rect, np.int32).reshape(4)
+        self.ctx._chk(self.L.artp_field_update(self.h, mask_ptr, on_device, r.ctypes.data if r is not None else None,
+                                               int(bool(refresh_heights))), "artp_field_update")
+        del keep
+        s = _capi.FieldUpdateStats()
+        self.ctx._chk(self.L.artp_field_update_stats(self.h, C.byref(s)), "artp_field_update_stats")
+        return {n: int(getattr(s, n)) for n, _ in _capi.FieldUpdateStats._fields_}
 
     def stats(self) -> dict:
         s = _capi.FieldStats()

@@ -402,6 +402,37 @@ class Planner {
     return dist;
   }
 
+  // The field a computeCostField call kept, brought in place to an edited mask (artp_field_update, include/artp_c.h):
+  // the same bits as computeCostField on it, at the price of the region whose costs change.  mask = rows * cols words;
+  // rect = (row0, col0, nrows, ncols) of the words that may differ (nullptr = all of them; the others are not read).
+  // refresh_heights re-reads the map's heights inside rect.  Returns dist and refreshes the "cost_to_go" layer.
+  std::vector<double> updateCostField(artp_field* kept, const std::vector<uint32_t>& mask,
+                                      const std::array<int, 4>* rect = nullptr, bool refresh_heights = false) {
+    std::lock_guard<std::mutex> lock(map_mutex_);
+    if (!map_) throw std::runtime_error("updateCostField: the planner does not have a map set");
+    if (!kept) throw std::runtime_error("updateCostField: no field");
+    const auto g = map_->getGeometry();
+    const size_t cells = static_cast<size_t>(g.rows) * g.cols;
+    artp_field_stats_t st;
+    throwOnError(gpu_->get(), artp_field_stats(kept, &st), "artp_field_stats");
+    if (mask.size() != cells || st.nodes % cells != 0)
+      throw std::runtime_error("updateCostField: the mask or the field does not have rows * cols cells");
+    const size_t n_yaw = st.nodes / cells;
+    throwOnError(gpu_->get(),
+                 artp_field_update(kept, mask.data(), 0, rect ? rect->data() : nullptr, refresh_heights ? 1 : 0),
+                 "artp_field_update");
+    std::vector<double> dist(st.nodes);
+    throwOnError(gpu_->get(), artp_field_dist(kept, dist.data()), "artp_field_dist");
+    std::vector<float> best(cells);
+    for (size_t i = 0; i < cells; ++i) {
+      double b = std::numeric_limits<double>::infinity();
+      for (size_t k = 0; k < n_yaw; ++k) b = std::min(b, dist[i * n_yaw + k]);
+      best[i] = static_cast<float>(b);
+    }
+    map_->addLayer("cost_to_go", best.data());
+    return dist;
+  }
+
   void setSeed(uint64_t seed) {
     seed_ = seed;
     prm_->setSeed(seed);

@@ -278,6 +278,34 @@ int artp_field_path(artp_field* f, const int target[3], int* nodes_out, double* 
  * moves from a_i or a node lies outside the rectangle.  The mask is not consulted. */
 int artp_field_edge_costs(artp_field* f, const int* a, const int* b, size_t n, double* cost_out);
 int artp_field_stats(artp_field* f, artp_field_stats_t* out);
+/* Update the field IN PLACE after its mask (and, on request, its heights) changed in a sub-rectangle (DESIGN.md section
+ * 13).  new_mask: nrows x ncols words of the FIELD's rectangle, column-major, host (mask_on_device = 0) or device (1).
+ * sub_rect = {row0, col0, nrows, ncols} local to the field's rectangle, NULL = all of it: only the words inside it are
+ * read; outside it the field keeps its own words whatever new_mask holds there.  refresh_heights != 0 re-reads the sampler
+ * layer's heights inside sub_rect (only objective 0 uses heights).
+ * After ARTP_OK dist, hops (artp_field_path), artp_field_edge_costs and reached_nodes are bit for bit those of
+ * artp_field_compute with the field's own params, n_yaw, rectangle, sources and reverse on the merged mask and the merged
+ * heights (the current ones where refreshed, the old ones elsewhere).  Where the context's map still has the geometry the
+ * field was computed on, the poses of artp_field_path are those of the current sampler layers, as a new field's would be.
+ * ARTP_ERR_INVALID_ARG with the field untouched: a source is no longer a node of the merged mask, sub_rect is empty or not
+ * inside the rectangle, refresh_heights without sampler layers of the geometry the field was computed on.
+ * Every launch is bounded; the round caps are artp_field_compute's.  Synchronous, on the context's current stream. */
+typedef struct artp_field_update_stats_t {
+  uint64_t changed_words;    /* words of sub_rect that differ in their low n_yaw bits */
+  uint64_t removed_nodes;    /* bits cleared */
+  uint64_t added_nodes;      /* bits set */
+  uint64_t dead_nodes;       /* nodes whose distance lost its support and was recomputed */
+  uint64_t hop_dead_nodes;   /* nodes whose hop count lost its support (at the new distances) and was recomputed */
+  uint64_t unsupport_rounds; /* launches of the two unsupport passes */
+  uint64_t dist_rounds;      /* launches of the distance search */
+  uint64_t hop_rounds;       /* launches of the hop-count search */
+  uint64_t tile_launches;    /* tiled form: tiles that ran, over all four passes */
+  uint64_t reached_nodes;    /* nodes with a finite distance after the update */
+} artp_field_update_stats_t;
+int artp_field_update(artp_field* f, const uint32_t* new_mask, int mask_on_device, const int sub_rect[4],
+                      int refresh_heights);
+/* the numbers of the last artp_field_update that returned ARTP_OK (zeros before the first) */
+int artp_field_update_stats(artp_field* f, artp_field_update_stats_t* out);
 void artp_field_destroy(artp_field* f);
 
 /* ---- ob::MotionValidator::checkMotion (OMPL DiscreteMotionValidator; call sites
