@@ -1,35 +1,46 @@
 // field.h -- cost-to-go fields: shortest lattice costs from a set of source poses to every cell and heading of a
-// rectangle of the map (include/artp_c.h artp_field_*).
+// rectangle of the map (include/artp_c.h artp_field_*, DESIGN.md sections 12 and 13).
 //
 // Node (r, c, k) exists iff bit k of mask[r + c nrows] is set; node index = (r + c nrows) n_yaw + k, the pose order of
 // reach.h.  Ten moves per node (eight neighbouring cells at the same heading, two rotations).  dist[] is the least fixed
 // point of dist[v] = min(dist[u] + w(u, v)) with dist[source] = 0: fl(+) is monotone and the weights are non-negative, so
-// that fixed point is unique and does not depend on the order of the relaxations -- every kernel here relaxes IN PLACE and
-// reads neighbours that other lanes or workgroups may be lowering at the same time (an aligned 8-byte load or store is
+// that fixed point is unique and does not depend on the order of the relaxations -- every kernel here works IN PLACE and
+// reads neighbours that other lanes or workgroups may be changing at the same time (an aligned 8-byte load or store is
 // not torn; any value read is the cost of a real path, so it can only delay the fixed point, never miss it).
-//   field_plain_kernel<PHASE>  one lane per node pulls from its <= 10 predecessors; one launch per sweep, a device counter
-//                              of waves that changed something: the stepping stone and the timing yardstick
-//   field_tile_kernel<PHASE>   a workgroup owns 16 x 16 cells x all headings: dist of the tile plus a one-cell halo, the
-//                              mask words, the heights and the weight table go to LDS (heading-major planes: the lanes of
-//                              a wave read neighbouring doubles); it sweeps inside LDS until nothing changes or
-//                              inner_sweeps are spent, writes its own cells back (plain vector stores; the halo is
-//                              read-only) and flags the neighbouring tiles whose halo it changed for the next launch.
-//                              A launch covers every tile; the ones nobody flagged leave at once.
-//   PHASE 0 = distances, PHASE 1 = hop counts: hops[v] = the fewest tight edges (dist[u] + w == dist[v] bit for bit)
-//                              from a source, the rule of roadmap_many_hops_kernel.  Objective 0's rotations cost 0, so
-//                              "tight" holds both ways there; a predecessor one hop closer cannot close a cycle.
-//   field_path_kernel          one wave walks from the target to a source: lane m tests move m, the first tight one wins
-// No launch waits for another workgroup and no kernel stays resident: the host reads one counter per outer round.
 //
+// Four rules decide what happens to one node, given its live neighbours u over the ten moves (PHASE 0 works on
+// distances, PHASE 1 on hop counts at settled distances):
+//   relax, PHASE 0      dist[v] = min(dist[v], dist[u] + w)
+//   relax, PHASE 1      hops[v] = the fewest tight edges (dist[u] + w == dist[v] bit for bit) from a source, the rule of
+//                       roadmap_many_hops_kernel.  Objective 0's rotations cost 0, so "tight" holds both ways there; a
+//                       predecessor one hop closer cannot close a cycle.
+//   unsupport, PHASE 0  a live node stays iff it is a source (the nodes at 0 hops) or some u has dist[u] + w == dist[v]
+//                       AND hops[u] + 1 == hops[v]; the others go back to +inf / NONE.  "Dead" is that value itself,
+//                       and dying only spreads, so a stale neighbour read delays a death, never prevents it.
+//   unsupport, PHASE 1  the same test at the settled distances; only the hop count dies (NONE)
+// Each rule is written twice, once per form, and nothing else is:
+//   plain form   field_plain_kernel<PHASE> / field_unsupport_plain_kernel<PHASE>: one lane per node, neighbours in
+//                global memory through field_walk; one launch per sweep and a device counter of the waves that changed
+//                something: the stepping stone and the timing yardstick
+//   tiled form   field_tile_kernel<PHASE, UNSUP>, the tile skeleton: a workgroup owns 16 x 16 cells x all headings.
+//                dist of the tile plus a one-cell halo, the table, the mask words, the heights and (all rules but
+//                relax PHASE 0) the hop counts go to LDS, heading-major planes so that the lanes of a wave read
+//                neighbouring words.  One lane per cell applies field_tile_rule to its headings (neighbours in LDS
+//                through field_tile_walk) until nothing changes or inner_sweeps are spent; the tile writes its own
+//                cells back (plain vector stores; the halo is read-only), flags the neighbouring tiles whose halo it
+//                changed for the next launch, and itself when it ran out of sweeps.  A launch covers every tile; the
+//                ones nobody flagged leave at once.
+// field_rounds is the host loop of both forms: launch, read the counters, stop when nothing was flagged, refuse after
+// n_nodes + 2 rounds.  No launch waits for another workgroup and no kernel stays resident.
+//
+// artp_field_compute: relax PHASE 0 from the sources' tiles, then relax PHASE 1.  field_path_kernel: one wave walks from
+// the target to a source: lane m tests move m, the first tight one that is one hop closer wins.
 // artp_field_update brings a computed field to the fixed point of an edited mask in place:
 //   field_update_sources_kernel / field_diff_kernel   refuse a removed source; install the changed words (and heights),
-//                              clear the removed nodes, flag the tiles around every changed cell
-//   field_unsupport_*_kernel<PHASE>  a live node stays iff it is a source or a live neighbour u has dist[u] + w == dist[v]
-//                              AND hops[u] + 1 == hops[v]; the others go back to +inf / NONE (PHASE 0) or NONE (PHASE 1:
-//                              hop counts at the settled distances) until nobody dies.  "Dead" is that value itself, and
-//                              dying only spreads, so a stale neighbour read delays a death, never prevents it.
-//   field_hop_reset_kernel     hops = NONE where dist differs from the snapshot taken before the searches
-// and the two searches above run again from the flagged tiles instead of from the sources' tiles.
+//                       clear the removed nodes, flag the tiles around every changed cell
+//   unsupport PHASE 0, relax PHASE 0 from the flagged tiles
+//   field_hop_reset_kernel   hops = NONE where dist differs from the snapshot taken before
+//   unsupport PHASE 1, relax PHASE 1 from the flagged tiles
 #pragma once
 
 namespace artp {
@@ -61,9 +72,11 @@ __device__ __forceinline__ double field_move_cost(const FieldGrid& G, const doub
   return tab[m * 32 + k];
 }
 
-// The edge between node v and its neighbour at offset j that the search pulls along: forward fields use the move
-// neighbour -> v (move 7 - j seen from the neighbour), reverse fields the move v -> neighbour (move j).
+// The edge between node v and its neighbour by move j that the rules pull along: forward fields use the move
+// neighbour -> v (move 7 - j seen from the neighbour), reverse fields the move v -> neighbour (move j); a rotation (8, 9)
+// costs the same both ways.
 __device__ __forceinline__ double field_pull_cost(const FieldGrid& G, const double* tab, int j, int k, float hv, float hn) {
+  if (j >= 8) return G.wrot;
   return G.reverse ? field_move_cost(G, tab, j, k, hv, hn) : field_move_cost(G, tab, 7 - j, k, hn, hv);
 }
 
@@ -113,6 +126,36 @@ field_seed_tiles_kernel(FieldGrid G, const int* __restrict__ src, int n_src, uns
         active[(ti + di) + (tj + dj) * G.tiles_r] = 1u;
 }
 
+// neighbour of (r, c, k) by move m (0..9); false when it leaves the rectangle (or n_yaw == 1 for a rotation)
+__device__ __forceinline__ bool field_neighbour(const FieldGrid& G, int r, int c, int k, int m, int* nr, int* nc, int* nk) {
+  if (m < 8) {
+    *nr = r + field_dr(m);
+    *nc = c + field_dc(m);
+    *nk = k;
+    return *nr >= 0 && *nr < G.nrows && *nc >= 0 && *nc < G.ncols;
+  }
+  *nr = r;
+  *nc = c;
+  *nk = m == 8 ? (k + 1 == G.n_yaw ? 0 : k + 1) : (k == 0 ? G.n_yaw - 1 : k - 1);
+  return G.n_yaw > 1;
+}
+
+// The live neighbours of node (cell, k) over the ten moves, for the kernels with one lane per node: visit(ni, w) with ni
+// the neighbour's node index (its cell and heading) and w() the pull cost of that move, computed when a rule asks.
+template <class F>
+__device__ __forceinline__ void field_walk(const FieldGrid& G, const uint32_t* __restrict__ mask, const float* __restrict__ h,
+                                           const double* __restrict__ tab, uint32_t cell, int k, F&& visit) {
+  const int r = (int)(cell % (uint32_t)G.nrows), c = (int)(cell / (uint32_t)G.nrows);
+#pragma unroll
+  for (int m = 0; m < 10; ++m) {
+    int nr, nc, nk;
+    if (!field_neighbour(G, r, c, k, m, &nr, &nc, &nk)) continue;
+    const uint32_t ncell = m < 8 ? (uint32_t)nr + (uint32_t)nc * (uint32_t)G.nrows : cell;  // a rotation: the node's own word
+    if (!((mask[ncell] >> nk) & 1u)) continue;
+    visit((size_t)ncell * G.n_yaw + nk, [&]() { return field_pull_cost(G, tab, m, k, h[cell], h[ncell]); });
+  }
+}
+
 template <int PHASE>
 __global__ void __launch_bounds__(256)
 field_plain_kernel(FieldGrid G, const uint32_t* __restrict__ mask, const float* __restrict__ h,
@@ -123,76 +166,167 @@ field_plain_kernel(FieldGrid G, const uint32_t* __restrict__ mask, const float* 
   if (i < n) {
     const uint32_t cell = (uint32_t)(i / (uint32_t)G.n_yaw);
     const int k = (int)(i - (size_t)cell * G.n_yaw);
-    const uint32_t mw = mask[cell] & G.yaw_bits;
-    if ((mw >> k) & 1u) {
-      const int r = (int)(cell % (uint32_t)G.nrows), c = (int)(cell / (uint32_t)G.nrows);
-      const float hv = h[cell];
-      double best = dist[i];
-      uint32_t hb = PHASE ? hops[i] : 0u;
-      const double old = best;
-      const uint32_t hold = hb;
-      if (!PHASE || best < INFINITY) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const int rr = r + field_dr(j), cc = c + field_dc(j);
-          if (rr < 0 || rr >= G.nrows || cc < 0 || cc >= G.ncols) continue;
-          const uint32_t nc = (uint32_t)rr + (uint32_t)cc * (uint32_t)G.nrows;
-          if (!((mask[nc] >> k) & 1u)) continue;
-          const size_t ni = (size_t)nc * G.n_yaw + k;
+    if ((mask[cell] >> k) & 1u) {
+      const double old = dist[i];
+      if (PHASE == 0) {
+        double best = old;
+        field_walk(G, mask, h, tab, cell, k, [&](size_t ni, auto&& w) {
           const double du = dist[ni];
-          if (PHASE == 0) {
-            if (!(du < best)) continue;  // w >= 0: no candidate below du
-            const double cand = du + field_pull_cost(G, tab, j, k, hv, h[nc]);
-            if (cand < best) best = cand;
-          } else {
-            const uint32_t hu = hops[ni];
-            if (hu == FIELD_NONE || hu + 1u >= hb) continue;
-            if (du + field_pull_cost(G, tab, j, k, hv, h[nc]) == old) hb = hu + 1u;
-          }
+          if (!(du < best)) return;  // w >= 0: no candidate below du
+          const double cand = du + w();
+          if (cand < best) best = cand;
+        });
+        if (best < old) {
+          dist[i] = best;
+          ch = true;
         }
-        if (G.n_yaw > 1) {
-#pragma unroll
-          for (int s = 0; s < 2; ++s) {
-            const int kk = s == 0 ? (k + 1 == G.n_yaw ? 0 : k + 1) : (k == 0 ? G.n_yaw - 1 : k - 1);
-            if (!((mw >> kk) & 1u)) continue;
-            const size_t ni = (size_t)cell * G.n_yaw + kk;
-            const double du = dist[ni];
-            if (PHASE == 0) {
-              const double cand = du + G.wrot;
-              if (cand < best) best = cand;
-            } else {
-              const uint32_t hu = hops[ni];
-              if (hu == FIELD_NONE || hu + 1u >= hb) continue;
-              if (du + G.wrot == old) hb = hu + 1u;
-            }
-          }
+      } else if (old < INFINITY) {
+        const uint32_t hold = hops[i];
+        uint32_t hb = hold;
+        field_walk(G, mask, h, tab, cell, k, [&](size_t ni, auto&& w) {
+          const uint32_t hu = hops[ni];
+          if (hu == FIELD_NONE || hu + 1u >= hb) return;
+          if (dist[ni] + w() == old) hb = hu + 1u;
+        });
+        if (hb < hold) {
+          hops[i] = hb;
+          ch = true;
         }
-      }
-      if (PHASE == 0 && best < old) {
-        dist[i] = best;
-        ch = true;
-      }
-      if (PHASE == 1 && hb < hold) {
-        hops[i] = hb;
-        ch = true;
       }
     }
   }
   if (__any(ch) && (threadIdx.x & 63) == 0) atomicAdd(changed, 1u);
 }
 
-// LDS of a tile launch: n_yaw distance planes | the table | mask words | heights | (PHASE 1) n_yaw hop planes | 4 words
-inline size_t field_tile_lds(int n_yaw, int phase) {
-  return (size_t)n_yaw * FIELD_PLANE * 8 + FIELD_TAB * 8 + FIELD_PLANE * 4 * 2 + (phase ? (size_t)n_yaw * FIELD_PLANE * 4 : 0) +
+// counters[0] += waves in which a node died, counters[2] += nodes that died
+template <int PHASE>
+__global__ void __launch_bounds__(256)
+field_unsupport_plain_kernel(FieldGrid G, const uint32_t* __restrict__ mask, const float* __restrict__ h,
+                             const double* __restrict__ tab, double* dist, uint32_t* hops, unsigned* __restrict__ counters) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t n = (size_t)G.nrows * G.ncols * G.n_yaw;
+  bool die = false;
+  if (i < n) {
+    const uint32_t cell = (uint32_t)(i / (uint32_t)G.n_yaw);
+    const int k = (int)(i - (size_t)cell * G.n_yaw);
+    if ((mask[cell] >> k) & 1u) {
+      const double dv = dist[i];
+      const uint32_t hv = hops[i];
+      // live, and not a source (the only nodes at 0 hops)
+      if (dv < INFINITY && hv != 0u && !(PHASE == 1 && hv == FIELD_NONE)) {
+        bool sup = false;
+        if (hv != FIELD_NONE)
+          field_walk(G, mask, h, tab, cell, k, [&](size_t ni, auto&& w) {
+            if (sup) return;
+            const uint32_t hu = hops[ni];
+            if (hu == FIELD_NONE || hu + 1u != hv) return;
+            sup = dist[ni] + w() == dv;
+          });
+        if (!sup) {
+          if (PHASE == 0) dist[i] = INFINITY;
+          hops[i] = FIELD_NONE;
+          die = true;
+        }
+      }
+    }
+  }
+  const unsigned long long b = __ballot(die);
+  if (b && (threadIdx.x & 63) == 0) {
+    atomicAdd(&counters[0], 1u);
+    atomicAdd(&counters[2], (unsigned)__popcll(b));
+  }
+}
+
+// LDS of a tile launch: n_yaw distance planes | the table | mask words | heights | (hop_planes) n_yaw hop planes | 4 words.
+// Relax PHASE 0 carries no hop planes: 88 KB at 32 headings against the 126 KB of the other three rules.
+inline size_t field_tile_lds(int n_yaw, bool hop_planes) {
+  return (size_t)n_yaw * FIELD_PLANE * 8 + FIELD_TAB * 8 + FIELD_PLANE * 4 * 2 + (hop_planes ? (size_t)n_yaw * FIELD_PLANE * 4 : 0) +
          16;
 }
 
-// counters[0] += flags set for the next round, counters[1] += tiles that ran (both cumulative over the call)
-template <int PHASE>
+// What a lane of a tile keeps in registers about its cell while it sweeps (every index is a constant once unrolled).
+struct FieldLane {
+  int me;           // the cell in an LDS plane
+  uint32_t mw;      // its mask word
+  uint32_t nbm[8];  // the mask words of the eight cells around it
+  double w8[8];     // objective 0: the eight translation costs of this cell
+  int widx0, wsgn;  // objective 1: table row of offset j = reverse ? j : 7 - j
+};
+
+// the pull cost of move m (0..9) at heading k of the lane's cell
+__device__ __forceinline__ double field_lane_cost(const FieldGrid& G, const FieldLane& L, const double* stab, int m, int k) {
+  if (m >= 8) return G.wrot;
+  return G.objective == 0 ? L.w8[m] : stab[(L.widx0 + L.wsgn * m) * 32 + k];
+}
+
+// The live neighbours of heading k of the lane's cell over the ten moves: visit(li, m) with li the neighbour's place in
+// the LDS planes (heading included) and m the move, for field_lane_cost (not a cost callable as in field_walk: a closure
+// over L sends the lane's arrays to scratch).
+template <class F>
+__device__ __forceinline__ void field_tile_walk(const FieldGrid& G, const FieldLane& L, int k, F&& visit) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j)
+    if ((L.nbm[j] >> k) & 1u) visit(k * FIELD_PLANE + L.me + field_dr(j) + field_dc(j) * FIELD_HP, j);
+  if (G.n_yaw > 1) {
+    const int kp = k + 1 == G.n_yaw ? 0 : k + 1, km = k == 0 ? G.n_yaw - 1 : k - 1;
+    if ((L.mw >> kp) & 1u) visit(kp * FIELD_PLANE + L.me, 8);
+    if ((L.mw >> km) & 1u) visit(km * FIELD_PLANE + L.me, 9);
+  }
+}
+
+// One of the four rules on heading k of the lane's cell, inside LDS; true when the node changed.
+template <int PHASE, bool UNSUP>
+__device__ __forceinline__ bool field_tile_rule(const FieldGrid& G, const FieldLane& L, const double* stab, double* sd,
+                                                uint32_t* shop, int k) {
+  const int own = k * FIELD_PLANE + L.me;
+  const double old = sd[own];
+  if (UNSUP) {
+    const uint32_t hv = shop[own];
+    // live, and not a source (the only nodes at 0 hops)
+    if (!(old < INFINITY) || hv == 0u || (PHASE == 1 && hv == FIELD_NONE)) return false;
+    bool sup = false;
+    if (hv != FIELD_NONE)
+      field_tile_walk(G, L, k, [&](int li, int m) {
+        const uint32_t hu = shop[li];
+        if (hu == FIELD_NONE || hu + 1u != hv) return;
+        if (sd[li] + field_lane_cost(G, L, stab, m, k) == old) sup = true;
+      });
+    if (sup) return false;
+    if (PHASE == 0) sd[own] = INFINITY;
+    shop[own] = FIELD_NONE;
+    return true;
+  }
+  if (PHASE == 0) {
+    double best = old;
+    field_tile_walk(G, L, k, [&](int li, int m) {
+      const double cand = sd[li] + field_lane_cost(G, L, stab, m, k);
+      if (cand < best) best = cand;
+    });
+    if (best < old) sd[own] = best;
+    return best < old;
+  }
+  if (!(old < INFINITY)) return false;
+  const uint32_t hold = shop[own];
+  uint32_t hb = hold;
+  field_tile_walk(G, L, k, [&](int li, int m) {
+    const uint32_t hu = shop[li];
+    if (hu == FIELD_NONE || hu + 1u >= hb) return;
+    if (sd[li] + field_lane_cost(G, L, stab, m, k) == old) hb = hu + 1u;
+  });
+  if (hb < hold) shop[own] = hb;
+  return hb < hold;
+}
+
+// The tile skeleton.  UNSUP = 0: relax (writes back the array of its PHASE; acc is not used); UNSUP = 1: unsupport
+// (writes hops back, and dist in PHASE 0; every change of a rule is a death).  counters[0] += flags set for the next
+// round, [1] += tiles that ran, [2] += nodes that died (all cumulative over the host's loop).  acc collects, over a whole
+// update, the tiles whose own cells or halo an unsupport pass changed: the seeds of the relax pass that follows.
+template <int PHASE, bool UNSUP>
 __global__ void __launch_bounds__(256)
 field_tile_kernel(FieldGrid G, const uint32_t* __restrict__ mask, const float* __restrict__ h,
                   const double* __restrict__ tabg, double* dist, uint32_t* hops, unsigned* act_cur, unsigned* act_nxt,
-                  unsigned* __restrict__ counters, int inner_max) {
+                  unsigned* acc, unsigned* __restrict__ counters, int inner_max) {
+  constexpr bool HOPS = PHASE == 1 || UNSUP;  // hop planes in LDS
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tile = blockIdx.x;
   if (!act_cur[tile]) return;  // nobody writes act_cur in this launch before the barrier below: uniform
@@ -202,7 +336,7 @@ field_tile_kernel(FieldGrid G, const uint32_t* __restrict__ mask, const float* _
   uint32_t* smask = reinterpret_cast<uint32_t*>(stab + FIELD_TAB);
   float* sh = reinterpret_cast<float*>(smask + FIELD_PLANE);
   uint32_t* shop = reinterpret_cast<uint32_t*>(sh + FIELD_PLANE);
-  unsigned* sflag = reinterpret_cast<unsigned*>(shop + (PHASE ? (size_t)ny * FIELD_PLANE : 0));
+  unsigned* sflag = reinterpret_cast<unsigned*>(shop + (HOPS ? (size_t)ny * FIELD_PLANE : 0));  // [0] border bits, [1] deaths
   const int tid = threadIdx.x;
   const int ti = tile % G.tiles_r, tj = tile / G.tiles_r;
   const int r0 = ti * FIELD_T, c0 = tj * FIELD_T;
@@ -220,88 +354,36 @@ field_tile_kernel(FieldGrid G, const uint32_t* __restrict__ mask, const float* _
     const bool in = r >= 0 && r < G.nrows && c >= 0 && c < G.ncols;
     const size_t node = in ? ((size_t)r + (size_t)c * G.nrows) * ny + k : 0;
     sd[k * FIELD_PLANE + ci] = in ? dist[node] : (double)INFINITY;
-    if (PHASE) shop[k * FIELD_PLANE + ci] = in ? hops[node] : FIELD_NONE;
+    if (HOPS) shop[k * FIELD_PLANE + ci] = in ? hops[node] : FIELD_NONE;
   }
   for (int e = tid; e < FIELD_TAB; e += 256) stab[e] = tabg[e];
-  if (tid == 0) sflag[0] = 0u;
+  if (tid < 2) sflag[tid] = 0u;
   __syncthreads();
 
   const int tr = tid & (FIELD_T - 1), tc = tid >> 4;
-  const int me = (tr + 1) + (tc + 1) * FIELD_HP;
-  const uint32_t mw = smask[me];
-  uint32_t nbm[8];
-  double w8[8];  // objective 0: the eight translation costs of this cell
+  FieldLane L;
+  L.me = (tr + 1) + (tc + 1) * FIELD_HP;
+  L.mw = smask[L.me];
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
-    const int nb = me + field_dr(j) + field_dc(j) * FIELD_HP;
-    nbm[j] = smask[nb];
-    w8[j] = G.objective == 0 ? field_pull_cost(G, stab, j, 0, sh[me], sh[nb]) : 0.0;
+    const int nb = L.me + field_dr(j) + field_dc(j) * FIELD_HP;
+    L.nbm[j] = smask[nb];
+    L.w8[j] = G.objective == 0 ? field_pull_cost(G, stab, j, 0, sh[L.me], sh[nb]) : 0.0;
   }
-  const int widx0 = G.reverse ? 0 : 7;  // objective 1: table row of offset j = reverse ? j : 7 - j
-  const int wsgn = G.reverse ? 1 : -1;
-  const double wrot = G.wrot;
+  L.widx0 = G.reverse ? 0 : 7;
+  L.wsgn = G.reverse ? 1 : -1;
   unsigned border = 0u;  // bit 0 / 1: a cell of the first / last row changed, bit 2 / 3: first / last column, bit 4: any
   const unsigned my_border = (tr == 0 ? 1u : 0u) | (tr == FIELD_T - 1 ? 2u : 0u) | (tc == 0 ? 4u : 0u) |
                              (tc == FIELD_T - 1 ? 8u : 0u) | 16u;
+  unsigned changes = 0u;
   int still = 0;
   for (int sweep = 0; sweep < inner_max; ++sweep) {
     bool ch = false;
     for (int k = 0; k < ny; ++k) {
-      if (!((mw >> k) & 1u)) continue;
-      double* plane = sd + k * FIELD_PLANE;
-      const double old = plane[me];
-      const int kp = k + 1 == ny ? 0 : k + 1, km = k == 0 ? ny - 1 : k - 1;
-      if (PHASE == 0) {
-        double best = old;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          if (!((nbm[j] >> k) & 1u)) continue;
-          const double w = G.objective == 0 ? w8[j] : stab[(widx0 + wsgn * j) * 32 + k];
-          const double cand = plane[me + field_dr(j) + field_dc(j) * FIELD_HP] + w;
-          if (cand < best) best = cand;
-        }
-        if (ny > 1) {
-          if ((mw >> kp) & 1u) {
-            const double cand = sd[kp * FIELD_PLANE + me] + wrot;
-            if (cand < best) best = cand;
-          }
-          if ((mw >> km) & 1u) {
-            const double cand = sd[km * FIELD_PLANE + me] + wrot;
-            if (cand < best) best = cand;
-          }
-        }
-        if (best < old) {
-          plane[me] = best;
-          ch = true;
-        }
-      } else {
-        if (!(old < INFINITY)) continue;
-        uint32_t* hplane = shop + k * FIELD_PLANE;
-        const uint32_t hold = hplane[me];
-        uint32_t hb = hold;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          if (!((nbm[j] >> k) & 1u)) continue;
-          const int nb = me + field_dr(j) + field_dc(j) * FIELD_HP;
-          const uint32_t hu = hplane[nb];
-          if (hu == FIELD_NONE || hu + 1u >= hb) continue;
-          const double w = G.objective == 0 ? w8[j] : stab[(widx0 + wsgn * j) * 32 + k];
-          if (plane[nb] + w == old) hb = hu + 1u;
-        }
-        if (ny > 1) {
-          if ((mw >> kp) & 1u) {
-            const uint32_t hu = shop[kp * FIELD_PLANE + me];
-            if (hu != FIELD_NONE && hu + 1u < hb && sd[kp * FIELD_PLANE + me] + wrot == old) hb = hu + 1u;
-          }
-          if ((mw >> km) & 1u) {
-            const uint32_t hu = shop[km * FIELD_PLANE + me];
-            if (hu != FIELD_NONE && hu + 1u < hb && sd[km * FIELD_PLANE + me] + wrot == old) hb = hu + 1u;
-          }
-        }
-        if (hb < hold) {
-          hplane[me] = hb;
-          ch = true;
-        }
+      if (!((L.mw >> k) & 1u)) continue;
+      if (field_tile_rule<PHASE, UNSUP>(G, L, stab, sd, shop, k)) {
+        ch = true;
+        ++changes;
       }
     }
     if (ch) border |= my_border;
@@ -309,6 +391,7 @@ field_tile_kernel(FieldGrid G, const uint32_t* __restrict__ mask, const float* _
     if (!still) break;
   }
   if (border) atomicOr(&sflag[0], border);
+  if (UNSUP && changes) atomicAdd(&sflag[1], changes);
   __syncthreads();
   const unsigned bits = sflag[0];
   if (bits) {  // own cells back; the halo belongs to the neighbours
@@ -320,7 +403,7 @@ field_tile_kernel(FieldGrid G, const uint32_t* __restrict__ mask, const float* _
       const size_t node = ((size_t)r + (size_t)c * G.nrows) * ny + k;
       const int li = k * FIELD_PLANE + (lr + 1) + (lc + 1) * FIELD_HP;
       if (PHASE == 0) dist[node] = sd[li];
-      else hops[node] = shop[li];
+      if (PHASE == 1 || UNSUP) hops[node] = shop[li];
     }
   }
   if (tid < 8) {
@@ -330,6 +413,7 @@ field_tile_kernel(FieldGrid G, const uint32_t* __restrict__ mask, const float* _
     const bool cols_ok = dc == 0 || (bits & (dc < 0 ? 4u : 8u));
     if (rows_ok && cols_ok && (bits & 16u) && ni >= 0 && ni < G.tiles_r && nj >= 0 && nj < G.tiles_c) {
       act_nxt[ni + nj * G.tiles_r] = 1u;
+      if (UNSUP) acc[ni + nj * G.tiles_r] = 1u;
       atomicAdd(&counters[0], 1u);
     }
   } else if (tid == 8) {
@@ -337,7 +421,9 @@ field_tile_kernel(FieldGrid G, const uint32_t* __restrict__ mask, const float* _
       act_nxt[tile] = 1u;
       atomicAdd(&counters[0], 1u);
     }
+    if (UNSUP && bits) acc[tile] = 1u;
     atomicAdd(&counters[1], 1u);
+    if (UNSUP && sflag[1]) atomicAdd(&counters[2], sflag[1]);
     act_cur[tile] = 0u;  // every lane read it in front of the first barrier
   }
 }
@@ -348,20 +434,6 @@ field_count_kernel(size_t n, const double* __restrict__ dist, unsigned long long
   const bool fin = i < n && dist[i] < INFINITY;
   const unsigned long long b = __ballot(fin);
   if ((threadIdx.x & 63) == 0 && b) atomicAdd(count, (unsigned long long)__popcll(b));
-}
-
-// neighbour of (r, c, k) by move m (0..9); false when it leaves the rectangle (or n_yaw == 1 for a rotation)
-__device__ __forceinline__ bool field_neighbour(const FieldGrid& G, int r, int c, int k, int m, int* nr, int* nc, int* nk) {
-  if (m < 8) {
-    *nr = r + field_dr(m);
-    *nc = c + field_dc(m);
-    *nk = k;
-    return *nr >= 0 && *nr < G.nrows && *nc >= 0 && *nc < G.ncols;
-  }
-  *nr = r;
-  *nc = c;
-  *nk = m == 8 ? (k + 1 == G.n_yaw ? 0 : k + 1) : (k == 0 ? G.n_yaw - 1 : k - 1);
-  return G.n_yaw > 1;
 }
 
 // One wave.  out_n: the states of the path (0 = unreachable, -1 = no tight predecessor: cannot happen at the fixed point);
@@ -397,7 +469,7 @@ field_path_kernel(FieldGrid G, const uint32_t* __restrict__ mask, const float* _
       const size_t ncell = (size_t)nr + (size_t)nc * G.nrows;
       if ((mask[ncell] >> nk) & 1u) {
         const size_t ni = ncell * G.n_yaw + nk;
-        const double w = lane < 8 ? field_pull_cost(G, tab, lane, k, h[(size_t)r + (size_t)c * G.nrows], h[ncell]) : G.wrot;
+        const double w = field_pull_cost(G, tab, lane, k, h[(size_t)r + (size_t)c * G.nrows], h[ncell]);
         ok = hops[ni] + 1u == hv && dist[ni] + w == dv;
       }
     }
@@ -518,194 +590,6 @@ field_diff_kernel(FieldGrid G, FieldSub sub, const uint32_t* __restrict__ new_ma
   if (touched) field_flag_around(G, r, c, acc);
 }
 
-// counters[0] += waves in which a node died, counters[2] += nodes that died
-template <int PHASE>
-__global__ void __launch_bounds__(256)
-field_unsupport_plain_kernel(FieldGrid G, const uint32_t* __restrict__ mask, const float* __restrict__ h,
-                             const double* __restrict__ tab, double* dist, uint32_t* hops, unsigned* __restrict__ counters) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t n = (size_t)G.nrows * G.ncols * G.n_yaw;
-  bool die = false;
-  if (i < n) {
-    const uint32_t cell = (uint32_t)(i / (uint32_t)G.n_yaw);
-    const int k = (int)(i - (size_t)cell * G.n_yaw);
-    if ((mask[cell] >> k) & 1u) {
-      const double dv = dist[i];
-      const uint32_t hv = hops[i];
-      // live, and not a source (the only nodes at 0 hops)
-      if (dv < INFINITY && hv != 0u && !(PHASE == 1 && hv == FIELD_NONE)) {
-        bool sup = false;
-        if (hv != FIELD_NONE) {
-          const int r = (int)(cell % (uint32_t)G.nrows), c = (int)(cell / (uint32_t)G.nrows);
-          const float hc = h[cell];
-          for (int m = 0; m < 10 && !sup; ++m) {
-            int nr, nc, nk;
-            if (!field_neighbour(G, r, c, k, m, &nr, &nc, &nk)) continue;
-            const size_t ncell = (size_t)nr + (size_t)nc * G.nrows;
-            if (!((mask[ncell] >> nk) & 1u)) continue;
-            const size_t ni = ncell * G.n_yaw + nk;
-            const uint32_t hu = hops[ni];
-            if (hu == FIELD_NONE || hu + 1u != hv) continue;
-            const double w = m < 8 ? field_pull_cost(G, tab, m, k, hc, h[ncell]) : G.wrot;
-            sup = dist[ni] + w == dv;
-          }
-        }
-        if (!sup) {
-          if (PHASE == 0) dist[i] = INFINITY;
-          hops[i] = FIELD_NONE;
-          die = true;
-        }
-      }
-    }
-  }
-  const unsigned long long b = __ballot(die);
-  if (b && (threadIdx.x & 63) == 0) {
-    atomicAdd(&counters[0], 1u);
-    atomicAdd(&counters[2], (unsigned)__popcll(b));
-  }
-}
-
-// The protocol and the LDS layout of field_tile_kernel<1> (field_tile_lds(n_yaw, 1)); sflag[1] counts the tile's deaths.
-// counters[0] += flags set for the next round, [1] += tiles that ran, [2] += nodes that died.  acc collects, over the
-// whole update, the tiles whose own cells or halo changed: the seeds of the search that follows.
-template <int PHASE>
-__global__ void __launch_bounds__(256)
-field_unsupport_tile_kernel(FieldGrid G, const uint32_t* __restrict__ mask, const float* __restrict__ h,
-                            const double* __restrict__ tabg, double* dist, uint32_t* hops, unsigned* act_cur,
-                            unsigned* act_nxt, unsigned* acc, unsigned* __restrict__ counters, int inner_max) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tile = blockIdx.x;
-  if (!act_cur[tile]) return;  // uniform, as in field_tile_kernel
-  const int ny = G.n_yaw;
-  double* sd = reinterpret_cast<double*>(smem);
-  double* stab = sd + (size_t)ny * FIELD_PLANE;
-  uint32_t* smask = reinterpret_cast<uint32_t*>(stab + FIELD_TAB);
-  float* sh = reinterpret_cast<float*>(smask + FIELD_PLANE);
-  uint32_t* shop = reinterpret_cast<uint32_t*>(sh + FIELD_PLANE);
-  unsigned* sflag = reinterpret_cast<unsigned*>(shop + (size_t)ny * FIELD_PLANE);
-  const int tid = threadIdx.x;
-  const int ti = tile % G.tiles_r, tj = tile / G.tiles_r;
-  const int r0 = ti * FIELD_T, c0 = tj * FIELD_T;
-
-  for (int e = tid; e < FIELD_PLANE; e += 256) {
-    const int r = r0 + e % FIELD_HP - 1, c = c0 + e / FIELD_HP - 1;
-    const bool in = r >= 0 && r < G.nrows && c >= 0 && c < G.ncols;
-    const size_t cell = in ? (size_t)r + (size_t)c * G.nrows : 0;
-    smask[e] = in ? mask[cell] & G.yaw_bits : 0u;
-    sh[e] = in ? h[cell] : 0.f;
-  }
-  for (int e = tid; e < FIELD_PLANE * ny; e += 256) {
-    const int ci = e / ny, k = e - ci * ny;
-    const int r = r0 + ci % FIELD_HP - 1, c = c0 + ci / FIELD_HP - 1;
-    const bool in = r >= 0 && r < G.nrows && c >= 0 && c < G.ncols;
-    const size_t node = in ? ((size_t)r + (size_t)c * G.nrows) * ny + k : 0;
-    sd[k * FIELD_PLANE + ci] = in ? dist[node] : (double)INFINITY;
-    shop[k * FIELD_PLANE + ci] = in ? hops[node] : FIELD_NONE;
-  }
-  for (int e = tid; e < FIELD_TAB; e += 256) stab[e] = tabg[e];
-  if (tid < 2) sflag[tid] = 0u;
-  __syncthreads();
-
-  const int tr = tid & (FIELD_T - 1), tc = tid >> 4;
-  const int me = (tr + 1) + (tc + 1) * FIELD_HP;
-  const uint32_t mw = smask[me];
-  uint32_t nbm[8];
-  double w8[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int nb = me + field_dr(j) + field_dc(j) * FIELD_HP;
-    nbm[j] = smask[nb];
-    w8[j] = G.objective == 0 ? field_pull_cost(G, stab, j, 0, sh[me], sh[nb]) : 0.0;
-  }
-  const int widx0 = G.reverse ? 0 : 7;
-  const int wsgn = G.reverse ? 1 : -1;
-  const double wrot = G.wrot;
-  unsigned border = 0u;
-  const unsigned my_border = (tr == 0 ? 1u : 0u) | (tr == FIELD_T - 1 ? 2u : 0u) | (tc == 0 ? 4u : 0u) |
-                             (tc == FIELD_T - 1 ? 8u : 0u) | 16u;
-  unsigned died = 0u;
-  int still = 0;
-  for (int sweep = 0; sweep < inner_max; ++sweep) {
-    bool ch = false;
-    for (int k = 0; k < ny; ++k) {
-      if (!((mw >> k) & 1u)) continue;
-      double* plane = sd + k * FIELD_PLANE;
-      uint32_t* hplane = shop + k * FIELD_PLANE;
-      const double old = plane[me];
-      const uint32_t hv = hplane[me];
-      if (!(old < INFINITY) || hv == 0u || (PHASE == 1 && hv == FIELD_NONE)) continue;
-      bool sup = false;
-      if (hv != FIELD_NONE) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          if (!((nbm[j] >> k) & 1u)) continue;
-          const int nb = me + field_dr(j) + field_dc(j) * FIELD_HP;
-          const uint32_t hu = hplane[nb];
-          if (hu == FIELD_NONE || hu + 1u != hv) continue;
-          const double w = G.objective == 0 ? w8[j] : stab[(widx0 + wsgn * j) * 32 + k];
-          if (plane[nb] + w == old) sup = true;
-        }
-        if (ny > 1) {
-          const int kp = k + 1 == ny ? 0 : k + 1, km = k == 0 ? ny - 1 : k - 1;
-          if ((mw >> kp) & 1u) {
-            const uint32_t hu = shop[kp * FIELD_PLANE + me];
-            if (hu != FIELD_NONE && hu + 1u == hv && sd[kp * FIELD_PLANE + me] + wrot == old) sup = true;
-          }
-          if ((mw >> km) & 1u) {
-            const uint32_t hu = shop[km * FIELD_PLANE + me];
-            if (hu != FIELD_NONE && hu + 1u == hv && sd[km * FIELD_PLANE + me] + wrot == old) sup = true;
-          }
-        }
-      }
-      if (!sup) {
-        if (PHASE == 0) plane[me] = INFINITY;
-        hplane[me] = FIELD_NONE;
-        ch = true;
-        ++died;
-      }
-    }
-    if (ch) border |= my_border;
-    still = __syncthreads_or(ch ? 1 : 0);
-    if (!still) break;
-  }
-  if (border) atomicOr(&sflag[0], border);
-  if (died) atomicAdd(&sflag[1], died);
-  __syncthreads();
-  const unsigned bits = sflag[0];
-  if (bits) {
-    for (int e = tid; e < FIELD_T * FIELD_T * ny; e += 256) {
-      const int ci = e / ny, k = e - ci * ny;
-      const int lr = ci & (FIELD_T - 1), lc = ci >> 4;
-      const int r = r0 + lr, c = c0 + lc;
-      if (r >= G.nrows || c >= G.ncols) continue;
-      const size_t node = ((size_t)r + (size_t)c * G.nrows) * ny + k;
-      const int li = k * FIELD_PLANE + (lr + 1) + (lc + 1) * FIELD_HP;
-      if (PHASE == 0) dist[node] = sd[li];
-      hops[node] = shop[li];
-    }
-  }
-  if (tid < 8) {
-    const int dr = field_dr(tid), dc = field_dc(tid);
-    const int ni = ti + dr, nj = tj + dc;
-    const bool rows_ok = dr == 0 || (bits & (dr < 0 ? 1u : 2u));
-    const bool cols_ok = dc == 0 || (bits & (dc < 0 ? 4u : 8u));
-    if (rows_ok && cols_ok && (bits & 16u) && ni >= 0 && ni < G.tiles_r && nj >= 0 && nj < G.tiles_c) {
-      act_nxt[ni + nj * G.tiles_r] = 1u;
-      acc[ni + nj * G.tiles_r] = 1u;
-      atomicAdd(&counters[0], 1u);
-    }
-  } else if (tid == 8) {
-    if (still) {
-      act_nxt[tile] = 1u;
-      atomicAdd(&counters[0], 1u);
-    }
-    if (bits) acc[tile] = 1u;
-    atomicAdd(&counters[1], 1u);
-    if (sflag[1]) atomicAdd(&counters[2], sflag[1]);
-    act_cur[tile] = 0u;
-  }
-}
-
 // hops = NONE where the distance is not the one of the snapshot; the tiles around such a node are flagged
 __global__ void __launch_bounds__(256)
 field_hop_reset_kernel(FieldGrid G, const double* __restrict__ dist, const double* __restrict__ snap,
@@ -796,70 +680,90 @@ void field_make_table(const artp_field_params& p, const MapGeom& g, int n_yaw, d
   }
 }
 
-// One search (PHASE 0: distances, 1: hop counts) to its fixed point.  The first round's tiles are those of the sources, or
-// the n_tiles flags of d_seed (artp_field_update: the tiles that changed) when it is given.
-template <int PHASE>
-int field_search(artp_field* f, const int* d_src, int n_src, const unsigned* d_seed = nullptr) {
+struct FieldRounds {
+  uint64_t rounds = 0;     // launches
+  uint64_t tile_runs = 0;  // tiled form: tiles that ran in them
+  uint64_t deaths = 0;     // unsupport: nodes that died
+};
+
+// The host loop of every pass: `batch` launches, one read of the counters, until a batch flagged nothing.
+// launch(cur, nxt, counters) enqueues one round; cur / nxt are the two flag arrays of d_flags in turn (the tiled form's;
+// the caller has seeded the first).  A round settles (or kills) at least what a plain sweep does, and sweep s settles every
+// node whose best path has <= s edges: more rounds than nodes + 2 end the call with `too_many`.
+template <class Launch>
+int field_rounds(artp_field* f, int batch, const char* too_many, FieldRounds* out, Launch&& launch) {
+  artp_ctx* c = f->ctx;
+  hipStream_t st = c->stream;
+  unsigned* counters = f->d_flags + 2 * f->n_tiles;
+  const uint64_t cap = (uint64_t)f->n_nodes + 2;
+  unsigned seen = 0;
+  for (uint64_t round = 0;;) {
+    if (round > cap) {
+      c->last_error = too_many;
+      return ARTP_ERR_CAPACITY;
+    }
+    for (int b = 0; b < batch; ++b, ++round)
+      launch(f->d_flags + (round & 1) * f->n_tiles, f->d_flags + ((round + 1) & 1) * f->n_tiles, counters);
+    HIP_TRY(c, hipGetLastError());
+    unsigned now[3] = {0, 0, 0};
+    HIP_TRY(c, hipMemcpyAsync(now, counters, sizeof(now), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    *out = FieldRounds{round, now[1], now[2]};
+    if (now[0] == seen) return ARTP_OK;  // nothing flagged for the next round
+    seen = now[0];
+  }
+}
+
+// One pass of one rule (UNSUP = 0: relax, 1: unsupport; PHASE 0: distances, 1: hop counts) to its fixed point, in the
+// field's form.  The tiled form's first round runs the n_tiles flags of d_seed (artp_field_update: the tiles that changed
+// so far, which an unsupport pass adds to), or the tiles of the sources without one.
+template <int PHASE, bool UNSUP>
+int field_pass(artp_field* f, unsigned* d_seed, FieldRounds* out) {
   artp_ctx* c = f->ctx;
   hipStream_t st = c->stream;
   const artp::FieldGrid& G = f->grid;
-  unsigned* counters = f->d_flags + 2 * f->n_tiles;
+  const char* too_many = UNSUP ? "artp_field_update: more unsupport rounds than nodes" : "artp_field_compute: more rounds than nodes";
   HIP_TRY(c, hipMemsetAsync(f->d_flags, 0, (2 * f->n_tiles + 4) * sizeof(unsigned), st));
-  const uint64_t cap = (uint64_t)f->n_nodes + 2;  // sweep s settles every node whose best path has <= s edges
   if (f->params.plain_sweeps) {
     const unsigned blocks = (unsigned)((f->n_nodes + 255) / 256);
-    unsigned seen = 0;
-    for (uint64_t sweeps = 0;;) {
-      if (sweeps > cap) {
-        c->last_error = "artp_field_compute: more sweeps than nodes";
-        return ARTP_ERR_CAPACITY;
-      }
-      for (int r = 0; r < 16; ++r)
-        hipLaunchKernelGGL(artp::field_plain_kernel<PHASE>, dim3(blocks), dim3(256), 0, st, G, (const uint32_t*)f->d_mask,
-                           (const float*)f->d_h, (const double*)f->d_tab, f->d_dist, f->d_hops, counters);
-      HIP_TRY(c, hipGetLastError());
-      sweeps += 16;
-      (PHASE ? f->stats.hop_rounds : f->stats.plain_sweeps) = sweeps;
-      unsigned now = 0;
-      HIP_TRY(c, hipMemcpyAsync(&now, counters, sizeof(unsigned), hipMemcpyDeviceToHost, st));
-      HIP_TRY(c, hipStreamSynchronize(st));
-      if (now == seen) break;  // sixteen sweeps changed nothing
-      seen = now;
-    }
-    return ARTP_OK;
+    return field_rounds(f, 16, too_many, out, [&](unsigned*, unsigned*, unsigned* counters) {
+      hipLaunchKernelGGL(UNSUP ? artp::field_unsupport_plain_kernel<PHASE> : artp::field_plain_kernel<PHASE>, dim3(blocks),
+                         dim3(256), 0, st, G, (const uint32_t*)f->d_mask, (const float*)f->d_h, (const double*)f->d_tab,
+                         f->d_dist, f->d_hops, counters);
+    });
   }
   if (d_seed) {
     HIP_TRY(c, hipMemcpyAsync(f->d_flags, d_seed, f->n_tiles * sizeof(unsigned), hipMemcpyDeviceToDevice, st));
   } else {
-    hipLaunchKernelGGL(artp::field_seed_tiles_kernel, dim3((unsigned)((n_src + 63) / 64)), dim3(64), 0, st, G, d_src, n_src,
-                       f->d_flags);
+    const int n_src = (int)(f->h_src.size() / 3);
+    hipLaunchKernelGGL(artp::field_seed_tiles_kernel, dim3((unsigned)((n_src + 63) / 64)), dim3(64), 0, st, G,
+                       (const int*)f->d_nodes, n_src, f->d_flags);
     HIP_TRY(c, hipGetLastError());
   }
-  const size_t lds = artp::field_tile_lds(G.n_yaw, PHASE);
+  const size_t lds = artp::field_tile_lds(G.n_yaw, PHASE == 1 || UNSUP);
   // a workgroup may ask for more than 64 KB of dynamic LDS once the function says so (32 headings: 88 / 126 KB)
   if (lds > 64 * 1024)
-    HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&artp::field_tile_kernel<PHASE>),
+    HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&artp::field_tile_kernel<PHASE, UNSUP>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  unsigned seen[2] = {0, 0};
-  for (uint64_t round = 0;; ++round) {
-    if (round > cap) {
-      c->last_error = "artp_field_compute: more outer rounds than nodes";
-      return ARTP_ERR_CAPACITY;
-    }
-    unsigned* cur = f->d_flags + (round & 1) * f->n_tiles;
-    unsigned* nxt = f->d_flags + ((round + 1) & 1) * f->n_tiles;
-    hipLaunchKernelGGL(artp::field_tile_kernel<PHASE>, dim3((unsigned)f->n_tiles), dim3(256), lds, st, G,
+  return field_rounds(f, 1, too_many, out, [&](unsigned* cur, unsigned* nxt, unsigned* counters) {
+    hipLaunchKernelGGL((artp::field_tile_kernel<PHASE, UNSUP>), dim3((unsigned)f->n_tiles), dim3(256), lds, st, G,
                        (const uint32_t*)f->d_mask, (const float*)f->d_h, (const double*)f->d_tab, f->d_dist, f->d_hops, cur,
-                       nxt, counters, f->params.inner_sweeps);
-    HIP_TRY(c, hipGetLastError());
-    unsigned now[2] = {0, 0};
-    HIP_TRY(c, hipMemcpyAsync(now, counters, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    (PHASE ? f->stats.hop_rounds : f->stats.outer_rounds) = round + 1;
-    (PHASE ? f->stats.hop_tile_launches : f->stats.tile_launches) = now[1];
-    if (now[0] == seen[0]) break;  // nothing flagged for the next round
-    seen[0] = now[0];
-  }
+                       nxt, UNSUP ? d_seed : nullptr, counters, f->params.inner_sweeps);
+  });
+}
+
+int field_count_reached(artp_field* f, uint64_t* reached) {
+  artp_ctx* c = f->ctx;
+  hipStream_t st = c->stream;
+  unsigned long long* d_count = reinterpret_cast<unsigned long long*>(f->d_out);  // >= 8 doubles since the compute
+  HIP_TRY(c, hipMemsetAsync(d_count, 0, sizeof(unsigned long long), st));
+  hipLaunchKernelGGL(artp::field_count_kernel, dim3((unsigned)((f->n_nodes + 255) / 256)), dim3(256), 0, st, f->n_nodes,
+                     (const double*)f->d_dist, d_count);
+  HIP_TRY(c, hipGetLastError());
+  unsigned long long n = 0;
+  HIP_TRY(c, hipMemcpyAsync(&n, d_count, sizeof(n), hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipStreamSynchronize(st));
+  *reached = n;
   return ARTP_OK;
 }
 
@@ -898,20 +802,16 @@ int field_compute_impl(artp_ctx* c, artp_field* f, const uint32_t* mask, int mas
     c->last_error = "artp_field_compute: a source is not a node of the mask";
     return ARTP_ERR_INVALID_ARG;
   }
-  rc = field_search<0>(f, f->d_nodes, (int)n_sources);
+  FieldRounds dist_pass, hop_pass;
+  rc = field_pass<0, false>(f, nullptr, &dist_pass);
   if (rc) return rc;
-  rc = field_search<1>(f, f->d_nodes, (int)n_sources);
+  rc = field_pass<1, false>(f, nullptr, &hop_pass);
   if (rc) return rc;
-  unsigned long long* d_count = reinterpret_cast<unsigned long long*>(f->d_out);
-  HIP_TRY(c, hipMemsetAsync(d_count, 0, sizeof(unsigned long long), st));
-  hipLaunchKernelGGL(artp::field_count_kernel, dim3((unsigned)((f->n_nodes + 255) / 256)), dim3(256), 0, st, f->n_nodes,
-                     (const double*)f->d_dist, d_count);
-  HIP_TRY(c, hipGetLastError());
-  unsigned long long reached = 0;
-  HIP_TRY(c, hipMemcpyAsync(&reached, d_count, sizeof(reached), hipMemcpyDeviceToHost, st));
-  HIP_TRY(c, hipStreamSynchronize(st));
-  f->stats.reached_nodes = reached;
-  return ARTP_OK;
+  (f->params.plain_sweeps ? f->stats.plain_sweeps : f->stats.outer_rounds) = dist_pass.rounds;
+  f->stats.tile_launches = dist_pass.tile_runs;
+  f->stats.hop_rounds = hop_pass.rounds;
+  f->stats.hop_tile_launches = hop_pass.tile_runs;
+  return field_count_reached(f, &f->stats.reached_nodes);
 }
 
 int field_update_scratch(artp_field* f, bool stage) {
@@ -927,96 +827,31 @@ int field_update_scratch(artp_field* f, bool stage) {
   return ARTP_OK;
 }
 
-// One unsupport pass (PHASE 0: on distances, 1: on hop counts at the settled distances) until no node dies, over the
-// tiles flagged in d_acc (tiled form) or over every node (plain form).  Each round kills a node or is the last.
-template <int PHASE>
-int field_unsupport(artp_field* f, artp_field_update_stats_t* us, uint64_t* dead) {
-  artp_ctx* c = f->ctx;
-  hipStream_t st = c->stream;
-  const artp::FieldGrid& G = f->grid;
-  unsigned* counters = f->d_flags + 2 * f->n_tiles;
-  HIP_TRY(c, hipMemsetAsync(f->d_flags, 0, (2 * f->n_tiles + 4) * sizeof(unsigned), st));
-  const uint64_t cap = (uint64_t)f->n_nodes + 2;
-  unsigned now[3] = {0, 0, 0};
-  if (f->params.plain_sweeps) {
-    const unsigned blocks = (unsigned)((f->n_nodes + 255) / 256);
-    unsigned seen = 0;
-    for (uint64_t sweeps = 0;;) {
-      if (sweeps > cap) {
-        c->last_error = "artp_field_update: more unsupport sweeps than nodes";
-        return ARTP_ERR_CAPACITY;
-      }
-      for (int r = 0; r < 16; ++r)
-        hipLaunchKernelGGL(artp::field_unsupport_plain_kernel<PHASE>, dim3(blocks), dim3(256), 0, st, G,
-                           (const uint32_t*)f->d_mask, (const float*)f->d_h, (const double*)f->d_tab, f->d_dist, f->d_hops,
-                           counters);
-      HIP_TRY(c, hipGetLastError());
-      sweeps += 16;
-      us->unsupport_rounds += 16;
-      HIP_TRY(c, hipMemcpyAsync(now, counters, sizeof(now), hipMemcpyDeviceToHost, st));
-      HIP_TRY(c, hipStreamSynchronize(st));
-      *dead = now[2];
-      if (now[0] == seen) break;
-      seen = now[0];
-    }
-    return ARTP_OK;
-  }
-  HIP_TRY(c, hipMemcpyAsync(f->d_flags, f->d_acc, f->n_tiles * sizeof(unsigned), hipMemcpyDeviceToDevice, st));
-  const size_t lds = artp::field_tile_lds(G.n_yaw, 1);  // distances and hop counts in both phases: 126 KB at 32 headings
-  if (lds > 64 * 1024)
-    HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&artp::field_unsupport_tile_kernel<PHASE>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const uint64_t tiles0 = us->tile_launches;
-  unsigned seen = 0;
-  for (uint64_t round = 0;; ++round) {
-    if (round > cap) {
-      c->last_error = "artp_field_update: more unsupport rounds than nodes";
-      return ARTP_ERR_CAPACITY;
-    }
-    unsigned* cur = f->d_flags + (round & 1) * f->n_tiles;
-    unsigned* nxt = f->d_flags + ((round + 1) & 1) * f->n_tiles;
-    hipLaunchKernelGGL(artp::field_unsupport_tile_kernel<PHASE>, dim3((unsigned)f->n_tiles), dim3(256), lds, st, G,
-                       (const uint32_t*)f->d_mask, (const float*)f->d_h, (const double*)f->d_tab, f->d_dist, f->d_hops, cur,
-                       nxt, f->d_acc, counters, f->params.inner_sweeps);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(now, counters, sizeof(now), hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    us->unsupport_rounds += 1;
-    us->tile_launches = tiles0 + now[1];
-    *dead = now[2];
-    if (now[0] == seen) break;
-    seen = now[0];
-  }
-  return ARTP_OK;
-}
-
-// The passes of an update after the diff found a change.  f->stats takes the searches' counts on the way; the caller
-// moves them to the update's own numbers.
+// The passes of an update after the diff found a change: unsupport and relax on distances, then on hop counts, each from
+// the tiles flagged so far.
 int field_update_passes(artp_field* f, artp_field_update_stats_t* us) {
   artp_ctx* c = f->ctx;
   hipStream_t st = c->stream;
   HIP_TRY(c, hipMemcpyAsync(f->d_snap, f->d_dist, f->n_nodes * sizeof(double), hipMemcpyDeviceToDevice, st));
-  const int n_src = (int)(f->h_src.size() / 3);
-  int rc = field_unsupport<0>(f, us, &us->dead_nodes);
+  FieldRounds unsup[2], relax[2];
+  int rc = field_pass<0, true>(f, f->d_acc, &unsup[0]);
   if (rc) return rc;
-  rc = field_search<0>(f, f->d_src, n_src, f->d_acc);
+  rc = field_pass<0, false>(f, f->d_acc, &relax[0]);
   if (rc) return rc;
   hipLaunchKernelGGL(artp::field_hop_reset_kernel, dim3((unsigned)((f->n_nodes + 255) / 256)), dim3(256), 0, st, f->grid,
                      (const double*)f->d_dist, (const double*)f->d_snap, f->d_hops, f->d_acc);
   HIP_TRY(c, hipGetLastError());
-  rc = field_unsupport<1>(f, us, &us->hop_dead_nodes);
+  rc = field_pass<1, true>(f, f->d_acc, &unsup[1]);
   if (rc) return rc;
-  rc = field_search<1>(f, f->d_src, n_src, f->d_acc);
+  rc = field_pass<1, false>(f, f->d_acc, &relax[1]);
   if (rc) return rc;
-  HIP_TRY(c, hipMemsetAsync(f->d_ucnt, 0, sizeof(unsigned long long), st));
-  hipLaunchKernelGGL(artp::field_count_kernel, dim3((unsigned)((f->n_nodes + 255) / 256)), dim3(256), 0, st, f->n_nodes,
-                     (const double*)f->d_dist, f->d_ucnt);
-  HIP_TRY(c, hipGetLastError());
-  unsigned long long reached = 0;
-  HIP_TRY(c, hipMemcpyAsync(&reached, f->d_ucnt, sizeof(reached), hipMemcpyDeviceToHost, st));
-  HIP_TRY(c, hipStreamSynchronize(st));
-  us->reached_nodes = reached;
-  return ARTP_OK;
+  us->dead_nodes = unsup[0].deaths;
+  us->hop_dead_nodes = unsup[1].deaths;
+  us->unsupport_rounds = unsup[0].rounds + unsup[1].rounds;
+  us->dist_rounds = relax[0].rounds;
+  us->hop_rounds = relax[1].rounds;
+  us->tile_launches = unsup[0].tile_runs + relax[0].tile_runs + unsup[1].tile_runs + relax[1].tile_runs;
+  return field_count_reached(f, &us->reached_nodes);
 }
 
 }  // namespace
@@ -1245,19 +1080,12 @@ int artp_field_update(artp_field* f, const uint32_t* new_mask, int mask_on_devic
   us.added_nodes = cnt[2];
   us.reached_nodes = f->stats.reached_nodes;
   if (cnt[0] || cnt[3]) {
-    const artp_field_stats_t keep = f->stats;
-    f->stats.outer_rounds = f->stats.tile_launches = f->stats.plain_sweeps = f->stats.hop_rounds =
-        f->stats.hop_tile_launches = 0;
     rc = field_update_passes(f, &us);
-    us.dist_rounds = f->params.plain_sweeps ? f->stats.plain_sweeps : f->stats.outer_rounds;
-    us.hop_rounds = f->stats.hop_rounds;
-    us.tile_launches += f->stats.tile_launches + f->stats.hop_tile_launches;
-    f->stats = keep;  // the numbers of artp_field_compute stay; only reached_nodes follows the field
     if (rc) {
       (void)hipStreamSynchronize(st);
       return rc;
     }
-    f->stats.reached_nodes = us.reached_nodes;
+    f->stats.reached_nodes = us.reached_nodes;  // the other numbers of artp_field_compute stay
   }
   if (same_map) {  // artp_field_path's poses: the current sampler layers, as a new field would take them
     f->sampler = c->sampler;

@@ -190,6 +190,51 @@ def test_random_flips_across_tile_borders(ctx, n_yaw):
         assert stats[0]["changed_words"] == int(flip.any(axis=2).sum())
 
 
+FEW_RECT = (7, 5, 37, 45)                           # 3 x 3 tiles, partial ones on both edges
+FEW_SUB = (8, 10, 20, 20)
+FEW_SRC = (2, 3, 0)                                 # outside FEW_SUB
+
+
+def few_sweeps_masks(n_yaw):
+    """A random mask at density 0.8 over FEW_RECT and the same with random flips inside FEW_SUB, as bits."""
+    rng = np.random.default_rng(300 + n_yaw)
+    bits = rng.random((FEW_RECT[2], FEW_RECT[3], n_yaw)) < 0.8
+    bits[FEW_SRC] = True
+    new = bits.copy()
+    r0, c0, nr, nc = FEW_SUB
+    new[r0:r0 + nr, c0:c0 + nc] ^= rng.random((nr, nc, n_yaw)) < 0.15
+    return bits, new
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n_yaw", [1, 32])
+@pytest.mark.parametrize("inner_sweeps", [1, 3])
+def test_tiles_that_run_out_of_inner_sweeps_flag_themselves(ctx, inner_sweeps, n_yaw):
+    """inner_sweeps spent while a tile still changes: it flags itself and goes on in the next round (every other test runs
+    the default of 64).  The bits of the plain form and lattice_ref's values, after the compute (step 0 hands the same mask
+    in, so drive checks the computed fields) and after an update; with one inner sweep the search needs more outer rounds
+    than with 64 -- the tiles did come back."""
+    elev = np.ascontiguousarray(perlin_terrain(83, 0.05, seed=21)[:, :71]) * np.float32(0.8)
+    gm = device_map(ctx, elev, 0.05, pos=(0.3, 0.7))
+    bits, new = few_sweeps_masks(n_yaw)
+    old_m, new_m = pack(bits), pack(new)
+    for objective, reverse in ((0, False), (1, True)):
+        kw = dict(rect=FEW_RECT, objective=objective, reverse=reverse)
+        refs = {m.tobytes(): lattice(ctx, gm, m, n_yaw, FEW_RECT, objective).dijkstra([FEW_SRC], reverse)[0]
+                for m in (old_m, new_m)}
+        assert all(np.isfinite(r).sum() * 2 > bits.sum() for r in refs.values())   # the source reaches most of the nodes
+        stats, _ = drive(ctx, n_yaw, [FEW_SRC], old_m, [(old_m, None, False), (new_m, FEW_SUB, False)],
+                         ref=lambda m: refs[m.tobytes()], inner_sweeps=inner_sweeps, **kw)
+        assert stats[0]["changed_words"] == 0 and stats[1]["changed_words"] == int((bits ^ new).any(axis=2).sum())
+        if inner_sweeps == 1:
+            with ctx.cost_field(old_m, n_yaw, [FEW_SRC], inner_sweeps=1, **kw) as few, \
+                    ctx.cost_field(old_m, n_yaw, [FEW_SRC], **kw) as usual:
+                for step in range(2):                   # the compute's own numbers, which an update leaves alone
+                    print(f"  outer rounds: {few.stats()['outer_rounds']} at 1 inner sweep, {usual.stats()['outer_rounds']} at 64")
+                    assert few.stats()["outer_rounds"] > usual.stats()["outer_rounds"]
+                    few.update(new_m, FEW_SUB), usual.update(new_m, FEW_SUB)
+
+
 @pytest.mark.gpu
 def test_a_chain_of_five_updates_on_one_field(ctx):
     n, n_yaw = 50, 4
