@@ -21,7 +21,7 @@ SYMBOLS = [
     "artp_sample_and_validate", "artp_reachability_map", "artp_reachability_map_dev", "artp_reachability_poses",
     "artp_reachability_halo", "artp_field_params_defaults", "artp_field_compute", "artp_field_dist", "artp_field_dist_dev",
     "artp_field_path", "artp_field_edge_costs", "artp_field_stats", "artp_field_update", "artp_field_update_stats",
-    "artp_field_destroy", "artp_check_motions_last_valid", "artp_check_motions_last_valid_dev",
+    "artp_field_destroy", "artp_field_learned_params_defaults", "artp_field_compute_learned", "artp_field_learned_stats", "artp_check_motions_last_valid", "artp_check_motions_last_valid_dev",
     "artp_set_z_bounds", "artp_set_few_edges", "artp_set_edge_passes", "artp_cost_set_fc_path", "artp_check_motions", "artp_check_motions_dev", "artp_check_edges_interp",
     "artp_check_edges_interp_dev", "artp_compact_valid_dev", "artp_compact_valid_indices_dev", "artp_sample_states_at_dev",
     "artp_pack_edge_results_dev", "artp_cost_update_map_dev", "artp_pack_valid_bits_dev", "artp_indices_from_bits_dev",
@@ -112,6 +112,16 @@ class FieldStats(C.Structure):  # artp_field_stats_t
                                           "hop_tile_launches", "nodes", "tiles")]
 
 
+class FieldLearnedParams(C.Structure):  # artp_field_learned_params
+    _fields_ = [("w_energy", C.c_float), ("w_time", C.c_float), ("w_risk", C.c_float), ("risk_threshold", C.c_float),
+                ("plain_sweeps", C.c_int32), ("inner_sweeps", C.c_int32)]
+
+
+class FieldLearnedStats(C.Structure):  # artp_field_learned_stats_t
+    _fields_ = ([(n, C.c_uint64) for n in ("table_rows", "table_bytes", "chunks")] +
+                [(n, C.c_double) for n in ("rows_ms", "query_ms", "combine_ms", "dist_ms", "hop_ms")])
+
+
 class FieldUpdateStats(C.Structure):  # artp_field_update_stats_t
     _fields_ = [(n, C.c_uint64) for n in ("changed_words", "removed_nodes", "added_nodes", "dead_nodes", "hop_dead_nodes",
                                           "unsupport_rounds", "dist_rounds", "hop_rounds", "tile_launches",
@@ -200,6 +210,11 @@ def _load_path(LIB_PATH):
     L.artp_field_update.argtypes = [vp, vp, i32, vp, i32]
     L.artp_field_update_stats.argtypes = [vp, C.POINTER(FieldUpdateStats)]
     L.artp_field_destroy.argtypes = [vp]
+    L.artp_field_learned_params_defaults.argtypes = [C.POINTER(FieldLearnedParams)]
+    L.artp_field_learned_params_defaults.restype = None
+    L.artp_field_compute_learned.argtypes = [vp, C.POINTER(FieldLearnedParams), i32, vp, vp, i32, vp, sz, i32,
+                                             C.POINTER(vp)]
+    L.artp_field_learned_stats.argtypes = [vp, C.POINTER(FieldLearnedStats)]
     L.artp_field_destroy.restype = None
     L.artp_map_version.argtypes = [vp]
     L.artp_map_version.restype = C.c_uint64

@@ -245,6 +245,17 @@ class Context:
                          max_lon_vel=max_lon_vel, max_lat_vel=max_lat_vel, max_ang_vel=max_ang_vel,
                          plain_sweeps=plain_sweeps, inner_sweeps=inner_sweeps)
 
+    def learned_cost_field(self, mask, n_yaw, sources, *, rect=None, reverse=False, w_energy=None, w_time=None,
+                           w_risk=None, risk_threshold=None, plain_sweeps=False, inner_sweeps=64):
+        """cost_field under the learned motion cost (artp_field_compute_learned): every lattice
+        move is priced by the loaded network on the installed cost map (cost_load_weights, cost_update_map*), always on
+        the device.  The weights and the threshold default to the roadmap's (None).  The cost is not symmetric: reverse=True
+        is a different field.  Returns a CostField; its update() is refused."""
+        from .field import CostField
+        return CostField.learned(self, mask, n_yaw, sources, rect=rect, reverse=reverse, w_energy=w_energy, w_time=w_time,
+                                 w_risk=w_risk, risk_threshold=risk_threshold, plain_sweeps=plain_sweeps,
+                                 inner_sweeps=inner_sweeps)
+
     def check_edges_interp(self, s1, s2):
         s1 = np.ascontiguousarray(s1, np.float64).reshape(-1, 7)
         s2 = np.ascontiguousarray(s2, np.float64).reshape(-1, 7)

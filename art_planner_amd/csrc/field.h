@@ -41,6 +41,13 @@
 //   unsupport PHASE 0, relax PHASE 0 from the flagged tiles
 //   field_hop_reset_kernel   hops = NONE where dist differs from the snapshot taken before
 //   unsupport PHASE 1, relax PHASE 1 from the flagged tiles
+//
+// artp_field_compute_learned: objective 2, the motion-cost network.  The cost of a move depends on
+// the start cell's features and on both poses, so it sits in neither the (m, k) table nor eight registers: a per-field
+// table in global memory holds one f64 pull weight per (node, offset), tile-major (field_wtab_index), filled once per
+// call by field_learned_rows_kernel -> the context's cost query -> field_learned_combine_kernel in chunks of at most
+// FIELD_LEARNED_CHUNK rows.  The rules are the same ones; only the cost source differs (field_walk's branch, the LEARNED
+// parameter of the tile skeleton).  w(a -> b) != w(b -> a) here, rotations included.
 #pragma once
 
 namespace artp {
@@ -62,6 +69,19 @@ struct FieldGrid {
 
 __host__ __device__ constexpr int field_dr(int m) { return m < 3 ? -1 : (m < 5 ? 0 : 1); }
 __host__ __device__ constexpr int field_dc(int m) { return (m == 0 || m == 3 || m == 5) ? -1 : ((m == 1 || m == 6) ? 0 : 1); }
+
+// Objective 2's weight table: slot (v, j) = the weight of the edge the rules pull along at node v = (r, c, k) from its
+// neighbour u by offset j (forward: w(u -> v), reverse: w(v -> u)); +inf where that edge does not exist.  Tile-major,
+// [tile][k][j][lane] with lane = the cell inside the tile as field_tile_kernel numbers its lanes, edge tiles padded: the
+// 64 lanes of a wave read 64 consecutive doubles for one (k, j).
+constexpr size_t FIELD_LEARNED_CHUNK = size_t(1) << 22;  // rows of the cost query per chunk (scratch: 36 bytes a row)
+__host__ __device__ inline size_t field_wtab_index(const FieldGrid& G, int r, int c, int k, int j) {
+  const size_t tile = (size_t)(r / FIELD_T) + (size_t)(c / FIELD_T) * (size_t)G.tiles_r;
+  return ((tile * (size_t)G.n_yaw + (size_t)k) * 10 + (size_t)j) * (FIELD_T * FIELD_T) + (size_t)((r % FIELD_T) + (c % FIELD_T) * FIELD_T);
+}
+__host__ __device__ inline size_t field_wtab_slots(const FieldGrid& G) {
+  return (size_t)G.tiles_r * G.tiles_c * (size_t)G.n_yaw * 10 * (FIELD_T * FIELD_T);
+}
 
 // cost of translation move m (0..7) from a cell of height ha to one of height hb at heading k; tab in LDS or global
 __device__ __forceinline__ double field_move_cost(const FieldGrid& G, const double* tab, int m, int k, float ha, float hb) {
@@ -140,8 +160,12 @@ __device__ __forceinline__ bool field_neighbour(const FieldGrid& G, int r, int c
   return G.n_yaw > 1;
 }
 
+// the move that leads back: b = a's neighbour by move m  <=>  a = b's neighbour by move field_back_move(m)
+__host__ __device__ constexpr int field_back_move(int m) { return m < 8 ? 7 - m : (m == 8 ? 9 : 8); }
+
 // The live neighbours of node (cell, k) over the ten moves, for the kernels with one lane per node: visit(ni, w) with ni
-// the neighbour's node index (its cell and heading) and w() the pull cost of that move, computed when a rule asks.
+// the neighbour's node index (its cell and heading) and w() the pull cost of that move, computed when a rule asks
+// (objective 2: read from the weight table, which `tab` then is).
 template <class F>
 __device__ __forceinline__ void field_walk(const FieldGrid& G, const uint32_t* __restrict__ mask, const float* __restrict__ h,
                                            const double* __restrict__ tab, uint32_t cell, int k, F&& visit) {
@@ -152,7 +176,9 @@ __device__ __forceinline__ void field_walk(const FieldGrid& G, const uint32_t* _
     if (!field_neighbour(G, r, c, k, m, &nr, &nc, &nk)) continue;
     const uint32_t ncell = m < 8 ? (uint32_t)nr + (uint32_t)nc * (uint32_t)G.nrows : cell;  // a rotation: the node's own word
     if (!((mask[ncell] >> nk) & 1u)) continue;
-    visit((size_t)ncell * G.n_yaw + nk, [&]() { return field_pull_cost(G, tab, m, k, h[cell], h[ncell]); });
+    visit((size_t)ncell * G.n_yaw + nk, [&]() {
+      return G.objective == 2 ? tab[field_wtab_index(G, r, c, k, m)] : field_pull_cost(G, tab, m, k, h[cell], h[ncell]);
+    });
   }
 }
 
@@ -275,9 +301,10 @@ __device__ __forceinline__ void field_tile_walk(const FieldGrid& G, const FieldL
 }
 
 // One of the four rules on heading k of the lane's cell, inside LDS; true when the node changed.
-template <int PHASE, bool UNSUP>
-__device__ __forceinline__ bool field_tile_rule(const FieldGrid& G, const FieldLane& L, const double* stab, double* sd,
-                                                uint32_t* shop, int k) {
+// LEARNED: the ten pull weights of this heading are wl[0..9], the lane's slots of the weight table.
+template <int PHASE, bool UNSUP, bool LEARNED>
+__device__ __forceinline__ bool field_tile_rule(const FieldGrid& G, const FieldLane& L, const double* stab, const double* wl,
+                                                double* sd, uint32_t* shop, int k) {
   const int own = k * FIELD_PLANE + L.me;
   const double old = sd[own];
   if (UNSUP) {
@@ -289,7 +316,7 @@ __device__ __forceinline__ bool field_tile_rule(const FieldGrid& G, const FieldL
       field_tile_walk(G, L, k, [&](int li, int m) {
         const uint32_t hu = shop[li];
         if (hu == FIELD_NONE || hu + 1u != hv) return;
-        if (sd[li] + field_lane_cost(G, L, stab, m, k) == old) sup = true;
+        if (sd[li] + (LEARNED ? wl[m] : field_lane_cost(G, L, stab, m, k)) == old) sup = true;
       });
     if (sup) return false;
     if (PHASE == 0) sd[own] = INFINITY;
@@ -299,7 +326,7 @@ __device__ __forceinline__ bool field_tile_rule(const FieldGrid& G, const FieldL
   if (PHASE == 0) {
     double best = old;
     field_tile_walk(G, L, k, [&](int li, int m) {
-      const double cand = sd[li] + field_lane_cost(G, L, stab, m, k);
+      const double cand = sd[li] + (LEARNED ? wl[m] : field_lane_cost(G, L, stab, m, k));
       if (cand < best) best = cand;
     });
     if (best < old) sd[own] = best;
@@ -311,7 +338,7 @@ __device__ __forceinline__ bool field_tile_rule(const FieldGrid& G, const FieldL
   field_tile_walk(G, L, k, [&](int li, int m) {
     const uint32_t hu = shop[li];
     if (hu == FIELD_NONE || hu + 1u >= hb) return;
-    if (sd[li] + field_lane_cost(G, L, stab, m, k) == old) hb = hu + 1u;
+    if (sd[li] + (LEARNED ? wl[m] : field_lane_cost(G, L, stab, m, k)) == old) hb = hu + 1u;
   });
   if (hb < hold) shop[own] = hb;
   return hb < hold;
@@ -321,7 +348,9 @@ __device__ __forceinline__ bool field_tile_rule(const FieldGrid& G, const FieldL
 // (writes hops back, and dist in PHASE 0; every change of a rule is a death).  counters[0] += flags set for the next
 // round, [1] += tiles that ran, [2] += nodes that died (all cumulative over the host's loop).  acc collects, over a whole
 // update, the tiles whose own cells or halo an unsupport pass changed: the seeds of the relax pass that follows.
-template <int PHASE, bool UNSUP>
+// LEARNED (objective 2): tabg is the weight table.  It is streamed from global memory, not staged: at 16 headings a tile's
+// weights are 328 KB.  The ten loads of a heading are issued in front of that heading's LDS reads.
+template <int PHASE, bool UNSUP, bool LEARNED = false>
 __global__ void __launch_bounds__(256)
 field_tile_kernel(FieldGrid G, const uint32_t* __restrict__ mask, const float* __restrict__ h,
                   const double* __restrict__ tabg, double* dist, uint32_t* hops, unsigned* act_cur, unsigned* act_nxt,
@@ -356,7 +385,8 @@ field_tile_kernel(FieldGrid G, const uint32_t* __restrict__ mask, const float* _
     sd[k * FIELD_PLANE + ci] = in ? dist[node] : (double)INFINITY;
     if (HOPS) shop[k * FIELD_PLANE + ci] = in ? hops[node] : FIELD_NONE;
   }
-  for (int e = tid; e < FIELD_TAB; e += 256) stab[e] = tabg[e];
+  if (!LEARNED)
+    for (int e = tid; e < FIELD_TAB; e += 256) stab[e] = tabg[e];
   if (tid < 2) sflag[tid] = 0u;
   __syncthreads();
 
@@ -368,7 +398,7 @@ field_tile_kernel(FieldGrid G, const uint32_t* __restrict__ mask, const float* _
   for (int j = 0; j < 8; ++j) {
     const int nb = L.me + field_dr(j) + field_dc(j) * FIELD_HP;
     L.nbm[j] = smask[nb];
-    L.w8[j] = G.objective == 0 ? field_pull_cost(G, stab, j, 0, sh[L.me], sh[nb]) : 0.0;
+    L.w8[j] = !LEARNED && G.objective == 0 ? field_pull_cost(G, stab, j, 0, sh[L.me], sh[nb]) : 0.0;
   }
   L.widx0 = G.reverse ? 0 : 7;
   L.wsgn = G.reverse ? 1 : -1;
@@ -381,7 +411,13 @@ field_tile_kernel(FieldGrid G, const uint32_t* __restrict__ mask, const float* _
     bool ch = false;
     for (int k = 0; k < ny; ++k) {
       if (!((L.mw >> k) & 1u)) continue;
-      if (field_tile_rule<PHASE, UNSUP>(G, L, stab, sd, shop, k)) {
+      double wl[10];
+      if (LEARNED) {  // the lane's slots (tile, k, j): 64 consecutive doubles per wave and j
+        const double* wk = tabg + ((size_t)tile * ny + k) * (10 * FIELD_T * FIELD_T) + tid;
+#pragma unroll
+        for (int j = 0; j < 10; ++j) wl[j] = wk[j * (FIELD_T * FIELD_T)];
+      }
+      if (field_tile_rule<PHASE, UNSUP, LEARNED>(G, L, stab, wl, sd, shop, k)) {
         ch = true;
         ++changes;
       }
@@ -469,7 +505,8 @@ field_path_kernel(FieldGrid G, const uint32_t* __restrict__ mask, const float* _
       const size_t ncell = (size_t)nr + (size_t)nc * G.nrows;
       if ((mask[ncell] >> nk) & 1u) {
         const size_t ni = ncell * G.n_yaw + nk;
-        const double w = field_pull_cost(G, tab, lane, k, h[(size_t)r + (size_t)c * G.nrows], h[ncell]);
+        const double w = G.objective == 2 ? tab[field_wtab_index(G, r, c, k, lane)]
+                                          : field_pull_cost(G, tab, lane, k, h[(size_t)r + (size_t)c * G.nrows], h[ncell]);
         ok = hops[ni] + 1u == hv && dist[ni] + w == dv;
       }
     }
@@ -517,12 +554,86 @@ field_edge_cost_kernel(FieldGrid G, const float* __restrict__ h, const double* _
     for (int m = 0; m < 10; ++m) {
       int nr, nc, nk;
       if (!field_neighbour(G, r, c, k, m, &nr, &nc, &nk) || nr != br || nc != bc || nk != bk) continue;
-      w = m < 8 ? field_move_cost(G, tab, m, k, h[(size_t)r + (size_t)c * G.nrows], h[(size_t)br + (size_t)bc * G.nrows])
-                : G.wrot;
+      if (G.objective == 2)  // the travel-direction cost of a -> b, where the field's direction stores it
+        w = G.reverse ? tab[field_wtab_index(G, r, c, k, m)] : tab[field_wtab_index(G, br, bc, bk, field_back_move(m))];
+      else
+        w = m < 8 ? field_move_cost(G, tab, m, k, h[(size_t)r + (size_t)c * G.nrows], h[(size_t)br + (size_t)bc * G.nrows])
+                  : G.wrot;
       break;
     }
   }
   out[i] = w;
+}
+
+// ---- objective 2: the weight table -------------------------------------------------------------------------------
+
+// Slot s of the weight table -> the edge it holds: false where the edge does not exist (a padded lane, an end outside the
+// rectangle or missing from the mask); else the pose indices (reach.h's order) of its start and target.
+__device__ __forceinline__ bool field_slot_edge(const FieldGrid& G, const uint32_t* __restrict__ mask, size_t s, uint32_t* from,
+                                                uint32_t* to) {
+  const int lane = (int)(s % (FIELD_T * FIELD_T));
+  size_t t = s / (FIELD_T * FIELD_T);
+  const int j = (int)(t % 10);
+  t /= 10;
+  const int k = (int)(t % (size_t)G.n_yaw);
+  const size_t tile = t / (size_t)G.n_yaw;
+  const int r = (int)(tile % (size_t)G.tiles_r) * FIELD_T + (lane & (FIELD_T - 1));
+  const int c = (int)(tile / (size_t)G.tiles_r) * FIELD_T + (lane >> 4);
+  if (r >= G.nrows || c >= G.ncols) return false;
+  int nr, nc, nk;
+  if (!field_neighbour(G, r, c, k, j, &nr, &nc, &nk)) return false;
+  const uint32_t cell = (uint32_t)r + (uint32_t)c * (uint32_t)G.nrows, ncell = (uint32_t)nr + (uint32_t)nc * (uint32_t)G.nrows;
+  if (!((mask[cell] >> k) & 1u) || !((mask[ncell] >> nk) & 1u)) return false;
+  const uint32_t v = cell * (uint32_t)G.n_yaw + (uint32_t)k, u = ncell * (uint32_t)G.n_yaw + (uint32_t)nk;
+  *from = G.reverse ? v : u;
+  *to = G.reverse ? u : v;
+  return true;
+}
+
+// One EdgeMatrix row per slot first .. first + n - 1: chain_edge_matrix_kernel's row of a chain of one sub-edge between the
+// lattice poses of the two nodes -- target (x, y, yaw) then start (x, y, yaw), as floats.  A slot without an edge gets a
+// row of zeros (the query clamps its cell; the combine kernel discards the answer).
+__global__ void __launch_bounds__(256)
+field_learned_rows_kernel(FieldGrid G, SamplerDev sm, MapGeom g, ReachRect rc, const uint32_t* __restrict__ mask, size_t first,
+                          uint32_t n, float* __restrict__ rows) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  float row[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  uint32_t from, to;
+  if (field_slot_edge(G, mask, first + i, &from, &to)) {
+    double a[7], b[7];
+    reach_lattice_pose(sm, g, rc, from, a);
+    reach_lattice_pose(sm, g, rc, to, b);
+    row[0] = (float)b[0];
+    row[1] = (float)b[1];
+    row[2] = (float)yaw_from_quat(b + 3);
+    row[3] = (float)a[0];
+    row[4] = (float)a[1];
+    row[5] = (float)yaw_from_quat(a + 3);
+  }
+#pragma unroll
+  for (int q = 0; q < 6; ++q) rows[6 * (size_t)i + q] = row[q];
+}
+
+// chain_motion_cost_kernel's pricing of a chain of one sub-edge; an edge whose cost is negative or NaN does not exist
+// (the rule of the roadmap's device search: the fixed point is unique for weights >= 0 only).
+__global__ void __launch_bounds__(256)
+field_learned_combine_kernel(FieldGrid G, const uint32_t* __restrict__ mask, size_t first, uint32_t n,
+                             const float* __restrict__ cost3, float w_energy, float w_time, float w_risk, float risk_threshold,
+                             double* __restrict__ wtab) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  double w = INFINITY;
+  uint32_t from, to;
+  if (field_slot_edge(G, mask, first + i, &from, &to)) {
+    const float* c = cost3 + 3 * (size_t)i;
+    const double en = c[0], ti = c[1], ri = c[2];
+    double total = 0.0;
+    total += en * w_energy + ti * w_time + ri * w_risk;
+    w = ri <= (double)risk_threshold ? total : (double)INFINITY;
+    if (!(w >= 0.0)) w = INFINITY;
+  }
+  wtab[first + i] = w;
 }
 
 // ---- artp_field_update ------------------------------------------------------------------------------------------
@@ -632,6 +743,10 @@ struct artp_field {
   unsigned long long* d_ucnt = nullptr; // the eight counts of the diff
   uint32_t* d_stage = nullptr;          // a host mask's sub-rectangle, in the field's layout
   artp_field_update_stats_t ustats{};
+  // artp_field_compute_learned: d_tab is the weight table (field_wtab_slots doubles); the scratch lives during the build
+  artp_field_learned_params lparams{};
+  artp_field_learned_stats_t lstats{};
+  float* d_lscratch = nullptr;          // per chunk: 6 floats of EdgeMatrix row, then 3 floats of answer, per row
 };
 
 namespace {
@@ -639,7 +754,7 @@ namespace {
 void field_free(artp_field* f) {
   for (void* p : {(void*)f->d_dist, (void*)f->d_hops, (void*)f->d_mask, (void*)f->d_h, (void*)f->d_tab, (void*)f->d_flags,
                   (void*)f->d_nodes, (void*)f->d_out, (void*)f->d_src, (void*)f->d_snap, (void*)f->d_acc, (void*)f->d_ucnt,
-                  (void*)f->d_stage})
+                  (void*)f->d_stage, (void*)f->d_lscratch})
     if (p) (void)hipFree(p);
   delete f;
 }
@@ -741,12 +856,16 @@ int field_pass(artp_field* f, unsigned* d_seed, FieldRounds* out) {
     HIP_TRY(c, hipGetLastError());
   }
   const size_t lds = artp::field_tile_lds(G.n_yaw, PHASE == 1 || UNSUP);
+  auto kernel = &artp::field_tile_kernel<PHASE, UNSUP, false>;
+  if constexpr (!UNSUP) {  // a learned field is never updated in place
+    if (G.objective == 2) kernel = &artp::field_tile_kernel<PHASE, false, true>;
+  }
   // a workgroup may ask for more than 64 KB of dynamic LDS once the function says so (32 headings: 88 / 126 KB)
   if (lds > 64 * 1024)
-    HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&artp::field_tile_kernel<PHASE, UNSUP>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)lds));
   return field_rounds(f, 1, too_many, out, [&](unsigned* cur, unsigned* nxt, unsigned* counters) {
-    hipLaunchKernelGGL((artp::field_tile_kernel<PHASE, UNSUP>), dim3((unsigned)f->n_tiles), dim3(256), lds, st, G,
+    hipLaunchKernelGGL(kernel, dim3((unsigned)f->n_tiles), dim3(256), lds, st, G,
                        (const uint32_t*)f->d_mask, (const float*)f->d_h, (const double*)f->d_tab, f->d_dist, f->d_hops, cur,
                        nxt, UNSUP ? d_seed : nullptr, counters, f->params.inner_sweeps);
   });
@@ -767,15 +886,86 @@ int field_count_reached(artp_field* f, uint64_t* reached) {
   return ARTP_OK;
 }
 
+// Objective 2: fill the weight table f->d_tab from f->d_mask, in chunks of at most FIELD_LEARNED_CHUNK rows: the rows, the
+// context's own cost query (always the device network: the kernels artp_cost_query_dev launches, on the context's stream,
+// whatever artp_cost_set_external_query installed), the combination.
+int field_learned_table(artp_ctx* c, artp_field* f) {
+  hipStream_t st = c->stream;
+  const artp::FieldGrid& G = f->grid;
+  const artp_field_learned_params& lp = f->lparams;
+  const size_t slots = artp::field_wtab_slots(G);
+  const size_t chunk = slots < artp::FIELD_LEARNED_CHUNK ? slots : artp::FIELD_LEARNED_CHUNK;
+  HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&f->d_lscratch), chunk * 9 * sizeof(float)));
+  float* rows = f->d_lscratch;
+  float* cost3 = f->d_lscratch + chunk * 6;
+  std::vector<hipEvent_t> ev;
+  int rc = ARTP_OK;
+  for (size_t first = 0; first < slots && rc == ARTP_OK; first += chunk) {
+    const uint32_t n = (uint32_t)(slots - first < chunk ? slots - first : chunk);
+    const unsigned blocks = (n + 255) / 256;
+    for (int e = 0; e < 4; ++e) {
+      hipEvent_t x = nullptr;
+      if (hipEventCreate(&x) != hipSuccess) x = nullptr;
+      ev.push_back(x);
+    }
+    hipEvent_t* e4 = ev.data() + ev.size() - 4;
+    if (e4[0]) (void)hipEventRecord(e4[0], st);
+    hipLaunchKernelGGL(artp::field_learned_rows_kernel, dim3(blocks), dim3(256), 0, st, G, f->sampler, f->geom, f->rect,
+                       (const uint32_t*)f->d_mask, first, n, rows);
+    if (e4[1]) (void)hipEventRecord(e4[1], st);
+    rc = artp_cost_query_dev(c, rows, n, cost3);
+    if (rc) break;
+    if (e4[2]) (void)hipEventRecord(e4[2], st);
+    hipLaunchKernelGGL(artp::field_learned_combine_kernel, dim3(blocks), dim3(256), 0, st, G, (const uint32_t*)f->d_mask, first, n,
+                       (const float*)cost3, lp.w_energy, lp.w_time, lp.w_risk, lp.risk_threshold, f->d_tab);
+    if (e4[3]) (void)hipEventRecord(e4[3], st);
+    if (hipGetLastError() != hipSuccess) rc = ARTP_ERR_HIP;
+    ++f->lstats.chunks;
+  }
+  if (hipStreamSynchronize(st) != hipSuccess && rc == ARTP_OK) rc = ARTP_ERR_HIP;
+  for (size_t i = 0; i + 3 < ev.size(); i += 4) {
+    float ms[3] = {0.f, 0.f, 0.f};
+    for (int q = 0; q < 3; ++q)
+      if (rc == ARTP_OK && ev[i + q] && ev[i + q + 1] && hipEventElapsedTime(&ms[q], ev[i + q], ev[i + q + 1]) != hipSuccess)
+        ms[q] = 0.f;
+    f->lstats.rows_ms += ms[0];
+    f->lstats.query_ms += ms[1];
+    f->lstats.combine_ms += ms[2];
+  }
+  for (hipEvent_t x : ev)
+    if (x) (void)hipEventDestroy(x);
+  (void)hipGetLastError();
+  if (rc == ARTP_ERR_HIP && c->last_error.empty()) c->last_error = "artp_field_compute_learned: building the weight table failed";
+  if (rc) return rc;
+  HIP_TRY(c, hipFree(f->d_lscratch));
+  f->d_lscratch = nullptr;
+  f->lstats.table_rows = slots;
+  f->lstats.table_bytes = slots * sizeof(double);
+  return ARTP_OK;
+}
+
 int field_compute_impl(artp_ctx* c, artp_field* f, const uint32_t* mask, int mask_on_device, const int* sources,
                        size_t n_sources) {
   hipStream_t st = c->stream;
   const artp::FieldGrid& G = f->grid;
+  const bool learned = G.objective == 2;
+  const size_t tab_doubles = learned ? artp::field_wtab_slots(G) : (size_t)artp::FIELD_TAB;
+  if (learned) {  // 80 bytes per node and the padding of the edge tiles, plus a chunk of scratch
+    const size_t chunk = tab_doubles < artp::FIELD_LEARNED_CHUNK ? tab_doubles : artp::FIELD_LEARNED_CHUNK;
+    const size_t need = tab_doubles * sizeof(double) + chunk * 9 * sizeof(float) + f->n_nodes * 12 + f->n_cells * 8;
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(c, hipMemGetInfo(&free_b, &total_b));
+    if (need > free_b) {
+      c->last_error = "artp_field_compute_learned: the weight table needs " + std::to_string(need >> 20) + " MB, the device has " +
+                      std::to_string(free_b >> 20) + " MB free";
+      return ARTP_ERR_CAPACITY;
+    }
+  }
   HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&f->d_dist), f->n_nodes * sizeof(double)));
   HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&f->d_hops), f->n_nodes * sizeof(uint32_t)));
   HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&f->d_mask), f->n_cells * sizeof(uint32_t)));
   HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&f->d_h), f->n_cells * sizeof(float)));
-  HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&f->d_tab), artp::FIELD_TAB * sizeof(double)));
+  HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&f->d_tab), tab_doubles * sizeof(double)));
   HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&f->d_flags), (2 * f->n_tiles + 4) * sizeof(unsigned)));
   int rc = field_ensure_scratch(f, 3 * n_sources, 8);
   if (rc) return rc;
@@ -783,7 +973,7 @@ int field_compute_impl(artp_ctx* c, artp_field* f, const uint32_t* mask, int mas
   field_make_table(f->params, f->geom, G.n_yaw, tab);
   HIP_TRY(c, hipMemcpyAsync(f->d_mask, mask, f->n_cells * sizeof(uint32_t),
                             mask_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
-  HIP_TRY(c, hipMemcpyAsync(f->d_tab, tab, sizeof(tab), hipMemcpyHostToDevice, st));
+  if (!learned) HIP_TRY(c, hipMemcpyAsync(f->d_tab, tab, sizeof(tab), hipMemcpyHostToDevice, st));
   HIP_TRY(c, hipMemcpyAsync(f->d_nodes, sources, 3 * n_sources * sizeof(int), hipMemcpyHostToDevice, st));
   f->h_src.assign(sources, sources + 3 * n_sources);  // d_nodes becomes path scratch; artp_field_update needs them
   HIP_TRY(c, hipMemsetAsync(f->d_flags, 0, (2 * f->n_tiles + 4) * sizeof(unsigned), st));
@@ -802,11 +992,19 @@ int field_compute_impl(artp_ctx* c, artp_field* f, const uint32_t* mask, int mas
     c->last_error = "artp_field_compute: a source is not a node of the mask";
     return ARTP_ERR_INVALID_ARG;
   }
+  if (learned) {
+    rc = field_learned_table(c, f);
+    if (rc) return rc;
+  }
   FieldRounds dist_pass, hop_pass;
+  const auto t0 = std::chrono::steady_clock::now();
   rc = field_pass<0, false>(f, nullptr, &dist_pass);
   if (rc) return rc;
+  const auto t1 = std::chrono::steady_clock::now();
   rc = field_pass<1, false>(f, nullptr, &hop_pass);
   if (rc) return rc;
+  f->lstats.dist_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
+  f->lstats.hop_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
   (f->params.plain_sweeps ? f->stats.plain_sweeps : f->stats.outer_rounds) = dist_pass.rounds;
   f->stats.tile_launches = dist_pass.tile_runs;
   f->stats.hop_rounds = hop_pass.rounds;
@@ -854,6 +1052,20 @@ int field_update_passes(artp_field* f, artp_field_update_stats_t* us) {
   return field_count_reached(f, &us->reached_nodes);
 }
 
+int field_check_sources(artp_ctx* c, const artp::ReachRect& r, int n_yaw, const int* sources, size_t n_sources) {
+  for (size_t i = 0; i < n_sources; ++i) {
+    const int sr = sources[3 * i], sc = sources[3 * i + 1], sk = sources[3 * i + 2];
+    if (sr < 0 || sr >= r.nrows || sc < 0 || sc >= r.ncols || sk < 0 || sk >= n_yaw) {
+      c->last_error = "artp_field_compute: a source lies outside the rectangle or its heading outside [0, n_yaw)";
+      return ARTP_ERR_INVALID_ARG;
+    }
+  }
+  return ARTP_OK;
+}
+
+int field_create(artp_ctx* c, const artp_field_params& params, const artp_field_learned_params* lp, const artp::ReachRect& r,
+                 const uint32_t* mask, int mask_on_device, const int* sources, size_t n_sources, int reverse, artp_field** out);
+
 }  // namespace
 
 extern "C" {
@@ -888,17 +1100,81 @@ int artp_field_compute(artp_ctx* c, const artp_field_params* params, int n_yaw, 
     c->last_error = "artp_field_compute: velocities must be positive and finite, inner_sweeps >= 1, n_sources <= 2^24";
     return ARTP_ERR_INVALID_ARG;
   }
-  for (size_t i = 0; i < n_sources; ++i) {
-    const int sr = sources[3 * i], sc = sources[3 * i + 1], sk = sources[3 * i + 2];
-    if (sr < 0 || sr >= r.nrows || sc < 0 || sc >= r.ncols || sk < 0 || sk >= n_yaw) {
-      c->last_error = "artp_field_compute: a source lies outside the rectangle or its heading outside [0, n_yaw)";
+  rc = field_check_sources(c, r, n_yaw, sources, n_sources);
+  if (rc) return rc;
+  return field_create(c, *params, nullptr, r, mask, mask_on_device, sources, n_sources, reverse, out);
+}
+
+void artp_field_learned_params_defaults(artp_field_learned_params* p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof(*p));
+  artp_roadmap_params rp;
+  artp_roadmap_params_defaults(&rp);  // Params::planner.prm_motion_cost.cost_weights and risk_threshold
+  p->w_energy = rp.w_energy;
+  p->w_time = rp.w_time;
+  p->w_risk = rp.w_risk;
+  p->risk_threshold = rp.risk_threshold;
+  p->plain_sweeps = 0;
+  p->inner_sweeps = 64;
+}
+
+int artp_field_compute_learned(artp_ctx* c, const artp_field_learned_params* params, int n_yaw, const int* rect,
+                               const uint32_t* mask, int mask_on_device, const int* sources, size_t n_sources, int reverse,
+                               artp_field** out) {
+  if (out) *out = nullptr;
+  if (!c || !params || !mask || !sources || !out || n_sources < 1) return ARTP_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> lock(c->mu);
+  if (!c->have_weights) {
+    c->last_error = "artp_field_compute_learned: artp_cost_load_weights has not been called";
+    return ARTP_ERR_NO_WEIGHTS;
+  }
+  if (!c->have_features) {
+    c->last_error = "artp_field_compute_learned: artp_cost_update_map has not been called";
+    return ARTP_ERR_NO_MAP;
+  }
+  if (!reach_have_lattice(c)) return ARTP_ERR_NO_MAP;
+  artp::ReachRect r;
+  int rc = reach_resolve(c, n_yaw, rect, &r);
+  if (rc) return rc;
+  const float wt[4] = {params->w_energy, params->w_time, params->w_risk, params->risk_threshold};
+  for (float v : wt)
+    if (!(v >= 0.0f) || !std::isfinite(v)) {
+      c->last_error = "artp_field_compute_learned: the weights and the risk threshold must be non-negative and finite";
       return ARTP_ERR_INVALID_ARG;
     }
+  if (params->inner_sweeps < 1 || n_sources > (size_t)1 << 24) {
+    c->last_error = "artp_field_compute_learned: inner_sweeps >= 1, n_sources <= 2^24";
+    return ARTP_ERR_INVALID_ARG;
   }
+  rc = field_check_sources(c, r, n_yaw, sources, n_sources);
+  if (rc) return rc;
+  artp_field_params fp;
+  artp_field_params_defaults(&fp);  // the velocities are not used
+  fp.objective = 2;
+  fp.plain_sweeps = params->plain_sweeps;
+  fp.inner_sweeps = params->inner_sweeps;
+  return field_create(c, fp, params, r, mask, mask_on_device, sources, n_sources, reverse, out);
+}
+
+int artp_field_learned_stats(artp_field* f, artp_field_learned_stats_t* out) {
+  if (!f || !out) return ARTP_ERR_INVALID_ARG;
+  *out = f->lstats;
+  return ARTP_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// the part of artp_field_compute and artp_field_compute_learned behind their checks (lp: objective 2 only)
+int field_create(artp_ctx* c, const artp_field_params& params, const artp_field_learned_params* lp, const artp::ReachRect& r,
+                 const uint32_t* mask, int mask_on_device, const int* sources, size_t n_sources, int reverse, artp_field** out) {
+  const int n_yaw = r.n_yaw;
   HIP_TRY(c, hipSetDevice(c->device));
   artp_field* f = new artp_field;
   f->ctx = c;
-  f->params = *params;
+  f->params = params;
+  if (lp) f->lparams = *lp;
   f->rect = r;
   f->geom = c->geom;
   f->sampler = c->sampler;
@@ -911,15 +1187,15 @@ int artp_field_compute(artp_ctx* c, const artp_field_params* params, int n_yaw, 
   G.n_yaw = n_yaw;
   G.tiles_r = (r.nrows + artp::FIELD_T - 1) / artp::FIELD_T;
   G.tiles_c = (r.ncols + artp::FIELD_T - 1) / artp::FIELD_T;
-  G.objective = params->objective;
+  G.objective = params.objective;
   G.reverse = reverse ? 1 : 0;
   G.yaw_bits = n_yaw == 32 ? 0xffffffffu : (1u << n_yaw) - 1u;
-  G.vlon = params->max_lon_vel;
-  G.wrot = params->objective == 0 ? 0.0 : (2.0 * 3.14159265358979323846 / (double)n_yaw) / params->max_ang_vel;
+  G.vlon = params.max_lon_vel;
+  G.wrot = params.objective == 0 ? 0.0 : (2.0 * 3.14159265358979323846 / (double)n_yaw) / params.max_ang_vel;
   f->n_tiles = (size_t)G.tiles_r * G.tiles_c;
   f->stats.nodes = f->n_nodes;
   f->stats.tiles = f->n_tiles;
-  rc = field_compute_impl(c, f, mask, mask_on_device, sources, n_sources);
+  const int rc = field_compute_impl(c, f, mask, mask_on_device, sources, n_sources);
   if (rc) {
     (void)hipStreamSynchronize(c->stream);
     field_free(f);
@@ -928,6 +1204,10 @@ int artp_field_compute(artp_ctx* c, const artp_field_params* params, int n_yaw, 
   *out = f;
   return ARTP_OK;
 }
+
+}  // namespace
+
+extern "C" {
 
 int artp_field_dist(artp_field* f, double* dist_out) {
   if (!f || !dist_out) return ARTP_ERR_INVALID_ARG;
@@ -1032,6 +1312,11 @@ int artp_field_update(artp_field* f, const uint32_t* new_mask, int mask_on_devic
   artp_ctx* c = f->ctx;
   std::lock_guard<std::recursive_mutex> lock(c->mu);
   const artp::FieldGrid& G = f->grid;
+  if (G.objective == 2) {
+    c->last_error = "artp_field_update: a learned field cannot be updated in place (a map change moves the network's "
+                    "features, and with them the weights, far beyond sub_rect): compute a new one";
+    return ARTP_ERR_INVALID_ARG;
+  }
   artp::FieldSub sub{0, 0, G.nrows, G.ncols};
   if (sub_rect) sub = artp::FieldSub{sub_rect[0], sub_rect[1], sub_rect[2], sub_rect[3]};
   if (sub.nrows < 1 || sub.ncols < 1 || sub.row0 < 0 || sub.col0 < 0 || sub.row0 > G.nrows - sub.nrows ||

@@ -13,21 +13,39 @@ class CostField:
 
     def __init__(self, ctx, mask, n_yaw, sources, rect=None, reverse=False, objective=1, max_lon_vel=0.5,
                  max_lat_vel=0.1, max_ang_vel=0.5, plain_sweeps=False, inner_sweeps=64):
+        p = _capi.FieldParams()
+        ctx.L.artp_field_params_defaults(C.byref(p))
+        p.objective, p.plain_sweeps, p.inner_sweeps = int(objective), int(bool(plain_sweeps)), int(inner_sweeps)
+        p.max_lon_vel, p.max_lat_vel, p.max_ang_vel = max_lon_vel, max_lat_vel, max_ang_vel
+        self._compute(ctx, ctx.L.artp_field_compute, "artp_field_compute", p, mask, n_yaw, sources, rect, reverse)
+
+    @classmethod
+    def learned(cls, ctx, mask, n_yaw, sources, rect=None, reverse=False, w_energy=None, w_time=None, w_risk=None,
+                risk_threshold=None, plain_sweeps=False, inner_sweeps=64):
+        """The field under the motion-cost network (artp_field_compute_learned); None keeps a default of the library."""
+        self = cls.__new__(cls)
+        p = _capi.FieldLearnedParams()
+        ctx.L.artp_field_learned_params_defaults(C.byref(p))
+        for name, v in (("w_energy", w_energy), ("w_time", w_time), ("w_risk", w_risk), ("risk_threshold", risk_threshold)):
+            if v is not None:
+                setattr(p, name, v)
+        p.plain_sweeps, p.inner_sweeps = int(bool(plain_sweeps)), int(inner_sweeps)
+        self._compute(ctx, ctx.L.artp_field_compute_learned, "artp_field_compute_learned", p, mask, n_yaw, sources, rect,
+                      reverse)
+        return self
+
+    def _compute(self, ctx, call, name, params, mask, n_yaw, sources, rect, reverse):
+        """The mask and source handling both constructors share; call = the C entry point, params = its struct."""
         self.ctx = ctx
         self.L = ctx.L
         self.h = None
-        p = _capi.FieldParams()
-        self.L.artp_field_params_defaults(C.byref(p))
-        p.objective, p.plain_sweeps, p.inner_sweeps = int(objective), int(bool(plain_sweeps)), int(inner_sweeps)
-        p.max_lon_vel, p.max_lat_vel, p.max_ang_vel = max_lon_vel, max_lat_vel, max_ang_vel
         r, nr, nc = ctx._reach_rect(rect)
         self.nrows, self.ncols, self.n_yaw, self.reverse = nr, nc, int(n_yaw), bool(reverse)
         mask_ptr, on_device, keep = self._mask_arg(mask, "cost_field")
         src = np.ascontiguousarray(sources, np.int32).reshape(-1, 3)
         h = C.c_void_p()
-        ctx._chk(self.L.artp_field_compute(ctx.h, C.byref(p), int(n_yaw), r.ctypes.data if r is not None else None,
-                                           mask_ptr, on_device, src.ctypes.data, len(src), int(bool(reverse)),
-                                           C.byref(h)), "artp_field_compute")
+        ctx._chk(call(ctx.h, C.byref(params), int(n_yaw), r.ctypes.data if r is not None else None, mask_ptr, on_device,
+                      src.ctypes.data, len(src), int(bool(reverse)), C.byref(h)), name)
         del keep
         self.h = h
 
@@ -123,6 +141,12 @@ class CostField:
         s = _capi.FieldUpdateStats()
         self.ctx._chk(self.L.artp_field_update_stats(self.h, C.byref(s)), "artp_field_update_stats")
         return {n: int(getattr(s, n)) for n, _ in _capi.FieldUpdateStats._fields_}
+
+    def learned_stats(self) -> dict:
+        """The weight table of a learned field and the time its steps took (artp_field_learned_stats)."""
+        s = _capi.FieldLearnedStats()
+        self.ctx._chk(self.L.artp_field_learned_stats(self.h, C.byref(s)), "artp_field_learned_stats")
+        return {n: getattr(s, n) for n, _ in _capi.FieldLearnedStats._fields_}
 
     def stats(self) -> dict:
         s = _capi.FieldStats()

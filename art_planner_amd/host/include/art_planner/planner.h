@@ -387,19 +387,37 @@ class Planner {
                  artp_field_compute(gpu_->get(), &fp, static_cast<int>(n_yaw), nullptr, mask.data(), 0, src.data(),
                                     sources.size(), reverse ? 1 : 0, &f),
                  "artp_field_compute");
-    std::vector<double> dist(cells * n_yaw);
-    const int rc = artp_field_dist(f, dist.data());
-    if (rc || !keep) artp_field_destroy(f);
-    throwOnError(gpu_->get(), rc, "artp_field_dist");
-    if (keep) *keep = f;   // the caller asks paths of it (artp_field_path) and destroys it
-    std::vector<float> best(cells);
-    for (size_t i = 0; i < cells; ++i) {
-      double b = std::numeric_limits<double>::infinity();
-      for (unsigned k = 0; k < n_yaw; ++k) b = std::min(b, dist[i * n_yaw + k]);
-      best[i] = static_cast<float>(b);
-    }
-    map_->addLayer("cost_to_go", best.data());
-    return dist;
+    return finishCostField(f, cells, n_yaw, keep);
+  }
+
+  // computeCostField under the learned motion cost (artp_field_compute_learned, include/artp_c.h): every lattice move is
+  // priced by the network on the device, which must hold weights and a feature map (artp_cost_load_weights,
+  // artp_cost_update_map*).  The weights and the risk threshold are Params::planner.prm_motion_cost's, the numbers
+  // setDevicePricing(true) gives the roadmap.  The cost is not symmetric: reverse is another field.  A kept field
+  // cannot go through updateCostField (the library refuses it).  Refreshes the "cost_to_go" layer.
+  std::vector<double> computeLearnedCostField(const std::vector<uint32_t>& mask, unsigned n_yaw,
+                                              const std::vector<std::array<int, 3>>& sources, bool reverse = false,
+                                              artp_field** keep = nullptr) {
+    std::lock_guard<std::mutex> lock(map_mutex_);
+    if (!map_) throw std::runtime_error("computeLearnedCostField: the planner does not have a map set");
+    const auto g = map_->getGeometry();
+    const size_t cells = static_cast<size_t>(g.rows) * g.cols;
+    if (mask.size() != cells) throw std::runtime_error("computeLearnedCostField: the mask does not have rows * cols words");
+    artp_field_learned_params lp;
+    artp_field_learned_params_defaults(&lp);
+    const auto& pmc = params_->planner.prm_motion_cost;
+    lp.w_energy = pmc.cost_weights.energy;
+    lp.w_time = pmc.cost_weights.time;
+    lp.w_risk = pmc.cost_weights.risk;
+    lp.risk_threshold = pmc.risk_threshold;
+    std::vector<int> src;
+    for (const auto& s : sources) src.insert(src.end(), s.begin(), s.end());
+    artp_field* f = nullptr;
+    throwOnError(gpu_->get(),
+                 artp_field_compute_learned(gpu_->get(), &lp, static_cast<int>(n_yaw), nullptr, mask.data(), 0, src.data(),
+                                            sources.size(), reverse ? 1 : 0, &f),
+                 "artp_field_compute_learned");
+    return finishCostField(f, cells, n_yaw, keep);
   }
 
   // The field a computeCostField call kept, brought in place to an edited mask (artp_field_update, include/artp_c.h):
@@ -544,6 +562,23 @@ class Planner {
   const std::shared_ptr<BatchTree>& tree() const { return tree_; }
 
  protected:
+  // the tail of both computeCostField calls: dist out of the field, the field kept or destroyed, the layer refreshed
+  std::vector<double> finishCostField(artp_field* f, size_t cells, unsigned n_yaw, artp_field** keep) {
+    std::vector<double> dist(cells * n_yaw);
+    const int rc = artp_field_dist(f, dist.data());
+    if (rc || !keep) artp_field_destroy(f);
+    throwOnError(gpu_->get(), rc, "artp_field_dist");
+    if (keep) *keep = f;   // the caller asks paths of it (artp_field_path) and destroys it
+    std::vector<float> best(cells);
+    for (size_t i = 0; i < cells; ++i) {
+      double b = std::numeric_limits<double>::infinity();
+      for (unsigned k = 0; k < n_yaw; ++k) b = std::min(b, dist[i * n_yaw + k]);
+      best[i] = static_cast<float>(b);
+    }
+    map_->addLayer("cost_to_go", best.data());
+    return dist;
+  }
+
   ParamsConstPtr params_;
   GpuContextPtr gpu_;
   std::shared_ptr<BatchPRM> prm_;

@@ -227,7 +227,7 @@ int artp_reachability_halo(artp_ctx* ctx, int* cells);
  *   objective 0: sqrt((dx^2 + dy^2) + dz^2) / max_lon_vel, rotations cost 0
  *   objective 1: max(|lon| / max_lon_vel, |lat| / max_lat_vel, yaw_dif / max_ang_vel), lon = cos(yaw_a) dx + sin(yaw_a) dy,
  *                lat = -sin(yaw_a) dx + cos(yaw_a) dy, yaw_dif = 2 pi / n_yaw for a rotation and 0 for a translation
- *   objective 2 (learned): ARTP_ERR_INVALID_ARG.
+ *   objective 2 (learned): ARTP_ERR_INVALID_ARG.  The learned objective has its own call, artp_field_compute_learned.
  * dist[node] (f64): reverse = 0: the smallest cost of a lattice path from any source to the node; reverse = 1: from the
  * node to any source.  A path's cost is the left fold ((0 + w1) + w2) + ... of its edge costs counted from the SOURCE end
  * outwards, in both forms.  +inf where the node does not exist or cannot be reached.  The least fixed point of
@@ -307,6 +307,44 @@ int artp_field_update(artp_field* f, const uint32_t* new_mask, int mask_on_devic
 /* the numbers of the last artp_field_update that returned ARTP_OK (zeros before the first) */
 int artp_field_update_stats(artp_field* f, artp_field_update_stats_t* out);
 void artp_field_destroy(artp_field* f);
+
+/* ---- Learned-cost fields: cost-to-go under the motion-cost network --------------
+ * The same graph, rules and results as artp_field_compute, under the roadmap's objective 2.  The cost of the move a -> b:
+ * ONE EdgeMatrix row -- target (x, y, yaw) then start (x, y, yaw) as floats, from the poses artp_reachability_poses gives
+ * the two nodes (a lattice move is shorter than any query edge length: no interpolation) -- answered by the network as
+ * (energy, time, risk) and priced in f64 as MotionCostObjective prices a chain of one sub-edge:
+ *   cost = 0.0 + (energy w_energy + time w_time + risk w_risk), +inf when risk > risk_threshold.
+ * An edge whose cost is negative or NaN does not exist (the least fixed point is unique for weights >= 0 only); an edge of
+ * cost 0 does.  The cost is NOT symmetric: a -> b and b -> a differ, rotations included, so reverse = 1 is another field.
+ * The weights live in a per-field device table of 80 bytes per node (edge tiles padded to 16 x 16 cells), built once per
+ * call in chunks of at most 2^22 rows; ARTP_ERR_CAPACITY, with a text, when the device has not that much memory free.
+ * The field always prices on the device network, through the kernels artp_cost_query_dev launches (artp_cost_set_fc_path
+ * and the load-time self-check hold): a function installed with artp_cost_set_external_query does NOT redirect it, as it
+ * does not redirect artp_cost_query.
+ * The result is an ordinary artp_field: artp_field_dist, _dist_dev, _path, _edge_costs (the travel-direction cost of
+ * a -> b; +inf for an absent edge between neighbouring nodes), _stats and _destroy work on it unchanged.
+ * artp_field_update refuses it with ARTP_ERR_INVALID_ARG: a map change moves the network's features, and with them the
+ * weights, far beyond any sub-rectangle.
+ * Statuses, with nothing computed: ARTP_ERR_NO_WEIGHTS without a network, ARTP_ERR_NO_MAP without a feature map
+ * (artp_cost_update_map*) or without the sampler layers, ARTP_ERR_INVALID_ARG for a negative or non-finite weight or
+ * threshold and for everything artp_field_compute refuses about n_yaw, rect, the sources and inner_sweeps. */
+typedef struct artp_field_learned_params {
+  float w_energy, w_time, w_risk, risk_threshold; /* the artp_roadmap_params defaults */
+  int32_t plain_sweeps, inner_sweeps;             /* as artp_field_params */
+} artp_field_learned_params;
+typedef struct artp_field_learned_stats_t {
+  uint64_t table_rows;   /* slots of the weight table = rows sent through the cost query */
+  uint64_t table_bytes;
+  uint64_t chunks;       /* query calls */
+  double rows_ms, query_ms, combine_ms; /* device time of the three steps of the table build, summed over the chunks */
+  double dist_ms, hop_ms;               /* host time of the two searches (every round is read by the host) */
+} artp_field_learned_stats_t;
+void artp_field_learned_params_defaults(artp_field_learned_params* p);
+int artp_field_compute_learned(artp_ctx* ctx, const artp_field_learned_params* params, int n_yaw, const int rect[4],
+                               const uint32_t* mask, int mask_on_device, const int* sources, size_t n_sources, int reverse,
+                               artp_field** out);
+/* the table's six members are zero for a field of artp_field_compute */
+int artp_field_learned_stats(artp_field* f, artp_field_learned_stats_t* out);
 
 /* ---- ob::MotionValidator::checkMotion (OMPL DiscreteMotionValidator; call sites
  *      prm_motion_cost.cpp:652, lazy_prm_star_min_update.cpp:725), batched -----------------------
