@@ -21,7 +21,8 @@ SYMBOLS = [
     "artp_sample_and_validate", "artp_reachability_map", "artp_reachability_map_dev", "artp_reachability_poses",
     "artp_reachability_halo", "artp_field_params_defaults", "artp_field_compute", "artp_field_dist", "artp_field_dist_dev",
     "artp_field_path", "artp_field_edge_costs", "artp_field_stats", "artp_field_update", "artp_field_update_stats",
-    "artp_field_destroy", "artp_field_learned_params_defaults", "artp_field_compute_learned", "artp_field_learned_stats", "artp_check_motions_last_valid", "artp_check_motions_last_valid_dev",
+    "artp_field_destroy", "artp_field_learned_params_defaults", "artp_field_compute_learned", "artp_field_learned_stats",
+    "artp_field_update_learned", "artp_field_learned_update_stats", "artp_check_motions_last_valid", "artp_check_motions_last_valid_dev",
     "artp_set_z_bounds", "artp_set_few_edges", "artp_set_edge_passes", "artp_cost_set_fc_path", "artp_check_motions", "artp_check_motions_dev", "artp_check_edges_interp",
     "artp_check_edges_interp_dev", "artp_compact_valid_dev", "artp_compact_valid_indices_dev", "artp_sample_states_at_dev",
     "artp_pack_edge_results_dev", "artp_cost_update_map_dev", "artp_pack_valid_bits_dev", "artp_indices_from_bits_dev",
@@ -128,6 +129,12 @@ class FieldUpdateStats(C.Structure):  # artp_field_update_stats_t
                                           "reached_nodes")]
 
 
+class FieldLearnedUpdateStats(C.Structure):  # artp_field_learned_update_stats_t
+    _fields_ = (list(FieldUpdateStats._fields_) +
+                [(n, C.c_uint64) for n in ("repriced_slots", "changed_slots", "weight_tiles")] +
+                [(n, C.c_double) for n in ("rows_ms", "query_ms", "reprice_ms", "passes_ms")])
+
+
 class TreeParams(C.Structure):  # artp_tree_params (include/artp_c.h)
     _fields_ = [("seed", C.c_uint64), ("first_index", C.c_uint64), ("variant", C.c_int32), ("objective", C.c_int32),
                 ("max_lon_vel", C.c_double), ("max_lat_vel", C.c_double), ("max_ang_vel", C.c_double),
@@ -215,6 +222,8 @@ def _load_path(LIB_PATH):
     L.artp_field_compute_learned.argtypes = [vp, C.POINTER(FieldLearnedParams), i32, vp, vp, i32, vp, sz, i32,
                                              C.POINTER(vp)]
     L.artp_field_learned_stats.argtypes = [vp, C.POINTER(FieldLearnedStats)]
+    L.artp_field_update_learned.argtypes = [vp, vp, i32, vp]
+    L.artp_field_learned_update_stats.argtypes = [vp, C.POINTER(FieldLearnedUpdateStats)]
     L.artp_field_destroy.restype = None
     L.artp_map_version.argtypes = [vp]
     L.artp_map_version.restype = C.c_uint64

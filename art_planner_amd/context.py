@@ -250,7 +250,8 @@ class Context:
         """cost_field under the learned motion cost (artp_field_compute_learned): every lattice
         move is priced by the loaded network on the installed cost map (cost_load_weights, cost_update_map*), always on
         the device.  The weights and the threshold default to the roadmap's (None).  The cost is not symmetric: reverse=True
-        is a different field.  Returns a CostField; its update() is refused."""
+        is a different field.  Returns a CostField; its update() is refused: update_learned(mask=None, rect=None) prices the
+        field again after the cost map, the network or the mask changed."""
         from .field import CostField
         return CostField.learned(self, mask, n_yaw, sources, rect=rect, reverse=reverse, w_energy=w_energy, w_time=w_time,
                                  w_risk=w_risk, risk_threshold=risk_threshold, plain_sweeps=plain_sweeps,

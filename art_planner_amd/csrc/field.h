@@ -48,6 +48,9 @@
 // call by field_learned_rows_kernel -> the context's cost query -> field_learned_combine_kernel in chunks of at most
 // FIELD_LEARNED_CHUNK rows.  The rules are the same ones; only the cost source differs (field_walk's branch, the LEARNED
 // parameter of the tile skeleton).  w(a -> b) != w(b -> a) here, rotations included.
+// artp_field_update_learned: the diff of artp_field_update, then every slot of the table priced
+// again against the context's current network and feature map (field_learned_reprice_kernel: a slot whose bits change is
+// written and flags its tile), then the same four passes, the tiled ones on the streamed table.
 #pragma once
 
 namespace artp {
@@ -615,25 +618,64 @@ field_learned_rows_kernel(FieldGrid G, SamplerDev sm, MapGeom g, ReachRect rc, c
   for (int q = 0; q < 6; ++q) rows[6 * (size_t)i + q] = row[q];
 }
 
-// chain_motion_cost_kernel's pricing of a chain of one sub-edge; an edge whose cost is negative or NaN does not exist
-// (the rule of the roadmap's device search: the fixed point is unique for weights >= 0 only).
+// chain_motion_cost_kernel's pricing of a chain of one sub-edge, for slot s of the table with the network's answer c;
+// an edge whose cost is negative or NaN does not exist (the rule of the roadmap's device search: the fixed point is unique
+// for weights >= 0 only).  Never NaN, never -0.
+struct FieldPricing {
+  float w_energy, w_time, w_risk, risk_threshold;
+};
+__device__ __forceinline__ double field_learned_price(const FieldGrid& G, const uint32_t* __restrict__ mask, size_t s,
+                                                      const float* __restrict__ c, const FieldPricing& p) {
+  uint32_t from, to;
+  if (!field_slot_edge(G, mask, s, &from, &to)) return INFINITY;
+  const double en = c[0], ti = c[1], ri = c[2];
+  double total = 0.0;
+  total += en * p.w_energy + ti * p.w_time + ri * p.w_risk;
+  double w = ri <= (double)p.risk_threshold ? total : (double)INFINITY;
+  if (!(w >= 0.0)) w = INFINITY;
+  return w;
+}
+
 __global__ void __launch_bounds__(256)
 field_learned_combine_kernel(FieldGrid G, const uint32_t* __restrict__ mask, size_t first, uint32_t n,
-                             const float* __restrict__ cost3, float w_energy, float w_time, float w_risk, float risk_threshold,
-                             double* __restrict__ wtab) {
+                             const float* __restrict__ cost3, FieldPricing p, double* __restrict__ wtab) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  double w = INFINITY;
-  uint32_t from, to;
-  if (field_slot_edge(G, mask, first + i, &from, &to)) {
-    const float* c = cost3 + 3 * (size_t)i;
-    const double en = c[0], ti = c[1], ri = c[2];
-    double total = 0.0;
-    total += en * w_energy + ti * w_time + ri * w_risk;
-    w = ri <= (double)risk_threshold ? total : (double)INFINITY;
-    if (!(w >= 0.0)) w = INFINITY;
+  wtab[first + i] = field_learned_price(G, mask, first + i, cost3 + 3 * (size_t)i, p);
+}
+
+// artp_field_update_learned: the same price against the slot's old BIT PATTERN; only a slot that differs is written, and
+// the tile that owns it is flagged in acc (the seeds of the update's passes) and in wacc (counted as weight_tiles).  A slot
+// is read by its own node alone, and that node's rule runs in its own tile alone: no other tile needs the flag.  `first`
+// and a tile's share of the table (2560 n_yaw slots) are multiples of 64: the slots of a wave lie in one tile.
+// cnt[5] += changed slots, one atomic per wave.
+__global__ void __launch_bounds__(256)
+field_learned_reprice_kernel(FieldGrid G, const uint32_t* __restrict__ mask, size_t first, uint32_t n,
+                             const float* __restrict__ cost3, FieldPricing p, double* __restrict__ wtab,
+                             unsigned* __restrict__ acc, unsigned* __restrict__ wacc, unsigned long long* __restrict__ cnt) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t s = first + i;
+  bool ch = false;
+  if (i < n) {
+    const double w = field_learned_price(G, mask, s, cost3 + 3 * (size_t)i, p);
+    ch = __double_as_longlong(w) != __double_as_longlong(wtab[s]);
+    if (ch) wtab[s] = w;
   }
-  wtab[first + i] = w;
+  const unsigned long long b = __ballot(ch);
+  if (b && (threadIdx.x & 63) == 0) {
+    const size_t tile = s / ((size_t)G.n_yaw * 10 * (FIELD_T * FIELD_T));  // lane 0 of a wave is never past n when b != 0
+    acc[tile] = 1u;
+    wacc[tile] = 1u;
+    atomicAdd(&cnt[5], (unsigned long long)__popcll(b));
+  }
+}
+
+// cnt[6] = the flags set among wacc[0 .. n_tiles - 1]
+__global__ void __launch_bounds__(256)
+field_count_flags_kernel(uint32_t n_tiles, const unsigned* __restrict__ wacc, unsigned long long* __restrict__ cnt) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  const unsigned long long b = __ballot(i < n_tiles && wacc[i] != 0u);
+  if (b && (threadIdx.x & 63) == 0) atomicAdd(&cnt[6], (unsigned long long)__popcll(b));
 }
 
 // ---- artp_field_update ------------------------------------------------------------------------------------------
@@ -651,7 +693,8 @@ struct FieldSub {
   int row0, col0, nrows, ncols;  // local to the field's rectangle
 };
 
-// cnt[0] changed words, [1] removed bits, [2] added bits, [3] changed heights, [4] sources that are no nodes any more
+// cnt[0] changed words, [1] removed bits, [2] added bits, [3] changed heights, [4] sources that are no nodes any more,
+// [5] changed slots and [6] tiles flagged by them (artp_field_update_learned)
 
 // one lane per source against the merged mask (the new word inside sub, the field's own outside)
 __global__ void __launch_bounds__(64)
@@ -747,6 +790,9 @@ struct artp_field {
   artp_field_learned_params lparams{};
   artp_field_learned_stats_t lstats{};
   float* d_lscratch = nullptr;          // per chunk: 6 floats of EdgeMatrix row, then 3 floats of answer, per row
+  // artp_field_update_learned: d_lscratch stays from the first update on
+  unsigned* d_wacc = nullptr;           // n_tiles flags: the tiles a changed weight flagged
+  artp_field_learned_update_stats_t lustats{};
 };
 
 namespace {
@@ -754,7 +800,7 @@ namespace {
 void field_free(artp_field* f) {
   for (void* p : {(void*)f->d_dist, (void*)f->d_hops, (void*)f->d_mask, (void*)f->d_h, (void*)f->d_tab, (void*)f->d_flags,
                   (void*)f->d_nodes, (void*)f->d_out, (void*)f->d_src, (void*)f->d_snap, (void*)f->d_acc, (void*)f->d_ucnt,
-                  (void*)f->d_stage, (void*)f->d_lscratch})
+                  (void*)f->d_stage, (void*)f->d_lscratch, (void*)f->d_wacc})
     if (p) (void)hipFree(p);
   delete f;
 }
@@ -857,9 +903,7 @@ int field_pass(artp_field* f, unsigned* d_seed, FieldRounds* out) {
   }
   const size_t lds = artp::field_tile_lds(G.n_yaw, PHASE == 1 || UNSUP);
   auto kernel = &artp::field_tile_kernel<PHASE, UNSUP, false>;
-  if constexpr (!UNSUP) {  // a learned field is never updated in place
-    if (G.objective == 2) kernel = &artp::field_tile_kernel<PHASE, false, true>;
-  }
+  if (G.objective == 2) kernel = &artp::field_tile_kernel<PHASE, UNSUP, true>;
   // a workgroup may ask for more than 64 KB of dynamic LDS once the function says so (32 headings: 88 / 126 KB)
   if (lds > 64 * 1024)
     HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -886,16 +930,20 @@ int field_count_reached(artp_field* f, uint64_t* reached) {
   return ARTP_OK;
 }
 
-// Objective 2: fill the weight table f->d_tab from f->d_mask, in chunks of at most FIELD_LEARNED_CHUNK rows: the rows, the
-// context's own cost query (always the device network: the kernels artp_cost_query_dev launches, on the context's stream,
-// whatever artp_cost_set_external_query installed), the combination.
-int field_learned_table(artp_ctx* c, artp_field* f) {
+// Objective 2: price every slot of the weight table f->d_tab from f->d_mask, in table order, in chunks of at most
+// FIELD_LEARNED_CHUNK rows: the rows, the context's own cost query (always the device network: the kernels
+// artp_cost_query_dev launches, on the context's stream, whatever artp_cost_set_external_query installed), then the
+// combination (reprice = false: every slot is written) or the repricing (true: the slots that change are written and
+// their tiles flagged in d_acc and d_wacc, their number added to d_ucnt[5]).  The scratch is allocated when there is
+// none and left to the caller.  ms[0..2] += the device time of the three steps, *chunks += the query calls.
+int field_learned_table(artp_ctx* c, artp_field* f, bool reprice, double ms[3], uint64_t* chunks) {
   hipStream_t st = c->stream;
   const artp::FieldGrid& G = f->grid;
   const artp_field_learned_params& lp = f->lparams;
+  const artp::FieldPricing price{lp.w_energy, lp.w_time, lp.w_risk, lp.risk_threshold};
   const size_t slots = artp::field_wtab_slots(G);
   const size_t chunk = slots < artp::FIELD_LEARNED_CHUNK ? slots : artp::FIELD_LEARNED_CHUNK;
-  HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&f->d_lscratch), chunk * 9 * sizeof(float)));
+  if (!f->d_lscratch) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&f->d_lscratch), chunk * 9 * sizeof(float)));
   float* rows = f->d_lscratch;
   float* cost3 = f->d_lscratch + chunk * 6;
   std::vector<hipEvent_t> ev;
@@ -916,31 +964,41 @@ int field_learned_table(artp_ctx* c, artp_field* f) {
     rc = artp_cost_query_dev(c, rows, n, cost3);
     if (rc) break;
     if (e4[2]) (void)hipEventRecord(e4[2], st);
-    hipLaunchKernelGGL(artp::field_learned_combine_kernel, dim3(blocks), dim3(256), 0, st, G, (const uint32_t*)f->d_mask, first, n,
-                       (const float*)cost3, lp.w_energy, lp.w_time, lp.w_risk, lp.risk_threshold, f->d_tab);
+    if (reprice)
+      hipLaunchKernelGGL(artp::field_learned_reprice_kernel, dim3(blocks), dim3(256), 0, st, G, (const uint32_t*)f->d_mask, first,
+                         n, (const float*)cost3, price, f->d_tab, f->d_acc, f->d_wacc, f->d_ucnt);
+    else
+      hipLaunchKernelGGL(artp::field_learned_combine_kernel, dim3(blocks), dim3(256), 0, st, G, (const uint32_t*)f->d_mask, first,
+                         n, (const float*)cost3, price, f->d_tab);
     if (e4[3]) (void)hipEventRecord(e4[3], st);
     if (hipGetLastError() != hipSuccess) rc = ARTP_ERR_HIP;
-    ++f->lstats.chunks;
+    ++*chunks;
   }
   if (hipStreamSynchronize(st) != hipSuccess && rc == ARTP_OK) rc = ARTP_ERR_HIP;
-  for (size_t i = 0; i + 3 < ev.size(); i += 4) {
-    float ms[3] = {0.f, 0.f, 0.f};
-    for (int q = 0; q < 3; ++q)
-      if (rc == ARTP_OK && ev[i + q] && ev[i + q + 1] && hipEventElapsedTime(&ms[q], ev[i + q], ev[i + q + 1]) != hipSuccess)
-        ms[q] = 0.f;
-    f->lstats.rows_ms += ms[0];
-    f->lstats.query_ms += ms[1];
-    f->lstats.combine_ms += ms[2];
-  }
+  for (size_t i = 0; i + 3 < ev.size(); i += 4)
+    for (int q = 0; q < 3; ++q) {
+      float t = 0.f;
+      if (rc == ARTP_OK && ev[i + q] && ev[i + q + 1] && hipEventElapsedTime(&t, ev[i + q], ev[i + q + 1]) == hipSuccess) ms[q] += t;
+    }
   for (hipEvent_t x : ev)
     if (x) (void)hipEventDestroy(x);
   (void)hipGetLastError();
-  if (rc == ARTP_ERR_HIP && c->last_error.empty()) c->last_error = "artp_field_compute_learned: building the weight table failed";
+  if (rc == ARTP_ERR_HIP && c->last_error.empty()) c->last_error = "learned field: pricing the weight table failed";
+  return rc;
+}
+
+// artp_field_compute_learned's table: built once, the scratch given back
+int field_learned_build(artp_ctx* c, artp_field* f) {
+  double ms[3] = {0.0, 0.0, 0.0};
+  const int rc = field_learned_table(c, f, false, ms, &f->lstats.chunks);
   if (rc) return rc;
+  f->lstats.rows_ms = ms[0];
+  f->lstats.query_ms = ms[1];
+  f->lstats.combine_ms = ms[2];
   HIP_TRY(c, hipFree(f->d_lscratch));
   f->d_lscratch = nullptr;
-  f->lstats.table_rows = slots;
-  f->lstats.table_bytes = slots * sizeof(double);
+  f->lstats.table_rows = artp::field_wtab_slots(f->grid);
+  f->lstats.table_bytes = f->lstats.table_rows * sizeof(double);
   return ARTP_OK;
 }
 
@@ -993,7 +1051,7 @@ int field_compute_impl(artp_ctx* c, artp_field* f, const uint32_t* mask, int mas
     return ARTP_ERR_INVALID_ARG;
   }
   if (learned) {
-    rc = field_learned_table(c, f);
+    rc = field_learned_build(c, f);
     if (rc) return rc;
   }
   FieldRounds dist_pass, hop_pass;
@@ -1050,6 +1108,33 @@ int field_update_passes(artp_field* f, artp_field_update_stats_t* us) {
   us->hop_rounds = relax[1].rounds;
   us->tile_launches = unsup[0].tile_runs + relax[0].tile_runs + unsup[1].tile_runs + relax[1].tile_runs;
   return field_count_reached(f, &us->reached_nodes);
+}
+
+// The diff of an update (step 1 of section 13): the sources tested against the merged mask on the device, then the words
+// of sub installed, the removed nodes cleared and the tiles around every changed cell flagged in d_acc; the caller has cleared d_acc and d_ucnt.
+// cnt = the first five counts of d_ucnt; cnt[4] != 0: a source is gone and nothing was written.
+int field_update_diff(artp_field* f, const uint32_t* new_mask, int mask_on_device, const artp::FieldSub& sub, bool refresh,
+                      const SamplerDev& sm, unsigned long long cnt[5]) {
+  artp_ctx* c = f->ctx;
+  hipStream_t st = c->stream;
+  const artp::FieldGrid& G = f->grid;
+  const uint32_t* nm = new_mask;
+  if (!mask_on_device) {  // the columns of sub_rect only, to the same place of a buffer in the field's layout
+    const size_t off = (size_t)sub.row0 + (size_t)sub.col0 * G.nrows, pitch = (size_t)G.nrows * sizeof(uint32_t);
+    HIP_TRY(c, hipMemcpy2DAsync(f->d_stage + off, pitch, new_mask + off, pitch, (size_t)sub.nrows * sizeof(uint32_t),
+                                (size_t)sub.ncols, hipMemcpyHostToDevice, st));
+    nm = f->d_stage;
+  }
+  const int n_src = (int)(f->h_src.size() / 3);
+  hipLaunchKernelGGL(artp::field_update_sources_kernel, dim3((unsigned)((n_src + 63) / 64)), dim3(64), 0, st, G, sub,
+                     (const uint32_t*)f->d_mask, nm, (const int*)f->d_src, n_src, f->d_ucnt);
+  const size_t sub_cells = (size_t)sub.nrows * sub.ncols;
+  hipLaunchKernelGGL(artp::field_diff_kernel, dim3((unsigned)((sub_cells + 255) / 256)), dim3(256), 0, st, G, sub, nm,
+                     f->d_mask, refresh ? 1 : 0, sm, f->geom.rows, f->rect, f->d_h, f->d_dist, f->d_hops, f->d_acc, f->d_ucnt);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(cnt, f->d_ucnt, 5 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipStreamSynchronize(st));  // the host copy of the mask is free from here
+  return ARTP_OK;
 }
 
 int field_check_sources(artp_ctx* c, const artp::ReachRect& r, int n_yaw, const int* sources, size_t n_sources) {
@@ -1313,8 +1398,8 @@ int artp_field_update(artp_field* f, const uint32_t* new_mask, int mask_on_devic
   std::lock_guard<std::recursive_mutex> lock(c->mu);
   const artp::FieldGrid& G = f->grid;
   if (G.objective == 2) {
-    c->last_error = "artp_field_update: a learned field cannot be updated in place (a map change moves the network's "
-                    "features, and with them the weights, far beyond sub_rect): compute a new one";
+    c->last_error = "artp_field_update: a learned field is not updated by a mask edit alone (a map change moves the network's "
+                    "features, and with them the weights, far beyond sub_rect): artp_field_update_learned prices it again";
     return ARTP_ERR_INVALID_ARG;
   }
   artp::FieldSub sub{0, 0, G.nrows, G.ncols};
@@ -1337,24 +1422,9 @@ int artp_field_update(artp_field* f, const uint32_t* new_mask, int mask_on_devic
   if (rc) return rc;
   HIP_TRY(c, hipMemsetAsync(f->d_acc, 0, f->n_tiles * sizeof(unsigned), st));
   HIP_TRY(c, hipMemsetAsync(f->d_ucnt, 0, 8 * sizeof(unsigned long long), st));
-  const uint32_t* nm = new_mask;
-  if (!mask_on_device) {  // the columns of sub_rect only, to the same place of a buffer in the field's layout
-    const size_t off = (size_t)sub.row0 + (size_t)sub.col0 * G.nrows, pitch = (size_t)G.nrows * sizeof(uint32_t);
-    HIP_TRY(c, hipMemcpy2DAsync(f->d_stage + off, pitch, new_mask + off, pitch, (size_t)sub.nrows * sizeof(uint32_t),
-                                (size_t)sub.ncols, hipMemcpyHostToDevice, st));
-    nm = f->d_stage;
-  }
-  const int n_src = (int)(f->h_src.size() / 3);
-  hipLaunchKernelGGL(artp::field_update_sources_kernel, dim3((unsigned)((n_src + 63) / 64)), dim3(64), 0, st, G, sub,
-                     (const uint32_t*)f->d_mask, nm, (const int*)f->d_src, n_src, f->d_ucnt);
-  const size_t sub_cells = (size_t)sub.nrows * sub.ncols;
-  hipLaunchKernelGGL(artp::field_diff_kernel, dim3((unsigned)((sub_cells + 255) / 256)), dim3(256), 0, st, G, sub, nm,
-                     f->d_mask, refresh_heights ? 1 : 0, refresh_heights ? c->sampler : f->sampler, f->geom.rows, f->rect,
-                     f->d_h, f->d_dist, f->d_hops, f->d_acc, f->d_ucnt);
-  HIP_TRY(c, hipGetLastError());
   unsigned long long cnt[5] = {0, 0, 0, 0, 0};
-  HIP_TRY(c, hipMemcpyAsync(cnt, f->d_ucnt, sizeof(cnt), hipMemcpyDeviceToHost, st));
-  HIP_TRY(c, hipStreamSynchronize(st));  // the host copy of the mask is free from here
+  rc = field_update_diff(f, new_mask, mask_on_device, sub, refresh_heights != 0, refresh_heights ? c->sampler : f->sampler, cnt);
+  if (rc) return rc;
   if (cnt[4]) {
     c->last_error = "artp_field_update: a source is no longer a node of the mask (the field is unchanged)";
     return ARTP_ERR_INVALID_ARG;
@@ -1383,6 +1453,117 @@ int artp_field_update(artp_field* f, const uint32_t* new_mask, int mask_on_devic
 int artp_field_update_stats(artp_field* f, artp_field_update_stats_t* out) {
   if (!f || !out) return ARTP_ERR_INVALID_ARG;
   *out = f->ustats;
+  return ARTP_OK;
+}
+
+int artp_field_update_learned(artp_field* f, const uint32_t* new_mask, int mask_on_device, const int* sub_rect) {
+  if (!f) return ARTP_ERR_INVALID_ARG;
+  artp_ctx* c = f->ctx;
+  std::lock_guard<std::recursive_mutex> lock(c->mu);
+  const artp::FieldGrid& G = f->grid;
+  // 1. the checks: nothing is written before the last of them
+  if (G.objective != 2) {
+    c->last_error = "artp_field_update_learned: not a field of artp_field_compute_learned (artp_field_update takes the others)";
+    return ARTP_ERR_INVALID_ARG;
+  }
+  if (!c->have_weights) {
+    c->last_error = "artp_field_update_learned: artp_cost_load_weights has not been called";
+    return ARTP_ERR_NO_WEIGHTS;
+  }
+  if (!c->have_features) {
+    c->last_error = "artp_field_update_learned: artp_cost_update_map has not been called";
+    return ARTP_ERR_NO_MAP;
+  }
+  artp::FieldSub sub{0, 0, G.nrows, G.ncols};
+  if (new_mask && sub_rect) sub = artp::FieldSub{sub_rect[0], sub_rect[1], sub_rect[2], sub_rect[3]};
+  if (sub.nrows < 1 || sub.ncols < 1 || sub.row0 < 0 || sub.col0 < 0 || sub.row0 > G.nrows - sub.nrows ||
+      sub.col0 > G.ncols - sub.ncols) {
+    c->last_error = "artp_field_update_learned: sub_rect is empty or not inside the field's rectangle";
+    return ARTP_ERR_INVALID_ARG;
+  }
+  const MapGeom &a = f->geom, &b = c->geom;
+  const bool same_map = reach_have_lattice(c) && a.rows == b.rows && a.cols == b.cols && a.len_x == b.len_x &&
+                        a.len_y == b.len_y && a.pos_x == b.pos_x && a.pos_y == b.pos_y && a.res == b.res;
+  if (!same_map) {
+    c->last_error = "artp_field_update_learned: the sampler layers do not have the geometry the field was computed on";
+    return ARTP_ERR_INVALID_ARG;
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  int rc = field_update_scratch(f, new_mask && !mask_on_device);
+  if (rc) return rc;
+  const size_t slots = artp::field_wtab_slots(G);
+  if (!f->d_wacc) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&f->d_wacc), f->n_tiles * sizeof(unsigned)));
+  if (!f->d_lscratch) {  // 36 bytes a row of a chunk, kept until artp_field_destroy
+    const size_t chunk = slots < artp::FIELD_LEARNED_CHUNK ? slots : artp::FIELD_LEARNED_CHUNK;
+    HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&f->d_lscratch), chunk * 9 * sizeof(float)));
+  }
+  HIP_TRY(c, hipMemsetAsync(f->d_acc, 0, f->n_tiles * sizeof(unsigned), st));
+  HIP_TRY(c, hipMemsetAsync(f->d_wacc, 0, f->n_tiles * sizeof(unsigned), st));
+  HIP_TRY(c, hipMemsetAsync(f->d_ucnt, 0, 8 * sizeof(unsigned long long), st));
+  // 2. the mask diff, behind the test of the sources on the device
+  unsigned long long cnt[7] = {0, 0, 0, 0, 0, 0, 0};
+  if (new_mask) {
+    rc = field_update_diff(f, new_mask, mask_on_device, sub, false, f->sampler, cnt);
+    if (rc) return rc;
+    if (cnt[4]) {
+      c->last_error = "artp_field_update_learned: a source is no longer a node of the mask (the field is unchanged)";
+      return ARTP_ERR_INVALID_ARG;
+    }
+  }
+  // what a new field would hold: the current sampler layers and their heights
+  f->sampler = c->sampler;
+  f->map_version = c->map_version.load();
+  hipLaunchKernelGGL(artp::field_heights_kernel, dim3((unsigned)((f->n_cells + 255) / 256)), dim3(256), 0, st, f->sampler,
+                     f->geom, f->rect, f->d_h);
+  HIP_TRY(c, hipGetLastError());
+  // 3. every slot priced again; a slot whose bits change flags its tile
+  artp_field_learned_update_stats_t us{};
+  double ms[3] = {0.0, 0.0, 0.0};
+  uint64_t chunks = 0;
+  rc = field_learned_table(c, f, true, ms, &chunks);
+  if (rc) return rc;
+  hipLaunchKernelGGL(artp::field_count_flags_kernel, dim3((unsigned)((f->n_tiles + 255) / 256)), dim3(256), 0, st,
+                     (uint32_t)f->n_tiles, (const unsigned*)f->d_wacc, f->d_ucnt);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(cnt + 5, f->d_ucnt + 5, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipStreamSynchronize(st));
+  us.changed_words = cnt[0];
+  us.removed_nodes = cnt[1];
+  us.added_nodes = cnt[2];
+  us.reached_nodes = f->stats.reached_nodes;
+  us.repriced_slots = slots;
+  us.changed_slots = cnt[5];
+  us.weight_tiles = cnt[6];
+  us.rows_ms = ms[0];
+  us.query_ms = ms[1];
+  us.reprice_ms = ms[2];
+  // 4. the passes of artp_field_update, from the tiles flagged by the diff and by the changed weights
+  if (cnt[0] || cnt[5]) {
+    artp_field_update_stats_t ps{};
+    const auto t0 = std::chrono::steady_clock::now();
+    rc = field_update_passes(f, &ps);
+    if (rc) {
+      (void)hipStreamSynchronize(st);
+      return rc;
+    }
+    us.passes_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    us.dead_nodes = ps.dead_nodes;
+    us.hop_dead_nodes = ps.hop_dead_nodes;
+    us.unsupport_rounds = ps.unsupport_rounds;
+    us.dist_rounds = ps.dist_rounds;
+    us.hop_rounds = ps.hop_rounds;
+    us.tile_launches = ps.tile_launches;
+    us.reached_nodes = ps.reached_nodes;
+    f->stats.reached_nodes = us.reached_nodes;  // the other numbers of artp_field_compute_learned stay
+  }
+  f->lustats = us;
+  return ARTP_OK;
+}
+
+int artp_field_learned_update_stats(artp_field* f, artp_field_learned_update_stats_t* out) {
+  if (!f || !out) return ARTP_ERR_INVALID_ARG;
+  *out = f->lustats;
   return ARTP_OK;
 }
 

@@ -142,6 +142,24 @@ class CostField:
         self.ctx._chk(self.L.artp_field_update_stats(self.h, C.byref(s)), "artp_field_update_stats")
         return {n: int(getattr(s, n)) for n, _ in _capi.FieldUpdateStats._fields_}
 
+    def update_learned(self, mask=None, rect=None) -> dict:
+        """Bring a learned field to the fixed point of the context's current state in place (artp_field_update_learned,
+        DESIGN.md section 15): every move priced again by the loaded network on the installed cost map, the mask edited
+        as in update() (None: the mask did not change, rect is ignored).  The same bits as a new learned_cost_field with
+        the field's own weights, sources and direction.  Returns the update's stats."""
+        mask_ptr, on_device, keep = (None, 0, None) if mask is None else self._mask_arg(mask, "CostField.update_learned")
+        r = None if rect is None or mask is None else np.ascontiguousarray(rect, np.int32).reshape(4)
+        self.ctx._chk(self.L.artp_field_update_learned(self.h, mask_ptr, on_device, r.ctypes.data if r is not None else None),
+                      "artp_field_update_learned")
+        del keep
+        return self.learned_update_stats()
+
+    def learned_update_stats(self) -> dict:
+        """The numbers of the last update_learned that succeeded (zeros before the first)."""
+        s = _capi.FieldLearnedUpdateStats()
+        self.ctx._chk(self.L.artp_field_learned_update_stats(self.h, C.byref(s)), "artp_field_learned_update_stats")
+        return {n: getattr(s, n) for n, _ in _capi.FieldLearnedUpdateStats._fields_}
+
     def learned_stats(self) -> dict:
         """The weight table of a learned field and the time its steps took (artp_field_learned_stats)."""
         s = _capi.FieldLearnedStats()

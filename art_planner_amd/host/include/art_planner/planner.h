@@ -394,7 +394,8 @@ class Planner {
   // priced by the network on the device, which must hold weights and a feature map (artp_cost_load_weights,
   // artp_cost_update_map*).  The weights and the risk threshold are Params::planner.prm_motion_cost's, the numbers
   // setDevicePricing(true) gives the roadmap.  The cost is not symmetric: reverse is another field.  A kept field
-  // cannot go through updateCostField (the library refuses it).  Refreshes the "cost_to_go" layer.
+  // cannot go through updateCostField (the library refuses it): updateLearnedCostField takes it.  Refreshes the
+  // "cost_to_go" layer.
   std::vector<double> computeLearnedCostField(const std::vector<uint32_t>& mask, unsigned n_yaw,
                                               const std::vector<std::array<int, 3>>& sources, bool reverse = false,
                                               artp_field** keep = nullptr) {
@@ -435,20 +436,32 @@ class Planner {
     throwOnError(gpu_->get(), artp_field_stats(kept, &st), "artp_field_stats");
     if (mask.size() != cells || st.nodes % cells != 0)
       throw std::runtime_error("updateCostField: the mask or the field does not have rows * cols cells");
-    const size_t n_yaw = st.nodes / cells;
     throwOnError(gpu_->get(),
                  artp_field_update(kept, mask.data(), 0, rect ? rect->data() : nullptr, refresh_heights ? 1 : 0),
                  "artp_field_update");
-    std::vector<double> dist(st.nodes);
-    throwOnError(gpu_->get(), artp_field_dist(kept, dist.data()), "artp_field_dist");
-    std::vector<float> best(cells);
-    for (size_t i = 0; i < cells; ++i) {
-      double b = std::numeric_limits<double>::infinity();
-      for (size_t k = 0; k < n_yaw; ++k) b = std::min(b, dist[i * n_yaw + k]);
-      best[i] = static_cast<float>(b);
-    }
-    map_->addLayer("cost_to_go", best.data());
-    return dist;
+    return refreshCostToGo(kept, cells, st.nodes);
+  }
+
+  // The field a computeLearnedCostField call kept, brought in place to the device's current state
+  // (artp_field_update_learned, include/artp_c.h): every move priced again by the loaded network on the cost map of the
+  // last artp_cost_update_map*, and the mask edited as updateCostField edits it (an empty mask = the mask did not change;
+  // rect is then ignored).  The same bits as computeLearnedCostField on that state.  Returns dist and refreshes the
+  // "cost_to_go" layer.
+  std::vector<double> updateLearnedCostField(artp_field* kept, const std::vector<uint32_t>& mask,
+                                             const std::array<int, 4>* rect = nullptr) {
+    std::lock_guard<std::mutex> lock(map_mutex_);
+    if (!map_) throw std::runtime_error("updateLearnedCostField: the planner does not have a map set");
+    if (!kept) throw std::runtime_error("updateLearnedCostField: no field");
+    const auto g = map_->getGeometry();
+    const size_t cells = static_cast<size_t>(g.rows) * g.cols;
+    artp_field_stats_t st;
+    throwOnError(gpu_->get(), artp_field_stats(kept, &st), "artp_field_stats");
+    if ((!mask.empty() && mask.size() != cells) || st.nodes % cells != 0)
+      throw std::runtime_error("updateLearnedCostField: the mask or the field does not have rows * cols cells");
+    throwOnError(gpu_->get(),
+                 artp_field_update_learned(kept, mask.empty() ? nullptr : mask.data(), 0, rect ? rect->data() : nullptr),
+                 "artp_field_update_learned");
+    return refreshCostToGo(kept, cells, st.nodes);
   }
 
   void setSeed(uint64_t seed) {
@@ -562,6 +575,21 @@ class Planner {
   const std::shared_ptr<BatchTree>& tree() const { return tree_; }
 
  protected:
+  // the tail of both update calls: dist out of the kept field, the layer refreshed
+  std::vector<double> refreshCostToGo(artp_field* kept, size_t cells, size_t nodes) {
+    const size_t n_yaw = nodes / cells;
+    std::vector<double> dist(nodes);
+    throwOnError(gpu_->get(), artp_field_dist(kept, dist.data()), "artp_field_dist");
+    std::vector<float> best(cells);
+    for (size_t i = 0; i < cells; ++i) {
+      double b = std::numeric_limits<double>::infinity();
+      for (size_t k = 0; k < n_yaw; ++k) b = std::min(b, dist[i * n_yaw + k]);
+      best[i] = static_cast<float>(b);
+    }
+    map_->addLayer("cost_to_go", best.data());
+    return dist;
+  }
+
   // the tail of both computeCostField calls: dist out of the field, the field kept or destroyed, the layer refreshed
   std::vector<double> finishCostField(artp_field* f, size_t cells, unsigned n_yaw, artp_field** keep) {
     std::vector<double> dist(cells * n_yaw);

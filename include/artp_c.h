@@ -324,7 +324,7 @@ void artp_field_destroy(artp_field* f);
  * The result is an ordinary artp_field: artp_field_dist, _dist_dev, _path, _edge_costs (the travel-direction cost of
  * a -> b; +inf for an absent edge between neighbouring nodes), _stats and _destroy work on it unchanged.
  * artp_field_update refuses it with ARTP_ERR_INVALID_ARG: a map change moves the network's features, and with them the
- * weights, far beyond any sub-rectangle.
+ * weights, far beyond any sub-rectangle.  artp_field_update_learned (below) prices the whole table again instead.
  * Statuses, with nothing computed: ARTP_ERR_NO_WEIGHTS without a network, ARTP_ERR_NO_MAP without a feature map
  * (artp_cost_update_map*) or without the sampler layers, ARTP_ERR_INVALID_ARG for a negative or non-finite weight or
  * threshold and for everything artp_field_compute refuses about n_yaw, rect, the sources and inner_sweeps. */
@@ -345,6 +345,32 @@ int artp_field_compute_learned(artp_ctx* ctx, const artp_field_learned_params* p
                                artp_field** out);
 /* the table's six members are zero for a field of artp_field_compute */
 int artp_field_learned_stats(artp_field* f, artp_field_learned_stats_t* out);
+/* Update a learned field IN PLACE after the cost map, the network or the mask changed.  new_mask and
+ * sub_rect as in artp_field_update; new_mask = NULL: the mask did not change (sub_rect is ignored).  The call prices against
+ * what the context holds NOW -- the loaded network, the feature map of the last artp_cost_update_map*, the sampler layers --
+ * as a new artp_field_compute_learned would; the pricing weights and the threshold stay the field's own.  Every slot of the
+ * weight table is priced again (in the chunks of the original build); a slot whose bit pattern changes is written and flags
+ * its tile; then the passes of artp_field_update run from the flagged tiles (none when no word and no slot changed).
+ * After ARTP_OK dist, hops (artp_field_path), artp_field_edge_costs and reached_nodes are bit for bit those of
+ * artp_field_compute_learned with the field's own params, n_yaw, rectangle, sources and reverse on the merged mask and the
+ * current context state.  The first update allocates the chunk scratch (36 bytes a row) and keeps it until
+ * artp_field_destroy.  artp_field_learned_stats keeps describing the original compute.
+ * With the field untouched: ARTP_ERR_INVALID_ARG when the field is not a learned one, sub_rect is empty or not inside the
+ * rectangle, a source is no node of the merged mask, or the sampler layers do not have the geometry the field was computed
+ * on; ARTP_ERR_NO_WEIGHTS / ARTP_ERR_NO_MAP as artp_field_compute_learned gives them.  A HIP failure (ARTP_ERR_HIP) or
+ * ARTP_ERR_CAPACITY after those checks leaves the field UNDEFINED: destroy it.  Synchronous, on the context's stream. */
+typedef struct artp_field_learned_update_stats_t {
+  uint64_t changed_words, removed_nodes, added_nodes, dead_nodes, hop_dead_nodes, unsupport_rounds, dist_rounds,
+      hop_rounds, tile_launches, reached_nodes; /* as artp_field_update_stats_t */
+  uint64_t repriced_slots; /* slots of the weight table = rows sent through the cost query */
+  uint64_t changed_slots;  /* slots whose weight changed its bit pattern */
+  uint64_t weight_tiles;   /* tiles flagged by a changed weight */
+  double rows_ms, query_ms, reprice_ms; /* device time of the three steps of the repricing, summed over the chunks */
+  double passes_ms;                     /* host time of the four passes (every round is read by the host) */
+} artp_field_learned_update_stats_t;
+int artp_field_update_learned(artp_field* f, const uint32_t* new_mask, int mask_on_device, const int sub_rect[4]);
+/* the numbers of the last artp_field_update_learned that returned ARTP_OK (zeros before the first) */
+int artp_field_learned_update_stats(artp_field* f, artp_field_learned_update_stats_t* out);
 
 /* ---- ob::MotionValidator::checkMotion (OMPL DiscreteMotionValidator; call sites
  *      prm_motion_cost.cpp:652, lazy_prm_star_min_update.cpp:725), batched -----------------------
