@@ -2218,9 +2218,13 @@ struct LazyTree {
             pred_edge[v] = adje[a];
             open.push({nd, v});
           }
-        } else if (nd == dist[v] && pred[v] != u && pred[v] != 0xffffffffu && before(u, pred[v])) {
+        } else if (nd == dist[v] && du < dist[v] && pred[v] != u && pred[v] != 0xffffffffu && before(u, pred[v])) {
           // an equally short way in through a parent that a search from scratch settles earlier: that search would
-          // have kept it (see before()).  v may lie outside the subtree -- then its own subtree moves with it
+          // have kept it (see before()).  v may lie outside the subtree -- then its own subtree moves with it.
+          // Only from a strictly closer u: a descendant of v is never closer than v, so u is none of them.  At equal
+          // distance (a zero-cost edge, or a cost the sum absorbs) u may hang below v, and taking it as v's parent
+          // would close a cycle that the walk from the far terminal to the root never leaves (roadmaps whose every
+          // edge costs 0 did that).
           if (!in_s[v]) {
             unlink(v);
             pred[v] = u;
@@ -2389,6 +2393,12 @@ int roadmap_solve_tree(artp_roadmap* rm, double* path_se3, size_t cap_states, si
         std::reverse(pedge.begin(), pedge.end());
       }  // either way pedge[i] = edge path[i] -> path[i + 1]
       path_cost = t.dist[far];
+      if (t.root != 0u) {
+        // a tree that hangs from the goal sums the same edges from the goal's end: the reported cost is the sum from
+        // the start, as the first search, the device search and solve_many fold it (equal to the last bit, not nearly)
+        path_cost = 0.0;
+        for (const uint32_t e : pedge) path_cost += rm->ecost[e];
+      }
     }
     const size_t np = path.size();
     auto slot = [&](size_t i) { return 2 * (size_t)pedge[i] + (path[i] == rm->eu[pedge[i]] ? 0u : 1u); };
