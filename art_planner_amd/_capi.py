@@ -22,7 +22,9 @@ SYMBOLS = [
     "artp_reachability_halo", "artp_field_params_defaults", "artp_field_compute", "artp_field_dist", "artp_field_dist_dev",
     "artp_field_path", "artp_field_edge_costs", "artp_field_stats", "artp_field_update", "artp_field_update_stats",
     "artp_field_destroy", "artp_field_learned_params_defaults", "artp_field_compute_learned", "artp_field_learned_stats",
-    "artp_field_update_learned", "artp_field_learned_update_stats", "artp_check_motions_last_valid", "artp_check_motions_last_valid_dev",
+    "artp_field_update_learned", "artp_field_learned_update_stats", "artp_field_block_moves", "artp_field_unblock",
+    "artp_field_blocked_count", "artp_field_blocked", "artp_field_plan", "artp_field_plan_stats", "artp_field_plan_round_tile_runs",
+    "artp_check_motions_last_valid", "artp_check_motions_last_valid_dev",
     "artp_set_z_bounds", "artp_set_few_edges", "artp_set_edge_passes", "artp_cost_set_fc_path", "artp_check_motions", "artp_check_motions_dev", "artp_check_edges_interp",
     "artp_check_edges_interp_dev", "artp_compact_valid_dev", "artp_compact_valid_indices_dev", "artp_sample_states_at_dev",
     "artp_pack_edge_results_dev", "artp_cost_update_map_dev", "artp_pack_valid_bits_dev", "artp_indices_from_bits_dev",
@@ -135,6 +137,12 @@ class FieldLearnedUpdateStats(C.Structure):  # artp_field_learned_update_stats_t
                 [(n, C.c_double) for n in ("rows_ms", "query_ms", "reprice_ms", "passes_ms")])
 
 
+class FieldPlanStats(C.Structure):  # artp_field_plan_stats_t
+    _fields_ = ([(n, C.c_uint64) for n in ("rounds", "moves_checked", "moves_blocked", "updates", "update_tile_runs",
+                                           "last_update_tile_runs")] +
+                [(n, C.c_double) for n in ("descent_ms", "check_ms", "round_ms", "passes_ms")])
+
+
 class TreeParams(C.Structure):  # artp_tree_params (include/artp_c.h)
     _fields_ = [("seed", C.c_uint64), ("first_index", C.c_uint64), ("variant", C.c_int32), ("objective", C.c_int32),
                 ("max_lon_vel", C.c_double), ("max_lat_vel", C.c_double), ("max_ang_vel", C.c_double),
@@ -225,6 +233,13 @@ def _load_path(LIB_PATH):
     L.artp_field_update_learned.argtypes = [vp, vp, i32, vp]
     L.artp_field_learned_update_stats.argtypes = [vp, C.POINTER(FieldLearnedUpdateStats)]
     L.artp_field_destroy.restype = None
+    L.artp_field_block_moves.argtypes = [vp, vp, vp, sz, C.POINTER(C.c_uint64)]
+    L.artp_field_unblock.argtypes = [vp, vp, C.POINTER(C.c_uint64)]
+    L.artp_field_blocked_count.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.artp_field_blocked.argtypes = [vp, vp]
+    L.artp_field_plan.argtypes = [vp, vp, sz, i32, vp, vp, vp, vp, vp, sz]
+    L.artp_field_plan_stats.argtypes = [vp, C.POINTER(FieldPlanStats)]
+    L.artp_field_plan_round_tile_runs.argtypes = [vp, vp, sz, C.POINTER(sz)]
     L.artp_map_version.argtypes = [vp]
     L.artp_map_version.restype = C.c_uint64
     L.artp_set_z_bounds.argtypes = [vp, dbl, dbl]

@@ -3689,6 +3689,7 @@ int artp_cost_get_features(artp_ctx* c, float* out, int* fh, int* fw) {
 #include "roadmap_many.h"
 #include "reach.h"
 #include "field.h"
+#include "field_plan.h"
 #include "preprocess.h"
 #include "group.h"
 

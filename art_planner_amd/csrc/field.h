@@ -34,7 +34,9 @@
 // n_nodes + 2 rounds.  No launch waits for another workgroup and no kernel stays resident.
 //
 // artp_field_compute: relax PHASE 0 from the sources' tiles, then relax PHASE 1.  field_path_kernel: one wave walks from
-// the target to a source: lane m tests move m, the first tight one that is one hop closer wins.
+// the target to a source (field_descend): lane m tests move m, the first tight one that is one hop closer wins.
+// Every reader of a pull cost skips the slots of the field's blocked-move set (field_blocked_word; field_plan.h and
+// DESIGN.md section 16), when the field has one.
 // artp_field_update brings a computed field to the fixed point of an edited mask in place:
 //   field_update_sources_kernel / field_diff_kernel   refuse a removed source; install the changed words (and heights),
 //                       clear the removed nodes, flag the tiles around every changed cell
@@ -166,17 +168,31 @@ __device__ __forceinline__ bool field_neighbour(const FieldGrid& G, int r, int c
 // the move that leads back: b = a's neighbour by move m  <=>  a = b's neighbour by move field_back_move(m)
 __host__ __device__ constexpr int field_back_move(int m) { return m < 8 ? 7 - m : (m == 8 ? 9 : 8); }
 
+// The blocked-move set of a field (field_plan.h): one 16-bit word per node, bit j set = pull slot
+// (v, j) is blocked, an absent edge.  blk == nullptr: the field never blocked anything.  Every reader of a pull cost goes
+// through this one function and skips the slots whose bit is set.
+__device__ __forceinline__ uint32_t field_blocked_word(const uint16_t* __restrict__ blk, size_t node) {
+  return blk ? (uint32_t)blk[node] : 0u;
+}
+// The bits of pull slot j.  At two headings moves 8 and 9 lead to the same neighbour: one directed rotation sits in both
+// slots of its owner, and the two bits are set, tested and counted as one.
+__device__ __forceinline__ uint32_t field_slot_bits(const FieldGrid& G, int j) {
+  return (G.n_yaw == 2 && j >= 8) ? 0x300u : 1u << j;
+}
+
 // The live neighbours of node (cell, k) over the ten moves, for the kernels with one lane per node: visit(ni, w) with ni
 // the neighbour's node index (its cell and heading) and w() the pull cost of that move, computed when a rule asks
 // (objective 2: read from the weight table, which `tab` then is).
 template <class F>
 __device__ __forceinline__ void field_walk(const FieldGrid& G, const uint32_t* __restrict__ mask, const float* __restrict__ h,
-                                           const double* __restrict__ tab, uint32_t cell, int k, F&& visit) {
+                                           const double* __restrict__ tab, const uint16_t* __restrict__ blk, uint32_t cell,
+                                           int k, F&& visit) {
   const int r = (int)(cell % (uint32_t)G.nrows), c = (int)(cell / (uint32_t)G.nrows);
+  const uint32_t bw = field_blocked_word(blk, (size_t)cell * G.n_yaw + k);
 #pragma unroll
   for (int m = 0; m < 10; ++m) {
     int nr, nc, nk;
-    if (!field_neighbour(G, r, c, k, m, &nr, &nc, &nk)) continue;
+    if (((bw >> m) & 1u) || !field_neighbour(G, r, c, k, m, &nr, &nc, &nk)) continue;
     const uint32_t ncell = m < 8 ? (uint32_t)nr + (uint32_t)nc * (uint32_t)G.nrows : cell;  // a rotation: the node's own word
     if (!((mask[ncell] >> nk) & 1u)) continue;
     visit((size_t)ncell * G.n_yaw + nk, [&]() {
@@ -188,7 +204,8 @@ __device__ __forceinline__ void field_walk(const FieldGrid& G, const uint32_t* _
 template <int PHASE>
 __global__ void __launch_bounds__(256)
 field_plain_kernel(FieldGrid G, const uint32_t* __restrict__ mask, const float* __restrict__ h,
-                   const double* __restrict__ tab, double* dist, uint32_t* hops, unsigned* __restrict__ changed) {
+                   const double* __restrict__ tab, const uint16_t* __restrict__ blk, double* dist, uint32_t* hops,
+                   unsigned* __restrict__ changed) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t n = (size_t)G.nrows * G.ncols * G.n_yaw;
   bool ch = false;
@@ -199,7 +216,7 @@ field_plain_kernel(FieldGrid G, const uint32_t* __restrict__ mask, const float* 
       const double old = dist[i];
       if (PHASE == 0) {
         double best = old;
-        field_walk(G, mask, h, tab, cell, k, [&](size_t ni, auto&& w) {
+        field_walk(G, mask, h, tab, blk, cell, k, [&](size_t ni, auto&& w) {
           const double du = dist[ni];
           if (!(du < best)) return;  // w >= 0: no candidate below du
           const double cand = du + w();
@@ -212,7 +229,7 @@ field_plain_kernel(FieldGrid G, const uint32_t* __restrict__ mask, const float* 
       } else if (old < INFINITY) {
         const uint32_t hold = hops[i];
         uint32_t hb = hold;
-        field_walk(G, mask, h, tab, cell, k, [&](size_t ni, auto&& w) {
+        field_walk(G, mask, h, tab, blk, cell, k, [&](size_t ni, auto&& w) {
           const uint32_t hu = hops[ni];
           if (hu == FIELD_NONE || hu + 1u >= hb) return;
           if (dist[ni] + w() == old) hb = hu + 1u;
@@ -231,7 +248,8 @@ field_plain_kernel(FieldGrid G, const uint32_t* __restrict__ mask, const float* 
 template <int PHASE>
 __global__ void __launch_bounds__(256)
 field_unsupport_plain_kernel(FieldGrid G, const uint32_t* __restrict__ mask, const float* __restrict__ h,
-                             const double* __restrict__ tab, double* dist, uint32_t* hops, unsigned* __restrict__ counters) {
+                             const double* __restrict__ tab, const uint16_t* __restrict__ blk, double* dist, uint32_t* hops,
+                             unsigned* __restrict__ counters) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t n = (size_t)G.nrows * G.ncols * G.n_yaw;
   bool die = false;
@@ -245,7 +263,7 @@ field_unsupport_plain_kernel(FieldGrid G, const uint32_t* __restrict__ mask, con
       if (dv < INFINITY && hv != 0u && !(PHASE == 1 && hv == FIELD_NONE)) {
         bool sup = false;
         if (hv != FIELD_NONE)
-          field_walk(G, mask, h, tab, cell, k, [&](size_t ni, auto&& w) {
+          field_walk(G, mask, h, tab, blk, cell, k, [&](size_t ni, auto&& w) {
             if (sup) return;
             const uint32_t hu = hops[ni];
             if (hu == FIELD_NONE || hu + 1u != hv) return;
@@ -290,16 +308,16 @@ __device__ __forceinline__ double field_lane_cost(const FieldGrid& G, const Fiel
 
 // The live neighbours of heading k of the lane's cell over the ten moves: visit(li, m) with li the neighbour's place in
 // the LDS planes (heading included) and m the move, for field_lane_cost (not a cost callable as in field_walk: a closure
-// over L sends the lane's arrays to scratch).
+// over L sends the lane's arrays to scratch).  bw: the node's blocked word (field_blocked_word); a set bit hides the slot.
 template <class F>
-__device__ __forceinline__ void field_tile_walk(const FieldGrid& G, const FieldLane& L, int k, F&& visit) {
+__device__ __forceinline__ void field_tile_walk(const FieldGrid& G, const FieldLane& L, int k, uint32_t bw, F&& visit) {
 #pragma unroll
   for (int j = 0; j < 8; ++j)
-    if ((L.nbm[j] >> k) & 1u) visit(k * FIELD_PLANE + L.me + field_dr(j) + field_dc(j) * FIELD_HP, j);
+    if ((L.nbm[j] >> k) & ~(bw >> j) & 1u) visit(k * FIELD_PLANE + L.me + field_dr(j) + field_dc(j) * FIELD_HP, j);
   if (G.n_yaw > 1) {
     const int kp = k + 1 == G.n_yaw ? 0 : k + 1, km = k == 0 ? G.n_yaw - 1 : k - 1;
-    if ((L.mw >> kp) & 1u) visit(kp * FIELD_PLANE + L.me, 8);
-    if ((L.mw >> km) & 1u) visit(km * FIELD_PLANE + L.me, 9);
+    if ((L.mw >> kp) & ~(bw >> 8) & 1u) visit(kp * FIELD_PLANE + L.me, 8);
+    if ((L.mw >> km) & ~(bw >> 9) & 1u) visit(km * FIELD_PLANE + L.me, 9);
   }
 }
 
@@ -307,7 +325,7 @@ __device__ __forceinline__ void field_tile_walk(const FieldGrid& G, const FieldL
 // LEARNED: the ten pull weights of this heading are wl[0..9], the lane's slots of the weight table.
 template <int PHASE, bool UNSUP, bool LEARNED>
 __device__ __forceinline__ bool field_tile_rule(const FieldGrid& G, const FieldLane& L, const double* stab, const double* wl,
-                                                double* sd, uint32_t* shop, int k) {
+                                                double* sd, uint32_t* shop, int k, uint32_t bw) {
   const int own = k * FIELD_PLANE + L.me;
   const double old = sd[own];
   if (UNSUP) {
@@ -316,7 +334,7 @@ __device__ __forceinline__ bool field_tile_rule(const FieldGrid& G, const FieldL
     if (!(old < INFINITY) || hv == 0u || (PHASE == 1 && hv == FIELD_NONE)) return false;
     bool sup = false;
     if (hv != FIELD_NONE)
-      field_tile_walk(G, L, k, [&](int li, int m) {
+      field_tile_walk(G, L, k, bw, [&](int li, int m) {
         const uint32_t hu = shop[li];
         if (hu == FIELD_NONE || hu + 1u != hv) return;
         if (sd[li] + (LEARNED ? wl[m] : field_lane_cost(G, L, stab, m, k)) == old) sup = true;
@@ -328,7 +346,7 @@ __device__ __forceinline__ bool field_tile_rule(const FieldGrid& G, const FieldL
   }
   if (PHASE == 0) {
     double best = old;
-    field_tile_walk(G, L, k, [&](int li, int m) {
+    field_tile_walk(G, L, k, bw, [&](int li, int m) {
       const double cand = sd[li] + (LEARNED ? wl[m] : field_lane_cost(G, L, stab, m, k));
       if (cand < best) best = cand;
     });
@@ -338,7 +356,7 @@ __device__ __forceinline__ bool field_tile_rule(const FieldGrid& G, const FieldL
   if (!(old < INFINITY)) return false;
   const uint32_t hold = shop[own];
   uint32_t hb = hold;
-  field_tile_walk(G, L, k, [&](int li, int m) {
+  field_tile_walk(G, L, k, bw, [&](int li, int m) {
     const uint32_t hu = shop[li];
     if (hu == FIELD_NONE || hu + 1u >= hb) return;
     if (sd[li] + (LEARNED ? wl[m] : field_lane_cost(G, L, stab, m, k)) == old) hb = hu + 1u;
@@ -353,11 +371,12 @@ __device__ __forceinline__ bool field_tile_rule(const FieldGrid& G, const FieldL
 // update, the tiles whose own cells or halo an unsupport pass changed: the seeds of the relax pass that follows.
 // LEARNED (objective 2): tabg is the weight table.  It is streamed from global memory, not staged: at 16 headings a tile's
 // weights are 328 KB.  The ten loads of a heading are issued in front of that heading's LDS reads.
+// blk (may be nullptr): the blocked words, streamed the same way: one 16-bit load per lane and heading in front of the rule.
 template <int PHASE, bool UNSUP, bool LEARNED = false>
 __global__ void __launch_bounds__(256)
 field_tile_kernel(FieldGrid G, const uint32_t* __restrict__ mask, const float* __restrict__ h,
-                  const double* __restrict__ tabg, double* dist, uint32_t* hops, unsigned* act_cur, unsigned* act_nxt,
-                  unsigned* acc, unsigned* __restrict__ counters, int inner_max) {
+                  const double* __restrict__ tabg, const uint16_t* __restrict__ blk, double* dist, uint32_t* hops,
+                  unsigned* act_cur, unsigned* act_nxt, unsigned* acc, unsigned* __restrict__ counters, int inner_max) {
   constexpr bool HOPS = PHASE == 1 || UNSUP;  // hop planes in LDS
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tile = blockIdx.x;
@@ -410,6 +429,8 @@ field_tile_kernel(FieldGrid G, const uint32_t* __restrict__ mask, const float* _
                              (tc == FIELD_T - 1 ? 8u : 0u) | 16u;
   unsigned changes = 0u;
   int still = 0;
+  // the lane's node at heading 0 (a lane outside the rectangle has L.mw == 0 and never reads)
+  const size_t node0 = ((size_t)(r0 + tr) + (size_t)(c0 + tc) * G.nrows) * ny;
   for (int sweep = 0; sweep < inner_max; ++sweep) {
     bool ch = false;
     for (int k = 0; k < ny; ++k) {
@@ -420,7 +441,8 @@ field_tile_kernel(FieldGrid G, const uint32_t* __restrict__ mask, const float* _
 #pragma unroll
         for (int j = 0; j < 10; ++j) wl[j] = wk[j * (FIELD_T * FIELD_T)];
       }
-      if (field_tile_rule<PHASE, UNSUP, LEARNED>(G, L, stab, wl, sd, shop, k)) {
+      const uint32_t bw = field_blocked_word(blk, node0 + k);
+      if (field_tile_rule<PHASE, UNSUP, LEARNED>(G, L, stab, wl, sd, shop, k, bw)) {
         ch = true;
         ++changes;
       }
@@ -475,17 +497,59 @@ field_count_kernel(size_t n, const double* __restrict__ dist, unsigned long long
   if ((threadIdx.x & 63) == 0 && b) atomicAdd(count, (unsigned long long)__popcll(b));
 }
 
+// The descent of one wave from node (r, c, k), at hv hops and distance dv, to a source: lane m tests move m, the first tight
+// one that is one hop closer and not blocked wins.  nodes (n = hv + 1 triples) in travel order.  false: no tight
+// predecessor (cannot happen at the fixed point).  Shared by field_path_kernel and field_paths_kernel (field_plan.h).
+__device__ __forceinline__ bool field_descend(const FieldGrid& G, const uint32_t* __restrict__ mask, const float* __restrict__ h,
+                                              const double* __restrict__ tab, const uint16_t* __restrict__ blk,
+                                              const double* __restrict__ dist, const uint32_t* __restrict__ hops, int r, int c,
+                                              int k, uint32_t hv, double dv, int* __restrict__ nodes) {
+  const int lane = threadIdx.x & 63;
+  const long long n = (long long)hv + 1;
+  for (long long step = 0;; ++step) {
+    if (lane == 0) {
+      int* o = nodes + 3 * (G.reverse ? step : n - 1 - step);
+      o[0] = r;
+      o[1] = c;
+      o[2] = k;
+    }
+    if (hv == 0u) return true;
+    bool ok = false;
+    int nr = 0, nc = 0, nk = 0;
+    const size_t cell = (size_t)r + (size_t)c * G.nrows;
+    if (lane < 10 && !((field_blocked_word(blk, cell * G.n_yaw + k) >> lane) & 1u) &&
+        field_neighbour(G, r, c, k, lane, &nr, &nc, &nk)) {
+      const size_t ncell = (size_t)nr + (size_t)nc * G.nrows;
+      if ((mask[ncell] >> nk) & 1u) {
+        const size_t ni = ncell * G.n_yaw + nk;
+        const double w = G.objective == 2 ? tab[field_wtab_index(G, r, c, k, lane)]
+                                          : field_pull_cost(G, tab, lane, k, h[cell], h[ncell]);
+        ok = hops[ni] + 1u == hv && dist[ni] + w == dv;
+      }
+    }
+    const unsigned long long b = __ballot(ok);
+    if (!b) return false;
+    const int m = __ffsll((long long)b) - 1;
+    field_neighbour(G, r, c, k, m, &nr, &nc, &nk);
+    r = nr;
+    c = nc;
+    k = nk;
+    dv = dist[((size_t)r + (size_t)c * G.nrows) * G.n_yaw + k];
+    hv -= 1u;
+  }
+}
+
 // One wave.  out_n: the states of the path (0 = unreachable, -1 = no tight predecessor: cannot happen at the fixed point);
 // nodes (cap triples) in travel order when they fit.
 __global__ void __launch_bounds__(64)
 field_path_kernel(FieldGrid G, const uint32_t* __restrict__ mask, const float* __restrict__ h,
-                  const double* __restrict__ tab, const double* __restrict__ dist, const uint32_t* __restrict__ hops,
-                  int r, int c, int k, long long cap, int* __restrict__ nodes, long long* __restrict__ out_n,
-                  double* __restrict__ out_cost) {
+                  const double* __restrict__ tab, const uint16_t* __restrict__ blk, const double* __restrict__ dist,
+                  const uint32_t* __restrict__ hops, int r, int c, int k, long long cap, int* __restrict__ nodes,
+                  long long* __restrict__ out_n, double* __restrict__ out_cost) {
   const int lane = threadIdx.x;
-  size_t node = ((size_t)r + (size_t)c * G.nrows) * G.n_yaw + k;
-  uint32_t hv = hops[node];
-  double dv = dist[node];
+  const size_t node = ((size_t)r + (size_t)c * G.nrows) * G.n_yaw + k;
+  const uint32_t hv = hops[node];
+  const double dv = dist[node];
   if (lane == 0) *out_cost = dv;
   if (hv == FIELD_NONE) {
     if (lane == 0) *out_n = 0;
@@ -494,39 +558,7 @@ field_path_kernel(FieldGrid G, const uint32_t* __restrict__ mask, const float* _
   const long long n = (long long)hv + 1;
   if (lane == 0) *out_n = n;
   if (n > cap) return;
-  for (long long step = 0;; ++step) {
-    if (lane == 0) {
-      int* o = nodes + 3 * (G.reverse ? step : n - 1 - step);
-      o[0] = r;
-      o[1] = c;
-      o[2] = k;
-    }
-    if (hv == 0u) break;
-    bool ok = false;
-    int nr = 0, nc = 0, nk = 0;
-    if (lane < 10 && field_neighbour(G, r, c, k, lane, &nr, &nc, &nk)) {
-      const size_t ncell = (size_t)nr + (size_t)nc * G.nrows;
-      if ((mask[ncell] >> nk) & 1u) {
-        const size_t ni = ncell * G.n_yaw + nk;
-        const double w = G.objective == 2 ? tab[field_wtab_index(G, r, c, k, lane)]
-                                          : field_pull_cost(G, tab, lane, k, h[(size_t)r + (size_t)c * G.nrows], h[ncell]);
-        ok = hops[ni] + 1u == hv && dist[ni] + w == dv;
-      }
-    }
-    const unsigned long long b = __ballot(ok);
-    if (!b) {
-      if (lane == 0) *out_n = -1;
-      return;
-    }
-    const int m = __ffsll((long long)b) - 1;
-    field_neighbour(G, r, c, k, m, &nr, &nc, &nk);
-    r = nr;
-    c = nc;
-    k = nk;
-    node = ((size_t)r + (size_t)c * G.nrows) * G.n_yaw + k;
-    dv = dist[node];
-    hv -= 1u;
-  }
+  if (!field_descend(G, mask, h, tab, blk, dist, hops, r, c, k, hv, dv, nodes) && lane == 0) *out_n = -1;
 }
 
 // the lattice poses of n nodes (triples local to the rectangle)
@@ -544,8 +576,9 @@ field_poses_kernel(SamplerDev sm, MapGeom g, ReachRect rc, const int* __restrict
 }
 
 __global__ void __launch_bounds__(256)
-field_edge_cost_kernel(FieldGrid G, const float* __restrict__ h, const double* __restrict__ tab, const int* __restrict__ a,
-                       const int* __restrict__ b, size_t n, double* __restrict__ out) {
+field_edge_cost_kernel(FieldGrid G, const float* __restrict__ h, const double* __restrict__ tab,
+                       const uint16_t* __restrict__ blk, const int* __restrict__ a, const int* __restrict__ b, size_t n,
+                       double* __restrict__ out) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const int r = a[3 * i], c = a[3 * i + 1], k = a[3 * i + 2];
@@ -562,6 +595,9 @@ field_edge_cost_kernel(FieldGrid G, const float* __restrict__ h, const double* _
       else
         w = m < 8 ? field_move_cost(G, tab, m, k, h[(size_t)r + (size_t)c * G.nrows], h[(size_t)br + (size_t)bc * G.nrows])
                   : G.wrot;
+      // the slot that holds a -> b: (a, m) of a reverse field, (b, the move back) of a forward one
+      const size_t owner = G.reverse ? ((size_t)r + (size_t)c * G.nrows) * G.n_yaw + k : ((size_t)br + (size_t)bc * G.nrows) * G.n_yaw + bk;
+      if (field_blocked_word(blk, owner) & field_slot_bits(G, G.reverse ? m : field_back_move(m))) w = INFINITY;
       break;
     }
   }
@@ -793,6 +829,14 @@ struct artp_field {
   // artp_field_update_learned: d_lscratch stays from the first update on
   unsigned* d_wacc = nullptr;           // n_tiles flags: the tiles a changed weight flagged
   artp_field_learned_update_stats_t lustats{};
+  // the blocked-move set (field_plan.h): allocated by the first block, one 16-bit word per node (padded to 32-bit words)
+  uint16_t* d_blk = nullptr;
+  uint64_t n_blocked = 0;               // bits set in d_blk
+  artp_field_plan_stats_t pstats{};
+  std::vector<uint64_t> plan_round_runs;  // tile runs of the repair of every round of the last artp_field_plan (0: none)
+  // artp_field_plan's scratch: per-target records, path nodes, poses, the move list, the (s1, s2) pairs and verdicts
+  void* d_plan = nullptr;
+  size_t plan_targets = 0, plan_states = 0;
 };
 
 namespace {
@@ -800,7 +844,7 @@ namespace {
 void field_free(artp_field* f) {
   for (void* p : {(void*)f->d_dist, (void*)f->d_hops, (void*)f->d_mask, (void*)f->d_h, (void*)f->d_tab, (void*)f->d_flags,
                   (void*)f->d_nodes, (void*)f->d_out, (void*)f->d_src, (void*)f->d_snap, (void*)f->d_acc, (void*)f->d_ucnt,
-                  (void*)f->d_stage, (void*)f->d_lscratch, (void*)f->d_wacc})
+                  (void*)f->d_stage, (void*)f->d_lscratch, (void*)f->d_wacc, (void*)f->d_blk, f->d_plan})
     if (p) (void)hipFree(p);
   delete f;
 }
@@ -890,7 +934,7 @@ int field_pass(artp_field* f, unsigned* d_seed, FieldRounds* out) {
     return field_rounds(f, 16, too_many, out, [&](unsigned*, unsigned*, unsigned* counters) {
       hipLaunchKernelGGL(UNSUP ? artp::field_unsupport_plain_kernel<PHASE> : artp::field_plain_kernel<PHASE>, dim3(blocks),
                          dim3(256), 0, st, G, (const uint32_t*)f->d_mask, (const float*)f->d_h, (const double*)f->d_tab,
-                         f->d_dist, f->d_hops, counters);
+                         (const uint16_t*)f->d_blk, f->d_dist, f->d_hops, counters);
     });
   }
   if (d_seed) {
@@ -910,8 +954,8 @@ int field_pass(artp_field* f, unsigned* d_seed, FieldRounds* out) {
                                    (int)lds));
   return field_rounds(f, 1, too_many, out, [&](unsigned* cur, unsigned* nxt, unsigned* counters) {
     hipLaunchKernelGGL(kernel, dim3((unsigned)f->n_tiles), dim3(256), lds, st, G,
-                       (const uint32_t*)f->d_mask, (const float*)f->d_h, (const double*)f->d_tab, f->d_dist, f->d_hops, cur,
-                       nxt, UNSUP ? d_seed : nullptr, counters, f->params.inner_sweeps);
+                       (const uint32_t*)f->d_mask, (const float*)f->d_h, (const double*)f->d_tab, (const uint16_t*)f->d_blk,
+                       f->d_dist, f->d_hops, cur, nxt, UNSUP ? d_seed : nullptr, counters, f->params.inner_sweeps);
   });
 }
 
@@ -1334,7 +1378,7 @@ int artp_field_path(artp_field* f, const int* target, int* nodes_out, double* se
   // d_out: [0] = cost, [1] = the count (as long long), [8 ..] = the poses
   long long* d_n = reinterpret_cast<long long*>(f->d_out + 1);
   hipLaunchKernelGGL(artp::field_path_kernel, dim3(1), dim3(64), 0, st, G, (const uint32_t*)f->d_mask, (const float*)f->d_h,
-                     (const double*)f->d_tab, (const double*)f->d_dist, (const uint32_t*)f->d_hops, target[0], target[1],
+                     (const double*)f->d_tab, (const uint16_t*)f->d_blk, (const double*)f->d_dist, (const uint32_t*)f->d_hops, target[0], target[1],
                      target[2], (long long)cap, f->d_nodes, d_n, f->d_out);
   HIP_TRY(c, hipGetLastError());
   double head[2];
@@ -1377,7 +1421,8 @@ int artp_field_edge_costs(artp_field* f, const int* a, const int* b, size_t n, d
   HIP_TRY(c, hipMemcpyAsync(f->d_nodes, a, 3 * n * sizeof(int), hipMemcpyHostToDevice, st));
   HIP_TRY(c, hipMemcpyAsync(f->d_nodes + 3 * n, b, 3 * n * sizeof(int), hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(artp::field_edge_cost_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, f->grid,
-                     (const float*)f->d_h, (const double*)f->d_tab, (const int*)f->d_nodes, (const int*)(f->d_nodes + 3 * n),
+                     (const float*)f->d_h, (const double*)f->d_tab, (const uint16_t*)f->d_blk, (const int*)f->d_nodes,
+                     (const int*)(f->d_nodes + 3 * n),
                      n, f->d_out);
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipMemcpyAsync(cost_out, f->d_out, n * sizeof(double), hipMemcpyDeviceToHost, st));

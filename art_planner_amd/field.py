@@ -160,6 +160,108 @@ class CostField:
         self.ctx._chk(self.L.artp_field_learned_update_stats(self.h, C.byref(s)), "artp_field_learned_update_stats")
         return {n: getattr(s, n) for n, _ in _capi.FieldLearnedUpdateStats._fields_}
 
+    def block_moves(self, a, b) -> int:
+        """Block the moves a[i] -> b[i] ((n, 3) node triples, travel direction) and repair the field in place
+        (artp_field_block_moves): the same bits as a new field with the same set blocked.  Only the
+        stated direction is blocked.  Returns the number of moves that were not blocked before."""
+        a = np.ascontiguousarray(a, np.int32).reshape(-1, 3)
+        b = np.ascontiguousarray(b, np.int32).reshape(-1, 3)
+        assert len(a) == len(b)
+        n = C.c_uint64(0)
+        self.ctx._chk(self.L.artp_field_block_moves(self.h, a.ctypes.data, b.ctypes.data, len(a), C.byref(n)),
+                      "artp_field_block_moves")
+        return int(n.value)
+
+    def unblock(self, rect=None) -> int:
+        """Clear the blocked moves of the nodes whose cell lies in rect = (row0, col0, nrows, ncols) local to the field
+        (None = all) and repair the field (artp_field_unblock).  Returns the number of moves unblocked."""
+        r = None if rect is None else np.ascontiguousarray(rect, np.int32).reshape(4)
+        n = C.c_uint64(0)
+        self.ctx._chk(self.L.artp_field_unblock(self.h, r.ctypes.data if r is not None else None, C.byref(n)),
+                      "artp_field_unblock")
+        return int(n.value)
+
+    def blocked(self) -> np.ndarray:
+        """(nrows, ncols, n_yaw) uint16: bit j of node v = pull slot (v, j) is blocked (forward field: the move onto v from
+        its neighbour by offset j; reverse field: the move from v to it).  Zeros when nothing was ever blocked."""
+        out = np.empty((self.ncols, self.nrows, self.n_yaw), np.uint16)
+        self.ctx._chk(self.L.artp_field_blocked(self.h, out.ctypes.data), "artp_field_blocked")
+        return out.transpose(1, 0, 2)
+
+    def blocked_count(self) -> int:
+        n = C.c_uint64(0)
+        self.ctx._chk(self.L.artp_field_blocked_count(self.h, C.byref(n)), "artp_field_blocked_count")
+        return int(n.value)
+
+    def plan(self, targets, max_rounds=64) -> list:
+        """Lazily checked paths to (n, 3) target triples (artp_field_plan): per round the field's path of every pending
+        target, one batched check_motions of all their moves, the failing moves blocked and the field repaired.
+        Returns one (status, nodes, se3, cost) per target: status 0 = every move passed (nodes (n, 3) int32 and se3
+        (n, 7) in travel order, cost = dist[target]), 1 = unreachable, 2 = max_rounds exhausted (nodes and se3 None,
+        cost +inf).  The blocks stay on the field: a second call continues."""
+        t = np.ascontiguousarray(targets, np.int32).reshape(-1, 3)
+        nt = len(t)
+        self._plan_stats = None
+        if nt == 0:
+            return []
+        st = np.empty(nt, np.int32)
+        cost = np.empty(nt, np.float64)
+        off = np.zeros(nt + 1, np.uint64)
+        cap = nt * min(self.nrows * self.ncols * self.n_yaw, 1024)
+        total, rounds_left = None, int(max_rounds)
+        while True:
+            nodes = np.empty((cap, 3), np.int32)
+            se3 = np.empty((cap, 7), np.float64)
+            rc = self.L.artp_field_plan(self.h, t.ctypes.data, nt, max(rounds_left, 1), st.ctypes.data, cost.ctypes.data,
+                                        off.ctypes.data, nodes.ctypes.data, se3.ctypes.data, cap)
+            if rc in (0, -5):
+                total = self._add_plan_stats(total, self._read_plan_stats())
+            if rc == -5 and int(off[nt]) > cap:
+                # the paths hold more states than the buffers: the work is done and stays on the field; one more
+                # round hands the checked paths out, and plan_stats() keeps describing both calls together
+                cap = int(off[nt])
+                rounds_left = int(max_rounds) - int(total["rounds"])
+                continue
+            self.ctx._chk(rc, "artp_field_plan")
+            break
+        self._plan_stats = total
+        out = []
+        for i in range(nt):
+            lo, hi = int(off[i]), int(off[i + 1])
+            if st[i] == 0:
+                out.append((0, nodes[lo:hi].copy(), se3[lo:hi].copy(), float(cost[i])))
+            else:
+                out.append((int(st[i]), None, None, float(cost[i])))
+        return out
+
+    def _read_plan_stats(self) -> dict:
+        s = _capi.FieldPlanStats()
+        self.ctx._chk(self.L.artp_field_plan_stats(self.h, C.byref(s)), "artp_field_plan_stats")
+        d = {n: getattr(s, n) for n, _ in _capi.FieldPlanStats._fields_}
+        n = C.c_size_t(0)
+        self.ctx._chk(self.L.artp_field_plan_round_tile_runs(self.h, None, 0, C.byref(n)), "artp_field_plan_round_tile_runs")
+        runs = np.zeros(max(n.value, 1), np.uint64)
+        self.ctx._chk(self.L.artp_field_plan_round_tile_runs(self.h, runs.ctypes.data, n.value, C.byref(n)),
+                      "artp_field_plan_round_tile_runs")
+        d["round_tile_runs"] = [int(v) for v in runs[:n.value]]
+        return d
+
+    @staticmethod
+    def _add_plan_stats(total, d):
+        if total is None:
+            return d
+        out = {k: total[k] + d[k] for k in d}          # counts and times add up, the rounds' lists follow one another
+        out["last_update_tile_runs"] = d["last_update_tile_runs"] if d["updates"] else total["last_update_tile_runs"]
+        return out
+
+    def plan_stats(self) -> dict:
+        """The numbers of the last plan() (artp_field_plan_stats, and round_tile_runs: the tiles that ran in the repair of
+        every round, artp_field_plan_round_tile_runs); where plan() had to ask twice because the paths outgrew its
+        buffers, the two calls together.  Before the first plan(): the library's own record."""
+        if getattr(self, "_plan_stats", None) is not None:
+            return dict(self._plan_stats)
+        return self._read_plan_stats()
+
     def learned_stats(self) -> dict:
         """The weight table of a learned field and the time its steps took (artp_field_learned_stats)."""
         s = _capi.FieldLearnedStats()

@@ -364,7 +364,8 @@ class Planner {
   // reverse.  mask = what computeReachability(n_yaw) returned, or an edited copy (keep-out zones).  Returns dist,
   // index (r + c rows) n_yaw + k, +inf where unreachable, and stores the smallest cost over the headings of each cell
   // as the float layer "cost_to_go" of the planner's Map.  The objective and its velocities come from
-  // Params::objectives.custom_path_length.  Lattice paths are proposals: their moves' interior states are not checked.
+  // Params::objectives.custom_path_length.  Lattice paths are proposals: their moves' interior states are not checked
+  // (planOnCostField checks them and takes the verdicts back into a kept field).
   std::vector<double> computeCostField(const std::vector<uint32_t>& mask, unsigned n_yaw,
                                        const std::vector<std::array<int, 3>>& sources, bool reverse = false,
                                        artp_field** keep = nullptr) {
@@ -462,6 +463,122 @@ class Planner {
                  artp_field_update_learned(kept, mask.empty() ? nullptr : mask.data(), 0, rect ? rect->data() : nullptr),
                  "artp_field_update_learned");
     return refreshCostToGo(kept, cells, st.nodes);
+  }
+
+  // Single moves taken out of a kept field (artp_field_block_moves, include/artp_c.h): from[i] -> to[i] in travel
+  // direction, each one of the ten lattice moves; the field is repaired in place and holds the bits of a new field with
+  // the same moves blocked.  Only the stated direction is blocked.  Returns dist and refreshes the "cost_to_go" layer.
+  std::vector<double> blockCostFieldMoves(artp_field* kept, const std::vector<std::array<int, 3>>& from,
+                                          const std::vector<std::array<int, 3>>& to, uint64_t* newly_blocked = nullptr) {
+    std::lock_guard<std::mutex> lock(map_mutex_);
+    if (!map_) throw std::runtime_error("blockCostFieldMoves: the planner does not have a map set");
+    if (!kept) throw std::runtime_error("blockCostFieldMoves: no field");
+    if (from.size() != to.size()) throw std::runtime_error("blockCostFieldMoves: from and to differ in length");
+    const auto g = map_->getGeometry();
+    const size_t cells = static_cast<size_t>(g.rows) * g.cols;
+    artp_field_stats_t st;
+    throwOnError(gpu_->get(), artp_field_stats(kept, &st), "artp_field_stats");
+    if (st.nodes % cells != 0) throw std::runtime_error("blockCostFieldMoves: the field does not have rows * cols cells");
+    std::vector<int> a, b;
+    for (const auto& s : from) a.insert(a.end(), s.begin(), s.end());
+    for (const auto& s : to) b.insert(b.end(), s.begin(), s.end());
+    throwOnError(gpu_->get(), artp_field_block_moves(kept, a.data(), b.data(), from.size(), newly_blocked),
+                 "artp_field_block_moves");
+    return refreshCostToGo(kept, cells, st.nodes);
+  }
+
+  // The blocked moves of the nodes whose cell lies in rect = (row0, col0, nrows, ncols) given back to a kept field
+  // (artp_field_unblock; nullptr = all of them): what a caller runs after the map changed there -- the written rectangle
+  // grown by artp_reachability_halo() plus one cell is enough.  Returns dist and refreshes the "cost_to_go" layer.
+  std::vector<double> unblockCostField(artp_field* kept, const std::array<int, 4>* rect = nullptr,
+                                       uint64_t* unblocked = nullptr) {
+    std::lock_guard<std::mutex> lock(map_mutex_);
+    if (!map_) throw std::runtime_error("unblockCostField: the planner does not have a map set");
+    if (!kept) throw std::runtime_error("unblockCostField: no field");
+    const auto g = map_->getGeometry();
+    const size_t cells = static_cast<size_t>(g.rows) * g.cols;
+    artp_field_stats_t st;
+    throwOnError(gpu_->get(), artp_field_stats(kept, &st), "artp_field_stats");
+    if (st.nodes % cells != 0) throw std::runtime_error("unblockCostField: the field does not have rows * cols cells");
+    throwOnError(gpu_->get(), artp_field_unblock(kept, rect ? rect->data() : nullptr, unblocked), "artp_field_unblock");
+    return refreshCostToGo(kept, cells, st.nodes);
+  }
+
+  // Lazily checked lattice paths on a kept field (artp_field_plan): per round the field's path to every pending target,
+  // checkMotion of all their moves in one device batch, the failing moves blocked and the field repaired, at most
+  // max_rounds rounds.  status 0: every move of the path passed (nodes and SE3 states in travel order, cost =
+  // dist[target]); 1: unreachable; 2: rounds exhausted.  The blocks stay on the field: a second call continues.
+  // Refreshes the "cost_to_go" layer, since the blocks move the field.  stats (may be null) takes the numbers of the
+  // call; should the paths outgrow the buffers, the call is made again with larger ones and stats holds both together.
+  struct CostFieldPlan {
+    int status = 2;
+    std::vector<std::array<int, 3>> nodes;
+    std::vector<std::array<double, 7>> states;
+    double cost = std::numeric_limits<double>::infinity();
+  };
+  std::vector<CostFieldPlan> planOnCostField(artp_field* kept, const std::vector<std::array<int, 3>>& targets,
+                                             int max_rounds = 64, artp_field_plan_stats_t* stats = nullptr) {
+    std::lock_guard<std::mutex> lock(map_mutex_);
+    if (!map_) throw std::runtime_error("planOnCostField: the planner does not have a map set");
+    if (!kept) throw std::runtime_error("planOnCostField: no field");
+    const auto g = map_->getGeometry();
+    const size_t cells = static_cast<size_t>(g.rows) * g.cols;
+    artp_field_stats_t st;
+    throwOnError(gpu_->get(), artp_field_stats(kept, &st), "artp_field_stats");
+    if (st.nodes % cells != 0) throw std::runtime_error("planOnCostField: the field does not have rows * cols cells");
+    const size_t n = targets.size();
+    std::vector<CostFieldPlan> out(n);
+    artp_field_plan_stats_t sum{};
+    if (stats) *stats = sum;
+    if (!n) return out;
+    std::vector<int> t;
+    for (const auto& s : targets) t.insert(t.end(), s.begin(), s.end());
+    std::vector<int32_t> status(n);
+    std::vector<double> cost(n);
+    std::vector<uint64_t> off(n + 1, 0);
+    size_t cap = 1024 * n;
+    std::vector<int> nodes;
+    std::vector<double> se3;
+    int rounds_left = max_rounds;
+    for (;;) {   // a second pass only when the paths hold more states than cap: the blocks of the first stay
+      nodes.resize(3 * cap);
+      se3.resize(7 * cap);
+      const int rc = artp_field_plan(kept, t.data(), n, std::max(rounds_left, 1), status.data(), cost.data(), off.data(),
+                                     nodes.data(), se3.data(), cap);
+      artp_field_plan_stats_t one{};
+      if ((rc == ARTP_OK || rc == ARTP_ERR_CAPACITY) && artp_field_plan_stats(kept, &one) == ARTP_OK) {
+        sum.rounds += one.rounds;
+        sum.moves_checked += one.moves_checked;
+        sum.moves_blocked += one.moves_blocked;
+        sum.updates += one.updates;
+        sum.update_tile_runs += one.update_tile_runs;
+        if (one.updates) sum.last_update_tile_runs = one.last_update_tile_runs;
+        sum.descent_ms += one.descent_ms;
+        sum.check_ms += one.check_ms;
+        sum.round_ms += one.round_ms;
+        sum.passes_ms += one.passes_ms;
+      }
+      if (rc == ARTP_ERR_CAPACITY && off[n] > cap) {
+        cap = static_cast<size_t>(off[n]);
+        rounds_left = max_rounds - static_cast<int>(sum.rounds);
+        continue;
+      }
+      throwOnError(gpu_->get(), rc, "artp_field_plan");
+      break;
+    }
+    for (size_t i = 0; i < n; ++i) {
+      out[i].status = status[i];
+      out[i].cost = cost[i];
+      for (uint64_t s = off[i]; s < off[i + 1]; ++s) {
+        out[i].nodes.push_back({{nodes[3 * s], nodes[3 * s + 1], nodes[3 * s + 2]}});
+        std::array<double, 7> q;
+        for (int j = 0; j < 7; ++j) q[j] = se3[7 * s + j];
+        out[i].states.push_back(q);
+      }
+    }
+    if (stats) *stats = sum;
+    refreshCostToGo(kept, cells, st.nodes);
+    return out;
   }
 
   void setSeed(uint64_t seed) {

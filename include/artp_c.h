@@ -233,7 +233,8 @@ int artp_reachability_halo(artp_ctx* ctx, int* cells);
  * outwards, in both forms.  +inf where the node does not exist or cannot be reached.  The least fixed point of
  * dist[v] = min(dist[u] + w) is unique (fl(+) is monotone, w >= 0), so both kernel forms give the same bits.
  * An edge is usable when both end poses are valid: the interior states of a move are NOT checked.  A lattice path is a
- * proposal; artp_field_path hands its states out as SE3 so that the caller can run them through artp_check_motions.
+ * proposal; artp_field_path hands its states out as SE3 so that the caller can run them through artp_check_motions, and
+ * artp_field_plan (below) does so on the device and takes the verdicts back into the field.
  * Nodes (sources, target, nodes_out) are int triples (r, c, k), r and c LOCAL to the rectangle. */
 typedef struct artp_field artp_field;
 typedef struct artp_field_params {
@@ -371,6 +372,71 @@ typedef struct artp_field_learned_update_stats_t {
 int artp_field_update_learned(artp_field* f, const uint32_t* new_mask, int mask_on_device, const int sub_rect[4]);
 /* the numbers of the last artp_field_update_learned that returned ARTP_OK (zeros before the first) */
 int artp_field_learned_update_stats(artp_field* f, artp_field_learned_update_stats_t* out);
+
+/* ---- Lazily checked paths on a field: blocked moves, plan, unblock -----------------
+ * A field may carry a BLOCKED-MOVE SET: single moves a -> b that are absent edges (weight +inf) although both ends are
+ * nodes -- what artp_check_motions says about a move whose interior states fail.  One 16-bit word per node, index as dist;
+ * bit j of node v = the edge the field pulls along at v from its neighbour u by offset j (the ten moves' numbering):
+ * forward field (reverse = 0): the edge u -> v; reverse field: the edge v -> u.  Only the stated travel direction is
+ * blocked: forward and reverse fields of objectives 0 and 1, equal until then, stop being equal once something is blocked.
+ * The set is allocated by the first block; a field that never blocked anything behaves and costs as before.
+ * After ARTP_OK from any call of this section dist, hops (artp_field_path), artp_field_edge_costs (+inf for a blocked move)
+ * and reached_nodes are bit for bit those of a new field on the same mask with the same set blocked in one call.
+ * artp_field_update and artp_field_update_learned keep the set: their contract becomes "bit for bit a new field on that
+ * state with the same moves blocked".  At n_yaw = 2 moves 8 and 9 are the same rotation: it sits in bits 8 and 9 of its
+ * word, which are set, cleared, honoured and counted as ONE move.  A failure of a repair after the checks (ARTP_ERR_HIP,
+ * or ARTP_ERR_CAPACITY when a pass exceeds artp_field_compute's cap of nodes + 2 rounds -- not artp_field_plan's
+ * cap_states, see there) leaves the field UNDEFINED: destroy it.  Synchronous, on the context's current stream.
+ *
+ * artp_field_block_moves: a, b = host arrays of n node triples, the moves a_i -> b_i in TRAVEL direction, as
+ * artp_field_edge_costs takes them.  *newly_blocked (may be NULL) = moves that were not blocked before.  ARTP_ERR_INVALID_ARG with
+ * nothing written: a pair that is not one of the ten moves or has an end outside the rectangle.  Blocking a move whose
+ * edge does not exist in the mask sets the bit and changes nothing else. */
+int artp_field_block_moves(artp_field* f, const int* a, const int* b, size_t n, uint64_t* newly_blocked);
+/* Clears every bit of the nodes whose cell lies in sub_rect ({row0, col0, nrows, ncols} local to the field's rectangle,
+ * NULL = all); *unblocked (may be NULL) = moves unblocked.  This is what a caller runs after a map change: a move's verdict
+ * depends on the cells its interior states touch, so a sufficient rectangle is the written one grown by
+ * artp_reachability_halo() plus one cell.  ARTP_ERR_INVALID_ARG for an empty rectangle or one not inside the field's. */
+int artp_field_unblock(artp_field* f, const int sub_rect[4], uint64_t* unblocked);
+/* *n = moves blocked; words_out: nrows * ncols * n_yaw words on the host (zeros when nothing was ever blocked) */
+int artp_field_blocked_count(artp_field* f, uint64_t* n);
+int artp_field_blocked(artp_field* f, uint16_t* words_out);
+/* The lazy loop (LazyPRM*'s): for n_targets node triples, paths whose every move passed checkMotion's first overload.
+ * Per round, for the targets still pending: the path artp_field_path returns at that moment; all moves of all paths
+ * through the batched motion check on the device; the moves that failed blocked; a target whose path held no failing move
+ * is finished with that path (later blocks only raise distances and its path stays tight: its cost is the final
+ * dist[target]); a target without a path is finished as unreachable; when a bit was newly set the field is repaired once
+ * and the others go round again, at most max_rounds (>= 1) rounds a call.
+ * statuses[i]: 0 = a checked path, 1 = unreachable (also: not a node of the mask), 2 = rounds exhausted; costs[i] = +inf
+ * unless status 0.  path_offsets (n_targets + 1 entries), nodes_out (3 ints a state) and se3_out (7 doubles a state; the
+ * states of target i at [path_offsets[i], path_offsets[i + 1]) in travel order as artp_field_path gives them) may be NULL.
+ * ARTP_ERR_CAPACITY when cap_states < path_offsets[n_targets]: the output buffers are too small, nothing else.  Statuses,
+ * costs and offsets are filled, the field is at its fixed point and artp_field_plan_stats describes the call.
+ * The blocks stay on the field after the call, status 2 and that ARTP_ERR_CAPACITY included: a second call continues
+ * where the first stopped (after too small a cap_states it finds every path checked and ends in one round).  Refused with nothing changed: what artp_field_path refuses, a changed map (ARTP_ERR_INVALID_ARG: the
+ * poses are gone), ARTP_ERR_NO_MAP without both validity layers and artp_set_z_bounds.  The host reads the round's totals
+ * once after the descents and the verdicts once after the check, besides the reads of the motion check itself. */
+typedef struct artp_field_plan_stats_t {
+  uint64_t rounds;                /* descents + checks that ran */
+  uint64_t moves_checked;         /* moves sent through checkMotion (a move on two paths counts twice) */
+  uint64_t moves_blocked;         /* moves newly blocked */
+  uint64_t updates;               /* rounds that repaired the field */
+  uint64_t update_tile_runs;      /* tiled form: tiles that ran in those repairs, summed; per round:
+                                     artp_field_plan_round_tile_runs */
+  uint64_t last_update_tile_runs; /* ... of the last repair alone */
+  double descent_ms;              /* stream time of the rounds' descents (field_paths_kernel), summed */
+  double check_ms;                /* stream time from there to the end of the block kernel: poses, checkMotion, blocks */
+  double round_ms;                /* host time of the same part of the rounds */
+  double passes_ms;               /* host time of the repairs (every round of a pass is read by the host) */
+} artp_field_plan_stats_t;
+int artp_field_plan(artp_field* f, const int* targets, size_t n_targets, int max_rounds, int32_t* statuses, double* costs,
+                    uint64_t* path_offsets, int* nodes_out, double* se3_out, size_t cap_states);
+/* the numbers of the last artp_field_plan that ran its rounds, whether it returned ARTP_OK or ARTP_ERR_CAPACITY for
+ * cap_states (zeros before the first) */
+int artp_field_plan_stats(artp_field* f, artp_field_plan_stats_t* out);
+/* Per round of that call: the tiles that ran in the round's repair (0 for a round that blocked nothing, and in the plain
+ * form).  *n_rounds = the rounds; runs_out (may be NULL with cap = 0) takes the first cap of them. */
+int artp_field_plan_round_tile_runs(artp_field* f, uint64_t* runs_out, size_t cap, size_t* n_rounds);
 
 /* ---- ob::MotionValidator::checkMotion (OMPL DiscreteMotionValidator; call sites
  *      prm_motion_cost.cpp:652, lazy_prm_star_min_update.cpp:725), batched -----------------------
