@@ -11,7 +11,7 @@
 //
 //   classify_states_kernel      1 lane / (state, box): poses, frame change, AABB, window, table statistics,
 //                               exits (b)-(e), 2 x 2 vertex probe of (f) for feet; undecided -> queue 1
-//   feet_stream_kernel          16 lanes / foot box  : (f) streamed off the map, list-free corner stage
+//   feet_stream_kernel          16 lanes / foot box  : list-free corner stage, then (f) streamed off the map
 //   resolve_boxes_kernel<.,64,0>  1 wave / torso box : the same for the ~900-sample torso windows
 //   resolve_boxes_kernel<.,16,2> 16 lanes / box      : candidates with possible partners: LDS tile,
 //                               kept-triangle list, partner search (queue 5)
@@ -1043,14 +1043,24 @@ feet_lane_kernel(FieldDev ff, RobotDev rb, PipelineQueues q, uint8_t* __restrict
 
 // ---- stage 1c: the foot queue, one 16-lane row per box, straight off the map ---------------------------
 // For the records whose exits (b)-(e) the tables already ruled out (all of them unless the window holds a
-// NaN or is thinner than the smallest table block): (f) streamed from the map, then the list-free corner
-// stage.  Decides everything except boxes whose corner candidates may have partners (-> queue 5, list
-// pass).  Records without table verdict go to queue 4 (sequential lane scan with the running-dMAX quirk).
-// 6 wavefronts per SIMD (80 VGPRs, nothing spilled): -2 % against 5; 7 lose it again.  (With LLVM's SLP pass on,
-// the kernel needed 96 VGPRs + 14 spills for 5 wavefronts and 6 were out of reach.)
+// NaN or is thinner than the smallest table block): the list-free corner stage, then (f) streamed from the map.
+// The label is "(f) fires OR the plane stage yields a contact": two independent existence tests, so the order is
+// free, and two boxes in three that get here end with a corner contact and never stream.  A wavefront runs the
+// corner stage over its whole chunk, collects the boxes still open by ballot and streams only those, four per round
+// (their records are read again: they are in L2) -- without that its four groups wait for the one that streams.
+// Decides everything except boxes whose corner candidates may have partners: they get their stream too and go to
+// queue 5 (list pass) when it finds nothing.  Records without table verdict are queue 4's (sequential lane scan
+// with the running-dMAX quirk).
+// 6 wavefronts per SIMD (80 VGPRs, nothing spilled to scratch): 5 are 2 % slower.  (With LLVM's SLP pass on, the
+// kernel needed 96 VGPRs + 14 spills for 5 wavefronts and 6 were out of reach.)
 #ifdef ARTP_STAGE_TIMING
-__device__ unsigned long long g_feet_cycles[4];  // stream cycles, corner cycles, boxes that reached the corners
+// stream cycles, corner cycles, boxes that ran the second stage, boxes taken, corner results 1 and 2, stream hits
+__device__ unsigned long long g_feet_cycles[8];
 #endif
+// one bit per 16-lane group out of a wavefront ballot of a group-uniform predicate (lanes 0, 16, 32, 48)
+__device__ __forceinline__ unsigned grp_bits4(unsigned long long bal) {
+  return (unsigned)((bal & 1ull) | ((bal >> 15) & 2ull) | ((bal >> 30) & 4ull) | ((bal >> 45) & 8ull));
+}
 #ifndef ARTP_FEET_WAVES_PER_SIMD
 #define ARTP_FEET_WAVES_PER_SIMD 6
 #endif
@@ -1063,46 +1073,74 @@ feet_stream_kernel(FieldDev ff, RobotDev rb, PipelineQueues q, uint8_t* __restri
   const int sq = blockIdx.x % ARTP_NSUB;  // this workgroup's foot sub-queue
   const unsigned long long count = *sub_counter(q, 1, sq);
   const unsigned long long first = sub_base(q, 1, sq);
-  // every wavefront takes ARTP_FEET_CHUNK boxes at a time from the sub-queue's cursor (4 rounds of its 4 groups)
+  // every wavefront takes ARTP_FEET_CHUNK boxes at a time from the sub-queue's cursor
+  static_assert(ARTP_FEET_CHUNK % GPW == 0 && ARTP_FEET_CHUNK <= 32, "one bit per box of the chunk in a 32-bit mask");
   unsigned long long* cursor = sub_cursor(q, 1, sq);
   for (;;) {
     unsigned long long chunk = 0;
     if (lane == 0) chunk = atomicAdd(cursor, (unsigned long long)ARTP_FEET_CHUNK);
-    chunk = __shfl(chunk, 0);
+    chunk = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(chunk >> 32)) << 32) |
+            (uint32_t)__builtin_amdgcn_readfirstlane((int)chunk);  // wave-uniform: the cursor stays in scalar registers
     if (chunk >= count) break;
+    // the corner stage over the whole chunk; bit k of `open`: box k still needs its stream, of `partner`: its corner
+    // candidates may have partners (queue 5 unless the stream finds a vertex)
+    unsigned open = 0, partner = 0;
+    const PendingBox* __restrict__ recs = q.q1 + (first + chunk);  // wave-uniform: the chunk's records
+    const unsigned left = (count - chunk < (unsigned long long)ARTP_FEET_CHUNK) ? (unsigned)(count - chunk) : (unsigned)ARTP_FEET_CHUNK;
     for (int r = 0; r < ARTP_FEET_CHUNK / GPW; ++r) {
-      const unsigned long long it = chunk + (unsigned long long)(r * GPW + lane / G);
-      if (it < count) {
-        const unsigned long long item = first + it;
-        const PendingBox rec = q.q1[item];
-        if (valid[rec.state] != 0) {  // else another box of this state already failed
-          if (rec.kind & ARTP_REC_EXITS_NEGATIVE) {  // (records without a table verdict are the lane scan's: classify listed them)
-            BoxHF b;
-            box_from_record(rec, rb, b);
+      const unsigned k = (unsigned)(r * GPW + lane / G);
+      int rr = 1;
+      if (k < left) {
+        const PendingBox rec = recs[k];
+        // (a state another box already failed is skipped; records without a table verdict are the lane scan's: classify listed them)
+        if (valid[rec.state] != 0 && (rec.kind & ARTP_REC_EXITS_NEGATIVE)) {
+          BoxHF b;
+          box_from_record(rec, rb, b);
 #ifdef ARTP_STAGE_TIMING
-            const long long tf0 = clock64();
+          const long long tf0 = clock64();
 #endif
-            const bool touches = grp_vertex_stream<G, ARTP_FEET_U>(ff, b, lane, (rec.kind & ARTP_REC_ALL_FINITE) != 0);  // ~80 samples
+          rr = grp_corner_stage_direct<G>(ff, b, lane);
 #ifdef ARTP_STAGE_TIMING
-            const long long tf1 = clock64();
-            if (gl == 0) atomicAdd(&g_feet_cycles[0], (unsigned long long)(tf1 - tf0));
-#endif
-            if (!touches) {
-              const int rr = grp_corner_stage_direct<G>(ff, b, lane);
-#ifdef ARTP_STAGE_TIMING
-              if (gl == 0) {
-                atomicAdd(&g_feet_cycles[1], (unsigned long long)(clock64() - tf1));
-                atomicAdd(&g_feet_cycles[2], 1ull);
-              }
-#endif
-              if (gl == 0) {
-                if (rr == 2)
-                  q.q5[atomicAdd(&q.counters[6], 1ull)] = (unsigned)item;
-                else if (rr == 0)
-                  valid[rec.state] = 0;  // a foot that touches nothing fails the state
-              }
-            }
+          if (gl == 0) {
+            atomicAdd(&g_feet_cycles[1], (unsigned long long)(clock64() - tf0));
+            atomicAdd(&g_feet_cycles[3], 1ull);
+            if (rr) atomicAdd(&g_feet_cycles[3 + rr], 1ull);
           }
+#endif
+        }
+      }
+      open |= grp_bits4(__ballot(rr != 1)) << (r * GPW);
+      partner |= grp_bits4(__ballot(rr == 2)) << (r * GPW);
+    }
+    // the boxes still open, four per round: the record is read again (it is in L2)
+    while (open) {
+      int mine = -1;
+#pragma unroll
+      for (int g = 0; g < GPW; ++g)
+        if (open) {
+          if (lane / G == g) mine = __builtin_ctz(open);
+          open &= open - 1;
+        }
+      if (mine >= 0) {
+        const PendingBox rec = recs[mine];
+        BoxHF b;
+        box_from_record(rec, rb, b);
+#ifdef ARTP_STAGE_TIMING
+        const long long tf1 = clock64();
+#endif
+        const bool touches = grp_vertex_stream<G, ARTP_FEET_U>(ff, b, lane, (rec.kind & ARTP_REC_ALL_FINITE) != 0);  // ~80 samples
+#ifdef ARTP_STAGE_TIMING
+        if (gl == 0) {
+          atomicAdd(&g_feet_cycles[0], (unsigned long long)(clock64() - tf1));
+          atomicAdd(&g_feet_cycles[2], 1ull);
+          if (touches) atomicAdd(&g_feet_cycles[6], 1ull);
+        }
+#endif
+        if (!touches && gl == 0) {
+          if ((partner >> mine) & 1u)
+            q.q5[atomicAdd(&q.counters[6], 1ull)] = (unsigned)(first + chunk) + (unsigned)mine;
+          else
+            valid[rec.state] = 0;  // a foot that touches nothing fails the state
         }
       }
     }

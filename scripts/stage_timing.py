@@ -30,7 +30,14 @@ cnt = ctx.pipeline_counters()
 print("counters", cnt)
 ff = (C.c_ulonglong * 20)()
 L.artp_debug_stage_cycles(ff, 3)  # reset >= 3: the feet_stream counters
-print("feet_stream: stream ticks", ff[0], "corner ticks", ff[1], "boxes reaching the corner stage", ff[2])
+print("feet_stream: stream ticks", ff[0], "corner ticks", ff[1], "boxes that ran the second stage", ff[2], "boxes taken", ff[3],
+      "corner result 1 (contact)", ff[4], "2 (may have partners)", ff[5], "streams that found a vertex", ff[6])
+# the corner stage runs first: the boxes that ran the second stage are the streamed ones (all boxes run the corner stage)
+n_stream, n_corner = ff[2], ff[3]
+print("  per box: stream (S) %.0f ticks, corner stage (C) %.0f ticks, C / S %.2f; streamed %.3f of the boxes taken, contact %.3f, "
+      "partners %.3f, vertex %.3f of the streamed"
+      % (ff[0] / max(n_stream, 1), ff[1] / max(n_corner, 1), (ff[1] / max(n_corner, 1)) / max(ff[0] / max(n_stream, 1), 1e-9),
+         n_stream / max(ff[3], 1), ff[4] / max(ff[3], 1), ff[5] / max(ff[3], 1), ff[6] / max(n_stream, 1)))
 ctx.sample_and_validate_dev(1234, n, n, se3, va)
 torch.cuda.synchronize()
 cc = (C.c_ulonglong * 20)()
