@@ -16,6 +16,7 @@
 #include <array>
 #include <vector>
 
+#include "device_scratch.h"
 #include "pipeline.h"
 #include "cost_kernels.h"
 
@@ -186,15 +187,6 @@ struct artp_ctx {
 };
 
 namespace {
-
-#define HIP_TRY(ctx, expr)                                                        \
-  do {                                                                            \
-    hipError_t _e = (expr);                                                       \
-    if (_e != hipSuccess) {                                                       \
-      (ctx)->last_error = std::string(#expr) + ": " + hipGetErrorString(_e);      \
-      return ARTP_ERR_HIP;                                                        \
-    }                                                                             \
-  } while (0)
 
 int ensure_tmp(artp_ctx* c, int slot, size_t bytes) {
   if (c->tmp_cap[slot] >= bytes) return ARTP_OK;

@@ -1,0 +1,75 @@
+// device_scratch.h -- who frees temporary device memory, and the one pair of error macros of the host code.
+// Includes the HIP runtime and standard headers only, so it compiles alone on the CPU (tests/cpp/device_scratch_test.cpp).
+// The macros expand ARTP_OK / ARTP_ERR_HIP (include/artp_c.h) where they are used.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstddef>
+#include <string>
+#include <vector>
+
+// a failed HIP call: its text and HIP's message go to ctx->last_error, the function returns ARTP_ERR_HIP
+#define HIP_TRY(ctx, expr)                                                        \
+  do {                                                                            \
+    hipError_t _e = (expr);                                                       \
+    if (_e != hipSuccess) {                                                       \
+      (ctx)->last_error = std::string(#expr) + ": " + hipGetErrorString(_e);      \
+      return ARTP_ERR_HIP;                                                        \
+    }                                                                             \
+  } while (0)
+// a failed call of our own (it has set last_error): the function returns its code
+#define ARTP_TRY(expr)                \
+  do {                                \
+    const int _rc = (expr);           \
+    if (_rc != ARTP_OK) return _rc;   \
+  } while (0)
+
+// Owner of device allocations: what it still holds when it goes out of scope is freed, on every way out.  Declared at
+// the top of the scope that owns the buffers (a function's temporaries) or as a member (an object's buffers).  Plain
+// hipMalloc / hipFree: a hipFree waits for the device, so where and how often memory is freed is part of a step's time.
+class DeviceScratch {
+ public:
+  DeviceScratch() = default;
+  DeviceScratch(const DeviceScratch&) = delete;
+  DeviceScratch& operator=(const DeviceScratch&) = delete;
+  ~DeviceScratch() {
+    for (void* p : ptrs_) (void)hipFree(p);
+  }
+  // count elements of T (at least one: the pointer is never null on success); *out = nullptr on failure
+  template <class T>
+  hipError_t alloc(T** out, size_t count) {
+    void* p = nullptr;
+    const hipError_t e = hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T));
+    if (e == hipSuccess) ptrs_.push_back(p);
+    *out = static_cast<T*>(p);
+    return e;
+  }
+  hipError_t alloc(void** out, size_t bytes) { return alloc(reinterpret_cast<char**>(out), bytes); }
+  // frees p now (early, to keep peak memory down, or ahead of a regrow); a pointer not held here, or null, is left alone
+  void release(void* p) {
+    if (forget(p)) (void)hipFree(p);
+  }
+  // hands p over to the caller: it is no longer freed here
+  template <class T>
+  T* take(T* p) {
+    forget(p);
+    return p;
+  }
+  // the other half of a hand-over between two owners: a buffer taken from another owner is freed here from now on
+  template <class T>
+  T* adopt(T* p) {
+    if (p) ptrs_.push_back(p);
+    return p;
+  }
+
+ private:
+  bool forget(void* p) {
+    const auto it = std::find(ptrs_.begin(), ptrs_.end(), p);
+    if (p == nullptr || it == ptrs_.end()) return false;
+    ptrs_.erase(it);
+    return true;
+  }
+  std::vector<void*> ptrs_;
+};

@@ -579,6 +579,7 @@ bool pre_sampling_distribution(artp_ctx* c, artp_preprocessed* pp, const artp_pr
   auto L = [&](int k) { return pp->layer(k); };
   const artp::PreGeom geom{rows, cols, (float)res, pp->pos_x, pp->pos_y, pp->len_x, pp->len_y};
   float* d_taps = nullptr;
+  DeviceScratch S;
   unsigned* max_bits = reinterpret_cast<unsigned*>(pp->scalars() + 1);
   double* mass = reinterpret_cast<double*>(pp->scalars() + 2);  // 8-byte aligned (even offset, see scalars())
   bool ok = hipMemsetAsync(pp->scalars(), 0, 8 * sizeof(float), st) == hipSuccess;
@@ -597,7 +598,7 @@ bool pre_sampling_distribution(artp_ctx* c, artp_preprocessed* pp, const artp_pr
       sum += taps[i];
     }
     for (int i = 0; i < k; ++i) taps[i] = (float)(taps[i] * (1.0 / sum));
-    ok = ok && hipMalloc(reinterpret_cast<void**>(&d_taps), k * sizeof(float)) == hipSuccess &&
+    ok = ok && S.alloc(&d_taps, (size_t)k) == hipSuccess &&
          hipMemcpyAsync(d_taps, taps.data(), k * sizeof(float), hipMemcpyHostToDevice, st) == hipSuccess &&
          hipMemsetAsync(L(PRE_T0), 0, (size_t)n * 4, st) == hipSuccess;
     if (ok) {
@@ -635,10 +636,7 @@ bool pre_sampling_distribution(artp_ctx* c, artp_preprocessed* pp, const artp_pr
   hipLaunchKernelGGL(artp::cdf_rowwise_kernel, dim3(1), dim3(256), 0, st, (const float*)row_sum, rows, pp->rowwise(),
                      total);
   ok = ok && hipGetLastError() == hipSuccess;
-  if (d_taps) {
-    ok = hipStreamSynchronize(st) == hipSuccess && ok;  // the taps are read by the kernels above
-    (void)hipFree(d_taps);
-  }
+  if (d_taps) ok = hipStreamSynchronize(st) == hipSuccess && ok;  // the taps are read by the kernels above
   return ok;
 }
 }  // namespace
@@ -763,7 +761,8 @@ int artp_preprocess_map_ex(artp_ctx* c, const artp_preprocess_inputs* in, const 
     fp_host.insert(fp_host.end(), spans.begin(), spans.end());
   }
   int* d_fp = nullptr;
-  ok = ok && hipMalloc(reinterpret_cast<void**>(&d_fp), fp_host.size() * sizeof(int)) == hipSuccess &&
+  DeviceScratch S;
+  ok = ok && S.alloc(&d_fp, fp_host.size()) == hipSuccess &&
        hipMemcpyAsync(d_fp, fp_host.data(), fp_host.size() * sizeof(int), hipMemcpyHostToDevice, st) == hipSuccess &&
        hipStreamSynchronize(st) == hipSuccess;  // fp_host dies with this call
   auto footprint = [&](int size, int* fsize) -> const int* {
@@ -808,13 +807,11 @@ int artp_preprocess_map_ex(artp_ctx* c, const artp_preprocess_inputs* in, const 
   // the sampling distribution (planner.cpp:43-56): [inverse vertex density] * sample filter [capped unknown share]
   double* d_verts = nullptr;
   if (prm->use_inverse_vertex_density && in->n_vertices > 0)
-    ok = ok && hipMalloc(reinterpret_cast<void**>(&d_verts), in->n_vertices * 7 * sizeof(double)) == hipSuccess &&
+    ok = ok && S.alloc(&d_verts, (size_t)in->n_vertices * 7) == hipSuccess &&
          hipMemcpyAsync(d_verts, in->vertex_se3, in->n_vertices * 7 * sizeof(double), hipMemcpyHostToDevice, st) ==
              hipSuccess;
   ok = ok && pre_sampling_distribution(c, pp, prm, d_verts, d_verts ? in->n_vertices : 0);
   ok = ok && hipGetLastError() == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
-  if (d_verts) (void)hipFree(d_verts);
-  if (d_fp) (void)hipFree(d_fp);
   if (!ok) {
     c->last_error = "device preprocessing failed";
     lock.unlock();
@@ -958,16 +955,13 @@ static int inpaint_dev(artp_ctx* c, const float* d_in, int rows, int cols, int m
   HIP_TRY(c, hipSetDevice(c->device));
   hipStream_t st = c->stream;
   unsigned char* buf = nullptr;
-  HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&buf), 4 * n + 64));
+  DeviceScratch S;
+  HIP_TRY(c, S.alloc(&buf, 4 * n + 64));
   unsigned char *q = buf, *known = buf + n, *q2 = buf + 2 * n, *known2 = buf + 3 * n;
   unsigned long long* d_holes = reinterpret_cast<unsigned long long*>(c->d_count);
   unsigned* d_left = reinterpret_cast<unsigned*>(buf + 4 * n + (8 - (4 * n) % 8) % 8);
   const dim3 grid((unsigned)((n + 255) / 256)), blk(256);
-  auto fail = [&](int code) {
-    (void)hipFree(buf);
-    return code;
-  };
-  if (hipMemsetAsync(d_holes, 0, 8, st) != hipSuccess) return fail(ARTP_ERR_HIP);
+  if (hipMemsetAsync(d_holes, 0, 8, st) != hipSuccess) return ARTP_ERR_HIP;
   if (!any || !(hi > lo)) {
     mode &= 1;
     // no valid cell at all, or a constant layer (the reference divides by max - min = 0 here): holes take the
@@ -975,14 +969,14 @@ static int inpaint_dev(artp_ctx* c, const float* d_in, int rows, int cols, int m
     hipLaunchKernelGGL(artp::inpaint_quantise_kernel, grid, blk, 0, st, d_in, (int)n, mode, 0.0f, 1.0f, q, known, d_holes);
     unsigned long long h = 0;
     if (hipMemcpyAsync(&h, d_holes, 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-      return fail(ARTP_ERR_HIP);
+      return ARTP_ERR_HIP;
     if (n_holes) *n_holes = h;
     std::vector<float> tmp(n);
-    if (hipMemcpy(tmp.data(), d_in, n * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(ARTP_ERR_HIP);
+    if (hipMemcpy(tmp.data(), d_in, n * 4, hipMemcpyDeviceToHost) != hipSuccess) return ARTP_ERR_HIP;
     for (float& v : tmp)
       if (!std::isfinite(v)) v = any ? lo : 0.0f;
-    if (hipMemcpy(d_out, tmp.data(), n * 4, hipMemcpyHostToDevice) != hipSuccess) return fail(ARTP_ERR_HIP);
-    return fail(ARTP_OK);
+    if (hipMemcpy(d_out, tmp.data(), n * 4, hipMemcpyHostToDevice) != hipSuccess) return ARTP_ERR_HIP;
+    return ARTP_OK;
   }
   // Telea's march reads a 3 x 3 neighbourhood around every band pixel with cv::inpaint's border index rule: it needs at
   // least two rows and two columns.  A one-row / one-column layer takes the device fill instead.
@@ -991,13 +985,13 @@ static int inpaint_dev(artp_ctx* c, const float* d_in, int rows, int cols, int m
   hipLaunchKernelGGL(artp::inpaint_quantise_kernel, grid, blk, 0, st, d_in, (int)n, mode, lo, hi, q, known, d_holes);
   unsigned long long h = 0;
   if (hipMemcpyAsync(&h, d_holes, 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-    return fail(ARTP_ERR_HIP);
+    return ARTP_ERR_HIP;
   if (n_holes) *n_holes = h;
   if (h == 0) {
     if (d_out != d_in && hipMemcpyAsync(d_out, d_in, n * 4, hipMemcpyDeviceToDevice, st) != hipSuccess)
-      return fail(ARTP_ERR_HIP);
-    if (hipStreamSynchronize(st) != hipSuccess) return fail(ARTP_ERR_HIP);
-    return fail(ARTP_OK);
+      return ARTP_ERR_HIP;
+    if (hipStreamSynchronize(st) != hipSuccess) return ARTP_ERR_HIP;
+    return ARTP_OK;
   }
   if (telea) {
     // Telea's fast-marching fill (telea.h) on the host, on the image as the reference hands it to cv::inpaint: the planner
@@ -1006,7 +1000,7 @@ static int inpaint_dev(artp_ctx* c, const float* d_in, int rows, int cols, int m
     std::vector<unsigned char> hq(n), hk(n), img(n), msk(n);
     if (hipMemcpyAsync(hq.data(), q, n, hipMemcpyDeviceToHost, st) != hipSuccess ||
         hipMemcpyAsync(hk.data(), known, n, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-      return fail(ARTP_ERR_HIP);
+      return ARTP_ERR_HIP;
     auto src_of = [&](size_t i) {   // image index -> layer index
       if (mode == 0) return i;
       const size_t r = i / (size_t)cols, cc = i % (size_t)cols;
@@ -1020,10 +1014,10 @@ static int inpaint_dev(artp_ctx* c, const float* d_in, int rows, int cols, int m
     else artp_telea::inpaint_u8(rows, cols, img.data(), msk.data(), 3);
     for (size_t i = 0; i < n; ++i) hq[src_of(i)] = img[i];
     if (hipMemcpyAsync(q, hq.data(), n, hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-      return fail(ARTP_ERR_HIP);
+      return ARTP_ERR_HIP;
   }
   for (int group = 0; !telea && group < (rows + cols) / 3 + 2; ++group) {
-    if (hipMemsetAsync(d_left, 0, 4, st) != hipSuccess) return fail(ARTP_ERR_HIP);
+    if (hipMemsetAsync(d_left, 0, 4, st) != hipSuccess) return ARTP_ERR_HIP;
     for (int p = 0; p < 4; ++p) {  // an even number of passes: the result is back in (q, known)
       hipLaunchKernelGGL(artp::inpaint_fill_pass_kernel, grid, blk, 0, st, (const unsigned char*)q,
                          (const unsigned char*)known, rows, cols, q2, known2, d_left);
@@ -1032,13 +1026,13 @@ static int inpaint_dev(artp_ctx* c, const float* d_in, int rows, int cols, int m
     }
     unsigned left = 0;
     if (hipMemcpyAsync(&left, d_left, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-      return fail(ARTP_ERR_HIP);
+      return ARTP_ERR_HIP;
     if (!left) break;
   }
   hipLaunchKernelGGL(artp::inpaint_dequantise_kernel, grid, blk, 0, st, (const unsigned char*)q, rows, cols, mode, lo, hi,
                      d_out);
-  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return fail(ARTP_ERR_HIP);
-  return fail(ARTP_OK);
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return ARTP_ERR_HIP;
+  return ARTP_OK;
 }
 
 int artp_inpaint_layer(artp_ctx* c, const float* layer, int rows, int cols, int mode, float* out, uint64_t* n_holes) {
@@ -1047,11 +1041,11 @@ int artp_inpaint_layer(artp_ctx* c, const float* layer, int rows, int cols, int 
   HIP_TRY(c, hipSetDevice(c->device));
   const size_t n = (size_t)rows * cols;
   float* d = nullptr;
-  HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&d), n * sizeof(float)));
+  DeviceScratch S;
+  HIP_TRY(c, S.alloc(&d, n));
   int rc = hipMemcpy(d, layer, n * 4, hipMemcpyHostToDevice) == hipSuccess ? ARTP_OK : ARTP_ERR_HIP;
   if (rc == ARTP_OK) rc = inpaint_dev(c, d, rows, cols, mode, d, n_holes);
   if (rc == ARTP_OK && hipMemcpy(out, d, n * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = ARTP_ERR_HIP;
-  (void)hipFree(d);
   return rc;
 }
 

@@ -25,6 +25,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <memory>
 #include <queue>
 #include <system_error>
 #include <thread>
@@ -673,24 +674,6 @@ bool roadmap_sssp_dev(artp_roadmap* rm, std::vector<uint32_t>* path, double* cos
   return true;
 }
 
-#define RM_TRY(expr)          \
-  do {                        \
-    const int rc_ = (expr);   \
-    if (rc_ != ARTP_OK) {     \
-      cleanup();              \
-      return rc_;             \
-    }                         \
-  } while (0)
-#define RM_HIP(expr)                                                                   \
-  do {                                                                                 \
-    const hipError_t e_ = (expr);                                                      \
-    if (e_ != hipSuccess) {                                                            \
-      c->last_error = std::string(#expr) + ": " + hipGetErrorString(e_);               \
-      cleanup();                                                                       \
-      return ARTP_ERR_HIP;                                                             \
-    }                                                                                  \
-  } while (0)
-
 // Verdict (0.5 m interpolation rule), interior-state count and chain cost of ne edges whose endpoint states
 // are on the device; results to the host arrays.
 // direct: no interpolation rule -- every edge is one sub-edge of unknown validity (reported valid), the way the
@@ -708,19 +691,15 @@ int roadmap_eval_edges_dev(artp_ctx* c, const artp_roadmap_params* prm, const do
   uint32_t *d_einterp = nullptr, *d_rows = nullptr, *d_off = nullptr, *d_ncost = nullptr;
   float *d_em = nullptr, *d_c3 = nullptr;
   void* d_cub2 = nullptr;
-  auto cleanup = [&]() {
-    for (void* p : {(void*)d_cost, (void*)d_evalid, (void*)d_einterp, (void*)d_rows, (void*)d_off, (void*)d_em,
-                    (void*)d_c3, d_cub2, (void*)d_ncost})
-      if (p) (void)hipFree(p);
-  };
-  RM_HIP(hipMalloc(reinterpret_cast<void**>(&d_cost), ne * sizeof(double)));
-  RM_HIP(hipMalloc(reinterpret_cast<void**>(&d_evalid), ne));
-  RM_HIP(hipMalloc(reinterpret_cast<void**>(&d_einterp), ne * sizeof(uint32_t)));
+  DeviceScratch S;
+  HIP_TRY(c, S.alloc(&d_cost, ne));
+  HIP_TRY(c, S.alloc(&d_evalid, ne));
+  HIP_TRY(c, S.alloc(&d_einterp, ne));
   if (direct) {
-    RM_HIP(hipMemsetAsync(d_evalid, 1, ne, st));
-    RM_HIP(hipMemsetAsync(d_einterp, 0, ne * sizeof(uint32_t), st));
+    HIP_TRY(c, hipMemsetAsync(d_evalid, 1, ne, st));
+    HIP_TRY(c, hipMemsetAsync(d_einterp, 0, ne * sizeof(uint32_t), st));
   } else {
-    RM_TRY(artp_check_edges_interp_dev(c, d_s1, d_s2, ne, d_evalid, d_einterp));
+    ARTP_TRY(artp_check_edges_interp_dev(c, d_s1, d_s2, ne, d_evalid, d_einterp));
   }
   if (prm->objective <= 1) {
     artp::PathLengthParams pl{prm->objective == 1, prm->max_lon_vel, prm->max_lat_vel, prm->max_ang_vel};
@@ -730,38 +709,37 @@ int roadmap_eval_edges_dev(artp_ctx* c, const artp_roadmap_params* prm, const do
     // learned cost: one EdgeMatrix row per sub-edge, one batched query, per-chain reduction
     const uint32_t* d_chain = d_einterp;  // sub-edges of the validity chain (what the reference's graph holds) ...
     if (segment_cost_step > 0.0) {        // ... or motionCost's own split of a path segment
-      RM_HIP(hipMalloc(reinterpret_cast<void**>(&d_ncost), ne * sizeof(uint32_t)));
+      HIP_TRY(c, S.alloc(&d_ncost, ne));
       hipLaunchKernelGGL(artp::motion_cost_interp_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st, d_s1, d_s2, ne,
                          segment_cost_step, d_ncost);
       d_chain = d_ncost;
     }
-    RM_HIP(hipMalloc(reinterpret_cast<void**>(&d_rows), (ne + 1) * 4));
-    RM_HIP(hipMalloc(reinterpret_cast<void**>(&d_off), (ne + 1) * 4));
+    HIP_TRY(c, S.alloc(&d_rows, ne + 1));
+    HIP_TRY(c, S.alloc(&d_off, ne + 1));
     size_t need = 0;
     uint32_t total = 0;
     hipLaunchKernelGGL(artp::chain_rows_kernel, dim3((unsigned)((ne + 256) / 256)), dim3(256), 0, st, d_chain, ne, d_rows);
-    RM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, need, d_rows, d_off, (int)(ne + 1), st));
-    RM_HIP(hipMalloc(&d_cub2, need + 256));
+    HIP_TRY(c, hipcub::DeviceScan::ExclusiveSum(nullptr, need, d_rows, d_off, (int)(ne + 1), st));
+    HIP_TRY(c, S.alloc(&d_cub2, need + 256));
     size_t cap2 = need + 256;
-    RM_HIP(hipcub::DeviceScan::ExclusiveSum(d_cub2, cap2, d_rows, d_off, (int)(ne + 1), st));
-    RM_HIP(hipMemcpyAsync(&total, d_off + ne, 4, hipMemcpyDeviceToHost, st));
-    RM_HIP(hipStreamSynchronize(st));
-    RM_HIP(hipMalloc(reinterpret_cast<void**>(&d_em), (size_t)total * 6 * 4));
-    RM_HIP(hipMalloc(reinterpret_cast<void**>(&d_c3), (size_t)total * 3 * 4));
+    HIP_TRY(c, hipcub::DeviceScan::ExclusiveSum(d_cub2, cap2, d_rows, d_off, (int)(ne + 1), st));
+    HIP_TRY(c, hipMemcpyAsync(&total, d_off + ne, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    HIP_TRY(c, S.alloc(&d_em, (size_t)total * 6));
+    HIP_TRY(c, S.alloc(&d_c3, (size_t)total * 3));
     hipLaunchKernelGGL(artp::chain_edge_matrix_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st, d_s1, d_s2,
                        d_chain, (const uint32_t*)d_off, ne, d_em);
-    RM_TRY(roadmap_cost_query_dev(c, d_em, total, d_c3));   // the caller's MotionCostFunc when one is installed
+    ARTP_TRY(roadmap_cost_query_dev(c, d_em, total, d_c3));   // the caller's MotionCostFunc when one is installed
     hipLaunchKernelGGL(artp::chain_motion_cost_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st,
                        (const float*)d_c3, (const uint32_t*)d_off, d_chain, ne, prm->w_energy,
                        prm->w_time, prm->w_risk, prm->risk_threshold, d_cost);
   }
-  RM_HIP(hipGetLastError());
-  RM_HIP(hipStreamSynchronize(st));
-  RM_HIP(hipMemcpy(evalid, d_evalid, ne, hipMemcpyDeviceToHost));
-  RM_HIP(hipMemcpy(einterp, d_einterp, ne * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  RM_HIP(hipMemcpy(ecost, d_cost, ne * sizeof(double), hipMemcpyDeviceToHost));
-  RM_TRY(check_error_flag(c));
-  cleanup();
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipStreamSynchronize(st));
+  HIP_TRY(c, hipMemcpy(evalid, d_evalid, ne, hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(einterp, d_einterp, ne * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(ecost, d_cost, ne * sizeof(double), hipMemcpyDeviceToHost));
+  ARTP_TRY(check_error_flag(c));
   return ARTP_OK;
 }
 
@@ -778,14 +756,11 @@ int roadmap_eval_edges_host(artp_ctx* c, const artp_roadmap_params* prm, const s
     std::memcpy(&s[(ne + e) * 7], &verts[(size_t)(fl ? eu[e] : ev[e]) * 7], 7 * sizeof(double));
   }
   double* d_s = nullptr;
-  auto cleanup = [&]() {
-    if (d_s) (void)hipFree(d_s);
-  };
-  RM_HIP(hipSetDevice(c->device));
-  RM_HIP(hipMalloc(reinterpret_cast<void**>(&d_s), s.size() * sizeof(double)));
-  RM_HIP(hipMemcpy(d_s, s.data(), s.size() * sizeof(double), hipMemcpyHostToDevice));
-  RM_TRY(roadmap_eval_edges_dev(c, prm, d_s, d_s + ne * 7, ne, evalid, einterp, ecost, direct, segment_cost_step));
-  cleanup();
+  DeviceScratch S;
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, S.alloc(&d_s, s.size()));
+  HIP_TRY(c, hipMemcpy(d_s, s.data(), s.size() * sizeof(double), hipMemcpyHostToDevice));
+  ARTP_TRY(roadmap_eval_edges_dev(c, prm, d_s, d_s + ne * 7, ne, evalid, einterp, ecost, direct, segment_cost_step));
   return ARTP_OK;
 }
 
@@ -836,13 +811,9 @@ static int roadmap_connect(artp_ctx* c, const artp_roadmap_params* prm, const do
   unsigned long long *d_keys = nullptr, *d_keys_sorted = nullptr, *d_keys_unique = nullptr;
   double *d_s1 = nullptr, *d_s2 = nullptr;
   void* d_cub = nullptr;
-  auto cleanup = [&]() {
-    for (void* p : {(void*)d_cnt, (void*)d_knn, (void*)d_knn_dist, (void*)d_keys, (void*)d_keys_sorted,
-                    (void*)d_keys_unique, (void*)d_s1, d_cub})
-      if (p) (void)hipFree(p);
-  };
+  DeviceScratch S;
   hipStream_t st = c->stream;
-  RM_HIP(hipMalloc(reinterpret_cast<void**>(&d_cnt), sizeof(uint64_t)));
+  HIP_TRY(c, S.alloc(&d_cnt, 1));
   // 2. k nearest neighbours
   int k = (int)prm->k_neighbors;
   if (k <= 0) k = roadmap_kstar((size_t)nv);
@@ -861,17 +832,17 @@ static int roadmap_connect(artp_ctx* c, const artp_roadmap_params* prm, const do
       if (ki > (int)i) ki = (int)i;
       k_of[i] = ki > k ? k : ki;
     }
-    if (hipMalloc(reinterpret_cast<void**>(&d_k_of), nv * sizeof(int)) != hipSuccess ||
+    if (S.alloc(&d_k_of, nv) != hipSuccess ||
         hipMemcpy(d_k_of, k_of.data(), nv * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
-      if (d_k_of) (void)hipFree(d_k_of);
       c->last_error = "k table upload failed";
-      cleanup();
       return ARTP_ERR_HIP;
     }
   }
-  RM_HIP(hipMalloc(reinterpret_cast<void**>(&d_knn), nv * k * sizeof(uint32_t)));
-  RM_HIP(hipMalloc(reinterpret_cast<void**>(&d_knn_dist), nv * k * sizeof(double)));
+  HIP_TRY(c, S.alloc(&d_knn, nv * k));
+  HIP_TRY(c, S.alloc(&d_knn_dist, nv * k));
+  bool okk;
   {
+    DeviceScratch G;  // the grid's buffers: gone before the key buffers are allocated
     // grid over the map: about three vertices per cell
     artp::KnnGrid g;
     {
@@ -890,20 +861,13 @@ static int roadmap_connect(artp_ctx* c, const artp_roadmap_params* prm, const do
     uint32_t *d_cell = nullptr, *d_id = nullptr, *d_cell_s = nullptr, *d_id_s = nullptr, *d_start = nullptr;
     double* d_vs = nullptr;
     void* d_cub1 = nullptr;
-    auto cleanup_knn = [&]() {
-      for (void* p : {(void*)d_cell, (void*)d_id, (void*)d_cell_s, (void*)d_id_s, (void*)d_start, (void*)d_vs, d_cub1})
-        if (p) (void)hipFree(p);
-    };
     size_t need = 0;
-    bool okk = hipMalloc(reinterpret_cast<void**>(&d_cell), nv * 4) == hipSuccess &&
-               hipMalloc(reinterpret_cast<void**>(&d_id), nv * 4) == hipSuccess &&
-               hipMalloc(reinterpret_cast<void**>(&d_cell_s), nv * 4) == hipSuccess &&
-               hipMalloc(reinterpret_cast<void**>(&d_id_s), nv * 4) == hipSuccess &&
-               hipMalloc(reinterpret_cast<void**>(&d_start), ((size_t)ncell + 1) * 4) == hipSuccess &&
-               hipMalloc(reinterpret_cast<void**>(&d_vs), nv * 7 * sizeof(double)) == hipSuccess &&
-               hipcub::DeviceRadixSort::SortPairs(nullptr, need, d_cell, d_cell_s, d_id, d_id_s, (int)nv, 0, 32, st) ==
-                   hipSuccess &&
-               hipMalloc(&d_cub1, need + 256) == hipSuccess;
+    okk = G.alloc(&d_cell, nv) == hipSuccess && G.alloc(&d_id, nv) == hipSuccess &&
+          G.alloc(&d_cell_s, nv) == hipSuccess && G.alloc(&d_id_s, nv) == hipSuccess &&
+          G.alloc(&d_start, (size_t)ncell + 1) == hipSuccess && G.alloc(&d_vs, nv * 7) == hipSuccess &&
+          hipcub::DeviceRadixSort::SortPairs(nullptr, need, d_cell, d_cell_s, d_id, d_id_s, (int)nv, 0, 32, st) ==
+              hipSuccess &&
+          G.alloc(&d_cub1, need + 256) == hipSuccess;
     if (okk) {
       hipLaunchKernelGGL(artp::knn_cell_ids_kernel, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, st,
                          (const double*)d_verts, (int)nv, g, d_cell, d_id);
@@ -925,65 +889,58 @@ static int roadmap_connect(artp_ctx* c, const artp_roadmap_params* prm, const do
         okk = hipGetLastError() == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
       }
     }
-    cleanup_knn();
-    if (d_k_of) (void)hipFree(d_k_of);
-    if (!okk) {
-      c->last_error = "k-NN stage failed";
-      cleanup();
-      return ARTP_ERR_HIP;
-    }
+  }
+  S.release(d_k_of);
+  if (!okk) {
+    c->last_error = "k-NN stage failed";
+    return ARTP_ERR_HIP;
   }
 
   // 3. candidate edges: symmetrised, unique
   const size_t nk = nv * (size_t)k;
-  RM_HIP(hipMalloc(reinterpret_cast<void**>(&d_keys), nk * 8));
-  RM_HIP(hipMalloc(reinterpret_cast<void**>(&d_keys_sorted), nk * 8));
-  RM_HIP(hipMalloc(reinterpret_cast<void**>(&d_keys_unique), nk * 8));
+  HIP_TRY(c, S.alloc(&d_keys, nk));
+  HIP_TRY(c, S.alloc(&d_keys_sorted, nk));
+  HIP_TRY(c, S.alloc(&d_keys_unique, nk));
   hipLaunchKernelGGL(artp::knn_edge_keys_kernel, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, st,
                      (const uint32_t*)d_knn, (int)nv, k, d_keys);
-  RM_HIP(hipGetLastError());
+  HIP_TRY(c, hipGetLastError());
   size_t ne = 0;
   {
     size_t need1 = 0, need2 = 0;
-    RM_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, need1, d_keys, d_keys_sorted, (int)nk, 0, 64, st));
-    RM_HIP(hipcub::DeviceSelect::Unique(nullptr, need2, d_keys_sorted, d_keys_unique,
+    HIP_TRY(c, hipcub::DeviceRadixSort::SortKeys(nullptr, need1, d_keys, d_keys_sorted, (int)nk, 0, 64, st));
+    HIP_TRY(c, hipcub::DeviceSelect::Unique(nullptr, need2, d_keys_sorted, d_keys_unique,
                                         reinterpret_cast<unsigned long long*>(d_cnt), (int)nk, st));
     const size_t need = std::max(need1, need2) + 256;
-    RM_HIP(hipMalloc(&d_cub, need));
+    HIP_TRY(c, S.alloc(&d_cub, need));
     size_t cap = need;
-    RM_HIP(hipcub::DeviceRadixSort::SortKeys(d_cub, cap, d_keys, d_keys_sorted, (int)nk, 0, 64, st));
+    HIP_TRY(c, hipcub::DeviceRadixSort::SortKeys(d_cub, cap, d_keys, d_keys_sorted, (int)nk, 0, 64, st));
     cap = need;
-    RM_HIP(hipcub::DeviceSelect::Unique(d_cub, cap, d_keys_sorted, d_keys_unique,
+    HIP_TRY(c, hipcub::DeviceSelect::Unique(d_cub, cap, d_keys_sorted, d_keys_unique,
                                         reinterpret_cast<unsigned long long*>(d_cnt), (int)nk, st));
     uint64_t nu = 0;
-    RM_HIP(hipMemcpyAsync(&nu, d_cnt, sizeof(nu), hipMemcpyDeviceToHost, st));
-    RM_HIP(hipStreamSynchronize(st));
+    HIP_TRY(c, hipMemcpyAsync(&nu, d_cnt, sizeof(nu), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
     ne = (size_t)nu;
     // the all-ones key (missing neighbour slots) sorts last
     unsigned long long last = 0;
     if (ne) {
-      RM_HIP(hipMemcpy(&last, d_keys_unique + (ne - 1), 8, hipMemcpyDeviceToHost));
+      HIP_TRY(c, hipMemcpy(&last, d_keys_unique + (ne - 1), 8, hipMemcpyDeviceToHost));
       if (last == ~0ull) --ne;
     }
   }
 
-  auto rm = new artp_roadmap();
+  std::unique_ptr<artp_roadmap, void (*)(artp_roadmap*)> rm(new artp_roadmap(), artp_roadmap_destroy);
   rm->ctx = c;
   rm->params = *prm;
-  roadmap_fix_params(rm);
+  roadmap_fix_params(rm.get());
   rm->k = k;
   rm->verts.resize(nv * 7);
   rm->knn.resize(nk);
   rm->knn_dist.resize(nk);
-  auto fail = [&](int rc) {
-    delete rm;
-    cleanup();
-    return rc;
-  };
   if (hipMemcpy(rm->verts.data(), d_verts, nv * 7 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
       hipMemcpy(rm->knn.data(), d_knn, nk * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess ||
       hipMemcpy(rm->knn_dist.data(), d_knn_dist, nk * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
-    return fail(ARTP_ERR_HIP);
+    return ARTP_ERR_HIP;
 
   // 4. edge verdicts (0.5 m interpolation rule) and chain costs
   rm->eu.resize(ne);
@@ -993,7 +950,7 @@ static int roadmap_connect(artp_ctx* c, const artp_roadmap_params* prm, const do
   rm->ecost.assign(ne, 0.0);
   rm->eremoved.assign(ne, 0);
   if (ne) {
-    if (hipMalloc(reinterpret_cast<void**>(&d_s1), 2 * ne * 7 * sizeof(double)) != hipSuccess) return fail(ARTP_ERR_HIP);
+    if (S.alloc(&d_s1, 2 * ne * 7) != hipSuccess) return ARTP_ERR_HIP;
     d_s2 = d_s1 + ne * 7;
     hipLaunchKernelGGL(artp::gather_edge_states_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st,
                        (const double*)d_verts, (const unsigned long long*)d_keys_unique, ne, d_s1, d_s2, pred_only ? 1 : 0);
@@ -1001,20 +958,18 @@ static int roadmap_connect(artp_ctx* c, const artp_roadmap_params* prm, const do
     // construction 2: the lazy planner puts DIRECT edges of unknown validity into its graph (no interpolation rule)
     const int rc = roadmap_eval_edges_dev(c, prm, d_s1, d_s2, ne, rm->evalid.data(), rm->einterp.data(),
                                           rm->ecost.data(), pred_only);
-    if (rc != ARTP_OK) return fail(rc);
+    if (rc != ARTP_OK) return rc;
     std::vector<unsigned long long> keys(ne);
-    if (hipMemcpy(keys.data(), d_keys_unique, ne * 8, hipMemcpyDeviceToHost) != hipSuccess) return fail(ARTP_ERR_HIP);
+    if (hipMemcpy(keys.data(), d_keys_unique, ne * 8, hipMemcpyDeviceToHost) != hipSuccess) return ARTP_ERR_HIP;
     for (size_t e = 0; e < ne; ++e) {
       rm->eu[e] = (uint32_t)(keys[e] >> 32);
       rm->ev[e] = (uint32_t)(keys[e] & 0xffffffffu);
     }
-    rm->d_edge_states = d_s1;  // stays resident (freed by artp_roadmap_destroy)
+    rm->d_edge_states = S.take(d_s1);  // stays resident (freed by artp_roadmap_destroy)
     rm->d_edge_cap = ne;
     rm->d_edge_states_stale = false;
-    d_s1 = d_s2 = nullptr;
   }
-  cleanup();
-  *out = rm;
+  *out = rm.release();
   return ARTP_OK;
 }
 
@@ -1035,14 +990,11 @@ static int roadmap_build_impl(artp_ctx* c, const artp_roadmap_params* prm_in, co
   uint8_t* d_valid = nullptr;
   double* d_compact = nullptr;
   uint64_t* d_cnt = nullptr;
-  auto cleanup = [&]() {
-    for (void* p : {(void*)d_verts, (void*)d_batch, (void*)d_valid, (void*)d_compact, (void*)d_cnt})
-      if (p) (void)hipFree(p);
-  };
-  RM_HIP(hipSetDevice(c->device));
+  DeviceScratch S;
+  HIP_TRY(c, hipSetDevice(c->device));
   hipStream_t st = c->stream;
-  RM_HIP(hipMalloc(reinterpret_cast<void**>(&d_verts), nv * 7 * sizeof(double)));
-  RM_HIP(hipMalloc(reinterpret_cast<void**>(&d_cnt), sizeof(uint64_t)));
+  HIP_TRY(c, S.alloc(&d_verts, nv * 7));
+  HIP_TRY(c, S.alloc(&d_cnt, 1));
 
   // start and goal must be valid states (baseSolve: INVALID_START / INVALID_GOAL, prm_motion_cost.cpp:452-476)
   {
@@ -1050,20 +1002,19 @@ static int roadmap_build_impl(artp_ctx* c, const artp_roadmap_params* prm_in, co
     std::memcpy(sg, start7, 7 * sizeof(double));
     std::memcpy(sg + 7, goal7, 7 * sizeof(double));
     uint8_t ok[2] = {0, 0};
-    RM_TRY(artp_validate_states(c, sg, 2, ok, nullptr));
+    ARTP_TRY(artp_validate_states(c, sg, 2, ok, nullptr));
     if (!ok[0] || !ok[1]) {
       c->last_error = !ok[0] ? "start state is not valid" : "goal state is not valid";
-      cleanup();
       return ARTP_ERR_INVALID_ARG;
     }
-    RM_HIP(hipMemcpyAsync(d_verts, sg, sizeof(sg), hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(d_verts, sg, sizeof(sg), hipMemcpyHostToDevice, st));
   }
 
   // 1. milestones: the kept ones, then accepted states of the sample stream, in index order
   size_t have = n_keep;
   uint64_t next = first_new;
   if (n_keep)
-    RM_HIP(hipMemcpyAsync(d_verts + 2 * 7, keep, n_keep * 7 * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(d_verts + 2 * 7, keep, n_keep * 7 * sizeof(double), hipMemcpyHostToDevice, st));
   uint64_t n_reweights = 0, budget_flags = 0;
   size_t nm_final = nm;  // fewer when the sampling-time budget ends the loop
   if (n_new) {
@@ -1078,30 +1029,30 @@ static int roadmap_build_impl(artp_ctx* c, const artp_roadmap_params* prm_in, co
     // with a sampling-time budget the clock is read after every batch (the reference reads it every 100 samples)
     if (prm->max_sample_time > 0.0 && batch > (1u << 16)) batch = 1u << 16;
     uint32_t* d_idx = nullptr;
-    RM_HIP(hipMalloc(reinterpret_cast<void**>(&d_batch), batch * 7 * sizeof(double)));
-    RM_HIP(hipMalloc(reinterpret_cast<void**>(&d_compact), batch * 7 * sizeof(double) + batch * sizeof(uint32_t)));
+    HIP_TRY(c, S.alloc(&d_batch, batch * 7));
+    HIP_TRY(c, S.alloc(&d_compact, batch * 7 + batch / 2));  // the batch's states, then its uint32 indices
     d_idx = reinterpret_cast<uint32_t*>(d_compact + batch * 7);
-    RM_HIP(hipMalloc(reinterpret_cast<void**>(&d_valid), batch));
+    HIP_TRY(c, S.alloc(&d_valid, batch));
     const auto t_start = std::chrono::steady_clock::now();
     size_t n_proc = have / (R ? R : 1);  // the reference counts the graph's milestones (start / goal join later)
     int rounds = 0;
     while (have < nm) {
-      RM_TRY(artp_sample_and_validate_dev(c, prm->seed, next, batch, d_batch, d_valid, nullptr));
-      RM_TRY(artp_compact_valid_dev(c, d_batch, d_valid, batch, d_compact, d_cnt));
+      ARTP_TRY(artp_sample_and_validate_dev(c, prm->seed, next, batch, d_batch, d_valid, nullptr));
+      ARTP_TRY(artp_compact_valid_dev(c, d_batch, d_valid, batch, d_compact, d_cnt));
       uint64_t got = 0;
-      RM_HIP(hipMemcpyAsync(&got, d_cnt, sizeof(got), hipMemcpyDeviceToHost, st));
-      RM_HIP(hipStreamSynchronize(st));
+      HIP_TRY(c, hipMemcpyAsync(&got, d_cnt, sizeof(got), hipMemcpyDeviceToHost, st));
+      HIP_TRY(c, hipStreamSynchronize(st));
       size_t want = nm - have;
       if (R) want = std::min(want, (n_proc + 1) * R - have);  // up to the next re-weighting point
       const size_t take = std::min<size_t>((size_t)got, want);
-      RM_HIP(hipMemcpyAsync(d_verts + (2 + have) * 7, d_compact, take * 7 * sizeof(double), hipMemcpyDeviceToDevice, st));
+      HIP_TRY(c, hipMemcpyAsync(d_verts + (2 + have) * 7, d_compact, take * 7 * sizeof(double), hipMemcpyDeviceToDevice, st));
       have += take;
       if (take < got) {
         // the round ended inside the batch: continue behind the sample that gave the last vertex taken
         uint32_t last = 0;
-        RM_TRY(artp_compact_valid_indices_dev(c, d_valid, batch, d_idx, d_cnt));
-        RM_HIP(hipMemcpyAsync(&last, d_idx + (take - 1), sizeof(last), hipMemcpyDeviceToHost, st));
-        RM_HIP(hipStreamSynchronize(st));
+        ARTP_TRY(artp_compact_valid_indices_dev(c, d_valid, batch, d_idx, d_cnt));
+        HIP_TRY(c, hipMemcpyAsync(&last, d_idx + (take - 1), sizeof(last), hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipStreamSynchronize(st));
         next += (uint64_t)last + 1;
       } else {
         next += batch;
@@ -1109,7 +1060,7 @@ static int roadmap_build_impl(artp_ctx* c, const artp_roadmap_params* prm_in, co
       if (R && have / R > n_proc) {
         // Map::reApplyPreprocessing(): the CDF follows the inverse vertex density from here on (also after the
         // last vertex, like the reference: the next growth samples from it)
-        RM_TRY(artp_preprocessed_reweight_dev(c, prm->density_map, prm->density_params, d_verts + 14, have, 1));
+        ARTP_TRY(artp_preprocessed_reweight_dev(c, prm->density_map, prm->density_params, d_verts + 14, have, 1));
         n_proc = have / R;
         ++n_reweights;
       }
@@ -1120,14 +1071,12 @@ static int roadmap_build_impl(artp_ctx* c, const artp_roadmap_params* prm_in, co
       }
       if (++rounds > 100000 || (got == 0 && rounds > 8 && !R)) {
         c->last_error = "sampler produced too few valid states for the requested roadmap";
-        cleanup();
         return ARTP_ERR_CAPACITY;
       }
     }
     nm_final = have;
     if (nm_final < 1) {
       c->last_error = "the sampling-time budget ended before the first milestone";
-      cleanup();
       return ARTP_ERR_CAPACITY;
     }
   }
@@ -1141,10 +1090,7 @@ static int roadmap_build_impl(artp_ctx* c, const artp_roadmap_params* prm_in, co
     artp_roadmap_params p_use = *prm;
     p_use.n_milestones = (uint32_t)(nv_use - 2);
     const int rc = roadmap_connect(c, &p_use, d_verts, nv_use, &rm);
-    if (rc != ARTP_OK) {
-      cleanup();
-      return rc;
-    }
+    if (rc != ARTP_OK) return rc;
     if (!prm->max_n_edges || rm->eu.size() <= prm->max_n_edges || nv_use <= 3 || attempt >= 12) break;
     std::vector<uint32_t> per_v(nv_use, 0);
     for (uint32_t v : rm->ev) ++per_v[v];
@@ -1166,7 +1112,6 @@ static int roadmap_build_impl(artp_ctx* c, const artp_roadmap_params* prm_in, co
   rm->samples_drawn = next - first_new;
   rm->n_reweights = n_reweights;
   rm->budget_flags = budget_flags;
-  cleanup();
   *out = rm;
   return ARTP_OK;
 }
@@ -1193,12 +1138,9 @@ struct IncrementalGraph {
   double *d_tasks = nullptr, *d_states = nullptr;
   uint8_t* d_valid = nullptr;
   size_t cap = 0;
+  DeviceScratch staging;  // owns the three
   std::vector<double> tasks, states;
   std::vector<uint8_t> valid;
-  ~IncrementalGraph() {
-    for (void* p : {(void*)d_tasks, (void*)d_states, (void*)d_valid})
-      if (p) (void)hipFree(p);
-  }
   size_t nv() const { return verts.size() / 7; }
   int cell_of(double v, double v0, int g) const {
     const int cc = (int)std::floor((v - v0) * inv_h);
@@ -1264,14 +1206,12 @@ struct IncrementalGraph {
     hipStream_t st = c->stream;
     if (hipSetDevice(c->device) != hipSuccess) return ARTP_ERR_HIP;
     if (cap < n) {
-      for (void* p : {(void*)d_tasks, (void*)d_states, (void*)d_valid})
-        if (p) (void)hipFree(p);
+      for (void* p : {(void*)d_tasks, (void*)d_states, (void*)d_valid}) staging.release(p);
       d_tasks = d_states = nullptr;
       d_valid = nullptr;
       cap = std::max<size_t>(2 * n, 1024);
-      if (hipMalloc(reinterpret_cast<void**>(&d_tasks), cap * 15 * sizeof(double)) != hipSuccess ||
-          hipMalloc(reinterpret_cast<void**>(&d_states), cap * 7 * sizeof(double)) != hipSuccess ||
-          hipMalloc(reinterpret_cast<void**>(&d_valid), cap) != hipSuccess) {
+      if (staging.alloc(&d_tasks, cap * 15) != hipSuccess || staging.alloc(&d_states, cap * 7) != hipSuccess ||
+          staging.alloc(&d_valid, cap) != hipSuccess) {
         cap = 0;
         c->last_error = "chain staging allocation failed";
         return ARTP_ERR_HIP;
@@ -1432,16 +1372,13 @@ static int incremental_sample_graph(IncrementalGraph& g, size_t max_vertices, ui
   uint8_t* d_valid = nullptr;
   uint32_t* d_idx = nullptr;
   uint64_t* d_cnt = nullptr;
-  auto cleanup = [&]() {
-    for (void* p : {(void*)d_batch, (void*)d_compact, (void*)d_valid, (void*)d_idx, (void*)d_cnt, (void*)d_verts})
-      if (p) (void)hipFree(p);
-  };
-  RM_HIP(hipSetDevice(c->device));
-  RM_HIP(hipMalloc(reinterpret_cast<void**>(&d_batch), batch * 7 * sizeof(double)));
-  RM_HIP(hipMalloc(reinterpret_cast<void**>(&d_compact), batch * 7 * sizeof(double)));
-  RM_HIP(hipMalloc(reinterpret_cast<void**>(&d_valid), batch));
-  RM_HIP(hipMalloc(reinterpret_cast<void**>(&d_idx), batch * sizeof(uint32_t)));
-  RM_HIP(hipMalloc(reinterpret_cast<void**>(&d_cnt), 2 * sizeof(uint64_t)));
+  DeviceScratch S;
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, S.alloc(&d_batch, batch * 7));
+  HIP_TRY(c, S.alloc(&d_compact, batch * 7));
+  HIP_TRY(c, S.alloc(&d_valid, batch));
+  HIP_TRY(c, S.alloc(&d_idx, batch));
+  HIP_TRY(c, S.alloc(&d_cnt, 2));
   const size_t R = (prm.density_map && prm.density_params && prm.recompute_density_after_n_samples)
                        ? prm.recompute_density_after_n_samples : 0;
   std::vector<double> acc(batch * 7);
@@ -1454,16 +1391,16 @@ static int incremental_sample_graph(IncrementalGraph& g, size_t max_vertices, ui
   while (g.n_graph < max_vertices && (!prm.max_n_edges || g.eu.size() < prm.max_n_edges)) {
     if (q_at == q_n) {
       base = next;
-      RM_TRY(artp_sample_and_validate_dev(c, prm.seed, base, batch, d_batch, d_valid, nullptr));
-      RM_TRY(artp_compact_valid_dev(c, d_batch, d_valid, batch, d_compact, d_cnt));
-      RM_TRY(artp_compact_valid_indices_dev(c, d_valid, batch, d_idx, d_cnt + 1));
+      ARTP_TRY(artp_sample_and_validate_dev(c, prm.seed, base, batch, d_batch, d_valid, nullptr));
+      ARTP_TRY(artp_compact_valid_dev(c, d_batch, d_valid, batch, d_compact, d_cnt));
+      ARTP_TRY(artp_compact_valid_indices_dev(c, d_valid, batch, d_idx, d_cnt + 1));
       uint64_t got = 0;
-      RM_HIP(hipMemcpyAsync(&got, d_cnt, sizeof(got), hipMemcpyDeviceToHost, st));
-      RM_HIP(hipStreamSynchronize(st));
+      HIP_TRY(c, hipMemcpyAsync(&got, d_cnt, sizeof(got), hipMemcpyDeviceToHost, st));
+      HIP_TRY(c, hipStreamSynchronize(st));
       if (got) {
-        RM_HIP(hipMemcpyAsync(acc.data(), d_compact, (size_t)got * 7 * sizeof(double), hipMemcpyDeviceToHost, st));
-        RM_HIP(hipMemcpyAsync(idx.data(), d_idx, (size_t)got * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        RM_HIP(hipStreamSynchronize(st));
+        HIP_TRY(c, hipMemcpyAsync(acc.data(), d_compact, (size_t)got * 7 * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipMemcpyAsync(idx.data(), d_idx, (size_t)got * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipStreamSynchronize(st));
       }
       q_n = (size_t)got;
       q_at = 0;
@@ -1471,7 +1408,6 @@ static int incremental_sample_graph(IncrementalGraph& g, size_t max_vertices, ui
       if (!got) {
         if (++empty_rounds > 64) {
           c->last_error = "sampler produced too few valid states for the requested roadmap";
-          cleanup();
           return ARTP_ERR_CAPACITY;
         }
         continue;
@@ -1484,16 +1420,15 @@ static int incremental_sample_graph(IncrementalGraph& g, size_t max_vertices, ui
     const uint64_t consumed = base + idx[q_at];
     ++q_at;
     if (q_at == q_n) next = base + batch; else next = consumed + 1;
-    RM_TRY(g.add_valid_milestone(m));
+    ARTP_TRY(g.add_valid_milestone(m));
     if (R && g.n_graph / R > n_proc) {
       // :190-193 Map::reApplyPreprocessing(): the distribution follows the inverse density of ALL graph vertices; the
       // stream continues right behind the sample that gave this milestone
       const size_t nvx = g.nv() - 2;
-      if (d_verts) (void)hipFree(d_verts);
-      d_verts = nullptr;
-      RM_HIP(hipMalloc(reinterpret_cast<void**>(&d_verts), nvx * 7 * sizeof(double)));
-      RM_HIP(hipMemcpyAsync(d_verts, g.verts.data() + 14, nvx * 7 * sizeof(double), hipMemcpyHostToDevice, st));
-      RM_TRY(artp_preprocessed_reweight_dev(c, prm.density_map, prm.density_params, d_verts, nvx, 1));
+      S.release(d_verts);  // regrown with the graph
+      HIP_TRY(c, S.alloc(&d_verts, nvx * 7));
+      HIP_TRY(c, hipMemcpyAsync(d_verts, g.verts.data() + 14, nvx * 7 * sizeof(double), hipMemcpyHostToDevice, st));
+      ARTP_TRY(artp_preprocessed_reweight_dev(c, prm.density_map, prm.density_params, d_verts, nvx, 1));
       ++n_proc;
       ++*n_reweights;
       next = consumed + 1;
@@ -1507,21 +1442,19 @@ static int incremental_sample_graph(IncrementalGraph& g, size_t max_vertices, ui
   }
   if (prm.max_n_edges && g.eu.size() >= prm.max_n_edges) *budget_flags |= 2u;
   *next_out = next;
-  cleanup();
   return ARTP_OK;
 }
 
 static int roadmap_build_incremental(artp_ctx* c, const artp_roadmap_params* prm, const double* start7,
                                      const double* goal7, artp_roadmap** out) {
   *out = nullptr;
-  auto cleanup = []() {};
   {
     double sg[14];
     std::memcpy(sg, start7, 7 * sizeof(double));
     std::memcpy(sg + 7, goal7, 7 * sizeof(double));
     uint8_t ok[2] = {0, 0};
-    RM_TRY(artp_validate_states(c, sg, 2, ok, nullptr));
-    RM_HIP(hipStreamSynchronize(c->stream));
+    ARTP_TRY(artp_validate_states(c, sg, 2, ok, nullptr));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (!ok[0] || !ok[1]) {
       c->last_error = !ok[0] ? "start state is not valid" : "goal state is not valid";
       return ARTP_ERR_INVALID_ARG;
@@ -1535,14 +1468,14 @@ static int roadmap_build_incremental(artp_ctx* c, const artp_roadmap_params* prm
   g.inserted.assign(2, 0);
   g.setup_grid(prm->n_milestones);
   uint64_t next = prm->first_index, n_reweights = 0, budget_flags = 0;
-  RM_TRY(incremental_sample_graph(g, prm->n_milestones, prm->first_index, &next, &n_reweights, &budget_flags));
+  ARTP_TRY(incremental_sample_graph(g, prm->n_milestones, prm->first_index, &next, &n_reweights, &budget_flags));
   if (g.n_graph < 1) {
     c->last_error = "the sampling-time budget ended before the first milestone";
     return ARTP_ERR_CAPACITY;
   }
   // baseSolve: start and goal become milestones of the finished roadmap (:447-470)
-  RM_TRY(g.add_valid_milestone(0));
-  RM_TRY(g.add_valid_milestone(1));
+  ARTP_TRY(g.add_valid_milestone(0));
+  ARTP_TRY(g.add_valid_milestone(1));
   auto rm = new artp_roadmap();
   const int rc = incremental_finish(g, rm, nullptr);
   if (rc != ARTP_OK) {
@@ -1561,11 +1494,10 @@ static int roadmap_build_incremental(artp_ctx* c, const artp_roadmap_params* prm
 // marked invalid; n_more = how many more graph vertices (chain vertices included) the budget allows.
 static int roadmap_grow_incremental(artp_roadmap* rm, uint64_t n_more, uint64_t out[2]) {
   artp_ctx* c = rm->ctx;
-  auto cleanup = []() {};
   const size_t nv = rm->nv();
   std::vector<uint8_t> vok(nv, 0);
-  RM_TRY(artp_validate_states(c, rm->verts.data(), nv, vok.data(), nullptr));
-  RM_HIP(hipStreamSynchronize(c->stream));
+  ARTP_TRY(artp_validate_states(c, rm->verts.data(), nv, vok.data(), nullptr));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
   if (!vok[0] || !vok[1]) {
     c->last_error = !vok[0] ? "start state is not valid" : "goal state is not valid";
     return ARTP_ERR_INVALID_ARG;
@@ -1597,7 +1529,7 @@ static int roadmap_grow_incremental(artp_roadmap* rm, uint64_t n_more, uint64_t 
     for (uint32_t t = 0; t < cnt; ++t) g.knn_rows.push_back(rm->knn[(size_t)m * rm->k + t]);
   }
   uint64_t next = rm->params.first_index + rm->samples_drawn, n_reweights = 0, budget_flags = 0;
-  RM_TRY(incremental_sample_graph(g, nv + (size_t)n_more, next, &next, &n_reweights, &budget_flags));
+  ARTP_TRY(incremental_sample_graph(g, nv + (size_t)n_more, next, &next, &n_reweights, &budget_flags));
   vok.resize(g.nv(), 1);
   auto fresh = new artp_roadmap();
   const int rc = incremental_finish(g, fresh, &vok);
@@ -1702,6 +1634,7 @@ int artp_roadmap_revalidate(artp_roadmap* rm, uint64_t out[4]) {
       // (2 MB for 10^4 vertices), the 19 MB of endpoint states are gathered on the device
       double* d_v = nullptr;
       uint32_t* d_uv = nullptr;
+      DeviceScratch S;
       bool okk = hipSetDevice(c->device) == hipSuccess;
       if (okk && rm->d_edge_cap < ne) {
         if (rm->d_edge_states) (void)hipFree(rm->d_edge_states);
@@ -1709,8 +1642,7 @@ int artp_roadmap_revalidate(artp_roadmap* rm, uint64_t out[4]) {
         okk = hipMalloc(reinterpret_cast<void**>(&rm->d_edge_states), 2 * ne * 7 * sizeof(double)) == hipSuccess;
         rm->d_edge_cap = okk ? ne : 0;
       }
-      okk = okk && hipMalloc(reinterpret_cast<void**>(&d_v), nv * 7 * sizeof(double)) == hipSuccess &&
-            hipMalloc(reinterpret_cast<void**>(&d_uv), 2 * ne * sizeof(uint32_t)) == hipSuccess &&
+      okk = okk && S.alloc(&d_v, nv * 7) == hipSuccess && S.alloc(&d_uv, 2 * ne) == hipSuccess &&
             hipMemcpyAsync(d_v, rm->verts.data(), nv * 7 * sizeof(double), hipMemcpyHostToDevice, c->stream) == hipSuccess &&
             hipMemcpyAsync(d_uv, rm->eu.data(), ne * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream) == hipSuccess &&
             hipMemcpyAsync(d_uv + ne, rm->ev.data(), ne * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream) == hipSuccess;
@@ -1729,8 +1661,6 @@ int artp_roadmap_revalidate(artp_roadmap* rm, uint64_t out[4]) {
                            rm->d_edge_states + ne * 7);
         okk = hipGetLastError() == hipSuccess && hipStreamSynchronize(c->stream) == hipSuccess;
       }
-      if (d_v) (void)hipFree(d_v);
-      if (d_uv) (void)hipFree(d_uv);
       if (!okk) {
         c->last_error = "staging the edge states failed";
         return ARTP_ERR_HIP;
@@ -2265,29 +2195,27 @@ int roadmap_check_motion_items(artp_roadmap* rm, const std::vector<uint32_t>& sr
   }
   // the context's host-entry staging slots (tmp[0], tmp[1]: the device entry point below does not touch them) instead of
   // four hipMalloc / hipFree pairs per call -- a hipFree alone waits for the device
-  auto cleanup = []() {};
-  RM_HIP(hipSetDevice(c->device));
-  RM_TRY(ensure_tmp(c, 0, nv * 7 * sizeof(double) + 2 * n * sizeof(uint32_t) + 64));
-  RM_TRY(ensure_tmp(c, 1, 2 * n * 7 * sizeof(double) + n + 64));
+  HIP_TRY(c, hipSetDevice(c->device));
+  ARTP_TRY(ensure_tmp(c, 0, nv * 7 * sizeof(double) + 2 * n * sizeof(uint32_t) + 64));
+  ARTP_TRY(ensure_tmp(c, 1, 2 * n * 7 * sizeof(double) + n + 64));
   double* d_v = static_cast<double*>(c->tmp[0]);
   uint32_t* d_uv = reinterpret_cast<uint32_t*>(d_v + nv * 7);
   double* d_s = static_cast<double*>(c->tmp[1]);
   uint8_t* d_ok = reinterpret_cast<uint8_t*>(d_s + 2 * n * 7);
-  RM_HIP(hipMemcpyAsync(d_v, rm->verts.data(), nv * 7 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  RM_HIP(hipMemcpyAsync(d_uv, src.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-  RM_HIP(hipMemcpyAsync(d_uv + n, dst.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(d_v, rm->verts.data(), nv * 7 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(d_uv, src.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(d_uv + n, dst.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
   hipLaunchKernelGGL(artp::gather_edge_states_uv_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream,
                      (const double*)d_v, (const uint32_t*)d_uv, (const uint32_t*)(d_uv + n), n, d_s, d_s + n * 7);
-  RM_HIP(hipGetLastError());
+  HIP_TRY(c, hipGetLastError());
   // in chunks of 2^18 motions (~13 M interior states): the pipeline's scratch (PoseRecs, queues) is sized by the largest
   // batch a context has seen, and a 10^6-motion batch would make it allocate tens of GB once
   for (size_t at = 0; at < n; at += (size_t)1 << 18) {
     const size_t m = std::min(n - at, (size_t)1 << 18);
-    RM_TRY(artp_check_motions_dev(c, d_s + at * 7, d_s + (n + at) * 7, m, d_ok + at));
+    ARTP_TRY(artp_check_motions_dev(c, d_s + at * 7, d_s + (n + at) * 7, m, d_ok + at));
   }
-  RM_HIP(hipMemcpyAsync(ok->data(), d_ok, n, hipMemcpyDeviceToHost, c->stream));
-  RM_HIP(hipStreamSynchronize(c->stream));
-  cleanup();
+  HIP_TRY(c, hipMemcpyAsync(ok->data(), d_ok, n, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
   return ARTP_OK;
 }
 

@@ -269,22 +269,6 @@ roadmap_many_resolve_kernel(int ng, uint32_t round, uint32_t max_replans, const 
 
 namespace {
 
-// device scratch of one solve_many call: freed on every way out
-struct ManyBufs {
-  std::vector<void*> ptrs;
-  ~ManyBufs() {
-    for (void* p : ptrs) (void)hipFree(p);
-  }
-  template <class T>
-  hipError_t alloc(T** out, size_t count) {
-    void* p = nullptr;
-    const hipError_t e = hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T));
-    if (e == hipSuccess) ptrs.push_back(p);
-    *out = static_cast<T*>(p);
-    return e;
-  }
-};
-
 // set_query's distance (artp_roadmap_set_query): |dp| + the host acos of the quaternion dot product
 inline double many_host_distance(const double* a, const double* b) {
   const double dx = a[0] - b[0], dy = a[1] - b[1], dz = a[2] - b[2];
@@ -360,22 +344,6 @@ struct QuerySnapshot {
   }
 };
 
-#define MANY_HIP(expr)                                                     \
-  do {                                                                     \
-    const hipError_t e_ = (expr);                                          \
-    if (e_ != hipSuccess) {                                                \
-      c->last_error = std::string(#expr) + ": " + hipGetErrorString(e_);   \
-      return ARTP_ERR_HIP;                                                 \
-    }                                                                      \
-  } while (0)
-#define MANY_TRY(expr)          \
-  do {                          \
-    const int rc_ = (expr);     \
-    if (rc_ != ARTP_OK) return rc_; \
-  } while (0)
-
-inline unsigned many_blocks(size_t n, unsigned bs = 256) { return (unsigned)std::max<size_t>((n + bs - 1) / bs, 1); }
-
 // the device part: goals gi[0 .. ng) (indices into goals), attached to an[ng x k] with weights aw; the start's
 // attachment list is snb.  Fills status / cost of those goals and their paths as vertex-id lists (vertex nv + i =
 // goals row gi[i]).
@@ -417,7 +385,7 @@ int many_device_solve(artp_roadmap* rm, const double* start7, const double* goal
   std::memcpy(hV.data(), start7, 7 * sizeof(double));
   for (size_t i = 0; i < ng; ++i) std::memcpy(&hV[(nv + i) * 7], goals + (size_t)gi[i] * 7, 7 * sizeof(double));
 
-  ManyBufs B;
+  DeviceScratch B;
   const size_t nvv = nv + ng, nga = ng * (size_t)k;
   double *d_V, *d_w, *d_aw, *d_cost, *d_s = nullptr;
   uint32_t *d_euv, *d_verdict, *d_an, *d_averdict, *d_hops, *d_best, *d_len, *d_off, *d_nbad, *d_remv, *d_fround,
@@ -427,48 +395,48 @@ int many_device_solve(artp_roadmap* rm, const double* start7, const double* goal
   unsigned *d_stamp, *d_hstamp, *d_cnt;
   uint8_t* d_removed;
   uint8_t* d_ok = nullptr;
-  MANY_HIP(hipSetDevice(c->device));
-  MANY_HIP(B.alloc(&d_V, nvv * 7));
-  MANY_HIP(B.alloc(&d_euv, 2 * ne));
-  MANY_HIP(B.alloc(&d_w, ne));
-  MANY_HIP(B.alloc(&d_removed, ne));
-  MANY_HIP(B.alloc(&d_verdict, 2 * ne));
-  MANY_HIP(B.alloc(&d_an, nga));
-  MANY_HIP(B.alloc(&d_aw, nga));
-  MANY_HIP(B.alloc(&d_averdict, nga));
-  MANY_HIP(B.alloc(&d_dist, nv));
-  MANY_HIP(B.alloc(&d_pkey, nv));
-  MANY_HIP(B.alloc(&d_stamp, nv));
-  MANY_HIP(B.alloc(&d_hstamp, nv));
-  MANY_HIP(B.alloc(&d_hops, nv));
-  MANY_HIP(B.alloc(&d_status, ng));
-  MANY_HIP(B.alloc(&d_cost, ng));
-  MANY_HIP(B.alloc(&d_best, ng));
-  MANY_HIP(B.alloc(&d_len, ng + 1));
-  MANY_HIP(B.alloc(&d_off, ng + 1));
-  MANY_HIP(B.alloc(&d_nbad, ng));
-  MANY_HIP(B.alloc(&d_remv, ng));
-  MANY_HIP(B.alloc(&d_fround, ng));
-  MANY_HIP(B.alloc(&d_foff, ng));
-  MANY_HIP(B.alloc(&d_flen, ng));
-  MANY_HIP(B.alloc(&d_cnt, 8));  // [0] sssp changed, [1] hops changed, [2] items, [3] goals with a bad path, [4] error
-  MANY_HIP(hipMemcpyAsync(d_V, hV.data(), nvv * 7 * sizeof(double), hipMemcpyHostToDevice, st));
-  MANY_HIP(hipMemcpyAsync(d_euv, heu.data(), ne * 4, hipMemcpyHostToDevice, st));
-  MANY_HIP(hipMemcpyAsync(d_euv + ne, hev.data(), ne * 4, hipMemcpyHostToDevice, st));
-  MANY_HIP(hipMemcpyAsync(d_w, hw.data(), ne * sizeof(double), hipMemcpyHostToDevice, st));
-  MANY_HIP(hipMemsetAsync(d_removed, 0, ne, st));
-  MANY_HIP(hipMemcpyAsync(d_verdict, hverdict.data(), 2 * ne * 4, hipMemcpyHostToDevice, st));
-  MANY_HIP(hipMemcpyAsync(d_an, an.data(), nga * 4, hipMemcpyHostToDevice, st));
-  MANY_HIP(hipMemcpyAsync(d_aw, aw.data(), nga * sizeof(double), hipMemcpyHostToDevice, st));
-  MANY_HIP(hipMemsetAsync(d_averdict, 0, nga * 4, st));
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, B.alloc(&d_V, nvv * 7));
+  HIP_TRY(c, B.alloc(&d_euv, 2 * ne));
+  HIP_TRY(c, B.alloc(&d_w, ne));
+  HIP_TRY(c, B.alloc(&d_removed, ne));
+  HIP_TRY(c, B.alloc(&d_verdict, 2 * ne));
+  HIP_TRY(c, B.alloc(&d_an, nga));
+  HIP_TRY(c, B.alloc(&d_aw, nga));
+  HIP_TRY(c, B.alloc(&d_averdict, nga));
+  HIP_TRY(c, B.alloc(&d_dist, nv));
+  HIP_TRY(c, B.alloc(&d_pkey, nv));
+  HIP_TRY(c, B.alloc(&d_stamp, nv));
+  HIP_TRY(c, B.alloc(&d_hstamp, nv));
+  HIP_TRY(c, B.alloc(&d_hops, nv));
+  HIP_TRY(c, B.alloc(&d_status, ng));
+  HIP_TRY(c, B.alloc(&d_cost, ng));
+  HIP_TRY(c, B.alloc(&d_best, ng));
+  HIP_TRY(c, B.alloc(&d_len, ng + 1));
+  HIP_TRY(c, B.alloc(&d_off, ng + 1));
+  HIP_TRY(c, B.alloc(&d_nbad, ng));
+  HIP_TRY(c, B.alloc(&d_remv, ng));
+  HIP_TRY(c, B.alloc(&d_fround, ng));
+  HIP_TRY(c, B.alloc(&d_foff, ng));
+  HIP_TRY(c, B.alloc(&d_flen, ng));
+  HIP_TRY(c, B.alloc(&d_cnt, 8));  // [0] sssp changed, [1] hops changed, [2] items, [3] goals with a bad path, [4] error
+  HIP_TRY(c, hipMemcpyAsync(d_V, hV.data(), nvv * 7 * sizeof(double), hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemcpyAsync(d_euv, heu.data(), ne * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemcpyAsync(d_euv + ne, hev.data(), ne * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemcpyAsync(d_w, hw.data(), ne * sizeof(double), hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemsetAsync(d_removed, 0, ne, st));
+  HIP_TRY(c, hipMemcpyAsync(d_verdict, hverdict.data(), 2 * ne * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemcpyAsync(d_an, an.data(), nga * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemcpyAsync(d_aw, aw.data(), nga * sizeof(double), hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemsetAsync(d_averdict, 0, nga * 4, st));
   {
     const std::vector<int32_t> pending(ng, artp::MANY_PENDING);
-    MANY_HIP(hipMemcpyAsync(d_status, pending.data(), ng * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(d_status, pending.data(), ng * 4, hipMemcpyHostToDevice, st));
   }
-  MANY_HIP(hipMemsetAsync(d_cost, 0, ng * sizeof(double), st));
-  MANY_HIP(hipMemsetAsync(d_nbad, 0, ng * 4, st));
-  MANY_HIP(hipMemsetAsync(d_remv, 0, ng * 4, st));
-  MANY_HIP(hipMemsetAsync(d_cnt, 0, 8 * 4, st));
+  HIP_TRY(c, hipMemsetAsync(d_cost, 0, ng * sizeof(double), st));
+  HIP_TRY(c, hipMemsetAsync(d_nbad, 0, ng * 4, st));
+  HIP_TRY(c, hipMemsetAsync(d_remv, 0, ng * 4, st));
+  HIP_TRY(c, hipMemsetAsync(d_cnt, 0, 8 * 4, st));
   const uint32_t* d_eu = d_euv;
   const uint32_t* d_ev = d_euv + ne;
   size_t blocks = (ne + 255) / 256;
@@ -476,8 +444,8 @@ int many_device_solve(artp_roadmap* rm, const double* start7, const double* goal
   if (blocks == 0) blocks = 1;
   void* d_scan = nullptr;
   size_t scan_bytes = 0;
-  MANY_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, d_len, d_off, (int)(ng + 1), st));
-  MANY_HIP(B.alloc(reinterpret_cast<uint8_t**>(&d_scan), scan_bytes + 256));
+  HIP_TRY(c, hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, d_len, d_off, (int)(ng + 1), st));
+  HIP_TRY(c, B.alloc(reinterpret_cast<uint8_t**>(&d_scan), scan_bytes + 256));
   scan_bytes += 256;
   std::vector<uint32_t*> round_pv;  // every round's path states: frozen goals point into them
   std::vector<uint32_t> round_total;
@@ -485,66 +453,66 @@ int many_device_solve(artp_roadmap* rm, const double* start7, const double* goal
   uint64_t rounds = 0, motions = 0;
   for (;;) {
     // 1. shortest paths from the start (sssp_relax_kernel as roadmap_sssp_dev runs it)
-    hipLaunchKernelGGL(artp::roadmap_many_init_kernel, dim3(many_blocks(nv)), dim3(256), 0, st, (int)nv, d_dist, d_stamp,
+    hipLaunchKernelGGL(artp::roadmap_many_init_kernel, dim3(tree_blocks(nv)), dim3(256), 0, st, (int)nv, d_dist, d_stamp,
                        d_hops, d_hstamp, d_pkey);
     unsigned cnt[8];
     // sweep groups of 16, 32, 64 between host reads: a sweep behind the wavefront costs two reads per edge, a read
     // a synchronisation (the sparse construction-1 graphs take hundreds of sweeps)
     for (unsigned sweep = 1, group = 16; sweep < 1000000u; sweep += group, group = std::min(2 * group, 64u)) {
-      MANY_HIP(hipMemsetAsync(d_cnt, 0, 4, st));
+      HIP_TRY(c, hipMemsetAsync(d_cnt, 0, 4, st));
       for (unsigned r = 0; r < group; ++r)
         hipLaunchKernelGGL(artp::sssp_relax_kernel, dim3((unsigned)blocks), dim3(256), 0, st, d_eu, d_ev,
                            (const double*)d_w, ne, d_dist, d_stamp, sweep + r, d_cnt);
-      MANY_HIP(hipMemcpyAsync(cnt, d_cnt, 4, hipMemcpyDeviceToHost, st));
-      MANY_HIP(hipStreamSynchronize(st));
+      HIP_TRY(c, hipMemcpyAsync(cnt, d_cnt, 4, hipMemcpyDeviceToHost, st));
+      HIP_TRY(c, hipStreamSynchronize(st));
       if (!cnt[0]) break;
     }
     // 2. hop counts over the tight edges, predecessors one hop closer
     for (unsigned sweep = 1, group = 16; sweep < 1000000u; sweep += group, group = std::min(2 * group, 64u)) {
-      MANY_HIP(hipMemsetAsync(d_cnt + 1, 0, 4, st));
+      HIP_TRY(c, hipMemsetAsync(d_cnt + 1, 0, 4, st));
       for (unsigned r = 0; r < group; ++r)
         hipLaunchKernelGGL(artp::roadmap_many_hops_kernel, dim3((unsigned)blocks), dim3(256), 0, st, d_eu, d_ev,
                            (const double*)d_w, ne, (const unsigned long long*)d_dist, d_hops, d_hstamp, sweep + r, d_cnt + 1);
-      MANY_HIP(hipMemcpyAsync(cnt + 1, d_cnt + 1, 4, hipMemcpyDeviceToHost, st));
-      MANY_HIP(hipStreamSynchronize(st));
+      HIP_TRY(c, hipMemcpyAsync(cnt + 1, d_cnt + 1, 4, hipMemcpyDeviceToHost, st));
+      HIP_TRY(c, hipStreamSynchronize(st));
       if (!cnt[1]) break;
     }
     hipLaunchKernelGGL(artp::roadmap_many_pred_kernel, dim3((unsigned)blocks), dim3(256), 0, st, d_eu, d_ev,
                        (const double*)d_w, ne, (const unsigned long long*)d_dist, (const uint32_t*)d_hops, d_pkey);
     // 3. best attachment per pending goal, 4. path lengths -> offsets
-    hipLaunchKernelGGL(artp::roadmap_many_attach_kernel, dim3(many_blocks(ng + 1)), dim3(256), 0, st, (int)ng, k,
+    hipLaunchKernelGGL(artp::roadmap_many_attach_kernel, dim3(tree_blocks(ng + 1)), dim3(256), 0, st, (int)ng, k,
                        (const uint32_t*)d_an, (const double*)d_aw, (const unsigned long long*)d_dist,
                        (const uint32_t*)d_hops, d_status, d_cost, d_best, d_len, d_cnt + 4);
-    MANY_HIP(hipcub::DeviceScan::ExclusiveSum(d_scan, scan_bytes, d_len, d_off, (int)(ng + 1), st));
+    HIP_TRY(c, hipcub::DeviceScan::ExclusiveSum(d_scan, scan_bytes, d_len, d_off, (int)(ng + 1), st));
     uint32_t total = 0;
-    MANY_HIP(hipMemcpyAsync(&total, d_off + ng, 4, hipMemcpyDeviceToHost, st));
-    MANY_HIP(hipStreamSynchronize(st));
+    HIP_TRY(c, hipMemcpyAsync(&total, d_off + ng, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
     if (total == 0) break;  // no pending goal has a path left
     ++rounds;
     uint32_t* d_pv;
-    MANY_HIP(B.alloc(&d_pv, total));
+    HIP_TRY(c, B.alloc(&d_pv, total));
     round_pv.push_back(d_pv);
     round_total.push_back(total);
     if (total > cap_items) {  // per-round scratch sized by the largest round
       cap_items = std::max<size_t>(total, 2 * cap_items);
-      MANY_HIP(B.alloc(&d_pitem, cap_items));
-      MANY_HIP(B.alloc(&d_pgoal, cap_items));
-      MANY_HIP(B.alloc(&d_items, cap_items));
-      MANY_HIP(B.alloc(&d_isrc, 2 * cap_items));
-      MANY_HIP(B.alloc(&d_s, 2 * cap_items * 7));
-      MANY_HIP(B.alloc(&d_ok, cap_items));
+      HIP_TRY(c, B.alloc(&d_pitem, cap_items));
+      HIP_TRY(c, B.alloc(&d_pgoal, cap_items));
+      HIP_TRY(c, B.alloc(&d_items, cap_items));
+      HIP_TRY(c, B.alloc(&d_isrc, 2 * cap_items));
+      HIP_TRY(c, B.alloc(&d_s, 2 * cap_items * 7));
+      HIP_TRY(c, B.alloc(&d_ok, cap_items));
     }
-    hipLaunchKernelGGL(artp::roadmap_many_path_kernel, dim3(many_blocks(ng)), dim3(256), 0, st, (int)ng, k, (int)nv, ne,
+    hipLaunchKernelGGL(artp::roadmap_many_path_kernel, dim3(tree_blocks(ng)), dim3(256), 0, st, (int)ng, k, (int)nv, ne,
                        d_eu, (const uint32_t*)d_an, (const uint32_t*)d_best, (const uint32_t*)d_len,
                        (const uint32_t*)d_off, (const unsigned long long*)d_pkey, d_pv, d_pitem, d_pgoal, d_cnt + 4);
     // 5. unchecked (edge, direction) items of all paths, once each
-    MANY_HIP(hipMemsetAsync(d_cnt + 2, 0, 8, st));
-    hipLaunchKernelGGL(artp::roadmap_many_collect_kernel, dim3(many_blocks(total)), dim3(256), 0, st, total, ne,
+    HIP_TRY(c, hipMemsetAsync(d_cnt + 2, 0, 8, st));
+    hipLaunchKernelGGL(artp::roadmap_many_collect_kernel, dim3(tree_blocks(total)), dim3(256), 0, st, total, ne,
                        (const uint32_t*)d_pv, (const uint32_t*)d_pitem, d_verdict, d_averdict, d_items, d_isrc,
                        d_isrc + cap_items, d_cnt + 2);
-    MANY_HIP(hipGetLastError());
-    MANY_HIP(hipMemcpyAsync(cnt + 2, d_cnt + 2, 12, hipMemcpyDeviceToHost, st));
-    MANY_HIP(hipStreamSynchronize(st));
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(cnt + 2, d_cnt + 2, 12, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
     if (cnt[4]) {
       c->last_error = "artp_roadmap_solve_many: broken predecessor chain";
       return ARTP_ERR_HIP;
@@ -552,30 +520,30 @@ int many_device_solve(artp_roadmap* rm, const double* start7, const double* goal
     const unsigned m = cnt[2];
     // 6. one motion check for all of them (chunks of 2^18 motions, as roadmap_check_motion_items), verdicts scattered
     if (m) {
-      hipLaunchKernelGGL(artp::gather_edge_states_uv_kernel, dim3(many_blocks(m)), dim3(256), 0, st, (const double*)d_V,
+      hipLaunchKernelGGL(artp::gather_edge_states_uv_kernel, dim3(tree_blocks(m)), dim3(256), 0, st, (const double*)d_V,
                          (const uint32_t*)d_isrc, (const uint32_t*)(d_isrc + cap_items), (size_t)m, d_s,
                          d_s + (size_t)m * 7);
-      MANY_HIP(hipGetLastError());
+      HIP_TRY(c, hipGetLastError());
       for (size_t at = 0; at < m; at += (size_t)1 << 18) {
         const size_t mm = std::min<size_t>(m - at, (size_t)1 << 18);
-        MANY_TRY(artp_check_motions_dev(c, d_s + at * 7, d_s + ((size_t)m + at) * 7, mm, d_ok + at));
+        ARTP_TRY(artp_check_motions_dev(c, d_s + at * 7, d_s + ((size_t)m + at) * 7, mm, d_ok + at));
       }
-      hipLaunchKernelGGL(artp::roadmap_many_scatter_kernel, dim3(many_blocks(m)), dim3(256), 0, st, m, ne,
+      hipLaunchKernelGGL(artp::roadmap_many_scatter_kernel, dim3(tree_blocks(m)), dim3(256), 0, st, m, ne,
                          (const uint32_t*)d_items, (const uint8_t*)d_ok, d_verdict, d_averdict);
       motions += m;
     }
     // 7. removals, then freeze the goals whose whole path passed
-    hipLaunchKernelGGL(artp::roadmap_many_remove_kernel, dim3(many_blocks(total)), dim3(256), 0, st, total, ne,
+    hipLaunchKernelGGL(artp::roadmap_many_remove_kernel, dim3(tree_blocks(total)), dim3(256), 0, st, total, ne,
                        (const uint32_t*)d_pitem, (const uint32_t*)d_pgoal, (const uint32_t*)d_verdict,
                        (const uint32_t*)d_averdict, d_w, d_removed, d_aw, d_nbad);
-    hipLaunchKernelGGL(artp::roadmap_many_resolve_kernel, dim3(many_blocks(ng)), dim3(256), 0, st, (int)ng,
+    hipLaunchKernelGGL(artp::roadmap_many_resolve_kernel, dim3(tree_blocks(ng)), dim3(256), 0, st, (int)ng,
                        (uint32_t)(round_pv.size() - 1), (uint32_t)rm->params.max_replans, (const uint32_t*)d_best,
                        (const uint32_t*)d_len, (const uint32_t*)d_off, d_nbad, d_remv, d_status, d_cost, d_fround,
                        d_foff, d_flen, d_cnt + 3);
-    MANY_HIP(hipGetLastError());
-    MANY_HIP(hipMemcpyAsync(cnt + 3, d_cnt + 3, 4, hipMemcpyDeviceToHost, st));
-    MANY_HIP(hipStreamSynchronize(st));
-    MANY_TRY(check_error_flag(c));
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(cnt + 3, d_cnt + 3, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    ARTP_TRY(check_error_flag(c));
     if (cnt[3] == 0) break;  // no pending goal's path had an invalid edge
   }
   // results: statuses, costs, frozen paths; removals and verdicts back into the roadmap
@@ -583,20 +551,20 @@ int many_device_solve(artp_roadmap* rm, const double* start7, const double* goal
   std::vector<double> hcost(ng);
   std::vector<uint32_t> fr(ng), fo(ng), fl(ng), hav(nga);
   std::vector<uint8_t> hrem(ne);
-  MANY_HIP(hipMemcpyAsync(hst.data(), d_status, ng * 4, hipMemcpyDeviceToHost, st));
-  MANY_HIP(hipMemcpyAsync(hcost.data(), d_cost, ng * sizeof(double), hipMemcpyDeviceToHost, st));
-  MANY_HIP(hipMemcpyAsync(fr.data(), d_fround, ng * 4, hipMemcpyDeviceToHost, st));
-  MANY_HIP(hipMemcpyAsync(fo.data(), d_foff, ng * 4, hipMemcpyDeviceToHost, st));
-  MANY_HIP(hipMemcpyAsync(fl.data(), d_flen, ng * 4, hipMemcpyDeviceToHost, st));
-  MANY_HIP(hipMemcpyAsync(hav.data(), d_averdict, nga * 4, hipMemcpyDeviceToHost, st));
-  MANY_HIP(hipMemcpyAsync(hrem.data(), d_removed, ne, hipMemcpyDeviceToHost, st));
-  MANY_HIP(hipMemcpyAsync(hverdict.data(), d_verdict, 2 * ne * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(hst.data(), d_status, ng * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(hcost.data(), d_cost, ng * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(fr.data(), d_fround, ng * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(fo.data(), d_foff, ng * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(fl.data(), d_flen, ng * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(hav.data(), d_averdict, nga * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(hrem.data(), d_removed, ne, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(hverdict.data(), d_verdict, 2 * ne * 4, hipMemcpyDeviceToHost, st));
   std::vector<std::vector<uint32_t>> rpv(round_pv.size());
   for (size_t r = 0; r < round_pv.size(); ++r) {
     rpv[r].resize(round_total[r]);
-    MANY_HIP(hipMemcpyAsync(rpv[r].data(), round_pv[r], (size_t)round_total[r] * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(rpv[r].data(), round_pv[r], (size_t)round_total[r] * 4, hipMemcpyDeviceToHost, st));
   }
-  MANY_HIP(hipStreamSynchronize(st));
+  HIP_TRY(c, hipStreamSynchronize(st));
   uint64_t n_removed = 0;
   for (size_t i = 0; i < ng; ++i) {
     const uint32_t g = gi[i];
@@ -680,7 +648,7 @@ int artp_roadmap_solve_many(artp_roadmap* rm, const double* start_se3, const dou
     std::vector<uint32_t> sid;
     std::vector<double> sd;
     if (kk > k) {
-      ManyBufs B;
+      DeviceScratch B;
       double *d_v, *d_q, *d_d;
       uint32_t* d_id;
       uint8_t* d_pr;
@@ -689,23 +657,23 @@ int artp_roadmap_solve_many(artp_roadmap* rm, const double* start_se3, const dou
       for (size_t i = 0; i < nq; ++i) std::memcpy(&q[i * 7], goals + (size_t)pend[i] * 7, 7 * sizeof(double));
       std::vector<uint8_t> pr(nv, 0);
       for (size_t j = 0; j < nv; ++j) pr[j] = j < 2 || (j < rm->vinvalid.size() && rm->vinvalid[j]);
-      MANY_HIP(hipSetDevice(c->device));
-      MANY_HIP(B.alloc(&d_v, nv * 7));
-      MANY_HIP(B.alloc(&d_q, nq * 7));
-      MANY_HIP(B.alloc(&d_d, nq * kk));
-      MANY_HIP(B.alloc(&d_id, nq * kk));
-      MANY_HIP(B.alloc(&d_pr, nv));
-      MANY_HIP(hipMemcpyAsync(d_v, rm->verts.data(), nv * 7 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-      MANY_HIP(hipMemcpyAsync(d_q, q.data(), nq * 7 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-      MANY_HIP(hipMemcpyAsync(d_pr, pr.data(), nv, hipMemcpyHostToDevice, c->stream));
-      hipLaunchKernelGGL(artp::tree_knn_kernel, dim3(many_blocks(nq, 4)), dim3(256), 0, c->stream, (const double*)d_v,
+      HIP_TRY(c, hipSetDevice(c->device));
+      HIP_TRY(c, B.alloc(&d_v, nv * 7));
+      HIP_TRY(c, B.alloc(&d_q, nq * 7));
+      HIP_TRY(c, B.alloc(&d_d, nq * kk));
+      HIP_TRY(c, B.alloc(&d_id, nq * kk));
+      HIP_TRY(c, B.alloc(&d_pr, nv));
+      HIP_TRY(c, hipMemcpyAsync(d_v, rm->verts.data(), nv * 7 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+      HIP_TRY(c, hipMemcpyAsync(d_q, q.data(), nq * 7 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+      HIP_TRY(c, hipMemcpyAsync(d_pr, pr.data(), nv, hipMemcpyHostToDevice, c->stream));
+      hipLaunchKernelGGL(artp::tree_knn_kernel, dim3(tree_blocks(nq, 4)), dim3(256), 0, c->stream, (const double*)d_v,
                          (int)nv, (const uint8_t*)d_pr, (const double*)d_q, (int)nq, kk, d_id, d_d);
-      MANY_HIP(hipGetLastError());
+      HIP_TRY(c, hipGetLastError());
       sid.resize(nq * kk);
       sd.resize(nq * kk);
-      MANY_HIP(hipMemcpyAsync(sid.data(), d_id, nq * kk * 4, hipMemcpyDeviceToHost, c->stream));
-      MANY_HIP(hipMemcpyAsync(sd.data(), d_d, nq * kk * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-      MANY_HIP(hipStreamSynchronize(c->stream));
+      HIP_TRY(c, hipMemcpyAsync(sid.data(), d_id, nq * kk * 4, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipMemcpyAsync(sd.data(), d_d, nq * kk * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
     }
     for (size_t i = 0; i < pend.size(); ++i) {
       const double* q = goals + (size_t)pend[i] * 7;
@@ -805,12 +773,12 @@ int artp_roadmap_solve_many(artp_roadmap* rm, const double* start_se3, const dou
     std::vector<uint32_t> einterp(at);
     std::vector<double> ecost(at);
     {
-      ManyBufs B;
+      DeviceScratch B;
       double* d_s12;
-      MANY_HIP(hipSetDevice(c->device));
-      MANY_HIP(B.alloc(&d_s12, 2 * na * 7));
-      MANY_HIP(hipMemcpy(d_s12, s12.data(), 2 * na * 7 * sizeof(double), hipMemcpyHostToDevice));
-      MANY_TRY(roadmap_eval_edges_dev(c, &rm->params, d_s12, d_s12 + na * 7, at, evalid.data(), einterp.data(),
+      HIP_TRY(c, hipSetDevice(c->device));
+      HIP_TRY(c, B.alloc(&d_s12, 2 * na * 7));
+      HIP_TRY(c, hipMemcpy(d_s12, s12.data(), 2 * na * 7 * sizeof(double), hipMemcpyHostToDevice));
+      ARTP_TRY(roadmap_eval_edges_dev(c, &rm->params, d_s12, d_s12 + na * 7, at, evalid.data(), einterp.data(),
                                       ecost.data(), rm->params.construction == 2));
     }
     auto usable = [&](size_t r) {
@@ -821,7 +789,7 @@ int artp_roadmap_solve_many(artp_roadmap* rm, const double* start_se3, const dou
     for (size_t i = 0; i < nfg; ++i)
       for (size_t t = 0; t < lg[far_row[i]].size(); ++t) aw[i * k + t] = usable(arow[ai++]);
     // 7. the lazy rounds on the device
-    MANY_TRY(many_device_solve(rm, start_se3, goals, far_goals, an, aw, snb, sw, status, cost, &paths, stats));
+    ARTP_TRY(many_device_solve(rm, start_se3, goals, far_goals, an, aw, snb, sw, status, cost, &paths, stats));
   }
   // 8. offsets and states
   std::vector<uint64_t> off(ng + 1, 0);

@@ -20,6 +20,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <vector>
 
 namespace artp {
@@ -510,6 +511,7 @@ struct artp_tree {
   uint64_t first_checked = 0;    // first motions checked (host count; the near ones are counted on the device)
   double stage_us[artp::TREE_NSTAGES] = {};
   hipEvent_t ev[artp::TREE_NSTAGES + 1] = {};
+  DeviceScratch mem;             // owns every d_ pointer above
 };
 
 namespace {
@@ -519,15 +521,8 @@ inline int tree_k(double rewire_factor, size_t n) {
   return (int)std::ceil(rewire_factor * (2.718281828459045 + 2.718281828459045 / 6.0) * std::log((double)n + 1.0));
 }
 
+// what artp_tree::mem does not own: the pinned host block and the events
 void tree_free(artp_tree* t) {
-  for (void* p : {(void*)t->d_verts, (void*)t->d_cost, (void*)t->d_ecost, (void*)t->d_parent, (void*)t->d_born,
-                  (void*)t->d_pruned, (void*)t->d_sg, (void*)t->d_samp, (void*)t->d_xnew, (void*)t->d_nd,
-                  (void*)t->d_xs, (void*)t->d_c0, (void*)t->d_s1, (void*)t->d_s2, (void*)t->d_nn, (void*)t->d_idx1,
-                  (void*)t->d_idx2, (void*)t->d_rank, (void*)t->d_par0, (void*)t->d_near, (void*)t->d_alive,
-                  (void*)t->d_valid1, (void*)t->d_validk, (void*)t->d_cnt, (void*)t->d_counters, (void*)t->d_err,
-                  (void*)t->d_best_bits, (void*)t->d_best_id, (void*)t->d_pred_w, (void*)t->d_hops, (void*)t->d_lu, (void*)t->d_lv,
-                  (void*)t->d_lbatch, (void*)t->d_lvalid, (void*)t->d_lcuv, (void*)t->d_lcvu})
-    if (p) (void)hipFree(p);
   if (t->h_cnt) (void)hipHostFree(t->h_cnt);
   for (hipEvent_t& e : t->ev)
     if (e) (void)hipEventDestroy(e);
@@ -536,48 +531,48 @@ void tree_free(artp_tree* t) {
 // make room for `need` log entries (doubling; the old entries are copied)
 int tree_log_reserve(artp_tree* t, size_t need) {
   artp_ctx* c = t->ctx;
-  auto cleanup = [] {};
   if (need <= t->log_cap) return ARTP_OK;
   size_t cap = t->log_cap ? t->log_cap : (1u << 16);
   while (cap < need) cap *= 2;
   uint32_t *lu = nullptr, *lv = nullptr, *lb = nullptr;
   uint8_t* lval = nullptr;
   double *cuv = nullptr, *cvu = nullptr;
-  RM_HIP(hipMalloc(reinterpret_cast<void**>(&lu), cap * 4));
-  RM_HIP(hipMalloc(reinterpret_cast<void**>(&lv), cap * 4));
-  RM_HIP(hipMalloc(reinterpret_cast<void**>(&lb), cap * 4));
-  RM_HIP(hipMalloc(reinterpret_cast<void**>(&lval), cap));
-  RM_HIP(hipMalloc(reinterpret_cast<void**>(&cuv), cap * 8));
-  RM_HIP(hipMalloc(reinterpret_cast<void**>(&cvu), cap * 8));
+  DeviceScratch S;  // the new six until the copy is through
+  HIP_TRY(c, S.alloc(&lu, cap));
+  HIP_TRY(c, S.alloc(&lv, cap));
+  HIP_TRY(c, S.alloc(&lb, cap));
+  HIP_TRY(c, S.alloc(&lval, cap));
+  HIP_TRY(c, S.alloc(&cuv, cap));
+  HIP_TRY(c, S.alloc(&cvu, cap));
   if (t->log_n) {
     const size_t m = t->log_n;
-    RM_HIP(hipMemcpyAsync(lu, t->d_lu, m * 4, hipMemcpyDeviceToDevice, c->stream));
-    RM_HIP(hipMemcpyAsync(lv, t->d_lv, m * 4, hipMemcpyDeviceToDevice, c->stream));
-    RM_HIP(hipMemcpyAsync(lb, t->d_lbatch, m * 4, hipMemcpyDeviceToDevice, c->stream));
-    RM_HIP(hipMemcpyAsync(lval, t->d_lvalid, m, hipMemcpyDeviceToDevice, c->stream));
-    RM_HIP(hipMemcpyAsync(cuv, t->d_lcuv, m * 8, hipMemcpyDeviceToDevice, c->stream));
-    RM_HIP(hipMemcpyAsync(cvu, t->d_lcvu, m * 8, hipMemcpyDeviceToDevice, c->stream));
-    RM_HIP(hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpyAsync(lu, t->d_lu, m * 4, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(lv, t->d_lv, m * 4, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(lb, t->d_lbatch, m * 4, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(lval, t->d_lvalid, m, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(cuv, t->d_lcuv, m * 8, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(cvu, t->d_lcvu, m * 8, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
   }
   for (void* p : {(void*)t->d_lu, (void*)t->d_lv, (void*)t->d_lbatch, (void*)t->d_lvalid, (void*)t->d_lcuv, (void*)t->d_lcvu})
-    if (p) (void)hipFree(p);
-  t->d_lu = lu;
-  t->d_lv = lv;
-  t->d_lbatch = lb;
-  t->d_lvalid = lval;
-  t->d_lcuv = cuv;
-  t->d_lcvu = cvu;
+    t->mem.release(p);
+  t->d_lu = t->mem.adopt(S.take(lu));
+  t->d_lv = t->mem.adopt(S.take(lv));
+  t->d_lbatch = t->mem.adopt(S.take(lb));
+  t->d_lvalid = t->mem.adopt(S.take(lval));
+  t->d_lcuv = t->mem.adopt(S.take(cuv));
+  t->d_lcvu = t->mem.adopt(S.take(cvu));
   t->log_cap = cap;
   return ARTP_OK;
 }
 
-inline unsigned tree_blocks(size_t n, unsigned bs = 256) { return (unsigned)((n + bs - 1) / bs); }
+// blocks of bs threads over n items, at least one (also what roadmap_many.h launches with)
+inline unsigned tree_blocks(size_t n, unsigned bs = 256) { return (unsigned)std::max<size_t>((n + bs - 1) / bs, 1); }
 
 // One batch (stages 1-10).  *stop = true when the tree cannot take another vertex.
 int tree_batch(artp_tree* t, bool* stop) {
   using namespace artp;
   artp_ctx* c = t->ctx;
-  auto cleanup = [] {};
   hipStream_t st = c->stream;
   const artp_tree_params& p = t->params;
   const int B = (int)p.batch;
@@ -586,50 +581,50 @@ int tree_batch(artp_tree* t, bool* stop) {
   const PathLengthParams pl{p.objective == 1, p.max_lon_vel, p.max_lat_vel, p.max_ang_vel};
   const bool prof = p.profile != 0;
   auto mark = [&](int i) -> int {
-    if (prof) RM_HIP(hipEventRecord(t->ev[i], st));
+    if (prof) HIP_TRY(c, hipEventRecord(t->ev[i], st));
     return ARTP_OK;
   };
   // 1. sample (slot i = stream index first_index + batch * B + i); the goal takes slot 0 while it is not a vertex
   //    (with B == 1: every 20th batch, OMPL's 5 % goal bias)
-  RM_TRY(mark(0));
-  RM_TRY(artp_sample_states_dev(c, p.seed, p.first_index + (uint64_t)batch * B, (size_t)B, t->d_samp));
+  ARTP_TRY(mark(0));
+  ARTP_TRY(artp_sample_states_dev(c, p.seed, p.first_index + (uint64_t)batch * B, (size_t)B, t->d_samp));
   const bool goal_slot = t->goal_id == TREE_NONE && (B > 1 || batch % 20 == 0);
   if (goal_slot)
-    RM_HIP(hipMemcpyAsync(t->d_samp, t->d_sg + 7, 7 * sizeof(double), hipMemcpyDeviceToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(t->d_samp, t->d_sg + 7, 7 * sizeof(double), hipMemcpyDeviceToDevice, st));
   // 2. nearest unpruned pre-batch vertex
-  RM_TRY(mark(1));
+  ARTP_TRY(mark(1));
   hipLaunchKernelGGL(tree_knn_kernel, dim3(tree_blocks(B, 4)), dim3(256), 0, st, t->d_verts, (int)n_pre,
                      (const uint8_t*)t->d_pruned, (const double*)t->d_samp, B, 1, t->d_nn, t->d_nd);
   // 2b / 3. steer, informed rejection, compaction of the survivors (host read 1)
-  RM_TRY(mark(2));
+  ARTP_TRY(mark(2));
   hipLaunchKernelGGL(tree_steer_kernel, dim3(tree_blocks(B)), dim3(256), 0, st, (const double*)t->d_verts,
                      (const double*)t->d_samp, (const uint32_t*)t->d_nn, (const double*)t->d_nd, B, t->range,
                      p.variant == 1 ? 1 : 0, (const double*)t->d_sg, (const double*)t->d_cost, t->goal_id, p.max_lon_vel,
                      t->d_xnew, t->d_alive, t->d_cnt + 2);
   hipLaunchKernelGGL(tree_compact_kernel, dim3(1), dim3(1024), 0, st, (const uint8_t*)t->d_alive, B, t->d_idx1,
                      (uint32_t*)nullptr, (const uint32_t*)nullptr, t->d_cnt);
-  RM_HIP(hipMemcpyAsync(t->h_cnt, t->d_cnt, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-  RM_HIP(hipStreamSynchronize(st));
+  HIP_TRY(c, hipMemcpyAsync(t->h_cnt, t->d_cnt, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipStreamSynchronize(st));
   const int m1 = (int)t->h_cnt[0];
   // 4. first motion checkMotion(nearest, x_new) (host read 2: survivors, and whether slot 0 -- the goal -- is one)
-  RM_TRY(mark(3));
+  ARTP_TRY(mark(3));
   int m2 = 0;
   uint32_t first_slot = TREE_NONE;
   if (m1) {
     hipLaunchKernelGGL(tree_gather_first_kernel, dim3(tree_blocks(m1)), dim3(256), 0, st, (const double*)t->d_verts,
                        (const double*)t->d_xnew, (const uint32_t*)t->d_nn, (const uint32_t*)t->d_idx1, m1, t->d_s1, t->d_s2);
-    RM_TRY(artp_check_motions_dev(c, t->d_s1, t->d_s2, (size_t)m1, t->d_valid1));
+    ARTP_TRY(artp_check_motions_dev(c, t->d_s1, t->d_s2, (size_t)m1, t->d_valid1));
     hipLaunchKernelGGL(tree_compact_kernel, dim3(1), dim3(1024), 0, st, (const uint8_t*)t->d_valid1, m1, t->d_idx2,
                        t->d_rank, (const uint32_t*)t->d_idx1, t->d_cnt);
-    RM_HIP(hipMemcpyAsync(t->h_cnt, t->d_cnt, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    RM_HIP(hipStreamSynchronize(st));
+    HIP_TRY(c, hipMemcpyAsync(t->h_cnt, t->d_cnt, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
     m2 = (int)std::min<uint32_t>(t->h_cnt[0], t->cap - n_pre);
     first_slot = t->h_cnt[2] ? t->h_cnt[1] : TREE_NONE;  // a goal steered short of the goal is not the goal
   }
   t->first_checked += (uint64_t)m1;
   const int k = std::max(1, std::min(tree_k(p.rewire_factor, n_pre), t->kmax));
   const size_t log0 = t->log_n, n_log = (size_t)m1 + (size_t)m2 * k;
-  RM_TRY(tree_log_reserve(t, log0 + n_log));
+  ARTP_TRY(tree_log_reserve(t, log0 + n_log));
   if (m1)
     hipLaunchKernelGGL(tree_first_log_kernel, dim3(tree_blocks(m1)), dim3(256), 0, st, pl, (const double*)t->d_verts,
                        (const double*)t->d_xnew, (const uint32_t*)t->d_nn, (const uint32_t*)t->d_idx1,
@@ -638,16 +633,16 @@ int tree_batch(artp_tree* t, bool* stop) {
                        t->d_lcuv + log0, t->d_lcvu + log0);
   if (m2) {
     // 5. near set of every survivor and its motions
-    RM_TRY(mark(4));
+    ARTP_TRY(mark(4));
     hipLaunchKernelGGL(tree_knn_kernel, dim3(tree_blocks(m2, 4)), dim3(256), 0, st, t->d_verts, (int)n_pre,
                        (const uint8_t*)t->d_pruned, (const double*)t->d_xs, m2, k, t->d_near, (double*)nullptr);
-    RM_TRY(mark(5));
+    ARTP_TRY(mark(5));
     hipLaunchKernelGGL(tree_near_pairs_kernel, dim3(tree_blocks((size_t)m2 * k)), dim3(256), 0, st,
                        (const double*)t->d_verts, (const double*)t->d_xs, (const uint32_t*)t->d_par0,
                        (const uint32_t*)t->d_near, m2, k, t->d_s1, t->d_s2);
-    RM_TRY(artp_check_motions_dev(c, t->d_s1, t->d_s2, (size_t)m2 * k, t->d_validk));
+    ARTP_TRY(artp_check_motions_dev(c, t->d_s1, t->d_s2, (size_t)m2 * k, t->d_validk));
     // 6. parent choice, new vertices n_pre .. n_pre + m2 - 1
-    RM_TRY(mark(6));
+    ARTP_TRY(mark(6));
     const size_t ln = log0 + (size_t)m1;
     hipLaunchKernelGGL(tree_parent_kernel, dim3(tree_blocks(m2)), dim3(256), 0, st, pl, t->d_verts, t->d_cost,
                        t->d_parent, t->d_ecost, t->d_born, t->d_pruned, (const double*)t->d_xs,
@@ -655,15 +650,15 @@ int tree_batch(artp_tree* t, bool* stop) {
                        (const uint8_t*)t->d_validk, m2, k, n_pre, batch, t->d_lu + ln, t->d_lv + ln,
                        t->d_lvalid + ln, t->d_lbatch + ln, t->d_lcuv + ln, t->d_lcvu + ln, t->d_counters);
   } else {
-    for (int i = 4; i < 7; ++i) RM_TRY(mark(i));
+    for (int i = 4; i < 7; ++i) ARTP_TRY(mark(i));
   }
   t->log_n = log0 + n_log;
   const uint32_t n_now = n_pre + (uint32_t)m2;
   // 7. rewiring (rrt_star, inf_rrt_star) over this batch's motions
-  RM_TRY(mark(7));
+  ARTP_TRY(mark(7));
   if (p.variant != 2 && m2) {
-    RM_HIP(hipMemsetAsync(t->d_best_bits, 0xff, (size_t)n_pre * 8, st));
-    RM_HIP(hipMemsetAsync(t->d_best_id, 0xff, (size_t)n_pre * 4, st));
+    HIP_TRY(c, hipMemsetAsync(t->d_best_bits, 0xff, (size_t)n_pre * 8, st));
+    HIP_TRY(c, hipMemsetAsync(t->d_best_id, 0xff, (size_t)n_pre * 4, st));
     for (int phase = 0; phase < 3; ++phase)
       hipLaunchKernelGGL(tree_rewire_kernel, dim3(tree_blocks(n_log)), dim3(256), 0, st, phase,
                          (const uint32_t*)t->d_lu + log0, (const uint32_t*)t->d_lv + log0,
@@ -672,15 +667,15 @@ int tree_batch(artp_tree* t, bool* stop) {
                          t->d_counters + 1);
   }
   // 9. rrt_sharp: shortest paths over the whole graph of valid checked motions
-  RM_TRY(mark(8));
+  ARTP_TRY(mark(8));
   if (p.variant == 2 && m2) {
-    RM_HIP(hipMemcpyAsync(t->d_best_bits, t->d_cost, (size_t)n_now * 8, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(t->d_best_bits, t->d_cost, (size_t)n_now * 8, hipMemcpyDeviceToDevice, st));
     hipLaunchKernelGGL(tree_sssp_kernel, dim3(1), dim3(1024), 0, st, (const uint32_t*)t->d_lu, (const uint32_t*)t->d_lv,
                        (const uint8_t*)t->d_lvalid, (const double*)t->d_lcuv, (const double*)t->d_lcvu, t->log_n,
                        t->d_best_bits, n_now + 2u, t->d_err);
-    RM_HIP(hipMemsetAsync(t->d_best_id, 0xff, (size_t)n_now * 4, st));
-    RM_HIP(hipMemsetAsync(t->d_hops, 0xff, (size_t)n_now * 4, st));
-    RM_HIP(hipMemsetAsync(t->d_hops, 0, 4, st));
+    HIP_TRY(c, hipMemsetAsync(t->d_best_id, 0xff, (size_t)n_now * 4, st));
+    HIP_TRY(c, hipMemsetAsync(t->d_hops, 0xff, (size_t)n_now * 4, st));
+    HIP_TRY(c, hipMemsetAsync(t->d_hops, 0, 4, st));
     hipLaunchKernelGGL(tree_hops_kernel, dim3(1), dim3(1024), 0, st, (const uint32_t*)t->d_lu, (const uint32_t*)t->d_lv,
                        (const uint8_t*)t->d_lvalid, (const double*)t->d_lcuv, (const double*)t->d_lcvu, t->log_n,
                        (const unsigned long long*)t->d_best_bits, t->d_hops, n_now + 2u, t->d_err);
@@ -694,11 +689,11 @@ int tree_batch(artp_tree* t, bool* stop) {
                        (const double*)t->d_pred_w, n_now, n_pre, t->d_parent, t->d_ecost, t->d_counters + 1);
   }
   // 8. cost-to-come: the left fold along every parent chain
-  RM_TRY(mark(9));
+  ARTP_TRY(mark(9));
   if (m2)
     hipLaunchKernelGGL(tree_cost_fold_kernel, dim3(tree_blocks(n_now)), dim3(256), 0, st, (const uint32_t*)t->d_parent,
                        (const double*)t->d_ecost, n_now, t->d_cost, t->d_err);
-  RM_HIP(hipGetLastError());
+  HIP_TRY(c, hipGetLastError());
   t->n = n_now;
   ++t->batches;
   if (goal_slot && first_slot == 0 && m2 > 0) {
@@ -709,12 +704,12 @@ int tree_batch(artp_tree* t, bool* stop) {
   if (p.variant == 1 && t->goal_id != TREE_NONE)
     hipLaunchKernelGGL(tree_prune_kernel, dim3(tree_blocks(n_now)), dim3(256), 0, st, (const double*)t->d_verts, n_now,
                        (const double*)t->d_sg, (const double*)t->d_cost, t->goal_id, p.max_lon_vel, t->d_pruned);
-  RM_TRY(mark(TREE_NSTAGES));
+  ARTP_TRY(mark(TREE_NSTAGES));
   if (prof) {
-    RM_HIP(hipEventSynchronize(t->ev[TREE_NSTAGES]));
+    HIP_TRY(c, hipEventSynchronize(t->ev[TREE_NSTAGES]));
     for (int i = 0; i < TREE_NSTAGES; ++i) {
       float ms = 0.0f;
-      RM_HIP(hipEventElapsedTime(&ms, t->ev[i], t->ev[i + 1]));
+      HIP_TRY(c, hipEventElapsedTime(&ms, t->ev[i], t->ev[i + 1]));
       t->stage_us[i] += 1000.0 * ms;
     }
   }
@@ -724,10 +719,9 @@ int tree_batch(artp_tree* t, bool* stop) {
 
 int tree_check_err(artp_tree* t) {
   artp_ctx* c = t->ctx;
-  auto cleanup = [] {};
   int err = 0;
-  RM_HIP(hipMemcpyAsync(&err, t->d_err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  RM_HIP(hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipMemcpyAsync(&err, t->d_err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
   if (err) {
     c->last_error = err == 1 ? "tree: a parent chain does not reach the root" : "tree: shortest-path sweeps did not settle";
     return ARTP_ERR_INVALID_ARG;
@@ -777,19 +771,18 @@ int artp_tree_create(artp_ctx* c, const artp_tree_params* prm, const double* sta
     return ARTP_ERR_INVALID_ARG;
   }
   if (!c->have_field[0] || !c->have_field[1] || !c->have_sampler || !c->have_z) return ARTP_ERR_NO_MAP;
-  artp_tree* t = new artp_tree();
+  std::unique_ptr<artp_tree, void (*)(artp_tree*)> owner(new artp_tree(), artp_tree_destroy);
+  artp_tree* t = owner.get();
   t->ctx = c;
   t->params = *prm;
   std::memcpy(t->sg, start7, 7 * sizeof(double));
   std::memcpy(t->sg + 7, goal7, 7 * sizeof(double));
-  auto cleanup = [&]() { artp_tree_destroy(t); };
-  RM_HIP(hipSetDevice(c->device));
+  HIP_TRY(c, hipSetDevice(c->device));
   {  // start and goal must be valid states (OMPL: INVALID_START / INVALID_GOAL)
     uint8_t ok[2] = {0, 0};
-    RM_TRY(artp_validate_states(c, t->sg, 2, ok, nullptr));
+    ARTP_TRY(artp_validate_states(c, t->sg, 2, ok, nullptr));
     if (!ok[0] || !ok[1]) {
       c->last_error = !ok[0] ? "start state is not valid" : "goal state is not valid";
-      cleanup();
       return ARTP_ERR_INVALID_ARG;
     }
   }
@@ -801,51 +794,51 @@ int artp_tree_create(artp_ctx* c, const artp_tree_params* prm, const double* sta
   t->cap = prm->max_vertices;
   t->kmax = std::max(1, tree_k(prm->rewire_factor, t->cap));
   const size_t cap = t->cap, B = prm->batch, BK = B * (size_t)t->kmax;
-  RM_HIP(hipMalloc(reinterpret_cast<void**>(&t->d_verts), cap * 7 * 8));
-  RM_HIP(hipMalloc(reinterpret_cast<void**>(&t->d_cost), cap * 8));
-  RM_HIP(hipMalloc(reinterpret_cast<void**>(&t->d_ecost), cap * 8));
-  RM_HIP(hipMalloc(reinterpret_cast<void**>(&t->d_parent), cap * 4));
-  RM_HIP(hipMalloc(reinterpret_cast<void**>(&t->d_born), cap * 4));
-  RM_HIP(hipMalloc(reinterpret_cast<void**>(&t->d_pruned), cap));
-  RM_HIP(hipMalloc(reinterpret_cast<void**>(&t->d_best_bits), cap * 8));
-  RM_HIP(hipMalloc(reinterpret_cast<void**>(&t->d_best_id), cap * 4));
-  RM_HIP(hipMalloc(reinterpret_cast<void**>(&t->d_pred_w), cap * 8));
-  RM_HIP(hipMalloc(reinterpret_cast<void**>(&t->d_hops), cap * 4));
-  RM_HIP(hipMalloc(reinterpret_cast<void**>(&t->d_sg), 14 * 8));
-  RM_HIP(hipMalloc(reinterpret_cast<void**>(&t->d_samp), B * 7 * 8));
-  RM_HIP(hipMalloc(reinterpret_cast<void**>(&t->d_xnew), B * 7 * 8));
-  RM_HIP(hipMalloc(reinterpret_cast<void**>(&t->d_xs), B * 7 * 8));
-  RM_HIP(hipMalloc(reinterpret_cast<void**>(&t->d_nd), B * 8));
-  RM_HIP(hipMalloc(reinterpret_cast<void**>(&t->d_c0), B * 8));
-  RM_HIP(hipMalloc(reinterpret_cast<void**>(&t->d_s1), BK * 7 * 8));
-  RM_HIP(hipMalloc(reinterpret_cast<void**>(&t->d_s2), BK * 7 * 8));
-  RM_HIP(hipMalloc(reinterpret_cast<void**>(&t->d_nn), B * 4));
-  RM_HIP(hipMalloc(reinterpret_cast<void**>(&t->d_idx1), B * 4));
-  RM_HIP(hipMalloc(reinterpret_cast<void**>(&t->d_idx2), B * 4));
-  RM_HIP(hipMalloc(reinterpret_cast<void**>(&t->d_rank), B * 4));
-  RM_HIP(hipMalloc(reinterpret_cast<void**>(&t->d_par0), B * 4));
-  RM_HIP(hipMalloc(reinterpret_cast<void**>(&t->d_near), BK * 4));
-  RM_HIP(hipMalloc(reinterpret_cast<void**>(&t->d_alive), B));
-  RM_HIP(hipMalloc(reinterpret_cast<void**>(&t->d_valid1), B));
-  RM_HIP(hipMalloc(reinterpret_cast<void**>(&t->d_validk), BK));
-  RM_HIP(hipMalloc(reinterpret_cast<void**>(&t->d_cnt), 4 * 4));
-  RM_HIP(hipHostMalloc(reinterpret_cast<void**>(&t->h_cnt), 4 * 4, hipHostMallocDefault));
-  RM_HIP(hipMalloc(reinterpret_cast<void**>(&t->d_counters), 2 * 8));
-  RM_HIP(hipMalloc(reinterpret_cast<void**>(&t->d_err), sizeof(int)));
+  HIP_TRY(c, t->mem.alloc(&t->d_verts, cap * 7));
+  HIP_TRY(c, t->mem.alloc(&t->d_cost, cap));
+  HIP_TRY(c, t->mem.alloc(&t->d_ecost, cap));
+  HIP_TRY(c, t->mem.alloc(&t->d_parent, cap));
+  HIP_TRY(c, t->mem.alloc(&t->d_born, cap));
+  HIP_TRY(c, t->mem.alloc(&t->d_pruned, cap));
+  HIP_TRY(c, t->mem.alloc(&t->d_best_bits, cap));
+  HIP_TRY(c, t->mem.alloc(&t->d_best_id, cap));
+  HIP_TRY(c, t->mem.alloc(&t->d_pred_w, cap));
+  HIP_TRY(c, t->mem.alloc(&t->d_hops, cap));
+  HIP_TRY(c, t->mem.alloc(&t->d_sg, 14));
+  HIP_TRY(c, t->mem.alloc(&t->d_samp, B * 7));
+  HIP_TRY(c, t->mem.alloc(&t->d_xnew, B * 7));
+  HIP_TRY(c, t->mem.alloc(&t->d_xs, B * 7));
+  HIP_TRY(c, t->mem.alloc(&t->d_nd, B));
+  HIP_TRY(c, t->mem.alloc(&t->d_c0, B));
+  HIP_TRY(c, t->mem.alloc(&t->d_s1, BK * 7));
+  HIP_TRY(c, t->mem.alloc(&t->d_s2, BK * 7));
+  HIP_TRY(c, t->mem.alloc(&t->d_nn, B));
+  HIP_TRY(c, t->mem.alloc(&t->d_idx1, B));
+  HIP_TRY(c, t->mem.alloc(&t->d_idx2, B));
+  HIP_TRY(c, t->mem.alloc(&t->d_rank, B));
+  HIP_TRY(c, t->mem.alloc(&t->d_par0, B));
+  HIP_TRY(c, t->mem.alloc(&t->d_near, BK));
+  HIP_TRY(c, t->mem.alloc(&t->d_alive, B));
+  HIP_TRY(c, t->mem.alloc(&t->d_valid1, B));
+  HIP_TRY(c, t->mem.alloc(&t->d_validk, BK));
+  HIP_TRY(c, t->mem.alloc(&t->d_cnt, 4));
+  HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&t->h_cnt), 4 * 4, hipHostMallocDefault));
+  HIP_TRY(c, t->mem.alloc(&t->d_counters, 2));
+  HIP_TRY(c, t->mem.alloc(&t->d_err, 1));
   if (prm->profile)
-    for (hipEvent_t& e : t->ev) RM_HIP(hipEventCreate(&e));
+    for (hipEvent_t& e : t->ev) HIP_TRY(c, hipEventCreate(&e));
   hipStream_t st = c->stream;
-  RM_HIP(hipMemcpyAsync(t->d_sg, t->sg, 14 * 8, hipMemcpyHostToDevice, st));
-  RM_HIP(hipMemcpyAsync(t->d_verts, t->sg, 7 * 8, hipMemcpyHostToDevice, st));
-  RM_HIP(hipMemsetAsync(t->d_cost, 0, 8, st));
-  RM_HIP(hipMemsetAsync(t->d_ecost, 0, 8, st));
-  RM_HIP(hipMemsetAsync(t->d_parent, 0xff, 4, st));
-  RM_HIP(hipMemsetAsync(t->d_born, 0, 4, st));
-  RM_HIP(hipMemsetAsync(t->d_pruned, 0, cap, st));
-  RM_HIP(hipMemsetAsync(t->d_counters, 0, 2 * 8, st));
-  RM_HIP(hipMemsetAsync(t->d_err, 0, sizeof(int), st));
-  RM_HIP(hipStreamSynchronize(st));
-  *out = t;
+  HIP_TRY(c, hipMemcpyAsync(t->d_sg, t->sg, 14 * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemcpyAsync(t->d_verts, t->sg, 7 * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemsetAsync(t->d_cost, 0, 8, st));
+  HIP_TRY(c, hipMemsetAsync(t->d_ecost, 0, 8, st));
+  HIP_TRY(c, hipMemsetAsync(t->d_parent, 0xff, 4, st));
+  HIP_TRY(c, hipMemsetAsync(t->d_born, 0, 4, st));
+  HIP_TRY(c, hipMemsetAsync(t->d_pruned, 0, cap, st));
+  HIP_TRY(c, hipMemsetAsync(t->d_counters, 0, 2 * 8, st));
+  HIP_TRY(c, hipMemsetAsync(t->d_err, 0, sizeof(int), st));
+  HIP_TRY(c, hipStreamSynchronize(st));
+  *out = owner.release();
   return ARTP_OK;
 }
 
@@ -853,8 +846,7 @@ int artp_tree_grow(artp_tree* t, uint64_t n_batches, uint64_t out[2]) {
   if (!t) return ARTP_ERR_INVALID_ARG;
   artp_ctx* c = t->ctx;
   std::lock_guard<std::recursive_mutex> lock(c->mu);
-  auto cleanup = [] {};
-  RM_HIP(hipSetDevice(c->device));
+  HIP_TRY(c, hipSetDevice(c->device));
   const artp_tree_params& p = t->params;
   if (!n_batches && !p.max_batches && !(p.plan_time > 0.0)) {
     c->last_error = "artp_tree_grow needs a budget: n_batches, max_batches or plan_time";
@@ -868,10 +860,10 @@ int artp_tree_grow(artp_tree* t, uint64_t n_batches, uint64_t out[2]) {
     if (p.max_batches && t->batches >= p.max_batches) break;
     if (p.plan_time > 0.0 && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() >= p.plan_time)
       break;
-    RM_TRY(tree_batch(t, &stop));
+    ARTP_TRY(tree_batch(t, &stop));
     ++ran;
   }
-  RM_TRY(tree_check_err(t));
+  ARTP_TRY(tree_check_err(t));
   if (out) {
     out[0] = ran;
     out[1] = t->n;
@@ -883,12 +875,11 @@ int artp_tree_stats(const artp_tree* t, uint64_t out[8]) {
   if (!t || !out) return ARTP_ERR_INVALID_ARG;
   artp_ctx* c = t->ctx;
   std::lock_guard<std::recursive_mutex> lock(c->mu);
-  auto cleanup = [] {};
   unsigned long long cnt[2] = {0, 0};
   std::vector<uint8_t> pr(t->n);
-  RM_HIP(hipMemcpyAsync(cnt, t->d_counters, sizeof(cnt), hipMemcpyDeviceToHost, c->stream));
-  RM_HIP(hipMemcpyAsync(pr.data(), t->d_pruned, t->n, hipMemcpyDeviceToHost, c->stream));
-  RM_HIP(hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipMemcpyAsync(cnt, t->d_counters, sizeof(cnt), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(pr.data(), t->d_pruned, t->n, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
   uint64_t np = 0;
   for (uint8_t b : pr) np += b ? 1 : 0;
   out[0] = t->n;
@@ -907,16 +898,15 @@ int artp_tree_export(const artp_tree* t, double* verts, uint32_t* parent, double
   if (!t) return ARTP_ERR_INVALID_ARG;
   artp_ctx* c = t->ctx;
   std::lock_guard<std::recursive_mutex> lock(c->mu);
-  auto cleanup = [] {};
   const size_t n = t->n;
   hipStream_t st = c->stream;
-  if (verts) RM_HIP(hipMemcpyAsync(verts, t->d_verts, n * 7 * 8, hipMemcpyDeviceToHost, st));
-  if (parent) RM_HIP(hipMemcpyAsync(parent, t->d_parent, n * 4, hipMemcpyDeviceToHost, st));
-  if (cost) RM_HIP(hipMemcpyAsync(cost, t->d_cost, n * 8, hipMemcpyDeviceToHost, st));
-  if (edge_cost) RM_HIP(hipMemcpyAsync(edge_cost, t->d_ecost, n * 8, hipMemcpyDeviceToHost, st));
-  if (born_batch) RM_HIP(hipMemcpyAsync(born_batch, t->d_born, n * 4, hipMemcpyDeviceToHost, st));
-  if (pruned) RM_HIP(hipMemcpyAsync(pruned, t->d_pruned, n, hipMemcpyDeviceToHost, st));
-  RM_HIP(hipStreamSynchronize(st));
+  if (verts) HIP_TRY(c, hipMemcpyAsync(verts, t->d_verts, n * 7 * 8, hipMemcpyDeviceToHost, st));
+  if (parent) HIP_TRY(c, hipMemcpyAsync(parent, t->d_parent, n * 4, hipMemcpyDeviceToHost, st));
+  if (cost) HIP_TRY(c, hipMemcpyAsync(cost, t->d_cost, n * 8, hipMemcpyDeviceToHost, st));
+  if (edge_cost) HIP_TRY(c, hipMemcpyAsync(edge_cost, t->d_ecost, n * 8, hipMemcpyDeviceToHost, st));
+  if (born_batch) HIP_TRY(c, hipMemcpyAsync(born_batch, t->d_born, n * 4, hipMemcpyDeviceToHost, st));
+  if (pruned) HIP_TRY(c, hipMemcpyAsync(pruned, t->d_pruned, n, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipStreamSynchronize(st));
   return ARTP_OK;
 }
 
@@ -925,17 +915,16 @@ int artp_tree_export_checked(const artp_tree* t, uint32_t* u, uint32_t* v, uint8
   if (!t || !n_out) return ARTP_ERR_INVALID_ARG;
   artp_ctx* c = t->ctx;
   std::lock_guard<std::recursive_mutex> lock(c->mu);
-  auto cleanup = [] {};
   const size_t m = t->log_n;
   std::vector<uint32_t> lu(m), lv(m), lb(m);
   std::vector<uint8_t> lval(m);
   hipStream_t st = c->stream;
   if (m) {
-    RM_HIP(hipMemcpyAsync(lu.data(), t->d_lu, m * 4, hipMemcpyDeviceToHost, st));
-    RM_HIP(hipMemcpyAsync(lv.data(), t->d_lv, m * 4, hipMemcpyDeviceToHost, st));
-    RM_HIP(hipMemcpyAsync(lb.data(), t->d_lbatch, m * 4, hipMemcpyDeviceToHost, st));
-    RM_HIP(hipMemcpyAsync(lval.data(), t->d_lvalid, m, hipMemcpyDeviceToHost, st));
-    RM_HIP(hipStreamSynchronize(st));
+    HIP_TRY(c, hipMemcpyAsync(lu.data(), t->d_lu, m * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(lv.data(), t->d_lv, m * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(lb.data(), t->d_lbatch, m * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(lval.data(), t->d_lvalid, m, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
   }
   size_t k = 0;
   for (size_t e = 0; e < m; ++e) {
@@ -960,17 +949,16 @@ int artp_tree_solve(const artp_tree* t, double* path_se3, size_t cap_states, siz
   if (!t || !n_path) return ARTP_ERR_INVALID_ARG;
   artp_ctx* c = t->ctx;
   std::lock_guard<std::recursive_mutex> lock(c->mu);
-  auto cleanup = [] {};
   *n_path = 0;
   if (cost) *cost = INFINITY;
   if (t->goal_id == artp::TREE_NONE) return ARTP_OK;
   const size_t n = t->n;
   std::vector<uint32_t> parent(n);
   std::vector<double> verts(n * 7), costs(n);
-  RM_HIP(hipMemcpyAsync(parent.data(), t->d_parent, n * 4, hipMemcpyDeviceToHost, c->stream));
-  RM_HIP(hipMemcpyAsync(verts.data(), t->d_verts, n * 7 * 8, hipMemcpyDeviceToHost, c->stream));
-  RM_HIP(hipMemcpyAsync(costs.data(), t->d_cost, n * 8, hipMemcpyDeviceToHost, c->stream));
-  RM_HIP(hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipMemcpyAsync(parent.data(), t->d_parent, n * 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(verts.data(), t->d_verts, n * 7 * 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(costs.data(), t->d_cost, n * 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
   std::vector<uint32_t> chain;
   for (uint32_t v = t->goal_id;; v = parent[v]) {
     chain.push_back(v);

@@ -1,0 +1,180 @@
+// device_scratch_test.cpp -- csrc/device_scratch.h on the CPU, over the counting hipMalloc / hipFree of
+// tests/fake_include/hip_stub.  Built with -fsanitize=address,undefined and run by tests/test_device_scratch.py:
+// a leak, a double free or a use after free ends the program with a non-zero status, like a failed CHECK.
+#include "../../include/artp_c.h"
+#include "../../art_planner_amd/csrc/device_scratch.h"
+
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+
+struct FakeCtx {
+  std::string last_error;
+};
+
+static int failures = 0;
+#define CHECK(cond)                                                  \
+  do {                                                               \
+    if (!(cond)) {                                                   \
+      std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond);  \
+      ++failures;                                                    \
+    }                                                                \
+  } while (0)
+
+// The owner of an object's buffers and the six it holds: artp_tree's log in small.
+struct Log {
+  uint32_t *lu = nullptr, *lv = nullptr, *lb = nullptr;
+  uint8_t* lval = nullptr;
+  double *cuv = nullptr, *cvu = nullptr;
+  size_t n = 0, cap = 0;
+  DeviceScratch mem;
+};
+
+// tree_log_reserve's body: six new buffers in a local owner, copy, release the old six, hand the new six over
+static int log_reserve(FakeCtx* c, Log* t, size_t cap) {
+  uint32_t *lu = nullptr, *lv = nullptr, *lb = nullptr;
+  uint8_t* lval = nullptr;
+  double *cuv = nullptr, *cvu = nullptr;
+  DeviceScratch S;
+  HIP_TRY(c, S.alloc(&lu, cap));
+  HIP_TRY(c, S.alloc(&lv, cap));
+  HIP_TRY(c, S.alloc(&lb, cap));
+  HIP_TRY(c, S.alloc(&lval, cap));
+  HIP_TRY(c, S.alloc(&cuv, cap));
+  HIP_TRY(c, S.alloc(&cvu, cap));
+  if (t->n) {
+    std::memcpy(lu, t->lu, t->n * 4);
+    std::memcpy(lv, t->lv, t->n * 4);
+    std::memcpy(lb, t->lb, t->n * 4);
+    std::memcpy(lval, t->lval, t->n);
+    std::memcpy(cuv, t->cuv, t->n * 8);
+    std::memcpy(cvu, t->cvu, t->n * 8);
+  }
+  for (void* p : {(void*)t->lu, (void*)t->lv, (void*)t->lb, (void*)t->lval, (void*)t->cuv, (void*)t->cvu}) t->mem.release(p);
+  t->lu = t->mem.adopt(S.take(lu));
+  t->lv = t->mem.adopt(S.take(lv));
+  t->lb = t->mem.adopt(S.take(lb));
+  t->lval = t->mem.adopt(S.take(lval));
+  t->cuv = t->mem.adopt(S.take(cuv));
+  t->cvu = t->mem.adopt(S.take(cvu));
+  t->cap = cap;
+  return ARTP_OK;
+}
+
+static int try_passes_code(int rc) {
+  ARTP_TRY(rc);
+  return ARTP_OK;
+}
+
+int main() {
+  FakeCtx ctx;
+  // every failure position of a first reserve: nothing stays allocated, the error and its text come back
+  const char* const exprs[6] = {"S.alloc(&lu, cap)",   "S.alloc(&lv, cap)",  "S.alloc(&lb, cap)",
+                                "S.alloc(&lval, cap)", "S.alloc(&cuv, cap)", "S.alloc(&cvu, cap)"};
+  for (int n = 1; n <= 6; ++n) {
+    Log t;
+    ctx.last_error.clear();
+    hip_stub::reset(n);
+    CHECK(log_reserve(&ctx, &t, 64) == ARTP_ERR_HIP);
+    CHECK(hip_stub::live == 0);
+    CHECK(hip_stub::mallocs == n && hip_stub::frees == n - 1);
+    CHECK(ctx.last_error == std::string(exprs[n - 1]) + ": out of memory");
+    CHECK(t.cap == 0 && t.lu == nullptr);
+  }
+  // ... and of a regrow: the old six stay the tree's, intact, and are freed with it
+  for (int n = 1; n <= 6; ++n) {
+    {
+      Log t;
+      hip_stub::reset();
+      CHECK(log_reserve(&ctx, &t, 64) == ARTP_OK);
+      CHECK(hip_stub::live == 6);
+      t.n = 64;
+      for (size_t i = 0; i < 64; ++i) t.lu[i] = (uint32_t)i, t.cvu[i] = 0.5 * (double)i;
+      hip_stub::reset(n);
+      CHECK(log_reserve(&ctx, &t, 128) == ARTP_ERR_HIP);
+      CHECK(hip_stub::live == 6 && t.cap == 64);
+      CHECK(t.lu[63] == 63u && t.cvu[63] == 31.5);
+    }
+    CHECK(hip_stub::live == 0);
+  }
+  // success: one malloc and one free per buffer, the entries copied, nothing live after the owner is gone
+  {
+    Log t;
+    hip_stub::reset();
+    CHECK(log_reserve(&ctx, &t, 64) == ARTP_OK);
+    t.n = 64;
+    for (size_t i = 0; i < 64; ++i) t.lv[i] = (uint32_t)(2 * i), t.lval[i] = (uint8_t)i;
+    CHECK(log_reserve(&ctx, &t, 128) == ARTP_OK);
+    CHECK(hip_stub::mallocs == 12 && hip_stub::frees == 6 && hip_stub::live == 6);
+    CHECK(t.cap == 128 && t.lv[63] == 126u && t.lval[63] == 63);
+    t.lv[127] = 1u;  // the new size is really there
+  }
+  CHECK(hip_stub::live == 0);
+  CHECK(hip_stub::mallocs == 12 && hip_stub::frees == 12);
+
+  // release frees exactly once: now, not again at the end of the scope, and not at all what the owner does not hold
+  {
+    DeviceScratch S;
+    float *a = nullptr, *b = nullptr;
+    hip_stub::reset();
+    CHECK(S.alloc(&a, 10) == hipSuccess && S.alloc(&b, 10) == hipSuccess);
+    CHECK(hip_stub::live == 2);
+    S.release(a);
+    CHECK(hip_stub::live == 1 && hip_stub::frees == 1);
+    S.release(a);        // forgotten: no second free (the address sanitizer would end the program)
+    S.release(nullptr);
+    CHECK(hip_stub::live == 1 && hip_stub::frees == 1);
+    b[9] = 1.0f;         // the other buffer is untouched
+  }
+  CHECK(hip_stub::live == 0 && hip_stub::frees == 2);
+
+  // take: the buffer stays live and is not the destructor's any more
+  {
+    double* kept = nullptr;
+    hip_stub::reset();
+    {
+      DeviceScratch S;
+      double* other = nullptr;
+      CHECK(S.alloc(&kept, 7) == hipSuccess && S.alloc(&other, 7) == hipSuccess);
+      CHECK(S.take(kept) == kept);
+    }
+    CHECK(hip_stub::live == 1 && hip_stub::frees == 1);
+    kept[6] = 2.0;
+    CHECK(hipFree(kept) == hipSuccess);
+    CHECK(hip_stub::live == 0);
+  }
+
+  // a request of zero elements is one element: a pointer that can be passed on, freed like the others
+  {
+    hip_stub::reset();
+    {
+      DeviceScratch S;
+      uint32_t* z = nullptr;
+      void* raw = nullptr;
+      CHECK(S.alloc(&z, 0) == hipSuccess && z != nullptr);
+      z[0] = 7u;
+      CHECK(S.alloc(&raw, 0) == hipSuccess && raw != nullptr);  // the untyped form counts bytes
+      CHECK(hip_stub::live == 2);
+    }
+    CHECK(hip_stub::live == 0 && hip_stub::frees == 2);
+  }
+
+  // a failed alloc leaves a null pointer and nothing to free
+  {
+    hip_stub::reset(1);
+    DeviceScratch S;
+    int* p = reinterpret_cast<int*>(&ctx);
+    CHECK(S.alloc(&p, 4) == hipErrorOutOfMemory && p == nullptr);
+    CHECK(hip_stub::live == 0);
+  }
+
+  CHECK(try_passes_code(ARTP_OK) == ARTP_OK);
+  CHECK(try_passes_code(ARTP_ERR_CAPACITY) == ARTP_ERR_CAPACITY);
+
+  if (failures) {
+    std::printf("%d checks failed\n", failures);
+    return 1;
+  }
+  std::printf("device_scratch ok\n");
+  return 0;
+}
