@@ -3695,6 +3695,11 @@ extern "C" int artp_debug_pool_trace(unsigned long long* out16) {
 extern "C" int artp_debug_stage_cycles(unsigned long long* out20, int reset) {
   if (out20 && hipMemcpyFromSymbol(out20, HIP_SYMBOL(artp::g_stage_cycles), 20 * sizeof(unsigned long long)) != hipSuccess)
     return -1;
+  if (reset == 7) {  // the torso stream pass's box counters (read + reset; every other reset clears them too): out20[0 .. 7], see g_torso_counts
+    if (out20 && hipMemcpyFromSymbol(out20, HIP_SYMBOL(artp::g_torso_counts), 8 * sizeof(unsigned long long)) != hipSuccess) return -1;
+    unsigned long long z8[8] = {};
+    return hipMemcpyToSymbol(HIP_SYMBOL(artp::g_torso_counts), z8, sizeof(z8)) == hipSuccess ? 0 : -1;
+  }
   if (out20 && reset >= 3 &&
       hipMemcpyFromSymbol(out20, HIP_SYMBOL(artp::g_feet_cycles), 8 * sizeof(unsigned long long)) != hipSuccess)
     return -1;
@@ -3729,6 +3734,7 @@ extern "C" int artp_debug_stage_cycles(unsigned long long* out20, int reset) {
     if (hipMemcpyToSymbol(HIP_SYMBOL(artp::g_classify_cycles), z16, sizeof(z16)) != hipSuccess) return -1;
     unsigned long long z[20] = {};
     if (hipMemcpyToSymbol(HIP_SYMBOL(artp::g_stage_cycles), z, sizeof(z)) != hipSuccess) return -1;
+    if (hipMemcpyToSymbol(HIP_SYMBOL(artp::g_torso_counts), z, 8 * sizeof(unsigned long long)) != hipSuccess) return -1;
   }
   return 0;
 }

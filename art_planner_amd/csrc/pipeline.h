@@ -1152,7 +1152,13 @@ feet_stream_kernel(FieldDev ff, RobotDev rb, PipelineQueues q, uint8_t* __restri
 
 #ifdef ARTP_STAGE_TIMING
 // tuning aid (never in the shipped build): cycles per stage of resolve_boxes_kernel, summed over boxes
+// (torso stream pass, PASS 0: [0] record, [2] vertex stream, [4] corner stage, [6] chunk fetch: queue-6 flush, cursor,
+// the chunk's headers)
 __device__ unsigned long long g_stage_cycles[2][10];
+// torso stream pass: boxes taken, skipped (their state had failed), forwarded without a stream, stream hits, boxes that
+// ran the corner stage, corner results 1 and 2
+__device__ unsigned long long g_torso_counts[8];
+#define ARTP_T_COUNT(slot) do { t_cnt[slot] += 1ull; } while (0)
 #define ARTP_T_MARK(slot)                    \
   do {                                       \
     const long long now_ = clock64();        \
@@ -1161,6 +1167,7 @@ __device__ unsigned long long g_stage_cycles[2][10];
   } while (0)
 #else
 #define ARTP_T_MARK(slot) do { } while (0)
+#define ARTP_T_COUNT(slot) do { } while (0)
 #endif
 
 // ---- stage 2: one lane group per undecided box ---------------------------------------------------------
@@ -1195,33 +1202,56 @@ resolve_boxes_kernel(FieldDev fld, RobotDev rb, PipelineQueues q, uint8_t* __res
   const unsigned long long stride = nblk * WAVES * GPW;
 #ifdef ARTP_STAGE_TIMING
   unsigned long long t_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  unsigned long long t_cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   const long long t_begin = clock64();
 #endif
   // PASS 0: every wavefront takes ARTP_TORSO_CHUNK boxes at a time from the sub-queue's cursor (see sub_cursor);
   // the other passes stride statically over their short index queues
-  unsigned long long next = PASS == 0 ? 0ull : blk * WAVES * GPW + unit_in_block, chunk_end = 0ull;
+  unsigned long long next = PASS == 0 ? 0ull : blk * WAVES * GPW + unit_in_block;
   // PASS 0: boxes handed on to the staged pass (queue 6) leave once per chunk
   __shared__ unsigned fwd_slots[PASS == 0 ? WAVES : 1][ARTP_TORSO_CHUNK];
   unsigned* fs = fwd_slots[PASS == 0 ? (threadIdx.x >> 6) : 0];
   if (PASS == 0 && lane < ARTP_TORSO_CHUNK) fs[lane] = 0u;
   unsigned long long chunk_first = 0ull;
+  // PASS 0: the chunk's headers are read together.  Lane k reads the state of box k and that state's label, a ballot
+  // gives `live` (bit k: the state has not failed yet), and the wavefront walks the set bits.  Read per box, the label
+  // is a second round trip behind every record, and a box of a failed state costs its wavefront both for nothing.  (A
+  // state has one torso box, so nothing in this pass can fail a box's state between the chunk's start and its turn.)
+  static_assert(ARTP_TORSO_CHUNK <= 32, "one bit per box of the chunk in a 32-bit mask");
+  unsigned live = 0u;
   for (;;) {
     if constexpr (PASS == 0) {
-      if (next >= chunk_end) {
+      bool more = true;
+      while (live == 0u) {
+#ifdef ARTP_STAGE_TIMING
+        const long long t_fetch = clock64();
+#endif
         fwd_flush_slots<ARTP_TORSO_CHUNK>(fs, sub_fwd(q, 0, sq), q.q6 + fwd_base(q, 0, sq), lane);
         unsigned long long c0 = 0;
         if (lane == 0) c0 = atomicAdd(sub_cursor(q, 0, sq), (unsigned long long)ARTP_TORSO_CHUNK);
         c0 = __shfl(c0, 0);
-        if (c0 >= count) break;
-        next = c0;
+        if (c0 >= count) {
+          more = false;
+          break;
+        }
         chunk_first = c0;
-        chunk_end = c0 + ARTP_TORSO_CHUNK < count ? c0 + ARTP_TORSO_CHUNK : count;
+        const unsigned long long left = count - c0 < (unsigned long long)ARTP_TORSO_CHUNK ? count - c0 : (unsigned long long)ARTP_TORSO_CHUNK;
+        bool alive = false;
+        if ((unsigned long long)lane < left) alive = valid[q.q1[first + c0 + lane].state] != 0;
+        live = (unsigned)__ballot(alive);
+#ifdef ARTP_STAGE_TIMING
+        t_acc[6] += (unsigned long long)(clock64() - t_fetch);
+        t_cnt[1] += left - (unsigned long long)__popc(live);
+#endif
       }
+      if (!more) break;
+      next = chunk_first + (unsigned long long)__builtin_ctz(live);
+      live &= live - 1u;
     } else {
       if (next >= count) break;
     }
     const unsigned long long it = next;
-    next += PASS == 0 ? 1ull : stride;
+    if (PASS != 0) next += stride;
     const unsigned long long item =
         PASS == 0 ? first + it
                   : (unsigned long long)(PASS == 1 ? (direct ? fwd_item(q, 1, q.q4, it) : q.q3[it])
@@ -1230,7 +1260,8 @@ resolve_boxes_kernel(FieldDev fld, RobotDev rb, PipelineQueues q, uint8_t* __res
     long long t_prev = clock64();
 #endif
     const PendingBox rec = q.q1[item];
-    if (valid[rec.state] == 0) continue;        // another box of this state already failed
+    if (PASS != 0 && valid[rec.state] == 0) continue;        // another box of this state already failed
+    if (PASS == 0) ARTP_T_COUNT(0);
     BoxHF b;
     box_from_record(rec, rb, b);
     ARTP_T_MARK(0);
@@ -1245,17 +1276,23 @@ resolve_boxes_kernel(FieldDev fld, RobotDev rb, PipelineQueues q, uint8_t* __res
       if (fld.partner_flags != nullptr && (rec.kind & ARTP_REC_ALL_FINITE)) {
         __shared__ unsigned short hot_blocks[WAVES][ARTP_HOT_BLOCKS];
         if (wave_vertex_stream_blocks<ARTP_TORSO_U>(fld, mm4, b, hot_blocks[threadIdx.x >> 6], lane)) {
+          ARTP_T_MARK(2);
+          ARTP_T_COUNT(3);
           result = 1;
           decided = true;
         } else {
           ARTP_T_MARK(2);
+          ARTP_T_COUNT(4);
           const int r = grp_corner_stage_direct<G>(fld, b, lane);
+          if (r) ARTP_T_COUNT(4 + r);
           if (r != 2) {
             result = r;
             decided = true;
           }
         }
         ARTP_T_MARK(4);
+      } else {
+        ARTP_T_COUNT(2);
       }
       if (!decided) {
         if (gl == 0) fs[it - chunk_first] = (unsigned)item + 1u;
@@ -1325,6 +1362,8 @@ resolve_boxes_kernel(FieldDev fld, RobotDev rb, PipelineQueues q, uint8_t* __res
 #ifdef ARTP_STAGE_TIMING
   if (gl == 0) {
     for (int k = 0; k < 8; ++k) atomicAdd(&g_stage_cycles[G == 64 ? 0 : 1][k], t_acc[k]);
+    if (PASS == 0)
+      for (int k = 0; k < 8; ++k) atomicAdd(&g_torso_counts[k], t_cnt[k]);
     atomicAdd(&g_stage_cycles[G == 64 ? 0 : 1][8], (unsigned long long)(clock64() - t_begin));
     atomicAdd(&g_stage_cycles[G == 64 ? 0 : 1][9], 1ull);
   }

@@ -28,6 +28,19 @@ a = np.array(list(out), dtype=np.float64).reshape(2, 10)
 names = ["record", "scan", "vertex(f)", "compact", "corners"]
 cnt = ctx.pipeline_counters()
 print("counters", cnt)
+tc = (C.c_ulonglong * 20)()
+L.artp_debug_stage_cycles(tc, 7)  # 7: the torso stream pass's box counters of the second batch (read + reset)
+t_taken, t_skip, t_fwd, t_vhit, t_corner, t_r1, t_r2 = (int(tc[k]) for k in range(7))
+t_stream = t_taken - t_fwd
+print("torso stream pass: boxes taken", t_taken, "skipped (state already failed)", t_skip, "forwarded without a stream", t_fwd,
+      "streamed", t_stream, "stream hits", t_vhit, "boxes that ran the corner stage", t_corner, "corner result 0", t_corner - t_r1 - t_r2,
+      "1 (contact)", t_r1, "2 (may have partners)", t_r2)
+# ticks summed over the wavefronts: [0] record, [2] stream, [4] corner stage, [6] chunk fetch (flush, cursor, the chunk's
+# headers), [8] lifetime (the near-empty G = 64 fallback launches add theirs to the same row)
+print("  ticks: record %.0f stream %.0f corner %.0f chunk fetch %.0f lifetime %.0f" % (a[0, 0], a[0, 2], a[0, 4], a[0, 6], a[0, 8]))
+print("  share of the lifetime: record %.3f stream %.3f corner %.3f chunk fetch %.3f" % tuple(a[0, k] / max(a[0, 8], 1) for k in (0, 2, 4, 6)))
+print("  ticks per box: record %.0f, stream %.0f per streamed box, corner stage %.0f per box that ran it; chunk fetch %.0f per box queued"
+      % (a[0, 0] / max(t_taken, 1), a[0, 2] / max(t_stream, 1), a[0, 4] / max(t_corner, 1), a[0, 6] / max(t_taken + t_skip, 1)))
 ff = (C.c_ulonglong * 20)()
 L.artp_debug_stage_cycles(ff, 3)  # reset >= 3: the feet_stream counters
 print("feet_stream: stream ticks", ff[0], "corner ticks", ff[1], "boxes that ran the second stage", ff[2], "boxes taken", ff[3],
