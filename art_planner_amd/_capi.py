@@ -24,6 +24,8 @@ SYMBOLS = [
     "artp_field_destroy", "artp_field_learned_params_defaults", "artp_field_compute_learned", "artp_field_learned_stats",
     "artp_field_update_learned", "artp_field_learned_update_stats", "artp_field_block_moves", "artp_field_unblock",
     "artp_field_blocked_count", "artp_field_blocked", "artp_field_plan", "artp_field_plan_stats", "artp_field_plan_round_tile_runs",
+    "artp_clearance_params_defaults", "artp_clearance_map", "artp_clearance_map_dev",
+    "artp_field_clearance_params_defaults", "artp_field_compute_clearance", "artp_field_clearance",
     "artp_check_motions_last_valid", "artp_check_motions_last_valid_dev",
     "artp_set_z_bounds", "artp_set_few_edges", "artp_set_edge_passes", "artp_cost_set_fc_path", "artp_check_motions", "artp_check_motions_dev", "artp_check_edges_interp",
     "artp_check_edges_interp_dev", "artp_compact_valid_dev", "artp_compact_valid_indices_dev", "artp_sample_states_at_dev",
@@ -143,6 +145,15 @@ class FieldPlanStats(C.Structure):  # artp_field_plan_stats_t
                 [(n, C.c_double) for n in ("descent_ms", "check_ms", "round_ms", "passes_ms")])
 
 
+class ClearanceParams(C.Structure):  # artp_clearance_params
+    _fields_ = [("radius_cells", C.c_int32), ("yaw_spread", C.c_int32), ("outside_is_obstacle", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class FieldClearanceParams(C.Structure):  # artp_field_clearance_params
+    _fields_ = [("base", FieldParams), ("clearance", ClearanceParams), ("margin", C.c_double), ("gain", C.c_double)]
+
+
 class TreeParams(C.Structure):  # artp_tree_params (include/artp_c.h)
     _fields_ = [("seed", C.c_uint64), ("first_index", C.c_uint64), ("variant", C.c_int32), ("objective", C.c_int32),
                 ("max_lon_vel", C.c_double), ("max_lat_vel", C.c_double), ("max_ang_vel", C.c_double),
@@ -240,6 +251,15 @@ def _load_path(LIB_PATH):
     L.artp_field_plan.argtypes = [vp, vp, sz, i32, vp, vp, vp, vp, vp, sz]
     L.artp_field_plan_stats.argtypes = [vp, C.POINTER(FieldPlanStats)]
     L.artp_field_plan_round_tile_runs.argtypes = [vp, vp, sz, C.POINTER(sz)]
+    L.artp_clearance_params_defaults.argtypes = [C.POINTER(ClearanceParams)]
+    L.artp_clearance_params_defaults.restype = None
+    for name in ("artp_clearance_map", "artp_clearance_map_dev"):
+        getattr(L, name).argtypes = [vp, C.POINTER(ClearanceParams), i32, i32, i32, vp, i32, vp]
+    L.artp_field_clearance_params_defaults.argtypes = [C.POINTER(FieldClearanceParams)]
+    L.artp_field_clearance_params_defaults.restype = None
+    L.artp_field_compute_clearance.argtypes = [vp, C.POINTER(FieldClearanceParams), i32, vp, vp, i32, vp, sz, i32,
+                                               C.POINTER(vp)]
+    L.artp_field_clearance.argtypes = [vp, vp]
     L.artp_map_version.argtypes = [vp]
     L.artp_map_version.restype = C.c_uint64
     L.artp_set_z_bounds.argtypes = [vp, dbl, dbl]

@@ -258,6 +258,65 @@ class Context:
                                  w_risk=w_risk, risk_threshold=risk_threshold, plain_sweeps=plain_sweeps,
                                  inner_sweeps=inner_sweeps)
 
+    def _clearance_args(self, mask, radius_cells, yaw_spread, outside_is_obstacle):
+        """(params, pointer, on_device, owner, nrows, ncols) of a clearance_map call; a device mask is (nrows, ncols)-shaped
+        in the layout reachability_map_dev writes: a column-major (nrows, ncols) tensor or its (ncols, nrows) transpose."""
+        p = _capi.ClearanceParams()
+        self.L.artp_clearance_params_defaults(C.byref(p))
+        p.radius_cells, p.yaw_spread = int(radius_cells), int(yaw_spread)
+        p.outside_is_obstacle = int(bool(outside_is_obstacle))
+        if hasattr(mask, "data_ptr"):
+            if mask.dim() != 2 or mask.element_size() != 4:
+                raise _capi.ArtpError("clearance_map: a device mask is a 2-D tensor of 32-bit words")
+            nr, nc = int(mask.shape[0]), int(mask.shape[1])
+            if not (mask.stride(0) == 1 and mask.stride(1) == nr):
+                raise _capi.ArtpError("clearance_map: a device mask must be column-major (stride (1, nrows))")
+            return p, mask.data_ptr(), 1, mask, nr, nc
+        m = np.asarray(mask)
+        if m.ndim != 2:
+            raise _capi.ArtpError(f"clearance_map: the mask is {m.shape}, not (nrows, ncols)")
+        keep = np.asfortranarray(m, dtype=np.uint32)
+        return p, keep.ctypes.data, 0, keep, int(m.shape[0]), int(m.shape[1])
+
+    def clearance_map(self, mask, n_yaw, radius_cells=12, *, yaw_spread=0, outside_is_obstacle=False) -> np.ndarray:
+        """(nrows, ncols, n_yaw) uint16 (the shape and order of CostField.dist()): the exact squared distance, in cells,
+        from every node of a reachability mask to the nearest cell where that heading -- and its yaw_spread neighbours on
+        either side -- is not a valid pose (artp_clearance_map).  0 = not a node (or, with
+        yaw_spread, an obstacle itself), 0xffff = nothing within radius_cells.  Cells outside the mask count as obstacles
+        iff outside_is_obstacle.  mask = (nrows, ncols) uint32 array or a column-major device tensor.  Needs no map."""
+        p, ptr, on_device, keep, nr, nc = self._clearance_args(mask, radius_cells, yaw_spread, outside_is_obstacle)
+        out = np.empty((nc, nr, max(int(n_yaw), 0)), np.uint16)
+        self._chk(self.L.artp_clearance_map(self.h, C.byref(p), int(n_yaw), nr, nc, ptr, on_device, out.ctypes.data),
+                  "artp_clearance_map")
+        del keep
+        return out.transpose(1, 0, 2)
+
+    def clearance_map_dev(self, mask, n_yaw, d2_t, radius_cells=12, *, yaw_spread=0, outside_is_obstacle=False):
+        """The same into a device tensor of >= nrows * ncols * n_yaw 16-bit words, index (r + c nrows) n_yaw + k,
+        asynchronous on the current stream."""
+        p, ptr, on_device, keep, nr, nc = self._clearance_args(mask, radius_cells, yaw_spread, outside_is_obstacle)
+        if d2_t.numel() * d2_t.element_size() < nr * nc * max(int(n_yaw), 0) * 2:
+            raise _capi.ArtpError("clearance_map_dev: d2_t holds fewer than nrows * ncols * n_yaw 16-bit words")
+        self._chk(self.L.artp_clearance_map_dev(self.h, C.byref(p), int(n_yaw), nr, nc, ptr, on_device, d2_t.data_ptr()),
+                  "artp_clearance_map_dev")
+        del keep
+
+    def clearance_cost_field(self, mask, n_yaw, sources, *, margin=0.2, gain=2.0, radius_cells=12, yaw_spread=0,
+                             outside_is_obstacle=False, rect=None, reverse=False, objective=1, max_lon_vel=0.5,
+                             max_lat_vel=0.1, max_ang_vel=0.5, plain_sweeps=False, inner_sweeps=64):
+        """cost_field with every move's cost inflated near obstacles (artp_field_compute_clearance):
+        w(a -> b) = base (1 + gain max(pen(a), pen(b))), pen(v) = max(0, 1 - res sqrt(d2[v]) / margin) with d2 the
+        clearance_map of the mask (0 where nothing lies within radius_cells).  margin (metres) may not exceed
+        radius_cells * resolution.  gain = 0 gives cost_field's bits.  Returns a CostField: dist, path, edge_costs,
+        block_moves, unblock and plan work unchanged, .clearance() hands out d2; update() and update_learned() are
+        refused (a mask edit moves clearances up to radius_cells around it): compute a new field."""
+        from .field import CostField
+        return CostField.clearance_weighted(self, mask, n_yaw, sources, margin=margin, gain=gain, radius_cells=radius_cells,
+                                            yaw_spread=yaw_spread, outside_is_obstacle=outside_is_obstacle, rect=rect,
+                                            reverse=reverse, objective=objective, max_lon_vel=max_lon_vel,
+                                            max_lat_vel=max_lat_vel, max_ang_vel=max_ang_vel, plain_sweeps=plain_sweeps,
+                                            inner_sweeps=inner_sweeps)
+
     def check_edges_interp(self, s1, s2):
         s1 = np.ascontiguousarray(s1, np.float64).reshape(-1, 7)
         s2 = np.ascontiguousarray(s2, np.float64).reshape(-1, 7)

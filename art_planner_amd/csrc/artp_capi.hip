@@ -135,6 +135,9 @@ struct artp_ctx {
   size_t tmp_cap[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   void* cub_tmp = nullptr;
   size_t cub_cap = 0;
+  // clearance.h: the offset list of the disc of radius R, built when R is first met and never rewritten
+  int32_t* clear_offs[33] = {};
+  uint32_t clear_n[33] = {};
   // Lanes (artp_set_lane): everything above that a call in flight owns -- stream, scratch buffers, counters -- exists
   // once per lane, so calls issued on different lanes (from one host thread, on different streams) overlap on the
   // GPU.  The members above are the CURRENT lane's; the others are parked here.  The map, its tables and the
@@ -1001,6 +1004,8 @@ void artp_destroy(artp_ctx* c) {
     if (c->d_convw[l]) (void)hipFree(c->d_convw[l]);
     if (c->d_convb[l]) (void)hipFree(c->d_convb[l]);
   }
+  for (int32_t* p : c->clear_offs)
+    if (p) (void)hipFree(p);
   if (c->d_fc) (void)hipFree(c->d_fc);
   if (c->d_fc_mfma) (void)hipFree(c->d_fc_mfma);
   if (c->d_c12) (void)hipFree(c->d_c12);
@@ -3681,6 +3686,7 @@ int artp_cost_get_features(artp_ctx* c, float* out, int* fh, int* fw) {
 #include "roadmap_many.h"
 #include "reach.h"
 #include "field.h"
+#include "clearance.h"
 #include "field_plan.h"
 #include "preprocess.h"
 #include "group.h"

@@ -1,0 +1,346 @@
+// clearance.h -- clearance maps and clearance-weighted cost-to-go fields (include/artp_c.h artp_clearance_map*,
+// artp_field_compute_clearance, artp_field_clearance).
+//
+// d2[node] (uint16, node order of reach.h and field.h) = the exact squared distance, in cells, from node (r, c, k) to the
+// nearest OBSTACLE of heading k within radius_cells R: a cell whose word lacks one of the bits k - s .. k + s (mod n_yaw),
+// s = yaw_spread, and -- with outside_is_obstacle -- every cell outside the rectangle.  0 where bit k of the node's own
+// word is clear, 0xffff where no obstacle lies within R.
+//   clearance_map_kernel          a workgroup of 256 lanes owns a 16 x 16 tile (field.h's tiling).  It stages the ERODED
+//                                 words of the tile and a halo of R cells in LDS: bit k of an eroded word is set iff the
+//                                 bits k - s .. k + s of the word are (an AND of rotations within the low n_yaw bits), so
+//                                 "obstacle for heading k" is "bit k clear", for all headings of a cell in one word.  One
+//                                 lane per cell walks the offsets of the disc in order of increasing d^2 (the host's list):
+//                                 hit = ~word & pending answers every heading in hit with this d^2.  The answers go to an
+//                                 LDS staging tile, each (cell, heading) once, and leave as rows of 16 n_yaw neighbours.
+//   field_clearance_table_kernel  one lane per slot of objective 2's weight table (field_slot_edge): the base cost of
+//                                 artp_field_compute in the field's direction (field_pull_cost) times
+//                                 1 + gain max(pen(a), pen(b)), pen(v) = max(0, 1 - res sqrt(d2[v]) / margin), 0 at 0xffff.
+// The field (objective id 3 inside the library) is searched by the table-driven kernels of the learned field, unchanged.
+// It is not updated in place: a mask edit moves clearances up to R cells around it (artp_field_update* refuse it).
+#pragma once
+
+namespace artp {
+
+constexpr int CLEAR_MAX_R = 32;
+constexpr int CLEAR_PITCH = FIELD_T * FIELD_T + 2;  // uint16 per heading of the staging tile: 129 words, one bank a heading
+constexpr uint16_t CLEAR_NONE = 0xffffu;
+
+struct ClearGrid {
+  int nrows, ncols, n_yaw;
+  int tiles_r;
+  int R, spread, outside;
+  int W;       // 16 + 2 R: edge of the staged window in cells
+  int S;       // its column pitch in words
+  uint32_t n_off;
+  uint32_t yaw_bits;
+};
+
+// Column pitch of the window: the least S >= W with S = 16 (mod 32).  A wave holds 16 rows x 4 columns of the tile and a
+// 32-lane group of ds_read_b32 two of those columns: their two runs of 16 words then lie in opposite halves of the 32 banks,
+// at every offset of the walk (all lanes of a wave read the same offset, so the window only shifts).
+__host__ __device__ constexpr int clearance_pitch(int W) { return ((W - 16 + 31) / 32) * 32 + 16; }
+
+inline size_t clearance_lds(int R, int n_yaw) {
+  const int W = FIELD_T + 2 * R;
+  return (size_t)clearance_pitch(W) * W * sizeof(uint32_t) + (size_t)n_yaw * CLEAR_PITCH * sizeof(uint16_t);
+}
+
+// bit k of the result = bits k - s .. k + s (mod n) of w (w within its low n bits; 1 <= t <= s <= n / 2 keeps the shifts in 1 .. 31)
+__device__ __forceinline__ uint32_t clearance_erode(uint32_t w, int n, int s, uint32_t yaw_bits) {
+  uint32_t e = w;
+  for (int t = 1; t <= s; ++t) e &= ((w << t) | (w >> (n - t))) & ((w >> t) | (w << (n - t)));
+  return e & yaw_bits;
+}
+
+// offs[i] = (dr + dc S) << 16 | d2 of the i-th offset of the disc, d2 ascending, (0, 0) first
+__global__ void __launch_bounds__(256)
+clearance_map_kernel(ClearGrid G, const uint32_t* __restrict__ mask, const int32_t* __restrict__ offs, uint16_t* __restrict__ d2) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  uint32_t* win = reinterpret_cast<uint32_t*>(smem);
+  uint16_t* stage = reinterpret_cast<uint16_t*>(win + (size_t)G.S * G.W);
+  const int tid = threadIdx.x;
+  const int tile = blockIdx.x;
+  const int r0 = (tile % G.tiles_r) * FIELD_T, c0 = (tile / G.tiles_r) * FIELD_T;
+  const int ny = G.n_yaw;
+
+  for (int e = tid; e < G.W * G.W; e += 256) {
+    const int wr = e % G.W, wc = e / G.W;
+    const int r = r0 - G.R + wr, c = c0 - G.R + wc;
+    uint32_t w = G.outside ? 0u : G.yaw_bits;  // outside the rectangle: an obstacle of every heading, or of none
+    if (r >= 0 && r < G.nrows && c >= 0 && c < G.ncols)
+      w = clearance_erode(mask[(size_t)r + (size_t)c * G.nrows] & G.yaw_bits, ny, G.spread, G.yaw_bits);
+    win[wr + wc * G.S] = w;
+  }
+  __syncthreads();
+
+  const int tr = tid & (FIELD_T - 1), tc = tid >> 4;
+  const bool in = r0 + tr < G.nrows && c0 + tc < G.ncols;
+  const uint32_t mw = in ? mask[(size_t)(r0 + tr) + (size_t)(c0 + tc) * G.nrows] & G.yaw_bits : 0u;
+  const int me = (tr + G.R) + (tc + G.R) * G.S;
+  uint16_t* mine = stage + tid;
+  uint32_t pending = mw;  // the headings that are nodes and have no answer yet
+  for (uint32_t i = 0; i < G.n_off && pending; ++i) {
+    const int32_t o = offs[i];
+    uint32_t hit = ~win[me + (o >> 16)] & pending;
+    pending &= ~hit;
+    while (hit) {
+      const int k = __ffs((int)hit) - 1;
+      hit &= hit - 1u;
+      mine[k * CLEAR_PITCH] = (uint16_t)(o & 0xffff);
+    }
+  }
+  while (pending) {  // no obstacle within R
+    const int k = __ffs((int)pending) - 1;
+    pending &= pending - 1u;
+    mine[k * CLEAR_PITCH] = CLEAR_NONE;
+  }
+  uint32_t none = ~mw & G.yaw_bits;  // not a node
+  while (none) {
+    const int k = __ffs((int)none) - 1;
+    none &= none - 1u;
+    mine[k * CLEAR_PITCH] = 0;
+  }
+  __syncthreads();
+
+  for (int e = tid; e < FIELD_T * FIELD_T * ny; e += 256) {
+    const int ci = e / ny, k = e - ci * ny;
+    const int r = r0 + (ci & (FIELD_T - 1)), c = c0 + (ci >> 4);
+    if (r >= G.nrows || c >= G.ncols) continue;
+    d2[((size_t)r + (size_t)c * G.nrows) * ny + k] = stage[k * CLEAR_PITCH + ci];
+  }
+}
+
+struct ClearWeight {
+  double res, margin, gain;
+};
+
+__device__ __forceinline__ double clearance_pen(const ClearWeight& p, uint16_t d2) {
+  if (d2 == CLEAR_NONE) return 0.0;
+  return fmax(0.0, 1.0 - (p.res * sqrt((double)d2)) / p.margin);
+}
+
+// G carries the BASE objective (0 or 1) here: field_pull_cost prices with it.  tab: the (m, k) table of that objective.
+__global__ void __launch_bounds__(256)
+field_clearance_table_kernel(FieldGrid G, const uint32_t* __restrict__ mask, const float* __restrict__ h,
+                             const double* __restrict__ tab, const uint16_t* __restrict__ d2, ClearWeight p, size_t slots,
+                             double* __restrict__ wtab) {
+  const size_t s = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= slots) return;
+  double w = INFINITY;
+  uint32_t from, to;
+  if (field_slot_edge(G, mask, s, &from, &to)) {
+    const uint32_t v = G.reverse ? from : to, u = G.reverse ? to : from;  // the slot's own node and its neighbour
+    const uint32_t cv = v / (uint32_t)G.n_yaw, cu = u / (uint32_t)G.n_yaw;
+    const int k = (int)(v - cv * (uint32_t)G.n_yaw);
+    const int j = (int)((s / (FIELD_T * FIELD_T)) % 10);
+    const double base = field_pull_cost(G, tab, j, k, h[cv], h[cu]);
+    w = base * (1.0 + p.gain * fmax(clearance_pen(p, d2[from]), clearance_pen(p, d2[to])));
+  }
+  wtab[s] = w;
+}
+
+}  // namespace artp
+
+namespace {
+
+int clearance_check(artp_ctx* c, const artp_clearance_params& p, int n_yaw) {
+  if (n_yaw < 1 || n_yaw > artp::ARTP_REACH_MAX_YAW) {
+    c->last_error = "n_yaw must lie in [1, 32]";
+    return ARTP_ERR_INVALID_ARG;
+  }
+  if (p.radius_cells < 1 || p.radius_cells > artp::CLEAR_MAX_R || p.yaw_spread < 0 || p.yaw_spread > n_yaw / 2 ||
+      (p.outside_is_obstacle != 0 && p.outside_is_obstacle != 1)) {
+    c->last_error = "clearance: radius_cells must lie in [1, 32], yaw_spread in [0, n_yaw / 2], outside_is_obstacle be 0 or 1";
+    return ARTP_ERR_INVALID_ARG;
+  }
+  return ARTP_OK;
+}
+
+// The offsets of the disc of radius R in order of increasing d^2, on the device: built the first time a context meets R,
+// then kept unchanged until artp_destroy (a kernel in flight on any stream may be reading it).
+int clearance_offsets(artp_ctx* c, int R) {
+  if (c->clear_offs[R]) return ARTP_OK;
+  const int S = artp::clearance_pitch(artp::FIELD_T + 2 * R);
+  std::vector<int32_t> offs;
+  for (int dc = -R; dc <= R; ++dc)
+    for (int dr = -R; dr <= R; ++dr)
+      if (dr * dr + dc * dc <= R * R) offs.push_back((int32_t)((uint32_t)(dr + dc * S) << 16) | (dr * dr + dc * dc));
+  std::stable_sort(offs.begin(), offs.end(), [](int32_t a, int32_t b) { return (a & 0xffff) < (b & 0xffff); });
+  int32_t* d = nullptr;
+  HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&d), offs.size() * sizeof(int32_t)));
+  if (hipMemcpy(d, offs.data(), offs.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(d);
+    c->last_error = "clearance: copying the offset list failed";
+    return ARTP_ERR_HIP;
+  }
+  c->clear_offs[R] = d;
+  c->clear_n[R] = (uint32_t)offs.size();
+  return ARTP_OK;
+}
+
+// clearance_map_kernel over a rectangle of device words into device d2, on the context's stream; the checks are the caller's
+int clearance_run(artp_ctx* c, const artp_clearance_params& p, int n_yaw, int nrows, int ncols, const uint32_t* d_mask,
+                  uint16_t* d_d2) {
+  const int R = p.radius_cells;
+  ARTP_TRY(clearance_offsets(c, R));
+  artp::ClearGrid G;
+  G.nrows = nrows;
+  G.ncols = ncols;
+  G.n_yaw = n_yaw;
+  G.tiles_r = (nrows + artp::FIELD_T - 1) / artp::FIELD_T;
+  G.R = R;
+  G.spread = p.yaw_spread;
+  G.outside = p.outside_is_obstacle;
+  G.W = artp::FIELD_T + 2 * R;
+  G.S = artp::clearance_pitch(G.W);
+  G.n_off = c->clear_n[R];
+  G.yaw_bits = n_yaw == 32 ? 0xffffffffu : (1u << n_yaw) - 1u;
+  const size_t tiles = (size_t)G.tiles_r * ((ncols + artp::FIELD_T - 1) / artp::FIELD_T);
+  hipLaunchKernelGGL(artp::clearance_map_kernel, dim3((unsigned)tiles), dim3(256), artp::clearance_lds(R, n_yaw), c->stream, G,
+                     d_mask, (const int32_t*)c->clear_offs[R], d_d2);
+  HIP_TRY(c, hipGetLastError());
+  return ARTP_OK;
+}
+
+int clearance_map_args(artp_ctx* c, const artp_clearance_params* p, int n_yaw, int nrows, int ncols) {
+  ARTP_TRY(clearance_check(c, *p, n_yaw));
+  if (nrows < 1 || ncols < 1 || (uint64_t)nrows * (uint64_t)ncols * (uint64_t)n_yaw >= (1ull << 32)) {
+    c->last_error = "clearance: nrows and ncols must be positive and nrows * ncols * n_yaw stay below 2^32";
+    return ARTP_ERR_INVALID_ARG;
+  }
+  return ARTP_OK;
+}
+
+// artp_field_compute_clearance's part of field_compute_impl: the field's d2 from its own mask, then the weight table.
+// tab: the host's (m, k) table of the base objective.
+int field_clearance_build(artp_ctx* c, artp_field* f, const double* tab) {
+  hipStream_t st = c->stream;
+  const artp_field_clearance_params& cp = f->cparams;
+  DeviceScratch tmp;
+  double* d_tab = nullptr;
+  HIP_TRY(c, tmp.alloc(&d_tab, (size_t)artp::FIELD_TAB));
+  HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&f->d_d2), f->n_nodes * sizeof(uint16_t)));
+  HIP_TRY(c, hipMemcpyAsync(d_tab, tab, artp::FIELD_TAB * sizeof(double), hipMemcpyHostToDevice, st));
+  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+  for (hipEvent_t& x : ev)
+    if (hipEventCreate(&x) != hipSuccess) x = nullptr;
+  if (ev[0]) (void)hipEventRecord(ev[0], st);
+  int rc = clearance_run(c, cp.clearance, f->grid.n_yaw, f->grid.nrows, f->grid.ncols, f->d_mask, f->d_d2);
+  if (ev[1]) (void)hipEventRecord(ev[1], st);
+  const size_t slots = artp::field_wtab_slots(f->grid);
+  if (rc == ARTP_OK) {
+    artp::FieldGrid Gb = f->grid;
+    Gb.objective = f->params.objective;
+    const artp::ClearWeight w{f->geom.res, cp.margin, cp.gain};
+    hipLaunchKernelGGL(artp::field_clearance_table_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, st, Gb,
+                       (const uint32_t*)f->d_mask, (const float*)f->d_h, (const double*)d_tab, (const uint16_t*)f->d_d2, w, slots,
+                       f->d_tab);
+    if (hipGetLastError() != hipSuccess) rc = ARTP_ERR_HIP;
+  }
+  if (ev[2]) (void)hipEventRecord(ev[2], st);
+  if (hipStreamSynchronize(st) != hipSuccess && rc == ARTP_OK) rc = ARTP_ERR_HIP;  // the host table and d_tab are free from here
+  float t = 0.f;
+  if (rc == ARTP_OK && ev[0] && ev[1] && hipEventElapsedTime(&t, ev[0], ev[1]) == hipSuccess) f->lstats.rows_ms = t;
+  if (rc == ARTP_OK && ev[1] && ev[2] && hipEventElapsedTime(&t, ev[1], ev[2]) == hipSuccess) f->lstats.combine_ms = t;
+  for (hipEvent_t x : ev)
+    if (x) (void)hipEventDestroy(x);
+  if (rc == ARTP_ERR_HIP && c->last_error.empty()) c->last_error = "clearance field: building the weight table failed";
+  f->lstats.table_rows = slots;
+  f->lstats.table_bytes = slots * sizeof(double);
+  return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+void artp_clearance_params_defaults(artp_clearance_params* p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof(*p));
+  p->radius_cells = 12;
+  p->yaw_spread = 0;
+  p->outside_is_obstacle = 0;
+}
+
+int artp_clearance_map_dev(artp_ctx* c, const artp_clearance_params* params, int n_yaw, int nrows, int ncols,
+                           const uint32_t* mask, int mask_on_device, uint16_t* d2_dev) {
+  if (!c || !params || !mask || !d2_dev) return ARTP_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> lock(c->mu);
+  ARTP_TRY(clearance_map_args(c, params, n_yaw, nrows, ncols));
+  HIP_TRY(c, hipSetDevice(c->device));
+  const uint32_t* d_mask = mask;
+  if (!mask_on_device) {  // staged through the context's scratch: the host words are read before the call returns
+    const size_t bytes = (size_t)nrows * ncols * sizeof(uint32_t);
+    ARTP_TRY(ensure_tmp(c, 0, bytes));
+    HIP_TRY(c, hipMemcpyAsync(c->tmp[0], mask, bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    d_mask = static_cast<const uint32_t*>(c->tmp[0]);
+  }
+  return clearance_run(c, *params, n_yaw, nrows, ncols, d_mask, d2_dev);
+}
+
+int artp_clearance_map(artp_ctx* c, const artp_clearance_params* params, int n_yaw, int nrows, int ncols, const uint32_t* mask,
+                       int mask_on_device, uint16_t* d2_out) {
+  if (!c || !params || !mask || !d2_out) return ARTP_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> lock(c->mu);
+  ARTP_TRY(clearance_map_args(c, params, n_yaw, nrows, ncols));
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t bytes = (size_t)nrows * ncols * n_yaw * sizeof(uint16_t);
+  ARTP_TRY(ensure_tmp(c, 1, bytes));
+  ARTP_TRY(artp_clearance_map_dev(c, params, n_yaw, nrows, ncols, mask, mask_on_device, static_cast<uint16_t*>(c->tmp[1])));
+  HIP_TRY(c, hipMemcpyAsync(d2_out, c->tmp[1], bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return ARTP_OK;
+}
+
+void artp_field_clearance_params_defaults(artp_field_clearance_params* p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof(*p));
+  artp_field_params_defaults(&p->base);
+  artp_clearance_params_defaults(&p->clearance);
+  p->margin = 0.2;
+  p->gain = 2.0;
+}
+
+int artp_field_compute_clearance(artp_ctx* c, const artp_field_clearance_params* params, int n_yaw, const int* rect,
+                                 const uint32_t* mask, int mask_on_device, const int* sources, size_t n_sources, int reverse,
+                                 artp_field** out) {
+  if (out) *out = nullptr;
+  if (!c || !params || !mask || !sources || !out || n_sources < 1) return ARTP_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> lock(c->mu);
+  if (!reach_have_lattice(c)) return ARTP_ERR_NO_MAP;
+  artp::ReachRect r;
+  ARTP_TRY(reach_resolve(c, n_yaw, rect, &r));
+  ARTP_TRY(field_check_params(c, params->base));
+  if (n_sources > (size_t)1 << 24) {
+    c->last_error = "artp_field_compute_clearance: n_sources <= 2^24";
+    return ARTP_ERR_INVALID_ARG;
+  }
+  ARTP_TRY(clearance_check(c, params->clearance, n_yaw));
+  if (!(params->margin > 0.0) || !std::isfinite(params->margin) || !(params->gain >= 0.0) || !std::isfinite(params->gain)) {
+    c->last_error = "artp_field_compute_clearance: margin must be positive and finite, gain non-negative and finite";
+    return ARTP_ERR_INVALID_ARG;
+  }
+  if (params->margin > (double)params->clearance.radius_cells * c->geom.res) {
+    c->last_error = "artp_field_compute_clearance: margin exceeds radius_cells * resolution (clearance beyond the cap is unknown)";
+    return ARTP_ERR_INVALID_ARG;
+  }
+  ARTP_TRY(field_check_sources(c, r, n_yaw, sources, n_sources));
+  return field_create(c, params->base, nullptr, params, r, mask, mask_on_device, sources, n_sources, reverse, out);
+}
+
+int artp_field_clearance(artp_field* f, uint16_t* d2_out) {
+  if (!f || !d2_out) return ARTP_ERR_INVALID_ARG;
+  artp_ctx* c = f->ctx;
+  std::lock_guard<std::recursive_mutex> lock(c->mu);
+  if (!f->d_d2) {
+    c->last_error = "artp_field_clearance: not a field of artp_field_compute_clearance";
+    return ARTP_ERR_INVALID_ARG;
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipMemcpyAsync(d2_out, f->d_d2, f->n_nodes * sizeof(uint16_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return ARTP_OK;
+}
+
+}  // extern "C"

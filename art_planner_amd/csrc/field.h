@@ -53,6 +53,10 @@
 // artp_field_update_learned: the diff of artp_field_update, then every slot of the table priced
 // again against the context's current network and feature map (field_learned_reprice_kernel: a slot whose bits change is
 // written and flags its tile), then the same four passes, the tiled ones on the streamed table.
+// artp_field_compute_clearance (clearance.h): objective id 3 inside the library.  The weights are the
+// base objective's (0 or 1) inflated near obstacles; they sit in the same table, filled by one kernel without the cost query,
+// and the same table-driven kernels search it (field_has_wtab).  Such a field is not updated in place: a mask edit moves
+// clearances, and with them weights, up to radius_cells around it; artp_field_update and artp_field_update_learned refuse it.
 #pragma once
 
 namespace artp {
@@ -87,6 +91,9 @@ __host__ __device__ inline size_t field_wtab_index(const FieldGrid& G, int r, in
 __host__ __device__ inline size_t field_wtab_slots(const FieldGrid& G) {
   return (size_t)G.tiles_r * G.tiles_c * (size_t)G.n_yaw * 10 * (FIELD_T * FIELD_T);
 }
+
+// Objectives 2 (learned) and 3 (clearance-weighted, clearance.h): the pull weights sit in the per-field table.
+__host__ __device__ inline bool field_has_wtab(const FieldGrid& G) { return G.objective >= 2; }
 
 // cost of translation move m (0..7) from a cell of height ha to one of height hb at heading k; tab in LDS or global
 __device__ __forceinline__ double field_move_cost(const FieldGrid& G, const double* tab, int m, int k, float ha, float hb) {
@@ -182,7 +189,7 @@ __device__ __forceinline__ uint32_t field_slot_bits(const FieldGrid& G, int j) {
 
 // The live neighbours of node (cell, k) over the ten moves, for the kernels with one lane per node: visit(ni, w) with ni
 // the neighbour's node index (its cell and heading) and w() the pull cost of that move, computed when a rule asks
-// (objective 2: read from the weight table, which `tab` then is).
+// (objectives 2 and 3: read from the weight table, which `tab` then is).
 template <class F>
 __device__ __forceinline__ void field_walk(const FieldGrid& G, const uint32_t* __restrict__ mask, const float* __restrict__ h,
                                            const double* __restrict__ tab, const uint16_t* __restrict__ blk, uint32_t cell,
@@ -196,7 +203,7 @@ __device__ __forceinline__ void field_walk(const FieldGrid& G, const uint32_t* _
     const uint32_t ncell = m < 8 ? (uint32_t)nr + (uint32_t)nc * (uint32_t)G.nrows : cell;  // a rotation: the node's own word
     if (!((mask[ncell] >> nk) & 1u)) continue;
     visit((size_t)ncell * G.n_yaw + nk, [&]() {
-      return G.objective == 2 ? tab[field_wtab_index(G, r, c, k, m)] : field_pull_cost(G, tab, m, k, h[cell], h[ncell]);
+      return field_has_wtab(G) ? tab[field_wtab_index(G, r, c, k, m)] : field_pull_cost(G, tab, m, k, h[cell], h[ncell]);
     });
   }
 }
@@ -369,7 +376,7 @@ __device__ __forceinline__ bool field_tile_rule(const FieldGrid& G, const FieldL
 // (writes hops back, and dist in PHASE 0; every change of a rule is a death).  counters[0] += flags set for the next
 // round, [1] += tiles that ran, [2] += nodes that died (all cumulative over the host's loop).  acc collects, over a whole
 // update, the tiles whose own cells or halo an unsupport pass changed: the seeds of the relax pass that follows.
-// LEARNED (objective 2): tabg is the weight table.  It is streamed from global memory, not staged: at 16 headings a tile's
+// LEARNED (objectives 2 and 3): tabg is the weight table.  It is streamed from global memory, not staged: at 16 headings a tile's
 // weights are 328 KB.  The ten loads of a heading are issued in front of that heading's LDS reads.
 // blk (may be nullptr): the blocked words, streamed the same way: one 16-bit load per lane and heading in front of the rule.
 template <int PHASE, bool UNSUP, bool LEARNED = false>
@@ -522,7 +529,7 @@ __device__ __forceinline__ bool field_descend(const FieldGrid& G, const uint32_t
       const size_t ncell = (size_t)nr + (size_t)nc * G.nrows;
       if ((mask[ncell] >> nk) & 1u) {
         const size_t ni = ncell * G.n_yaw + nk;
-        const double w = G.objective == 2 ? tab[field_wtab_index(G, r, c, k, lane)]
+        const double w = field_has_wtab(G) ? tab[field_wtab_index(G, r, c, k, lane)]
                                           : field_pull_cost(G, tab, lane, k, h[cell], h[ncell]);
         ok = hops[ni] + 1u == hv && dist[ni] + w == dv;
       }
@@ -590,7 +597,7 @@ field_edge_cost_kernel(FieldGrid G, const float* __restrict__ h, const double* _
     for (int m = 0; m < 10; ++m) {
       int nr, nc, nk;
       if (!field_neighbour(G, r, c, k, m, &nr, &nc, &nk) || nr != br || nc != bc || nk != bk) continue;
-      if (G.objective == 2)  // the travel-direction cost of a -> b, where the field's direction stores it
+      if (field_has_wtab(G))  // the travel-direction cost of a -> b, where the field's direction stores it
         w = G.reverse ? tab[field_wtab_index(G, r, c, k, m)] : tab[field_wtab_index(G, br, bc, bk, field_back_move(m))];
       else
         w = m < 8 ? field_move_cost(G, tab, m, k, h[(size_t)r + (size_t)c * G.nrows], h[(size_t)br + (size_t)bc * G.nrows])
@@ -825,6 +832,9 @@ struct artp_field {
   // artp_field_compute_learned: d_tab is the weight table (field_wtab_slots doubles); the scratch lives during the build
   artp_field_learned_params lparams{};
   artp_field_learned_stats_t lstats{};
+  // artp_field_compute_clearance (clearance.h): grid.objective = 3, params = the base objective's, d_tab the weight table
+  artp_field_clearance_params cparams{};
+  uint16_t* d_d2 = nullptr;             // the clearance map of the field's own mask, one word per node
   float* d_lscratch = nullptr;          // per chunk: 6 floats of EdgeMatrix row, then 3 floats of answer, per row
   // artp_field_update_learned: d_lscratch stays from the first update on
   unsigned* d_wacc = nullptr;           // n_tiles flags: the tiles a changed weight flagged
@@ -844,7 +854,7 @@ namespace {
 void field_free(artp_field* f) {
   for (void* p : {(void*)f->d_dist, (void*)f->d_hops, (void*)f->d_mask, (void*)f->d_h, (void*)f->d_tab, (void*)f->d_flags,
                   (void*)f->d_nodes, (void*)f->d_out, (void*)f->d_src, (void*)f->d_snap, (void*)f->d_acc, (void*)f->d_ucnt,
-                  (void*)f->d_stage, (void*)f->d_lscratch, (void*)f->d_wacc, (void*)f->d_blk, f->d_plan})
+                  (void*)f->d_stage, (void*)f->d_lscratch, (void*)f->d_wacc, (void*)f->d_blk, (void*)f->d_d2, f->d_plan})
     if (p) (void)hipFree(p);
   delete f;
 }
@@ -947,7 +957,7 @@ int field_pass(artp_field* f, unsigned* d_seed, FieldRounds* out) {
   }
   const size_t lds = artp::field_tile_lds(G.n_yaw, PHASE == 1 || UNSUP);
   auto kernel = &artp::field_tile_kernel<PHASE, UNSUP, false>;
-  if (G.objective == 2) kernel = &artp::field_tile_kernel<PHASE, UNSUP, true>;
+  if (artp::field_has_wtab(G)) kernel = &artp::field_tile_kernel<PHASE, UNSUP, true>;
   // a workgroup may ask for more than 64 KB of dynamic LDS once the function says so (32 headings: 88 / 126 KB)
   if (lds > 64 * 1024)
     HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1046,19 +1056,23 @@ int field_learned_build(artp_ctx* c, artp_field* f) {
   return ARTP_OK;
 }
 
+int field_clearance_build(artp_ctx* c, artp_field* f, const double* tab);  // clearance.h
+
 int field_compute_impl(artp_ctx* c, artp_field* f, const uint32_t* mask, int mask_on_device, const int* sources,
                        size_t n_sources) {
   hipStream_t st = c->stream;
   const artp::FieldGrid& G = f->grid;
-  const bool learned = G.objective == 2;
-  const size_t tab_doubles = learned ? artp::field_wtab_slots(G) : (size_t)artp::FIELD_TAB;
-  if (learned) {  // 80 bytes per node and the padding of the edge tiles, plus a chunk of scratch
+  const bool learned = G.objective == 2, wtab = artp::field_has_wtab(G);
+  const size_t tab_doubles = wtab ? artp::field_wtab_slots(G) : (size_t)artp::FIELD_TAB;
+  if (wtab) {  // 80 bytes per node and the padding of the edge tiles, plus a chunk of query scratch (learned) or d2 (clearance)
     const size_t chunk = tab_doubles < artp::FIELD_LEARNED_CHUNK ? tab_doubles : artp::FIELD_LEARNED_CHUNK;
-    const size_t need = tab_doubles * sizeof(double) + chunk * 9 * sizeof(float) + f->n_nodes * 12 + f->n_cells * 8;
+    const size_t extra = learned ? chunk * 9 * sizeof(float) : f->n_nodes * sizeof(uint16_t) + artp::FIELD_TAB * sizeof(double);
+    const size_t need = tab_doubles * sizeof(double) + extra + f->n_nodes * 12 + f->n_cells * 8;
     size_t free_b = 0, total_b = 0;
     HIP_TRY(c, hipMemGetInfo(&free_b, &total_b));
     if (need > free_b) {
-      c->last_error = "artp_field_compute_learned: the weight table needs " + std::to_string(need >> 20) + " MB, the device has " +
+      c->last_error = std::string(learned ? "artp_field_compute_learned" : "artp_field_compute_clearance") +
+                      ": the weight table needs " + std::to_string(need >> 20) + " MB, the device has " +
                       std::to_string(free_b >> 20) + " MB free";
       return ARTP_ERR_CAPACITY;
     }
@@ -1075,7 +1089,7 @@ int field_compute_impl(artp_ctx* c, artp_field* f, const uint32_t* mask, int mas
   field_make_table(f->params, f->geom, G.n_yaw, tab);
   HIP_TRY(c, hipMemcpyAsync(f->d_mask, mask, f->n_cells * sizeof(uint32_t),
                             mask_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
-  if (!learned) HIP_TRY(c, hipMemcpyAsync(f->d_tab, tab, sizeof(tab), hipMemcpyHostToDevice, st));
+  if (!wtab) HIP_TRY(c, hipMemcpyAsync(f->d_tab, tab, sizeof(tab), hipMemcpyHostToDevice, st));
   HIP_TRY(c, hipMemcpyAsync(f->d_nodes, sources, 3 * n_sources * sizeof(int), hipMemcpyHostToDevice, st));
   f->h_src.assign(sources, sources + 3 * n_sources);  // d_nodes becomes path scratch; artp_field_update needs them
   HIP_TRY(c, hipMemsetAsync(f->d_flags, 0, (2 * f->n_tiles + 4) * sizeof(unsigned), st));
@@ -1096,6 +1110,9 @@ int field_compute_impl(artp_ctx* c, artp_field* f, const uint32_t* mask, int mas
   }
   if (learned) {
     rc = field_learned_build(c, f);
+    if (rc) return rc;
+  } else if (wtab) {
+    rc = field_clearance_build(c, f, tab);
     if (rc) return rc;
   }
   FieldRounds dist_pass, hop_pass;
@@ -1192,8 +1209,23 @@ int field_check_sources(artp_ctx* c, const artp::ReachRect& r, int n_yaw, const 
   return ARTP_OK;
 }
 
-int field_create(artp_ctx* c, const artp_field_params& params, const artp_field_learned_params* lp, const artp::ReachRect& r,
-                 const uint32_t* mask, int mask_on_device, const int* sources, size_t n_sources, int reverse, artp_field** out);
+// what artp_field_compute refuses about its params
+int field_check_params(artp_ctx* c, const artp_field_params& p) {
+  if (p.objective != 0 && p.objective != 1) {
+    c->last_error = "artp_field_compute: objective must be 0 or 1 (the learned objective has no lattice form)";
+    return ARTP_ERR_INVALID_ARG;
+  }
+  if (!(p.max_lon_vel > 0.0) || !(p.max_lat_vel > 0.0) || !(p.max_ang_vel > 0.0) || !std::isfinite(p.max_lon_vel) ||
+      !std::isfinite(p.max_lat_vel) || !std::isfinite(p.max_ang_vel) || p.inner_sweeps < 1) {
+    c->last_error = "artp_field_compute: velocities must be positive and finite, inner_sweeps >= 1, n_sources <= 2^24";
+    return ARTP_ERR_INVALID_ARG;
+  }
+  return ARTP_OK;
+}
+
+int field_create(artp_ctx* c, const artp_field_params& params, const artp_field_learned_params* lp,
+                 const artp_field_clearance_params* cp, const artp::ReachRect& r, const uint32_t* mask, int mask_on_device,
+                 const int* sources, size_t n_sources, int reverse, artp_field** out);
 
 }  // namespace
 
@@ -1219,19 +1251,15 @@ int artp_field_compute(artp_ctx* c, const artp_field_params* params, int n_yaw, 
   artp::ReachRect r;
   int rc = reach_resolve(c, n_yaw, rect, &r);
   if (rc) return rc;
-  if (params->objective != 0 && params->objective != 1) {
-    c->last_error = "artp_field_compute: objective must be 0 or 1 (the learned objective has no lattice form)";
-    return ARTP_ERR_INVALID_ARG;
-  }
-  if (!(params->max_lon_vel > 0.0) || !(params->max_lat_vel > 0.0) || !(params->max_ang_vel > 0.0) ||
-      !std::isfinite(params->max_lon_vel) || !std::isfinite(params->max_lat_vel) || !std::isfinite(params->max_ang_vel) ||
-      params->inner_sweeps < 1 || n_sources > (size_t)1 << 24) {
+  rc = field_check_params(c, *params);
+  if (rc) return rc;
+  if (n_sources > (size_t)1 << 24) {
     c->last_error = "artp_field_compute: velocities must be positive and finite, inner_sweeps >= 1, n_sources <= 2^24";
     return ARTP_ERR_INVALID_ARG;
   }
   rc = field_check_sources(c, r, n_yaw, sources, n_sources);
   if (rc) return rc;
-  return field_create(c, *params, nullptr, r, mask, mask_on_device, sources, n_sources, reverse, out);
+  return field_create(c, *params, nullptr, nullptr, r, mask, mask_on_device, sources, n_sources, reverse, out);
 }
 
 void artp_field_learned_params_defaults(artp_field_learned_params* p) {
@@ -1282,7 +1310,7 @@ int artp_field_compute_learned(artp_ctx* c, const artp_field_learned_params* par
   fp.objective = 2;
   fp.plain_sweeps = params->plain_sweeps;
   fp.inner_sweeps = params->inner_sweeps;
-  return field_create(c, fp, params, r, mask, mask_on_device, sources, n_sources, reverse, out);
+  return field_create(c, fp, params, nullptr, r, mask, mask_on_device, sources, n_sources, reverse, out);
 }
 
 int artp_field_learned_stats(artp_field* f, artp_field_learned_stats_t* out) {
@@ -1295,15 +1323,18 @@ int artp_field_learned_stats(artp_field* f, artp_field_learned_stats_t* out) {
 
 namespace {
 
-// the part of artp_field_compute and artp_field_compute_learned behind their checks (lp: objective 2 only)
-int field_create(artp_ctx* c, const artp_field_params& params, const artp_field_learned_params* lp, const artp::ReachRect& r,
-                 const uint32_t* mask, int mask_on_device, const int* sources, size_t n_sources, int reverse, artp_field** out) {
+// the part of artp_field_compute, _learned and _clearance behind their checks (lp: objective 2 only; cp: the clearance
+// field, params = its base objective's)
+int field_create(artp_ctx* c, const artp_field_params& params, const artp_field_learned_params* lp,
+                 const artp_field_clearance_params* cp, const artp::ReachRect& r, const uint32_t* mask, int mask_on_device,
+                 const int* sources, size_t n_sources, int reverse, artp_field** out) {
   const int n_yaw = r.n_yaw;
   HIP_TRY(c, hipSetDevice(c->device));
   artp_field* f = new artp_field;
   f->ctx = c;
   f->params = params;
   if (lp) f->lparams = *lp;
+  if (cp) f->cparams = *cp;
   f->rect = r;
   f->geom = c->geom;
   f->sampler = c->sampler;
@@ -1316,7 +1347,7 @@ int field_create(artp_ctx* c, const artp_field_params& params, const artp_field_
   G.n_yaw = n_yaw;
   G.tiles_r = (r.nrows + artp::FIELD_T - 1) / artp::FIELD_T;
   G.tiles_c = (r.ncols + artp::FIELD_T - 1) / artp::FIELD_T;
-  G.objective = params.objective;
+  G.objective = cp ? 3 : params.objective;
   G.reverse = reverse ? 1 : 0;
   G.yaw_bits = n_yaw == 32 ? 0xffffffffu : (1u << n_yaw) - 1u;
   G.vlon = params.max_lon_vel;
@@ -1442,6 +1473,11 @@ int artp_field_update(artp_field* f, const uint32_t* new_mask, int mask_on_devic
   artp_ctx* c = f->ctx;
   std::lock_guard<std::recursive_mutex> lock(c->mu);
   const artp::FieldGrid& G = f->grid;
+  if (G.objective == 3) {
+    c->last_error = "artp_field_update: a clearance-weighted field is not updated in place (a mask edit moves clearances, and "
+                    "with them the weights, up to radius_cells around it): compute a new one";
+    return ARTP_ERR_INVALID_ARG;
+  }
   if (G.objective == 2) {
     c->last_error = "artp_field_update: a learned field is not updated by a mask edit alone (a map change moves the network's "
                     "features, and with them the weights, far beyond sub_rect): artp_field_update_learned prices it again";

@@ -34,6 +34,25 @@ class CostField:
                       reverse)
         return self
 
+    @classmethod
+    def clearance_weighted(cls, ctx, mask, n_yaw, sources, margin=0.2, gain=2.0, radius_cells=12, yaw_spread=0,
+                           outside_is_obstacle=False, rect=None, reverse=False, objective=1, max_lon_vel=0.5,
+                           max_lat_vel=0.1, max_ang_vel=0.5, plain_sweeps=False, inner_sweeps=64):
+        """The field whose move costs are the objective's, inflated near obstacles (artp_field_compute_clearance,
+        DESIGN.md section 17)."""
+        self = cls.__new__(cls)
+        p = _capi.FieldClearanceParams()
+        ctx.L.artp_field_clearance_params_defaults(C.byref(p))
+        b = p.base
+        b.objective, b.plain_sweeps, b.inner_sweeps = int(objective), int(bool(plain_sweeps)), int(inner_sweeps)
+        b.max_lon_vel, b.max_lat_vel, b.max_ang_vel = max_lon_vel, max_lat_vel, max_ang_vel
+        p.clearance.radius_cells, p.clearance.yaw_spread = int(radius_cells), int(yaw_spread)
+        p.clearance.outside_is_obstacle = int(bool(outside_is_obstacle))
+        p.margin, p.gain = float(margin), float(gain)
+        self._compute(ctx, ctx.L.artp_field_compute_clearance, "artp_field_compute_clearance", p, mask, n_yaw, sources, rect,
+                      reverse)
+        return self
+
     def _compute(self, ctx, call, name, params, mask, n_yaw, sources, rect, reverse):
         """The mask and source handling both constructors share; call = the C entry point, params = its struct."""
         self.ctx = ctx
@@ -83,6 +102,13 @@ class CostField:
         """(nrows, ncols, n_yaw) float64; +inf where the node does not exist or cannot be reached."""
         out = np.empty((self.ncols, self.nrows, self.n_yaw), np.float64)
         self.ctx._chk(self.L.artp_field_dist(self.h, out.ctypes.data), "artp_field_dist")
+        return out.transpose(1, 0, 2)
+
+    def clearance(self) -> np.ndarray:
+        """(nrows, ncols, n_yaw) uint16: the clearance map d2 of a clearance-weighted field (artp_field_clearance); any
+        other field is refused."""
+        out = np.empty((self.ncols, self.nrows, self.n_yaw), np.uint16)
+        self.ctx._chk(self.L.artp_field_clearance(self.h, out.ctypes.data), "artp_field_clearance")
         return out.transpose(1, 0, 2)
 
     def dist_dev(self):

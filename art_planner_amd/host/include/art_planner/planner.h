@@ -422,6 +422,67 @@ class Planner {
     return finishCostField(f, cells, n_yaw, keep);
   }
 
+  // How far every node of a reachability mask is from the nearest cell where its heading -- and yaw_spread neighbours on
+  // either side -- is not a valid pose (artp_clearance_map, include/artp_c.h): d2, index (r + c rows) n_yaw + k, the exact
+  // squared distance in cells; 0 = not a node, 0xffff = nothing within radius_cells.  The clearance in metres is
+  // res * sqrt(d2).
+  std::vector<uint16_t> computeClearance(const std::vector<uint32_t>& mask, unsigned n_yaw, int radius_cells = 12,
+                                         int yaw_spread = 0, bool outside_is_obstacle = false) {
+    std::lock_guard<std::mutex> lock(map_mutex_);
+    if (!map_) throw std::runtime_error("computeClearance: the planner does not have a map set");
+    const auto g = map_->getGeometry();
+    const size_t cells = static_cast<size_t>(g.rows) * g.cols;
+    if (mask.size() != cells) throw std::runtime_error("computeClearance: the mask does not have rows * cols words");
+    artp_clearance_params cp;
+    artp_clearance_params_defaults(&cp);
+    cp.radius_cells = radius_cells;
+    cp.yaw_spread = yaw_spread;
+    cp.outside_is_obstacle = outside_is_obstacle ? 1 : 0;
+    std::vector<uint16_t> d2(cells * (n_yaw >= 1 && n_yaw <= 32 ? n_yaw : 1));
+    throwOnError(gpu_->get(),
+                 artp_clearance_map(gpu_->get(), &cp, static_cast<int>(n_yaw), g.rows, g.cols, mask.data(), 0, d2.data()),
+                 "artp_clearance_map");
+    return d2;
+  }
+
+  // computeCostField with every move's cost inflated near obstacles (artp_field_compute_clearance, include/artp_c.h):
+  // w(a -> b) = base (1 + gain max(pen(a), pen(b))), pen(v) = max(0, 1 - res sqrt(d2[v]) / margin) with d2 the clearance
+  // map of the mask; margin (metres) may not exceed radius_cells * res; gain = 0 gives computeCostField's bits.  A kept
+  // field works with blockCostFieldMoves, unblockCostField and planOnCostField; updateCostField and
+  // updateLearnedCostField are refused (a mask edit moves clearances up to radius_cells around it): compute a new one.
+  // Refreshes the "cost_to_go" layer.
+  std::vector<double> computeClearanceCostField(const std::vector<uint32_t>& mask, unsigned n_yaw,
+                                                const std::vector<std::array<int, 3>>& sources, double margin = 0.2,
+                                                double gain = 2.0, int radius_cells = 12, int yaw_spread = 0,
+                                                bool outside_is_obstacle = false, bool reverse = false,
+                                                artp_field** keep = nullptr) {
+    std::lock_guard<std::mutex> lock(map_mutex_);
+    if (!map_) throw std::runtime_error("computeClearanceCostField: the planner does not have a map set");
+    const auto g = map_->getGeometry();
+    const size_t cells = static_cast<size_t>(g.rows) * g.cols;
+    if (mask.size() != cells) throw std::runtime_error("computeClearanceCostField: the mask does not have rows * cols words");
+    artp_field_clearance_params fp;
+    artp_field_clearance_params_defaults(&fp);
+    const auto& cpl = params_->objectives.custom_path_length;
+    fp.base.objective = cpl.use_directional_cost ? 1 : 0;
+    fp.base.max_lon_vel = cpl.max_lon_vel;
+    fp.base.max_lat_vel = cpl.max_lat_vel;
+    fp.base.max_ang_vel = cpl.max_ang_vel;
+    fp.clearance.radius_cells = radius_cells;
+    fp.clearance.yaw_spread = yaw_spread;
+    fp.clearance.outside_is_obstacle = outside_is_obstacle ? 1 : 0;
+    fp.margin = margin;
+    fp.gain = gain;
+    std::vector<int> src;
+    for (const auto& s : sources) src.insert(src.end(), s.begin(), s.end());
+    artp_field* f = nullptr;
+    throwOnError(gpu_->get(),
+                 artp_field_compute_clearance(gpu_->get(), &fp, static_cast<int>(n_yaw), nullptr, mask.data(), 0, src.data(),
+                                              sources.size(), reverse ? 1 : 0, &f),
+                 "artp_field_compute_clearance");
+    return finishCostField(f, cells, n_yaw, keep);
+  }
+
   // The field a computeCostField call kept, brought in place to an edited mask (artp_field_update, include/artp_c.h):
   // the same bits as computeCostField on it, at the price of the region whose costs change.  mask = rows * cols words;
   // rect = (row0, col0, nrows, ncols) of the words that may differ (nullptr = all of them; the others are not read).

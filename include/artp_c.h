@@ -289,7 +289,8 @@ int artp_field_stats(artp_field* f, artp_field_stats_t* out);
  * heights (the current ones where refreshed, the old ones elsewhere).  Where the context's map still has the geometry the
  * field was computed on, the poses of artp_field_path are those of the current sampler layers, as a new field's would be.
  * ARTP_ERR_INVALID_ARG with the field untouched: a source is no longer a node of the merged mask, sub_rect is empty or not
- * inside the rectangle, refresh_heights without sampler layers of the geometry the field was computed on.
+ * inside the rectangle, refresh_heights without sampler layers of the geometry the field was computed on, a learned or a
+ * clearance-weighted field (artp_field_compute_learned, artp_field_compute_clearance: see there).
  * Every launch is bounded; the round caps are artp_field_compute's.  Synchronous, on the context's current stream. */
 typedef struct artp_field_update_stats_t {
   uint64_t changed_words;    /* words of sub_rect that differ in their low n_yaw bits */
@@ -437,6 +438,66 @@ int artp_field_plan_stats(artp_field* f, artp_field_plan_stats_t* out);
 /* Per round of that call: the tiles that ran in the round's repair (0 for a round that blocked nothing, and in the plain
  * form).  *n_rounds = the rounds; runs_out (may be NULL with cap = 0) takes the first cap of them. */
 int artp_field_plan_round_tile_runs(artp_field* f, uint64_t* runs_out, size_t cap, size_t* n_rounds);
+
+/* ---- Clearance maps and clearance-weighted fields -------------------------------------------
+ * A cost-to-go field finds the CHEAPEST lattice path, and under PathLengthObjective that path hugs the boundary of the
+ * valid set.  A clearance map measures how far every node is from that boundary; a clearance-weighted field prefers to
+ * keep away from it.  (The reference declares MinClearanceObjective, objectives/min_clearance_objective.h, but none of its
+ * checkers implements clearance(); here the reachability mask is the data.)
+ *
+ * artp_clearance_map: mask = nrows x ncols words, column-major, the layout of artp_reachability_map; only the low n_yaw
+ * bits (1 <= n_yaw <= 32) count, higher bits may hold anything.  OBSTACLE SET of heading k: a cell of the rectangle whose
+ * word has ANY of the bits k - yaw_spread .. k + yaw_spread (mod n_yaw) clear (yaw_spread = 0: bit k is clear;
+ * yaw_spread = n_yaw / 2: any heading is clear); the cells outside the rectangle are obstacles of every heading iff
+ * outside_is_obstacle, and ignored otherwise.  d2[(r + c nrows) n_yaw + k] (uint16, the node order of artp_field_dist):
+ *   0        bit k of the node's own word is clear (not a node)
+ *   else     the minimum of dr^2 + dc^2 over the obstacles of heading k with dr^2 + dc^2 <= radius_cells^2; offset (0, 0)
+ *            counts, so a node can have d2 = 0 when yaw_spread >= 1
+ *   0xffff   no such obstacle
+ * The value is an exact integer; the clearance in metres is res sqrt(d2).  Needs no installed map, only the context for
+ * its stream.  ARTP_ERR_INVALID_ARG, with nothing computed: n_yaw outside [1, 32], radius_cells outside [1, 32],
+ * yaw_spread outside [0, n_yaw / 2], outside_is_obstacle not 0 or 1, nrows or ncols < 1, nrows * ncols * n_yaw >= 2^32.
+ * Host form (d2_out in host memory): synchronous.  _dev form (d2_dev in device memory): asynchronous on the context's
+ * current stream; a host mask (mask_on_device = 0) is copied before either form returns. */
+typedef struct artp_clearance_params {
+  int32_t radius_cells;        /* R: the cap of the search, 1 .. 32 (default 12) */
+  int32_t yaw_spread;          /* s: neighbouring headings that must be valid too, 0 .. n_yaw / 2 (default 0) */
+  int32_t outside_is_obstacle; /* 0 (default) or 1 */
+  int32_t reserved;
+} artp_clearance_params;
+void artp_clearance_params_defaults(artp_clearance_params* p);
+int artp_clearance_map(artp_ctx* ctx, const artp_clearance_params* params, int n_yaw, int nrows, int ncols,
+                       const uint32_t* mask, int mask_on_device, uint16_t* d2_out);
+int artp_clearance_map_dev(artp_ctx* ctx, const artp_clearance_params* params, int n_yaw, int nrows, int ncols,
+                           const uint32_t* mask, int mask_on_device, uint16_t* d2_dev);
+/* artp_field_compute_clearance: the graph, rules and results of artp_field_compute with `base` (objective 0 or 1, heights
+ * included), every move priced in f64, in this order of operations, as
+ *   w(a -> b) = base(a -> b) (1.0 + gain max(pen(a), pen(b)))
+ *   pen(v)    = 0 if d2[v] == 0xffff, else max(0.0, 1.0 - (res sqrt((double)d2[v])) / margin)
+ * with d2 = the clearance map of the field's own mask under `clearance` and res = the resolution of the installed map.
+ * gain = 0 makes the factor exactly 1.0: the field then equals artp_field_compute's bit for bit.  The weights live in the
+ * per-field table of the learned field (80 bytes per node, edge tiles padded; ARTP_ERR_CAPACITY, with a text, when the
+ * device has not that much memory free) and the field is searched by the same kernels; it also keeps d2 (2 bytes per node).
+ * The result is an ordinary artp_field: artp_field_dist, _dist_dev, _path, _edge_costs, _stats, _block_moves, _unblock,
+ * _blocked*, _plan and _destroy work on it unchanged.  artp_field_learned_stats reports its table (table_rows, table_bytes),
+ * rows_ms = the device time of the clearance map, combine_ms = that of the table build, chunks = 0, query_ms = 0.
+ * It is NOT updated in place: a mask edit moves clearances, and with them weights, up to radius_cells around it.
+ * artp_field_update and artp_field_update_learned refuse it with ARTP_ERR_INVALID_ARG and leave it untouched.
+ * ARTP_ERR_INVALID_ARG, with nothing computed: what artp_clearance_map refuses about n_yaw, radius_cells, yaw_spread and
+ * outside_is_obstacle; margin not positive or not finite; margin > radius_cells res (clearance beyond the cap is unknown);
+ * gain negative or not finite; everything artp_field_compute refuses.  ARTP_ERR_NO_MAP as artp_field_compute. */
+typedef struct artp_field_clearance_params {
+  artp_field_params base;          /* artp_field_params_defaults */
+  artp_clearance_params clearance; /* artp_clearance_params_defaults */
+  double margin;                   /* metres: the penalty falls from 1 at an obstacle to 0 at this clearance (default 0.2) */
+  double gain;                     /* the factor at an obstacle is 1 + gain (default 2.0) */
+} artp_field_clearance_params;
+void artp_field_clearance_params_defaults(artp_field_clearance_params* p);
+int artp_field_compute_clearance(artp_ctx* ctx, const artp_field_clearance_params* params, int n_yaw, const int rect[4],
+                                 const uint32_t* mask, int mask_on_device, const int* sources, size_t n_sources, int reverse,
+                                 artp_field** out);
+/* the field's own d2 (nrows * ncols * n_yaw words on the host, index as dist); ARTP_ERR_INVALID_ARG for any other field */
+int artp_field_clearance(artp_field* f, uint16_t* d2_out);
 
 /* ---- ob::MotionValidator::checkMotion (OMPL DiscreteMotionValidator; call sites
  *      prm_motion_cost.cpp:652, lazy_prm_star_min_update.cpp:725), batched -----------------------
