@@ -1293,7 +1293,12 @@ static int upload_layer_from_device(artp_ctx* c, int slot, const float* d_layer,
   HIP_TRY(c, hipSetDevice(c->device));
   const size_t elems = (size_t)rows * cols;
   const FieldDev& f0 = c->field[slot];
-  const bool same_geometry = c->have_field[slot] && c->have_geom && f0.nW == rows && f0.nD == cols &&
+  // c->geom is shared by both slots: once the other slot has moved to a new position or size it already holds the new
+  // values while THIS slot's frame (finish_layer: width, depth, pos) still stands at the old ones, so the slot's own
+  // frame is compared as well -- a map that moved takes the full path and gets its frame set.
+  const bool same_frame = f0.width == (float)len_x && f0.depth == (float)len_y && f0.pos[0] == (float)pos_x &&
+                          f0.pos[1] == (float)pos_y;
+  const bool same_geometry = c->have_field[slot] && c->have_geom && f0.nW == rows && f0.nD == cols && same_frame &&
                              c->geom.len_x == len_x && c->geom.len_y == len_y && c->geom.pos_x == pos_x &&
                              c->geom.pos_y == pos_y && c->tables[slot].valid && c->field_elems[slot] >= elems;
   {

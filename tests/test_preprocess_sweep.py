@@ -90,7 +90,7 @@ def contexts():
         c.close()
 
 
-def _inputs(pt, seed=0):
+def _inputs(pt, seed=0, pos=POS):
     rows, cols = pt["shape"]
     res = pt["res"]
     elev, trav = P.sweep_map(rows, cols, res, seed=seed + rows + cols)
@@ -99,13 +99,13 @@ def _inputs(pt, seed=0):
         obs = np.ones((rows, cols), F32)
         obs[:, : max(cols // 4, 1)] = 0.0                      # unobserved strips
         obs[rows // 2: rows // 2 + max(rows // 8, 1), :] = 0.0
-    verts = P.sweep_vertices(rows, cols, res, *POS, seed=seed) if pt["verts"] else None
+    verts = P.sweep_vertices(rows, cols, res, *pos, seed=seed) if pt["verts"] else None
     return elev, (trav if pt["trav"] else None), obs, verts
 
 
-def _device(ctx, pt, elev, trav, obs, verts):
+def _device(ctx, pt, elev, trav, obs, verts, pos=POS):
     rows, cols = elev.shape
-    return ctx.preprocess_map(elev, rows * pt["res"], cols * pt["res"], *POS, traversability=trav, kind=pt["kind"],
+    return ctx.preprocess_map(elev, rows * pt["res"], cols * pt["res"], *pos, traversability=trav, kind=pt["kind"],
                               observed=obs, vertices=verts, **pt["over"])
 
 
@@ -123,19 +123,20 @@ def _compare(pp, L, tag):
     return got, bad
 
 
-def _expected(name):
-    """The restated layers of one point, after checking that the point reaches what it is there for."""
+def _expected(name, pos=POS):
+    """The restated layers of one point at map position pos, after checking that the point reaches what it is there
+    for."""
     pt = POINTS[name]
     rows, cols = pt["shape"]
     res = pt["res"]
     prm = P.params(pt["kind"], **pt["over"])
     rob = P.robot(pt["robot"], unknown_space_untraversable=pt["untrav"])
-    geom = (rows * res, cols * res) + POS
+    geom = (rows * res, cols * res) + tuple(pos)
     # the point reaches the footprint sizes it is there for
     sz = P.sizes(prm, P.cell_size(rows, geom[0]))
     for k, v in pt["disks"].items():
         assert sz[k] == v, (k, sz)
-    elev, trav, obs, verts = _inputs(pt)
+    elev, trav, obs, verts = _inputs(pt, pos=pos)
     L = P.preprocess(elev, *geom, traversability=trav, observed=obs, vertices=verts, prm=prm, rob=rob)
     if min(rows, cols) >= 32:    # the comparison cannot pass on an all-pass map
         for what in ("_hole", "_wall", "_keep"):
@@ -152,12 +153,9 @@ def _expected(name):
     return pt, prm, rob, geom, (elev, trav, obs, verts), L
 
 
-@pytest.mark.parametrize("name", list(POINTS))
-def test_preprocessing_is_bit_equal_to_the_restatement(contexts, name):
-    pt, prm, rob, geom, (elev, trav, obs, verts), L = _expected(name)
-    pp = _device(contexts(pt["robot"], pt["untrav"]), pt, elev, trav, obs, verts)
-    got, bad = _compare(pp, L, name)
-    # the device within the float64 bounds
+def _float64_violations(got, L, elev, geom, prm, rob):
+    """The device's floating-point layers against the float64 reference's derived bounds: the layers outside them."""
+    bad = []
     Ld = dict(L)
     Ld["sample_probability"] = got["sample_probability"]
     R = P.reference64(Ld, elev, geom, prm, rob)
@@ -173,12 +171,29 @@ def test_preprocessing_is_bit_equal_to_the_restatement(contexts, name):
         bad.append("float64:cum_prob")
     if not P.within(got["cum_prob_rowwise"], R["cum_prob_rowwise"], R["cum_prob_rowwise_tol"]):
         bad.append("float64:cum_prob_rowwise")
+    return bad
+
+
+def _check_point(contexts, name, pos=POS, float64=True, expected=None):
+    """One point at map position pos: every layer bit-equal to the restatement (expected: what _expected(name, pos)
+    returned, if the caller has it) and, where float64 is set, the device within the float64 bounds.  Returns the number
+    of compared cells."""
+    pt, prm, rob, geom, (elev, trav, obs, verts), L = expected or _expected(name, pos)
+    pp = _device(contexts(pt["robot"], pt["untrav"]), pt, elev, trav, obs, verts, pos)
+    got, bad = _compare(pp, L, name)
+    if float64:
+        bad += _float64_violations(got, L, elev, geom, prm, rob)
     pp.close()
     assert not bad, bad
+    return sum(got[k].size for k in LAYERS)
 
 
-@pytest.mark.parametrize("shape", [(97, 61), (61, 97)])
-def test_change_from_on_shifted_non_square_maps(contexts, shape):
+@pytest.mark.parametrize("name", list(POINTS))
+def test_preprocessing_is_bit_equal_to_the_restatement(contexts, name):
+    _check_point(contexts, name)
+
+
+def _check_change_from(contexts, shape, pos=POS, shifts=((0, 0), (3, -2), (-4, 5), (None, -1), (2, None))):
     """computeChange between maps whose origins differ by (+-k, -+m) cells and by more than the map: the updated layer,
     its rectangle and its count are exact; the partial last wavefront of change_kernel's reduction is in play
     (rows * cols is no multiple of 64)."""
@@ -187,15 +202,16 @@ def test_change_from_on_shifted_non_square_maps(contexts, shape):
     ctx = contexts()
     elev, trav = P.sweep_map(rows, cols, res, seed=3)
     len_x, len_y = rows * res, cols * res
-    old = ctx.preprocess_map(elev, len_x, len_y, *POS, traversability=trav)
+    shifts = [(rows + 3 if si is None else si, -(cols + 1) if sj is None else sj) for si, sj in shifts]
+    old = ctx.preprocess_map(elev, len_x, len_y, *pos, traversability=trav)
     e2 = elev.copy()
     e2[10:20, 5:17] += F32(0.2)
     t2 = trav.copy()
     t2[40:50, 30:40] = 0.0
     upd, rect, cnt = old.change_from(old, 0.05)
     assert cnt == 0 and rect == (0, 0, 0, 0) and not upd.any()
-    for si, sj in [(0, 0), (3, -2), (-4, 5), (rows + 3, -1), (2, -(cols + 1))]:
-        new = ctx.preprocess_map(e2, len_x, len_y, POS[0] + si * res, POS[1] + sj * res, traversability=t2)
+    for si, sj in shifts:
+        new = ctx.preprocess_map(e2, len_x, len_y, pos[0] + si * res, pos[1] + sj * res, traversability=t2)
         upd, rect, cnt = new.change_from(old, 0.05)
         eu, erect, ecnt = P.change(new.layer("elevation"), new.layer("traversability_thresholded"),
                                    old.layer("elevation"), old.layer("traversability_thresholded"), si, sj, 0.05)
@@ -208,6 +224,11 @@ def test_change_from_on_shifted_non_square_maps(contexts, shape):
             assert cnt == rows * cols and rect == (0, 0, rows, cols)
         new.close()
     old.close()
+
+
+@pytest.mark.parametrize("shape", [(97, 61), (61, 97)])
+def test_change_from_on_shifted_non_square_maps(contexts, shape):
+    _check_change_from(contexts, shape)
 
 
 def test_reweight_equals_a_fresh_preprocessing(contexts):
