@@ -308,8 +308,8 @@ class Context:
         w(a -> b) = base (1 + gain max(pen(a), pen(b))), pen(v) = max(0, 1 - res sqrt(d2[v]) / margin) with d2 the
         clearance_map of the mask (0 where nothing lies within radius_cells).  margin (metres) may not exceed
         radius_cells * resolution.  gain = 0 gives cost_field's bits.  Returns a CostField: dist, path, edge_costs,
-        block_moves, unblock and plan work unchanged, .clearance() hands out d2; update() and update_learned() are
-        refused (a mask edit moves clearances up to radius_cells around it): compute a new field."""
+        block_moves, unblock and plan work unchanged, .clearance() hands out d2; update() and update_learned() refuse it
+        (a mask edit moves clearances up to radius_cells around it), update_clearance() updates it in place."""
         from .field import CostField
         return CostField.clearance_weighted(self, mask, n_yaw, sources, margin=margin, gain=gain, radius_cells=radius_cells,
                                             yaw_spread=yaw_spread, outside_is_obstacle=outside_is_obstacle, rect=rect,

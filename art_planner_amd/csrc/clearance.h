@@ -16,7 +16,16 @@
 //                                 artp_field_compute in the field's direction (field_pull_cost) times
 //                                 1 + gain max(pen(a), pen(b)), pen(v) = max(0, 1 - res sqrt(d2[v]) / margin), 0 at 0xffff.
 // The field (objective id 3 inside the library) is searched by the table-driven kernels of the learned field, unchanged.
-// It is not updated in place: a mask edit moves clearances up to R cells around it (artp_field_update* refuse it).
+// artp_field_update_clearance brings such a field to an edited mask in place: the diff of
+// artp_field_update, then
+//   clearance_window_kernel          clearance_map_kernel's tile (clearance_tile, the one body of both) on the tiles that
+//                                    intersect sub_rect grown by R cells, written into the field's own d2; counts the
+//                                    nodes whose value changed
+//   field_clearance_reprice_kernel   field_clearance_table_kernel's price (field_clearance_price, shared) on the tiles
+//                                    that intersect sub_rect grown by R + 1 cells, against the slot's old bit pattern: a
+//                                    slot that differs is written and flags its tile, as field_learned_reprice_kernel does
+// and the four passes of artp_field_update from the flagged tiles.  artp_field_update and artp_field_update_learned
+// refuse the field.
 #pragma once
 
 namespace artp {
@@ -52,15 +61,17 @@ __device__ __forceinline__ uint32_t clearance_erode(uint32_t w, int n, int s, ui
   return e & yaw_bits;
 }
 
-// offs[i] = (dr + dc S) << 16 | d2 of the i-th offset of the disc, d2 ascending, (0, 0) first
-__global__ void __launch_bounds__(256)
-clearance_map_kernel(ClearGrid G, const uint32_t* __restrict__ mask, const int32_t* __restrict__ offs, uint16_t* __restrict__ d2) {
+// The tile whose first cell is (r0, c0), by its workgroup.  offs[i] = (dr + dc S) << 16 | d2 of the i-th offset of the
+// disc, d2 ascending, (0, 0) first.  COUNT = false: every node of the tile is written.  COUNT = true (the update's
+// window): d2 holds an earlier map; only a word that differs is written, and *changed += their number, one atomic per wave.
+template <bool COUNT>
+__device__ __forceinline__ void clearance_tile(const ClearGrid& G, const uint32_t* __restrict__ mask,
+                                               const int32_t* __restrict__ offs, uint16_t* __restrict__ d2, int r0, int c0,
+                                               unsigned long long* __restrict__ changed) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   uint32_t* win = reinterpret_cast<uint32_t*>(smem);
   uint16_t* stage = reinterpret_cast<uint16_t*>(win + (size_t)G.S * G.W);
   const int tid = threadIdx.x;
-  const int tile = blockIdx.x;
-  const int r0 = (tile % G.tiles_r) * FIELD_T, c0 = (tile / G.tiles_r) * FIELD_T;
   const int ny = G.n_yaw;
 
   for (int e = tid; e < G.W * G.W; e += 256) {
@@ -102,12 +113,43 @@ clearance_map_kernel(ClearGrid G, const uint32_t* __restrict__ mask, const int32
   }
   __syncthreads();
 
+  unsigned n_changed = 0;  // COUNT: of this wave (the loop's trip count is the same for every lane of the workgroup)
   for (int e = tid; e < FIELD_T * FIELD_T * ny; e += 256) {
     const int ci = e / ny, k = e - ci * ny;
     const int r = r0 + (ci & (FIELD_T - 1)), c = c0 + (ci >> 4);
-    if (r >= G.nrows || c >= G.ncols) continue;
-    d2[((size_t)r + (size_t)c * G.nrows) * ny + k] = stage[k * CLEAR_PITCH + ci];
+    const bool inside = r < G.nrows && c < G.ncols;
+    if (!COUNT) {
+      if (inside) d2[((size_t)r + (size_t)c * G.nrows) * ny + k] = stage[k * CLEAR_PITCH + ci];
+      continue;
+    }
+    bool ch = false;
+    if (inside) {
+      const size_t node = ((size_t)r + (size_t)c * G.nrows) * ny + k;
+      const uint16_t v = stage[k * CLEAR_PITCH + ci];
+      ch = d2[node] != v;
+      if (ch) d2[node] = v;
+    }
+    n_changed += (unsigned)__popcll(__ballot(ch));
   }
+  if (COUNT && n_changed && (tid & 63) == 0) atomicAdd(changed, (unsigned long long)n_changed);
+}
+
+// the whole rectangle: workgroup = tile, in field.h's order of tiles
+__global__ void __launch_bounds__(256)
+clearance_map_kernel(ClearGrid G, const uint32_t* __restrict__ mask, const int32_t* __restrict__ offs, uint16_t* __restrict__ d2) {
+  const int tile = blockIdx.x;
+  clearance_tile<false>(G, mask, offs, d2, (tile % G.tiles_r) * FIELD_T, (tile / G.tiles_r) * FIELD_T, nullptr);
+}
+
+// A window of tiles of a rectangle (artp_field_update_clearance): wn_r x (gridDim.x / wn_r) tiles from tile (t_r0, t_c0).
+struct ClearWindow {
+  int t_r0, t_c0, wn_r;
+};
+__global__ void __launch_bounds__(256)
+clearance_window_kernel(ClearGrid G, ClearWindow w, const uint32_t* __restrict__ mask, const int32_t* __restrict__ offs,
+                        uint16_t* __restrict__ d2, unsigned long long* __restrict__ changed) {
+  const int b = blockIdx.x;
+  clearance_tile<true>(G, mask, offs, d2, (w.t_r0 + b % w.wn_r) * FIELD_T, (w.t_c0 + b / w.wn_r) * FIELD_T, changed);
 }
 
 struct ClearWeight {
@@ -120,23 +162,52 @@ __device__ __forceinline__ double clearance_pen(const ClearWeight& p, uint16_t d
 }
 
 // G carries the BASE objective (0 or 1) here: field_pull_cost prices with it.  tab: the (m, k) table of that objective.
+// The weight of slot s of the table, for the build and for the update's repricing: +inf where the edge does not exist.
+__device__ __forceinline__ double field_clearance_price(const FieldGrid& G, const uint32_t* __restrict__ mask,
+                                                        const float* __restrict__ h, const double* __restrict__ tab,
+                                                        const uint16_t* __restrict__ d2, const ClearWeight& p, size_t s) {
+  uint32_t from, to;
+  if (!field_slot_edge(G, mask, s, &from, &to)) return INFINITY;
+  const uint32_t v = G.reverse ? from : to, u = G.reverse ? to : from;  // the slot's own node and its neighbour
+  const uint32_t cv = v / (uint32_t)G.n_yaw, cu = u / (uint32_t)G.n_yaw;
+  const int k = (int)(v - cv * (uint32_t)G.n_yaw);
+  const int j = (int)((s / (FIELD_T * FIELD_T)) % 10);
+  const double base = field_pull_cost(G, tab, j, k, h[cv], h[cu]);
+  return base * (1.0 + p.gain * fmax(clearance_pen(p, d2[from]), clearance_pen(p, d2[to])));
+}
+
 __global__ void __launch_bounds__(256)
 field_clearance_table_kernel(FieldGrid G, const uint32_t* __restrict__ mask, const float* __restrict__ h,
                              const double* __restrict__ tab, const uint16_t* __restrict__ d2, ClearWeight p, size_t slots,
                              double* __restrict__ wtab) {
   const size_t s = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= slots) return;
-  double w = INFINITY;
-  uint32_t from, to;
-  if (field_slot_edge(G, mask, s, &from, &to)) {
-    const uint32_t v = G.reverse ? from : to, u = G.reverse ? to : from;  // the slot's own node and its neighbour
-    const uint32_t cv = v / (uint32_t)G.n_yaw, cu = u / (uint32_t)G.n_yaw;
-    const int k = (int)(v - cv * (uint32_t)G.n_yaw);
-    const int j = (int)((s / (FIELD_T * FIELD_T)) % 10);
-    const double base = field_pull_cost(G, tab, j, k, h[cv], h[cu]);
-    w = base * (1.0 + p.gain * fmax(clearance_pen(p, d2[from]), clearance_pen(p, d2[to])));
+  wtab[s] = field_clearance_price(G, mask, h, tab, d2, p, s);
+}
+
+// artp_field_update_clearance: the same price against the slot's old BIT PATTERN, on a window of tiles (w as
+// clearance_window_kernel takes it).  A tile's share of the table is 10 n_yaw runs of 256 slots: workgroup b prices run
+// b % (10 n_yaw) of window tile b / (10 n_yaw), so every lane has a slot and the slots of a workgroup lie in one tile.
+// Only a slot that differs is written; its tile is flagged in acc (the seeds of the passes) and in wacc (weight_tiles) --
+// a slot is read by its own node's rule alone, which runs in its own tile alone.  cnt[5] += changed slots, one atomic per wave.
+__global__ void __launch_bounds__(256)
+field_clearance_reprice_kernel(FieldGrid G, ClearWindow w, const uint32_t* __restrict__ mask, const float* __restrict__ h,
+                               const double* __restrict__ tab, const uint16_t* __restrict__ d2, ClearWeight p,
+                               double* __restrict__ wtab, unsigned* __restrict__ acc, unsigned* __restrict__ wacc,
+                               unsigned long long* __restrict__ cnt) {
+  const uint32_t runs = 10u * (uint32_t)G.n_yaw;
+  const uint32_t wt = blockIdx.x / runs, run = blockIdx.x - wt * runs;
+  const size_t tile = (size_t)(w.t_r0 + (int)(wt % (uint32_t)w.wn_r)) + (size_t)(w.t_c0 + (int)(wt / (uint32_t)w.wn_r)) * (size_t)G.tiles_r;
+  const size_t s = (tile * runs + run) * (FIELD_T * FIELD_T) + threadIdx.x;
+  const double price = field_clearance_price(G, mask, h, tab, d2, p, s);
+  const bool ch = __double_as_longlong(price) != __double_as_longlong(wtab[s]);
+  if (ch) wtab[s] = price;
+  const unsigned long long b = __ballot(ch);
+  if (b && (threadIdx.x & 63) == 0) {
+    acc[tile] = 1u;
+    wacc[tile] = 1u;
+    atomicAdd(&cnt[5], (unsigned long long)__popcll(b));
   }
-  wtab[s] = w;
 }
 
 }  // namespace artp
@@ -178,9 +249,22 @@ int clearance_offsets(artp_ctx* c, int R) {
   return ARTP_OK;
 }
 
-// clearance_map_kernel over a rectangle of device words into device d2, on the context's stream; the checks are the caller's
+// The tiles that intersect sub grown by `grow` cells and clipped to the rectangle, as a window of tiles.
+struct ClearTiles {
+  artp::ClearWindow w;
+  size_t n;  // tiles of the window
+};
+ClearTiles clearance_window(const artp::FieldGrid& G, const artp::FieldSub& sub, int grow) {
+  const int T = artp::FIELD_T;
+  const int r_lo = std::max(sub.row0 - grow, 0) / T, r_hi = std::min(sub.row0 + sub.nrows - 1 + grow, G.nrows - 1) / T;
+  const int c_lo = std::max(sub.col0 - grow, 0) / T, c_hi = std::min(sub.col0 + sub.ncols - 1 + grow, G.ncols - 1) / T;
+  return ClearTiles{artp::ClearWindow{r_lo, c_lo, r_hi - r_lo + 1}, (size_t)(r_hi - r_lo + 1) * (size_t)(c_hi - c_lo + 1)};
+}
+
+// clearance_map_kernel over a rectangle of device words into device d2, on the context's stream; the checks are the caller's.
+// win: clearance_window_kernel on that window of tiles instead, d_d2 holding an earlier map, *d_changed += the nodes that changed.
 int clearance_run(artp_ctx* c, const artp_clearance_params& p, int n_yaw, int nrows, int ncols, const uint32_t* d_mask,
-                  uint16_t* d_d2) {
+                  uint16_t* d_d2, const ClearTiles* win = nullptr, unsigned long long* d_changed = nullptr) {
   const int R = p.radius_cells;
   ARTP_TRY(clearance_offsets(c, R));
   artp::ClearGrid G;
@@ -196,8 +280,12 @@ int clearance_run(artp_ctx* c, const artp_clearance_params& p, int n_yaw, int nr
   G.n_off = c->clear_n[R];
   G.yaw_bits = n_yaw == 32 ? 0xffffffffu : (1u << n_yaw) - 1u;
   const size_t tiles = (size_t)G.tiles_r * ((ncols + artp::FIELD_T - 1) / artp::FIELD_T);
-  hipLaunchKernelGGL(artp::clearance_map_kernel, dim3((unsigned)tiles), dim3(256), artp::clearance_lds(R, n_yaw), c->stream, G,
-                     d_mask, (const int32_t*)c->clear_offs[R], d_d2);
+  if (win)
+    hipLaunchKernelGGL(artp::clearance_window_kernel, dim3((unsigned)win->n), dim3(256), artp::clearance_lds(R, n_yaw), c->stream,
+                       G, win->w, d_mask, (const int32_t*)c->clear_offs[R], d_d2, d_changed);
+  else
+    hipLaunchKernelGGL(artp::clearance_map_kernel, dim3((unsigned)tiles), dim3(256), artp::clearance_lds(R, n_yaw), c->stream, G,
+                       d_mask, (const int32_t*)c->clear_offs[R], d_d2);
   HIP_TRY(c, hipGetLastError());
   return ARTP_OK;
 }
@@ -212,13 +300,13 @@ int clearance_map_args(artp_ctx* c, const artp_clearance_params* p, int n_yaw, i
 }
 
 // artp_field_compute_clearance's part of field_compute_impl: the field's d2 from its own mask, then the weight table.
-// tab: the host's (m, k) table of the base objective.
+// tab: the host's (m, k) table of the base objective; its device copy stays with the field (artp_field_update_clearance
+// prices with it again).
 int field_clearance_build(artp_ctx* c, artp_field* f, const double* tab) {
   hipStream_t st = c->stream;
   const artp_field_clearance_params& cp = f->cparams;
-  DeviceScratch tmp;
-  double* d_tab = nullptr;
-  HIP_TRY(c, tmp.alloc(&d_tab, (size_t)artp::FIELD_TAB));
+  HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&f->d_btab), artp::FIELD_TAB * sizeof(double)));
+  double* d_tab = f->d_btab;
   HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&f->d_d2), f->n_nodes * sizeof(uint16_t)));
   HIP_TRY(c, hipMemcpyAsync(d_tab, tab, artp::FIELD_TAB * sizeof(double), hipMemcpyHostToDevice, st));
   hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
@@ -238,7 +326,7 @@ int field_clearance_build(artp_ctx* c, artp_field* f, const double* tab) {
     if (hipGetLastError() != hipSuccess) rc = ARTP_ERR_HIP;
   }
   if (ev[2]) (void)hipEventRecord(ev[2], st);
-  if (hipStreamSynchronize(st) != hipSuccess && rc == ARTP_OK) rc = ARTP_ERR_HIP;  // the host table and d_tab are free from here
+  if (hipStreamSynchronize(st) != hipSuccess && rc == ARTP_OK) rc = ARTP_ERR_HIP;  // the host table is free from here
   float t = 0.f;
   if (rc == ARTP_OK && ev[0] && ev[1] && hipEventElapsedTime(&t, ev[0], ev[1]) == hipSuccess) f->lstats.rows_ms = t;
   if (rc == ARTP_OK && ev[1] && ev[2] && hipEventElapsedTime(&t, ev[1], ev[2]) == hipSuccess) f->lstats.combine_ms = t;
@@ -340,6 +428,126 @@ int artp_field_clearance(artp_field* f, uint16_t* d2_out) {
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, hipMemcpyAsync(d2_out, f->d_d2, f->n_nodes * sizeof(uint16_t), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return ARTP_OK;
+}
+
+int artp_field_update_clearance(artp_field* f, const uint32_t* new_mask, int mask_on_device, const int* sub_rect,
+                                int refresh_heights) {
+  if (!f || !new_mask) return ARTP_ERR_INVALID_ARG;
+  artp_ctx* c = f->ctx;
+  std::lock_guard<std::recursive_mutex> lock(c->mu);
+  const artp::FieldGrid& G = f->grid;
+  // 1. the checks: nothing is written before the last of them
+  if (G.objective != 3) {
+    c->last_error = "artp_field_update_clearance: not a field of artp_field_compute_clearance (artp_field_update and "
+                    "artp_field_update_learned take the others)";
+    return ARTP_ERR_INVALID_ARG;
+  }
+  artp::FieldSub sub{0, 0, G.nrows, G.ncols};
+  if (sub_rect) sub = artp::FieldSub{sub_rect[0], sub_rect[1], sub_rect[2], sub_rect[3]};
+  if (sub.nrows < 1 || sub.ncols < 1 || sub.row0 < 0 || sub.col0 < 0 || sub.row0 > G.nrows - sub.nrows ||
+      sub.col0 > G.ncols - sub.ncols) {
+    c->last_error = "artp_field_update_clearance: sub_rect is empty or not inside the field's rectangle";
+    return ARTP_ERR_INVALID_ARG;
+  }
+  const MapGeom &a = f->geom, &b = c->geom;
+  const bool same_map = reach_have_lattice(c) && a.rows == b.rows && a.cols == b.cols && a.len_x == b.len_x &&
+                        a.len_y == b.len_y && a.pos_x == b.pos_x && a.pos_y == b.pos_y && a.res == b.res;
+  if (refresh_heights && !same_map) {
+    c->last_error = "artp_field_update_clearance: refresh_heights needs sampler layers of the geometry the field was computed on";
+    return ARTP_ERR_INVALID_ARG;
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  ARTP_TRY(field_update_scratch(f, !mask_on_device));
+  if (!f->d_wacc) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&f->d_wacc), f->n_tiles * sizeof(unsigned)));
+  HIP_TRY(c, hipMemsetAsync(f->d_acc, 0, f->n_tiles * sizeof(unsigned), st));
+  HIP_TRY(c, hipMemsetAsync(f->d_wacc, 0, f->n_tiles * sizeof(unsigned), st));
+  HIP_TRY(c, hipMemsetAsync(f->d_ucnt, 0, 8 * sizeof(unsigned long long), st));
+  // 2. the mask diff, behind the test of the sources on the device
+  unsigned long long cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  ARTP_TRY(field_update_diff(f, new_mask, mask_on_device, sub, refresh_heights != 0, refresh_heights ? c->sampler : f->sampler, cnt));
+  if (cnt[4]) {
+    c->last_error = "artp_field_update_clearance: a source is no longer a node of the mask (the field is unchanged)";
+    return ARTP_ERR_INVALID_ARG;
+  }
+  artp_field_clearance_update_stats_t us{};
+  us.changed_words = cnt[0];
+  us.removed_nodes = cnt[1];
+  us.added_nodes = cnt[2];
+  us.reached_nodes = f->stats.reached_nodes;
+  if (cnt[0] || cnt[3]) {
+    // 3. d2 again on the tiles within R cells of sub_rect (d_ucnt[7] += the nodes whose value changed), 4. the slots of the
+    // tiles within R + 1 cells priced again; a slot whose bits change flags its tile
+    const int R = f->cparams.clearance.radius_cells;
+    const ClearTiles cw = clearance_window(G, sub, R), pw = clearance_window(G, sub, R + 1);
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    for (hipEvent_t& x : ev)
+      if (hipEventCreate(&x) != hipSuccess) x = nullptr;
+    if (ev[0]) (void)hipEventRecord(ev[0], st);
+    int rc = clearance_run(c, f->cparams.clearance, G.n_yaw, G.nrows, G.ncols, f->d_mask, f->d_d2, &cw, f->d_ucnt + 7);
+    if (ev[1]) (void)hipEventRecord(ev[1], st);
+    if (rc == ARTP_OK) {
+      artp::FieldGrid Gb = G;
+      Gb.objective = f->params.objective;
+      const artp::ClearWeight w{f->geom.res, f->cparams.margin, f->cparams.gain};
+      hipLaunchKernelGGL(artp::field_clearance_reprice_kernel, dim3((unsigned)(pw.n * 10 * (size_t)G.n_yaw)), dim3(256), 0, st, Gb,
+                         pw.w, (const uint32_t*)f->d_mask, (const float*)f->d_h, (const double*)f->d_btab,
+                         (const uint16_t*)f->d_d2, w, f->d_tab, f->d_acc, f->d_wacc, f->d_ucnt);
+      if (hipGetLastError() != hipSuccess) rc = ARTP_ERR_HIP;
+    }
+    if (ev[2]) (void)hipEventRecord(ev[2], st);
+    if (rc == ARTP_OK) {
+      hipLaunchKernelGGL(artp::field_count_flags_kernel, dim3((unsigned)((f->n_tiles + 255) / 256)), dim3(256), 0, st,
+                         (uint32_t)f->n_tiles, (const unsigned*)f->d_wacc, f->d_ucnt);
+      if (hipGetLastError() != hipSuccess ||
+          hipMemcpyAsync(cnt + 5, f->d_ucnt + 5, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st) != hipSuccess)
+        rc = ARTP_ERR_HIP;
+    }
+    if (hipStreamSynchronize(st) != hipSuccess && rc == ARTP_OK) rc = ARTP_ERR_HIP;
+    float t = 0.f;
+    if (rc == ARTP_OK && ev[0] && ev[1] && hipEventElapsedTime(&t, ev[0], ev[1]) == hipSuccess) us.clearance_ms = t;
+    if (rc == ARTP_OK && ev[1] && ev[2] && hipEventElapsedTime(&t, ev[1], ev[2]) == hipSuccess) us.reprice_ms = t;
+    for (hipEvent_t x : ev)
+      if (x) (void)hipEventDestroy(x);
+    if (rc) {
+      if (rc == ARTP_ERR_HIP && c->last_error.empty()) c->last_error = "artp_field_update_clearance: repricing the weight table failed";
+      return rc;
+    }
+    us.clearance_tiles = cw.n;
+    us.changed_d2 = cnt[7];
+    us.repriced_slots = pw.n * 10 * (uint64_t)G.n_yaw * (artp::FIELD_T * artp::FIELD_T);
+    us.changed_slots = cnt[5];
+    us.weight_tiles = cnt[6];
+    // 5. the passes of artp_field_update, from the tiles flagged by the diff and by the changed weights
+    artp_field_update_stats_t ps{};
+    const auto t0 = std::chrono::steady_clock::now();
+    rc = field_update_passes(f, &ps);
+    if (rc) {
+      (void)hipStreamSynchronize(st);
+      return rc;
+    }
+    us.passes_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    us.dead_nodes = ps.dead_nodes;
+    us.hop_dead_nodes = ps.hop_dead_nodes;
+    us.unsupport_rounds = ps.unsupport_rounds;
+    us.dist_rounds = ps.dist_rounds;
+    us.hop_rounds = ps.hop_rounds;
+    us.tile_launches = ps.tile_launches;
+    us.reached_nodes = ps.reached_nodes;
+    f->stats.reached_nodes = us.reached_nodes;  // the other numbers of artp_field_compute_clearance stay
+  }
+  if (same_map) {  // artp_field_path's poses: the current sampler layers, as a new field would take them
+    f->sampler = c->sampler;
+    f->map_version = c->map_version.load();
+  }
+  f->custats = us;
+  return ARTP_OK;
+}
+
+int artp_field_clearance_update_stats(artp_field* f, artp_field_clearance_update_stats_t* out) {
+  if (!f || !out) return ARTP_ERR_INVALID_ARG;
+  *out = f->custats;
   return ARTP_OK;
 }
 

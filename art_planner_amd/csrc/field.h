@@ -55,8 +55,9 @@
 // written and flags its tile), then the same four passes, the tiled ones on the streamed table.
 // artp_field_compute_clearance (clearance.h): objective id 3 inside the library.  The weights are the
 // base objective's (0 or 1) inflated near obstacles; they sit in the same table, filled by one kernel without the cost query,
-// and the same table-driven kernels search it (field_has_wtab).  Such a field is not updated in place: a mask edit moves
-// clearances, and with them weights, up to radius_cells around it; artp_field_update and artp_field_update_learned refuse it.
+// and the same table-driven kernels search it (field_has_wtab).  A mask edit moves clearances, and with them weights, up to
+// radius_cells around it: artp_field_update and artp_field_update_learned refuse such a field, artp_field_update_clearance
+// (clearance.h) recomputes both on a window of tiles and runs the passes of artp_field_update.
 #pragma once
 
 namespace artp {
@@ -737,7 +738,8 @@ struct FieldSub {
 };
 
 // cnt[0] changed words, [1] removed bits, [2] added bits, [3] changed heights, [4] sources that are no nodes any more,
-// [5] changed slots and [6] tiles flagged by them (artp_field_update_learned)
+// [5] changed slots and [6] tiles flagged by them (artp_field_update_learned, artp_field_update_clearance), [7] nodes whose
+// clearance changed (artp_field_update_clearance)
 
 // one lane per source against the merged mask (the new word inside sub, the field's own outside)
 __global__ void __launch_bounds__(64)
@@ -835,6 +837,8 @@ struct artp_field {
   // artp_field_compute_clearance (clearance.h): grid.objective = 3, params = the base objective's, d_tab the weight table
   artp_field_clearance_params cparams{};
   uint16_t* d_d2 = nullptr;             // the clearance map of the field's own mask, one word per node
+  double* d_btab = nullptr;             // the base objective's (m, k) table (FIELD_TAB doubles): d_tab is the weight table
+  artp_field_clearance_update_stats_t custats{};  // artp_field_update_clearance; d_wacc stays from its first call on
   float* d_lscratch = nullptr;          // per chunk: 6 floats of EdgeMatrix row, then 3 floats of answer, per row
   // artp_field_update_learned: d_lscratch stays from the first update on
   unsigned* d_wacc = nullptr;           // n_tiles flags: the tiles a changed weight flagged
@@ -854,7 +858,7 @@ namespace {
 void field_free(artp_field* f) {
   for (void* p : {(void*)f->d_dist, (void*)f->d_hops, (void*)f->d_mask, (void*)f->d_h, (void*)f->d_tab, (void*)f->d_flags,
                   (void*)f->d_nodes, (void*)f->d_out, (void*)f->d_src, (void*)f->d_snap, (void*)f->d_acc, (void*)f->d_ucnt,
-                  (void*)f->d_stage, (void*)f->d_lscratch, (void*)f->d_wacc, (void*)f->d_blk, (void*)f->d_d2, f->d_plan})
+                  (void*)f->d_stage, (void*)f->d_lscratch, (void*)f->d_wacc, (void*)f->d_blk, (void*)f->d_d2, (void*)f->d_btab, f->d_plan})
     if (p) (void)hipFree(p);
   delete f;
 }
@@ -1474,8 +1478,8 @@ int artp_field_update(artp_field* f, const uint32_t* new_mask, int mask_on_devic
   std::lock_guard<std::recursive_mutex> lock(c->mu);
   const artp::FieldGrid& G = f->grid;
   if (G.objective == 3) {
-    c->last_error = "artp_field_update: a clearance-weighted field is not updated in place (a mask edit moves clearances, and "
-                    "with them the weights, up to radius_cells around it): compute a new one";
+    c->last_error = "artp_field_update: a clearance-weighted field is not updated by a mask edit alone (it moves clearances, and "
+                    "with them the weights, up to radius_cells around it): artp_field_update_clearance takes it";
     return ARTP_ERR_INVALID_ARG;
   }
   if (G.objective == 2) {
@@ -1544,7 +1548,8 @@ int artp_field_update_learned(artp_field* f, const uint32_t* new_mask, int mask_
   const artp::FieldGrid& G = f->grid;
   // 1. the checks: nothing is written before the last of them
   if (G.objective != 2) {
-    c->last_error = "artp_field_update_learned: not a field of artp_field_compute_learned (artp_field_update takes the others)";
+    c->last_error = "artp_field_update_learned: not a field of artp_field_compute_learned (artp_field_update and "
+                    "artp_field_update_clearance take the others)";
     return ARTP_ERR_INVALID_ARG;
   }
   if (!c->have_weights) {

@@ -186,6 +186,24 @@ class CostField:
         self.ctx._chk(self.L.artp_field_learned_update_stats(self.h, C.byref(s)), "artp_field_learned_update_stats")
         return {n: getattr(s, n) for n, _ in _capi.FieldLearnedUpdateStats._fields_}
 
+    def update_clearance(self, mask, rect=None, refresh_heights=False) -> dict:
+        """Bring a clearance-weighted field to the fixed point of an edited mask in place (artp_field_update_clearance,
+        DESIGN.md section 18): the clearance map and the weight table computed again around rect, then the passes of
+        update().  mask, rect and refresh_heights as in update().  The same bits -- dist, paths, clearance(), edge_costs --
+        as a new clearance_cost_field with the field's own parameters on the merged mask.  Returns the update's stats."""
+        mask_ptr, on_device, keep = self._mask_arg(mask, "CostField.update_clearance")
+        r = None if rect is None else np.ascontiguousarray(rect, np.int32).reshape(4)
+        self.ctx._chk(self.L.artp_field_update_clearance(self.h, mask_ptr, on_device, r.ctypes.data if r is not None else None,
+                                                         int(bool(refresh_heights))), "artp_field_update_clearance")
+        del keep
+        return self.clearance_update_stats()
+
+    def clearance_update_stats(self) -> dict:
+        """The numbers of the last update_clearance that succeeded (zeros before the first)."""
+        s = _capi.FieldClearanceUpdateStats()
+        self.ctx._chk(self.L.artp_field_clearance_update_stats(self.h, C.byref(s)), "artp_field_clearance_update_stats")
+        return {n: getattr(s, n) for n, _ in _capi.FieldClearanceUpdateStats._fields_}
+
     def block_moves(self, a, b) -> int:
         """Block the moves a[i] -> b[i] ((n, 3) node triples, travel direction) and repair the field in place
         (artp_field_block_moves): the same bits as a new field with the same set blocked.  Only the

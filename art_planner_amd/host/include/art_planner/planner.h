@@ -449,8 +449,8 @@ class Planner {
   // w(a -> b) = base (1 + gain max(pen(a), pen(b))), pen(v) = max(0, 1 - res sqrt(d2[v]) / margin) with d2 the clearance
   // map of the mask; margin (metres) may not exceed radius_cells * res; gain = 0 gives computeCostField's bits.  A kept
   // field works with blockCostFieldMoves, unblockCostField and planOnCostField; updateCostField and
-  // updateLearnedCostField are refused (a mask edit moves clearances up to radius_cells around it): compute a new one.
-  // Refreshes the "cost_to_go" layer.
+  // updateLearnedCostField refuse it (a mask edit moves clearances up to radius_cells around it):
+  // updateClearanceCostField takes it.  Refreshes the "cost_to_go" layer.
   std::vector<double> computeClearanceCostField(const std::vector<uint32_t>& mask, unsigned n_yaw,
                                                 const std::vector<std::array<int, 3>>& sources, double margin = 0.2,
                                                 double gain = 2.0, int radius_cells = 12, int yaw_spread = 0,
@@ -501,6 +501,27 @@ class Planner {
     throwOnError(gpu_->get(),
                  artp_field_update(kept, mask.data(), 0, rect ? rect->data() : nullptr, refresh_heights ? 1 : 0),
                  "artp_field_update");
+    return refreshCostToGo(kept, cells, st.nodes);
+  }
+
+  // The field a computeClearanceCostField call kept, brought in place to an edited mask (artp_field_update_clearance,
+  // include/artp_c.h): the clearance map and the move costs computed again around rect, then updateCostField's passes.
+  // mask, rect and refresh_heights as updateCostField takes them.  The same bits as computeClearanceCostField with the
+  // field's own parameters on that mask.  Returns dist and refreshes the "cost_to_go" layer.
+  std::vector<double> updateClearanceCostField(artp_field* kept, const std::vector<uint32_t>& mask,
+                                               const std::array<int, 4>* rect = nullptr, bool refresh_heights = false) {
+    std::lock_guard<std::mutex> lock(map_mutex_);
+    if (!map_) throw std::runtime_error("updateClearanceCostField: the planner does not have a map set");
+    if (!kept) throw std::runtime_error("updateClearanceCostField: no field");
+    const auto g = map_->getGeometry();
+    const size_t cells = static_cast<size_t>(g.rows) * g.cols;
+    artp_field_stats_t st;
+    throwOnError(gpu_->get(), artp_field_stats(kept, &st), "artp_field_stats");
+    if (mask.size() != cells || st.nodes % cells != 0)
+      throw std::runtime_error("updateClearanceCostField: the mask or the field does not have rows * cols cells");
+    throwOnError(gpu_->get(),
+                 artp_field_update_clearance(kept, mask.data(), 0, rect ? rect->data() : nullptr, refresh_heights ? 1 : 0),
+                 "artp_field_update_clearance");
     return refreshCostToGo(kept, cells, st.nodes);
   }
 

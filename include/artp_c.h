@@ -290,7 +290,7 @@ int artp_field_stats(artp_field* f, artp_field_stats_t* out);
  * field was computed on, the poses of artp_field_path are those of the current sampler layers, as a new field's would be.
  * ARTP_ERR_INVALID_ARG with the field untouched: a source is no longer a node of the merged mask, sub_rect is empty or not
  * inside the rectangle, refresh_heights without sampler layers of the geometry the field was computed on, a learned or a
- * clearance-weighted field (artp_field_compute_learned, artp_field_compute_clearance: see there).
+ * clearance-weighted field (artp_field_update_learned and artp_field_update_clearance take those).
  * Every launch is bounded; the round caps are artp_field_compute's.  Synchronous, on the context's current stream. */
 typedef struct artp_field_update_stats_t {
   uint64_t changed_words;    /* words of sub_rect that differ in their low n_yaw bits */
@@ -481,8 +481,9 @@ int artp_clearance_map_dev(artp_ctx* ctx, const artp_clearance_params* params, i
  * The result is an ordinary artp_field: artp_field_dist, _dist_dev, _path, _edge_costs, _stats, _block_moves, _unblock,
  * _blocked*, _plan and _destroy work on it unchanged.  artp_field_learned_stats reports its table (table_rows, table_bytes),
  * rows_ms = the device time of the clearance map, combine_ms = that of the table build, chunks = 0, query_ms = 0.
- * It is NOT updated in place: a mask edit moves clearances, and with them weights, up to radius_cells around it.
- * artp_field_update and artp_field_update_learned refuse it with ARTP_ERR_INVALID_ARG and leave it untouched.
+ * A mask edit moves clearances, and with them weights, up to radius_cells around it: artp_field_update and
+ * artp_field_update_learned refuse the field with ARTP_ERR_INVALID_ARG and leave it untouched; artp_field_update_clearance
+ * (below) updates it in place.
  * ARTP_ERR_INVALID_ARG, with nothing computed: what artp_clearance_map refuses about n_yaw, radius_cells, yaw_spread and
  * outside_is_obstacle; margin not positive or not finite; margin > radius_cells res (clearance beyond the cap is unknown);
  * gain negative or not finite; everything artp_field_compute refuses.  ARTP_ERR_NO_MAP as artp_field_compute. */
@@ -498,6 +499,40 @@ int artp_field_compute_clearance(artp_ctx* ctx, const artp_field_clearance_param
                                  artp_field** out);
 /* the field's own d2 (nrows * ncols * n_yaw words on the host, index as dist); ARTP_ERR_INVALID_ARG for any other field */
 int artp_field_clearance(artp_field* f, uint16_t* d2_out);
+/* Update a clearance-weighted field IN PLACE after its mask (and, on request, its heights) changed in a sub-rectangle
+ * (DESIGN.md section 18).  new_mask, mask_on_device, sub_rect and refresh_heights as in artp_field_update: new_mask covers the
+ * field's whole rectangle, only the words inside sub_rect are read (NULL = all), refresh_heights != 0 re-reads the sampler
+ * layer's heights inside sub_rect (only base objective 0 uses heights).
+ * After the diff of artp_field_update, d2 is computed again on the 16 x 16 tiles that intersect sub_rect grown by
+ * radius_cells (a mask word moves no clearance further away), the weight table is priced again on the tiles that intersect
+ * sub_rect grown by radius_cells + 1 (a slot depends on its node and one neighbour); a slot whose bit pattern changes is
+ * written and flags its tile; then the passes of artp_field_update run from the flagged tiles.  When no word and no height
+ * changed the call ends after the diff.  sub_rect = NULL recomputes the clearance map and the table of the whole rectangle.
+ * After ARTP_OK dist, hops (artp_field_path), artp_field_clearance, artp_field_edge_costs (every slot of the table) and
+ * reached_nodes are bit for bit those of artp_field_compute_clearance with the field's own params, n_yaw, rectangle,
+ * sources and reverse on the merged mask and the merged heights, with the same moves blocked.  The poses of
+ * artp_field_path follow the current sampler layers as after artp_field_update.  The first update allocates its scratch and
+ * keeps it until artp_field_destroy.  artp_field_learned_stats keeps describing the original compute.
+ * ARTP_ERR_INVALID_ARG with the field untouched: the field is not a clearance-weighted one, sub_rect is empty or not inside
+ * the rectangle, refresh_heights without sampler layers of the geometry the field was computed on, a source is no longer a
+ * node of the merged mask.  A HIP failure (ARTP_ERR_HIP) or ARTP_ERR_CAPACITY after those checks leaves the field
+ * UNDEFINED: destroy it.  Synchronous, on the context's current stream. */
+typedef struct artp_field_clearance_update_stats_t {
+  uint64_t changed_words, removed_nodes, added_nodes, dead_nodes, hop_dead_nodes, unsupport_rounds, dist_rounds,
+      hop_rounds, tile_launches, reached_nodes; /* as artp_field_update_stats_t */
+  uint64_t clearance_tiles; /* tiles whose d2 was computed again */
+  uint64_t changed_d2;      /* nodes whose d2 changed */
+  uint64_t repriced_slots;  /* slots of the weight table priced again (2560 n_yaw a tile) */
+  uint64_t changed_slots;   /* slots whose weight changed its bit pattern */
+  uint64_t weight_tiles;    /* tiles flagged by a changed weight */
+  double clearance_ms, reprice_ms; /* device time of the two windows */
+  double passes_ms;                /* host time of the four passes (every round is read by the host) */
+} artp_field_clearance_update_stats_t;
+int artp_field_update_clearance(artp_field* f, const uint32_t* new_mask, int mask_on_device, const int sub_rect[4],
+                                int refresh_heights);
+/* the numbers of the last artp_field_update_clearance that returned ARTP_OK (zeros before the first; after a call that found
+ * no change: zeros apart from reached_nodes) */
+int artp_field_clearance_update_stats(artp_field* f, artp_field_clearance_update_stats_t* out);
 
 /* ---- ob::MotionValidator::checkMotion (OMPL DiscreteMotionValidator; call sites
  *      prm_motion_cost.cpp:652, lazy_prm_star_min_update.cpp:725), batched -----------------------
