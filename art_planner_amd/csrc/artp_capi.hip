@@ -3712,11 +3712,11 @@ extern "C" int artp_debug_stage_cycles(unsigned long long* out20, int reset) {
     return hipMemcpyToSymbol(HIP_SYMBOL(artp::g_torso_counts), z8, sizeof(z8)) == hipSuccess ? 0 : -1;
   }
   if (out20 && reset >= 3 &&
-      hipMemcpyFromSymbol(out20, HIP_SYMBOL(artp::g_feet_cycles), 8 * sizeof(unsigned long long)) != hipSuccess)
+      hipMemcpyFromSymbol(out20, HIP_SYMBOL(artp::g_feet_cycles), 16 * sizeof(unsigned long long)) != hipSuccess)
     return -1;
   if (reset) {
-    unsigned long long z8[8] = {};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(artp::g_feet_cycles), z8, sizeof(z8)) != hipSuccess) return -1;
+    unsigned long long z16[16] = {};
+    if (hipMemcpyToSymbol(HIP_SYMBOL(artp::g_feet_cycles), z16, sizeof(z16)) != hipSuccess) return -1;
   }
   if (reset == 6) {  // conv_ksplit_kernel's per-workgroup records: out20[0 .. 6143] (1024 x {HW_ID, XCC_ID, 4 x s_memrealtime})
     return out20 && hipMemcpyFromSymbol(out20, HIP_SYMBOL(artp::g_ks_trace), 1024 * 6 * sizeof(unsigned long long)) == hipSuccess ? 0 : -1;

@@ -967,11 +967,48 @@ __device__ __forceinline__ int grp_plane_stage_corners(const FieldDev& f, const 
 // contacts right there; when the map's partner table cannot rule out a partner for some kept candidate the box
 // needs the list (2).  Same candidates, same planes and same contact tests as grp_plane_stage_corners in fast mode
 // (a triangle nominated by two corners is tested twice: harmless).
+// One (corner, cell, triangle kind) pair of that stage: the triangle `c_up` of window-local cell (cx, cz), nominated by a
+// box corner at height py.  Shared by grp_corner_stage_direct and lane_corner_probe, so that both run the same
+// arithmetic on the same operands.
+enum : unsigned { PAIR_KEPT = 1u, PAIR_FILTERED = 2u, PAIR_PARTNER = 4u, PAIR_HIT = 8u };
+__device__ __forceinline__ unsigned corner_pair(const FieldDev& f, const BoxHF& b, int cx, int cz, bool c_up, float py,
+                                                float reach, bool window_covered) {
+  const float minO2 = b.aabb[2];
+  const unsigned at = (unsigned)((b.minX + cx) + (b.minZ + cz) * f.nW);
+  const float hA = gather32(f.data, at), hB = gather32(f.data, at + 1u);
+  const float hC = gather32(f.data, at + (unsigned)f.nW), hD = gather32(f.data, at + (unsigned)f.nW + 1u);
+  const bool fA = is_finite(hA), fB = is_finite(hB), fC = is_finite(hC), fD = is_finite(hD);
+  const bool kA = fA && hA > minO2, kB = fB && hB > minO2, kC = fC && hC > minO2, kD = fD && hD > minO2;
+  bool kept = c_up ? ((kA || kB || kC) && (fA && fB && fC)) : ((kB || kC || kD) && (fB && fC && fD));
+  if (!kept) return 0u;
+  const float h0 = c_up ? hA : hD;
+  const float h4 = (hB + hC) - h0;
+  const float top = fmaxf(fmaxf(h0, h4), fmaxf(hB, hC));
+  const float spread = fabsf(hB - h0) + fabsf(hC - h0);
+  if (py > top + spread * reach + 1.0e-3f) return PAIR_FILTERED;
+  unsigned out = PAIR_KEPT;
+  if (!window_covered || ((gather32(f.partner_flags, at) >> (c_up ? 0 : 1)) & 1)) out |= PAIR_PARTNER;
+  const float xA = (float)(b.minX + cx) * f.sample_w, xB = (float)(b.minX + cx + 1) * f.sample_w;
+  const float zA = (float)(b.minZ + cz) * f.sample_d, zC = (float)(b.minZ + cz + 1) * f.sample_d;
+  float cpl[4];
+  if (c_up)
+    triangle_plane(xA, hA, zA, xB, hB, zA, xA, hC, zC, true, cpl);
+  else
+    triangle_plane(xB, hD, zC, xB, hB, zA, xA, hC, zC, false, cpl);
+  const int gx = b.minX + cx + (c_up ? 0 : 1), gz = b.minZ + cz + (c_up ? 0 : 1);
+  float cpos[4][3];
+  const int nc = box_plane_contacts(b, cpl[0], cpl[1], cpl[2], cpl[3], 10, cpos);
+  bool hit = false;
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+    if (i < nc) hit = hit || is_on_heightfield2(f, gx, gz, cpos[i][0], cpos[i][2], c_up);
+  return hit ? (out | PAIR_HIT) : out;
+}
+
 template <int G>
 __device__ __forceinline__ int grp_corner_stage_direct(const FieldDev& f, const BoxHF& b, int lane) {
   const int gl = grp_lane<G>(lane);
   const int cellsX = b.maxX - b.minX, cellsZ = b.maxZ - b.minZ;
-  const float minO2 = b.aabb[2];
   const float margin = 1.0e-4f;  // see grp_plane_stage_corners
   const bool window_covered = f.partner_flags != nullptr && cellsX <= f.partner_R && cellsZ <= f.partner_R;
   const int base_slot = gl & 15;
@@ -984,49 +1021,75 @@ __device__ __forceinline__ int grp_corner_stage_direct(const FieldDev& f, const 
   const float reach = 2.0f * margin * fmaxf(f.inv_w, f.inv_d);
   const int cxa = (int)floorf((px - margin) * f.inv_w), cxb = (int)floorf((px + margin) * f.inv_w);
   const int cza = (int)floorf((pz - margin) * f.inv_d), czb = (int)floorf((pz + margin) * f.inv_d);
-  bool maybe_partner = false, hit = false;
+  unsigned seen = 0u;
   for (int r = 0; r < 4; ++r) {
     const int off = (G == 64) ? (gl >> 4) : r;
     const int dx = off & 1, dz = off >> 1;
     const bool wanted = (cxa + dx <= cxb) && (cza + dz <= czb);
     if (G != 64 && r > 0 && !grp_any<G>(wanted, lane)) continue;
     const int cx = cxa + dx - b.minX, cz = cza + dz - b.minZ;  // window-local cell
-    if (wanted && cx >= 0 && cz >= 0 && cx < cellsX && cz < cellsZ) {
-      const unsigned at = (unsigned)((b.minX + cx) + (b.minZ + cz) * f.nW);
-      const float hA = gather32(f.data, at), hB = gather32(f.data, at + 1u);
-      const float hC = gather32(f.data, at + (unsigned)f.nW), hD = gather32(f.data, at + (unsigned)f.nW + 1u);
-      const bool fA = is_finite(hA), fB = is_finite(hB), fC = is_finite(hC), fD = is_finite(hD);
-      const bool kA = fA && hA > minO2, kB = fB && hB > minO2, kC = fC && hC > minO2, kD = fD && hD > minO2;
-      bool kept = c_up ? ((kA || kB || kC) && (fA && fB && fC)) : ((kB || kC || kD) && (fB && fC && fD));
-      if (kept) {
-        const float h0 = c_up ? hA : hD;
-        const float h4 = (hB + hC) - h0;
-        const float top = fmaxf(fmaxf(h0, h4), fmaxf(hB, hC));
-        const float spread = fabsf(hB - h0) + fabsf(hC - h0);
-        kept = !(py > top + spread * reach + 1.0e-3f);
-      }
-      if (kept) {
-        maybe_partner = maybe_partner || !window_covered || ((gather32(f.partner_flags, at) >> (c_up ? 0 : 1)) & 1);
-        const float xA = (float)(b.minX + cx) * f.sample_w, xB = (float)(b.minX + cx + 1) * f.sample_w;
-        const float zA = (float)(b.minZ + cz) * f.sample_d, zC = (float)(b.minZ + cz + 1) * f.sample_d;
-        float cpl[4];
-        if (c_up)
-          triangle_plane(xA, hA, zA, xB, hB, zA, xA, hC, zC, true, cpl);
-        else
-          triangle_plane(xB, hD, zC, xB, hB, zA, xA, hC, zC, false, cpl);
-        const int gx = b.minX + cx + (c_up ? 0 : 1), gz = b.minZ + cz + (c_up ? 0 : 1);
-        float cpos[4][3];
-        const int nc = box_plane_contacts(b, cpl[0], cpl[1], cpl[2], cpl[3], 10, cpos);
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-          if (i < nc) hit = hit || is_on_heightfield2(f, gx, gz, cpos[i][0], cpos[i][2], c_up);
-      }
-    }
+    if (wanted && cx >= 0 && cz >= 0 && cx < cellsX && cz < cellsZ)
+      seen |= corner_pair(f, b, cx, cz, c_up, py, reach, window_covered);
     if (G == 64) break;  // the four offsets were handled side by side
   }
-  if (grp_any<G>(maybe_partner, lane)) return 2;
-  return grp_any<G>(hit, lane) ? 1 : 0;
+  if (grp_any<G>((seen & PAIR_PARTNER) != 0u, lane)) return 2;
+  return grp_any<G>((seen & PAIR_HIT) != 0u, lane) ? 1 : 0;
 }
+
+// The pre-pass of feet_stream_kernel, one lane per (box, triangle kind): the box's LOWEST corner in the field frame and
+// the triangle `c_up` of the cell under it.  The label of the box is "a vertex inside OR a plane contact", and a kept
+// candidate whose own partner bit is clear in a covered window is a group of its own in the reference's greedy grouping
+// (see grp_plane_stage_corners): a contact it accepts makes dCollide non-zero whatever the other candidates, their
+// groups and the window's vertices are.  So true here is the box's final "touches"; false says nothing, and the box
+// runs the full stage.  Any subset of the pairs of grp_corner_stage_direct would do; the lowest corner is the contact
+// that fires whenever that corner lies under the terrain at its own (x, z).  A corner within the margin of a cell
+// border nominates more than one cell and is left to the full stage.  `why` (optional) receives the outcome.
+enum : int { PROBE_DECIDED = 0, PROBE_BORDER = 1, PROBE_NOT_KEPT = 2, PROBE_FILTERED = 3, PROBE_PARTNER = 4, PROBE_NO_CONTACT = 5 };
+// the probe of one corner (s0, s1, s2 = +-0.5 per box axis) against the triangle `c_up` of the cell under it
+__device__ __forceinline__ bool corner_probe_at(const FieldDev& f, const BoxHF& b, float s0, float s1, float s2, bool c_up,
+                                                int* why = nullptr) {
+  const int cellsX = b.maxX - b.minX, cellsZ = b.maxZ - b.minZ;
+  const float margin = 1.0e-4f;  // see grp_plane_stage_corners
+  const bool window_covered = f.partner_flags != nullptr && cellsX <= f.partner_R && cellsZ <= f.partner_R;
+  const float px = b.pos[0] + s0 * b.side[0] * b.R[0] + s1 * b.side[1] * b.R[1] + s2 * b.side[2] * b.R[2];
+  const float py = b.pos[1] + s0 * b.side[0] * b.R[3] + s1 * b.side[1] * b.R[4] + s2 * b.side[2] * b.R[5];
+  const float pz = b.pos[2] + s0 * b.side[0] * b.R[6] + s1 * b.side[1] * b.R[7] + s2 * b.side[2] * b.R[8];
+  const float reach = 2.0f * margin * fmaxf(f.inv_w, f.inv_d);
+  const int cxa = (int)floorf((px - margin) * f.inv_w), cxb = (int)floorf((px + margin) * f.inv_w);
+  const int cza = (int)floorf((pz - margin) * f.inv_d), czb = (int)floorf((pz + margin) * f.inv_d);
+  int w = PROBE_BORDER;
+  if (cxb == cxa && czb == cza) {
+    const int cx = cxa - b.minX, cz = cza - b.minZ;  // window-local cell
+    w = PROBE_NOT_KEPT;
+    if (cx >= 0 && cz >= 0 && cx < cellsX && cz < cellsZ) {
+      const unsigned p = corner_pair(f, b, cx, cz, c_up, py, reach, window_covered);
+      w = !(p & PAIR_KEPT) ? ((p & PAIR_FILTERED) ? PROBE_FILTERED : PROBE_NOT_KEPT)
+                           : ((p & PAIR_PARTNER) ? PROBE_PARTNER : ((p & PAIR_HIT) ? PROBE_DECIDED : PROBE_NO_CONTACT));
+    }
+  }
+  if (why) *why = w;
+  return w == PROBE_DECIDED;
+}
+__device__ __forceinline__ bool lane_corner_probe(const FieldDev& f, const BoxHF& b, bool c_up, int* why = nullptr) {
+  // the corner of grp_corner_stage_direct whose three terms of py are all <= 0
+  return corner_probe_at(f, b, (b.R[3] > 0.0f) ? -0.5f : 0.5f, (b.R[4] > 0.0f) ? -0.5f : 0.5f, (b.R[5] > 0.0f) ? -0.5f : 0.5f,
+                         c_up, why);
+}
+#ifdef ARTP_STAGE_TIMING
+// tuning aid: would the four corners of the face whose outward normal points most downward settle the box?  (One lane
+// per triangle kind, the corners in turn; the lowest corner is one of the four.)
+__device__ __forceinline__ bool face_corner_probe(const FieldDev& f, const BoxHF& b, bool c_up) {
+  const float a0 = fabsf(b.R[3]), a1 = fabsf(b.R[4]), a2 = fabsf(b.R[5]);
+  const int ax = (a0 >= a1 && a0 >= a2) ? 0 : (a1 >= a2 ? 1 : 2);
+  bool any = false;
+  for (int c = 0; c < 4; ++c) {
+    const float u = (c & 1) ? 0.5f : -0.5f, v = (c & 2) ? 0.5f : -0.5f;
+    const float d = ((ax == 0 ? b.R[3] : (ax == 1 ? b.R[4] : b.R[5])) > 0.0f) ? -0.5f : 0.5f;
+    any = corner_probe_at(f, b, ax == 0 ? d : u, ax == 1 ? d : (ax == 0 ? u : v), ax == 2 ? d : v, c_up) || any;
+  }
+  return any;
+}
+#endif
 
 __device__ __forceinline__ int wave_plane_stage_corners(const FieldDev& f, const BoxHF& b,
                                                         const WaveScratch& s, int lane, int T) {

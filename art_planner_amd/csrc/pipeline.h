@@ -951,6 +951,9 @@ classify_states_kernel(FieldDev fb, FieldDev ff, TablesDev tb, TablesDev tf, Map
 #ifndef ARTP_FEET_CHUNK
 #define ARTP_FEET_CHUNK 32
 #endif
+#ifndef ARTP_FEET_PRE_LANES
+#define ARTP_FEET_PRE_LANES 2  // lanes per box in the feet pre-pass: the two triangle kinds of the cell under the lowest corner
+#endif
 #ifndef ARTP_TORSO_CHUNK
 #define ARTP_TORSO_CHUNK 8
 #endif
@@ -1045,21 +1048,38 @@ feet_lane_kernel(FieldDev ff, RobotDev rb, PipelineQueues q, uint8_t* __restrict
 // For the records whose exits (b)-(e) the tables already ruled out (all of them unless the window holds a
 // NaN or is thinner than the smallest table block): the list-free corner stage, then (f) streamed from the map.
 // The label is "(f) fires OR the plane stage yields a contact": two independent existence tests, so the order is
-// free, and two boxes in three that get here end with a corner contact and never stream.  A wavefront runs the
-// corner stage over its whole chunk, collects the boxes still open by ballot and streams only those, four per round
-// (their records are read again: they are in L2) -- without that its four groups wait for the one that streams.
+// free, and two boxes in three that get here end with a corner contact and never stream.  The corner stage's 16
+// slots per box (8 corners x 2 triangle kinds) all nominate, and two to five lanes of the 64 then do the expensive
+// part; so a pre-pass goes first, two lanes per box over the whole chunk: the box's lowest corner against the two
+// triangles of the cell under it (lane_corner_probe).  A contact there settles the box -- 56 % of the live boxes of
+// the headline batch -- and the 16-lane stage runs only for the rest, four per round (3.9 rounds per chunk instead of
+// 8).  The pre-pass also reads the chunk's records and their states' labels together, once, so a box of a state that
+// has failed costs no round (profiles/feet_prepass.txt).  A wavefront then collects the boxes still open and streams
+// only those, four per round (their records are read again: they are in L2) -- without that its four groups wait for
+// the one that streams.
 // Decides everything except boxes whose corner candidates may have partners: they get their stream too and go to
 // queue 5 (list pass) when it finds nothing.  Records without table verdict are queue 4's (sequential lane scan
 // with the running-dMAX quirk).
-// 6 wavefronts per SIMD (80 VGPRs, nothing spilled to scratch): 5 are 2 % slower.  (With LLVM's SLP pass on, the
-// kernel needed 96 VGPRs + 14 spills for 5 wavefronts and 6 were out of reach.)
+// 6 wavefronts per SIMD (71 VGPRs, nothing spilled to scratch).  (With LLVM's SLP pass on, the kernel needed 96
+// VGPRs + 14 spills for 5 wavefronts and 6 were out of reach.)
 #ifdef ARTP_STAGE_TIMING
-// stream cycles, corner cycles, boxes that ran the second stage, boxes taken, corner results 1 and 2, stream hits
-__device__ unsigned long long g_feet_cycles[8];
+// stream cycles, corner cycles, boxes that ran the second stage, boxes that ran the corner stage, corner results 1 and 2,
+// stream hits; pre-pass: [7] boxes live, [8] boxes it settled, [9] refused at a cell border, [10] ticks (per wavefront),
+// [11] corner rounds run, [12] boxes the four bottom-face corners would settle (counted only, never used)
+__device__ unsigned long long g_feet_cycles[16];
 #endif
 // one bit per 16-lane group out of a wavefront ballot of a group-uniform predicate (lanes 0, 16, 32, 48)
 __device__ __forceinline__ unsigned grp_bits4(unsigned long long bal) {
   return (unsigned)((bal & 1ull) | ((bal >> 15) & 2ull) | ((bal >> 30) & 4ull) | ((bal >> 45) & 8ull));
+}
+// bit k = bit 2k | bit 2k + 1 of a wavefront ballot: one bit per box out of the pre-pass's two lanes per box
+__device__ __forceinline__ unsigned pair_bits32(unsigned long long x) {
+  x = (x | (x >> 1)) & 0x5555555555555555ull;
+  x = (x | (x >> 1)) & 0x3333333333333333ull;
+  x = (x | (x >> 2)) & 0x0f0f0f0f0f0f0f0full;
+  x = (x | (x >> 4)) & 0x00ff00ff00ff00ffull;
+  x = (x | (x >> 8)) & 0x0000ffff0000ffffull;
+  return (unsigned)(x | (x >> 16));
 }
 #ifndef ARTP_FEET_WAVES_PER_SIMD
 #define ARTP_FEET_WAVES_PER_SIMD 6
@@ -1075,6 +1095,7 @@ feet_stream_kernel(FieldDev ff, RobotDev rb, PipelineQueues q, uint8_t* __restri
   const unsigned long long first = sub_base(q, 1, sq);
   // every wavefront takes ARTP_FEET_CHUNK boxes at a time from the sub-queue's cursor
   static_assert(ARTP_FEET_CHUNK % GPW == 0 && ARTP_FEET_CHUNK <= 32, "one bit per box of the chunk in a 32-bit mask");
+  static_assert(ARTP_FEET_PRE_LANES == 2 && ARTP_FEET_CHUNK * ARTP_FEET_PRE_LANES <= 64, "the pre-pass takes the chunk in one go");
   unsigned long long* cursor = sub_cursor(q, 1, sq);
   for (;;) {
     unsigned long long chunk = 0;
@@ -1087,30 +1108,90 @@ feet_stream_kernel(FieldDev ff, RobotDev rb, PipelineQueues q, uint8_t* __restri
     unsigned open = 0, partner = 0;
     const PendingBox* __restrict__ recs = q.q1 + (first + chunk);  // wave-uniform: the chunk's records
     const unsigned left = (count - chunk < (unsigned long long)ARTP_FEET_CHUNK) ? (unsigned)(count - chunk) : (unsigned)ARTP_FEET_CHUNK;
-    for (int r = 0; r < ARTP_FEET_CHUNK / GPW; ++r) {
-      const unsigned k = (unsigned)(r * GPW + lane / G);
-      int rr = 1;
+    // the pre-pass over the chunk, ARTP_FEET_PRE_LANES lanes per box: each reads its box's record and that state's
+    // label once.  bit k of `todo`: box k is live (its state has not failed, and its record has a table verdict:
+    // the others are the lane scan's, classify listed them) and its lowest corner did not settle it
+    unsigned todo;
+    {
+#ifdef ARTP_STAGE_TIMING
+      const long long tp0 = clock64();
+      int why = -1;
+#endif
+      const unsigned k = (unsigned)lane / ARTP_FEET_PRE_LANES;
+      bool alive = false, decided = false;
       if (k < left) {
         const PendingBox rec = recs[k];
-        // (a state another box already failed is skipped; records without a table verdict are the lane scan's: classify listed them)
-        if (valid[rec.state] != 0 && (rec.kind & ARTP_REC_EXITS_NEGATIVE)) {
+        alive = valid[rec.state] != 0 && (rec.kind & ARTP_REC_EXITS_NEGATIVE);
+        if (alive) {
           BoxHF b;
           box_from_record(rec, rb, b);
 #ifdef ARTP_STAGE_TIMING
-          const long long tf0 = clock64();
-#endif
-          rr = grp_corner_stage_direct<G>(ff, b, lane);
-#ifdef ARTP_STAGE_TIMING
-          if (gl == 0) {
-            atomicAdd(&g_feet_cycles[1], (unsigned long long)(clock64() - tf0));
-            atomicAdd(&g_feet_cycles[3], 1ull);
-            if (rr) atomicAdd(&g_feet_cycles[3 + rr], 1ull);
-          }
+          decided = lane_corner_probe(ff, b, !(lane & 1), &why);
+#else
+          decided = lane_corner_probe(ff, b, !(lane & 1));
 #endif
         }
       }
-      open |= grp_bits4(__ballot(rr != 1)) << (r * GPW);
-      partner |= grp_bits4(__ballot(rr == 2)) << (r * GPW);
+      const unsigned live = pair_bits32(__ballot(alive));
+      const unsigned settled = pair_bits32(__ballot(decided));
+      todo = live & ~settled;
+#ifdef ARTP_STAGE_TIMING
+      const unsigned long long border = __ballot(why == PROBE_BORDER && !(lane & 1));
+      // (measured after the pre-pass's ticks are taken)
+      const long long tp1 = clock64();
+      bool face = false;
+      if (alive) {
+        BoxHF b;
+        box_from_record(recs[k], rb, b);
+        face = face_corner_probe(ff, b, !(lane & 1));
+      }
+      const unsigned face32 = pair_bits32(__ballot(face));
+      if (lane == 0) {
+        atomicAdd(&g_feet_cycles[12], (unsigned long long)__popc(face32));
+        atomicAdd(&g_feet_cycles[10], (unsigned long long)(tp1 - tp0));
+        atomicAdd(&g_feet_cycles[7], (unsigned long long)__popc(live));
+        atomicAdd(&g_feet_cycles[8], (unsigned long long)__popc(settled));
+        atomicAdd(&g_feet_cycles[9], (unsigned long long)__popcll(border));
+      }
+#endif
+    }
+    // the full corner stage for what is left, four boxes per round (their records are read again: they are in L2)
+    while (todo) {
+      unsigned at[GPW];
+      int mine = -1;
+#pragma unroll
+      for (int g = 0; g < GPW; ++g) {
+        at[g] = todo ? (unsigned)__builtin_ctz(todo) : 32u;
+        if (lane / G == g && todo) mine = (int)at[g];
+        todo &= todo - 1;
+      }
+      int rr = 1;
+      if (mine >= 0) {
+        const PendingBox rec = recs[mine];
+        BoxHF b;
+        box_from_record(rec, rb, b);
+#ifdef ARTP_STAGE_TIMING
+        const long long tf0 = clock64();
+#endif
+        rr = grp_corner_stage_direct<G>(ff, b, lane);
+#ifdef ARTP_STAGE_TIMING
+        if (gl == 0) {
+          atomicAdd(&g_feet_cycles[1], (unsigned long long)(clock64() - tf0));
+          atomicAdd(&g_feet_cycles[3], 1ull);
+          if (rr) atomicAdd(&g_feet_cycles[3 + rr], 1ull);
+        }
+#endif
+      }
+#ifdef ARTP_STAGE_TIMING
+      if (lane == 0) atomicAdd(&g_feet_cycles[11], 1ull);
+#endif
+      const unsigned o4 = grp_bits4(__ballot(rr != 1)), p4 = grp_bits4(__ballot(rr == 2));
+#pragma unroll
+      for (int g = 0; g < GPW; ++g)
+        if (at[g] < 32u) {
+          open |= ((o4 >> g) & 1u) << at[g];
+          partner |= ((p4 >> g) & 1u) << at[g];
+        }
     }
     // the boxes still open, four per round: the record is read again (it is in L2)
     while (open) {

@@ -43,12 +43,18 @@ print("  ticks per box: record %.0f, stream %.0f per streamed box, corner stage 
       % (a[0, 0] / max(t_taken, 1), a[0, 2] / max(t_stream, 1), a[0, 4] / max(t_corner, 1), a[0, 6] / max(t_taken + t_skip, 1)))
 ff = (C.c_ulonglong * 20)()
 L.artp_debug_stage_cycles(ff, 3)  # reset >= 3: the feet_stream counters
-print("feet_stream: stream ticks", ff[0], "corner ticks", ff[1], "boxes that ran the second stage", ff[2], "boxes taken", ff[3],
+print("feet_stream: stream ticks", ff[0], "corner ticks", ff[1], "boxes that ran the second stage", ff[2], "boxes that ran the corner stage", ff[3],
       "corner result 1 (contact)", ff[4], "2 (may have partners)", ff[5], "streams that found a vertex", ff[6])
-# the corner stage runs first: the boxes that ran the second stage are the streamed ones (all boxes run the corner stage)
+# the pre-pass (two lanes per box, the lowest corner) runs first; ticks are per wavefront here, per 16-lane group above
+live, settled, border, pre_ticks, rounds, face = (int(ff[k]) for k in range(7, 13))
+print("  pre-pass: boxes live %d, settled %d (X = %.3f of the live), refused at a cell border %d, ticks %d (%.0f per live box), "
+      "corner rounds %d (%.2f per chunk of 32 live boxes); the four bottom-face corners would settle %d (X = %.3f)"
+      % (live, settled, settled / max(live, 1), border, pre_ticks, pre_ticks / max(live, 1), rounds, rounds * 32 / max(live, 1),
+         face, face / max(live, 1)))
+# the boxes that ran the second stage are the streamed ones
 n_stream, n_corner = ff[2], ff[3]
-print("  per box: stream (S) %.0f ticks, corner stage (C) %.0f ticks, C / S %.2f; streamed %.3f of the boxes taken, contact %.3f, "
-      "partners %.3f, vertex %.3f of the streamed"
+print("  per box: stream (S) %.0f ticks, corner stage (C) %.0f ticks, C / S %.2f; of the boxes that ran the corner stage: streamed "
+      "%.3f, contact %.3f, partners %.3f; vertex %.3f of the streamed"
       % (ff[0] / max(n_stream, 1), ff[1] / max(n_corner, 1), (ff[1] / max(n_corner, 1)) / max(ff[0] / max(n_stream, 1), 1e-9),
          n_stream / max(ff[3], 1), ff[4] / max(ff[3], 1), ff[5] / max(ff[3], 1), ff[6] / max(n_stream, 1)))
 ctx.sample_and_validate_dev(1234, n, n, se3, va)
