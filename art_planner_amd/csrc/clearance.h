@@ -305,16 +305,14 @@ int clearance_map_args(artp_ctx* c, const artp_clearance_params* p, int n_yaw, i
 int field_clearance_build(artp_ctx* c, artp_field* f, const double* tab) {
   hipStream_t st = c->stream;
   const artp_field_clearance_params& cp = f->cparams;
-  HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&f->d_btab), artp::FIELD_TAB * sizeof(double)));
+  HIP_TRY(c, f->mem.alloc(&f->d_btab, artp::FIELD_TAB));
   double* d_tab = f->d_btab;
-  HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&f->d_d2), f->n_nodes * sizeof(uint16_t)));
+  HIP_TRY(c, f->mem.alloc(&f->d_d2, f->n_nodes));
   HIP_TRY(c, hipMemcpyAsync(d_tab, tab, artp::FIELD_TAB * sizeof(double), hipMemcpyHostToDevice, st));
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-  for (hipEvent_t& x : ev)
-    if (hipEventCreate(&x) != hipSuccess) x = nullptr;
-  if (ev[0]) (void)hipEventRecord(ev[0], st);
+  StreamTimer<3> tm(st);
+  tm.mark(0);
   int rc = clearance_run(c, cp.clearance, f->grid.n_yaw, f->grid.nrows, f->grid.ncols, f->d_mask, f->d_d2);
-  if (ev[1]) (void)hipEventRecord(ev[1], st);
+  tm.mark(1);
   const size_t slots = artp::field_wtab_slots(f->grid);
   if (rc == ARTP_OK) {
     artp::FieldGrid Gb = f->grid;
@@ -325,13 +323,10 @@ int field_clearance_build(artp_ctx* c, artp_field* f, const double* tab) {
                        f->d_tab);
     if (hipGetLastError() != hipSuccess) rc = ARTP_ERR_HIP;
   }
-  if (ev[2]) (void)hipEventRecord(ev[2], st);
+  tm.mark(2);
   if (hipStreamSynchronize(st) != hipSuccess && rc == ARTP_OK) rc = ARTP_ERR_HIP;  // the host table is free from here
-  float t = 0.f;
-  if (rc == ARTP_OK && ev[0] && ev[1] && hipEventElapsedTime(&t, ev[0], ev[1]) == hipSuccess) f->lstats.rows_ms = t;
-  if (rc == ARTP_OK && ev[1] && ev[2] && hipEventElapsedTime(&t, ev[1], ev[2]) == hipSuccess) f->lstats.combine_ms = t;
-  for (hipEvent_t x : ev)
-    if (x) (void)hipEventDestroy(x);
+  f->lstats.rows_ms = tm.ms(0, 1, rc == ARTP_OK);
+  f->lstats.combine_ms = tm.ms(1, 2, rc == ARTP_OK);
   if (rc == ARTP_ERR_HIP && c->last_error.empty()) c->last_error = "clearance field: building the weight table failed";
   f->lstats.table_rows = slots;
   f->lstats.table_bytes = slots * sizeof(double);
@@ -437,112 +432,58 @@ int artp_field_update_clearance(artp_field* f, const uint32_t* new_mask, int mas
   artp_ctx* c = f->ctx;
   std::lock_guard<std::recursive_mutex> lock(c->mu);
   const artp::FieldGrid& G = f->grid;
-  // 1. the checks: nothing is written before the last of them
   if (G.objective != 3) {
     c->last_error = "artp_field_update_clearance: not a field of artp_field_compute_clearance (artp_field_update and "
                     "artp_field_update_learned take the others)";
     return ARTP_ERR_INVALID_ARG;
   }
-  artp::FieldSub sub{0, 0, G.nrows, G.ncols};
-  if (sub_rect) sub = artp::FieldSub{sub_rect[0], sub_rect[1], sub_rect[2], sub_rect[3]};
-  if (sub.nrows < 1 || sub.ncols < 1 || sub.row0 < 0 || sub.col0 < 0 || sub.row0 > G.nrows - sub.nrows ||
-      sub.col0 > G.ncols - sub.ncols) {
-    c->last_error = "artp_field_update_clearance: sub_rect is empty or not inside the field's rectangle";
-    return ARTP_ERR_INVALID_ARG;
-  }
-  const MapGeom &a = f->geom, &b = c->geom;
-  const bool same_map = reach_have_lattice(c) && a.rows == b.rows && a.cols == b.cols && a.len_x == b.len_x &&
-                        a.len_y == b.len_y && a.pos_x == b.pos_x && a.pos_y == b.pos_y && a.res == b.res;
+  artp::FieldSub sub;
+  ARTP_TRY(field_sub_rect(f, "artp_field_update_clearance", sub_rect, &sub));
+  const bool same_map = field_same_map(c, f);
   if (refresh_heights && !same_map) {
     c->last_error = "artp_field_update_clearance: refresh_heights needs sampler layers of the geometry the field was computed on";
     return ARTP_ERR_INVALID_ARG;
   }
-  HIP_TRY(c, hipSetDevice(c->device));
-  hipStream_t st = c->stream;
-  ARTP_TRY(field_update_scratch(f, !mask_on_device));
-  if (!f->d_wacc) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&f->d_wacc), f->n_tiles * sizeof(unsigned)));
-  HIP_TRY(c, hipMemsetAsync(f->d_acc, 0, f->n_tiles * sizeof(unsigned), st));
-  HIP_TRY(c, hipMemsetAsync(f->d_wacc, 0, f->n_tiles * sizeof(unsigned), st));
-  HIP_TRY(c, hipMemsetAsync(f->d_ucnt, 0, 8 * sizeof(unsigned long long), st));
-  // 2. the mask diff, behind the test of the sources on the device
-  unsigned long long cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  ARTP_TRY(field_update_diff(f, new_mask, mask_on_device, sub, refresh_heights != 0, refresh_heights ? c->sampler : f->sampler, cnt));
-  if (cnt[4]) {
-    c->last_error = "artp_field_update_clearance: a source is no longer a node of the mask (the field is unchanged)";
-    return ARTP_ERR_INVALID_ARG;
-  }
-  artp_field_clearance_update_stats_t us{};
-  us.changed_words = cnt[0];
-  us.removed_nodes = cnt[1];
-  us.added_nodes = cnt[2];
-  us.reached_nodes = f->stats.reached_nodes;
-  if (cnt[0] || cnt[3]) {
-    // 3. d2 again on the tiles within R cells of sub_rect (d_ucnt[7] += the nodes whose value changed), 4. the slots of the
-    // tiles within R + 1 cells priced again; a slot whose bits change flags its tile
-    const int R = f->cparams.clearance.radius_cells;
-    const ClearTiles cw = clearance_window(G, sub, R), pw = clearance_window(G, sub, R + 1);
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    for (hipEvent_t& x : ev)
-      if (hipEventCreate(&x) != hipSuccess) x = nullptr;
-    if (ev[0]) (void)hipEventRecord(ev[0], st);
-    int rc = clearance_run(c, f->cparams.clearance, G.n_yaw, G.nrows, G.ncols, f->d_mask, f->d_d2, &cw, f->d_ucnt + 7);
-    if (ev[1]) (void)hipEventRecord(ev[1], st);
-    if (rc == ARTP_OK) {
-      artp::FieldGrid Gb = G;
-      Gb.objective = f->params.objective;
-      const artp::ClearWeight w{f->geom.res, f->cparams.margin, f->cparams.gain};
-      hipLaunchKernelGGL(artp::field_clearance_reprice_kernel, dim3((unsigned)(pw.n * 10 * (size_t)G.n_yaw)), dim3(256), 0, st, Gb,
-                         pw.w, (const uint32_t*)f->d_mask, (const float*)f->d_h, (const double*)f->d_btab,
-                         (const uint16_t*)f->d_d2, w, f->d_tab, f->d_acc, f->d_wacc, f->d_ucnt);
-      if (hipGetLastError() != hipSuccess) rc = ARTP_ERR_HIP;
-    }
-    if (ev[2]) (void)hipEventRecord(ev[2], st);
-    if (rc == ARTP_OK) {
-      hipLaunchKernelGGL(artp::field_count_flags_kernel, dim3((unsigned)((f->n_tiles + 255) / 256)), dim3(256), 0, st,
-                         (uint32_t)f->n_tiles, (const unsigned*)f->d_wacc, f->d_ucnt);
-      if (hipGetLastError() != hipSuccess ||
-          hipMemcpyAsync(cnt + 5, f->d_ucnt + 5, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st) != hipSuccess)
-        rc = ARTP_ERR_HIP;
-    }
-    if (hipStreamSynchronize(st) != hipSuccess && rc == ARTP_OK) rc = ARTP_ERR_HIP;
-    float t = 0.f;
-    if (rc == ARTP_OK && ev[0] && ev[1] && hipEventElapsedTime(&t, ev[0], ev[1]) == hipSuccess) us.clearance_ms = t;
-    if (rc == ARTP_OK && ev[1] && ev[2] && hipEventElapsedTime(&t, ev[1], ev[2]) == hipSuccess) us.reprice_ms = t;
-    for (hipEvent_t x : ev)
-      if (x) (void)hipEventDestroy(x);
-    if (rc) {
-      if (rc == ARTP_ERR_HIP && c->last_error.empty()) c->last_error = "artp_field_update_clearance: repricing the weight table failed";
-      return rc;
-    }
-    us.clearance_tiles = cw.n;
-    us.changed_d2 = cnt[7];
-    us.repriced_slots = pw.n * 10 * (uint64_t)G.n_yaw * (artp::FIELD_T * artp::FIELD_T);
-    us.changed_slots = cnt[5];
-    us.weight_tiles = cnt[6];
-    // 5. the passes of artp_field_update, from the tiles flagged by the diff and by the changed weights
-    artp_field_update_stats_t ps{};
-    const auto t0 = std::chrono::steady_clock::now();
-    rc = field_update_passes(f, &ps);
-    if (rc) {
-      (void)hipStreamSynchronize(st);
-      return rc;
-    }
-    us.passes_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    us.dead_nodes = ps.dead_nodes;
-    us.hop_dead_nodes = ps.hop_dead_nodes;
-    us.unsupport_rounds = ps.unsupport_rounds;
-    us.dist_rounds = ps.dist_rounds;
-    us.hop_rounds = ps.hop_rounds;
-    us.tile_launches = ps.tile_launches;
-    us.reached_nodes = ps.reached_nodes;
-    f->stats.reached_nodes = us.reached_nodes;  // the other numbers of artp_field_compute_clearance stay
-  }
-  if (same_map) {  // artp_field_path's poses: the current sampler layers, as a new field would take them
-    f->sampler = c->sampler;
-    f->map_version = c->map_version.load();
-  }
-  f->custats = us;
-  return ARTP_OK;
+  // The kind's step, when a word or a height changed: d2 again on the tiles within R cells of sub_rect (d_ucnt[7] += the
+  // nodes whose value changed), then the slots of the tiles within R + 1 cells priced again; a slot whose bits change flags
+  // its tile.  The passes run whenever the windows ran.
+  return field_update_run(
+      f, "artp_field_update_clearance", new_mask, mask_on_device, sub, refresh_heights != 0, same_map, &f->custats,
+      [&](unsigned long long* cnt, artp_field_clearance_update_stats_t* us, bool* run) -> int {
+        if (!cnt[0] && !cnt[3]) return ARTP_OK;
+        hipStream_t st = c->stream;
+        const int R = f->cparams.clearance.radius_cells;
+        const ClearTiles cw = clearance_window(G, sub, R), pw = clearance_window(G, sub, R + 1);
+        StreamTimer<3> tm(st);
+        tm.mark(0);
+        int rc = clearance_run(c, f->cparams.clearance, G.n_yaw, G.nrows, G.ncols, f->d_mask, f->d_d2, &cw, f->d_ucnt + 7);
+        tm.mark(1);
+        if (rc == ARTP_OK) {
+          artp::FieldGrid Gb = G;
+          Gb.objective = f->params.objective;
+          const artp::ClearWeight w{f->geom.res, f->cparams.margin, f->cparams.gain};
+          hipLaunchKernelGGL(artp::field_clearance_reprice_kernel, dim3((unsigned)(pw.n * 10 * (size_t)G.n_yaw)), dim3(256), 0, st, Gb,
+                             pw.w, (const uint32_t*)f->d_mask, (const float*)f->d_h, (const double*)f->d_btab,
+                             (const uint16_t*)f->d_d2, w, f->d_tab, f->d_acc, f->d_wacc, f->d_ucnt);
+          if (hipGetLastError() != hipSuccess) rc = ARTP_ERR_HIP;
+        }
+        tm.mark(2);
+        if (rc == ARTP_OK) rc = field_weight_counts(f, cnt, 3);
+        if (rc) {
+          (void)hipStreamSynchronize(st);
+          if (rc == ARTP_ERR_HIP && c->last_error.empty()) c->last_error = "artp_field_update_clearance: repricing the weight table failed";
+          return rc;
+        }
+        us->clearance_ms = tm.ms(0, 1, true);
+        us->reprice_ms = tm.ms(1, 2, true);
+        us->clearance_tiles = cw.n;
+        us->changed_d2 = cnt[7];
+        us->repriced_slots = pw.n * 10 * (uint64_t)G.n_yaw * (artp::FIELD_T * artp::FIELD_T);
+        us->changed_slots = cnt[5];
+        us->weight_tiles = cnt[6];
+        *run = true;
+        return ARTP_OK;
+      });
 }
 
 int artp_field_clearance_update_stats(artp_field* f, artp_field_clearance_update_stats_t* out) {

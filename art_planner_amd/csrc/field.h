@@ -58,7 +58,11 @@
 // and the same table-driven kernels search it (field_has_wtab).  A mask edit moves clearances, and with them weights, up to
 // radius_cells around it: artp_field_update and artp_field_update_learned refuse such a field, artp_field_update_clearance
 // (clearance.h) recomputes both on a window of tiles and runs the passes of artp_field_update.
+// The host side of the three updates is one procedure, field_update_run; an entry point adds its refusals and its own step.
 #pragma once
+
+#include <cstddef>
+#include <deque>
 
 namespace artp {
 
@@ -851,36 +855,71 @@ struct artp_field {
   // artp_field_plan's scratch: per-target records, path nodes, poses, the move list, the (s1, s2) pairs and verdicts
   void* d_plan = nullptr;
   size_t plan_targets = 0, plan_states = 0;
+  DeviceScratch mem;  // owns every d_* above: freed with the field, or earlier by mem.release
 };
 
 namespace {
 
+// the caller has set the device
 void field_free(artp_field* f) {
-  for (void* p : {(void*)f->d_dist, (void*)f->d_hops, (void*)f->d_mask, (void*)f->d_h, (void*)f->d_tab, (void*)f->d_flags,
-                  (void*)f->d_nodes, (void*)f->d_out, (void*)f->d_src, (void*)f->d_snap, (void*)f->d_acc, (void*)f->d_ucnt,
-                  (void*)f->d_stage, (void*)f->d_lscratch, (void*)f->d_wacc, (void*)f->d_blk, (void*)f->d_d2, (void*)f->d_btab, f->d_plan})
-    if (p) (void)hipFree(p);
+  (void)hipStreamSynchronize(f->ctx->stream);
   delete f;
 }
 
-int field_ensure_scratch(artp_field* f, size_t ints, size_t doubles) {
-  artp_ctx* c = f->ctx;
-  if (f->nodes_cap < ints) {
-    if (f->d_nodes) HIP_TRY(c, hipFree(f->d_nodes));
-    f->d_nodes = nullptr;
-    f->nodes_cap = 0;
-    HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&f->d_nodes), ints * sizeof(int)));
-    f->nodes_cap = ints;
-  }
-  if (f->out_cap < doubles) {
-    if (f->d_out) HIP_TRY(c, hipFree(f->d_out));
-    f->d_out = nullptr;
-    f->out_cap = 0;
-    HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&f->d_out), doubles * sizeof(double)));
-    f->out_cap = doubles;
-  }
+// a buffer of the field that is allocated by whoever needs it first
+template <class T>
+int field_lazy(artp_field* f, T** p, size_t count) {
+  if (!*p) HIP_TRY(f->ctx, f->mem.alloc(p, count));
   return ARTP_OK;
 }
+
+// a buffer that grows to the largest request: the old block is freed ahead of the new one (its contents are scratch)
+template <class T>
+int field_grow(artp_field* f, T** p, size_t* cap, size_t count) {
+  if (*cap >= count) return ARTP_OK;
+  f->mem.release(*p);
+  *p = nullptr;
+  *cap = 0;
+  HIP_TRY(f->ctx, f->mem.alloc(p, count));
+  *cap = count;
+  return ARTP_OK;
+}
+
+int field_ensure_scratch(artp_field* f, size_t ints, size_t doubles) {
+  ARTP_TRY(field_grow(f, &f->d_nodes, &f->nodes_cap, ints));
+  return field_grow(f, &f->d_out, &f->out_cap, doubles);
+}
+
+// rows of the cost query per chunk of a learned field's table, and of its scratch (d_lscratch: 36 bytes a row)
+size_t field_learned_chunk(const artp::FieldGrid& G) { return std::min(artp::field_wtab_slots(G), artp::FIELD_LEARNED_CHUNK); }
+
+// N timing events on a stream.  An event that could not be created is skipped; ms(i, j, clean) is the stream time between
+// marks i and j, 0 unless both events exist and the caller says the run between them ended clean (and is synchronised).
+template <int N>
+class StreamTimer {
+ public:
+  explicit StreamTimer(hipStream_t st) : st_(st) {
+    for (hipEvent_t& x : e_)
+      if (hipEventCreate(&x) != hipSuccess) x = nullptr;
+  }
+  StreamTimer(const StreamTimer&) = delete;
+  StreamTimer& operator=(const StreamTimer&) = delete;
+  ~StreamTimer() {
+    for (hipEvent_t x : e_)
+      if (x) (void)hipEventDestroy(x);
+  }
+  void mark(int i) {
+    if (e_[i]) (void)hipEventRecord(e_[i], st_);
+  }
+  double ms(int i, int j, bool clean) const {
+    float t = 0.f;
+    return clean && e_[i] && e_[j] && hipEventElapsedTime(&t, e_[i], e_[j]) == hipSuccess ? (double)t : 0.0;
+  }
+
+ private:
+  hipStream_t st_;
+  hipEvent_t e_[N];
+};
 
 // the (m, k) table of objective 1 and the squared planar step lengths of objective 0
 void field_make_table(const artp_field_params& p, const MapGeom& g, int n_yaw, double* tab) {
@@ -999,47 +1038,37 @@ int field_learned_table(artp_ctx* c, artp_field* f, bool reprice, double ms[3], 
   const artp::FieldGrid& G = f->grid;
   const artp_field_learned_params& lp = f->lparams;
   const artp::FieldPricing price{lp.w_energy, lp.w_time, lp.w_risk, lp.risk_threshold};
-  const size_t slots = artp::field_wtab_slots(G);
-  const size_t chunk = slots < artp::FIELD_LEARNED_CHUNK ? slots : artp::FIELD_LEARNED_CHUNK;
-  if (!f->d_lscratch) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&f->d_lscratch), chunk * 9 * sizeof(float)));
+  const size_t slots = artp::field_wtab_slots(G), chunk = field_learned_chunk(G);
+  ARTP_TRY(field_lazy(f, &f->d_lscratch, chunk * 9));
   float* rows = f->d_lscratch;
   float* cost3 = f->d_lscratch + chunk * 6;
-  std::vector<hipEvent_t> ev;
+  std::deque<StreamTimer<4>> timers;  // one per chunk, read behind the one synchronisation
   int rc = ARTP_OK;
   for (size_t first = 0; first < slots && rc == ARTP_OK; first += chunk) {
     const uint32_t n = (uint32_t)(slots - first < chunk ? slots - first : chunk);
     const unsigned blocks = (n + 255) / 256;
-    for (int e = 0; e < 4; ++e) {
-      hipEvent_t x = nullptr;
-      if (hipEventCreate(&x) != hipSuccess) x = nullptr;
-      ev.push_back(x);
-    }
-    hipEvent_t* e4 = ev.data() + ev.size() - 4;
-    if (e4[0]) (void)hipEventRecord(e4[0], st);
+    StreamTimer<4>& tm = timers.emplace_back(st);
+    tm.mark(0);
     hipLaunchKernelGGL(artp::field_learned_rows_kernel, dim3(blocks), dim3(256), 0, st, G, f->sampler, f->geom, f->rect,
                        (const uint32_t*)f->d_mask, first, n, rows);
-    if (e4[1]) (void)hipEventRecord(e4[1], st);
+    tm.mark(1);
     rc = artp_cost_query_dev(c, rows, n, cost3);
     if (rc) break;
-    if (e4[2]) (void)hipEventRecord(e4[2], st);
+    tm.mark(2);
     if (reprice)
       hipLaunchKernelGGL(artp::field_learned_reprice_kernel, dim3(blocks), dim3(256), 0, st, G, (const uint32_t*)f->d_mask, first,
                          n, (const float*)cost3, price, f->d_tab, f->d_acc, f->d_wacc, f->d_ucnt);
     else
       hipLaunchKernelGGL(artp::field_learned_combine_kernel, dim3(blocks), dim3(256), 0, st, G, (const uint32_t*)f->d_mask, first,
                          n, (const float*)cost3, price, f->d_tab);
-    if (e4[3]) (void)hipEventRecord(e4[3], st);
+    tm.mark(3);
     if (hipGetLastError() != hipSuccess) rc = ARTP_ERR_HIP;
     ++*chunks;
   }
   if (hipStreamSynchronize(st) != hipSuccess && rc == ARTP_OK) rc = ARTP_ERR_HIP;
-  for (size_t i = 0; i + 3 < ev.size(); i += 4)
-    for (int q = 0; q < 3; ++q) {
-      float t = 0.f;
-      if (rc == ARTP_OK && ev[i + q] && ev[i + q + 1] && hipEventElapsedTime(&t, ev[i + q], ev[i + q + 1]) == hipSuccess) ms[q] += t;
-    }
-  for (hipEvent_t x : ev)
-    if (x) (void)hipEventDestroy(x);
+  for (const StreamTimer<4>& tm : timers)
+    for (int q = 0; q < 3; ++q) ms[q] += tm.ms(q, q + 1, rc == ARTP_OK);
+  timers.clear();
   (void)hipGetLastError();
   if (rc == ARTP_ERR_HIP && c->last_error.empty()) c->last_error = "learned field: pricing the weight table failed";
   return rc;
@@ -1053,7 +1082,7 @@ int field_learned_build(artp_ctx* c, artp_field* f) {
   f->lstats.rows_ms = ms[0];
   f->lstats.query_ms = ms[1];
   f->lstats.combine_ms = ms[2];
-  HIP_TRY(c, hipFree(f->d_lscratch));
+  f->mem.release(f->d_lscratch);
   f->d_lscratch = nullptr;
   f->lstats.table_rows = artp::field_wtab_slots(f->grid);
   f->lstats.table_bytes = f->lstats.table_rows * sizeof(double);
@@ -1069,8 +1098,7 @@ int field_compute_impl(artp_ctx* c, artp_field* f, const uint32_t* mask, int mas
   const bool learned = G.objective == 2, wtab = artp::field_has_wtab(G);
   const size_t tab_doubles = wtab ? artp::field_wtab_slots(G) : (size_t)artp::FIELD_TAB;
   if (wtab) {  // 80 bytes per node and the padding of the edge tiles, plus a chunk of query scratch (learned) or d2 (clearance)
-    const size_t chunk = tab_doubles < artp::FIELD_LEARNED_CHUNK ? tab_doubles : artp::FIELD_LEARNED_CHUNK;
-    const size_t extra = learned ? chunk * 9 * sizeof(float) : f->n_nodes * sizeof(uint16_t) + artp::FIELD_TAB * sizeof(double);
+    const size_t extra = learned ? field_learned_chunk(G) * 9 * sizeof(float) : f->n_nodes * sizeof(uint16_t) + artp::FIELD_TAB * sizeof(double);
     const size_t need = tab_doubles * sizeof(double) + extra + f->n_nodes * 12 + f->n_cells * 8;
     size_t free_b = 0, total_b = 0;
     HIP_TRY(c, hipMemGetInfo(&free_b, &total_b));
@@ -1081,12 +1109,12 @@ int field_compute_impl(artp_ctx* c, artp_field* f, const uint32_t* mask, int mas
       return ARTP_ERR_CAPACITY;
     }
   }
-  HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&f->d_dist), f->n_nodes * sizeof(double)));
-  HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&f->d_hops), f->n_nodes * sizeof(uint32_t)));
-  HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&f->d_mask), f->n_cells * sizeof(uint32_t)));
-  HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&f->d_h), f->n_cells * sizeof(float)));
-  HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&f->d_tab), tab_doubles * sizeof(double)));
-  HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&f->d_flags), (2 * f->n_tiles + 4) * sizeof(unsigned)));
+  HIP_TRY(c, f->mem.alloc(&f->d_dist, f->n_nodes));
+  HIP_TRY(c, f->mem.alloc(&f->d_hops, f->n_nodes));
+  HIP_TRY(c, f->mem.alloc(&f->d_mask, f->n_cells));
+  HIP_TRY(c, f->mem.alloc(&f->d_h, f->n_cells));
+  HIP_TRY(c, f->mem.alloc(&f->d_tab, tab_doubles));
+  HIP_TRY(c, f->mem.alloc(&f->d_flags, 2 * f->n_tiles + 4));
   int rc = field_ensure_scratch(f, 3 * n_sources, 8);
   if (rc) return rc;
   double tab[artp::FIELD_TAB];
@@ -1135,16 +1163,19 @@ int field_compute_impl(artp_ctx* c, artp_field* f, const uint32_t* mask, int mas
   return field_count_reached(f, &f->stats.reached_nodes);
 }
 
-int field_update_scratch(artp_field* f, bool stage) {
+// What an update, a block or a plan works in, allocated by the first of them.  stage: d_stage, for a host mask; wacc:
+// d_wacc, for the two kinds whose weights sit in the table.
+int field_update_scratch(artp_field* f, bool stage, bool wacc = false) {
   artp_ctx* c = f->ctx;
   if (!f->d_src) {
-    HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&f->d_src), f->h_src.size() * sizeof(int)));
+    HIP_TRY(c, f->mem.alloc(&f->d_src, f->h_src.size()));
     HIP_TRY(c, hipMemcpyAsync(f->d_src, f->h_src.data(), f->h_src.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
   }
-  if (!f->d_snap) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&f->d_snap), f->n_nodes * sizeof(double)));
-  if (!f->d_acc) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&f->d_acc), f->n_tiles * sizeof(unsigned)));
-  if (!f->d_ucnt) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&f->d_ucnt), 8 * sizeof(unsigned long long)));
-  if (stage && !f->d_stage) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&f->d_stage), f->n_cells * sizeof(uint32_t)));
+  ARTP_TRY(field_lazy(f, &f->d_snap, f->n_nodes));
+  ARTP_TRY(field_lazy(f, &f->d_acc, f->n_tiles));
+  ARTP_TRY(field_lazy(f, &f->d_ucnt, 8));
+  if (stage) ARTP_TRY(field_lazy(f, &f->d_stage, f->n_cells));
+  if (wacc) ARTP_TRY(field_lazy(f, &f->d_wacc, f->n_tiles));
   return ARTP_OK;
 }
 
@@ -1199,6 +1230,112 @@ int field_update_diff(artp_field* f, const uint32_t* new_mask, int mask_on_devic
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipMemcpyAsync(cnt, f->d_ucnt, 5 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
   HIP_TRY(c, hipStreamSynchronize(st));  // the host copy of the mask is free from here
+  return ARTP_OK;
+}
+
+// sub_rect of an update or an unblock as a FieldSub (nullptr: the whole rectangle); `who` is the entry point in the error
+int field_sub_rect(artp_field* f, const char* who, const int* sub_rect, artp::FieldSub* sub) {
+  const artp::FieldGrid& G = f->grid;
+  *sub = sub_rect ? artp::FieldSub{sub_rect[0], sub_rect[1], sub_rect[2], sub_rect[3]} : artp::FieldSub{0, 0, G.nrows, G.ncols};
+  if (sub->nrows < 1 || sub->ncols < 1 || sub->row0 < 0 || sub->col0 < 0 || sub->row0 > G.nrows - sub->nrows ||
+      sub->col0 > G.ncols - sub->ncols) {
+    f->ctx->last_error = std::string(who) + ": sub_rect is empty or not inside the field's rectangle";
+    return ARTP_ERR_INVALID_ARG;
+  }
+  return ARTP_OK;
+}
+
+// the context's sampler layers have the geometry the field was computed on
+bool field_same_map(artp_ctx* c, const artp_field* f) {
+  const MapGeom &a = f->geom, &b = c->geom;
+  return reach_have_lattice(c) && a.rows == b.rows && a.cols == b.cols && a.len_x == b.len_x && a.len_y == b.len_y &&
+         a.pos_x == b.pos_x && a.pos_y == b.pos_y && a.res == b.res;
+}
+
+// artp_field_path's poses: the current sampler layers, as a new field would take them
+void field_adopt_sampler(artp_ctx* c, artp_field* f) {
+  f->sampler = c->sampler;
+  f->map_version = c->map_version.load();
+}
+
+// The stats of the two weight-table updates begin with the members of artp_field_update_stats_t, at its offsets.
+#define FIELD_STATS_PREFIX(X)                                                                                         \
+  X(changed_words) X(removed_nodes) X(added_nodes) X(dead_nodes) X(hop_dead_nodes) X(unsupport_rounds) X(dist_rounds) \
+  X(hop_rounds) X(tile_launches) X(reached_nodes)
+#define FIELD_STATS_SAME_OFFSET(m)                                                                              \
+  static_assert(offsetof(artp_field_learned_update_stats_t, m) == offsetof(artp_field_update_stats_t, m) &&     \
+                    offsetof(artp_field_clearance_update_stats_t, m) == offsetof(artp_field_update_stats_t, m), \
+                "the update stats structs share their first ten members");
+FIELD_STATS_PREFIX(FIELD_STATS_SAME_OFFSET)
+static_assert(sizeof(artp_field_update_stats_t) == 10 * sizeof(uint64_t), "ten members, and FIELD_STATS_PREFIX names them all");
+void field_store_stats(const artp_field_update_stats_t& ps, double, artp_field_update_stats_t* out) { *out = ps; }
+template <class Stats>
+void field_store_stats(const artp_field_update_stats_t& ps, double passes_ms, Stats* out) {
+#define FIELD_STATS_COPY(m) out->m = ps.m;
+  FIELD_STATS_PREFIX(FIELD_STATS_COPY)
+  out->passes_ms = passes_ms;
+}
+#undef FIELD_STATS_COPY
+#undef FIELD_STATS_SAME_OFFSET
+#undef FIELD_STATS_PREFIX
+
+// the tiles flagged in d_wacc counted into d_ucnt[6]; cnt[5 .. 5 + n) read from the device (synchronises)
+int field_weight_counts(artp_field* f, unsigned long long* cnt, int n) {
+  artp_ctx* c = f->ctx;
+  hipLaunchKernelGGL(artp::field_count_flags_kernel, dim3((unsigned)((f->n_tiles + 255) / 256)), dim3(256), 0, c->stream,
+                     (uint32_t)f->n_tiles, (const unsigned*)f->d_wacc, f->d_ucnt);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(cnt + 5, f->d_ucnt + 5, n * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return ARTP_OK;
+}
+
+// The update of a field of any kind behind its entry point's checks: the scratch, the diff of
+// new_mask inside sub (nullptr: no diff) behind the test of the sources, the kind's own step, the four passes, the
+// sampler adopted where it fits the field (adopt), the stats stored.  middle(cnt, us, run) is the kind's step: cnt = the
+// counts of d_ucnt read so far, us = its stats to complete; it sets *run when the passes are to run.  `who` is the entry
+// point in the error.  A refusal writes nothing; a failure later leaves the field undefined.
+template <class Stats, class Middle>
+int field_update_run(artp_field* f, const char* who, const uint32_t* new_mask, int mask_on_device, const artp::FieldSub& sub,
+                     bool refresh, bool adopt, Stats* stored, Middle&& middle) {
+  artp_ctx* c = f->ctx;
+  HIP_TRY(c, hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  const bool wtab = artp::field_has_wtab(f->grid);
+  ARTP_TRY(field_update_scratch(f, new_mask && !mask_on_device, wtab));
+  HIP_TRY(c, hipMemsetAsync(f->d_acc, 0, f->n_tiles * sizeof(unsigned), st));
+  if (wtab) HIP_TRY(c, hipMemsetAsync(f->d_wacc, 0, f->n_tiles * sizeof(unsigned), st));
+  HIP_TRY(c, hipMemsetAsync(f->d_ucnt, 0, 8 * sizeof(unsigned long long), st));
+  unsigned long long cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (new_mask) {
+    ARTP_TRY(field_update_diff(f, new_mask, mask_on_device, sub, refresh, refresh ? c->sampler : f->sampler, cnt));
+    if (cnt[4]) {
+      c->last_error = std::string(who) + ": a source is no longer a node of the mask (the field is unchanged)";
+      return ARTP_ERR_INVALID_ARG;
+    }
+  }
+  artp_field_update_stats_t ps{};
+  ps.changed_words = cnt[0];
+  ps.removed_nodes = cnt[1];
+  ps.added_nodes = cnt[2];
+  ps.reached_nodes = f->stats.reached_nodes;
+  Stats us{};
+  bool run = false;
+  ARTP_TRY(middle(cnt, &us, &run));
+  double passes_ms = 0.0;
+  if (run) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const int rc = field_update_passes(f, &ps);
+    if (rc) {
+      (void)hipStreamSynchronize(st);
+      return rc;
+    }
+    passes_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    f->stats.reached_nodes = ps.reached_nodes;  // the other numbers of the compute stay
+  }
+  if (adopt) field_adopt_sampler(c, f);
+  field_store_stats(ps, passes_ms, &us);
+  *stored = us;
   return ARTP_OK;
 }
 
@@ -1361,7 +1498,6 @@ int field_create(artp_ctx* c, const artp_field_params& params, const artp_field_
   f->stats.tiles = f->n_tiles;
   const int rc = field_compute_impl(c, f, mask, mask_on_device, sources, n_sources);
   if (rc) {
-    (void)hipStreamSynchronize(c->stream);
     field_free(f);
     return rc;
   }
@@ -1476,63 +1612,29 @@ int artp_field_update(artp_field* f, const uint32_t* new_mask, int mask_on_devic
   if (!f || !new_mask) return ARTP_ERR_INVALID_ARG;
   artp_ctx* c = f->ctx;
   std::lock_guard<std::recursive_mutex> lock(c->mu);
-  const artp::FieldGrid& G = f->grid;
-  if (G.objective == 3) {
+  if (f->grid.objective == 3) {
     c->last_error = "artp_field_update: a clearance-weighted field is not updated by a mask edit alone (it moves clearances, and "
                     "with them the weights, up to radius_cells around it): artp_field_update_clearance takes it";
     return ARTP_ERR_INVALID_ARG;
   }
-  if (G.objective == 2) {
+  if (f->grid.objective == 2) {
     c->last_error = "artp_field_update: a learned field is not updated by a mask edit alone (a map change moves the network's "
                     "features, and with them the weights, far beyond sub_rect): artp_field_update_learned prices it again";
     return ARTP_ERR_INVALID_ARG;
   }
-  artp::FieldSub sub{0, 0, G.nrows, G.ncols};
-  if (sub_rect) sub = artp::FieldSub{sub_rect[0], sub_rect[1], sub_rect[2], sub_rect[3]};
-  if (sub.nrows < 1 || sub.ncols < 1 || sub.row0 < 0 || sub.col0 < 0 || sub.row0 > G.nrows - sub.nrows ||
-      sub.col0 > G.ncols - sub.ncols) {
-    c->last_error = "artp_field_update: sub_rect is empty or not inside the field's rectangle";
-    return ARTP_ERR_INVALID_ARG;
-  }
-  const MapGeom &a = f->geom, &b = c->geom;
-  const bool same_map = reach_have_lattice(c) && a.rows == b.rows && a.cols == b.cols && a.len_x == b.len_x &&
-                        a.len_y == b.len_y && a.pos_x == b.pos_x && a.pos_y == b.pos_y && a.res == b.res;
+  artp::FieldSub sub;
+  ARTP_TRY(field_sub_rect(f, "artp_field_update", sub_rect, &sub));
+  const bool same_map = field_same_map(c, f);
   if (refresh_heights && !same_map) {
     c->last_error = "artp_field_update: refresh_heights needs sampler layers of the geometry the field was computed on";
     return ARTP_ERR_INVALID_ARG;
   }
-  HIP_TRY(c, hipSetDevice(c->device));
-  hipStream_t st = c->stream;
-  int rc = field_update_scratch(f, !mask_on_device);
-  if (rc) return rc;
-  HIP_TRY(c, hipMemsetAsync(f->d_acc, 0, f->n_tiles * sizeof(unsigned), st));
-  HIP_TRY(c, hipMemsetAsync(f->d_ucnt, 0, 8 * sizeof(unsigned long long), st));
-  unsigned long long cnt[5] = {0, 0, 0, 0, 0};
-  rc = field_update_diff(f, new_mask, mask_on_device, sub, refresh_heights != 0, refresh_heights ? c->sampler : f->sampler, cnt);
-  if (rc) return rc;
-  if (cnt[4]) {
-    c->last_error = "artp_field_update: a source is no longer a node of the mask (the field is unchanged)";
-    return ARTP_ERR_INVALID_ARG;
-  }
-  artp_field_update_stats_t us{};
-  us.changed_words = cnt[0];
-  us.removed_nodes = cnt[1];
-  us.added_nodes = cnt[2];
-  us.reached_nodes = f->stats.reached_nodes;
-  if (cnt[0] || cnt[3]) {
-    rc = field_update_passes(f, &us);
-    if (rc) {
-      (void)hipStreamSynchronize(st);
-      return rc;
-    }
-    f->stats.reached_nodes = us.reached_nodes;  // the other numbers of artp_field_compute stay
-  }
-  if (same_map) {  // artp_field_path's poses: the current sampler layers, as a new field would take them
-    f->sampler = c->sampler;
-    f->map_version = c->map_version.load();
-  }
-  f->ustats = us;
-  return ARTP_OK;
+  // the kind's step: none.  The passes run when a word or a height changed.
+  return field_update_run(f, "artp_field_update", new_mask, mask_on_device, sub, refresh_heights != 0, same_map, &f->ustats,
+                          [](const unsigned long long* cnt, artp_field_update_stats_t*, bool* run) -> int {
+                            *run = cnt[0] || cnt[3];
+                            return ARTP_OK;
+                          });
 }
 
 int artp_field_update_stats(artp_field* f, artp_field_update_stats_t* out) {
@@ -1545,9 +1647,7 @@ int artp_field_update_learned(artp_field* f, const uint32_t* new_mask, int mask_
   if (!f) return ARTP_ERR_INVALID_ARG;
   artp_ctx* c = f->ctx;
   std::lock_guard<std::recursive_mutex> lock(c->mu);
-  const artp::FieldGrid& G = f->grid;
-  // 1. the checks: nothing is written before the last of them
-  if (G.objective != 2) {
+  if (f->grid.objective != 2) {
     c->last_error = "artp_field_update_learned: not a field of artp_field_compute_learned (artp_field_update and "
                     "artp_field_update_clearance take the others)";
     return ARTP_ERR_INVALID_ARG;
@@ -1560,91 +1660,34 @@ int artp_field_update_learned(artp_field* f, const uint32_t* new_mask, int mask_
     c->last_error = "artp_field_update_learned: artp_cost_update_map has not been called";
     return ARTP_ERR_NO_MAP;
   }
-  artp::FieldSub sub{0, 0, G.nrows, G.ncols};
-  if (new_mask && sub_rect) sub = artp::FieldSub{sub_rect[0], sub_rect[1], sub_rect[2], sub_rect[3]};
-  if (sub.nrows < 1 || sub.ncols < 1 || sub.row0 < 0 || sub.col0 < 0 || sub.row0 > G.nrows - sub.nrows ||
-      sub.col0 > G.ncols - sub.ncols) {
-    c->last_error = "artp_field_update_learned: sub_rect is empty or not inside the field's rectangle";
-    return ARTP_ERR_INVALID_ARG;
-  }
-  const MapGeom &a = f->geom, &b = c->geom;
-  const bool same_map = reach_have_lattice(c) && a.rows == b.rows && a.cols == b.cols && a.len_x == b.len_x &&
-                        a.len_y == b.len_y && a.pos_x == b.pos_x && a.pos_y == b.pos_y && a.res == b.res;
-  if (!same_map) {
+  artp::FieldSub sub;
+  ARTP_TRY(field_sub_rect(f, "artp_field_update_learned", new_mask ? sub_rect : nullptr, &sub));
+  if (!field_same_map(c, f)) {
     c->last_error = "artp_field_update_learned: the sampler layers do not have the geometry the field was computed on";
     return ARTP_ERR_INVALID_ARG;
   }
-  HIP_TRY(c, hipSetDevice(c->device));
-  hipStream_t st = c->stream;
-  int rc = field_update_scratch(f, new_mask && !mask_on_device);
-  if (rc) return rc;
-  const size_t slots = artp::field_wtab_slots(G);
-  if (!f->d_wacc) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&f->d_wacc), f->n_tiles * sizeof(unsigned)));
-  if (!f->d_lscratch) {  // 36 bytes a row of a chunk, kept until artp_field_destroy
-    const size_t chunk = slots < artp::FIELD_LEARNED_CHUNK ? slots : artp::FIELD_LEARNED_CHUNK;
-    HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&f->d_lscratch), chunk * 9 * sizeof(float)));
-  }
-  HIP_TRY(c, hipMemsetAsync(f->d_acc, 0, f->n_tiles * sizeof(unsigned), st));
-  HIP_TRY(c, hipMemsetAsync(f->d_wacc, 0, f->n_tiles * sizeof(unsigned), st));
-  HIP_TRY(c, hipMemsetAsync(f->d_ucnt, 0, 8 * sizeof(unsigned long long), st));
-  // 2. the mask diff, behind the test of the sources on the device
-  unsigned long long cnt[7] = {0, 0, 0, 0, 0, 0, 0};
-  if (new_mask) {
-    rc = field_update_diff(f, new_mask, mask_on_device, sub, false, f->sampler, cnt);
-    if (rc) return rc;
-    if (cnt[4]) {
-      c->last_error = "artp_field_update_learned: a source is no longer a node of the mask (the field is unchanged)";
-      return ARTP_ERR_INVALID_ARG;
-    }
-  }
-  // what a new field would hold: the current sampler layers and their heights
-  f->sampler = c->sampler;
-  f->map_version = c->map_version.load();
-  hipLaunchKernelGGL(artp::field_heights_kernel, dim3((unsigned)((f->n_cells + 255) / 256)), dim3(256), 0, st, f->sampler,
-                     f->geom, f->rect, f->d_h);
-  HIP_TRY(c, hipGetLastError());
-  // 3. every slot priced again; a slot whose bits change flags its tile
-  artp_field_learned_update_stats_t us{};
-  double ms[3] = {0.0, 0.0, 0.0};
-  uint64_t chunks = 0;
-  rc = field_learned_table(c, f, true, ms, &chunks);
-  if (rc) return rc;
-  hipLaunchKernelGGL(artp::field_count_flags_kernel, dim3((unsigned)((f->n_tiles + 255) / 256)), dim3(256), 0, st,
-                     (uint32_t)f->n_tiles, (const unsigned*)f->d_wacc, f->d_ucnt);
-  HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, hipMemcpyAsync(cnt + 5, f->d_ucnt + 5, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-  HIP_TRY(c, hipStreamSynchronize(st));
-  us.changed_words = cnt[0];
-  us.removed_nodes = cnt[1];
-  us.added_nodes = cnt[2];
-  us.reached_nodes = f->stats.reached_nodes;
-  us.repriced_slots = slots;
-  us.changed_slots = cnt[5];
-  us.weight_tiles = cnt[6];
-  us.rows_ms = ms[0];
-  us.query_ms = ms[1];
-  us.reprice_ms = ms[2];
-  // 4. the passes of artp_field_update, from the tiles flagged by the diff and by the changed weights
-  if (cnt[0] || cnt[5]) {
-    artp_field_update_stats_t ps{};
-    const auto t0 = std::chrono::steady_clock::now();
-    rc = field_update_passes(f, &ps);
-    if (rc) {
-      (void)hipStreamSynchronize(st);
-      return rc;
-    }
-    us.passes_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    us.dead_nodes = ps.dead_nodes;
-    us.hop_dead_nodes = ps.hop_dead_nodes;
-    us.unsupport_rounds = ps.unsupport_rounds;
-    us.dist_rounds = ps.dist_rounds;
-    us.hop_rounds = ps.hop_rounds;
-    us.tile_launches = ps.tile_launches;
-    us.reached_nodes = ps.reached_nodes;
-    f->stats.reached_nodes = us.reached_nodes;  // the other numbers of artp_field_compute_learned stay
-  }
-  f->lustats = us;
-  return ARTP_OK;
+  // the kind's step: what a new field would hold -- the current sampler layers and their heights over the whole rectangle --
+  // then every slot priced again (a slot whose bits change flags its tile).  The passes run when a word or a slot changed.
+  return field_update_run(
+      f, "artp_field_update_learned", new_mask, mask_on_device, sub, false, true, &f->lustats,
+      [&](unsigned long long* cnt, artp_field_learned_update_stats_t* us, bool* run) -> int {
+        field_adopt_sampler(c, f);
+        hipLaunchKernelGGL(artp::field_heights_kernel, dim3((unsigned)((f->n_cells + 255) / 256)), dim3(256), 0, c->stream,
+                           f->sampler, f->geom, f->rect, f->d_h);
+        HIP_TRY(c, hipGetLastError());
+        double ms[3] = {0.0, 0.0, 0.0};
+        uint64_t chunks = 0;
+        ARTP_TRY(field_learned_table(c, f, true, ms, &chunks));
+        ARTP_TRY(field_weight_counts(f, cnt, 2));
+        us->repriced_slots = artp::field_wtab_slots(f->grid);
+        us->changed_slots = cnt[5];
+        us->weight_tiles = cnt[6];
+        us->rows_ms = ms[0];
+        us->query_ms = ms[1];
+        us->reprice_ms = ms[2];
+        *run = cnt[0] || cnt[5];
+        return ARTP_OK;
+      });
 }
 
 int artp_field_learned_update_stats(artp_field* f, artp_field_learned_update_stats_t* out) {
@@ -1656,7 +1699,6 @@ int artp_field_learned_update_stats(artp_field* f, artp_field_learned_update_sta
 void artp_field_destroy(artp_field* f) {
   if (!f) return;
   (void)hipSetDevice(f->ctx->device);
-  (void)hipStreamSynchronize(f->ctx->stream);
   field_free(f);
 }
 

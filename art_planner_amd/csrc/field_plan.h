@@ -136,9 +136,9 @@ namespace {
 int field_blocked_alloc(artp_field* f) {
   if (f->d_blk) return ARTP_OK;
   artp_ctx* c = f->ctx;
-  const size_t bytes = ((f->n_nodes + 1) / 2) * sizeof(uint32_t);
-  HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&f->d_blk), bytes));
-  HIP_TRY(c, hipMemsetAsync(f->d_blk, 0, bytes, c->stream));
+  const size_t words = (f->n_nodes + 1) / 2 * 2;  // whole 32-bit words
+  HIP_TRY(c, f->mem.alloc(&f->d_blk, words));
+  HIP_TRY(c, hipMemsetAsync(f->d_blk, 0, words * sizeof(uint16_t), c->stream));
   return ARTP_OK;
 }
 
@@ -196,11 +196,11 @@ int field_plan_scratch(artp_field* f, size_t targets, size_t states, FieldPlanBu
     if (targets < f->plan_targets) targets = f->plan_targets;
     if (states < f->plan_states) states = f->plan_states;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (f->d_plan) HIP_TRY(c, hipFree(f->d_plan));
+    f->mem.release(f->d_plan);
     f->d_plan = nullptr;
     f->plan_targets = f->plan_states = 0;
     FieldPlanBuf tmp;
-    HIP_TRY(c, hipMalloc(&f->d_plan, field_plan_layout(nullptr, targets, states, &tmp)));
+    HIP_TRY(c, f->mem.alloc(&f->d_plan, field_plan_layout(nullptr, targets, states, &tmp)));
     f->plan_targets = targets;
     f->plan_states = states;
   }
@@ -267,13 +267,8 @@ int artp_field_unblock(artp_field* f, const int* sub_rect, uint64_t* unblocked) 
   artp_ctx* c = f->ctx;
   std::lock_guard<std::recursive_mutex> lock(c->mu);
   const artp::FieldGrid& G = f->grid;
-  artp::FieldSub sub{0, 0, G.nrows, G.ncols};
-  if (sub_rect) sub = artp::FieldSub{sub_rect[0], sub_rect[1], sub_rect[2], sub_rect[3]};
-  if (sub.nrows < 1 || sub.ncols < 1 || sub.row0 < 0 || sub.col0 < 0 || sub.row0 > G.nrows - sub.nrows ||
-      sub.col0 > G.ncols - sub.ncols) {
-    c->last_error = "artp_field_unblock: sub_rect is empty or not inside the field's rectangle";
-    return ARTP_ERR_INVALID_ARG;
-  }
+  artp::FieldSub sub;
+  ARTP_TRY(field_sub_rect(f, "artp_field_unblock", sub_rect, &sub));
   if (!f->d_blk || !f->n_blocked) return ARTP_OK;
   HIP_TRY(c, hipSetDevice(c->device));
   hipStream_t st = c->stream;
@@ -361,22 +356,11 @@ int artp_field_plan(artp_field* f, const int* targets, size_t n_targets, int max
     statuses[i] = 2;
     costs[i] = INFINITY;
   }
-  struct Events {  // the stream time of a round's descent and of its check
-    hipEvent_t e[3] = {nullptr, nullptr, nullptr};
-    Events() {
-      for (hipEvent_t& x : e)
-        if (hipEventCreate(&x) != hipSuccess) x = nullptr;
-    }
-    ~Events() {
-      for (hipEvent_t x : e)
-        if (x) (void)hipEventDestroy(x);
-    }
-  } events;
-  hipEvent_t* ev = events.e;
+  StreamTimer<3> tm(st);  // the stream time of a round's descent and of its check
   while (!pending.empty() && ps.rounds < (uint64_t)max_rounds) {
     const size_t np = pending.size();
     const auto h0 = std::chrono::steady_clock::now();
-    if (ev[0]) (void)hipEventRecord(ev[0], st);
+    tm.mark(0);
     // 1. the descents; run again with more room when the states did not fit
     unsigned long long tot[2] = {0, 0};
     for (;;) {
@@ -388,7 +372,7 @@ int artp_field_plan(artp_field* f, const int* targets, size_t n_targets, int max
                          (const uint32_t*)f->d_hops, (const int*)B.targets, (const uint32_t*)B.pend, (long long)f->plan_states,
                          B.nodes, B.move_src, B.move_tgt, B.recs, B.tot);
       HIP_TRY(c, hipGetLastError());
-      if (ev[1]) (void)hipEventRecord(ev[1], st);
+      tm.mark(1);
       HIP_TRY(c, hipMemcpyAsync(tot, B.tot, sizeof(tot), hipMemcpyDeviceToHost, st));
       HIP_TRY(c, hipMemcpyAsync(recs.data(), B.recs, n_targets * sizeof(artp::FieldPlanRec), hipMemcpyDeviceToHost, st));
       HIP_TRY(c, hipStreamSynchronize(st));
@@ -423,11 +407,11 @@ int artp_field_plan(artp_field* f, const int* targets, size_t n_targets, int max
                          (const int*)B.nodes, (const int*)(B.nodes + 3), (const uint32_t*)B.move_src, (const uint8_t*)B.valid,
                          n_moves, reinterpret_cast<uint32_t*>(f->d_blk), f->d_acc, f->d_ucnt, (const uint32_t*)B.move_tgt, B.fail);
       HIP_TRY(c, hipGetLastError());
-      if (ev[2]) (void)hipEventRecord(ev[2], st);
+      tm.mark(2);
       HIP_TRY(c, hipMemcpyAsync(&newly, f->d_ucnt + 7, sizeof(newly), hipMemcpyDeviceToHost, st));
       HIP_TRY(c, hipMemcpyAsync(fail.data(), B.fail, n_targets * sizeof(unsigned), hipMemcpyDeviceToHost, st));
     } else {
-      if (ev[2]) (void)hipEventRecord(ev[2], st);
+      tm.mark(2);
       std::fill(fail.begin(), fail.end(), 0u);
     }
     HIP_TRY(c, hipStreamSynchronize(st));
@@ -452,9 +436,8 @@ int artp_field_plan(artp_field* f, const int* targets, size_t n_targets, int max
       }
     }
     HIP_TRY(c, hipStreamSynchronize(st));
-    float dev_ms = 0.f;
-    if (ev[0] && ev[1] && hipEventElapsedTime(&dev_ms, ev[0], ev[1]) == hipSuccess) ps.descent_ms += dev_ms;
-    if (ev[1] && ev[2] && hipEventElapsedTime(&dev_ms, ev[1], ev[2]) == hipSuccess) ps.check_ms += dev_ms;
+    ps.descent_ms += tm.ms(0, 1, true);
+    ps.check_ms += tm.ms(1, 2, true);
     const auto h1 = std::chrono::steady_clock::now();
     ps.round_ms += std::chrono::duration<double, std::milli>(h1 - h0).count();
     pending.swap(next);

@@ -159,50 +159,48 @@ class CostField:
         same bits as a new cost_field on it.  mask as in the constructor, over the field's whole rectangle; rect =
         (row0, col0, nrows, ncols) local to the field: only the words inside it are read (None = all).
         refresh_heights re-reads the sampler layer's heights inside rect.  Returns the update's stats."""
-        mask_ptr, on_device, keep = self._mask_arg(mask, "CostField.update")
-        r = None if rect is None else np.ascontiguousarray(rect, np.int32).reshape(4)
-        self.ctx._chk(self.L.artp_field_update(self.h, mask_ptr, on_device, r.ctypes.data if r is not None else None,
-                                               int(bool(refresh_heights))), "artp_field_update")
-        del keep
-        s = _capi.FieldUpdateStats()
-        self.ctx._chk(self.L.artp_field_update_stats(self.h, C.byref(s)), "artp_field_update_stats")
-        return {n: int(getattr(s, n)) for n, _ in _capi.FieldUpdateStats._fields_}
+        self._update(self.L.artp_field_update, "update", mask, rect, int(bool(refresh_heights)))
+        return self._stats(_capi.FieldUpdateStats, self.L.artp_field_update_stats, "artp_field_update_stats", int)
 
     def update_learned(self, mask=None, rect=None) -> dict:
         """Bring a learned field to the fixed point of the context's current state in place (artp_field_update_learned,
         DESIGN.md section 15): every move priced again by the loaded network on the installed cost map, the mask edited
         as in update() (None: the mask did not change, rect is ignored).  The same bits as a new learned_cost_field with
         the field's own weights, sources and direction.  Returns the update's stats."""
-        mask_ptr, on_device, keep = (None, 0, None) if mask is None else self._mask_arg(mask, "CostField.update_learned")
-        r = None if rect is None or mask is None else np.ascontiguousarray(rect, np.int32).reshape(4)
-        self.ctx._chk(self.L.artp_field_update_learned(self.h, mask_ptr, on_device, r.ctypes.data if r is not None else None),
-                      "artp_field_update_learned")
-        del keep
+        self._update(self.L.artp_field_update_learned, "update_learned", mask, rect)
         return self.learned_update_stats()
 
     def learned_update_stats(self) -> dict:
         """The numbers of the last update_learned that succeeded (zeros before the first)."""
-        s = _capi.FieldLearnedUpdateStats()
-        self.ctx._chk(self.L.artp_field_learned_update_stats(self.h, C.byref(s)), "artp_field_learned_update_stats")
-        return {n: getattr(s, n) for n, _ in _capi.FieldLearnedUpdateStats._fields_}
+        return self._stats(_capi.FieldLearnedUpdateStats, self.L.artp_field_learned_update_stats,
+                           "artp_field_learned_update_stats")
 
     def update_clearance(self, mask, rect=None, refresh_heights=False) -> dict:
         """Bring a clearance-weighted field to the fixed point of an edited mask in place (artp_field_update_clearance,
         DESIGN.md section 18): the clearance map and the weight table computed again around rect, then the passes of
         update().  mask, rect and refresh_heights as in update().  The same bits -- dist, paths, clearance(), edge_costs --
         as a new clearance_cost_field with the field's own parameters on the merged mask.  Returns the update's stats."""
-        mask_ptr, on_device, keep = self._mask_arg(mask, "CostField.update_clearance")
-        r = None if rect is None else np.ascontiguousarray(rect, np.int32).reshape(4)
-        self.ctx._chk(self.L.artp_field_update_clearance(self.h, mask_ptr, on_device, r.ctypes.data if r is not None else None,
-                                                         int(bool(refresh_heights))), "artp_field_update_clearance")
-        del keep
+        self._update(self.L.artp_field_update_clearance, "update_clearance", mask, rect, int(bool(refresh_heights)))
         return self.clearance_update_stats()
 
     def clearance_update_stats(self) -> dict:
         """The numbers of the last update_clearance that succeeded (zeros before the first)."""
-        s = _capi.FieldClearanceUpdateStats()
-        self.ctx._chk(self.L.artp_field_clearance_update_stats(self.h, C.byref(s)), "artp_field_clearance_update_stats")
-        return {n: getattr(s, n) for n, _ in _capi.FieldClearanceUpdateStats._fields_}
+        return self._stats(_capi.FieldClearanceUpdateStats, self.L.artp_field_clearance_update_stats,
+                           "artp_field_clearance_update_stats")
+
+    def _update(self, call, name, mask, rect, *extra):
+        """The mask and rect handling the three updates share; call = the C entry point artp_field_<name>.  mask None
+        (update_learned only): no mask and no rect go down."""
+        mask_ptr, on_device, keep = (None, 0, None) if mask is None else self._mask_arg(mask, "CostField." + name)
+        r = None if rect is None or mask is None else np.ascontiguousarray(rect, np.int32).reshape(4)
+        self.ctx._chk(call(self.h, mask_ptr, on_device, r.ctypes.data if r is not None else None, *extra), "artp_field_" + name)
+        del keep
+
+    def _stats(self, struct, call, name, conv=lambda v: v) -> dict:
+        """One of the library's stats structs of this field as a dict of its members."""
+        s = struct()
+        self.ctx._chk(call(self.h, C.byref(s)), name)
+        return {n: conv(getattr(s, n)) for n, _ in struct._fields_}
 
     def block_moves(self, a, b) -> int:
         """Block the moves a[i] -> b[i] ((n, 3) node triples, travel direction) and repair the field in place
@@ -279,9 +277,7 @@ class CostField:
         return out
 
     def _read_plan_stats(self) -> dict:
-        s = _capi.FieldPlanStats()
-        self.ctx._chk(self.L.artp_field_plan_stats(self.h, C.byref(s)), "artp_field_plan_stats")
-        d = {n: getattr(s, n) for n, _ in _capi.FieldPlanStats._fields_}
+        d = self._stats(_capi.FieldPlanStats, self.L.artp_field_plan_stats, "artp_field_plan_stats")
         n = C.c_size_t(0)
         self.ctx._chk(self.L.artp_field_plan_round_tile_runs(self.h, None, 0, C.byref(n)), "artp_field_plan_round_tile_runs")
         runs = np.zeros(max(n.value, 1), np.uint64)
@@ -308,11 +304,7 @@ class CostField:
 
     def learned_stats(self) -> dict:
         """The weight table of a learned field and the time its steps took (artp_field_learned_stats)."""
-        s = _capi.FieldLearnedStats()
-        self.ctx._chk(self.L.artp_field_learned_stats(self.h, C.byref(s)), "artp_field_learned_stats")
-        return {n: getattr(s, n) for n, _ in _capi.FieldLearnedStats._fields_}
+        return self._stats(_capi.FieldLearnedStats, self.L.artp_field_learned_stats, "artp_field_learned_stats")
 
     def stats(self) -> dict:
-        s = _capi.FieldStats()
-        self.ctx._chk(self.L.artp_field_stats(self.h, C.byref(s)), "artp_field_stats")
-        return {n: int(getattr(s, n)) for n, _ in _capi.FieldStats._fields_}
+        return self._stats(_capi.FieldStats, self.L.artp_field_stats, "artp_field_stats", int)

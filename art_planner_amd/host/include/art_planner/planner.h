@@ -489,19 +489,9 @@ class Planner {
   // refresh_heights re-reads the map's heights inside rect.  Returns dist and refreshes the "cost_to_go" layer.
   std::vector<double> updateCostField(artp_field* kept, const std::vector<uint32_t>& mask,
                                       const std::array<int, 4>* rect = nullptr, bool refresh_heights = false) {
-    std::lock_guard<std::mutex> lock(map_mutex_);
-    if (!map_) throw std::runtime_error("updateCostField: the planner does not have a map set");
-    if (!kept) throw std::runtime_error("updateCostField: no field");
-    const auto g = map_->getGeometry();
-    const size_t cells = static_cast<size_t>(g.rows) * g.cols;
-    artp_field_stats_t st;
-    throwOnError(gpu_->get(), artp_field_stats(kept, &st), "artp_field_stats");
-    if (mask.size() != cells || st.nodes % cells != 0)
-      throw std::runtime_error("updateCostField: the mask or the field does not have rows * cols cells");
-    throwOnError(gpu_->get(),
-                 artp_field_update(kept, mask.data(), 0, rect ? rect->data() : nullptr, refresh_heights ? 1 : 0),
-                 "artp_field_update");
-    return refreshCostToGo(kept, cells, st.nodes);
+    return updateKeptField("updateCostField", "artp_field_update", kept, mask, false, [&] {
+      return artp_field_update(kept, mask.data(), 0, rect ? rect->data() : nullptr, refresh_heights ? 1 : 0);
+    });
   }
 
   // The field a computeClearanceCostField call kept, brought in place to an edited mask (artp_field_update_clearance,
@@ -510,19 +500,9 @@ class Planner {
   // field's own parameters on that mask.  Returns dist and refreshes the "cost_to_go" layer.
   std::vector<double> updateClearanceCostField(artp_field* kept, const std::vector<uint32_t>& mask,
                                                const std::array<int, 4>* rect = nullptr, bool refresh_heights = false) {
-    std::lock_guard<std::mutex> lock(map_mutex_);
-    if (!map_) throw std::runtime_error("updateClearanceCostField: the planner does not have a map set");
-    if (!kept) throw std::runtime_error("updateClearanceCostField: no field");
-    const auto g = map_->getGeometry();
-    const size_t cells = static_cast<size_t>(g.rows) * g.cols;
-    artp_field_stats_t st;
-    throwOnError(gpu_->get(), artp_field_stats(kept, &st), "artp_field_stats");
-    if (mask.size() != cells || st.nodes % cells != 0)
-      throw std::runtime_error("updateClearanceCostField: the mask or the field does not have rows * cols cells");
-    throwOnError(gpu_->get(),
-                 artp_field_update_clearance(kept, mask.data(), 0, rect ? rect->data() : nullptr, refresh_heights ? 1 : 0),
-                 "artp_field_update_clearance");
-    return refreshCostToGo(kept, cells, st.nodes);
+    return updateKeptField("updateClearanceCostField", "artp_field_update_clearance", kept, mask, false, [&] {
+      return artp_field_update_clearance(kept, mask.data(), 0, rect ? rect->data() : nullptr, refresh_heights ? 1 : 0);
+    });
   }
 
   // The field a computeLearnedCostField call kept, brought in place to the device's current state
@@ -532,19 +512,9 @@ class Planner {
   // "cost_to_go" layer.
   std::vector<double> updateLearnedCostField(artp_field* kept, const std::vector<uint32_t>& mask,
                                              const std::array<int, 4>* rect = nullptr) {
-    std::lock_guard<std::mutex> lock(map_mutex_);
-    if (!map_) throw std::runtime_error("updateLearnedCostField: the planner does not have a map set");
-    if (!kept) throw std::runtime_error("updateLearnedCostField: no field");
-    const auto g = map_->getGeometry();
-    const size_t cells = static_cast<size_t>(g.rows) * g.cols;
-    artp_field_stats_t st;
-    throwOnError(gpu_->get(), artp_field_stats(kept, &st), "artp_field_stats");
-    if ((!mask.empty() && mask.size() != cells) || st.nodes % cells != 0)
-      throw std::runtime_error("updateLearnedCostField: the mask or the field does not have rows * cols cells");
-    throwOnError(gpu_->get(),
-                 artp_field_update_learned(kept, mask.empty() ? nullptr : mask.data(), 0, rect ? rect->data() : nullptr),
-                 "artp_field_update_learned");
-    return refreshCostToGo(kept, cells, st.nodes);
+    return updateKeptField("updateLearnedCostField", "artp_field_update_learned", kept, mask, true, [&] {
+      return artp_field_update_learned(kept, mask.empty() ? nullptr : mask.data(), 0, rect ? rect->data() : nullptr);
+    });
   }
 
   // Single moves taken out of a kept field (artp_field_block_moves, include/artp_c.h): from[i] -> to[i] in travel
@@ -825,6 +795,24 @@ class Planner {
 #endif
 
  private:
+  // The three update calls around their library call: `who` = the public method in the exception texts, `what` = the
+  // library call in throwOnError's; an empty mask passes only where empty_ok (updateLearnedCostField: unchanged).
+  template <class Call>
+  std::vector<double> updateKeptField(const char* who, const char* what, artp_field* kept, const std::vector<uint32_t>& mask,
+                                      bool empty_ok, Call&& call) {
+    std::lock_guard<std::mutex> lock(map_mutex_);
+    if (!map_) throw std::runtime_error(std::string(who) + ": the planner does not have a map set");
+    if (!kept) throw std::runtime_error(std::string(who) + ": no field");
+    const auto g = map_->getGeometry();
+    const size_t cells = static_cast<size_t>(g.rows) * g.cols;
+    artp_field_stats_t st;
+    throwOnError(gpu_->get(), artp_field_stats(kept, &st), "artp_field_stats");
+    if ((mask.size() != cells && !(empty_ok && mask.empty())) || st.nodes % cells != 0)
+      throw std::runtime_error(std::string(who) + ": the mask or the field does not have rows * cols cells");
+    throwOnError(gpu_->get(), call(), what);
+    return refreshCostToGo(kept, cells, st.nodes);
+  }
+
   static std::shared_ptr<BatchTree> makeTree(const ParamsConstPtr& params, const GpuContextPtr& gpu) {
     const int variant = BatchTree::variantOf(params->planner.name);
     return variant < 0 ? nullptr : std::make_shared<BatchTree>(params, gpu, variant);

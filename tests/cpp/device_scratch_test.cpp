@@ -61,6 +61,58 @@ static int log_reserve(FakeCtx* c, Log* t, size_t cap) {
   return ARTP_OK;
 }
 
+// A field in small (csrc/field.h artp_field): plain typed pointers beside the owner of what they point to.
+struct SmallField {
+  FakeCtx* ctx = nullptr;
+  double* dist = nullptr;     // allocated by the build, kept to the end
+  float* chunk = nullptr;     // the build's scratch, given back before the build ends
+  unsigned* wacc = nullptr;   // lazy: the first update of some kinds allocates it, many fields never do
+  int* nodes = nullptr;       // grows with the largest request
+  size_t nodes_cap = 0;
+  DeviceScratch mem;
+};
+
+// field_lazy's body
+template <class T>
+static int small_lazy(SmallField* f, T** p, size_t count) {
+  if (!*p) HIP_TRY(f->ctx, f->mem.alloc(p, count));
+  return ARTP_OK;
+}
+
+// field_ensure_scratch's body: the old block released ahead of the new alloc
+static int small_ensure(SmallField* f, size_t ints) {
+  if (f->nodes_cap >= ints) return ARTP_OK;
+  f->mem.release(f->nodes);
+  f->nodes = nullptr;
+  f->nodes_cap = 0;
+  HIP_TRY(f->ctx, f->mem.alloc(&f->nodes, ints));
+  f->nodes_cap = ints;
+  return ARTP_OK;
+}
+
+// field_create's shape: build, and on a failure delete what was built so far; *out only on success
+static int small_create(FakeCtx* c, SmallField** out) {
+  *out = nullptr;
+  SmallField* f = new SmallField;
+  f->ctx = c;
+  const auto build = [&]() -> int {
+    HIP_TRY(c, f->mem.alloc(&f->dist, 100));
+    ARTP_TRY(small_ensure(f, 6));
+    ARTP_TRY(small_lazy(f, &f->chunk, 900));
+    f->chunk[899] = 1.0f;
+    f->mem.release(f->chunk);  // the scratch goes back here, not with the field
+    f->chunk = nullptr;
+    return ARTP_OK;
+  };
+  const int rc = build();
+  if (rc) {
+    delete f;
+    return rc;
+  }
+  *out = f;
+  return ARTP_OK;
+}
+
 static int try_passes_code(int rc) {
   ARTP_TRY(rc);
   return ARTP_OK;
@@ -165,6 +217,49 @@ int main() {
     DeviceScratch S;
     int* p = reinterpret_cast<int*>(&ctx);
     CHECK(S.alloc(&p, 4) == hipErrorOutOfMemory && p == nullptr);
+    CHECK(hip_stub::live == 0);
+  }
+
+  // a field in small: every failure position of the build frees what the build had, and nothing twice
+  for (int n = 1; n <= 3; ++n) {
+    SmallField* f = reinterpret_cast<SmallField*>(&ctx);
+    hip_stub::reset(n);
+    CHECK(small_create(&ctx, &f) == ARTP_ERR_HIP && f == nullptr);
+    CHECK(hip_stub::live == 0 && hip_stub::mallocs == n && hip_stub::frees == n - 1);
+  }
+  // ... a field that is built and destroyed: the lazy buffer never allocated, the build's scratch long gone
+  {
+    SmallField* f = nullptr;
+    hip_stub::reset();
+    CHECK(small_create(&ctx, &f) == ARTP_OK && f != nullptr);
+    CHECK(hip_stub::live == 2 && hip_stub::frees == 1 && f->chunk == nullptr && f->wacc == nullptr);
+    delete f;
+    CHECK(hip_stub::live == 0 && hip_stub::mallocs == 3 && hip_stub::frees == 3);
+  }
+  // ... and one that lives: the lazy buffer allocated once, the scratch back for good, two regrows, a failed third
+  {
+    SmallField* f = nullptr;
+    hip_stub::reset();
+    CHECK(small_create(&ctx, &f) == ARTP_OK);
+    CHECK(small_lazy(f, &f->wacc, 9) == ARTP_OK && small_lazy(f, &f->wacc, 9) == ARTP_OK);
+    CHECK(hip_stub::mallocs == 4 && hip_stub::live == 3);
+    f->wacc[8] = 1u;
+    CHECK(small_lazy(f, &f->chunk, 900) == ARTP_OK && small_lazy(f, &f->chunk, 900) == ARTP_OK);  // kept from here on
+    f->chunk[899] = 2.0f;
+    int* const first = f->nodes;
+    CHECK(small_ensure(f, 4) == ARTP_OK && f->nodes == first && f->nodes_cap == 6);  // fits: nothing happens
+    CHECK(small_ensure(f, 64) == ARTP_OK && f->nodes_cap == 64);
+    f->nodes[63] = 1;
+    CHECK(small_ensure(f, 640) == ARTP_OK && f->nodes_cap == 640);
+    f->nodes[639] = 1;
+    CHECK(hip_stub::mallocs == 7 && hip_stub::frees == 3 && hip_stub::live == 4);
+    hip_stub::reset(1);
+    ctx.last_error.clear();
+    CHECK(small_ensure(f, 6400) == ARTP_ERR_HIP && f->nodes == nullptr && f->nodes_cap == 0);  // the old block is gone,
+    CHECK(ctx.last_error == "f->mem.alloc(&f->nodes, ints): out of memory");                   // the field says so
+    CHECK(hip_stub::live == 3);
+    f->dist[99] = 1.0;  // the others are untouched
+    delete f;
     CHECK(hip_stub::live == 0);
   }
 
