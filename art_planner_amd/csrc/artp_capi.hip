@@ -879,9 +879,25 @@ int artp_persistent_latency_stats(artp_ctx* c, uint64_t out[2]) {
   return ARTP_OK;
 }
 
+// Box sizes reach launch geometry and LDS sizes through (int)ceil(diag / spacing) (size_scratch, partner_radius), the
+// offsets every box pose, the limits the sampler: nothing non-finite, no empty box, no negative limit gets that far.
+static bool params_usable(const artp_params& p) {
+  const double sizes[6] = {p.torso_length, p.torso_width, p.torso_height, p.reach_x, p.reach_y, p.reach_z};
+  const double offsets[6] = {p.torso_off_x, p.torso_off_y, p.torso_off_z, p.feet_off_x, p.feet_off_y, p.feet_off_z};
+  const double limits[2] = {p.max_pitch_pert, p.max_roll_pert};
+  for (double v : sizes)
+    if (!std::isfinite(v) || v <= 0.0) return false;
+  for (double v : offsets)
+    if (!std::isfinite(v)) return false;
+  for (double v : limits)
+    if (!std::isfinite(v) || v < 0.0) return false;
+  return true;
+}
+
 int artp_create(int device, const artp_params* params, artp_ctx** out) {
   if (!params || !out) return ARTP_ERR_INVALID_ARG;
   *out = nullptr;
+  if (!params_usable(*params)) return ARTP_ERR_INVALID_ARG;
   int count = 0;
   if (hipGetDeviceCount(&count) != hipSuccess || count <= 0 || device < 0 || device >= count)
     return ARTP_ERR_NO_DEVICE;

@@ -68,7 +68,10 @@ const char* artp_last_error(const artp_ctx* ctx);
 const char* artp_device_arch(const artp_ctx* ctx);
 
 /* Planner / StateValidityChecker construction (art_planner/src/planner.cpp:75-131,
- * validity_checker.cpp:9-15).  Fails with ARTP_ERR_NO_DEVICE when there is no GPU. */
+ * validity_checker.cpp:9-15).  ARTP_ERR_INVALID_ARG, with *out = NULL and before any device is asked for: a torso or
+ * reach size that is not finite or not positive, an offset that is not finite, a perturbation limit that is not finite
+ * or negative (the sizes become window tiles and LDS sizes at the first upload).  Then ARTP_ERR_NO_DEVICE when there is
+ * no GPU. */
 int artp_create(int device, const artp_params* params, artp_ctx** out);
 void artp_destroy(artp_ctx* ctx);
 /* Run the context's work on a caller-provided hipStream_t (NULL = HIP's legacy default stream).

@@ -2,6 +2,7 @@
 of their definition, every mask bit against the CPU oracle and Context.validate_states on the device's own poses, rectangles,
 chunking, the _dev form, argument checks and the incremental halo rule."""
 import ctypes as C
+import math
 
 import numpy as np
 import pytest
@@ -58,20 +59,54 @@ def assert_poses(gm, dev, n_yaw, rect=None):
     assert np.isnan(dev[~fin][..., 2:]).all()
 
 
-def check_every_label(ctx, gm, n_yaw, robot=ROBOT):
-    """Every bit of the whole map's mask == the oracle's and validate_states' label of the device's own pose."""
-    mask = ctx.reachability_map(n_yaw)
-    poses = ctx.reachability_poses(n_yaw)
-    assert mask.shape == (gm.rows, gm.cols) and mask.dtype == np.uint32
-    assert_poses(gm, poses, n_yaw)
+def check_every_label(ctx, gm, n_yaw, robot=ROBOT, rect=None):
+    """Every bit of the mask of the whole map (or of rect = (row0, col0, nrows, ncols)) == the oracle's and
+    validate_states' label of the device's own pose.  robot: a preset's name or the oracle's Robot of the context."""
+    rob = robot if isinstance(robot, O.Robot) else O.robot(robot)
+    mask = ctx.reachability_map(n_yaw, rect)
+    poses = ctx.reachability_poses(n_yaw, rect)
+    assert mask.shape == ((gm.rows, gm.cols) if rect is None else tuple(rect[2:])) and mask.dtype == np.uint32
+    assert_poses(gm, poses, n_yaw, rect)
     assert (mask >> np.uint32(n_yaw) == 0).all()
-    fin = cells_finite(gm)
+    fin = cells_finite(gm, rect)
     assert (mask[~fin] == 0).all()
     states = poses[fin].reshape(-1, 7)
     bits = mask_bits(mask, n_yaw)[fin].reshape(-1)
-    assert np.array_equal(bits, common.oracle_states_valid_threaded(gm, O.robot(robot), states))
+    assert np.array_equal(bits, common.oracle_states_valid_threaded(gm, rob, states))
     assert np.array_equal(bits, ctx.validate_states(states))
     return mask
+
+
+def halo_cells(rob, res):
+    """artp_reachability_halo's definition: a box of a lattice pose lies within |offset| + its 3-D half-diagonal of the
+    cell centre whatever the attitude (the feet's offset in the plane, the torso's from the feet plane); the larger of the
+    two in cells, rounded up, plus the window margin of 4 samples."""
+    toz = rob.torso_off_z - rob.feet_off_z
+    torso = math.sqrt(rob.torso_off_x ** 2 + rob.torso_off_y ** 2 + toz ** 2) + 0.5 * math.sqrt(
+        rob.torso_length ** 2 + rob.torso_width ** 2 + rob.torso_height ** 2)
+    feet = math.sqrt(rob.feet_off_x ** 2 + rob.feet_off_y ** 2) + 0.5 * math.sqrt(
+        rob.reach_x ** 2 + rob.reach_y ** 2 + rob.reach_z ** 2)
+    return int(math.ceil(max(torso, feet) / res)) + 4
+
+
+def check_halo_grown_recompute(ctx, gm, n_yaw, block, full0=None):
+    """Raise block = (row0, col0, nrows, ncols) of both validity layers by 1 m, recompute the block grown by the halo
+    (clipped to the map), paste it into the mask from before the edit: equal to a full recompute.  Returns (mask before,
+    mask after, halo)."""
+    full0 = ctx.reachability_map(n_yaw) if full0 is None else full0
+    halo = ctx.reachability_halo()
+    r0, c0, nr, nc = block
+    sl = (slice(r0, r0 + nr), slice(c0, c0 + nc))
+    # an obstacle block written to both validity layers; the sampler layers (heights, normals: the poses) stay
+    ctx.update_layer_rects(0, [gm["elevation"][sl] + np.float32(1.0)], [(r0, c0)])
+    ctx.update_layer_rects(1, [gm["elevation_masked"][sl] + np.float32(1.0)], [(r0, c0)])
+    g0, h0 = max(0, r0 - halo), max(0, c0 - halo)
+    g1, h1 = min(gm.rows, r0 + nr + halo), min(gm.cols, c0 + nc + halo)
+    pasted = full0.copy()
+    pasted[g0:g1, h0:h1] = ctx.reachability_map(n_yaw, (g0, h0, g1 - g0, h1 - h0))
+    full1 = ctx.reachability_map(n_yaw)
+    assert np.array_equal(pasted, full1)
+    return full0, full1, halo
 
 
 # ---- maps -------------------------------------------------------------------------------------------------------
@@ -262,30 +297,14 @@ def test_bad_arguments_raise_and_leave_the_context_usable(ctx):
 def test_halo_grown_recompute_equals_a_full_recompute(ctx):
     gm = c2_map(ctx)
     n_yaw = 8
-    full0 = ctx.reachability_map(n_yaw)
-    halo = ctx.reachability_halo()
-    assert halo > 4
     r0, c0, nr, nc = 180, 150, 20, 25
-    block = (slice(r0, r0 + nr), slice(c0, c0 + nc))
-    # an obstacle block written to both validity layers; the sampler layers (heights, normals: the poses) stay
-    ctx.update_layer_rects(0, [gm["elevation"][block] + np.float32(1.0)], [(r0, c0)])
-    ctx.update_layer_rects(1, [gm["elevation_masked"][block] + np.float32(1.0)], [(r0, c0)])
-    g0, h0 = max(0, r0 - halo), max(0, c0 - halo)
-    g1, h1 = min(gm.rows, r0 + nr + halo), min(gm.cols, c0 + nc + halo)
-    pasted = full0.copy()
-    pasted[g0:g1, h0:h1] = ctx.reachability_map(n_yaw, (g0, h0, g1 - g0, h1 - h0))
-    full1 = ctx.reachability_map(n_yaw)
-    assert np.array_equal(pasted, full1)
+    full0, full1, halo = check_halo_grown_recompute(ctx, gm, n_yaw, (r0, c0, nr, nc))
+    assert halo > 4
+    assert halo == halo_cells(O.robot(ROBOT), gm.res)
     written = np.zeros(full0.shape, bool)
-    written[block] = True
+    written[r0:r0 + nr, c0:c0 + nc] = True
     changed = full1 != full0
     assert (changed & ~written).any()   # the halo is not 0: cells next to the block change too
     # the same near a corner: the grown rectangle clipped to the map
-    r0, c0 = 3, 390
-    block = (slice(r0, r0 + 6), slice(c0, c0 + 10))
-    ctx.update_layer_rects(0, [gm["elevation"][block] + np.float32(1.0)], [(r0, c0)])
-    ctx.update_layer_rects(1, [gm["elevation_masked"][block] + np.float32(1.0)], [(r0, c0)])
-    g0, h0, g1, h1 = 0, max(0, c0 - halo), min(gm.rows, r0 + 6 + halo), gm.cols
-    pasted = full1.copy()
-    pasted[g0:g1, h0:h1] = ctx.reachability_map(n_yaw, (g0, h0, g1 - g0, h1 - h0))
-    assert np.array_equal(pasted, ctx.reachability_map(n_yaw))
+    assert halo > 3 and 390 + 10 + halo >= gm.cols
+    check_halo_grown_recompute(ctx, gm, n_yaw, (3, 390, 6, 10), full0=full1)
