@@ -28,7 +28,7 @@ SYMBOLS = [
     "artp_field_clearance_params_defaults", "artp_field_compute_clearance", "artp_field_clearance",
     "artp_field_update_clearance", "artp_field_clearance_update_stats",
     "artp_check_motions_last_valid", "artp_check_motions_last_valid_dev",
-    "artp_set_z_bounds", "artp_set_few_edges", "artp_set_edge_passes", "artp_cost_set_fc_path", "artp_check_motions", "artp_check_motions_dev", "artp_check_edges_interp",
+    "artp_set_z_bounds", "artp_set_few_edges", "artp_set_tail_mode", "artp_last_tail", "artp_set_edge_passes", "artp_cost_set_fc_path", "artp_check_motions", "artp_check_motions_dev", "artp_check_edges_interp",
     "artp_check_edges_interp_dev", "artp_compact_valid_dev", "artp_compact_valid_indices_dev", "artp_sample_states_at_dev",
     "artp_pack_edge_results_dev", "artp_cost_update_map_dev", "artp_pack_valid_bits_dev", "artp_indices_from_bits_dev",
     "artp_materialise_from_bits_dev",
@@ -273,6 +273,8 @@ def _load_path(LIB_PATH):
     L.artp_map_version.restype = C.c_uint64
     L.artp_set_z_bounds.argtypes = [vp, dbl, dbl]
     L.artp_set_few_edges.argtypes = [vp, i32]
+    L.artp_set_tail_mode.argtypes = [vp, i32]
+    L.artp_last_tail.argtypes = [vp]
     L.artp_set_persistent_latency.argtypes = [vp, i32]
     L.artp_persistent_latency_stats.argtypes = [vp, C.POINTER(u64 * 2)]
     L.artp_set_edge_passes.argtypes = [vp, i32, i32]

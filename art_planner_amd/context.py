@@ -146,6 +146,15 @@ class Context:
         """<= 64 edges per host call: the one-launch latency kernel (default) or the batch pipeline (enabled=False)."""
         self._chk(self.L.artp_set_few_edges(self.h, 1 if enabled else 0), "artp_set_few_edges")
 
+    def set_tail_mode(self, mode=0):
+        """Tail of the batch validity step: 0 = chosen per call from the previous call's leftover count (default), 1 = always
+        the five-launch full tail, 2 = always the one-launch rare tail.  Same labels either way (artp_set_tail_mode)."""
+        self._chk(self.L.artp_set_tail_mode(self.h, int(mode)), "artp_set_tail_mode")
+
+    def last_tail(self):
+        """The tail the last validity pass on the current lane took: 1 full, 2 rare, 0 = none yet."""
+        return int(self.L.artp_last_tail(self.h))
+
     def set_edge_passes(self, two_pass=True, coarse_stride=0):
         self._chk(self.L.artp_set_edge_passes(self.h, 1 if two_pass else 0, coarse_stride), "artp_set_edge_passes")
 
@@ -402,7 +411,7 @@ class Context:
         self._chk(self.L.artp_debug_pipeline_counters(self.h, C.byref(out)), "artp_debug_pipeline_counters")
         return {"torso_queued": out[0], "feet_queued": out[4], "exact_grouping": out[1], "feet_plane_stage": out[5],
                 "feet_partner_pass": out[6],
-                "torso_staged_pass": out[2]}
+                "torso_staged_pass": out[2], "feet_lane_scan": out[7]}
 
     def partner_table(self, slot, shape):
         """(flags[nD, nW] uint8 in ODE sample layout, radius) of a layer's partner table; (None, 0) if

@@ -33,6 +33,12 @@ using namespace artp;
 #define FEW_EDGE_STATUS (FEW_EDGE_AUX + ARTP_FEW_EDGES * sizeof(uint32_t))
 #define FEW_EDGE_BLOCK_BYTES (FEW_EDGE_STATUS + ARTP_FEW_EDGES)
 #define ARTP_MAX_LANES 4
+// Kinds of validity call that keep a tail history of their own (launch_validate_pipeline): a checkMotion batch runs two
+// validity passes of very different size in turn, and each is like ITS predecessor, not like the call in front of it.
+#define ARTP_TAIL_STATES 0   // state batches (validate, fused sample + validate, reachability chunks)
+#define ARTP_TAIL_EDGES_1 1  // edge batches: the coarse pass, or the only one
+#define ARTP_TAIL_EDGES_2 2  // edge batches: the second pass
+#define ARTP_TAIL_KINDS 3
 
 struct artp_ctx {
   int device = 0;
@@ -154,6 +160,15 @@ struct artp_ctx {
   };
   lane_state lanes[ARTP_MAX_LANES];
   int cur_lane = 0;
+  // The tail of the validity step (launch_validate_pipeline).  tail_hint: mapped pinned host memory, one word per lane
+  // and kind of call (ARTP_TAIL_*), each on a 64-byte line of its own, written by the last kernel of such a call on that
+  // lane (store_tail_hint, pipeline.h) and read by the host, unsynchronised, when it queues the next one of that kind.
+  int tail_mode = 0;                        // artp_set_tail_mode: 0 auto, 1 always the full tail, 2 always the rare tail
+  volatile unsigned* tail_hint = nullptr;   // host view, ARTP_MAX_LANES x ARTP_TAIL_KINDS x 16 words
+  unsigned* tail_hint_dev = nullptr;        // device view
+  uint64_t tail_map_version[ARTP_MAX_LANES][ARTP_TAIL_KINDS] = {};  // map_version + 1 the hint belongs to (0 = none yet)
+  uint32_t tail_tag[ARTP_MAX_LANES][ARTP_TAIL_KINDS] = {};          // changes whenever tail_map_version does
+  int tail_last[ARTP_MAX_LANES] = {0, 0, 0, 0};       // artp_last_tail: 1 full, 2 rare, 0 = no call yet
   // motion cost (R8/R9)
   bool have_weights = false;
   int cost_net = 0;                    // blob version of the loaded network: 1 light (network_light.py), 2 full width (network.py)
@@ -397,6 +412,7 @@ int set_kernel_lds(artp_ctx* c) {
   ARTP_OPT_IN(c, check_boxes_kernel<1>, lds_full(c));
   ARTP_OPT_IN(c, validate_states_kernel<1>, lds_full(c));
   ARTP_OPT_IN(c, plane_stage_kernel<1>, lds_full(c));
+  ARTP_OPT_IN(c, rare_boxes_kernel, lds_full(c));
   ARTP_OPT_IN(c, validate_few_kernel, lds_few(c));
   ARTP_OPT_IN(c, check_motions_few_kernel, lds_few(c));
   ARTP_OPT_IN(c, validate_service_kernel, lds_few(c));
@@ -626,7 +642,8 @@ int ensure_recs(artp_ctx* c, size_t n) { return ensure_tmp(c, 7, n * sizeof(Pose
 
 // classify -> resolve -> plane stage on the context's stream (all asynchronous).  recs_ready: the PoseRecs of
 // the batch are already in tmp[7] (the fused sampler wrote them); otherwise pose_rec_kernel makes them from se3.
-int launch_validate_pipeline(artp_ctx* c, const double* se3, size_t n, uint8_t* valid, bool recs_ready = false) {
+int launch_validate_pipeline(artp_ctx* c, const double* se3, size_t n, uint8_t* valid, bool recs_ready = false,
+                             int tail_kind = ARTP_TAIL_STATES) {
   if (n >= (1ull << 32)) {
     c->last_error = "batch too large (state index is 32 bit)";
     return ARTP_ERR_INVALID_ARG;
@@ -673,8 +690,30 @@ int launch_validate_pipeline(artp_ctx* c, const double* se3, size_t n, uint8_t* 
 #endif
     hipLaunchKernelGGL(feet_stream_kernel<ARTP_STREAM_WAVES>, dim3(grid_sub(c, ARTP_FEET_WAVES_PER_SIMD)), dim3(64 * ARTP_STREAM_WAVES), 0,
                        c->stream, c->field[1], c->robot, q, valid);
-  hipLaunchKernelGGL(feet_lane_kernel, dim3((unsigned)c->n_cus * 8), dim3(ARTP_LANE_THREADS), 0, c->stream,
-                     c->field[1], c->robot, q, valid);
+  // The tail: five launches that get through any number of leftover boxes, or one that gets through a few (pipeline.h,
+  // rare_boxes_kernel).  Either is right for any counts, so the choice is a speed hint, taken from the lane's previous
+  // call of the same kind: consecutive batches on one map leave about as many boxes behind.  The first call of a kind on
+  // a lane, and the first after anything changed the map or its tables, has no such history and takes the full tail.
+  const int lane_id = c->cur_lane;
+  const uint64_t map_v = c->map_version.load(std::memory_order_acquire) + 1;
+  const bool fresh = c->tail_map_version[lane_id][tail_kind] != map_v;
+  if (fresh) {
+    c->tail_map_version[lane_id][tail_kind] = map_v;
+    ++c->tail_tag[lane_id][tail_kind];
+  }
+  const unsigned hint_tag = c->tail_tag[lane_id][tail_kind] & 0xffu;
+  const size_t hint_at = 16 * (size_t)(lane_id * ARTP_TAIL_KINDS + tail_kind);
+  unsigned* hint_dev = c->tail_hint_dev + hint_at;
+  const unsigned rare_waves = (unsigned)grid_full(c, 0);  // one wavefront per workgroup
+  bool rare = c->tail_mode == 2;
+  if (c->tail_mode == 0 && !fresh) {
+    const unsigned word = c->tail_hint[hint_at];  // whatever is there now: no wait
+    rare = (word & 0xffu) == hint_tag && (word >> 8) <= rare_waves;
+  }
+  c->tail_last[lane_id] = rare ? 2 : 1;
+  if (!rare)
+    hipLaunchKernelGGL(feet_lane_kernel, dim3((unsigned)c->n_cus * 8), dim3(ARTP_LANE_THREADS), 0, c->stream,
+                       c->field[1], c->robot, q, valid);
   {
     // streaming pass: no LDS at all; the staged pass behind it takes the window tile and the list
     const ScratchCaps caps_stream{0, 0, 0, 0};
@@ -682,6 +721,12 @@ int launch_validate_pipeline(artp_ctx* c, const double* se3, size_t n, uint8_t* 
     hipLaunchKernelGGL((resolve_boxes_kernel<ARTP_WAVES_PER_BLOCK, 64, 0>), dim3(grid_sub(c, ARTP_TORSO_WGS_PER_CU)),
                        dim3(64 * ARTP_WAVES_PER_BLOCK), lds_stream, c->stream, c->field[0], c->robot, q, valid,
                        caps_stream, c->d_error, c->tables[0].valid ? c->tables[0].mm : (const float2*)nullptr);
+  }
+  if (rare) {
+    hipLaunchKernelGGL(rare_boxes_kernel, dim3(rare_waves), dim3(64), lds_full(c), c->stream, c->field[0], c->field[1],
+                       c->robot, q, valid, c->caps_full, c->d_error, hint_dev, hint_tag);
+    HIP_TRY(c, hipGetLastError());
+    return ARTP_OK;
   }
   hipLaunchKernelGGL((resolve_boxes_kernel<ARTP_WAVES_PER_BLOCK, 64, 3>), dim3(grid_scan(c, lds_scan(c))),
                      dim3(64 * ARTP_WAVES_PER_BLOCK), lds_scan(c), c->stream, c->field[0], c->robot, q, valid,
@@ -694,7 +739,7 @@ int launch_validate_pipeline(artp_ctx* c, const double* se3, size_t n, uint8_t* 
                      dim3(64 * ARTP_WAVES_PER_BLOCK), lds_feet_wave(c), c->stream, c->field[1], c->robot, q, valid,
                      c->caps_feet_wave, c->d_error);
   hipLaunchKernelGGL(plane_stage_kernel<1>, dim3(grid_full(c, 0)), dim3(64), lds_full(c), c->stream,
-                     c->field[0], c->field[1], c->robot, q, valid, c->caps_full, c->d_error);
+                     c->field[0], c->field[1], c->robot, q, valid, c->caps_full, c->d_error, hint_dev, hint_tag);
   HIP_TRY(c, hipGetLastError());
   return ARTP_OK;
 }
@@ -962,6 +1007,20 @@ int artp_create(int device, const artp_params* params, artp_ctx** out) {
       c->pin_edges = static_cast<char*>(pe);
       c->pin_edges_dev = static_cast<char*>(ped);
     }
+    {
+      void *ph = nullptr, *phd = nullptr;
+      if (hipHostMalloc(&ph, ARTP_MAX_LANES * ARTP_TAIL_KINDS * 16 * sizeof(unsigned), hipHostMallocMapped) != hipSuccess ||
+          hipHostGetDevicePointer(&phd, ph, 0) != hipSuccess) {
+        if (ph) (void)hipHostFree(ph);
+        (void)hipHostFree(ps);
+        (void)hipHostFree(pl);
+        artp_destroy(c);
+        return ARTP_ERR_HIP;
+      }
+      std::memset(ph, 0xff, ARTP_MAX_LANES * ARTP_TAIL_KINDS * 16 * sizeof(unsigned));  // no call has left a count yet
+      c->tail_hint = static_cast<volatile unsigned*>(ph);
+      c->tail_hint_dev = static_cast<unsigned*>(phd);
+    }
     c->pin_states = static_cast<double*>(ps);
     c->pin_labels = static_cast<volatile uint8_t*>(pl);
     c->pin_states_dev = static_cast<double*>(psd);
@@ -1045,6 +1104,7 @@ void artp_destroy(artp_ctx* c) {
   if (c->pin_edges) (void)hipHostFree(c->pin_edges);
   if (c->pin_edges_in) (void)hipHostFree(c->pin_edges_in);
   if (c->d_few_sync) (void)hipFree(c->d_few_sync);
+  if (c->tail_hint) (void)hipHostFree(const_cast<unsigned*>(c->tail_hint));
   if (c->pin_states) (void)hipHostFree(c->pin_states);
   if (c->pin_labels) (void)hipHostFree(const_cast<uint8_t*>(c->pin_labels));
   delete c;  // d_error / d_count of every lane went with the lanes above
@@ -1983,7 +2043,7 @@ static int run_edges_dev(artp_ctx* c, int mode, const double* s1, const double* 
                          offs, (const uint32_t*)aux, (const SlerpEdge*)d_slerp, static_cast<PoseRec*>(c->tmp[7]), edge_of,
                          pass, (uint32_t)c->edge_coarse_stride);
       HIP_TRY(c, hipGetLastError());
-      r = launch_validate_pipeline(c, nullptr, tot, ex_valid, true);
+      r = launch_validate_pipeline(c, nullptr, tot, ex_valid, true, pass == 2 ? ARTP_TAIL_EDGES_2 : ARTP_TAIL_EDGES_1);
       if (r) return r;
       hipLaunchKernelGGL(reduce_edges_kernel, dim3((unsigned)pb), dim3(256), 0, c->stream, (const uint8_t*)ex_valid,
                          (const uint32_t*)edge_of, offs, n, valid);
@@ -2016,7 +2076,7 @@ static int run_edges_dev(artp_ctx* c, int mode, const double* s1, const double* 
                        (const uint32_t*)offsets, (const uint32_t*)aux, (const SlerpEdge*)d_slerp,
                        static_cast<PoseRec*>(c->tmp[7]), edge_of);
     HIP_TRY(c, hipGetLastError());
-    rc = launch_validate_pipeline(c, nullptr, total, ex_valid, true);
+    rc = launch_validate_pipeline(c, nullptr, total, ex_valid, true, ARTP_TAIL_EDGES_1);
     if (rc) return rc;
     hipLaunchKernelGGL(reduce_edges_kernel, dim3((unsigned)eb), dim3(256), 0, c->stream,
                        (const uint8_t*)ex_valid, (const uint32_t*)edge_of, (const uint32_t*)offsets, n, valid);
@@ -2395,6 +2455,17 @@ int artp_set_few_edges(artp_ctx* c, int enabled) {
   c->few_edges = enabled != 0;
   return ARTP_OK;
 }
+int artp_set_tail_mode(artp_ctx* c, int mode) {
+  if (!c || mode < 0 || mode > 2) return ARTP_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> lock(c->mu);
+  c->tail_mode = mode;
+  return ARTP_OK;
+}
+int artp_last_tail(artp_ctx* c) {
+  if (!c) return -1;
+  std::lock_guard<std::recursive_mutex> lock(c->mu);
+  return c->tail_last[c->cur_lane];
+}
 int artp_check_motions_dev(artp_ctx* c, const double* s1, const double* s2, size_t n, uint8_t* valid) {
   return run_edges_dev(c, 0, s1, s2, n, valid, nullptr);
 }
@@ -2434,6 +2505,7 @@ int artp_debug_pipeline_counters(artp_ctx* c, uint64_t out[8]) {
   HIP_TRY(c, hipMemcpyAsync(raw, c->tmp[5], sizeof(raw), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   for (int k = 0; k < 8; ++k) out[k] = raw[k];
+  out[1] += raw[3];  // boxes through the exact grouping: queue 2 (full tail) + those rare_boxes_kernel grouped itself
   out[0] = out[4] = out[2] = out[7] = 0;  // the torso / foot queues and the two fallback queues: sums over the sub-queues
   for (int s = 0; s < ARTP_NSUB; ++s) {
     out[0] += raw[16 + (size_t)s * 16];

@@ -451,7 +451,8 @@ struct PipelineQueues {
   unsigned* q4;                  // foot boxes whose exits the tables could not evaluate (lane-scan path)
   unsigned* q5;                  // foot boxes whose corner candidates may have partners (list pass)
   unsigned* q6;                  // torso boxes the streaming pass cannot finish (staged pass)
-  unsigned long long* counters;  // [1] q2, [5] q3, [6] q5 counts (queues 4 and 6 are segmented: sub_fwd)
+  unsigned long long* counters;  // [1] q2, [5] q3, [6] q5 counts (queues 4 and 6 are segmented: sub_fwd); [3] no queue's:
+                                 // the boxes rare_boxes_kernel took through the exact grouping (a statistic)
   unsigned long long feet_base;  // = ARTP_NSUB * seg_t
 };
 
@@ -1451,14 +1452,27 @@ resolve_boxes_kernel(FieldDev fld, RobotDev rb, PipelineQueues q, uint8_t* __res
 #endif
 }
 
+// ---- the tail hint -----------------------------------------------------------------------------------
+// The last kernel of a validity call leaves the number of boxes the tail had to look at (queues 4, 5, 6 and 2) in a
+// word of host-mapped memory; the host reads it, without waiting for anything, when it queues the NEXT call of the
+// same kind on that lane and picks the tail by it (launch_validate_pipeline).  Low byte: the tag the host gave this call (it changes
+// with every map write, so a word left by a call on the previous map is recognised), the rest: the count, saturated.
+// A stale word costs speed, never a label: both tails are complete for any counts.
+__device__ __forceinline__ void store_tail_hint(const PipelineQueues& q, unsigned* hint, unsigned tag) {
+  const unsigned long long n = fwd_total(q, 1) + fwd_total(q, 0) + q.counters[6] + q.counters[1];
+  *hint = (tag & 0xffu) | ((n > 0xffffffull ? 0xffffffu : (unsigned)n) << 8);
+}
+
 // ---- stage 3: plane stage ---------------------------------------------------------------------------
 template <int WAVES>
 __global__ void __launch_bounds__(64 * WAVES)
 plane_stage_kernel(FieldDev fb, FieldDev ff, RobotDev rb, PipelineQueues q, uint8_t* __restrict__ valid,
-                   ScratchCaps caps, int* __restrict__ error_flag) {
+                   ScratchCaps caps, int* __restrict__ error_flag, unsigned* __restrict__ hint = nullptr,
+                   unsigned hint_tag = 0u) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63;
   const WaveScratch s = carve_scratch(smem, threadIdx.x >> 6, caps);
+  if (hint != nullptr && blockIdx.x == 0 && threadIdx.x == 0) store_tail_hint(q, hint, hint_tag);  // every count is final
   const unsigned long long count = q.counters[1];
   const unsigned long long stride = (unsigned long long)gridDim.x * WAVES;
   for (unsigned long long item = (unsigned long long)blockIdx.x * WAVES + (threadIdx.x >> 6); item < count;
@@ -1481,6 +1495,77 @@ plane_stage_kernel(FieldDev fb, FieldDev ff, RobotDev rb, PipelineQueues q, uint
       result = (T > 0 && (foot ? wave_plane_stage(ff, b, s, lane, T) : wave_plane_stage(fb, b, s, lane, T))) ? 1 : 0;
     if (lane == 0) {
       const bool ok = (rec.kind & 1u) ? (result != 0) : (result == 0);
+      if (!ok) valid[rec.state] = 0;
+    }
+    wave_lds_sync();
+  }
+}
+
+// ---- the rare tail: everything behind the two stream passes in ONE launch ----------------------------------
+// On terrain without unknown cells a batch of 2^22 states leaves a few dozen boxes behind the stream passes, and the
+// five launches that take them in turn (lane scan, PASS 3, PASS 1, PASS 2, plane stage) are five launch-and-drain
+// slots and two dependent one-box chains for no work.  Here one wavefront takes one leftover box -- the items of
+// queue 4, then queue 6, then queue 5 -- through to its label:
+//   queue 4 (foot boxes without a table verdict) and queue 6 (torso boxes the stream pass handed on): ordered window
+//     scan, exits (b)-(e), (f), then the exact grouping -- PASS 1 in its direct mode / PASS 3, and the plane stage
+//     behind them, without the corner short cut in between: grp_plane_stage_corners answers 0 / 1 only where every kept
+//     candidate is a group of its own in the greedy grouping, i.e. where the grouping gives that answer too, and 2
+//     ("may have partners") otherwise (box_check.h, above grp_plane_stage_corners) --
+//     wave_check_box falls back from it to wave_plane_stage in the same way;
+//   queue 5 (foot boxes whose exits and (f) are known negative): the window tile and the exact grouping, which is
+//     plane_stage_kernel's body.
+// Nothing is pushed to any queue, queue 3 and queue 2 and their counters stay empty.  The boxes that ran the exact
+// grouping here are counted in a slot of their own (counters[3]), which artp_debug_pipeline_counters adds to queue 2's
+// count: "boxes of the batch that went through the exact grouping" in either tail.  Right for any counts, slow for many: one wavefront per box is the way through dozens of
+// boxes, not through the millions a map with unknown regions leaves (launch_validate_pipeline picks the tail).
+template <bool EXITS_AND_F>
+__device__ __forceinline__ int rare_resolve_box(const FieldDev& f, const BoxHF& b, const WaveScratch& s, int lane,
+                                                bool exits_negative, unsigned long long* grouped) {
+  WindowStats w;
+  wave_scan_window(f, b, s, lane, w);
+  if (EXITS_AND_F) {
+    int result = 0, ec;
+    if (!exits_negative && decide_exits(b, w, result, ec)) return result;
+    if (wave_vertex_pass(f, b, s, lane, w.allFinite)) return 1;
+  }
+  if (lane == 0) atomicAdd(grouped, 1ull);
+  const int T = wave_compact_triangles<true>(b, s, lane);
+  if (T < 0) return wave_plane_stage_unlisted(f, b, s, lane) ? 1 : 0;  // more kept triangles than the list holds
+  return (T > 0 && wave_plane_stage(f, b, s, lane, T)) ? 1 : 0;
+}
+
+__global__ void __launch_bounds__(64)
+rare_boxes_kernel(FieldDev fb, FieldDev ff, RobotDev rb, PipelineQueues q, uint8_t* __restrict__ valid,
+                  ScratchCaps caps, int* __restrict__ error_flag, unsigned* __restrict__ hint, unsigned hint_tag) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int lane = threadIdx.x;
+  const WaveScratch s = carve_scratch(smem, 0, caps);
+  if (hint != nullptr && blockIdx.x == 0 && lane == 0) store_tail_hint(q, hint, hint_tag);  // every count is final (queue 2: 0)
+  const unsigned long long n4 = fwd_total(q, 1), n6 = fwd_total(q, 0), n5 = q.counters[6];
+  const unsigned long long count = n4 + n6 + n5;
+  for (unsigned long long it = blockIdx.x; it < count; it += gridDim.x) {
+    // 0: queue 4, 1: queue 6, 2: queue 5 (wave-uniform)
+    const int from = it < n4 ? 0 : (it < n4 + n6 ? 1 : 2);
+    const unsigned item = from == 0 ? fwd_item(q, 1, q.q4, it) : (from == 1 ? fwd_item(q, 0, q.q6, it - n4) : q.q5[it - n4 - n6]);
+    const PendingBox rec = q.q1[item];
+    if (valid[rec.state] == 0) continue;  // another box of this state already failed
+    BoxHF b;
+    box_from_record(rec, rb, b);
+    const int total = (b.maxX - b.minX + 1) * (b.maxZ - b.minZ + 1);
+    if (total > s.cap_verts) {  // the window is held in LDS
+      if (lane == 0) atomicExch(error_flag, 1);
+      continue;
+    }
+    const bool foot = (rec.kind & 1u) != 0;
+    int result;
+    if (from == 2)  // foot boxes only
+      result = rare_resolve_box<false>(ff, b, s, lane, true, &q.counters[3]);
+    else if (foot)  // a record with a table verdict has its exits ruled out (the lane scan's rule); queue 4 holds none such
+      result = rare_resolve_box<true>(ff, b, s, lane, (rec.kind & ARTP_REC_EXITS_NEGATIVE) != 0, &q.counters[3]);
+    else            // PASS 3 evaluates the exits of every torso box from its own scan
+      result = rare_resolve_box<true>(fb, b, s, lane, false, &q.counters[3]);
+    if (lane == 0) {
+      const bool ok = foot ? (result != 0) : (result == 0);
       if (!ok) valid[rec.state] = 0;
     }
     wave_lds_sync();

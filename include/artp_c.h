@@ -560,6 +560,17 @@ int artp_set_few_edges(artp_ctx* ctx, int enabled);
  * interior state of every edge first, the rest only for the edges still alive (an edge is valid iff all its states are, so
  * the verdicts do not depend on it); two_pass == 0 = one pass over all states.  coarse_stride >= 2, 0 = the default (8). */
 int artp_set_edge_passes(artp_ctx* ctx, int two_pass, int coarse_stride);
+/* The tail of the batch validity step: what runs behind the two stream passes for the boxes they leave over.  The full
+ * tail is five launches that get through any number of such boxes (millions on a map with unknown regions); the rare tail
+ * is one launch, a wavefront per box, for the few dozen that terrain without unknown cells leaves.  Both give the same
+ * labels for any batch.  mode 0 (default) = pick per call from the count that the previous call OF THE SAME KIND on
+ * the lane left behind -- state batches, the first (or only) pass of an edge batch and its second pass keep a count each,
+ * since a checkMotion batch alternates two passes of very different size --, and take the full tail on the first such call
+ * on a lane and after every map, layer or table write; 1 = always the full tail; 2 = always the
+ * rare tail (correct, slow with many leftover boxes).  For tests and A/B runs.  artp_last_tail: the tail the last validity
+ * pass queued on the current lane took (1 full, 2 rare, 0 = none yet). */
+int artp_set_tail_mode(artp_ctx* ctx, int mode);
+int artp_last_tail(artp_ctx* ctx);
 int artp_check_motions_dev(artp_ctx* ctx, const double* s1, const double* s2, size_t n,
                            uint8_t* valid);
 /* ob::MotionValidator::checkMotion(s1, s2, std::pair<State*, double>& lastValid) (pure virtual in OMPL 1.4.2;
@@ -688,7 +699,9 @@ int artp_group_abort(artp_group* g);
  * the field.  Host result. */
 int artp_algorithmic_vertices_dev(artp_ctx* ctx, const double* se3, size_t n, uint64_t* total_vertices);
 /* Diagnostics of the last validity batch: out[0] = torso boxes queued for the window stage,
- * out[4] = foot boxes queued, out[1] = boxes that needed the exact plane grouping. */
+ * out[4] = foot boxes queued, out[1] = boxes that went through the exact plane grouping: queue 2 of the full tail plus
+ * the boxes the rare tail (artp_set_tail_mode) grouped itself -- every leftover box that exits and (f) left open, since
+ * that tail has no cheaper stage in front of the grouping. */
 int artp_debug_pipeline_counters(artp_ctx* ctx, uint64_t out[8]);
 /* Diagnostics: the partner table of a layer (one byte per sample in ODE sample layout, bit 0 / bit 1 =
  * the ABC / DBC triangle of the cell has an epsilon-equal plane within *radius cells).
