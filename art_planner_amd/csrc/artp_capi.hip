@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "device_scratch.h"
+#include "pinned_buffer.h"
 #include "pipeline.h"
 #include "cost_kernels.h"
 
@@ -40,10 +41,41 @@ using namespace artp;
 #define ARTP_TAIL_EDGES_2 2  // edge batches: the second pass
 #define ARTP_TAIL_KINDS 3
 
+// Everything a call in flight owns exists once per lane (artp_set_lane), so calls issued on different lanes (from one host
+// thread, on different streams) overlap on the GPU.  The map, its tables and the sampler are shared and read-only while
+// states are validated.  init_lane makes a lane; its buffers go with the context.
+struct lane_state {
+  int id = 0;
+  bool init = false;
+  hipStream_t own_stream = nullptr, stream = nullptr;  // stream: where this lane's calls go (artp_set_stream)
+  DeviceBuffer<unsigned long long> d_count;
+  DeviceBuffer<int> d_error;  // per lane: a capacity overflow is reported to the caller of the batch that raised it
+  // Scratch, grown on demand (ensure_scratch).  A buffer is its user's from the ensure_scratch to the end of the call;
+  // users of one buffer never nest, users of different buffers do (host entry points over their _dev twins, the edge
+  // paths and reachability over the validity pipeline).
+  DeviceBuffer<> host_args;     // a host entry point's arguments on the device (or, where it has none, its results)
+  DeviceBuffer<> host_results;  // ... and its results
+  DeviceBuffer<> edge_plan;     // run_edges_dev: per-edge counts, offsets, aux, first_bad, totals, slerp constants
+  DeviceBuffer<> edge_states;   // run_edges_dev: edge_of (u32) | labels (bytes) of the expanded interior states
+  DeviceBuffer<> box_queue;     // validity pipeline: the PendingBox sub-queues (PipelineQueues::q1)
+  DeviceBuffer<> index_queues;  // validity pipeline: counters | sub-queue counters | the index queues q2 .. q6
+  DeviceBuffer<> call_scratch;  // a device entry point's own side array: selected indices (artp_pack_edge_results_dev),
+                                // word offsets (artp_materialise_from_bits_dev), a chunk's labels (reachability)
+  DeviceBuffer<> pose_recs;     // the PoseRecs of the batch the validity pipeline runs on (ensure_recs)
+  DeviceBuffer<> cub_tmp;       // hipcub's workspace (ensure_cub_tmp)
+  // Ordering of map writes against the lanes: see artp_ctx::map_written
+  hipEvent_t lane_mark = nullptr;
+  uint64_t map_seen = 0;
+  // Tail history of the validity step (launch_validate_pipeline), per kind of call (ARTP_TAIL_*)
+  struct {
+    uint64_t map_version = 0;  // map_version + 1 the hint word belongs to (0 = none yet)
+    uint32_t tag = 0;          // changes whenever map_version does
+  } tail[ARTP_TAIL_KINDS];
+  int tail_last = 0;  // artp_last_tail: 1 full, 2 rare, 0 = no call yet
+};
+
 struct artp_ctx {
   int device = 0;
-  hipStream_t own_stream = nullptr;
-  hipStream_t stream = nullptr;
   artp_params params{};
   RobotDev robot{};
   MapGeom geom{};
@@ -51,24 +83,20 @@ struct artp_ctx {
   // artp_map_version(): bumped (under `mu`) by everything that changes a layer, its tables or the sampler tables
   std::atomic<uint64_t> map_version{0};
   FieldDev field[2]{};
-  float* field_data[2] = {nullptr, nullptr};
-  size_t field_elems[2] = {0, 0};
+  DeviceBuffer<float> field_data[2];
   bool have_field[2] = {false, false};
-  void* rect_stage_host = nullptr;   // artp_update_layer_rects: pinned staging (rectangle records + patches) ...
-  void* rect_stage_dev = nullptr;    // ... and its device twin
-  size_t rect_stage_cap = 0;
+  PinnedBuffer<> rect_stage_host;    // artp_update_layer_rects: pinned staging (rectangle records + patches) ...
+  DeviceBuffer<> rect_stage_dev;     // ... and its device twin
   hipEvent_t rect_stage_done = nullptr;  // the last update's host-to-device copy
   // Ordering of map writes against the lanes: a map write is issued on the current lane's stream.  In
   // front of it that stream waits for the work every other lane has been given so far (they may still read the old
   // samples / tables: lane_mark); behind it `map_written` is recorded, and a lane whose map_seen is behind
   // map_write_seq waits for that event before its next launch (artp_set_lane / the write itself for the current lane).
   hipEvent_t map_written = nullptr;
-  hipEvent_t lane_mark[4] = {nullptr, nullptr, nullptr, nullptr};
   uint64_t map_write_seq = 0;
-  uint64_t map_seen[4] = {0, 0, 0, 0};
   SamplerDev sampler{};
-  float* sampler_buf = nullptr;
-  float* sampler_pack = nullptr;  // derived tables: packed cells, row-major CDF, pivots
+  DeviceBuffer<float> sampler_buf;
+  DeviceBuffer<float> sampler_pack;  // derived tables: packed cells, row-major CDF, pivots
   int sampler_rows = 0, sampler_cols = 0;  // grid size sampler_buf / sampler_pack were allocated for
   bool have_sampler = false;
   double z_low = 0.0, z_high = 0.0;
@@ -81,16 +109,16 @@ struct artp_ctx {
   int edge_coarse_stride = ARTP_COARSE_STRIDE;  // $ARTP_COARSE_STRIDE (tuning)
   // map tables (pipeline.h): per layer 6 levels of {max, min} + 6 levels of non-finite / NaN flag bytes, the
   // partner table and the raw cross products it is built from
-  float* table_buf[2] = {nullptr, nullptr};
-  unsigned char* flag_buf[2] = {nullptr, nullptr};  // per-level non-finite / NaN block flags
-  unsigned* stride_buf[2] = {nullptr, nullptr};      // stride tables (TablesDev::st)
-  unsigned char* partner_buf[2] = {nullptr, nullptr};
-  unsigned* partner_cnt[2] = {nullptr, nullptr};  // partner counts per cell (pipeline.h partner_count_kernel)
-  int* d_diff = nullptr;                          // result of layer_diff_kernel (six ints)
+  DeviceBuffer<float> table_buf[2];
+  DeviceBuffer<unsigned char> flag_buf[2];    // per-level non-finite / NaN block flags
+  DeviceBuffer<unsigned> stride_buf[2];       // stride tables (TablesDev::st)
+  DeviceBuffer<unsigned char> partner_buf[2];
+  DeviceBuffer<unsigned> partner_cnt[2];  // partner counts per cell (pipeline.h partner_count_kernel)
+  DeviceBuffer<int> d_diff;               // result of layer_diff_kernel (six ints)
   int partner_R_built[2] = {-1, -1};
   int layer_has_nonfinite[2] = {1, 1};
-  float4* tri_raw_buf[2] = {nullptr, nullptr};
-  size_t table_elems[2] = {0, 0};
+  DeviceBuffer<float4> tri_raw_buf[2];
+  size_t table_elems[2] = {0, 0};   // the samples the six buffers of a layer were allocated for
   TablesDev tables[2]{};
   ScratchCaps caps_full{0, 0, 0, 0};  // window tile + triangle list + hash table (1 wave / block)
   ScratchCaps caps_scan{0, 0, 0, 0};  // torso resolve stage: window tile + short triangle list, per wave
@@ -99,17 +127,14 @@ struct artp_ctx {
   ScratchCaps caps_foot_full{0, 0, 0, 0};  // validate_few_kernel: a foot wavefront's full zone-test scratch
   int n_cus = 256;
   // latency path (<= ARTP_FEW_STATES states per call): mapped pinned host memory, read / written by the kernel
-  double* pin_states = nullptr;           // host view, ARTP_FEW_STATES x 7
-  volatile uint8_t* pin_labels = nullptr; // host view
-  double* pin_states_dev = nullptr;       // device view of the same memory
-  uint8_t* pin_labels_dev = nullptr;
+  PinnedBuffer<double> pin_states;            // ARTP_FEW_STATES x 7
+  PinnedBuffer<volatile uint8_t> pin_labels;
   bool poll_labels = true;                // spin on the mapped labels instead of hipStreamSynchronize
   // persistent latency service (artp_set_persistent_latency): its own stream, a mailbox in mapped host memory
   bool svc_enabled = false, svc_launched = false;
   hipStream_t svc_stream = nullptr;
   hipEvent_t svc_after_map = nullptr;     // orders a (re)launch behind the map writes already on the context's stream
-  SvcMailbox* svc = nullptr;              // host view
-  SvcMailbox* svc_dev = nullptr;          // device view
+  PinnedBuffer<SvcMailbox> svc;
   uint32_t svc_seq = 0;
   uint64_t svc_map_version = 0;
   uint64_t svc_launches = 0, svc_requests = 0;
@@ -117,11 +142,10 @@ struct artp_ctx {
   bool pool_launched = false;
   hipStream_t pool_stream = nullptr;
   hipEvent_t pool_after_map = nullptr;
-  EdgeMailbox* pool_mb = nullptr;         // the request block: DEVICE memory that the host writes through the PCIe BAR
+  DeviceBuffer<EdgeMailbox> pool_mb;      // the request block: DEVICE memory that the host writes through the PCIe BAR
   int pool_bar = -1;                      // does the device expose its memory to the host (large BAR)?  -1 = not asked yet
-  PoolResponse* pool_resp = nullptr;      // host view (per-workgroup slots)
-  PoolResponse* pool_resp_dev = nullptr;
-  PoolCtl* pool_ctl = nullptr;            // device memory
+  PinnedBuffer<PoolResponse> pool_resp;   // per-workgroup slots
+  DeviceBuffer<PoolCtl> pool_ctl;
   uint64_t pool_shadow[5][7] = {};        // the payload words of the request block as last written
   unsigned pool_wgs = ARTP_POOL_WGS;
   uint32_t pool_seq = 0;
@@ -129,70 +153,40 @@ struct artp_ctx {
   uint64_t pool_launches = 0, pool_requests = 0;
   // latency path of the edge checks (<= ARTP_FEW_EDGES edges per call): one mapped block
   //   s1 | s2 (64 x 7 f64 each) | last_t (64 f64) | last_state (64 x 7 f64) | aux (64 u32) | status (64 u8)
-  char* pin_edges_in = nullptr;           // s1 | s2 of a call, host view
-  char* pin_edges_in_dev = nullptr;
-  char* pin_edges = nullptr;              // host view
-  char* pin_edges_dev = nullptr;          // device view
-  FewEdgeSync* d_few_sync = nullptr;      // device, armed {~0, 0, 0} per edge (the kernel re-arms what it used)
-  // device scratch
-  int* d_error = nullptr;
-  unsigned long long* d_count = nullptr;
-  void* tmp[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  size_t tmp_cap[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  void* cub_tmp = nullptr;
-  size_t cub_cap = 0;
+  PinnedBuffer<char> pin_edges_in;        // s1 | s2 of a call
+  PinnedBuffer<char> pin_edges;
+  DeviceBuffer<FewEdgeSync> d_few_sync;   // armed {~0, 0, 0} per edge (the kernel re-arms what it used)
   // clearance.h: the offset list of the disc of radius R, built when R is first met and never rewritten
-  int32_t* clear_offs[33] = {};
+  DeviceBuffer<int32_t> clear_offs[33];
   uint32_t clear_n[33] = {};
-  // Lanes (artp_set_lane): everything above that a call in flight owns -- stream, scratch buffers, counters -- exists
-  // once per lane, so calls issued on different lanes (from one host thread, on different streams) overlap on the
-  // GPU.  The members above are the CURRENT lane's; the others are parked here.  The map, its tables and the
-  // sampler are shared and read-only while states are validated.
-  struct lane_state {
-    bool init = false;
-    hipStream_t own_stream = nullptr, stream = nullptr;
-    unsigned long long* d_count = nullptr;
-    int* d_error = nullptr;  // per lane: a capacity overflow is reported to the caller of the batch that raised it
-    void* tmp[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t tmp_cap[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    void* cub_tmp = nullptr;
-    size_t cub_cap = 0;
-  };
   lane_state lanes[ARTP_MAX_LANES];
-  int cur_lane = 0;
+  lane_state* lane = &lanes[0];  // the current lane (artp_set_lane)
   // The tail of the validity step (launch_validate_pipeline).  tail_hint: mapped pinned host memory, one word per lane
   // and kind of call (ARTP_TAIL_*), each on a 64-byte line of its own, written by the last kernel of such a call on that
   // lane (store_tail_hint, pipeline.h) and read by the host, unsynchronised, when it queues the next one of that kind.
   int tail_mode = 0;                        // artp_set_tail_mode: 0 auto, 1 always the full tail, 2 always the rare tail
-  volatile unsigned* tail_hint = nullptr;   // host view, ARTP_MAX_LANES x ARTP_TAIL_KINDS x 16 words
-  unsigned* tail_hint_dev = nullptr;        // device view
-  uint64_t tail_map_version[ARTP_MAX_LANES][ARTP_TAIL_KINDS] = {};  // map_version + 1 the hint belongs to (0 = none yet)
-  uint32_t tail_tag[ARTP_MAX_LANES][ARTP_TAIL_KINDS] = {};          // changes whenever tail_map_version does
-  int tail_last[ARTP_MAX_LANES] = {0, 0, 0, 0};       // artp_last_tail: 1 full, 2 rare, 0 = no call yet
+  PinnedBuffer<volatile unsigned> tail_hint;   // ARTP_MAX_LANES x ARTP_TAIL_KINDS x 16 words
   // motion cost (R8/R9)
   bool have_weights = false;
   int cost_net = 0;                    // blob version of the loaded network: 1 light (network_light.py), 2 full width (network.py)
-  half8* d_convw[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // [4]: the 15 x 15 layer's B fragments, per-row packing
-  float* d_convb[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  float* d_c12 = nullptr;              // conv1 o conv2 composed: [24][25] + [24] (conv12_pool_kernel)
-  unsigned char* d_c12m = nullptr;     // the same as MFMA fragments, hi / lo half floats + bias[32] (conv12_mfma_kernel)
+  DeviceBuffer<half8> d_convw[5];      // [4]: the 15 x 15 layer's B fragments, per-row packing; the others stay empty
+  DeviceBuffer<float> d_convb[5];
+  DeviceBuffer<float> d_c12;           // conv1 o conv2 composed: [24][25] + [24] (conv12_pool_kernel)
+  DeviceBuffer<unsigned char> d_c12m;  // the same as MFMA fragments, hi / lo half floats + bias[32] (conv12_mfma_kernel)
   int conv12_mfma = 1;                 // $ARTP_CONV12_MFMA=0: the VALU form (rounds 3-4)
-  half8* d_convw_chunk[3] = {nullptr, nullptr, nullptr};  // conv3..5 B fragments in chunk order (conv345_kernel)
-  half8* d_convw_p32 = nullptr;   // variants build: the 15 x 15 layer's weights for conv15_pair32_kernel
-  float* d_fc = nullptr;               // FcWeights::TOTAL floats
-  char* d_fc_mfma = nullptr;           // FcMfma::TOTAL bytes: the same MLP in MFMA fragment order (fc_mfma_pack)
+  DeviceBuffer<half8> d_convw_chunk[3];  // conv3..5 B fragments in chunk order (conv345_kernel)
+  DeviceBuffer<half8> d_convw_p32;     // variants build: the 15 x 15 layer's weights for conv15_pair32_kernel
+  DeviceBuffer<float> d_fc;            // FcWeights::TOTAL floats
+  DeviceBuffer<char> d_fc_mfma;        // FcMfma::TOTAL bytes: the same MLP in MFMA fragment order (fc_mfma_pack)
   int feet_dense = 0;                  // $ARTP_FEET_DENSE=1: feet_stream2_kernel (corner arithmetic on dense lanes; measured: no faster)
   double r3_extent_override = 0.0;     // artp_set_r3_extent: > 0 = checkMotion's R^3 maxExtent, whatever the installed map's bounds
   int fc_mfma = 1;                     // the kernel artp_cost_query uses now (artp_cost_fc_path)
   int fc_selfcheck = -1;               // artp_cost_load_weights' probe batch: 1 = the MFMA kernel agreed with the fp32 one,
                                        // 0 = it did not (fc_mfma forced to 0), -1 = not run
   float fc_selfcheck_err = 0.f;        // largest |MFMA - fp32| of the probe batch
-  half_t* d_act[2] = {nullptr, nullptr};
-  size_t act_cap = 0;
-  half_t* d_feat = nullptr;            // NHWC [Fh][Fw][48 | 64] (the loaded network's feature channels)
-  size_t feat_cap = 0;
-  float* d_map_f32 = nullptr;
-  size_t map_cap = 0;
+  DeviceBuffer<half_t> d_act[2];
+  DeviceBuffer<half_t> d_feat;         // NHWC [Fh][Fw][48 | 64] (the loaded network's feature channels)
+  DeviceBuffer<float> d_map_f32;
   CostMapGeom cost_geom{};
   int feat_h = 0, feat_w = 0;
   int cost_forms[4] = {0, 0, 0, 0};    // artp_cost_debug_forms: network, conv345 tile edge, 15 x 15 tile rows, its threads
@@ -206,54 +200,42 @@ struct artp_ctx {
 
 namespace {
 
-int ensure_tmp(artp_ctx* c, int slot, size_t bytes) {
-  if (c->tmp_cap[slot] >= bytes) return ARTP_OK;
-  if (c->tmp[slot]) HIP_TRY(c, hipFree(c->tmp[slot]));
-  c->tmp[slot] = nullptr;
-  c->tmp_cap[slot] = 0;
-  const size_t want = bytes + bytes / 4 + 256;
-  HIP_TRY(c, hipMalloc(&c->tmp[slot], want));
-  c->tmp_cap[slot] = want;
+// Room for `bytes` in one of the current lane's scratch buffers, with a quarter more so that slowly growing batches do not
+// reallocate at every call.
+int ensure_scratch(artp_ctx* c, DeviceBuffer<>& buf, size_t bytes) {
+  if (buf.capacity() < bytes) HIP_TRY(c, buf.reserve(bytes + bytes / 4 + 256));
   return ARTP_OK;
 }
 
-void park_lane(artp_ctx* c) {  // current members -> lanes[cur_lane]
-  artp_ctx::lane_state& l = c->lanes[c->cur_lane];
-  l.init = true;
-  l.own_stream = c->own_stream;
-  l.stream = c->stream;
-  l.d_count = c->d_count;
-  l.d_error = c->d_error;
-  l.cub_tmp = c->cub_tmp;
-  l.cub_cap = c->cub_cap;
-  for (int k = 0; k < 8; ++k) {
-    l.tmp[k] = c->tmp[k];
-    l.tmp_cap[k] = c->tmp_cap[k];
-  }
+// Room for `need` bytes of hipcub workspace on the current lane (hipcub takes a null workspace for a size query and
+// does nothing: the pointer must be there).
+int ensure_cub_tmp(artp_ctx* c, size_t need) {
+  if (c->lane->cub_tmp.capacity() < need) HIP_TRY(c, c->lane->cub_tmp.reserve(need + 256));
+  return ARTP_OK;
 }
 
-void unpark_lane(artp_ctx* c, int lane) {
-  const artp_ctx::lane_state& l = c->lanes[lane];
-  c->own_stream = l.own_stream;
-  c->stream = l.stream;
-  c->d_count = l.d_count;
-  c->d_error = l.d_error;
-  c->cub_tmp = l.cub_tmp;
-  c->cub_cap = l.cub_cap;
-  for (int k = 0; k < 8; ++k) {
-    c->tmp[k] = l.tmp[k];
-    c->tmp_cap[k] = l.tmp_cap[k];
-  }
-  c->cur_lane = lane;
+// A lane's stream and counters, the first time the lane is used (artp_create: lane 0, artp_set_lane: the others).  What a
+// failure leaves half made is kept for the next attempt and goes with the context.
+int init_lane(artp_ctx* c, int id) {
+  lane_state& l = c->lanes[id];
+  if (l.init) return ARTP_OK;
+  l.id = id;
+  if (!l.own_stream) HIP_TRY(c, hipStreamCreateWithFlags(&l.own_stream, hipStreamNonBlocking));
+  HIP_TRY(c, l.d_count.reserve(sizeof(unsigned long long)));
+  HIP_TRY(c, l.d_error.reserve(sizeof(int)));
+  HIP_TRY(c, hipMemset(l.d_error.get(), 0, sizeof(int)));
+  l.stream = l.own_stream;
+  l.init = true;
+  return ARTP_OK;
 }
 
 // In front of a map write: the current stream waits for everything the other lanes were given so far.
 int order_after_other_lanes(artp_ctx* c) {
-  for (int l = 0; l < ARTP_MAX_LANES; ++l) {
-    if (l == c->cur_lane || !c->lanes[l].init) continue;
-    if (!c->lane_mark[l]) HIP_TRY(c, hipEventCreateWithFlags(&c->lane_mark[l], hipEventDisableTiming));
-    HIP_TRY(c, hipEventRecord(c->lane_mark[l], c->lanes[l].stream));
-    HIP_TRY(c, hipStreamWaitEvent(c->stream, c->lane_mark[l], 0));
+  for (lane_state& l : c->lanes) {
+    if (&l == c->lane || !l.init) continue;
+    if (!l.lane_mark) HIP_TRY(c, hipEventCreateWithFlags(&l.lane_mark, hipEventDisableTiming));
+    HIP_TRY(c, hipEventRecord(l.lane_mark, l.stream));
+    HIP_TRY(c, hipStreamWaitEvent(c->lane->stream, l.lane_mark, 0));
   }
   return ARTP_OK;
 }
@@ -262,15 +244,15 @@ int order_after_other_lanes(artp_ctx* c) {
 // lanes' next launches wait for it.  The host-synchronous writers (full upload, sampler layers) call it too: free.
 int publish_map_write(artp_ctx* c) {
   if (!c->map_written) HIP_TRY(c, hipEventCreateWithFlags(&c->map_written, hipEventDisableTiming));
-  HIP_TRY(c, hipEventRecord(c->map_written, c->stream));
-  c->map_seen[c->cur_lane] = ++c->map_write_seq;
+  HIP_TRY(c, hipEventRecord(c->map_written, c->lane->stream));
+  c->lane->map_seen = ++c->map_write_seq;
   return ARTP_OK;
 }
 
-int lane_sees_map(artp_ctx* c) {  // after unpark_lane: the now-current lane catches up with the last map write
-  if (c->map_seen[c->cur_lane] != c->map_write_seq && c->map_written) {
-    HIP_TRY(c, hipStreamWaitEvent(c->stream, c->map_written, 0));
-    c->map_seen[c->cur_lane] = c->map_write_seq;
+int lane_sees_map(artp_ctx* c) {  // artp_set_lane: the now-current lane catches up with the last map write
+  if (c->lane->map_seen != c->map_write_seq && c->map_written) {
+    HIP_TRY(c, hipStreamWaitEvent(c->lane->stream, c->map_written, 0));
+    c->lane->map_seen = c->map_write_seq;
   }
   return ARTP_OK;
 }
@@ -481,15 +463,15 @@ int build_partner_table_full(artp_ctx* c, int slot) {
   all.x1[0] = f.nW - 1;   // the last column / row hold no cell: tri_raw writes +inf there, the counts stay 0
   all.z1[0] = f.nD - 1;
   const int ncell = f.nW * f.nD;
-  hipLaunchKernelGGL(tri_raw_rects_kernel, dim3((ncell + 255) / 256, 1), dim3(256), 0, c->stream, f, all,
-                     c->tri_raw_buf[slot], c->partner_cnt[slot]);
-  hipLaunchKernelGGL(partner_count_kernel<false>, dim3((ncell + 255) / 256, 2 * R + 1, 1), dim3(256), 0, c->stream, f, R,
-                     (const float4*)c->tri_raw_buf[slot], c->partner_cnt[slot], all, 1);
-  hipLaunchKernelGGL(partner_flags_from_counts_kernel, dim3((ncell + 255) / 256, 1), dim3(256), 0, c->stream, f.nW, f.nD, all,
-                     0, (const unsigned*)c->partner_cnt[slot], c->partner_buf[slot]);
+  hipLaunchKernelGGL(tri_raw_rects_kernel, dim3((ncell + 255) / 256, 1), dim3(256), 0, c->lane->stream, f, all,
+                     c->tri_raw_buf[slot].get(), c->partner_cnt[slot].get());
+  hipLaunchKernelGGL(partner_count_kernel<false>, dim3((ncell + 255) / 256, 2 * R + 1, 1), dim3(256), 0, c->lane->stream, f, R,
+                     (const float4*)c->tri_raw_buf[slot].get(), c->partner_cnt[slot].get(), all, 1);
+  hipLaunchKernelGGL(partner_flags_from_counts_kernel, dim3((ncell + 255) / 256, 1), dim3(256), 0, c->lane->stream, f.nW, f.nD, all,
+                     0, (const unsigned*)c->partner_cnt[slot].get(), c->partner_buf[slot].get());
   HIP_TRY(c, hipGetLastError());
   c->partner_R_built[slot] = R;
-  f.partner_flags = c->partner_buf[slot];
+  f.partner_flags = c->partner_buf[slot].get();
   f.partner_R = R;
   return ARTP_OK;
 }
@@ -532,8 +514,8 @@ int partner_update_begin(artp_ctx* c, int slot, const int* dirty, int n_dirty, P
   if (pr->n == 0) return ARTP_OK;
   int cells, rows;
   partner_rect_extent(f, *pr, R, &cells, &rows);
-  hipLaunchKernelGGL(partner_count_kernel<true>, dim3((cells + 255) / 256, rows, pr->n), dim3(256), 0, c->stream, f, R,
-                     (const float4*)c->tri_raw_buf[slot], c->partner_cnt[slot], *pr, -1);
+  hipLaunchKernelGGL(partner_count_kernel<true>, dim3((cells + 255) / 256, rows, pr->n), dim3(256), 0, c->lane->stream, f, R,
+                     (const float4*)c->tri_raw_buf[slot].get(), c->partner_cnt[slot].get(), *pr, -1);
   HIP_TRY(c, hipGetLastError());
   // From here to the end of step 2 the counts are half-updated: until partner_update_end has queued its passes the
   // table counts as NOT built, so a failure in between (the copy, the scatter, the range tables) makes the next update
@@ -554,17 +536,17 @@ int partner_update_end(artp_ctx* c, int slot, const PartnerRects& pr) {
   int cells0, cellsR, rows;
   partner_rect_extent(f, pr, 0, &cells0, &rows);
   partner_rect_extent(f, pr, R, &cellsR, &rows);
-  hipLaunchKernelGGL(tri_raw_rects_kernel, dim3((cells0 + 255) / 256, pr.n), dim3(256), 0, c->stream, f, pr,
-                     c->tri_raw_buf[slot], c->partner_cnt[slot]);
-  hipLaunchKernelGGL(partner_count_kernel<true>, dim3((cellsR + 255) / 256, rows, pr.n), dim3(256), 0, c->stream, f, R,
-                     (const float4*)c->tri_raw_buf[slot], c->partner_cnt[slot], pr, 1);
-  hipLaunchKernelGGL(partner_count_kernel<false>, dim3((cells0 + 255) / 256, 2 * R + 1, pr.n), dim3(256), 0, c->stream, f, R,
-                     (const float4*)c->tri_raw_buf[slot], c->partner_cnt[slot], pr, 1);
-  hipLaunchKernelGGL(partner_flags_from_counts_kernel, dim3((cellsR + 255) / 256, pr.n), dim3(256), 0, c->stream, f.nW, f.nD,
-                     pr, R, (const unsigned*)c->partner_cnt[slot], c->partner_buf[slot]);
+  hipLaunchKernelGGL(tri_raw_rects_kernel, dim3((cells0 + 255) / 256, pr.n), dim3(256), 0, c->lane->stream, f, pr,
+                     c->tri_raw_buf[slot].get(), c->partner_cnt[slot].get());
+  hipLaunchKernelGGL(partner_count_kernel<true>, dim3((cellsR + 255) / 256, rows, pr.n), dim3(256), 0, c->lane->stream, f, R,
+                     (const float4*)c->tri_raw_buf[slot].get(), c->partner_cnt[slot].get(), pr, 1);
+  hipLaunchKernelGGL(partner_count_kernel<false>, dim3((cells0 + 255) / 256, 2 * R + 1, pr.n), dim3(256), 0, c->lane->stream, f, R,
+                     (const float4*)c->tri_raw_buf[slot].get(), c->partner_cnt[slot].get(), pr, 1);
+  hipLaunchKernelGGL(partner_flags_from_counts_kernel, dim3((cellsR + 255) / 256, pr.n), dim3(256), 0, c->lane->stream, f.nW, f.nD,
+                     pr, R, (const unsigned*)c->partner_cnt[slot].get(), c->partner_buf[slot].get());
   HIP_TRY(c, hipGetLastError());
   c->partner_R_built[slot] = R;
-  f.partner_flags = c->partner_buf[slot];
+  f.partner_flags = c->partner_buf[slot].get();
   f.partner_R = R;
   return ARTP_OK;
 }
@@ -575,38 +557,34 @@ int build_tables(artp_ctx* c, int slot, const PartnerRects* pr = nullptr) {
   const FieldDev& f = c->field[slot];
   const size_t elems = (size_t)f.nW * f.nD;
   if (c->table_elems[slot] < elems) {
-    if (c->table_buf[slot]) HIP_TRY(c, hipFree(c->table_buf[slot]));
-    if (c->flag_buf[slot]) HIP_TRY(c, hipFree(c->flag_buf[slot]));
-    if (c->stride_buf[slot]) HIP_TRY(c, hipFree(c->stride_buf[slot]));
-    c->stride_buf[slot] = nullptr;
-    if (c->partner_buf[slot]) HIP_TRY(c, hipFree(c->partner_buf[slot]));
-    if (c->partner_cnt[slot]) HIP_TRY(c, hipFree(c->partner_cnt[slot]));
-    c->partner_cnt[slot] = nullptr;
-    HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->partner_cnt[slot]), elems * sizeof(unsigned)));
-    if (c->tri_raw_buf[slot]) HIP_TRY(c, hipFree(c->tri_raw_buf[slot]));
-    c->tri_raw_buf[slot] = nullptr;
-    HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->tri_raw_buf[slot]), elems * sizeof(float4)));
-    c->table_buf[slot] = nullptr;
-    c->flag_buf[slot] = nullptr;
-    c->partner_buf[slot] = nullptr;
-    HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->partner_buf[slot]), (elems + 3) / 4 * 4));
+    c->table_elems[slot] = 0;
     c->partner_R_built[slot] = -1;
-    HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->table_buf[slot]), 12 * elems * sizeof(float)));
-    HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->flag_buf[slot]), 6 * elems));
+    // all six go before the first comes back: peak memory stays at one set of tables
+    HIP_TRY(c, c->partner_cnt[slot].reset());
+    HIP_TRY(c, c->tri_raw_buf[slot].reset());
+    HIP_TRY(c, c->partner_buf[slot].reset());
+    HIP_TRY(c, c->table_buf[slot].reset());
+    HIP_TRY(c, c->flag_buf[slot].reset());
+    HIP_TRY(c, c->stride_buf[slot].reset());
+    HIP_TRY(c, c->partner_cnt[slot].reserve(elems * sizeof(unsigned)));
+    HIP_TRY(c, c->tri_raw_buf[slot].reserve(elems * sizeof(float4)));
+    HIP_TRY(c, c->partner_buf[slot].reserve((elems + 3) / 4 * 4));
+    HIP_TRY(c, c->table_buf[slot].reserve(12 * elems * sizeof(float)));
+    HIP_TRY(c, c->flag_buf[slot].reserve(6 * elems));
     // stride tables: (nW / s) x (nD / s) entries for s = 2, 4, 8 -- less than elems / 2 entries in all
-    HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->stride_buf[slot]), (elems / 2 + 3 * (f.nW + f.nD) + 16) * sizeof(unsigned)));
+    HIP_TRY(c, c->stride_buf[slot].reserve((elems / 2 + 3 * (f.nW + f.nD) + 16) * sizeof(unsigned)));
     c->table_elems[slot] = elems;
   }
   float2* mm[6];
   unsigned char* fl[6];
   for (int l = 0; l < 6; ++l) {
-    mm[l] = reinterpret_cast<float2*>(c->table_buf[slot]) + (size_t)l * elems;
-    fl[l] = reinterpret_cast<unsigned char*>(c->flag_buf[slot]) + (size_t)l * elems;
+    mm[l] = c->table_buf[slot].as<float2>() + (size_t)l * elems;
+    fl[l] = c->flag_buf[slot].get() + (size_t)l * elems;
   }
   const int n = (int)elems;
-  hipLaunchKernelGGL(table_level0_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, f.data, n, mm[0], fl[0]);
+  hipLaunchKernelGGL(table_level0_kernel, dim3((n + 255) / 256), dim3(256), 0, c->lane->stream, f.data, n, mm[0], fl[0]);
   for (int l = 1; l < 6; ++l)
-    hipLaunchKernelGGL(table_level_up_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream,
+    hipLaunchKernelGGL(table_level_up_kernel, dim3((n + 255) / 256), dim3(256), 0, c->lane->stream,
                        (const float2*)mm[l - 1], (const unsigned char*)fl[l - 1], f.nW, f.nD, 1 << (l - 1), mm[l],
                        fl[l]);
   HIP_TRY(c, hipGetLastError());
@@ -622,134 +600,130 @@ int build_tables(artp_ctx* c, int slot, const PartnerRects* pr = nullptr) {
       const int s = 2 << l;
       off[l + 1] = off[l] + (unsigned)(((f.nW + s - 1) / s) * ((f.nD + s - 1) / s));
     }
-    t.st = c->stride_buf[slot];
+    t.st = c->stride_buf[slot].get();
     t.st_off1 = off[1];
     t.st_off2 = off[2];
-    hipLaunchKernelGGL(stride_tables_kernel, dim3((off[3] + 255) / 256), dim3(256), 0, c->stream, t.mm, t.fl, t.stride,
-                       f.nW, f.nD, off[1], off[2], off[3], c->stride_buf[slot]);
+    hipLaunchKernelGGL(stride_tables_kernel, dim3((off[3] + 255) / 256), dim3(256), 0, c->lane->stream, t.mm, t.fl, t.stride,
+                       f.nW, f.nD, off[1], off[2], off[3], c->stride_buf[slot].get());
     HIP_TRY(c, hipGetLastError());
   }
   // a rectangle update that met a table not built for this R (or too many / too large rectangles) has pr->n = 0 and
   // rebuilds the whole table
-  const int rc_partner = pr ? partner_update_end(c, slot, *pr) : build_partner_table_full(c, slot);
-  if (rc_partner != ARTP_OK) return rc_partner;
+  ARTP_TRY(pr ? partner_update_end(c, slot, *pr) : build_partner_table_full(c, slot));
   t.valid = 1;
   return ARTP_OK;
 }
 
-// Room for the PoseRecs of a batch (tmp[7]).
-int ensure_recs(artp_ctx* c, size_t n) { return ensure_tmp(c, 7, n * sizeof(PoseRec)); }
+// Room for the PoseRecs of a batch.
+int ensure_recs(artp_ctx* c, size_t n) { return ensure_scratch(c, c->lane->pose_recs, n * sizeof(PoseRec)); }
 
 // classify -> resolve -> plane stage on the context's stream (all asynchronous).  recs_ready: the PoseRecs of
-// the batch are already in tmp[7] (the fused sampler wrote them); otherwise pose_rec_kernel makes them from se3.
+// the batch are already in pose_recs (the fused sampler wrote them); otherwise pose_rec_kernel makes them from se3.
 int launch_validate_pipeline(artp_ctx* c, const double* se3, size_t n, uint8_t* valid, bool recs_ready = false,
                              int tail_kind = ARTP_TAIL_STATES) {
   if (n >= (1ull << 32)) {
     c->last_error = "batch too large (state index is 32 bit)";
     return ARTP_ERR_INVALID_ARG;
   }
-  int rc = ensure_recs(c, n);
-  if (rc) return rc;
-  PoseRec* recs = static_cast<PoseRec*>(c->tmp[7]);
+  ARTP_TRY(ensure_recs(c, n));
+  PoseRec* recs = c->lane->pose_recs.as<PoseRec>();
   if (!recs_ready)
-    hipLaunchKernelGGL(pose_rec_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->field[0], se3, n,
+    hipLaunchKernelGGL(pose_rec_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->lane->stream, c->field[0], se3, n,
                        recs);
   const size_t per_block_states = 64 * ARTP_CLASSIFY_SUB;
   const size_t n_blocks = (n + per_block_states - 1) / per_block_states;
   // sub-queue capacity: every workgroup of a sub-queue may queue all of its boxes
   const size_t seg_t = ((n_blocks + ARTP_NSUB - 1) / ARTP_NSUB) * per_block_states;
-  rc = ensure_tmp(c, 4, 5 * ARTP_NSUB * seg_t * sizeof(PendingBox));
-  if (rc) return rc;
-  // tmp[5]: 8 counters | pad to 128 B | 2 * ARTP_NSUB sub-queue counters, one per 128-byte line | index queues
+  ARTP_TRY(ensure_scratch(c, c->lane->box_queue, 5 * ARTP_NSUB * seg_t * sizeof(PendingBox)));
+  // index_queues: 8 counters | pad to 128 B | 2 * ARTP_NSUB sub-queue counters, one per 128-byte line | index queues
   const size_t ctr_bytes = 128 + (size_t)2 * ARTP_NSUB * 128;
   // index queues: q2 (5 n), q3 (4 n), q5 (4 n) | q4 and q6 in ARTP_NSUB segments like the big queues (4 seg_t / seg_t each)
-  rc = ensure_tmp(c, 5, ctr_bytes + ((5 + 4 + 4) * n + 5 * (size_t)ARTP_NSUB * seg_t) * sizeof(unsigned) + 64);
-  if (rc) return rc;
+  ARTP_TRY(ensure_scratch(c, c->lane->index_queues, ctr_bytes + ((5 + 4 + 4) * n + 5 * (size_t)ARTP_NSUB * seg_t) * sizeof(unsigned) + 64));
   PipelineQueues q;
-  q.q1 = static_cast<PendingBox*>(c->tmp[4]);
-  q.counters = static_cast<unsigned long long*>(c->tmp[5]);
+  q.q1 = c->lane->box_queue.as<PendingBox>();
+  q.counters = c->lane->index_queues.as<unsigned long long>();
   q.sub = q.counters + 16;
   q.seg_t = seg_t;
-  q.q2 = reinterpret_cast<unsigned*>(static_cast<char*>(c->tmp[5]) + ctr_bytes);
+  q.q2 = reinterpret_cast<unsigned*>(c->lane->index_queues.as<char>() + ctr_bytes);
   q.q3 = q.q2 + 5 * n;
   q.q5 = q.q3 + 4 * n;
   q.q4 = q.q5 + 4 * n;
   q.q6 = q.q4 + 4 * (size_t)ARTP_NSUB * seg_t;
   q.feet_base = (unsigned long long)ARTP_NSUB * seg_t;
-  HIP_TRY(c, hipMemsetAsync(q.counters, 0, ctr_bytes, c->stream));
+  HIP_TRY(c, hipMemsetAsync(q.counters, 0, ctr_bytes, c->lane->stream));
   const size_t per_block = 64 * ARTP_CLASSIFY_SUB;
   hipLaunchKernelGGL(classify_states_kernel, dim3((unsigned)((n + per_block - 1) / per_block)),
-                     dim3(ARTP_CLASSIFY_THREADS), 0, c->stream,
+                     dim3(ARTP_CLASSIFY_THREADS), 0, c->lane->stream,
                      c->field[0], c->field[1], c->tables[0], c->tables[1], c->geom, c->robot, (const PoseRec*)recs, n,
                      valid, q);
 #ifdef ARTP_VARIANTS
   if (c->feet_dense)   // round 5 experiment: the corner stage's plane / contact arithmetic on dense lanes (pipeline_variants.h)
     hipLaunchKernelGGL(feet_stream2_kernel<ARTP_STREAM_WAVES>, dim3(grid_sub(c, ARTP_FEET_WAVES_PER_SIMD)), dim3(64 * ARTP_STREAM_WAVES), 0,
-                       c->stream, c->field[1], c->robot, q, valid);
+                       c->lane->stream, c->field[1], c->robot, q, valid);
   else
 #endif
     hipLaunchKernelGGL(feet_stream_kernel<ARTP_STREAM_WAVES>, dim3(grid_sub(c, ARTP_FEET_WAVES_PER_SIMD)), dim3(64 * ARTP_STREAM_WAVES), 0,
-                       c->stream, c->field[1], c->robot, q, valid);
+                       c->lane->stream, c->field[1], c->robot, q, valid);
   // The tail: five launches that get through any number of leftover boxes, or one that gets through a few (pipeline.h,
   // rare_boxes_kernel).  Either is right for any counts, so the choice is a speed hint, taken from the lane's previous
   // call of the same kind: consecutive batches on one map leave about as many boxes behind.  The first call of a kind on
   // a lane, and the first after anything changed the map or its tables, has no such history and takes the full tail.
-  const int lane_id = c->cur_lane;
+  auto& hist = c->lane->tail[tail_kind];
   const uint64_t map_v = c->map_version.load(std::memory_order_acquire) + 1;
-  const bool fresh = c->tail_map_version[lane_id][tail_kind] != map_v;
+  const bool fresh = hist.map_version != map_v;
   if (fresh) {
-    c->tail_map_version[lane_id][tail_kind] = map_v;
-    ++c->tail_tag[lane_id][tail_kind];
+    hist.map_version = map_v;
+    ++hist.tag;
   }
-  const unsigned hint_tag = c->tail_tag[lane_id][tail_kind] & 0xffu;
-  const size_t hint_at = 16 * (size_t)(lane_id * ARTP_TAIL_KINDS + tail_kind);
-  unsigned* hint_dev = c->tail_hint_dev + hint_at;
+  const unsigned hint_tag = hist.tag & 0xffu;
+  const size_t hint_at = 16 * (size_t)(c->lane->id * ARTP_TAIL_KINDS + tail_kind);
+  unsigned* hint_dev = const_cast<unsigned*>(c->tail_hint.dev()) + hint_at;
   const unsigned rare_waves = (unsigned)grid_full(c, 0);  // one wavefront per workgroup
   bool rare = c->tail_mode == 2;
   if (c->tail_mode == 0 && !fresh) {
-    const unsigned word = c->tail_hint[hint_at];  // whatever is there now: no wait
+    const unsigned word = c->tail_hint.host()[hint_at];  // whatever is there now: no wait
     rare = (word & 0xffu) == hint_tag && (word >> 8) <= rare_waves;
   }
-  c->tail_last[lane_id] = rare ? 2 : 1;
+  c->lane->tail_last = rare ? 2 : 1;
   if (!rare)
-    hipLaunchKernelGGL(feet_lane_kernel, dim3((unsigned)c->n_cus * 8), dim3(ARTP_LANE_THREADS), 0, c->stream,
+    hipLaunchKernelGGL(feet_lane_kernel, dim3((unsigned)c->n_cus * 8), dim3(ARTP_LANE_THREADS), 0, c->lane->stream,
                        c->field[1], c->robot, q, valid);
   {
     // streaming pass: no LDS at all; the staged pass behind it takes the window tile and the list
     const ScratchCaps caps_stream{0, 0, 0, 0};
     const size_t lds_stream = 0;
     hipLaunchKernelGGL((resolve_boxes_kernel<ARTP_WAVES_PER_BLOCK, 64, 0>), dim3(grid_sub(c, ARTP_TORSO_WGS_PER_CU)),
-                       dim3(64 * ARTP_WAVES_PER_BLOCK), lds_stream, c->stream, c->field[0], c->robot, q, valid,
-                       caps_stream, c->d_error, c->tables[0].valid ? c->tables[0].mm : (const float2*)nullptr);
+                       dim3(64 * ARTP_WAVES_PER_BLOCK), lds_stream, c->lane->stream, c->field[0], c->robot, q, valid,
+                       caps_stream, c->lane->d_error.get(), c->tables[0].valid ? c->tables[0].mm : (const float2*)nullptr);
   }
   if (rare) {
-    hipLaunchKernelGGL(rare_boxes_kernel, dim3(rare_waves), dim3(64), lds_full(c), c->stream, c->field[0], c->field[1],
-                       c->robot, q, valid, c->caps_full, c->d_error, hint_dev, hint_tag);
+    hipLaunchKernelGGL(rare_boxes_kernel, dim3(rare_waves), dim3(64), lds_full(c), c->lane->stream, c->field[0], c->field[1],
+                       c->robot, q, valid, c->caps_full, c->lane->d_error.get(), hint_dev, hint_tag);
     HIP_TRY(c, hipGetLastError());
     return ARTP_OK;
   }
   hipLaunchKernelGGL((resolve_boxes_kernel<ARTP_WAVES_PER_BLOCK, 64, 3>), dim3(grid_scan(c, lds_scan(c))),
-                     dim3(64 * ARTP_WAVES_PER_BLOCK), lds_scan(c), c->stream, c->field[0], c->robot, q, valid,
-                     c->caps_scan, c->d_error);
+                     dim3(64 * ARTP_WAVES_PER_BLOCK), lds_scan(c), c->lane->stream, c->field[0], c->robot, q, valid,
+                     c->caps_scan, c->lane->d_error.get());
   hipLaunchKernelGGL((resolve_boxes_kernel<ARTP_WAVES_PER_BLOCK, 16, 1>), dim3(grid_scan(c, lds_feet(c))),
-                     dim3(64 * ARTP_WAVES_PER_BLOCK), lds_feet(c), c->stream, c->field[1], c->robot, q, valid,
-                     c->caps_feet, c->d_error);
+                     dim3(64 * ARTP_WAVES_PER_BLOCK), lds_feet(c), c->lane->stream, c->field[1], c->robot, q, valid,
+                     c->caps_feet, c->lane->d_error.get());
   // list pass: few boxes (dozens on natural terrain), each a long chain -> a whole wavefront per box
   hipLaunchKernelGGL((resolve_boxes_kernel<ARTP_WAVES_PER_BLOCK, 64, 2>), dim3(grid_scan(c, lds_feet_wave(c))),
-                     dim3(64 * ARTP_WAVES_PER_BLOCK), lds_feet_wave(c), c->stream, c->field[1], c->robot, q, valid,
-                     c->caps_feet_wave, c->d_error);
-  hipLaunchKernelGGL(plane_stage_kernel<1>, dim3(grid_full(c, 0)), dim3(64), lds_full(c), c->stream,
-                     c->field[0], c->field[1], c->robot, q, valid, c->caps_full, c->d_error, hint_dev, hint_tag);
+                     dim3(64 * ARTP_WAVES_PER_BLOCK), lds_feet_wave(c), c->lane->stream, c->field[1], c->robot, q, valid,
+                     c->caps_feet_wave, c->lane->d_error.get());
+  hipLaunchKernelGGL(plane_stage_kernel<1>, dim3(grid_full(c, 0)), dim3(64), lds_full(c), c->lane->stream,
+                     c->field[0], c->field[1], c->robot, q, valid, c->caps_full, c->lane->d_error.get(), hint_dev, hint_tag);
   HIP_TRY(c, hipGetLastError());
   return ARTP_OK;
 }
 
 int check_error_flag(artp_ctx* c) {
   int flag = 0;
-  HIP_TRY(c, hipMemcpyAsync(&flag, c->d_error, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipMemcpyAsync(&flag, c->lane->d_error.get(), sizeof(int), hipMemcpyDeviceToHost, c->lane->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->lane->stream));
   if (flag) {
-    HIP_TRY(c, hipMemsetAsync(c->d_error, 0, sizeof(int), c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->lane->d_error.get(), 0, sizeof(int), c->lane->stream));
     c->last_error = "a box window exceeded the LDS tile capacity";
     return ARTP_ERR_CAPACITY;
   }
@@ -806,37 +780,33 @@ const char* artp_device_arch(const artp_ctx* ctx) { return ctx ? ctx->arch.c_str
 // idle / lifetime limits whatever happens).
 static void pool_stop(artp_ctx* c);
 static void svc_stop(artp_ctx* c) {
-  if (!c->svc || !c->svc_launched) return;
-  c->svc->n_quit = 0x100u;
+  if (!c->svc.host() || !c->svc_launched) return;
+  c->svc.host()->n_quit = 0x100u;
   std::atomic_thread_fence(std::memory_order_seq_cst);
   const auto t0 = std::chrono::steady_clock::now();
-  while (c->svc->running && std::chrono::steady_clock::now() - t0 < std::chrono::milliseconds(200))
+  while (c->svc.host()->running && std::chrono::steady_clock::now() - t0 < std::chrono::milliseconds(200))
     ;
   (void)hipStreamSynchronize(c->svc_stream);   // the kernel has returned (at the latest after its lifetime limit)
   c->svc_launched = false;
 }
 
 static int svc_start(artp_ctx* c) {
-  if (!c->svc) {
-    void *p = nullptr, *pd = nullptr;
-    HIP_TRY(c, hipHostMalloc(&p, sizeof(SvcMailbox), hipHostMallocMapped));
-    HIP_TRY(c, hipHostGetDevicePointer(&pd, p, 0));
-    std::memset(p, 0, sizeof(SvcMailbox));
-    c->svc = static_cast<SvcMailbox*>(p);
-    c->svc_dev = static_cast<SvcMailbox*>(pd);
-    HIP_TRY(c, hipStreamCreateWithFlags(&c->svc_stream, hipStreamNonBlocking));
-    HIP_TRY(c, hipEventCreateWithFlags(&c->svc_after_map, hipEventDisableTiming));
+  if (!c->svc.host()) {
+    HIP_TRY(c, c->svc.reserve(sizeof(SvcMailbox), hipHostMallocMapped));
+    std::memset(c->svc.host(), 0, sizeof(SvcMailbox));
   }
+  if (!c->svc_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->svc_stream, hipStreamNonBlocking));
+  if (!c->svc_after_map) HIP_TRY(c, hipEventCreateWithFlags(&c->svc_after_map, hipEventDisableTiming));
   // behind every map write already enqueued on the context's stream: the kernel captures the field arguments of NOW
-  HIP_TRY(c, hipEventRecord(c->svc_after_map, c->stream));
+  HIP_TRY(c, hipEventRecord(c->svc_after_map, c->lane->stream));
   HIP_TRY(c, hipStreamWaitEvent(c->svc_stream, c->svc_after_map, 0));
-  c->svc->n_quit = 0u;
-  c->svc->running = 1u;
-  c->svc->resp = c->svc_seq << 8;
-  c->svc->req_seq = c->svc_seq;
+  c->svc.host()->n_quit = 0u;
+  c->svc.host()->running = 1u;
+  c->svc.host()->resp = c->svc_seq << 8;
+  c->svc.host()->req_seq = c->svc_seq;
   std::atomic_thread_fence(std::memory_order_seq_cst);
   hipLaunchKernelGGL(validate_service_kernel, dim3(1), dim3(320), lds_few(c), c->svc_stream, c->field[0], c->field[1], c->geom,
-                     c->robot, c->svc_dev, c->svc_seq, c->caps_full, c->caps_foot_full);
+                     c->robot, c->svc.dev(), c->svc_seq, c->caps_full, c->caps_foot_full);
   HIP_TRY(c, hipGetLastError());
   c->svc_launched = true;
   c->svc_map_version = c->map_version.load(std::memory_order_acquire);
@@ -849,34 +819,31 @@ static int svc_validate(artp_ctx* c, const double* se3, size_t n, uint8_t* valid
   for (int attempt = 0; attempt < 3; ++attempt) {
     const bool stale = c->svc_launched && c->svc_map_version != c->map_version.load(std::memory_order_acquire);
     if (stale) svc_stop(c);                              // a map write since the launch: its field arguments are history
-    if (c->svc_launched && !c->svc->running) {            // it left on its own (idle / lifetime limit)
+    if (c->svc_launched && !c->svc.host()->running) {            // it left on its own (idle / lifetime limit)
       (void)hipStreamSynchronize(c->svc_stream);
       c->svc_launched = false;
     }
-    if (!c->svc_launched) {
-      const int rc = svc_start(c);
-      if (rc) return rc;
-    }
-    if (n > 1) std::memcpy(c->svc->state1, se3 + 7, 7 * sizeof(double));
-    std::memcpy(c->svc->state0, se3, 7 * sizeof(double));
-    c->svc->n_quit = (uint32_t)n;
+    if (!c->svc_launched) ARTP_TRY(svc_start(c));
+    if (n > 1) std::memcpy(c->svc.host()->state1, se3 + 7, 7 * sizeof(double));
+    std::memcpy(c->svc.host()->state0, se3, 7 * sizeof(double));
+    c->svc.host()->n_quit = (uint32_t)n;
     // the state is globally visible before the number, and the number goes out NOW: a full fence on both sides
     std::atomic_thread_fence(std::memory_order_seq_cst);
     const uint32_t seq = ++c->svc_seq;
-    c->svc->req_seq = seq;
+    c->svc.host()->req_seq = seq;
     std::atomic_thread_fence(std::memory_order_seq_cst);
     const auto t0 = std::chrono::steady_clock::now();
     bool answered = false, gone = false;
     for (unsigned spin = 0;; ++spin) {
-      if ((c->svc->resp >> 8) == (seq & 0xffffffu)) { answered = true; break; }
+      if ((c->svc.host()->resp >> 8) == (seq & 0xffffffu)) { answered = true; break; }
       if ((spin & 255u) == 255u) {
-        if (!c->svc->running) { gone = true; break; }     // it left between our check and our request: start it again
+        if (!c->svc.host()->running) { gone = true; break; }     // it left between our check and our request: start it again
         if (std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(50)) break;
       }
     }
-    if (!answered && gone && (c->svc->resp >> 8) == (seq & 0xffffffu)) answered = true;   // it answered in its last breath
+    if (!answered && gone && (c->svc.host()->resp >> 8) == (seq & 0xffffffu)) answered = true;   // it answered in its last breath
     if (answered) {
-      const uint32_t r = c->svc->resp;   // one word: the labels came with the number
+      const uint32_t r = c->svc.host()->resp;   // one word: the labels came with the number
       bool overflow = false;
       for (size_t i = 0; i < n; ++i) {
         const unsigned b = (r >> (2 * i)) & 3u;
@@ -960,81 +927,41 @@ int artp_create(int device, const artp_params* params, artp_ctx** out) {
   }
   c->arch = prop.gcnArchName;
   c->n_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  if (hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) != hipSuccess ||
-      hipMalloc(&c->d_error, sizeof(int)) != hipSuccess ||
-      hipMalloc(&c->d_count, sizeof(unsigned long long)) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void**>(&c->d_diff), 8 * sizeof(int)) != hipSuccess ||
-      hipMemset(c->d_error, 0, sizeof(int)) != hipSuccess) {
+  // Whatever fails from here on, artp_destroy takes what exists.  The mapped blocks: the states and labels of the few-state
+  // path, the edges of a call (host -> device) in a block of their own apart from the polled results, the tail hints.
+  // Plain coherent mapped memory: a non-coherent mapping (L2-cacheable for the length of a kernel, so that only the first
+  // workgroup's read of an edge crosses PCIe) was measured -- no difference at any call size -- and is not worth a second
+  // coherence rule.
+  const std::vector<FewEdgeSync> armed(ARTP_FEW_EDGES, FewEdgeSync{0xffffffffu, 0u, 0u, {0u}});
+  const size_t states_bytes = ARTP_FEW_STATES * 7 * sizeof(double), edges_in_bytes = 2 * ARTP_FEW_EDGES * 7 * sizeof(double);
+  const size_t sync_bytes = armed.size() * sizeof(FewEdgeSync);
+  const size_t hint_bytes = ARTP_MAX_LANES * ARTP_TAIL_KINDS * 16 * sizeof(unsigned);
+  const auto build = [&]() -> int {
+    ARTP_TRY(init_lane(c, 0));
+    HIP_TRY(c, c->d_diff.reserve(8 * sizeof(int)));
+    HIP_TRY(c, c->pin_states.reserve(states_bytes, hipHostMallocMapped));
+    HIP_TRY(c, c->pin_labels.reserve(64, hipHostMallocMapped));
+    HIP_TRY(c, c->pin_edges_in.reserve(edges_in_bytes, hipHostMallocMapped));
+    HIP_TRY(c, c->pin_edges.reserve(FEW_EDGE_BLOCK_BYTES, hipHostMallocMapped));
+    HIP_TRY(c, c->d_few_sync.reserve(sync_bytes));
+    HIP_TRY(c, hipMemcpy(c->d_few_sync.get(), armed.data(), sync_bytes, hipMemcpyHostToDevice));
+    HIP_TRY(c, c->tail_hint.reserve(hint_bytes, hipHostMallocMapped));
+    std::memset(const_cast<unsigned*>(c->tail_hint.host()), 0xff, hint_bytes);  // no call has left a count yet
+    return ARTP_OK;
+  };
+  if (build() != ARTP_OK) {
     artp_destroy(c);
     return ARTP_ERR_HIP;
   }
-  c->stream = c->own_stream;
-  {
-    void *ps = nullptr, *pl = nullptr, *psd = nullptr, *pld = nullptr;
-    if (hipHostMalloc(&ps, ARTP_FEW_STATES * 7 * sizeof(double), hipHostMallocMapped) != hipSuccess ||
-        hipHostMalloc(&pl, 64, hipHostMallocMapped) != hipSuccess ||
-        hipHostGetDevicePointer(&psd, ps, 0) != hipSuccess || hipHostGetDevicePointer(&pld, pl, 0) != hipSuccess) {
-      if (ps) (void)hipHostFree(ps);
-      if (pl) (void)hipHostFree(pl);
-      artp_destroy(c);
-      return ARTP_ERR_HIP;
-    }
-    {
-      void *pe = nullptr, *ped = nullptr;
-      std::vector<FewEdgeSync> armed(ARTP_FEW_EDGES, FewEdgeSync{0xffffffffu, 0u, 0u, {0u}});
-      void *pi = nullptr, *pid = nullptr;
-      // the edges (host -> device) in a block of their own, apart from the polled results.  Plain coherent mapped memory:
-      // a non-coherent mapping (L2-cacheable for the length of a kernel, so that only the first workgroup's read of an
-      // edge crosses PCIe) was measured -- no difference at any call size -- and is not worth a second coherence rule.
-      if (hipHostMalloc(&pi, 2 * ARTP_FEW_EDGES * 7 * sizeof(double), hipHostMallocMapped) == hipSuccess &&
-          hipHostGetDevicePointer(&pid, pi, 0) == hipSuccess) {
-        c->pin_edges_in = static_cast<char*>(pi);
-        c->pin_edges_in_dev = static_cast<char*>(pid);
-      } else if (pi) {
-        (void)hipHostFree(pi);
-      }
-      if (!c->pin_edges_in ||
-          hipHostMalloc(&pe, FEW_EDGE_BLOCK_BYTES, hipHostMallocMapped) != hipSuccess ||
-          hipHostGetDevicePointer(&ped, pe, 0) != hipSuccess ||
-          hipMalloc(reinterpret_cast<void**>(&c->d_few_sync), ARTP_FEW_EDGES * sizeof(FewEdgeSync)) != hipSuccess ||
-          hipMemcpy(c->d_few_sync, armed.data(), ARTP_FEW_EDGES * sizeof(FewEdgeSync), hipMemcpyHostToDevice) != hipSuccess) {
-        if (pe) (void)hipHostFree(pe);
-        (void)hipHostFree(ps);
-        (void)hipHostFree(pl);
-        artp_destroy(c);
-        return ARTP_ERR_HIP;
-      }
-      c->pin_edges = static_cast<char*>(pe);
-      c->pin_edges_dev = static_cast<char*>(ped);
-    }
-    {
-      void *ph = nullptr, *phd = nullptr;
-      if (hipHostMalloc(&ph, ARTP_MAX_LANES * ARTP_TAIL_KINDS * 16 * sizeof(unsigned), hipHostMallocMapped) != hipSuccess ||
-          hipHostGetDevicePointer(&phd, ph, 0) != hipSuccess) {
-        if (ph) (void)hipHostFree(ph);
-        (void)hipHostFree(ps);
-        (void)hipHostFree(pl);
-        artp_destroy(c);
-        return ARTP_ERR_HIP;
-      }
-      std::memset(ph, 0xff, ARTP_MAX_LANES * ARTP_TAIL_KINDS * 16 * sizeof(unsigned));  // no call has left a count yet
-      c->tail_hint = static_cast<volatile unsigned*>(ph);
-      c->tail_hint_dev = static_cast<unsigned*>(phd);
-    }
-    c->pin_states = static_cast<double*>(ps);
-    c->pin_labels = static_cast<volatile uint8_t*>(pl);
-    c->pin_states_dev = static_cast<double*>(psd);
-    c->pin_labels_dev = static_cast<uint8_t*>(pld);
-    const char* e = std::getenv("ARTP_NO_POLL");   // one of the library's three environment variables (include/artp_c.h)
-    c->poll_labels = !(e && e[0] == '1');
+  const char* e = std::getenv("ARTP_NO_POLL");   // one of the library's three environment variables (include/artp_c.h)
+  c->poll_labels = !(e && e[0] == '1');
 #ifdef ARTP_VARIANTS
-    if (const char* fd = std::getenv("ARTP_FEET_DENSE")) c->feet_dense = fd[0] != '0';
-    if (const char* pw = std::getenv("ARTP_POOL_WGS")) {
-      const long v = std::strtol(pw, nullptr, 10);
-      if (v >= 1 && v <= ARTP_POOL_MAX_WGS) c->pool_wgs = (unsigned)v;
-    }
-#endif
+  if (const char* fd = std::getenv("ARTP_FEET_DENSE")) c->feet_dense = fd[0] != '0';
+  if (const char* pw = std::getenv("ARTP_POOL_WGS")) {
+    const long v = std::strtol(pw, nullptr, 10);
+    if (v >= 1 && v <= ARTP_POOL_MAX_WGS) c->pool_wgs = (unsigned)v;
   }
+#endif
   fill_robot(c);
   *out = c;
   return ARTP_OK;
@@ -1045,78 +972,26 @@ void artp_destroy(artp_ctx* c) {
   (void)hipSetDevice(c->device);
   svc_stop(c);   // the resident latency workgroups (if any) leave before anything they read is freed
   pool_stop(c);
-  park_lane(c);
   for (auto& l : c->lanes)
     if (l.init && l.stream) (void)hipStreamSynchronize(l.stream);
-  for (int s = 0; s < 2; ++s)
-    if (c->field_data[s]) (void)hipFree(c->field_data[s]);
-  if (c->sampler_buf) (void)hipFree(c->sampler_buf);
-  if (c->sampler_pack) (void)hipFree(c->sampler_pack);
-  if (c->rect_stage_host) (void)hipHostFree(c->rect_stage_host);
-  if (c->rect_stage_dev) (void)hipFree(c->rect_stage_dev);
-  if (c->rect_stage_done) (void)hipEventDestroy(c->rect_stage_done);
-  if (c->map_written) (void)hipEventDestroy(c->map_written);
-  for (auto& e : c->lane_mark)
-    if (e) (void)hipEventDestroy(e);
   for (auto& l : c->lanes) {
-    if (!l.init) continue;
-    for (int s = 0; s < 8; ++s)
-      if (l.tmp[s]) (void)hipFree(l.tmp[s]);
-    if (l.cub_tmp) (void)hipFree(l.cub_tmp);
-    if (l.d_count) (void)hipFree(l.d_count);
-    if (l.d_error) (void)hipFree(l.d_error);
     if (l.own_stream) (void)hipStreamDestroy(l.own_stream);
+    if (l.lane_mark) (void)hipEventDestroy(l.lane_mark);
   }
-  for (int s = 0; s < 2; ++s) {
-    if (c->table_buf[s]) (void)hipFree(c->table_buf[s]);
-    if (c->flag_buf[s]) (void)hipFree(c->flag_buf[s]);
-    if (c->stride_buf[s]) (void)hipFree(c->stride_buf[s]);
-    if (c->partner_buf[s]) (void)hipFree(c->partner_buf[s]);
-    if (c->partner_cnt[s]) (void)hipFree(c->partner_cnt[s]);
-    if (c->tri_raw_buf[s]) (void)hipFree(c->tri_raw_buf[s]);
-  }
-  for (int l = 0; l < 5; ++l) {
-    if (c->d_convw[l]) (void)hipFree(c->d_convw[l]);
-    if (c->d_convb[l]) (void)hipFree(c->d_convb[l]);
-  }
-  for (int32_t* p : c->clear_offs)
-    if (p) (void)hipFree(p);
-  if (c->d_fc) (void)hipFree(c->d_fc);
-  if (c->d_fc_mfma) (void)hipFree(c->d_fc_mfma);
-  if (c->d_c12) (void)hipFree(c->d_c12);
-  if (c->d_c12m) (void)hipFree(c->d_c12m);
-  for (int l = 0; l < 3; ++l)
-    if (c->d_convw_chunk[l]) (void)hipFree(c->d_convw_chunk[l]);
-  if (c->d_convw_p32) (void)hipFree(c->d_convw_p32);
-  for (int l = 0; l < 2; ++l)
-    if (c->d_act[l]) (void)hipFree(c->d_act[l]);
-  if (c->d_feat) (void)hipFree(c->d_feat);
-  if (c->d_map_f32) (void)hipFree(c->d_map_f32);
-  if (c->d_diff) (void)hipFree(c->d_diff);
-  if (c->svc) (void)hipHostFree(c->svc);
-  if (c->svc_stream) (void)hipStreamDestroy(c->svc_stream);
-  if (c->svc_after_map) (void)hipEventDestroy(c->svc_after_map);
-  if (c->pool_stream) (void)hipStreamDestroy(c->pool_stream);
-  if (c->pool_after_map) (void)hipEventDestroy(c->pool_after_map);
-  if (c->pool_mb) (void)hipFree(c->pool_mb);
-  if (c->pool_resp) (void)hipHostFree(c->pool_resp);
-  if (c->pool_ctl) (void)hipFree(c->pool_ctl);
-  if (c->pin_edges) (void)hipHostFree(c->pin_edges);
-  if (c->pin_edges_in) (void)hipHostFree(c->pin_edges_in);
-  if (c->d_few_sync) (void)hipFree(c->d_few_sync);
-  if (c->tail_hint) (void)hipHostFree(const_cast<unsigned*>(c->tail_hint));
-  if (c->pin_states) (void)hipHostFree(c->pin_states);
-  if (c->pin_labels) (void)hipHostFree(const_cast<uint8_t*>(c->pin_labels));
-  delete c;  // d_error / d_count of every lane went with the lanes above
+  for (hipStream_t st : {c->svc_stream, c->pool_stream})
+    if (st) (void)hipStreamDestroy(st);
+  for (hipEvent_t ev : {c->rect_stage_done, c->map_written, c->svc_after_map, c->pool_after_map})
+    if (ev) (void)hipEventDestroy(ev);
+  delete c;  // every buffer goes with its owner: the device is set, nothing runs any more
 }
 
 int artp_set_stream(artp_ctx* c, void* hip_stream) {
   if (!c) return ARTP_ERR_INVALID_ARG;
   std::lock_guard<std::recursive_mutex> lock(c->mu);
-  c->stream = static_cast<hipStream_t>(hip_stream);  // NULL = HIP's legacy default stream
+  c->lane->stream = static_cast<hipStream_t>(hip_stream);  // NULL = HIP's legacy default stream
   if (c->map_written) {  // a stream this context has not used before: order it behind the last map write
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamWaitEvent(c->stream, c->map_written, 0));
+    HIP_TRY(c, hipStreamWaitEvent(c->lane->stream, c->map_written, 0));
   }
   return ARTP_OK;
 }
@@ -1124,10 +999,10 @@ int artp_set_stream(artp_ctx* c, void* hip_stream) {
 int artp_use_own_stream(artp_ctx* c) {
   if (!c) return ARTP_ERR_INVALID_ARG;
   std::lock_guard<std::recursive_mutex> lock(c->mu);
-  c->stream = c->own_stream;
+  c->lane->stream = c->lane->own_stream;
   if (c->map_written) {
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamWaitEvent(c->stream, c->map_written, 0));
+    HIP_TRY(c, hipStreamWaitEvent(c->lane->stream, c->map_written, 0));
   }
   return ARTP_OK;
 }
@@ -1136,38 +1011,23 @@ int artp_synchronize(artp_ctx* c) {
   if (!c) return ARTP_ERR_INVALID_ARG;
   std::lock_guard<std::recursive_mutex> lock(c->mu);
   HIP_TRY(c, hipSetDevice(c->device));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  for (int l = 0; l < ARTP_MAX_LANES; ++l)
-    if (l != c->cur_lane && c->lanes[l].init) HIP_TRY(c, hipStreamSynchronize(c->lanes[l].stream));
+  HIP_TRY(c, hipStreamSynchronize(c->lane->stream));
+  for (lane_state& l : c->lanes)
+    if (&l != c->lane && l.init) HIP_TRY(c, hipStreamSynchronize(l.stream));
   return ARTP_OK;
 }
 
 int artp_set_lane(artp_ctx* c, int lane) {
   if (!c || lane < 0 || lane >= ARTP_MAX_LANES) return ARTP_ERR_INVALID_ARG;
   std::lock_guard<std::recursive_mutex> lock(c->mu);
-  if (lane == c->cur_lane) return ARTP_OK;
+  if (lane == c->lane->id) return ARTP_OK;
   HIP_TRY(c, hipSetDevice(c->device));
-  if (!c->lanes[lane].init) {
-    artp_ctx::lane_state l;
-    HIP_TRY(c, hipStreamCreateWithFlags(&l.own_stream, hipStreamNonBlocking));
-    if (hipMalloc(&l.d_count, sizeof(unsigned long long)) != hipSuccess ||
-        hipMalloc(&l.d_error, sizeof(int)) != hipSuccess || hipMemset(l.d_error, 0, sizeof(int)) != hipSuccess) {
-      if (l.d_count) (void)hipFree(l.d_count);
-      if (l.d_error) (void)hipFree(l.d_error);
-      (void)hipStreamDestroy(l.own_stream);
-      c->last_error = "hipMalloc failed (lane counters)";
-      return ARTP_ERR_HIP;
-    }
-    l.stream = l.own_stream;
-    l.init = true;
-    c->lanes[lane] = l;
-  }
-  park_lane(c);
-  unpark_lane(c, lane);
+  ARTP_TRY(init_lane(c, lane));
+  c->lane = &c->lanes[lane];
   return lane_sees_map(c);
 }
 
-int artp_get_lane(artp_ctx* c) { return c ? c->cur_lane : -1; }
+int artp_get_lane(artp_ctx* c) { return c ? c->lane->id : -1; }
 
 uint64_t artp_map_version(const artp_ctx* c) { return c ? c->map_version.load(std::memory_order_acquire) : 0; }
 
@@ -1228,7 +1088,7 @@ int finish_layer(artp_ctx* c, int slot, int rows, int cols, double len_x, double
                  int has_nan, int has_nonfinite) {
   c->layer_has_nonfinite[slot] = has_nonfinite;
   FieldDev& f = c->field[slot];
-  f.data = c->field_data[slot];
+  f.data = c->field_data[slot].get();
   // dxHeightfieldData::SetData (ode/ode/src/heightfield.cpp:130-169), single precision
   f.nW = rows;
   f.nD = cols;
@@ -1267,24 +1127,16 @@ int finish_layer(artp_ctx* c, int slot, int rows, int cols, double len_x, double
   c->geom.cols = cols;
   c->geom.res = len_x / rows;
   c->have_geom = true;
-  int rc = size_scratch(c);
-  if (rc != ARTP_OK) return rc;
-  rc = set_kernel_lds(c);
-  if (rc != ARTP_OK) return rc;
+  ARTP_TRY(size_scratch(c));
+  ARTP_TRY(set_kernel_lds(c));
   c->map_version.fetch_add(1, std::memory_order_release);  // even when the tables fail: the samples did change
-  rc = build_tables(c, slot);
-  if (rc != ARTP_OK) return rc;
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  ARTP_TRY(build_tables(c, slot));
+  HIP_TRY(c, hipStreamSynchronize(c->lane->stream));
   return ARTP_OK;
 }
 
 int ensure_field_storage(artp_ctx* c, int slot, size_t elems) {
-  if (c->field_elems[slot] < elems) {
-    if (c->field_data[slot]) HIP_TRY(c, hipFree(c->field_data[slot]));
-    c->field_data[slot] = nullptr;
-    HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->field_data[slot]), elems * sizeof(float)));
-    c->field_elems[slot] = elems;
-  }
+  HIP_TRY(c, c->field_data[slot].reserve(elems * sizeof(float)));
   return ARTP_OK;
 }
 
@@ -1307,15 +1159,12 @@ int artp_upload_layer(artp_ctx* c, int slot, const float* layer, int rows, int c
       has_nan |= (v != v);
       has_nonfinite |= !std::isfinite(v);
     }
-  int rc = order_after_other_lanes(c);  // lanes that still validate on the old samples
-  if (rc != ARTP_OK) return rc;
-  rc = ensure_field_storage(c, slot, elems);
-  if (rc != ARTP_OK) return rc;
-  HIP_TRY(c, hipMemcpyAsync(c->field_data[slot], host.data(), elems * sizeof(float),
-                            hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  rc = finish_layer(c, slot, rows, cols, len_x, len_y, pos_x, pos_y, has_nan, has_nonfinite);
-  if (rc != ARTP_OK) return rc;
+  ARTP_TRY(order_after_other_lanes(c));  // lanes that still validate on the old samples
+  ARTP_TRY(ensure_field_storage(c, slot, elems));
+  HIP_TRY(c, hipMemcpyAsync(c->field_data[slot].get(), host.data(), elems * sizeof(float),
+                            hipMemcpyHostToDevice, c->lane->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->lane->stream));
+  ARTP_TRY(finish_layer(c, slot, rows, cols, len_x, len_y, pos_x, pos_y, has_nan, has_nonfinite));
   return publish_map_write(c);
 }
 
@@ -1376,50 +1225,43 @@ static int upload_layer_from_device(artp_ctx* c, int slot, const float* d_layer,
                           f0.pos[1] == (float)pos_y;
   const bool same_geometry = c->have_field[slot] && c->have_geom && f0.nW == rows && f0.nD == cols && same_frame &&
                              c->geom.len_x == len_x && c->geom.len_y == len_y && c->geom.pos_x == pos_x &&
-                             c->geom.pos_y == pos_y && c->tables[slot].valid && c->field_elems[slot] >= elems;
-  {
-    const int rco = order_after_other_lanes(c);
-    if (rco != ARTP_OK) return rco;
-  }
+                             c->geom.pos_y == pos_y && c->tables[slot].valid && c->field_data[slot].capacity() >= elems * sizeof(float);
+  ARTP_TRY(order_after_other_lanes(c));
   if (same_geometry) {
     int init[6] = {0x7fffffff, 0x7fffffff, -1, -1, 0, 0}, got[6];
-    int* d_out = reinterpret_cast<int*>(c->d_diff);
-    HIP_TRY(c, hipMemcpyAsync(d_out, init, sizeof(init), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(layer_diff_kernel, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, c->stream, d_layer, rows, cols,
-                       (const float*)c->field_data[slot], d_out);
+    int* d_out = reinterpret_cast<int*>(c->d_diff.get());
+    HIP_TRY(c, hipMemcpyAsync(d_out, init, sizeof(init), hipMemcpyHostToDevice, c->lane->stream));
+    hipLaunchKernelGGL(layer_diff_kernel, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, c->lane->stream, d_layer, rows, cols,
+                       (const float*)c->field_data[slot].get(), d_out);
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(got, d_out, sizeof(got), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpyAsync(got, d_out, sizeof(got), hipMemcpyDeviceToHost, c->lane->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->lane->stream));
     if (got[0] > got[2]) return ARTP_OK;  // bit-identical: the installed layer and its tables stand
     const int nx = got[2] - got[0] + 1, nz = got[3] - got[1] + 1;
     if ((size_t)nx * nz * 4 <= elems) {
       c->map_version.fetch_add(1, std::memory_order_release);
       const int dirty[4] = {got[0], got[1], got[2], got[3]};
       PartnerRects pr;
-      int rc = partner_update_begin(c, slot, dirty, 1, &pr);  // the old triangles' contributions: before the copy
-      if (rc != ARTP_OK) return rc;
-      hipLaunchKernelGGL(copy_rect_to_ode_layout_kernel, dim3((unsigned)((nx * nz + 255) / 256)), dim3(256), 0, c->stream,
-                         d_layer, rows, cols, got[0], got[1], nx, nz, c->field_data[slot]);
+      ARTP_TRY(partner_update_begin(c, slot, dirty, 1, &pr));  // the old triangles' contributions: before the copy
+      hipLaunchKernelGGL(copy_rect_to_ode_layout_kernel, dim3((unsigned)((nx * nz + 255) / 256)), dim3(256), 0, c->lane->stream,
+                         d_layer, rows, cols, got[0], got[1], nx, nz, c->field_data[slot].get());
       HIP_TRY(c, hipGetLastError());
       c->field[slot].has_nan = got[5];          // exact: the flags are those of the whole new layer
       c->layer_has_nonfinite[slot] = got[4];
-      rc = build_tables(c, slot, &pr);
-      if (rc != ARTP_OK) return rc;
+      ARTP_TRY(build_tables(c, slot, &pr));
       return publish_map_write(c);  // asynchronous like the rectangle updates: the other lanes wait on the device
     }
   }
-  int rc = ensure_field_storage(c, slot, elems);
-  if (rc != ARTP_OK) return rc;
-  HIP_TRY(c, hipMemsetAsync(c->d_count, 0, sizeof(unsigned long long), c->stream));
-  int* d_flags = reinterpret_cast<int*>(c->d_count);
-  hipLaunchKernelGGL(flip_to_ode_layout_kernel, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, c->stream, d_layer,
-                     rows, cols, c->field_data[slot], d_flags);
+  ARTP_TRY(ensure_field_storage(c, slot, elems));
+  HIP_TRY(c, hipMemsetAsync(c->lane->d_count.get(), 0, sizeof(unsigned long long), c->lane->stream));
+  int* d_flags = reinterpret_cast<int*>(c->lane->d_count.get());
+  hipLaunchKernelGGL(flip_to_ode_layout_kernel, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, c->lane->stream, d_layer,
+                     rows, cols, c->field_data[slot].get(), d_flags);
   HIP_TRY(c, hipGetLastError());
   int flags[2] = {0, 0};
-  HIP_TRY(c, hipMemcpyAsync(flags, d_flags, sizeof(flags), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  rc = finish_layer(c, slot, rows, cols, len_x, len_y, pos_x, pos_y, flags[1], flags[0]);
-  if (rc != ARTP_OK) return rc;
+  HIP_TRY(c, hipMemcpyAsync(flags, d_flags, sizeof(flags), hipMemcpyDeviceToHost, c->lane->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->lane->stream));
+  ARTP_TRY(finish_layer(c, slot, rows, cols, len_x, len_y, pos_x, pos_y, flags[1], flags[0]));
   return publish_map_write(c);
 }
 
@@ -1466,34 +1308,26 @@ int artp_update_layer_rects(artp_ctx* c, int slot, int n_rects, const float* con
     max_cells = std::max(max_cells, nrows * ncols);
   }
   HIP_TRY(c, hipSetDevice(c->device));
-  {
-    const int rco = order_after_other_lanes(c);
-    if (rco != ARTP_OK) return rco;
-  }
+  ARTP_TRY(order_after_other_lanes(c));
   c->map_version.fetch_add(1, std::memory_order_release);
   // staging: pinned host buffer (patches + rectangle records), reused once the previous update's copy is done
   const size_t rec_bytes = ((size_t)n_rects * sizeof(RectDev) + 15) & ~(size_t)15;
   const size_t need = rec_bytes + total * sizeof(float);
-  if (c->rect_stage_cap < need) {
-    if (c->rect_stage_host) {
-      HIP_TRY(c, hipEventSynchronize(c->rect_stage_done));
-      HIP_TRY(c, hipHostFree(c->rect_stage_host));
-      HIP_TRY(c, hipFree(c->rect_stage_dev));
-    } else {
-      HIP_TRY(c, hipEventCreateWithFlags(&c->rect_stage_done, hipEventDisableTiming));
-    }
-    c->rect_stage_host = nullptr;
-    c->rect_stage_dev = nullptr;
-    c->rect_stage_cap = 0;
-    const size_t cap = need * 2;
-    HIP_TRY(c, hipHostMalloc(&c->rect_stage_host, cap, hipHostMallocDefault));
-    HIP_TRY(c, hipMalloc(&c->rect_stage_dev, cap));
-    c->rect_stage_cap = cap;
-  } else {
+  // (the first update has no copy to wait for: it makes the event)
+  if (c->rect_stage_done)
     HIP_TRY(c, hipEventSynchronize(c->rect_stage_done));
+  else
+    HIP_TRY(c, hipEventCreateWithFlags(&c->rect_stage_done, hipEventDisableTiming));
+  // The pair is one staging area: both blocks always hold the same capacity, twice the need that last grew them.  They
+  // go and come back together; the second test only matters after a failed allocation left one of them empty.
+  if (c->rect_stage_host.capacity() < need || c->rect_stage_dev.capacity() < need) {
+    HIP_TRY(c, c->rect_stage_host.reset());
+    HIP_TRY(c, c->rect_stage_dev.reset());
+    HIP_TRY(c, c->rect_stage_host.reserve(need * 2, hipHostMallocDefault));
+    HIP_TRY(c, c->rect_stage_dev.reserve(need * 2));
   }
-  RectDev* h_rec = static_cast<RectDev*>(c->rect_stage_host);
-  float* h_pat = reinterpret_cast<float*>(static_cast<char*>(c->rect_stage_host) + rec_bytes);
+  RectDev* h_rec = static_cast<RectDev*>(c->rect_stage_host.host());
+  float* h_pat = reinterpret_cast<float*>(static_cast<char*>(c->rect_stage_host.host()) + rec_bytes);
   int has_nan = c->field[slot].has_nan, has_nonfinite = c->layer_has_nonfinite[slot];
   size_t off = 0;
   for (int k = 0; k < n_rects; ++k) {
@@ -1523,24 +1357,18 @@ int artp_update_layer_rects(artp_ctx* c, int slot, int n_rects, const float* con
     dirty[4 * k + 3] = cols - 1 - col0;
   }
   PartnerRects pr;
-  {
-    const int rcp = partner_update_begin(c, slot, dirty.data(), n_rects, &pr);
-    if (rcp != ARTP_OK) return rcp;
-  }
-  HIP_TRY(c, hipMemcpyAsync(c->rect_stage_dev, c->rect_stage_host, need, hipMemcpyHostToDevice, c->stream));
-  hipLaunchKernelGGL(scatter_rects_kernel, dim3((unsigned)((max_cells + 255) / 256), (unsigned)n_rects), dim3(256), 0, c->stream,
-                     reinterpret_cast<const float*>(static_cast<const char*>(c->rect_stage_dev) + rec_bytes),
-                     static_cast<const RectDev*>(c->rect_stage_dev), n_rects, rows, cols, c->field_data[slot]);
+  ARTP_TRY(partner_update_begin(c, slot, dirty.data(), n_rects, &pr));
+  HIP_TRY(c, hipMemcpyAsync(c->rect_stage_dev.get(), c->rect_stage_host.host(), need, hipMemcpyHostToDevice, c->lane->stream));
+  hipLaunchKernelGGL(scatter_rects_kernel, dim3((unsigned)((max_cells + 255) / 256), (unsigned)n_rects), dim3(256), 0, c->lane->stream,
+                     reinterpret_cast<const float*>(static_cast<const char*>(c->rect_stage_dev.get()) + rec_bytes),
+                     static_cast<const RectDev*>(c->rect_stage_dev.get()), n_rects, rows, cols, c->field_data[slot].get());
   HIP_TRY(c, hipGetLastError());
   // both staging buffers are free again once the scatter has run: the next update (whatever stream the context is on
   // by then) waits for this event before it touches them
-  HIP_TRY(c, hipEventRecord(c->rect_stage_done, c->stream));
+  HIP_TRY(c, hipEventRecord(c->rect_stage_done, c->lane->stream));
   // range / stride tables once (the whole map is ~1 MB: rebuilding beats tracking dirty blocks); the partner table,
   // step 2: the new triangles' contributions and a recount of the changed cells
-  {
-    const int rct = build_tables(c, slot, &pr);
-    if (rct != ARTP_OK) return rct;
-  }
+  ARTP_TRY(build_tables(c, slot, &pr));
   // the call returns with the device work queued: launches on the context's OTHER lanes are ordered behind it on the
   // device (map_written), this lane's by stream order
   return publish_map_write(c);
@@ -1558,9 +1386,9 @@ int artp_check_boxes_dev(artp_ctx* c, int slot, const float box[3], const float*
   if (!c->have_field[slot]) return ARTP_ERR_NO_MAP;
   if (n == 0) return ARTP_OK;
   HIP_TRY(c, hipSetDevice(c->device));
-  hipLaunchKernelGGL(check_boxes_kernel<1>, dim3(grid_full(c, n)), dim3(64), lds_full(c), c->stream,
+  hipLaunchKernelGGL(check_boxes_kernel<1>, dim3(grid_full(c, n)), dim3(64), lds_full(c), c->lane->stream,
                      c->field[slot], box[0], box[1], box[2], dposes, n, hit, exit_codes, c->caps_full,
-                     c->d_error);
+                     c->lane->d_error.get());
   HIP_TRY(c, hipGetLastError());
   return ARTP_OK;
 }
@@ -1569,21 +1397,18 @@ int artp_check_boxes(artp_ctx* c, int slot, const float box[3], const float* dpo
                      uint8_t* hit, uint8_t* exit_codes) {
   if (!c || (n && (!dposes || !hit))) return ARTP_ERR_INVALID_ARG;
   if (n == 0) return ARTP_OK;
-  // one lock for the whole call: the staging buffers c->tmp[0..1] are shared by every host entry point
+  // one lock for the whole call: the staging buffers host_args / host_results are shared by every host entry point
   std::lock_guard<std::recursive_mutex> lock(c->mu);
   HIP_TRY(c, hipSetDevice(c->device));
-  int rc = ensure_tmp(c, 0, n * 16 * sizeof(float));
-  if (rc) return rc;
-  rc = ensure_tmp(c, 1, n * 2);
-  if (rc) return rc;
-  HIP_TRY(c, hipMemcpyAsync(c->tmp[0], dposes, n * 16 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-  uint8_t* d_hit = static_cast<uint8_t*>(c->tmp[1]);
+  ARTP_TRY(ensure_scratch(c, c->lane->host_args, n * 16 * sizeof(float)));
+  ARTP_TRY(ensure_scratch(c, c->lane->host_results, n * 2));
+  HIP_TRY(c, hipMemcpyAsync(c->lane->host_args.get(), dposes, n * 16 * sizeof(float), hipMemcpyHostToDevice, c->lane->stream));
+  uint8_t* d_hit = c->lane->host_results.as<uint8_t>();
   uint8_t* d_ec = d_hit + n;
-  rc = artp_check_boxes_dev(c, slot, box, static_cast<const float*>(c->tmp[0]), n, d_hit,
-                            exit_codes ? d_ec : nullptr);
-  if (rc) return rc;
-  HIP_TRY(c, hipMemcpyAsync(hit, d_hit, n, hipMemcpyDeviceToHost, c->stream));
-  if (exit_codes) HIP_TRY(c, hipMemcpyAsync(exit_codes, d_ec, n, hipMemcpyDeviceToHost, c->stream));
+  ARTP_TRY(artp_check_boxes_dev(c, slot, box, c->lane->host_args.as<const float>(), n, d_hit,
+                            exit_codes ? d_ec : nullptr));
+  HIP_TRY(c, hipMemcpyAsync(hit, d_hit, n, hipMemcpyDeviceToHost, c->lane->stream));
+  if (exit_codes) HIP_TRY(c, hipMemcpyAsync(exit_codes, d_ec, n, hipMemcpyDeviceToHost, c->lane->stream));
   return check_error_flag(c);
 }
 
@@ -1596,16 +1421,16 @@ int artp_validate_states_dev(artp_ctx* c, const double* se3, size_t n, uint8_t* 
   if (!detail && n <= ARTP_FEW_STATES) {
     // tiny batches (the per-state isValid() of the host mirror): ONE launch, one workgroup per state with the
     // five boxes side by side; the labels are the same by construction (both are pinned to the oracle)
-    hipLaunchKernelGGL(validate_few_kernel, dim3((unsigned)n), dim3(320), lds_few(c), c->stream, c->field[0],
-                       c->field[1], c->geom, c->robot, se3, n, valid, c->caps_full, c->caps_foot_full, c->d_error, 0u);
+    hipLaunchKernelGGL(validate_few_kernel, dim3((unsigned)n), dim3(320), lds_few(c), c->lane->stream, c->field[0],
+                       c->field[1], c->geom, c->robot, se3, n, valid, c->caps_full, c->caps_foot_full, c->lane->d_error.get(), 0u);
     HIP_TRY(c, hipGetLastError());
     return ARTP_OK;
   }
   if (detail) {
     // per-box exit codes in the reference's evaluation order: wave-per-state kernel
-    hipLaunchKernelGGL(validate_states_kernel<1>, dim3(grid_full(c, n)), dim3(64), lds_full(c), c->stream,
+    hipLaunchKernelGGL(validate_states_kernel<1>, dim3(grid_full(c, n)), dim3(64), lds_full(c), c->lane->stream,
                        c->field[0], c->field[1], c->geom, c->robot, se3, n, valid, detail, c->caps_full,
-                       c->d_error, (unsigned long long*)nullptr);
+                       c->lane->d_error.get(), (unsigned long long*)nullptr);
     HIP_TRY(c, hipGetLastError());
     return ARTP_OK;
   }
@@ -1625,29 +1450,29 @@ int artp_validate_states(artp_ctx* c, const double* se3, size_t n, uint8_t* vali
     // the resident workgroup (no launch at all) for the one-state call OMPL makes; it takes its states one after the other,
     // so from three states on the launch with a workgroup per state is the faster one (measured: 4 states 37 us against 17)
     if (c->svc_enabled && n <= ARTP_SVC_MAX_STATES) return svc_validate(c, se3, n, valid);
-    std::memcpy(c->pin_states, se3, n * 7 * sizeof(double));
-    for (size_t i = 0; i < n; ++i) c->pin_labels[i] = 0;
+    std::memcpy(c->pin_states.host(), se3, n * 7 * sizeof(double));
+    for (size_t i = 0; i < n; ++i) c->pin_labels.host()[i] = 0;
     const unsigned tag = 0x80u;
-    hipLaunchKernelGGL(validate_few_kernel, dim3((unsigned)n), dim3(320), lds_few(c), c->stream, c->field[0],
-                       c->field[1], c->geom, c->robot, (const double*)c->pin_states_dev, n,
-                       (volatile uint8_t*)c->pin_labels_dev, c->caps_full, c->caps_foot_full, c->d_error, tag);
+    hipLaunchKernelGGL(validate_few_kernel, dim3((unsigned)n), dim3(320), lds_few(c), c->lane->stream, c->field[0],
+                       c->field[1], c->geom, c->robot, (const double*)c->pin_states.dev(), n,
+                       (volatile uint8_t*)c->pin_labels.dev(), c->caps_full, c->caps_foot_full, c->lane->d_error.get(), tag);
     HIP_TRY(c, hipGetLastError());
     bool done = false;
     if (c->poll_labels) {
       const auto t0 = std::chrono::steady_clock::now();
       for (unsigned spin = 0; !done; ++spin) {
         done = true;
-        for (size_t i = 0; i < n; ++i) done = done && (c->pin_labels[i] & 0x80u);
+        for (size_t i = 0; i < n; ++i) done = done && (c->pin_labels.host()[i] & 0x80u);
         if (!done && (spin & 1023u) == 1023u &&
             std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2))
           break;
       }
     }
-    if (!done) HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (!done) HIP_TRY(c, hipStreamSynchronize(c->lane->stream));
     bool overflow = false;
     for (size_t i = 0; i < n; ++i) {
-      valid[i] = c->pin_labels[i] & 1u;
-      overflow = overflow || (c->pin_labels[i] & 2u);
+      valid[i] = c->pin_labels.host()[i] & 1u;
+      overflow = overflow || (c->pin_labels.host()[i] & 2u);
     }
     if (overflow) {
       c->last_error = "a box window exceeded the LDS tile capacity";
@@ -1655,18 +1480,15 @@ int artp_validate_states(artp_ctx* c, const double* se3, size_t n, uint8_t* vali
     }
     return ARTP_OK;
   }
-  int rc = ensure_tmp(c, 0, n * 7 * sizeof(double));
-  if (rc) return rc;
-  rc = ensure_tmp(c, 1, n * 7);
-  if (rc) return rc;
-  HIP_TRY(c, hipMemcpyAsync(c->tmp[0], se3, n * 7 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  uint8_t* d_valid = static_cast<uint8_t*>(c->tmp[1]);
+  ARTP_TRY(ensure_scratch(c, c->lane->host_args, n * 7 * sizeof(double)));
+  ARTP_TRY(ensure_scratch(c, c->lane->host_results, n * 7));
+  HIP_TRY(c, hipMemcpyAsync(c->lane->host_args.get(), se3, n * 7 * sizeof(double), hipMemcpyHostToDevice, c->lane->stream));
+  uint8_t* d_valid = c->lane->host_results.as<uint8_t>();
   int8_t* d_detail = reinterpret_cast<int8_t*>(d_valid + n);
-  rc = artp_validate_states_dev(c, static_cast<const double*>(c->tmp[0]), n, d_valid,
-                                detail ? d_detail : nullptr);
-  if (rc) return rc;
-  HIP_TRY(c, hipMemcpyAsync(valid, d_valid, n, hipMemcpyDeviceToHost, c->stream));
-  if (detail) HIP_TRY(c, hipMemcpyAsync(detail, d_detail, n * 6, hipMemcpyDeviceToHost, c->stream));
+  ARTP_TRY(artp_validate_states_dev(c, c->lane->host_args.as<const double>(), n, d_valid,
+                                detail ? d_detail : nullptr));
+  HIP_TRY(c, hipMemcpyAsync(valid, d_valid, n, hipMemcpyDeviceToHost, c->lane->stream));
+  if (detail) HIP_TRY(c, hipMemcpyAsync(detail, d_detail, n * 6, hipMemcpyDeviceToHost, c->lane->stream));
   return check_error_flag(c);
 }
 
@@ -1677,21 +1499,20 @@ static int pack_sampler_tables(artp_ctx* c, int rows, int cols);
 // hipFree / hipMalloc per round, and no free that is unordered against another lane still sampling).  On a size
 // change every lane's stream is drained before the old buffers go.
 static int ensure_sampler_storage(artp_ctx* c, int rows, int cols) {
-  if (c->sampler_buf && c->sampler_pack && c->sampler_rows == rows && c->sampler_cols == cols) return ARTP_OK;
+  if (c->sampler_buf.get() && c->sampler_pack.get() && c->sampler_rows == rows && c->sampler_cols == cols) return ARTP_OK;
   const size_t e = (size_t)rows * cols;
   const int npiv = (cols + 15) / 16, pitch = npiv * 16, ppitch = (npiv + 3) & ~3;
   const size_t floats = (size_t)rows * pitch + (size_t)rows * ppitch + 8 * e + 64;
-  for (int l = 0; l < ARTP_MAX_LANES; ++l)
-    if (l != c->cur_lane && c->lanes[l].init) HIP_TRY(c, hipStreamSynchronize(c->lanes[l].stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  for (lane_state& l : c->lanes)
+    if (&l != c->lane && l.init) HIP_TRY(c, hipStreamSynchronize(l.stream));
+  HIP_TRY(c, hipStreamSynchronize(c->lane->stream));
   c->have_sampler = false;
-  if (c->sampler_buf) HIP_TRY(c, hipFree(c->sampler_buf));
-  c->sampler_buf = nullptr;
-  if (c->sampler_pack) HIP_TRY(c, hipFree(c->sampler_pack));
-  c->sampler_pack = nullptr;
   c->sampler_rows = c->sampler_cols = 0;
-  HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->sampler_buf), (6 * e + rows) * sizeof(float)));
-  HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->sampler_pack), floats * sizeof(float)));
+  // another size, larger or smaller: both old buffers go, then both come back at exactly the new size
+  HIP_TRY(c, c->sampler_buf.reset());
+  HIP_TRY(c, c->sampler_pack.reset());
+  HIP_TRY(c, c->sampler_buf.reserve((6 * e + rows) * sizeof(float)));
+  HIP_TRY(c, c->sampler_pack.reserve(floats * sizeof(float)));
   c->sampler_rows = rows;
   c->sampler_cols = cols;
   return ARTP_OK;
@@ -1708,26 +1529,20 @@ int artp_upload_sampler_layers(artp_ctx* c, const float* cum_prob, const float* 
   HIP_TRY(c, hipSetDevice(c->device));
   const size_t e = (size_t)rows * cols;
   c->map_version.fetch_add(1, std::memory_order_release);
-  {
-    const int rcs = ensure_sampler_storage(c, rows, cols);
-    if (rcs != ARTP_OK) return rcs;
-  }
-  float* p = c->sampler_buf;
+  ARTP_TRY(ensure_sampler_storage(c, rows, cols));
+  float* p = c->sampler_buf.get();
   const float* src[6] = {cum_prob, elevation, normal_x, normal_y, normal_z, plane_fit_std_dev};
   const float** dst[6] = {&c->sampler.cum_prob, &c->sampler.elevation, &c->sampler.normal_x,
                           &c->sampler.normal_y, &c->sampler.normal_z, &c->sampler.plane_fit_std_dev};
   for (int k = 0; k < 6; ++k) {
-    HIP_TRY(c, hipMemcpyAsync(p, src[k], e * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(p, src[k], e * sizeof(float), hipMemcpyHostToDevice, c->lane->stream));
     *dst[k] = p;
     p += e;
   }
-  HIP_TRY(c, hipMemcpyAsync(p, cum_prob_rowwise, rows * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(p, cum_prob_rowwise, rows * sizeof(float), hipMemcpyHostToDevice, c->lane->stream));
   c->sampler.cum_prob_rowwise = p;
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  {
-    const int rcp = pack_sampler_tables(c, rows, cols);
-    if (rcp != ARTP_OK) return rcp;
-  }
+  HIP_TRY(c, hipStreamSynchronize(c->lane->stream));
+  ARTP_TRY(pack_sampler_tables(c, rows, cols));
   if (!c->have_geom) {
     c->geom.len_x = len_x; c->geom.len_y = len_y; c->geom.pos_x = pos_x; c->geom.pos_y = pos_y;
     c->geom.rows = rows; c->geom.cols = cols; c->geom.res = len_x / rows;
@@ -1744,20 +1559,20 @@ static int pack_sampler_tables(artp_ctx* c, int rows, int cols) {
   const int npiv = (cols + 15) / 16, pitch = npiv * 16, ppitch = (npiv + 3) & ~3;
   const size_t floats = (size_t)rows * pitch + (size_t)rows * ppitch + 8 * e + 64;
   // storage from ensure_sampler_storage (same size for the same rows x cols)
-  HIP_TRY(c, hipMemsetAsync(c->sampler_pack, 0, floats * sizeof(float), c->stream));
-  float* cells = c->sampler_pack;                       // 8 floats per cell, 32-byte aligned
+  HIP_TRY(c, hipMemsetAsync(c->sampler_pack.get(), 0, floats * sizeof(float), c->lane->stream));
+  float* cells = c->sampler_pack.get();                       // 8 floats per cell, 32-byte aligned
   float* cdf_t = cells + 8 * e;
   float* piv = cdf_t + (size_t)rows * pitch;
   c->sampler.npiv = npiv;
   c->sampler.pitch = pitch;
   c->sampler.ppitch = ppitch;
-  hipLaunchKernelGGL(sampler_pack_kernel, dim3((unsigned)((e + 255) / 256)), dim3(256), 0, c->stream, c->sampler, rows,
+  hipLaunchKernelGGL(sampler_pack_kernel, dim3((unsigned)((e + 255) / 256)), dim3(256), 0, c->lane->stream, c->sampler, rows,
                      cols, cdf_t, piv, reinterpret_cast<float4*>(cells));
   HIP_TRY(c, hipGetLastError());
   c->sampler.cells = reinterpret_cast<const float4*>(cells);
   c->sampler.cum_prob_t = cdf_t;
   c->sampler.pivots = piv;
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->lane->stream));
   return ARTP_OK;
 }
 
@@ -1770,26 +1585,20 @@ static int upload_sampler_layers_from_device(artp_ctx* c, const float* cum_prob,
   HIP_TRY(c, hipSetDevice(c->device));
   const size_t e = (size_t)rows * cols;
   c->map_version.fetch_add(1, std::memory_order_release);
-  {
-    const int rcs = ensure_sampler_storage(c, rows, cols);
-    if (rcs != ARTP_OK) return rcs;
-  }
-  float* p = c->sampler_buf;
+  ARTP_TRY(ensure_sampler_storage(c, rows, cols));
+  float* p = c->sampler_buf.get();
   const float* src[6] = {cum_prob, elevation, normal_x, normal_y, normal_z, plane_fit_std_dev};
   const float** dst[6] = {&c->sampler.cum_prob, &c->sampler.elevation, &c->sampler.normal_x,
                           &c->sampler.normal_y, &c->sampler.normal_z, &c->sampler.plane_fit_std_dev};
   for (int k = 0; k < 6; ++k) {
-    HIP_TRY(c, hipMemcpyAsync(p, src[k], e * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(p, src[k], e * sizeof(float), hipMemcpyDeviceToDevice, c->lane->stream));
     *dst[k] = p;
     p += e;
   }
-  HIP_TRY(c, hipMemcpyAsync(p, cum_prob_rowwise, rows * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(p, cum_prob_rowwise, rows * sizeof(float), hipMemcpyDeviceToDevice, c->lane->stream));
   c->sampler.cum_prob_rowwise = p;
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  {
-    const int rcp = pack_sampler_tables(c, rows, cols);
-    if (rcp != ARTP_OK) return rcp;
-  }
+  HIP_TRY(c, hipStreamSynchronize(c->lane->stream));
+  ARTP_TRY(pack_sampler_tables(c, rows, cols));
   if (!c->have_geom) {
     c->geom.len_x = len_x; c->geom.len_y = len_y; c->geom.pos_x = pos_x; c->geom.pos_y = pos_y;
     c->geom.rows = rows; c->geom.cols = cols; c->geom.res = len_x / rows;
@@ -1805,14 +1614,14 @@ static int finite_min_max_dev(artp_ctx* c, const float* d_layer, size_t n, float
   std::lock_guard<std::recursive_mutex> lock(c->mu);
   HIP_TRY(c, hipSetDevice(c->device));
   int init[2] = {0x7fffffff, (int)0x80000000};
-  int* d_keys = reinterpret_cast<int*>(c->d_count);
-  HIP_TRY(c, hipMemcpyAsync(d_keys, init, sizeof(init), hipMemcpyHostToDevice, c->stream));
+  int* d_keys = reinterpret_cast<int*>(c->lane->d_count.get());
+  HIP_TRY(c, hipMemcpyAsync(d_keys, init, sizeof(init), hipMemcpyHostToDevice, c->lane->stream));
   hipLaunchKernelGGL(finite_min_max_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, (size_t)c->n_cus)), dim3(256), 0,
-                     c->stream, d_layer, (int)n, d_keys);
+                     c->lane->stream, d_layer, (int)n, d_keys);
   HIP_TRY(c, hipGetLastError());
   int keys[2];
-  HIP_TRY(c, hipMemcpyAsync(keys, d_keys, sizeof(keys), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipMemcpyAsync(keys, d_keys, sizeof(keys), hipMemcpyDeviceToHost, c->lane->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->lane->stream));
   *any = keys[0] <= keys[1];
   auto unkey = [](int k) {
     const int i = k >= 0 ? k : k ^ 0x7fffffff;
@@ -1833,10 +1642,10 @@ static int launch_sampler(artp_ctx* c, uint64_t seed, uint64_t first_index, size
     return ARTP_ERR_INVALID_ARG;
   }
   if (c->sampler.from_distribution)
-    hipLaunchKernelGGL(sample_states_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, c->stream, c->sampler,
+    hipLaunchKernelGGL(sample_states_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, c->lane->stream, c->sampler,
                        c->geom, c->robot, seed, first_index, n, se3_out, c->field[0], recs);
   else
-    hipLaunchKernelGGL(sample_states_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, c->stream, c->sampler,
+    hipLaunchKernelGGL(sample_states_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, c->lane->stream, c->sampler,
                        c->geom, c->robot, seed, first_index, n, se3_out, c->field[0], recs);
   HIP_TRY(c, hipGetLastError());
   return ARTP_OK;
@@ -1856,12 +1665,10 @@ int artp_sample_states(artp_ctx* c, uint64_t seed, uint64_t first_index, size_t 
   if (n == 0) return ARTP_OK;
   std::lock_guard<std::recursive_mutex> lock(c->mu);
   HIP_TRY(c, hipSetDevice(c->device));
-  int rc = ensure_tmp(c, 0, n * 7 * sizeof(double));
-  if (rc) return rc;
-  rc = artp_sample_states_dev(c, seed, first_index, n, static_cast<double*>(c->tmp[0]));
-  if (rc) return rc;
-  HIP_TRY(c, hipMemcpyAsync(se3_out, c->tmp[0], n * 7 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  ARTP_TRY(ensure_scratch(c, c->lane->host_args, n * 7 * sizeof(double)));
+  ARTP_TRY(artp_sample_states_dev(c, seed, first_index, n, c->lane->host_args.as<double>()));
+  HIP_TRY(c, hipMemcpyAsync(se3_out, c->lane->host_args.get(), n * 7 * sizeof(double), hipMemcpyDeviceToHost, c->lane->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->lane->stream));
   return ARTP_OK;
 }
 
@@ -1881,33 +1688,28 @@ int artp_sample_and_validate_dev(artp_ctx* c, uint64_t seed, uint64_t first_inde
   HIP_TRY(c, hipSetDevice(c->device));
   // fused: the sampler hands the per-state part of the validity check (float pose, orthogonalised rotation in the
   // field frame) to the pipeline while the state is still in its registers
-  int rc = ensure_recs(c, n);
-  if (rc) return rc;
+  ARTP_TRY(ensure_recs(c, n));
   if (n <= ARTP_FEW_STATES) {  // the few-state kernel reads the states themselves
-    rc = launch_sampler(c, seed, first_index, n, se3_out, nullptr);
-    if (rc) return rc;
-    rc = artp_validate_states_dev(c, se3_out, n, valid_out, nullptr);
-    if (rc) return rc;
+    ARTP_TRY(launch_sampler(c, seed, first_index, n, se3_out, nullptr));
+    ARTP_TRY(artp_validate_states_dev(c, se3_out, n, valid_out, nullptr));
   } else {
-    rc = launch_sampler(c, seed, first_index, n, se3_out, static_cast<PoseRec*>(c->tmp[7]));
-    if (rc) return rc;
+    ARTP_TRY(launch_sampler(c, seed, first_index, n, se3_out, c->lane->pose_recs.as<PoseRec>()));
   }
   if (n > ARTP_FEW_STATES) {
-    const int rcv = launch_validate_pipeline(c, se3_out, n, valid_out, true);
-    if (rcv) return rcv;
+    ARTP_TRY(launch_validate_pipeline(c, se3_out, n, valid_out, true));
   }
   if (n_valid) {
-    HIP_TRY(c, hipMemsetAsync(c->d_count, 0, sizeof(unsigned long long), c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->lane->d_count.get(), 0, sizeof(unsigned long long), c->lane->stream));
     size_t blocks = (n / 16 + 255) / 256 + 1;
     if (blocks > (size_t)c->n_cus * 4) blocks = (size_t)c->n_cus * 4;
-    hipLaunchKernelGGL(count_valid_kernel, dim3((unsigned)blocks), dim3(256), 0, c->stream,
-                       (const uint8_t*)valid_out, n, c->d_count);
+    hipLaunchKernelGGL(count_valid_kernel, dim3((unsigned)blocks), dim3(256), 0, c->lane->stream,
+                       (const uint8_t*)valid_out, n, c->lane->d_count.get());
     HIP_TRY(c, hipGetLastError());
   }
   if (n_valid) {
     unsigned long long cnt = 0;
-    HIP_TRY(c, hipMemcpyAsync(&cnt, c->d_count, sizeof(cnt), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpyAsync(&cnt, c->lane->d_count.get(), sizeof(cnt), hipMemcpyDeviceToHost, c->lane->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->lane->stream));
     *n_valid = (size_t)cnt;
   }
   return ARTP_OK;
@@ -1922,15 +1724,12 @@ int artp_sample_and_validate(artp_ctx* c, uint64_t seed, uint64_t first_index, s
   if (map_version) *map_version = c->map_version.load(std::memory_order_acquire);  // fixed while `mu` is held
   if (n == 0) return ARTP_OK;
   HIP_TRY(c, hipSetDevice(c->device));
-  int rc = ensure_tmp(c, 0, n * 7 * sizeof(double));
-  if (rc) return rc;
-  rc = ensure_tmp(c, 1, n);
-  if (rc) return rc;
-  rc = artp_sample_and_validate_dev(c, seed, first_index, n, static_cast<double*>(c->tmp[0]),
-                                    static_cast<uint8_t*>(c->tmp[1]), nullptr);
-  if (rc) return rc;
-  HIP_TRY(c, hipMemcpyAsync(se3_out, c->tmp[0], n * 7 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(valid_out, c->tmp[1], n, hipMemcpyDeviceToHost, c->stream));
+  ARTP_TRY(ensure_scratch(c, c->lane->host_args, n * 7 * sizeof(double)));
+  ARTP_TRY(ensure_scratch(c, c->lane->host_results, n));
+  ARTP_TRY(artp_sample_and_validate_dev(c, seed, first_index, n, c->lane->host_args.as<double>(),
+                                    c->lane->host_results.as<uint8_t>(), nullptr));
+  HIP_TRY(c, hipMemcpyAsync(se3_out, c->lane->host_args.get(), n * 7 * sizeof(double), hipMemcpyDeviceToHost, c->lane->stream));
+  HIP_TRY(c, hipMemcpyAsync(valid_out, c->lane->host_results.get(), n, hipMemcpyDeviceToHost, c->lane->stream));
   return check_error_flag(c);
 }
 
@@ -1967,11 +1766,10 @@ static int run_edges_dev(artp_ctx* c, int mode, const double* s1, const double* 
     return ARTP_ERR_CAPACITY;
   }
   HIP_TRY(c, hipSetDevice(c->device));
-  // tmp[2]: counts (n+1) | offsets (n+1) | aux (n) | first_bad (n) | total64, overflow flag, total of pass 1, pad |
-  //         slerp constants (n x 24 B) | counts of the coarse pass (n+1) | their offsets (n+1)
-  int rc = ensure_tmp(c, 2, (6 * n + 4) * sizeof(uint32_t) + 64 + n * sizeof(SlerpEdge));
-  if (rc) return rc;
-  uint32_t* counts = static_cast<uint32_t*>(c->tmp[2]);
+  // edge_plan: counts (n+1) | offsets (n+1) | aux (n) | first_bad (n) | total64, overflow flag, total of pass 1, pad |
+  //            slerp constants (n x 24 B) | counts of the coarse pass (n+1) | their offsets (n+1)
+  ARTP_TRY(ensure_scratch(c, c->lane->edge_plan, (6 * n + 4) * sizeof(uint32_t) + 64 + n * sizeof(SlerpEdge)));
+  uint32_t* counts = c->lane->edge_plan.as<uint32_t>();
   uint32_t* offsets = counts + (n + 1);
   uint32_t* aux = aux_out ? aux_out : offsets + (n + 1);
   uint32_t* first_bad = offsets + (n + 1) + n;
@@ -1985,35 +1783,30 @@ static int run_edges_dev(artp_ctx* c, int mode, const double* s1, const double* 
   // checkMotion's first overload in two passes (kernels.h ARTP_COARSE_STRIDE): worth its second pipeline pass for real batches
   const bool want_last_ = (mode == 0) && last_t;
   const bool two_pass_possible = mode == 0 && !want_last_ && n >= 4096 && c->edge_two_pass;
-  HIP_TRY(c, hipMemsetAsync(counts + n, 0, sizeof(uint32_t), c->stream));
-  HIP_TRY(c, hipMemsetAsync(d_total, 0, 32, c->stream));
+  HIP_TRY(c, hipMemsetAsync(counts + n, 0, sizeof(uint32_t), c->lane->stream));
+  HIP_TRY(c, hipMemsetAsync(d_total, 0, 32, c->lane->stream));
   size_t blocks = (n + 255) / 256;
   if (blocks > (size_t)c->n_cus * 4) blocks = (size_t)c->n_cus * 4;  // grid-stride; one atomic per workgroup on the total
-  if (two_pass_possible) HIP_TRY(c, hipMemsetAsync(counts1 + n, 0, sizeof(uint32_t), c->stream));
-  hipLaunchKernelGGL(motion_plan_kernel, dim3((unsigned)blocks), dim3(256), 0, c->stream, c->geom,
+  if (two_pass_possible) HIP_TRY(c, hipMemsetAsync(counts1 + n, 0, sizeof(uint32_t), c->lane->stream));
+  hipLaunchKernelGGL(motion_plan_kernel, dim3((unsigned)blocks), dim3(256), 0, c->lane->stream, c->geom,
                      c->z_high - c->z_low, mode, s1, s2, n, counts, aux, valid, d_overflow, d_total, d_slerp,
                      two_pass_possible ? counts1 : (uint32_t*)nullptr, two_pass_possible ? d_total1 : (unsigned long long*)nullptr,
                      (uint32_t)c->edge_coarse_stride, c->r3_extent_override);
   HIP_TRY(c, hipGetLastError());
   size_t need = 0;
-  HIP_TRY(c, hipcub::DeviceScan::ExclusiveSum(nullptr, need, counts, offsets, (int)(n + 1), c->stream));
-  if (c->cub_cap < need) {
-    if (c->cub_tmp) HIP_TRY(c, hipFree(c->cub_tmp));
-    c->cub_tmp = nullptr;
-    HIP_TRY(c, hipMalloc(&c->cub_tmp, need + 256));
-    c->cub_cap = need + 256;
-  }
-  size_t cap = c->cub_cap;
-  HIP_TRY(c, hipcub::DeviceScan::ExclusiveSum(c->cub_tmp, cap, counts, offsets, (int)(n + 1), c->stream));
+  HIP_TRY(c, hipcub::DeviceScan::ExclusiveSum(nullptr, need, counts, offsets, (int)(n + 1), c->lane->stream));
+  ARTP_TRY(ensure_cub_tmp(c, need));
+  size_t cap = c->lane->cub_tmp.capacity();
+  HIP_TRY(c, hipcub::DeviceScan::ExclusiveSum(c->lane->cub_tmp.get(), cap, counts, offsets, (int)(n + 1), c->lane->stream));
   if (two_pass_possible) {
-    cap = c->cub_cap;
-    HIP_TRY(c, hipcub::DeviceScan::ExclusiveSum(c->cub_tmp, cap, counts1, offsets1, (int)(n + 1), c->stream));
+    cap = c->lane->cub_tmp.capacity();
+    HIP_TRY(c, hipcub::DeviceScan::ExclusiveSum(c->lane->cub_tmp.get(), cap, counts1, offsets1, (int)(n + 1), c->lane->stream));
   }
   // expand every interior state into one state batch, validate it with the standard pipeline, then
   // fold the labels back onto the edges
   struct { unsigned long long total; int overflow; int pad; unsigned long long total1; unsigned long long pad2; } plan{0, 0, 0, 0, 0};
-  HIP_TRY(c, hipMemcpyAsync(&plan, d_total, 32, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipMemcpyAsync(&plan, d_total, 32, hipMemcpyDeviceToHost, c->lane->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->lane->stream));
   if (plan.overflow) {
     c->last_error = "an edge has non-finite states or needs more than 2^22 interpolation states";
     return ARTP_ERR_INVALID_ARG;
@@ -2024,7 +1817,7 @@ static int run_edges_dev(artp_ctx* c, int mode, const double* s1, const double* 
   }
   const uint32_t total = (uint32_t)plan.total;
   const bool want_last = want_last_;
-  if (want_last) HIP_TRY(c, hipMemsetAsync(first_bad, 0xff, n * sizeof(uint32_t), c->stream));
+  if (want_last) HIP_TRY(c, hipMemsetAsync(first_bad, 0xff, n * sizeof(uint32_t), c->lane->stream));
   size_t eb = ((size_t)total + 255) / 256;
   if (eb > (size_t)c->n_cus * 32) eb = (size_t)c->n_cus * 32;
   if (two_pass_possible && plan.total >= 24ull * n) {
@@ -2033,61 +1826,54 @@ static int run_edges_dev(artp_ctx* c, int mode, const double* s1, const double* 
       if (tot == 0) return ARTP_OK;
       size_t pb = ((size_t)tot + 255) / 256;
       if (pb > (size_t)c->n_cus * 32) pb = (size_t)c->n_cus * 32;
-      int r = ensure_tmp(c, 3, (size_t)tot * (sizeof(uint32_t) + 1) + 64);
-      if (r) return r;
-      r = ensure_recs(c, tot);
-      if (r) return r;
-      uint32_t* edge_of = static_cast<uint32_t*>(c->tmp[3]);
+      ARTP_TRY(ensure_scratch(c, c->lane->edge_states, (size_t)tot * (sizeof(uint32_t) + 1) + 64));
+      ARTP_TRY(ensure_recs(c, tot));
+      uint32_t* edge_of = c->lane->edge_states.as<uint32_t>();
       uint8_t* ex_valid = reinterpret_cast<uint8_t*>(edge_of + tot);
-      hipLaunchKernelGGL(expand_edges_recs_kernel, dim3((unsigned)pb), dim3(256), 0, c->stream, c->field[0], mode, s1, s2, n,
-                         offs, (const uint32_t*)aux, (const SlerpEdge*)d_slerp, static_cast<PoseRec*>(c->tmp[7]), edge_of,
+      hipLaunchKernelGGL(expand_edges_recs_kernel, dim3((unsigned)pb), dim3(256), 0, c->lane->stream, c->field[0], mode, s1, s2, n,
+                         offs, (const uint32_t*)aux, (const SlerpEdge*)d_slerp, c->lane->pose_recs.as<PoseRec>(), edge_of,
                          pass, (uint32_t)c->edge_coarse_stride);
       HIP_TRY(c, hipGetLastError());
-      r = launch_validate_pipeline(c, nullptr, tot, ex_valid, true, pass == 2 ? ARTP_TAIL_EDGES_2 : ARTP_TAIL_EDGES_1);
-      if (r) return r;
-      hipLaunchKernelGGL(reduce_edges_kernel, dim3((unsigned)pb), dim3(256), 0, c->stream, (const uint8_t*)ex_valid,
+      ARTP_TRY(launch_validate_pipeline(c, nullptr, tot, ex_valid, true, pass == 2 ? ARTP_TAIL_EDGES_2 : ARTP_TAIL_EDGES_1));
+      hipLaunchKernelGGL(reduce_edges_kernel, dim3((unsigned)pb), dim3(256), 0, c->lane->stream, (const uint8_t*)ex_valid,
                          (const uint32_t*)edge_of, offs, n, valid);
       HIP_TRY(c, hipGetLastError());
       return ARTP_OK;
     };
-    rc = run_pass(1, offsets1, (uint32_t)plan.total1);
-    if (rc) return rc;
+    ARTP_TRY(run_pass(1, offsets1, (uint32_t)plan.total1));
     // pass 2: counts of what is left, for the edges still valid (reuses the pass-1 arrays)
-    HIP_TRY(c, hipMemsetAsync(d_total1, 0, sizeof(unsigned long long), c->stream));
-    hipLaunchKernelGGL(coarse_pass2_counts_kernel, dim3((unsigned)blocks), dim3(256), 0, c->stream, (const uint32_t*)aux,
+    HIP_TRY(c, hipMemsetAsync(d_total1, 0, sizeof(unsigned long long), c->lane->stream));
+    hipLaunchKernelGGL(coarse_pass2_counts_kernel, dim3((unsigned)blocks), dim3(256), 0, c->lane->stream, (const uint32_t*)aux,
                        (const uint8_t*)valid, n, (uint32_t)c->edge_coarse_stride, counts1, d_total1);
     HIP_TRY(c, hipGetLastError());
-    cap = c->cub_cap;
-    HIP_TRY(c, hipcub::DeviceScan::ExclusiveSum(c->cub_tmp, cap, counts1, offsets1, (int)(n + 1), c->stream));
+    cap = c->lane->cub_tmp.capacity();
+    HIP_TRY(c, hipcub::DeviceScan::ExclusiveSum(c->lane->cub_tmp.get(), cap, counts1, offsets1, (int)(n + 1), c->lane->stream));
     unsigned long long total2 = 0;
-    HIP_TRY(c, hipMemcpyAsync(&total2, d_total1, sizeof(total2), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpyAsync(&total2, d_total1, sizeof(total2), hipMemcpyDeviceToHost, c->lane->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->lane->stream));
     return run_pass(2, offsets1, (uint32_t)total2);
   }
   if (total != 0) {
-    // tmp[3]: edge_of (total u32) | ex_valid (total bytes); the interior states themselves only exist as PoseRecs (tmp[7])
-    rc = ensure_tmp(c, 3, (size_t)total * (sizeof(uint32_t) + 1) + 64);
-    if (rc) return rc;
-    rc = ensure_recs(c, total);
-    if (rc) return rc;
-    uint32_t* edge_of = static_cast<uint32_t*>(c->tmp[3]);
+    // edge_states: edge_of (total u32) | ex_valid (total bytes); the interior states themselves only exist as PoseRecs
+    ARTP_TRY(ensure_scratch(c, c->lane->edge_states, (size_t)total * (sizeof(uint32_t) + 1) + 64));
+    ARTP_TRY(ensure_recs(c, total));
+    uint32_t* edge_of = c->lane->edge_states.as<uint32_t>();
     uint8_t* ex_valid = reinterpret_cast<uint8_t*>(edge_of + total);
-    hipLaunchKernelGGL(expand_edges_recs_kernel, dim3((unsigned)eb), dim3(256), 0, c->stream, c->field[0], mode, s1, s2, n,
+    hipLaunchKernelGGL(expand_edges_recs_kernel, dim3((unsigned)eb), dim3(256), 0, c->lane->stream, c->field[0], mode, s1, s2, n,
                        (const uint32_t*)offsets, (const uint32_t*)aux, (const SlerpEdge*)d_slerp,
-                       static_cast<PoseRec*>(c->tmp[7]), edge_of);
+                       c->lane->pose_recs.as<PoseRec>(), edge_of);
     HIP_TRY(c, hipGetLastError());
-    rc = launch_validate_pipeline(c, nullptr, total, ex_valid, true, ARTP_TAIL_EDGES_1);
-    if (rc) return rc;
-    hipLaunchKernelGGL(reduce_edges_kernel, dim3((unsigned)eb), dim3(256), 0, c->stream,
+    ARTP_TRY(launch_validate_pipeline(c, nullptr, total, ex_valid, true, ARTP_TAIL_EDGES_1));
+    hipLaunchKernelGGL(reduce_edges_kernel, dim3((unsigned)eb), dim3(256), 0, c->lane->stream,
                        (const uint8_t*)ex_valid, (const uint32_t*)edge_of, (const uint32_t*)offsets, n, valid);
     if (want_last)
-      hipLaunchKernelGGL(reduce_edges_first_bad_kernel, dim3((unsigned)eb), dim3(256), 0, c->stream,
+      hipLaunchKernelGGL(reduce_edges_first_bad_kernel, dim3((unsigned)eb), dim3(256), 0, c->lane->stream,
                          (const uint8_t*)ex_valid, (const uint32_t*)edge_of, (const uint32_t*)offsets,
                          (const uint32_t*)aux, n, first_bad);
     HIP_TRY(c, hipGetLastError());
   }
   if (want_last) {
-    hipLaunchKernelGGL(last_valid_kernel, dim3((unsigned)blocks), dim3(256), 0, c->stream, s1, s2, n,
+    hipLaunchKernelGGL(last_valid_kernel, dim3((unsigned)blocks), dim3(256), 0, c->lane->stream, s1, s2, n,
                        (const uint32_t*)aux, (const uint32_t*)first_bad, last_t, last_state);
     HIP_TRY(c, hipGetLastError());
   }
@@ -2129,12 +1915,12 @@ static double few_edges_task_estimate(const artp_ctx* c, int mode, const double*
 // either way the verdict's status bytes come back through mapped memory and the call returns when they are there.
 static int run_edges_few(artp_ctx* c, int mode, bool host_io, const double* s1, const double* s2, size_t n, uint8_t* valid,
                          uint32_t* aux_out, double* last_t, double* last_state, double max_tasks_per_edge) {
-  char* hb = c->pin_edges;
-  char* db = c->pin_edges_dev;
+  char* hb = c->pin_edges.host();
+  char* db = c->pin_edges.dev();
   volatile uint8_t* status = reinterpret_cast<volatile uint8_t*>(hb + FEW_EDGE_STATUS);
   if (host_io) {
-    std::memcpy(c->pin_edges_in + FEW_EDGE_S1, s1, n * 7 * sizeof(double));
-    std::memcpy(c->pin_edges_in + FEW_EDGE_S2, s2, n * 7 * sizeof(double));
+    std::memcpy(c->pin_edges_in.host() + FEW_EDGE_S1, s1, n * 7 * sizeof(double));
+    std::memcpy(c->pin_edges_in.host() + FEW_EDGE_S2, s2, n * 7 * sizeof(double));
   }
   for (size_t i = 0; i < n; ++i) status[i] = 0;
   // workgroups per edge: one per task of the longest edge (estimated; <= ~100 for edges shorter than the map), ~2048
@@ -2144,10 +1930,10 @@ static int run_edges_few(artp_ctx* c, int mode, bool host_io, const double* s1, 
   chunks = chunks > want ? want : chunks;
   const unsigned tag = 0x80u;
   const bool want_last = mode == 0 && last_t;
-  hipLaunchKernelGGL(check_motions_few_kernel, dim3(chunks, (unsigned)n), dim3(320), lds_few(c), c->stream, c->field[0],
+  hipLaunchKernelGGL(check_motions_few_kernel, dim3(chunks, (unsigned)n), dim3(320), lds_few(c), c->lane->stream, c->field[0],
                      c->field[1], c->geom, c->robot, c->z_high - c->z_low, c->r3_extent_override, mode,
-                     host_io ? reinterpret_cast<const double*>(c->pin_edges_in_dev + FEW_EDGE_S1) : s1,
-                     host_io ? reinterpret_cast<const double*>(c->pin_edges_in_dev + FEW_EDGE_S2) : s2, (uint32_t)n, c->d_few_sync,
+                     host_io ? reinterpret_cast<const double*>(c->pin_edges_in.dev() + FEW_EDGE_S1) : s1,
+                     host_io ? reinterpret_cast<const double*>(c->pin_edges_in.dev() + FEW_EDGE_S2) : s2, (uint32_t)n, c->d_few_sync.get(),
                      reinterpret_cast<volatile uint8_t*>(db + FEW_EDGE_STATUS), host_io ? (uint8_t*)nullptr : valid,
                      !aux_out ? (uint32_t*)nullptr : host_io ? reinterpret_cast<uint32_t*>(db + FEW_EDGE_AUX) : aux_out,
                      !want_last ? (double*)nullptr : host_io ? reinterpret_cast<double*>(db + FEW_EDGE_LAST_T) : last_t,
@@ -2165,7 +1951,7 @@ static int run_edges_few(artp_ctx* c, int mode, bool host_io, const double* s1, 
         break;
     }
   }
-  if (!done) HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (!done) HIP_TRY(c, hipStreamSynchronize(c->lane->stream));
   std::atomic_thread_fence(std::memory_order_acquire);
   unsigned flags = 0;
   for (size_t i = 0; i < n; ++i) flags |= status[i];
@@ -2189,7 +1975,7 @@ static int run_edges_few(artp_ctx* c, int mode, bool host_io, const double* s1, 
 // ---- resident pool for calls of one or two edges (kernels.h check_motions_pool_kernel) --------------------------------
 static bool pool_any_exited(const artp_ctx* c) {
   for (unsigned w = 0; w < c->pool_wgs; ++w)
-    if (c->pool_resp->exited[w]) return true;
+    if (c->pool_resp.host()->exited[w]) return true;
   return false;
 }
 
@@ -2210,7 +1996,7 @@ static bool pool_available(artp_ctx* c) {
     if (hipDeviceGetAttribute(&large_bar, hipDeviceAttributeIsLargeBar, c->device) == hipSuccess && large_bar &&
         hipExtMallocWithFlags(&p, sizeof(EdgeMailbox), hipDeviceMallocFinegrained) == hipSuccess) {
       // the request block: DEVICE memory the host writes through the PCIe BAR (kernels.h), cleared the same way
-      c->pool_mb = static_cast<EdgeMailbox*>(p);
+      c->pool_mb.adopt(p, sizeof(EdgeMailbox));
       for (size_t i = 0; i < sizeof(EdgeMailbox) / 8; ++i) reinterpret_cast<volatile uint64_t*>(p)[i] = 0;
       c->pool_bar = 1;
     } else {
@@ -2222,14 +2008,14 @@ static bool pool_available(artp_ctx* c) {
 }
 
 static void pool_stop(artp_ctx* c) {
-  if (!c->pool_mb || !c->pool_launched) return;
+  if (!c->pool_mb.get() || !c->pool_launched) return;
   // (line 0 is never READ by the host -- a read across the BAR is a microsecond: the request number is c->pool_seq)
-  reinterpret_cast<volatile uint64_t*>(&c->pool_mb->line[0])[0] = ((uint64_t)0x100u << 32) | c->pool_seq;
+  reinterpret_cast<volatile uint64_t*>(&c->pool_mb.get()->line[0])[0] = ((uint64_t)0x100u << 32) | c->pool_seq;
   pool_store_fence();
   const auto t0 = std::chrono::steady_clock::now();
   for (;;) {
     bool all = true;
-    for (unsigned w = 0; w < c->pool_wgs; ++w) all = all && c->pool_resp->exited[w];
+    for (unsigned w = 0; w < c->pool_wgs; ++w) all = all && c->pool_resp.host()->exited[w];
     if (all || std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(200)) break;
   }
   (void)hipStreamSynchronize(c->pool_stream);   // every workgroup has returned (at the latest after the lifetime limit)
@@ -2237,30 +2023,26 @@ static void pool_stop(artp_ctx* c) {
 }
 
 static int pool_start(artp_ctx* c) {
-  if (!c->pool_resp) {
-    void *r = nullptr, *rd = nullptr;
-    HIP_TRY(c, hipHostMalloc(&r, sizeof(PoolResponse), hipHostMallocMapped));
-    c->pool_resp = static_cast<PoolResponse*>(r);
-    HIP_TRY(c, hipHostGetDevicePointer(&rd, r, 0));
-    c->pool_resp_dev = static_cast<PoolResponse*>(rd);
-    std::memset(r, 0, sizeof(PoolResponse));
-    HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->pool_ctl), sizeof(PoolCtl)));
-    HIP_TRY(c, hipStreamCreateWithFlags(&c->pool_stream, hipStreamNonBlocking));
-    HIP_TRY(c, hipEventCreateWithFlags(&c->pool_after_map, hipEventDisableTiming));
+  if (!c->pool_resp.host()) {
+    HIP_TRY(c, c->pool_resp.reserve(sizeof(PoolResponse), hipHostMallocMapped));
+    std::memset(c->pool_resp.host(), 0, sizeof(PoolResponse));
   }
+  HIP_TRY(c, c->pool_ctl.reserve(sizeof(PoolCtl)));
+  if (!c->pool_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->pool_stream, hipStreamNonBlocking));
+  if (!c->pool_after_map) HIP_TRY(c, hipEventCreateWithFlags(&c->pool_after_map, hipEventDisableTiming));
   if (c->pool_seq >= 0xfffffff0u) {   // the request numbers wrap: every tag back to "never"
-    reinterpret_cast<volatile uint64_t*>(&c->pool_mb->line[0])[0] = 0;
-    std::memset(c->pool_resp, 0, sizeof(PoolResponse));
+    reinterpret_cast<volatile uint64_t*>(&c->pool_mb.get()->line[0])[0] = 0;
+    std::memset(c->pool_resp.host(), 0, sizeof(PoolResponse));
     c->pool_seq = 0;
   }
-  HIP_TRY(c, hipEventRecord(c->pool_after_map, c->stream));          // behind the map writes already enqueued
+  HIP_TRY(c, hipEventRecord(c->pool_after_map, c->lane->stream));          // behind the map writes already enqueued
   HIP_TRY(c, hipStreamWaitEvent(c->pool_stream, c->pool_after_map, 0));
-  HIP_TRY(c, hipMemsetAsync(c->pool_ctl, 0, sizeof(PoolCtl), c->pool_stream));
-  reinterpret_cast<volatile uint64_t*>(&c->pool_mb->line[0])[0] = c->pool_seq;   // word 0: nothing to do, do not leave
-  for (unsigned w = 0; w < ARTP_POOL_MAX_WGS; ++w) c->pool_resp->exited[w] = 0;
+  HIP_TRY(c, hipMemsetAsync(c->pool_ctl.get(), 0, sizeof(PoolCtl), c->pool_stream));
+  reinterpret_cast<volatile uint64_t*>(&c->pool_mb.get()->line[0])[0] = c->pool_seq;   // word 0: nothing to do, do not leave
+  for (unsigned w = 0; w < ARTP_POOL_MAX_WGS; ++w) c->pool_resp.host()->exited[w] = 0;
   pool_store_fence();
   hipLaunchKernelGGL(check_motions_pool_kernel, dim3(c->pool_wgs), dim3(320), lds_few(c), c->pool_stream, c->field[0],
-                     c->field[1], c->geom, c->robot, c->pool_mb, c->pool_resp_dev, c->pool_ctl, c->pool_seq, c->caps_full,
+                     c->field[1], c->geom, c->robot, c->pool_mb.get(), c->pool_resp.dev(), c->pool_ctl.get(), c->pool_seq, c->caps_full,
                      c->caps_foot_full);
   HIP_TRY(c, hipGetLastError());
   c->pool_launched = true;
@@ -2278,11 +2060,8 @@ static int run_edges_pool(artp_ctx* c, int mode, const double* s1, const double*
   for (int attempt = 0; attempt < 3; ++attempt) {
     const bool stale = c->pool_launched && c->pool_map_version != c->map_version.load(std::memory_order_acquire);
     if (stale || (c->pool_launched && (c->pool_seq >= 0xfffffff0u || pool_any_exited(c)))) pool_stop(c);
-    if (!c->pool_launched) {
-      const int rc = pool_start(c);
-      if (rc) return rc;
-    }
-    EdgeMailbox* mb = c->pool_mb;
+    if (!c->pool_launched) ARTP_TRY(pool_start(c));
+    EdgeMailbox* mb = c->pool_mb.get();
     const unsigned P = c->pool_wgs;
     // the block as the device will see it (c->pool_shadow: the host never reads across the BAR): payloads, header word, checksum
     const uint32_t seq = ++c->pool_seq;
@@ -2317,7 +2096,7 @@ static int run_edges_pool(artp_ctx* c, int mode, const double* s1, const double*
     for (unsigned spin = 0; !done; ++spin) {
       for (;;) {
         const unsigned w = (lead + idx) % P;
-        const volatile PoolSlot& sl = c->pool_resp->slot[e][w];
+        const volatile PoolSlot& sl = c->pool_resp.host()->slot[e][w];
         if (sl.tag != seq) break;
         std::atomic_thread_fence(std::memory_order_acquire);
         // the slot as a whole: taken when its check word verifies (with the lastValid state it announces), else not there yet
@@ -2326,7 +2105,7 @@ static int run_edges_pool(artp_ctx* c, int mode, const double* s1, const double*
         if (want_last && s_bad != 0xffffffffu)
           for (int i = 0; i < 7; ++i) {
             uint64_t u;
-            const double v = c->pool_resp->last_state[e][w][i];
+            const double v = c->pool_resp.host()->last_state[e][w][i];
             std::memcpy(&u, &v, 8);
             state_xor ^= u;
           }
@@ -2354,7 +2133,7 @@ static int run_edges_pool(artp_ctx* c, int mode, const double* s1, const double*
             const int nd = (int)aux;
             last_t[e] = nd > 0 ? (double)fbad / (double)nd : (double)(nd - 1) / (double)nd;
             if (last_state)
-              std::memcpy(last_state + 7 * e, const_cast<const double*>(c->pool_resp->last_state[e][who]), 7 * sizeof(double));
+              std::memcpy(last_state + 7 * e, const_cast<const double*>(c->pool_resp.host()->last_state[e][who]), 7 * sizeof(double));
           }
         }
         if (++e == n) {
@@ -2372,9 +2151,9 @@ static int run_edges_pool(artp_ctx* c, int mode, const double* s1, const double*
         // one (a 200 us request on a map full of unknown cells), and those others still answer.  Its slot is written in
         // front of its exit flag, so a flag without a verifying slot means it never saw the request.
         const unsigned w = (lead + idx) % P;
-        if (c->pool_resp->exited[w]) {
+        if (c->pool_resp.host()->exited[w]) {
           std::atomic_thread_fence(std::memory_order_acquire);
-          if (c->pool_resp->slot[e][w].tag != seq) { gone = true; break; }
+          if (c->pool_resp.host()->slot[e][w].tag != seq) { gone = true; break; }
         }
         if (std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(50)) break;
       }
@@ -2407,7 +2186,7 @@ static int run_edges_host(artp_ctx* c, int mode, const double* s1, const double*
                           uint8_t* valid, uint32_t* aux_out, double* last_t = nullptr, double* last_state = nullptr) {
   if (!c || (n && (!s1 || !s2 || !valid))) return ARTP_ERR_INVALID_ARG;
   if (n == 0) return ARTP_OK;
-  // one lock for the whole call: the staging buffers c->tmp[0..1] are shared by every host entry point
+  // one lock for the whole call: the staging buffers host_args / host_results are shared by every host entry point
   std::lock_guard<std::recursive_mutex> lock(c->mu);
   HIP_TRY(c, hipSetDevice(c->device));
   double few_max = 0.0;
@@ -2418,27 +2197,24 @@ static int run_edges_host(artp_ctx* c, int mode, const double* s1, const double*
       return run_edges_pool(c, mode, s1, s2, n, valid, aux_out, last_t, last_state);
     return run_edges_few(c, mode, true, s1, s2, n, valid, aux_out, last_t, last_state, few_max);
   }
-  int rc = ensure_tmp(c, 0, 2 * n * 7 * sizeof(double));
-  if (rc) return rc;
-  // tmp[1]: last_t (n doubles) | last_state (7n doubles) | aux (n u32) | valid (n)
-  rc = ensure_tmp(c, 1, n * 8 * sizeof(double) + n * 4 + n + 16);
-  if (rc) return rc;
-  HIP_TRY(c, hipMemcpyAsync(c->tmp[0], s1, n * 7 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(static_cast<double*>(c->tmp[0]) + 7 * n, s2, n * 7 * sizeof(double),
-                            hipMemcpyHostToDevice, c->stream));
-  double* d_last_t = static_cast<double*>(c->tmp[1]);
+  ARTP_TRY(ensure_scratch(c, c->lane->host_args, 2 * n * 7 * sizeof(double)));
+  // host_results: last_t (n doubles) | last_state (7n doubles) | aux (n u32) | valid (n)
+  ARTP_TRY(ensure_scratch(c, c->lane->host_results, n * 8 * sizeof(double) + n * 4 + n + 16));
+  HIP_TRY(c, hipMemcpyAsync(c->lane->host_args.get(), s1, n * 7 * sizeof(double), hipMemcpyHostToDevice, c->lane->stream));
+  HIP_TRY(c, hipMemcpyAsync(c->lane->host_args.as<double>() + 7 * n, s2, n * 7 * sizeof(double),
+                            hipMemcpyHostToDevice, c->lane->stream));
+  double* d_last_t = c->lane->host_results.as<double>();
   double* d_last_state = d_last_t + n;
   uint32_t* d_aux = reinterpret_cast<uint32_t*>(d_last_state + 7 * n);
   uint8_t* d_valid = reinterpret_cast<uint8_t*>(d_aux + n);
-  rc = run_edges_dev(c, mode, static_cast<const double*>(c->tmp[0]),
-                     static_cast<const double*>(c->tmp[0]) + 7 * n, n, d_valid, d_aux,
-                     last_t ? d_last_t : nullptr, last_state ? d_last_state : nullptr);
-  if (rc) return rc;
-  HIP_TRY(c, hipMemcpyAsync(valid, d_valid, n, hipMemcpyDeviceToHost, c->stream));
-  if (aux_out) HIP_TRY(c, hipMemcpyAsync(aux_out, d_aux, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-  if (last_t) HIP_TRY(c, hipMemcpyAsync(last_t, d_last_t, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  ARTP_TRY(run_edges_dev(c, mode, c->lane->host_args.as<const double>(),
+                     c->lane->host_args.as<const double>() + 7 * n, n, d_valid, d_aux,
+                     last_t ? d_last_t : nullptr, last_state ? d_last_state : nullptr));
+  HIP_TRY(c, hipMemcpyAsync(valid, d_valid, n, hipMemcpyDeviceToHost, c->lane->stream));
+  if (aux_out) HIP_TRY(c, hipMemcpyAsync(aux_out, d_aux, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->lane->stream));
+  if (last_t) HIP_TRY(c, hipMemcpyAsync(last_t, d_last_t, n * sizeof(double), hipMemcpyDeviceToHost, c->lane->stream));
   if (last_t && last_state)
-    HIP_TRY(c, hipMemcpyAsync(last_state, d_last_state, n * 7 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(last_state, d_last_state, n * 7 * sizeof(double), hipMemcpyDeviceToHost, c->lane->stream));
   return check_error_flag(c);
 }
 
@@ -2464,7 +2240,7 @@ int artp_set_tail_mode(artp_ctx* c, int mode) {
 int artp_last_tail(artp_ctx* c) {
   if (!c) return -1;
   std::lock_guard<std::recursive_mutex> lock(c->mu);
-  return c->tail_last[c->cur_lane];
+  return c->lane->tail_last;
 }
 int artp_check_motions_dev(artp_ctx* c, const double* s1, const double* s2, size_t n, uint8_t* valid) {
   return run_edges_dev(c, 0, s1, s2, n, valid, nullptr);
@@ -2499,11 +2275,11 @@ struct Se3Row { double v[7]; };
 int artp_debug_pipeline_counters(artp_ctx* c, uint64_t out[8]) {
   if (!c || !out) return ARTP_ERR_INVALID_ARG;
   std::lock_guard<std::recursive_mutex> lock(c->mu);
-  if (!c->tmp[5]) return ARTP_ERR_NO_MAP;
+  if (!c->lane->index_queues.get()) return ARTP_ERR_NO_MAP;
   HIP_TRY(c, hipSetDevice(c->device));
   uint64_t raw[16 + 2 * ARTP_NSUB * 16];
-  HIP_TRY(c, hipMemcpyAsync(raw, c->tmp[5], sizeof(raw), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipMemcpyAsync(raw, c->lane->index_queues.get(), sizeof(raw), hipMemcpyDeviceToHost, c->lane->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->lane->stream));
   for (int k = 0; k < 8; ++k) out[k] = raw[k];
   out[1] += raw[3];  // boxes through the exact grouping: queue 2 (full tail) + those rare_boxes_kernel grouped itself
   out[0] = out[4] = out[2] = out[7] = 0;  // the torso / foot queues and the two fallback queues: sums over the sub-queues
@@ -2526,8 +2302,8 @@ int artp_debug_partner_table(artp_ctx* c, int slot, uint8_t* out, size_t out_byt
   const size_t need = (size_t)f.nW * f.nD;
   if (out_bytes < need) return ARTP_ERR_INVALID_ARG;
   HIP_TRY(c, hipSetDevice(c->device));
-  HIP_TRY(c, hipMemcpyAsync(out, f.partner_flags, need, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipMemcpyAsync(out, f.partner_flags, need, hipMemcpyDeviceToHost, c->lane->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->lane->stream));
   return ARTP_OK;
 }
 
@@ -2537,22 +2313,17 @@ int artp_compact_valid_dev(artp_ctx* c, const double* se3, const uint8_t* valid,
   std::lock_guard<std::recursive_mutex> lock(c->mu);
   HIP_TRY(c, hipSetDevice(c->device));
   if (n == 0) {
-    HIP_TRY(c, hipMemsetAsync(n_out_dev, 0, sizeof(uint64_t), c->stream));
+    HIP_TRY(c, hipMemsetAsync(n_out_dev, 0, sizeof(uint64_t), c->lane->stream));
     return ARTP_OK;
   }
   const Se3Row* in = reinterpret_cast<const Se3Row*>(se3);
   Se3Row* out = reinterpret_cast<Se3Row*>(out_se3);
   unsigned long long* cnt = reinterpret_cast<unsigned long long*>(n_out_dev);
   size_t need = 0;
-  HIP_TRY(c, hipcub::DeviceSelect::Flagged(nullptr, need, in, valid, out, cnt, (int)n, c->stream));
-  if (c->cub_cap < need) {
-    if (c->cub_tmp) HIP_TRY(c, hipFree(c->cub_tmp));
-    c->cub_tmp = nullptr;
-    HIP_TRY(c, hipMalloc(&c->cub_tmp, need + 256));
-    c->cub_cap = need + 256;
-  }
-  size_t cap = c->cub_cap;
-  HIP_TRY(c, hipcub::DeviceSelect::Flagged(c->cub_tmp, cap, in, valid, out, cnt, (int)n, c->stream));
+  HIP_TRY(c, hipcub::DeviceSelect::Flagged(nullptr, need, in, valid, out, cnt, (int)n, c->lane->stream));
+  ARTP_TRY(ensure_cub_tmp(c, need));
+  size_t cap = c->lane->cub_tmp.capacity();
+  HIP_TRY(c, hipcub::DeviceSelect::Flagged(c->lane->cub_tmp.get(), cap, in, valid, out, cnt, (int)n, c->lane->stream));
   return ARTP_OK;
 }
 
@@ -2562,21 +2333,16 @@ int artp_compact_valid_indices_dev(artp_ctx* c, const uint8_t* valid, size_t n, 
   std::lock_guard<std::recursive_mutex> lock(c->mu);
   HIP_TRY(c, hipSetDevice(c->device));
   if (n == 0) {
-    HIP_TRY(c, hipMemsetAsync(n_out_dev, 0, sizeof(uint64_t), c->stream));
+    HIP_TRY(c, hipMemsetAsync(n_out_dev, 0, sizeof(uint64_t), c->lane->stream));
     return ARTP_OK;
   }
   hipcub::CountingInputIterator<uint32_t> in(0u);
   unsigned long long* cnt = reinterpret_cast<unsigned long long*>(n_out_dev);
   size_t need = 0;
-  HIP_TRY(c, hipcub::DeviceSelect::Flagged(nullptr, need, in, valid, out_idx, cnt, (int)n, c->stream));
-  if (c->cub_cap < need) {
-    if (c->cub_tmp) HIP_TRY(c, hipFree(c->cub_tmp));
-    c->cub_tmp = nullptr;
-    HIP_TRY(c, hipMalloc(&c->cub_tmp, need + 256));
-    c->cub_cap = need + 256;
-  }
-  size_t cap = c->cub_cap;
-  HIP_TRY(c, hipcub::DeviceSelect::Flagged(c->cub_tmp, cap, in, valid, out_idx, cnt, (int)n, c->stream));
+  HIP_TRY(c, hipcub::DeviceSelect::Flagged(nullptr, need, in, valid, out_idx, cnt, (int)n, c->lane->stream));
+  ARTP_TRY(ensure_cub_tmp(c, need));
+  size_t cap = c->lane->cub_tmp.capacity();
+  HIP_TRY(c, hipcub::DeviceSelect::Flagged(c->lane->cub_tmp.get(), cap, in, valid, out_idx, cnt, (int)n, c->lane->stream));
   return ARTP_OK;
 }
 
@@ -2605,17 +2371,15 @@ int artp_pack_edge_results_dev(artp_ctx* c, const uint8_t* valid, const uint32_t
   std::lock_guard<std::recursive_mutex> lock(c->mu);
   HIP_TRY(c, hipSetDevice(c->device));
   if (n == 0) {
-    HIP_TRY(c, hipMemsetAsync(n_out_dev, 0, sizeof(uint64_t), c->stream));
+    HIP_TRY(c, hipMemsetAsync(n_out_dev, 0, sizeof(uint64_t), c->lane->stream));
     return ARTP_OK;
   }
-  int rc = ensure_tmp(c, 6, n * sizeof(uint32_t));
-  if (rc) return rc;
-  uint32_t* sel = static_cast<uint32_t*>(c->tmp[6]);
-  rc = artp_compact_valid_indices_dev(c, valid, n, sel, n_out_dev);  // input order is kept
-  if (rc) return rc;
+  ARTP_TRY(ensure_scratch(c, c->lane->call_scratch, n * sizeof(uint32_t)));
+  uint32_t* sel = c->lane->call_scratch.as<uint32_t>();
+  ARTP_TRY(artp_compact_valid_indices_dev(c, valid, n, sel, n_out_dev));  // input order is kept
   size_t blocks = (n + 255) / 256;
   if (blocks > (size_t)c->n_cus * 16) blocks = (size_t)c->n_cus * 16;
-  hipLaunchKernelGGL(gather_edge_records_kernel, dim3((unsigned)blocks), dim3(256), 0, c->stream, (const uint32_t*)sel,
+  hipLaunchKernelGGL(gather_edge_records_kernel, dim3((unsigned)blocks), dim3(256), 0, c->lane->stream, (const uint32_t*)sel,
                      reinterpret_cast<const unsigned long long*>(n_out_dev), edge_i, edge_j, cost, records_out);
   HIP_TRY(c, hipGetLastError());
   return ARTP_OK;
@@ -2643,7 +2407,7 @@ int artp_pack_valid_bits_dev(artp_ctx* c, const uint8_t* valid, size_t n, uint64
   if (n == 0) return ARTP_OK;
   HIP_TRY(c, hipSetDevice(c->device));
   const size_t padded = (n + 63) & ~(size_t)63;  // whole wavefronts: the ballot covers the tail
-  hipLaunchKernelGGL(pack_valid_bits_kernel, dim3((unsigned)((padded + 255) / 256)), dim3(256), 0, c->stream, valid, n,
+  hipLaunchKernelGGL(pack_valid_bits_kernel, dim3((unsigned)((padded + 255) / 256)), dim3(256), 0, c->lane->stream, valid, n,
                      reinterpret_cast<unsigned long long*>(bits_out));
   HIP_TRY(c, hipGetLastError());
   return ARTP_OK;
@@ -2654,7 +2418,7 @@ int artp_indices_from_bits_dev(artp_ctx* c, const uint64_t* bits, size_t n, uint
   std::lock_guard<std::recursive_mutex> lock(c->mu);
   HIP_TRY(c, hipSetDevice(c->device));
   if (n == 0) {
-    HIP_TRY(c, hipMemsetAsync(n_out_dev, 0, sizeof(uint64_t), c->stream));
+    HIP_TRY(c, hipMemsetAsync(n_out_dev, 0, sizeof(uint64_t), c->lane->stream));
     return ARTP_OK;
   }
   hipcub::CountingInputIterator<uint32_t> in(0u);
@@ -2662,15 +2426,10 @@ int artp_indices_from_bits_dev(artp_ctx* c, const uint64_t* bits, size_t n, uint
       in, BitAt{reinterpret_cast<const unsigned long long*>(bits)});
   unsigned long long* cnt = reinterpret_cast<unsigned long long*>(n_out_dev);
   size_t need = 0;
-  HIP_TRY(c, hipcub::DeviceSelect::Flagged(nullptr, need, in, flags, out_idx, cnt, (int)n, c->stream));
-  if (c->cub_cap < need) {
-    if (c->cub_tmp) HIP_TRY(c, hipFree(c->cub_tmp));
-    c->cub_tmp = nullptr;
-    HIP_TRY(c, hipMalloc(&c->cub_tmp, need + 256));
-    c->cub_cap = need + 256;
-  }
-  size_t cap = c->cub_cap;
-  HIP_TRY(c, hipcub::DeviceSelect::Flagged(c->cub_tmp, cap, in, flags, out_idx, cnt, (int)n, c->stream));
+  HIP_TRY(c, hipcub::DeviceSelect::Flagged(nullptr, need, in, flags, out_idx, cnt, (int)n, c->lane->stream));
+  ARTP_TRY(ensure_cub_tmp(c, need));
+  size_t cap = c->lane->cub_tmp.capacity();
+  HIP_TRY(c, hipcub::DeviceSelect::Flagged(c->lane->cub_tmp.get(), cap, in, flags, out_idx, cnt, (int)n, c->lane->stream));
   return ARTP_OK;
 }
 
@@ -2685,16 +2444,15 @@ int artp_materialise_from_bits_dev(artp_ctx* c, uint64_t seed, const uint64_t* b
   HIP_TRY(c, hipSetDevice(c->device));
   const size_t words = (prefix_bits + 63) / 64;
   if (words == 0 || cap == 0) {
-    HIP_TRY(c, hipMemsetAsync(counts_dev, 0, (size_t)n_ranks * sizeof(uint64_t), c->stream));
+    HIP_TRY(c, hipMemsetAsync(counts_dev, 0, (size_t)n_ranks * sizeof(uint64_t), c->lane->stream));
     return ARTP_OK;
   }
   const size_t n_tiles = (words + ARTP_BITS_TILE - 1) / ARTP_BITS_TILE;
-  int rc = ensure_tmp(c, 6, (size_t)n_ranks * (words + n_tiles) * sizeof(unsigned));
-  if (rc) return rc;
-  unsigned* offsets = static_cast<unsigned*>(c->tmp[6]);
+  ARTP_TRY(ensure_scratch(c, c->lane->call_scratch, (size_t)n_ranks * (words + n_tiles) * sizeof(unsigned)));
+  unsigned* offsets = c->lane->call_scratch.as<unsigned>();
   unsigned* tile_tot = offsets + (size_t)n_ranks * words;
-  HIP_TRY(c, hipMemsetAsync(counts_dev, 0, (size_t)n_ranks * sizeof(uint64_t), c->stream));
-  hipLaunchKernelGGL(bits_word_offsets_kernel, dim3((unsigned)n_tiles, (unsigned)n_ranks), dim3(256), 0, c->stream,
+  HIP_TRY(c, hipMemsetAsync(counts_dev, 0, (size_t)n_ranks * sizeof(uint64_t), c->lane->stream));
+  hipLaunchKernelGGL(bits_word_offsets_kernel, dim3((unsigned)n_tiles, (unsigned)n_ranks), dim3(256), 0, c->lane->stream,
                      reinterpret_cast<const unsigned long long*>(bits), words_per_rank, words, prefix_bits, offsets, tile_tot,
                      reinterpret_cast<unsigned long long*>(counts_dev));
   RankBases bases{};
@@ -2703,12 +2461,12 @@ int artp_materialise_from_bits_dev(artp_ctx* c, uint64_t seed, const uint64_t* b
   const size_t max_out = cap < prefix_bits ? cap : prefix_bits;
   const dim3 grid((unsigned)((max_out + 255) / 256), (unsigned)n_ranks);
   if (c->sampler.from_distribution)
-    hipLaunchKernelGGL(materialise_from_bits_kernel<true>, grid, dim3(256), 0, c->stream, c->sampler, c->geom, c->robot, seed,
+    hipLaunchKernelGGL(materialise_from_bits_kernel<true>, grid, dim3(256), 0, c->lane->stream, c->sampler, c->geom, c->robot, seed,
                        bases, reinterpret_cast<const unsigned long long*>(bits), words_per_rank, words, prefix_bits,
                        (const unsigned*)offsets, (const unsigned*)tile_tot, (int)n_tiles, cap,
                        reinterpret_cast<const unsigned long long*>(counts_dev), se3_out);
   else
-    hipLaunchKernelGGL(materialise_from_bits_kernel<false>, grid, dim3(256), 0, c->stream, c->sampler, c->geom, c->robot, seed,
+    hipLaunchKernelGGL(materialise_from_bits_kernel<false>, grid, dim3(256), 0, c->lane->stream, c->sampler, c->geom, c->robot, seed,
                        bases, reinterpret_cast<const unsigned long long*>(bits), words_per_rank, words, prefix_bits,
                        (const unsigned*)offsets, (const unsigned*)tile_tot, (int)n_tiles, cap,
                        reinterpret_cast<const unsigned long long*>(counts_dev), se3_out);
@@ -2726,11 +2484,11 @@ int artp_sample_states_at_dev(artp_ctx* c, uint64_t seed, uint64_t base_index, c
   size_t blocks = (cap + 255) / 256;
   if (blocks > (size_t)c->n_cus * 16) blocks = (size_t)c->n_cus * 16;
   if (c->sampler.from_distribution)
-    hipLaunchKernelGGL(sample_states_at_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, c->stream, c->sampler, c->geom,
+    hipLaunchKernelGGL(sample_states_at_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, c->lane->stream, c->sampler, c->geom,
                      c->robot, seed, base_index, idx, reinterpret_cast<const unsigned long long*>(count_dev), cap,
                      se3_out);
   else
-    hipLaunchKernelGGL(sample_states_at_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, c->stream, c->sampler, c->geom,
+    hipLaunchKernelGGL(sample_states_at_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, c->lane->stream, c->sampler, c->geom,
                      c->robot, seed, base_index, idx, reinterpret_cast<const unsigned long long*>(count_dev), cap,
                      se3_out);
   HIP_TRY(c, hipGetLastError());
@@ -2742,17 +2500,17 @@ int artp_algorithmic_vertices_dev(artp_ctx* c, const double* se3, size_t n, uint
   std::lock_guard<std::recursive_mutex> lock(c->mu);
   if (!c->have_field[0] || !c->have_field[1]) return ARTP_ERR_NO_MAP;
   HIP_TRY(c, hipSetDevice(c->device));
-  HIP_TRY(c, hipMemsetAsync(c->d_count, 0, sizeof(unsigned long long), c->stream));
+  HIP_TRY(c, hipMemsetAsync(c->lane->d_count.get(), 0, sizeof(unsigned long long), c->lane->stream));
   if (n) {
     size_t blocks = (n + 255) / 256;
     if (blocks > (size_t)c->n_cus * 32) blocks = (size_t)c->n_cus * 32;
-    hipLaunchKernelGGL(alg_vertices_kernel, dim3((unsigned)blocks), dim3(256), 0, c->stream, c->field[0],
-                       c->field[1], c->geom, c->robot, se3, n, c->d_count);
+    hipLaunchKernelGGL(alg_vertices_kernel, dim3((unsigned)blocks), dim3(256), 0, c->lane->stream, c->field[0],
+                       c->field[1], c->geom, c->robot, se3, n, c->lane->d_count.get());
     HIP_TRY(c, hipGetLastError());
   }
   unsigned long long v = 0;
-  HIP_TRY(c, hipMemcpyAsync(&v, c->d_count, sizeof(v), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipMemcpyAsync(&v, c->lane->d_count.get(), sizeof(v), hipMemcpyDeviceToHost, c->lane->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->lane->stream));
   *total = v;
   return ARTP_OK;
 }
@@ -2972,25 +2730,25 @@ static int cost_fc_selfcheck(artp_ctx* c) {
   float* d_edges = reinterpret_cast<float*>(d + ((fb + 15) & ~(size_t)15));
   float* d_c0 = d_edges + edges.size();
   float* d_c1 = d_c0 + (size_t)B * 3;
-  hipError_t e1 = hipMemcpyAsync(d_feat, feat.data(), fb, hipMemcpyHostToDevice, c->stream);
-  if (e1 == hipSuccess) e1 = hipMemcpyAsync(d_edges, edges.data(), eb, hipMemcpyHostToDevice, c->stream);
+  hipError_t e1 = hipMemcpyAsync(d_feat, feat.data(), fb, hipMemcpyHostToDevice, c->lane->stream);
+  if (e1 == hipSuccess) e1 = hipMemcpyAsync(d_edges, edges.data(), eb, hipMemcpyHostToDevice, c->lane->stream);
   std::vector<float> c0((size_t)B * 3), c1((size_t)B * 3);
   if (e1 == hipSuccess && !full) {
-    hipLaunchKernelGGL(fc_cost_mfma_kernel, dim3(2), dim3(256), 0, c->stream, (const float*)d_edges, (size_t)B, (const half_t*)d_feat, g,
-                       (const char*)c->d_fc_mfma, d_c0);
-    hipLaunchKernelGGL(fc_cost_kernel<FcWeights>, dim3((B + 255) / 256), dim3(256), 0, c->stream, (const float*)d_edges, (size_t)B,
-                       (const half_t*)d_feat, g, (const float*)c->d_fc, d_c1);
+    hipLaunchKernelGGL(fc_cost_mfma_kernel, dim3(2), dim3(256), 0, c->lane->stream, (const float*)d_edges, (size_t)B, (const half_t*)d_feat, g,
+                       (const char*)c->d_fc_mfma.get(), d_c0);
+    hipLaunchKernelGGL(fc_cost_kernel<FcWeights>, dim3((B + 255) / 256), dim3(256), 0, c->lane->stream, (const float*)d_edges, (size_t)B,
+                       (const half_t*)d_feat, g, (const float*)c->d_fc.get(), d_c1);
     e1 = hipGetLastError();
   } else if (e1 == hipSuccess) {
-    hipLaunchKernelGGL(fc_cost_mfma_full_kernel, dim3(2), dim3(256), 0, c->stream, (const float*)d_edges, (size_t)B,
-                       (const half_t*)d_feat, g, (const char*)c->d_fc_mfma, d_c0);
-    hipLaunchKernelGGL(fc_cost_kernel<FcWeightsFull>, dim3((B + 255) / 256), dim3(256), 0, c->stream, (const float*)d_edges, (size_t)B,
-                       (const half_t*)d_feat, g, (const float*)c->d_fc, d_c1);
+    hipLaunchKernelGGL(fc_cost_mfma_full_kernel, dim3(2), dim3(256), 0, c->lane->stream, (const float*)d_edges, (size_t)B,
+                       (const half_t*)d_feat, g, (const char*)c->d_fc_mfma.get(), d_c0);
+    hipLaunchKernelGGL(fc_cost_kernel<FcWeightsFull>, dim3((B + 255) / 256), dim3(256), 0, c->lane->stream, (const float*)d_edges, (size_t)B,
+                       (const half_t*)d_feat, g, (const float*)c->d_fc.get(), d_c1);
     e1 = hipGetLastError();
   }
-  if (e1 == hipSuccess) e1 = hipMemcpyAsync(c0.data(), d_c0, cb, hipMemcpyDeviceToHost, c->stream);
-  if (e1 == hipSuccess) e1 = hipMemcpyAsync(c1.data(), d_c1, cb, hipMemcpyDeviceToHost, c->stream);
-  if (e1 == hipSuccess) e1 = hipStreamSynchronize(c->stream);
+  if (e1 == hipSuccess) e1 = hipMemcpyAsync(c0.data(), d_c0, cb, hipMemcpyDeviceToHost, c->lane->stream);
+  if (e1 == hipSuccess) e1 = hipMemcpyAsync(c1.data(), d_c1, cb, hipMemcpyDeviceToHost, c->lane->stream);
+  if (e1 == hipSuccess) e1 = hipStreamSynchronize(c->lane->stream);
   (void)hipFree(d);
   HIP_TRY(c, e1);
   float worst = 0.f;
@@ -3078,25 +2836,25 @@ int artp_cost_load_weights(artp_ctx* c, const void* blob, size_t bytes) {
                   p32[((size_t)(kh + 1) * P32::KH_FR + (size_t)ks * P32::KS_FR + sh * P32::SH_FR + co * 2 + kq) * 8 + j] =
                       f32_to_f16_bits(v);
                 }
-      if (c->d_convw_p32) HIP_TRY(c, hipFree(c->d_convw_p32));
-      c->d_convw_p32 = nullptr;
-      HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_convw_p32), p32.size() * 2));
-      HIP_TRY(c, hipMemcpy(c->d_convw_p32, p32.data(), p32.size() * 2, hipMemcpyHostToDevice));
+      HIP_TRY(c, c->d_convw_p32.reset());
+      HIP_TRY(c, c->d_convw_p32.reserve(p32.size() * 2));
+      HIP_TRY(c, hipMemcpy(c->d_convw_p32.get(), p32.data(), p32.size() * 2, hipMemcpyHostToDevice));
     }
 #endif
     w += (size_t)s.cout * s.cin * s.kh * s.kw;
-    if (c->d_convw[l]) HIP_TRY(c, hipFree(c->d_convw[l]));
-    c->d_convw[l] = nullptr;
-    if (c->d_convb[l]) HIP_TRY(c, hipFree(c->d_convb[l]));
-    c->d_convb[l] = nullptr;
+    // every load frees the old conv blocks and allocates the new ones at exactly their size (the two networks' differ).
+    // The free is also what keeps a reload behind cost kernels still reading the old weights on a lane: it waits for
+    // the device, and the first one runs before any copy below (which the lanes' non-blocking streams do not wait for).
+    HIP_TRY(c, c->d_convw[l].reset());
+    HIP_TRY(c, c->d_convb[l].reset());
     if (l == 4) {
-      HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_convw[l]), packed.size() * 2));
-      HIP_TRY(c, hipMemcpy(c->d_convw[l], packed.data(), packed.size() * 2, hipMemcpyHostToDevice));
+      HIP_TRY(c, c->d_convw[l].reserve(packed.size() * 2));
+      HIP_TRY(c, hipMemcpy(c->d_convw[l].get(), packed.data(), packed.size() * 2, hipMemcpyHostToDevice));
     }
-    HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_convb[l]), 64 * sizeof(float)));
+    HIP_TRY(c, c->d_convb[l].reserve(64 * sizeof(float)));
     float bias[64] = {0};
     std::memcpy(bias, w, s.cout * sizeof(float));
-    HIP_TRY(c, hipMemcpy(c->d_convb[l], bias, sizeof(bias), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(c->d_convb[l].get(), bias, sizeof(bias), hipMemcpyHostToDevice));
     w += s.cout;
   }
   {
@@ -3128,8 +2886,8 @@ int artp_cost_load_weights(artp_ctx* c, const void* blob, size_t bytes) {
         for (int k = 0; k < 25; ++k) h12[co * 25 + k] = (float)wc[co][k];
         h12[600 + co] = (float)bc[co];
       }
-      if (!c->d_c12) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_c12), sizeof(h12)));
-      HIP_TRY(c, hipMemcpy(c->d_c12, h12, sizeof(h12), hipMemcpyHostToDevice));
+      HIP_TRY(c, c->d_c12.reserve(sizeof(h12)));
+      HIP_TRY(c, hipMemcpy(c->d_c12.get(), h12, sizeof(h12), hipMemcpyHostToDevice));
     }
     {
       // conv12_mfma_kernel's operand: [channel tile t][hi, lo][lane][8 half floats] + bias[32].  Lane l = (m = l & 15, g = l >> 4)
@@ -3150,8 +2908,8 @@ int artp_cost_load_weights(artp_ctx* c, const void* blob, size_t bytes) {
       float b32[32] = {0};
       for (int co = 0; co < C1; ++co) b32[co] = (float)bc[co];
       std::memcpy(blob.data() + (size_t)C12M_FRAG_HALFS * 2, b32, sizeof(b32));
-      if (!c->d_c12m) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_c12m), blob.size()));
-      HIP_TRY(c, hipMemcpy(c->d_c12m, blob.data(), blob.size(), hipMemcpyHostToDevice));
+      HIP_TRY(c, c->d_c12m.reserve(blob.size()));
+      HIP_TRY(c, hipMemcpy(c->d_c12m.get(), blob.data(), blob.size(), hipMemcpyHostToDevice));
     }
     // conv3..5 for conv345_kernel: K walked in 16-byte chunks over the whole (kh, kw, cin) window; fragment
     // [ks][nt][lane][8]: lane l, element j holds B[k][n] with chunk q = 4 ks + (l >> 4), k = 8 q + j, n = 16 nt + (l & 15)
@@ -3172,16 +2930,15 @@ int artp_cost_load_weights(artp_ctx* c, const void* blob, size_t bytes) {
               }
               packed[(((size_t)ks * s.nt + nt) * 64 + ln) * 8 + j] = f32_to_f16_bits(v);
             }
-      if (c->d_convw_chunk[l]) HIP_TRY(c, hipFree(c->d_convw_chunk[l]));
-      c->d_convw_chunk[l] = nullptr;
-      HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_convw_chunk[l]), packed.size() * 2));
-      HIP_TRY(c, hipMemcpy(c->d_convw_chunk[l], packed.data(), packed.size() * 2, hipMemcpyHostToDevice));
+      HIP_TRY(c, c->d_convw_chunk[l].reset());
+      HIP_TRY(c, c->d_convw_chunk[l].reserve(packed.size() * 2));
+      HIP_TRY(c, hipMemcpy(c->d_convw_chunk[l].get(), packed.data(), packed.size() * 2, hipMemcpyHostToDevice));
       wl += (size_t)s.cout * s.cin * 9 + s.cout;
     }
   }
   // the FC blobs are sized for the larger (full-width) network: a switch reuses them
-  if (!c->d_fc) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_fc), FcWeightsFull::TOTAL * sizeof(float)));
-  HIP_TRY(c, hipMemcpy(c->d_fc, w, (size_t)net.fc_floats * sizeof(float), hipMemcpyHostToDevice));
+  HIP_TRY(c, c->d_fc.reserve(FcWeightsFull::TOTAL * sizeof(float)));
+  HIP_TRY(c, hipMemcpy(c->d_fc.get(), w, (size_t)net.fc_floats * sizeof(float), hipMemcpyHostToDevice));
   {
     std::vector<unsigned char> blob;
     if (net.version == 1)
@@ -3189,18 +2946,15 @@ int artp_cost_load_weights(artp_ctx* c, const void* blob, size_t bytes) {
     else
       fc_mfma_pack_full(w, &blob);
     static_assert(FcMfmaFull::TOTAL >= FcMfma::TOTAL, "one allocation for both");
-    if (!c->d_fc_mfma) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_fc_mfma), FcMfmaFull::TOTAL));
-    HIP_TRY(c, hipMemcpy(c->d_fc_mfma, blob.data(), blob.size(), hipMemcpyHostToDevice));
+    HIP_TRY(c, c->d_fc_mfma.reserve(FcMfmaFull::TOTAL));
+    HIP_TRY(c, hipMemcpy(c->d_fc_mfma.get(), blob.data(), blob.size(), hipMemcpyHostToDevice));
     c->fc_mfma = c->fc_mfma_wanted;   // artp_cost_set_fc_path
   }
   c->have_weights = true;
   // The MFMA form of the MLP depends on a software-managed hazard of the matrix pipe (cost_kernels.h FCM_SHAPE_CHANGE) that
   // only the device can confirm for the toolchain that built this library: a probe batch goes through it and through the
   // fp32 VALU kernel; if they disagree the context falls back to the fp32 kernels and says so (artp_cost_fc_path).
-  if (c->fc_mfma) {
-    const int rc = cost_fc_selfcheck(c);
-    if (rc != ARTP_OK) return rc;
-  }
+  if (c->fc_mfma) ARTP_TRY(cost_fc_selfcheck(c));
   return ARTP_OK;
 }
 
@@ -3233,6 +2987,17 @@ int artp_cost_fc_path(artp_ctx* c, int* mfma, int* selfcheck, float* max_abs_dif
 //  (C) conv_ksplit_kernel at Cin = Cout = 64: K per kernel row = 960 = 30 k-steps, four 16-channel n-tiles.  8-row tiles with
 //      eight wavefronts (144 KB of LDS, one workgroup per CU) where they are no more than the CUs, else 6-row tiles with four
 //      wavefronts (76 KB, two per CU).
+// Room for the two activation images (zeroed when new) and the feature map.
+static int cost_ensure_activations(artp_ctx* c, size_t act_bytes, size_t feat_bytes) {
+  for (auto& act : c->d_act)
+    if (act.capacity() < act_bytes) {
+      HIP_TRY(c, act.reserve(act_bytes));
+      HIP_TRY(c, hipMemset(act.get(), 0, act_bytes));
+    }
+  HIP_TRY(c, c->d_feat.reserve(feat_bytes));
+  return ARTP_OK;
+}
+
 static int cost_run_cnn_full(artp_ctx* c, const float* d_map, int H, int W) {
   constexpr int C = 64, T = 12;
   const int h2 = H - 4, w2 = W - 4, hp = h2 / 2, wpp = w2 / 2;
@@ -3243,24 +3008,9 @@ static int cost_run_cnn_full(artp_ctx* c, const float* d_map, int H, int W) {
   }
   // conv5's output [h5][w5][64] halfs; (H-2)(W-2) * 48 bytes (the light path's sizing) is more whenever hf >= 3
   const size_t act_bytes = std::max((size_t)(H - 2) * (W - 2) * 24 * 2, (size_t)h5 * w5 * C * 2) + 8192;
-  if (c->act_cap < act_bytes) {
-    for (int l = 0; l < 2; ++l) {
-      if (c->d_act[l]) HIP_TRY(c, hipFree(c->d_act[l]));
-      c->d_act[l] = nullptr;
-      HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_act[l]), act_bytes));
-      HIP_TRY(c, hipMemset(c->d_act[l], 0, act_bytes));
-    }
-    c->act_cap = act_bytes;
-  }
-  const size_t feat_bytes = (size_t)hf * wf * C * 2 + 256;
-  if (c->feat_cap < feat_bytes) {
-    if (c->d_feat) HIP_TRY(c, hipFree(c->d_feat));
-    c->d_feat = nullptr;
-    HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_feat), feat_bytes));
-    c->feat_cap = feat_bytes;
-  }
-  half_t* Bf = c->d_act[1];
-  hipStream_t st = c->stream;
+  ARTP_TRY(cost_ensure_activations(c, act_bytes, (size_t)hf * wf * C * 2 + 256));
+  half_t* Bf = c->d_act[1].get();
+  hipStream_t st = c->lane->stream;
   bool wide = false;
   {
     auto k345 = conv345_kernel<T, true, true, 32, C>;
@@ -3269,25 +3019,24 @@ static int cost_run_cnn_full(artp_ctx* c, const float* d_map, int H, int W) {
     const unsigned blocks = (unsigned)(((w5 + T - 1) / T) * ((h5 + T - 1) / T));
     // `in` is not read by the fused form (F12): the patch comes from the map
     hipLaunchKernelGGL(k345, dim3(blocks), dim3(C345_NT), lds, st, (const half_t*)Bf, hp, wpp,
-                       (const half8*)c->d_convw_chunk[0], (const float*)c->d_convb[1], (const half8*)c->d_convw_chunk[1],
-                       (const float*)c->d_convb[2], (const half8*)c->d_convw_chunk[2], (const float*)c->d_convb[3], Bf,
-                       d_map, H, W, (const half8*)c->d_c12m, (const float*)(c->d_c12m + (size_t)C12M_FRAG_HALFS * 2));
+                       (const half8*)c->d_convw_chunk[0].get(), (const float*)c->d_convb[1].get(), (const half8*)c->d_convw_chunk[1].get(),
+                       (const float*)c->d_convb[2].get(), (const half8*)c->d_convw_chunk[2].get(), (const float*)c->d_convb[3].get(), Bf,
+                       d_map, H, W, (const half8*)c->d_c12m.get(), (const float*)(c->d_c12m.get() + (size_t)C12M_FRAG_HALFS * 2));
     HIP_TRY(c, hipGetLastError());
   }
   {
     auto launch = [&](auto kfn, int lds, int tr, int threads) -> int {
       HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
       const unsigned blocks = (unsigned)(((wf + 15) / 16) * ((hf + tr - 1) / tr));
-      hipLaunchKernelGGL(kfn, dim3(blocks), dim3(threads), lds, st, (const half_t*)Bf, h5, w5, (const half8*)c->d_convw[4],
-                         (const float*)c->d_convb[4], c->d_feat);
+      hipLaunchKernelGGL(kfn, dim3(blocks), dim3(threads), lds, st, (const half_t*)Bf, h5, w5, (const half8*)c->d_convw[4].get(),
+                         (const float*)c->d_convb[4].get(), c->d_feat.get());
       return ARTP_OK;
     };
     const long tiles8 = (long)((wf + 15) / 16) * ((hf + 7) / 8);
     wide = tiles8 <= c->n_cus;
-    const int rcl = wide
+    ARTP_TRY(wide
                         ? launch(conv_ksplit_kernel<15, 15, C, C, 4, true, 8, 8>, ConvKsplitCfg<15, 15, C, C, 4, true, 8, 8>::LDS_BYTES, 8, 512)
-                        : launch(conv_ksplit_kernel<15, 15, C, C, 4, true, 6>, ConvKsplitCfg<15, 15, C, C, 4, true, 6>::LDS_BYTES, 6, 256);
-    if (rcl != ARTP_OK) return rcl;
+                        : launch(conv_ksplit_kernel<15, 15, C, C, 4, true, 6>, ConvKsplitCfg<15, 15, C, C, 4, true, 6>::LDS_BYTES, 6, 256));
   }
   HIP_TRY(c, hipGetLastError());
   c->feat_h = hf;
@@ -3310,25 +3059,10 @@ static int cost_run_cnn(artp_ctx* c, const float* d_map, int H, int W) {
     return ARTP_ERR_INVALID_ARG;
   }
   const size_t act_bytes = (size_t)h1 * w1 * 24 * 2 + 8192;
-  if (c->act_cap < act_bytes) {
-    for (int l = 0; l < 2; ++l) {
-      if (c->d_act[l]) HIP_TRY(c, hipFree(c->d_act[l]));
-      c->d_act[l] = nullptr;
-      HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_act[l]), act_bytes));
-      HIP_TRY(c, hipMemset(c->d_act[l], 0, act_bytes));
-    }
-    c->act_cap = act_bytes;
-  }
-  const size_t feat_bytes = (size_t)hf * wf * 48 * 2 + 256;
-  if (c->feat_cap < feat_bytes) {
-    if (c->d_feat) HIP_TRY(c, hipFree(c->d_feat));
-    c->d_feat = nullptr;
-    HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_feat), feat_bytes));
-    c->feat_cap = feat_bytes;
-  }
-  half_t* A = c->d_act[0];
-  half_t* Bf = c->d_act[1];
-  hipStream_t st = c->stream;
+  ARTP_TRY(cost_ensure_activations(c, act_bytes, (size_t)hf * wf * 48 * 2 + 256));
+  half_t* A = c->d_act[0].get();
+  half_t* Bf = c->d_act[1].get();
+  hipStream_t st = c->lane->stream;
   bool fuse12 = false;
   int forms[4] = {1, 0, 0, 256};   // -> c->cost_forms once the update has succeeded
   {
@@ -3350,12 +3084,12 @@ static int cost_run_cnn(artp_ctx* c, const float* d_map, int H, int W) {
     if (fuse12) {
     } else if (c12m) {
       const unsigned blocks_m = (unsigned)(((wpp + C12M_PX - 1) / C12M_PX) * ((hp + C12M_PY - 1) / C12M_PY));
-      hipLaunchKernelGGL(conv12_mfma_kernel, dim3(blocks_m), dim3(256), 0, st, d_map, H, W, (const half8*)c->d_c12m,
-                         (const float*)(c->d_c12m + (size_t)C12M_FRAG_HALFS * 2), A);
+      hipLaunchKernelGGL(conv12_mfma_kernel, dim3(blocks_m), dim3(256), 0, st, d_map, H, W, (const half8*)c->d_c12m.get(),
+                         (const float*)(c->d_c12m.get() + (size_t)C12M_FRAG_HALFS * 2), A);
     } else {
       const unsigned blocks_a = (unsigned)(((wpp + C12_PT - 1) / C12_PT) * ((hp + C12_PT - 1) / C12_PT));
       hipLaunchKernelGGL(conv12_pool_kernel, dim3(blocks_a), dim3(256), 0, st, d_map, H, W,
-                         (const float*)c->d_c12, (const float*)(c->d_c12 + 600), A);
+                         (const float*)c->d_c12.get(), (const float*)(c->d_c12.get() + 600), A);
     }
 #endif
     // tile edge of (B): one workgroup per CU, and a partly filled last round costs a full round -- rounds x patch
@@ -3368,10 +3102,10 @@ static int cost_run_cnn(artp_ctx* c, const float* d_map, int H, int W) {
       HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k345), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
       const unsigned blocks_b = (unsigned)(((w5 + t - 1) / t) * ((h5 + t - 1) / t));
       hipLaunchKernelGGL(k345, dim3(blocks_b), dim3(C345_NT), lds, st, (const half_t*)A, hp, wpp,
-                         (const half8*)c->d_convw_chunk[0], (const float*)c->d_convb[1], (const half8*)c->d_convw_chunk[1],
-                         (const float*)c->d_convb[2], (const half8*)c->d_convw_chunk[2], (const float*)c->d_convb[3], Bf,
-                         (const float*)d_map, H, W, (const half8*)c->d_c12m,
-                         (const float*)(c->d_c12m + (size_t)C12M_FRAG_HALFS * 2));
+                         (const half8*)c->d_convw_chunk[0].get(), (const float*)c->d_convb[1].get(), (const half8*)c->d_convw_chunk[1].get(),
+                         (const float*)c->d_convb[2].get(), (const half8*)c->d_convw_chunk[2].get(), (const float*)c->d_convb[3].get(), Bf,
+                         (const float*)d_map, H, W, (const half8*)c->d_c12m.get(),
+                         (const float*)(c->d_c12m.get() + (size_t)C12M_FRAG_HALFS * 2));
       return ARTP_OK;
     };
     // (round 4: 12 added -- 400 x 400 is 256 tiles of 12 = ONE round on all 256 CUs against 144 tiles of 16 on 144 CUs)
@@ -3425,8 +3159,8 @@ static int cost_run_cnn(artp_ctx* c, const float* d_map, int H, int W) {
     auto launch = [&](auto kfn, int lds, int tr, int threads = 256) -> int {
       HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
       const unsigned blocks = (unsigned)(((wf + 15) / 16) * ((hf + tr - 1) / tr));
-      hipLaunchKernelGGL(kfn, dim3(blocks), dim3(threads), lds, st, (const half_t*)A, h5, w5, (const half8*)c->d_convw[4],
-                         (const float*)c->d_convb[4], c->d_feat);
+      hipLaunchKernelGGL(kfn, dim3(blocks), dim3(threads), lds, st, (const half_t*)A, h5, w5, (const half8*)c->d_convw[4].get(),
+                         (const float*)c->d_convb[4].get(), c->d_feat.get());
       return ARTP_OK;
     };
     int rcl;
@@ -3449,8 +3183,8 @@ static int cost_run_cnn(artp_ctx* c, const float* d_map, int H, int W) {
       }
       HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
       const unsigned blocks = (unsigned)(((wf + 15) / 16) * ((hf + tr - 1) / tr));
-      hipLaunchKernelGGL(kfn, dim3(blocks), dim3(threads), lds, st, (const half_t*)A, h5, w5, (const half8*)c->d_convw[4],
-                         (const float*)c->d_convb[4], c->d_feat);
+      hipLaunchKernelGGL(kfn, dim3(blocks), dim3(threads), lds, st, (const half_t*)A, h5, w5, (const half8*)c->d_convw[4].get(),
+                         (const float*)c->d_convb[4].get(), c->d_feat.get());
       return ARTP_OK;
     };
     int rcl;
@@ -3475,8 +3209,8 @@ static int cost_run_cnn(artp_ctx* c, const float* d_map, int H, int W) {
         HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         const int tps = (hf + tr - 1) / tr, tiles = ((wf + 15) / 16) * tps;
         const int g = tiles < c->n_cus ? tiles : c->n_cus;
-        hipLaunchKernelGGL(kfn, dim3((unsigned)g), dim3(threads), lds, st, (const half_t*)A, h5, w5, (const half8*)c->d_convw[4],
-                           (const float*)c->d_convb[4], c->d_feat, tps, tiles);
+        hipLaunchKernelGGL(kfn, dim3((unsigned)g), dim3(threads), lds, st, (const half_t*)A, h5, w5, (const half8*)c->d_convw[4].get(),
+                           (const float*)c->d_convb[4].get(), c->d_feat.get(), tps, tiles);
         return ARTP_OK;
       };
       int variant = 0;   // 0: BD 5, rows early; 1: BD 5, rows late; 2: BD 15, rows late  (tuning)
@@ -3518,8 +3252,8 @@ static int cost_run_cnn(artp_ctx* c, const float* d_map, int H, int W) {
       auto launch32 = [&](auto kfn, int lds, int tr) -> int {
         HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         const unsigned blocks = (unsigned)(((wf + 31) / 32) * ((hf + tr - 1) / tr));
-        hipLaunchKernelGGL(kfn, dim3(blocks), dim3(256), lds, st, (const half_t*)A, h5, w5, (const half8*)c->d_convw_p32,
-                           (const float*)c->d_convb[4], c->d_feat);
+        hipLaunchKernelGGL(kfn, dim3(blocks), dim3(256), lds, st, (const half_t*)A, h5, w5, (const half8*)c->d_convw_p32.get(),
+                           (const float*)c->d_convb[4].get(), c->d_feat.get());
         return ARTP_OK;
       };
       rcl = cost32(6) <= cost32(8) ? launch32(conv15_pair32_kernel<6>, Conv15P32Cfg<6>::LDS_BYTES, 6)
@@ -3557,17 +3291,11 @@ static int cost_update_map_impl(artp_ctx* c, const float* elev_xy, bool on_devic
   const size_t n = (size_t)rows * cols;
   const float* d_map = elev_xy;  // a device array is read where it lies (stream-ordered, like every _dev argument)
   if (!on_device) {
-    if (c->map_cap < n) {
-      if (c->d_map_f32) HIP_TRY(c, hipFree(c->d_map_f32));
-      c->d_map_f32 = nullptr;
-      HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_map_f32), n * sizeof(float)));
-      c->map_cap = n;
-    }
-    HIP_TRY(c, hipMemcpyAsync(c->d_map_f32, elev_xy, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    d_map = c->d_map_f32;
+    HIP_TRY(c, c->d_map_f32.reserve(n * sizeof(float)));
+    HIP_TRY(c, hipMemcpyAsync(c->d_map_f32.get(), elev_xy, n * sizeof(float), hipMemcpyHostToDevice, c->lane->stream));
+    d_map = c->d_map_f32.get();
   }
-  const int rc = cost_run_cnn(c, d_map, rows, cols);
-  if (rc) return rc;
+  ARTP_TRY(cost_run_cnn(c, d_map, rows, cols));
   // CostQuery.setMapParams (cost_query.py:26-35): featureResFactor = 2, mapClip = 24
   CostMapGeom& g = c->cost_geom;
   g.Fh = c->feat_h;  // predictor.features.shape[2] / shape[3] (cost_query.py:54-55): maps need not be square
@@ -3577,7 +3305,7 @@ static int cost_update_map_impl(artp_ctx* c, const float* elev_xy, bool on_devic
   g.col_bias = (int)((len_y / res - 2 * 24) / 2 * 0.5);
   g.cx = cx;
   g.cy = cy;
-  if (!on_device) HIP_TRY(c, hipStreamSynchronize(c->stream));  // the caller's host buffer is free again
+  if (!on_device) HIP_TRY(c, hipStreamSynchronize(c->lane->stream));  // the caller's host buffer is free again
   c->have_features = true;
   return ARTP_OK;
 }
@@ -3638,24 +3366,24 @@ int artp_cost_query_dev(artp_ctx* c, const float* edges, size_t b, float* cost) 
     if (c->fc_mfma) {
       size_t blocks = (b + 255) / 256;
       if (blocks > (size_t)c->n_cus * 2) blocks = (size_t)c->n_cus * 2;
-      hipLaunchKernelGGL(fc_cost_mfma_full_kernel, dim3((unsigned)blocks), dim3(256), 0, c->stream, edges, b,
-                         (const half_t*)c->d_feat, c->cost_geom, (const char*)c->d_fc_mfma, cost);
+      hipLaunchKernelGGL(fc_cost_mfma_full_kernel, dim3((unsigned)blocks), dim3(256), 0, c->lane->stream, edges, b,
+                         (const half_t*)c->d_feat.get(), c->cost_geom, (const char*)c->d_fc_mfma.get(), cost);
     } else {
-      hipLaunchKernelGGL(fc_cost_kernel<FcWeightsFull>, dim3((unsigned)((b + 255) / 256)), dim3(256), 0, c->stream, edges, b,
-                         (const half_t*)c->d_feat, c->cost_geom, (const float*)c->d_fc, cost);
+      hipLaunchKernelGGL(fc_cost_kernel<FcWeightsFull>, dim3((unsigned)((b + 255) / 256)), dim3(256), 0, c->lane->stream, edges, b,
+                         (const half_t*)c->d_feat.get(), c->cost_geom, (const float*)c->d_fc.get(), cost);
     }
   } else if (c->fc_mfma) {
     // the MLP as MFMA tiles (cost_kernels.h fc_cost_mfma_kernel): 64 edges per wavefront, 256 per workgroup
     size_t blocks = (b + 255) / 256;
     if (blocks > (size_t)c->n_cus * 3) blocks = (size_t)c->n_cus * 3;  // three workgroups per CU fit (50 KB of LDS each)
-    hipLaunchKernelGGL(fc_cost_mfma_kernel, dim3((unsigned)blocks), dim3(256), 0, c->stream, edges, b,
-                       (const half_t*)c->d_feat, c->cost_geom, (const char*)c->d_fc_mfma, cost);
+    hipLaunchKernelGGL(fc_cost_mfma_kernel, dim3((unsigned)blocks), dim3(256), 0, c->lane->stream, edges, b,
+                       (const half_t*)c->d_feat.get(), c->cost_geom, (const char*)c->d_fc_mfma.get(), cost);
   } else if (b <= (1u << 16))
-    hipLaunchKernelGGL(fc_cost_split_kernel, dim3((unsigned)((b + FC_SPLIT_EDGES - 1) / FC_SPLIT_EDGES)), dim3(256), 0, c->stream,
-                       edges, b, (const half_t*)c->d_feat, c->cost_geom, (const float*)c->d_fc, cost);
+    hipLaunchKernelGGL(fc_cost_split_kernel, dim3((unsigned)((b + FC_SPLIT_EDGES - 1) / FC_SPLIT_EDGES)), dim3(256), 0, c->lane->stream,
+                       edges, b, (const half_t*)c->d_feat.get(), c->cost_geom, (const float*)c->d_fc.get(), cost);
   else
-    hipLaunchKernelGGL(fc_cost_kernel<FcWeights>, dim3((unsigned)((b + 255) / 256)), dim3(256), 0, c->stream, edges, b,
-                       (const half_t*)c->d_feat, c->cost_geom, (const float*)c->d_fc, cost);
+    hipLaunchKernelGGL(fc_cost_kernel<FcWeights>, dim3((unsigned)((b + 255) / 256)), dim3(256), 0, c->lane->stream, edges, b,
+                       (const half_t*)c->d_feat.get(), c->cost_geom, (const float*)c->d_fc.get(), cost);
   HIP_TRY(c, hipGetLastError());
   return ARTP_OK;
 }
@@ -3675,14 +3403,14 @@ int roadmap_cost_query_dev(artp_ctx* c, const float* d_edges, size_t b, float* d
   if (!c->ext_cost_fn) return artp_cost_query_dev(c, d_edges, b, d_cost);
   if (b == 0) return ARTP_OK;
   std::vector<float> em(b * 6), c3(b * 3, 0.0f);
-  HIP_TRY(c, hipMemcpyAsync(em.data(), d_edges, b * 6 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipMemcpyAsync(em.data(), d_edges, b * 6 * sizeof(float), hipMemcpyDeviceToHost, c->lane->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->lane->stream));
   if (c->ext_cost_fn(c->ext_cost_user, em.data(), b, c3.data()) != 0) {
     c->last_error = "Motion cost call failed";   // motion_cost_objective.cpp:81
     return ARTP_ERR_COST_FUNC;
   }
-  HIP_TRY(c, hipMemcpyAsync(d_cost, c3.data(), b * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));   // c3 leaves scope
+  HIP_TRY(c, hipMemcpyAsync(d_cost, c3.data(), b * 3 * sizeof(float), hipMemcpyHostToDevice, c->lane->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->lane->stream));   // c3 leaves scope
   return ARTP_OK;
 }
 
@@ -3694,18 +3422,16 @@ int artp_cost_debug_query_cells(artp_ctx* c, const float* edges, size_t b, int32
   if (!c->have_features) return ARTP_ERR_NO_MAP;
   if (b == 0) return ARTP_OK;
   HIP_TRY(c, hipSetDevice(c->device));
-  int rc = ensure_tmp(c, 0, b * 6 * sizeof(float));
-  if (rc) return rc;
-  rc = ensure_tmp(c, 1, 2 * b * sizeof(int));
-  if (rc) return rc;
-  int* d_rc = static_cast<int*>(c->tmp[1]);
-  HIP_TRY(c, hipMemcpyAsync(c->tmp[0], edges, b * 6 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-  hipLaunchKernelGGL(cost_query_cells_kernel, dim3((unsigned)((b + 255) / 256)), dim3(256), 0, c->stream,
-                     static_cast<const float*>(c->tmp[0]), b, c->cost_geom, d_rc, d_rc + b);
+  ARTP_TRY(ensure_scratch(c, c->lane->host_args, b * 6 * sizeof(float)));
+  ARTP_TRY(ensure_scratch(c, c->lane->host_results, 2 * b * sizeof(int)));
+  int* d_rc = c->lane->host_results.as<int>();
+  HIP_TRY(c, hipMemcpyAsync(c->lane->host_args.get(), edges, b * 6 * sizeof(float), hipMemcpyHostToDevice, c->lane->stream));
+  hipLaunchKernelGGL(cost_query_cells_kernel, dim3((unsigned)((b + 255) / 256)), dim3(256), 0, c->lane->stream,
+                     c->lane->host_args.as<const float>(), b, c->cost_geom, d_rc, d_rc + b);
   HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, hipMemcpyAsync(rows_out, d_rc, b * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(cols_out, d_rc + b, b * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipMemcpyAsync(rows_out, d_rc, b * sizeof(int), hipMemcpyDeviceToHost, c->lane->stream));
+  HIP_TRY(c, hipMemcpyAsync(cols_out, d_rc + b, b * sizeof(int), hipMemcpyDeviceToHost, c->lane->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->lane->stream));
   return ARTP_OK;
 }
 
@@ -3722,15 +3448,12 @@ int artp_cost_query(artp_ctx* c, const float* edges, size_t b, float* cost) {
   if (b == 0) return ARTP_OK;
   std::lock_guard<std::recursive_mutex> lock(c->mu);
   HIP_TRY(c, hipSetDevice(c->device));
-  int rc = ensure_tmp(c, 0, b * 6 * sizeof(float));
-  if (rc) return rc;
-  rc = ensure_tmp(c, 1, b * 3 * sizeof(float));
-  if (rc) return rc;
-  HIP_TRY(c, hipMemcpyAsync(c->tmp[0], edges, b * 6 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-  rc = artp_cost_query_dev(c, static_cast<const float*>(c->tmp[0]), b, static_cast<float*>(c->tmp[1]));
-  if (rc) return rc;
-  HIP_TRY(c, hipMemcpyAsync(cost, c->tmp[1], b * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  ARTP_TRY(ensure_scratch(c, c->lane->host_args, b * 6 * sizeof(float)));
+  ARTP_TRY(ensure_scratch(c, c->lane->host_results, b * 3 * sizeof(float)));
+  HIP_TRY(c, hipMemcpyAsync(c->lane->host_args.get(), edges, b * 6 * sizeof(float), hipMemcpyHostToDevice, c->lane->stream));
+  ARTP_TRY(artp_cost_query_dev(c, c->lane->host_args.as<const float>(), b, c->lane->host_results.as<float>()));
+  HIP_TRY(c, hipMemcpyAsync(cost, c->lane->host_results.get(), b * 3 * sizeof(float), hipMemcpyDeviceToHost, c->lane->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->lane->stream));
   return ARTP_OK;
 }
 
@@ -3757,11 +3480,11 @@ int artp_cost_get_features_c(artp_ctx* c, float* out, int channels, int* fh, int
   if (!out) return ARTP_OK;
   HIP_TRY(c, hipSetDevice(c->device));
   const size_t n = (size_t)c->feat_h * c->feat_w * nc;
-  std::vector<uint16_t> tmp(n);
-  HIP_TRY(c, hipMemcpy(tmp.data(), c->d_feat, n * 2, hipMemcpyDeviceToHost));
+  std::vector<uint16_t> halfs(n);
+  HIP_TRY(c, hipMemcpy(halfs.data(), c->d_feat.get(), n * 2, hipMemcpyDeviceToHost));
   for (size_t i = 0; i < n; ++i) {
     _Float16 h;
-    std::memcpy(&h, &tmp[i], 2);
+    std::memcpy(&h, &halfs[i], 2);
     out[i] = (float)h;
   }
   return ARTP_OK;

@@ -230,21 +230,20 @@ int clearance_check(artp_ctx* c, const artp_clearance_params& p, int n_yaw) {
 // The offsets of the disc of radius R in order of increasing d^2, on the device: built the first time a context meets R,
 // then kept unchanged until artp_destroy (a kernel in flight on any stream may be reading it).
 int clearance_offsets(artp_ctx* c, int R) {
-  if (c->clear_offs[R]) return ARTP_OK;
+  if (c->clear_offs[R].get()) return ARTP_OK;
   const int S = artp::clearance_pitch(artp::FIELD_T + 2 * R);
   std::vector<int32_t> offs;
   for (int dc = -R; dc <= R; ++dc)
     for (int dr = -R; dr <= R; ++dr)
       if (dr * dr + dc * dc <= R * R) offs.push_back((int32_t)((uint32_t)(dr + dc * S) << 16) | (dr * dr + dc * dc));
   std::stable_sort(offs.begin(), offs.end(), [](int32_t a, int32_t b) { return (a & 0xffff) < (b & 0xffff); });
-  int32_t* d = nullptr;
-  HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&d), offs.size() * sizeof(int32_t)));
-  if (hipMemcpy(d, offs.data(), offs.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipFree(d);
+  DeviceBuffer<int32_t>& d = c->clear_offs[R];
+  HIP_TRY(c, d.reserve(offs.size() * sizeof(int32_t)));
+  if (hipMemcpy(d.get(), offs.data(), offs.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)d.reset();
     c->last_error = "clearance: copying the offset list failed";
     return ARTP_ERR_HIP;
   }
-  c->clear_offs[R] = d;
   c->clear_n[R] = (uint32_t)offs.size();
   return ARTP_OK;
 }
@@ -281,11 +280,11 @@ int clearance_run(artp_ctx* c, const artp_clearance_params& p, int n_yaw, int nr
   G.yaw_bits = n_yaw == 32 ? 0xffffffffu : (1u << n_yaw) - 1u;
   const size_t tiles = (size_t)G.tiles_r * ((ncols + artp::FIELD_T - 1) / artp::FIELD_T);
   if (win)
-    hipLaunchKernelGGL(artp::clearance_window_kernel, dim3((unsigned)win->n), dim3(256), artp::clearance_lds(R, n_yaw), c->stream,
-                       G, win->w, d_mask, (const int32_t*)c->clear_offs[R], d_d2, d_changed);
+    hipLaunchKernelGGL(artp::clearance_window_kernel, dim3((unsigned)win->n), dim3(256), artp::clearance_lds(R, n_yaw), c->lane->stream,
+                       G, win->w, d_mask, (const int32_t*)c->clear_offs[R].get(), d_d2, d_changed);
   else
-    hipLaunchKernelGGL(artp::clearance_map_kernel, dim3((unsigned)tiles), dim3(256), artp::clearance_lds(R, n_yaw), c->stream, G,
-                       d_mask, (const int32_t*)c->clear_offs[R], d_d2);
+    hipLaunchKernelGGL(artp::clearance_map_kernel, dim3((unsigned)tiles), dim3(256), artp::clearance_lds(R, n_yaw), c->lane->stream, G,
+                       d_mask, (const int32_t*)c->clear_offs[R].get(), d_d2);
   HIP_TRY(c, hipGetLastError());
   return ARTP_OK;
 }
@@ -303,7 +302,7 @@ int clearance_map_args(artp_ctx* c, const artp_clearance_params* p, int n_yaw, i
 // tab: the host's (m, k) table of the base objective; its device copy stays with the field (artp_field_update_clearance
 // prices with it again).
 int field_clearance_build(artp_ctx* c, artp_field* f, const double* tab) {
-  hipStream_t st = c->stream;
+  hipStream_t st = c->lane->stream;
   const artp_field_clearance_params& cp = f->cparams;
   HIP_TRY(c, f->mem.alloc(&f->d_btab, artp::FIELD_TAB));
   double* d_tab = f->d_btab;
@@ -354,10 +353,10 @@ int artp_clearance_map_dev(artp_ctx* c, const artp_clearance_params* params, int
   const uint32_t* d_mask = mask;
   if (!mask_on_device) {  // staged through the context's scratch: the host words are read before the call returns
     const size_t bytes = (size_t)nrows * ncols * sizeof(uint32_t);
-    ARTP_TRY(ensure_tmp(c, 0, bytes));
-    HIP_TRY(c, hipMemcpyAsync(c->tmp[0], mask, bytes, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    d_mask = static_cast<const uint32_t*>(c->tmp[0]);
+    ARTP_TRY(ensure_scratch(c, c->lane->host_args, bytes));
+    HIP_TRY(c, hipMemcpyAsync(c->lane->host_args.get(), mask, bytes, hipMemcpyHostToDevice, c->lane->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->lane->stream));
+    d_mask = c->lane->host_args.as<const uint32_t>();
   }
   return clearance_run(c, *params, n_yaw, nrows, ncols, d_mask, d2_dev);
 }
@@ -369,10 +368,10 @@ int artp_clearance_map(artp_ctx* c, const artp_clearance_params* params, int n_y
   ARTP_TRY(clearance_map_args(c, params, n_yaw, nrows, ncols));
   HIP_TRY(c, hipSetDevice(c->device));
   const size_t bytes = (size_t)nrows * ncols * n_yaw * sizeof(uint16_t);
-  ARTP_TRY(ensure_tmp(c, 1, bytes));
-  ARTP_TRY(artp_clearance_map_dev(c, params, n_yaw, nrows, ncols, mask, mask_on_device, static_cast<uint16_t*>(c->tmp[1])));
-  HIP_TRY(c, hipMemcpyAsync(d2_out, c->tmp[1], bytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  ARTP_TRY(ensure_scratch(c, c->lane->host_results, bytes));
+  ARTP_TRY(artp_clearance_map_dev(c, params, n_yaw, nrows, ncols, mask, mask_on_device, c->lane->host_results.as<uint16_t>()));
+  HIP_TRY(c, hipMemcpyAsync(d2_out, c->lane->host_results.get(), bytes, hipMemcpyDeviceToHost, c->lane->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->lane->stream));
   return ARTP_OK;
 }
 
@@ -421,8 +420,8 @@ int artp_field_clearance(artp_field* f, uint16_t* d2_out) {
     return ARTP_ERR_INVALID_ARG;
   }
   HIP_TRY(c, hipSetDevice(c->device));
-  HIP_TRY(c, hipMemcpyAsync(d2_out, f->d_d2, f->n_nodes * sizeof(uint16_t), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipMemcpyAsync(d2_out, f->d_d2, f->n_nodes * sizeof(uint16_t), hipMemcpyDeviceToHost, c->lane->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->lane->stream));
   return ARTP_OK;
 }
 
@@ -451,7 +450,7 @@ int artp_field_update_clearance(artp_field* f, const uint32_t* new_mask, int mas
       f, "artp_field_update_clearance", new_mask, mask_on_device, sub, refresh_heights != 0, same_map, &f->custats,
       [&](unsigned long long* cnt, artp_field_clearance_update_stats_t* us, bool* run) -> int {
         if (!cnt[0] && !cnt[3]) return ARTP_OK;
-        hipStream_t st = c->stream;
+        hipStream_t st = c->lane->stream;
         const int R = f->cparams.clearance.radius_cells;
         const ClearTiles cw = clearance_window(G, sub, R), pw = clearance_window(G, sub, R + 1);
         StreamTimer<3> tm(st);

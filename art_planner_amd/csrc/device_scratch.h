@@ -1,6 +1,6 @@
-// device_scratch.h -- who frees temporary device memory, and the one pair of error macros of the host code.
-// Includes the HIP runtime and standard headers only, so it compiles alone on the CPU (tests/cpp/device_scratch_test.cpp).
-// The macros expand ARTP_OK / ARTP_ERR_HIP (include/artp_c.h) where they are used.
+// device_scratch.h -- who frees device memory, and the one pair of error macros of the host code (pinned host memory:
+// pinned_buffer.h).  Includes the HIP runtime and standard headers only, so it compiles alone on the CPU
+// (tests/cpp/device_scratch_test.cpp).  The macros expand ARTP_OK / ARTP_ERR_HIP (include/artp_c.h) where they are used.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -72,4 +72,45 @@ class DeviceScratch {
     return true;
   }
   std::vector<void*> ptrs_;
+};
+
+// One grow-only block of device memory with its owner: a member of whatever keeps the block (artp_ctx, a lane).  The
+// caller decides how much to ask for (padding is its policy); the block is freed with its owner.
+template <class T = void>
+class DeviceBuffer {
+ public:
+  DeviceBuffer() = default;
+  DeviceBuffer(const DeviceBuffer&) = delete;
+  DeviceBuffer& operator=(const DeviceBuffer&) = delete;
+  ~DeviceBuffer() { (void)reset(); }
+  // Nothing if `bytes` fit; else the old block is freed FIRST (peak memory: one block), then exactly `bytes` are
+  // allocated.  After a failure the buffer is empty -- null and capacity 0 -- so the next request allocates again.
+  hipError_t reserve(size_t bytes) {
+    if (cap_ >= bytes) return hipSuccess;
+    hipError_t e = reset();
+    if (e == hipSuccess) e = hipMalloc(&p_, bytes);
+    if (e != hipSuccess) p_ = nullptr;
+    cap_ = p_ ? bytes : 0;
+    return e;
+  }
+  hipError_t reset() {  // frees the block now
+    void* p = p_;
+    p_ = nullptr;
+    cap_ = 0;
+    return p ? hipFree(p) : hipSuccess;
+  }
+  // a block that hipFree frees but hipMalloc did not make (hipExtMallocWithFlags) is freed here from now on
+  void adopt(void* p, size_t bytes) {
+    (void)reset();
+    p_ = p;
+    cap_ = p ? bytes : 0;
+  }
+  T* get() const { return static_cast<T*>(p_); }
+  template <class U>
+  U* as() const { return static_cast<U*>(p_); }
+  size_t capacity() const { return cap_; }
+
+ private:
+  void* p_ = nullptr;
+  size_t cap_ = 0;
 };

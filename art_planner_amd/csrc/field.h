@@ -862,7 +862,7 @@ namespace {
 
 // the caller has set the device
 void field_free(artp_field* f) {
-  (void)hipStreamSynchronize(f->ctx->stream);
+  (void)hipStreamSynchronize(f->ctx->lane->stream);
   delete f;
 }
 
@@ -951,7 +951,7 @@ struct FieldRounds {
 template <class Launch>
 int field_rounds(artp_field* f, int batch, const char* too_many, FieldRounds* out, Launch&& launch) {
   artp_ctx* c = f->ctx;
-  hipStream_t st = c->stream;
+  hipStream_t st = c->lane->stream;
   unsigned* counters = f->d_flags + 2 * f->n_tiles;
   const uint64_t cap = (uint64_t)f->n_nodes + 2;
   unsigned seen = 0;
@@ -978,7 +978,7 @@ int field_rounds(artp_field* f, int batch, const char* too_many, FieldRounds* ou
 template <int PHASE, bool UNSUP>
 int field_pass(artp_field* f, unsigned* d_seed, FieldRounds* out) {
   artp_ctx* c = f->ctx;
-  hipStream_t st = c->stream;
+  hipStream_t st = c->lane->stream;
   const artp::FieldGrid& G = f->grid;
   const char* too_many = UNSUP ? "artp_field_update: more unsupport rounds than nodes" : "artp_field_compute: more rounds than nodes";
   HIP_TRY(c, hipMemsetAsync(f->d_flags, 0, (2 * f->n_tiles + 4) * sizeof(unsigned), st));
@@ -1014,7 +1014,7 @@ int field_pass(artp_field* f, unsigned* d_seed, FieldRounds* out) {
 
 int field_count_reached(artp_field* f, uint64_t* reached) {
   artp_ctx* c = f->ctx;
-  hipStream_t st = c->stream;
+  hipStream_t st = c->lane->stream;
   unsigned long long* d_count = reinterpret_cast<unsigned long long*>(f->d_out);  // >= 8 doubles since the compute
   HIP_TRY(c, hipMemsetAsync(d_count, 0, sizeof(unsigned long long), st));
   hipLaunchKernelGGL(artp::field_count_kernel, dim3((unsigned)((f->n_nodes + 255) / 256)), dim3(256), 0, st, f->n_nodes,
@@ -1034,7 +1034,7 @@ int field_count_reached(artp_field* f, uint64_t* reached) {
 // their tiles flagged in d_acc and d_wacc, their number added to d_ucnt[5]).  The scratch is allocated when there is
 // none and left to the caller.  ms[0..2] += the device time of the three steps, *chunks += the query calls.
 int field_learned_table(artp_ctx* c, artp_field* f, bool reprice, double ms[3], uint64_t* chunks) {
-  hipStream_t st = c->stream;
+  hipStream_t st = c->lane->stream;
   const artp::FieldGrid& G = f->grid;
   const artp_field_learned_params& lp = f->lparams;
   const artp::FieldPricing price{lp.w_energy, lp.w_time, lp.w_risk, lp.risk_threshold};
@@ -1093,7 +1093,7 @@ int field_clearance_build(artp_ctx* c, artp_field* f, const double* tab);  // cl
 
 int field_compute_impl(artp_ctx* c, artp_field* f, const uint32_t* mask, int mask_on_device, const int* sources,
                        size_t n_sources) {
-  hipStream_t st = c->stream;
+  hipStream_t st = c->lane->stream;
   const artp::FieldGrid& G = f->grid;
   const bool learned = G.objective == 2, wtab = artp::field_has_wtab(G);
   const size_t tab_doubles = wtab ? artp::field_wtab_slots(G) : (size_t)artp::FIELD_TAB;
@@ -1169,7 +1169,7 @@ int field_update_scratch(artp_field* f, bool stage, bool wacc = false) {
   artp_ctx* c = f->ctx;
   if (!f->d_src) {
     HIP_TRY(c, f->mem.alloc(&f->d_src, f->h_src.size()));
-    HIP_TRY(c, hipMemcpyAsync(f->d_src, f->h_src.data(), f->h_src.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(f->d_src, f->h_src.data(), f->h_src.size() * sizeof(int), hipMemcpyHostToDevice, c->lane->stream));
   }
   ARTP_TRY(field_lazy(f, &f->d_snap, f->n_nodes));
   ARTP_TRY(field_lazy(f, &f->d_acc, f->n_tiles));
@@ -1183,7 +1183,7 @@ int field_update_scratch(artp_field* f, bool stage, bool wacc = false) {
 // the tiles flagged so far.
 int field_update_passes(artp_field* f, artp_field_update_stats_t* us) {
   artp_ctx* c = f->ctx;
-  hipStream_t st = c->stream;
+  hipStream_t st = c->lane->stream;
   HIP_TRY(c, hipMemcpyAsync(f->d_snap, f->d_dist, f->n_nodes * sizeof(double), hipMemcpyDeviceToDevice, st));
   FieldRounds unsup[2], relax[2];
   int rc = field_pass<0, true>(f, f->d_acc, &unsup[0]);
@@ -1212,7 +1212,7 @@ int field_update_passes(artp_field* f, artp_field_update_stats_t* us) {
 int field_update_diff(artp_field* f, const uint32_t* new_mask, int mask_on_device, const artp::FieldSub& sub, bool refresh,
                       const SamplerDev& sm, unsigned long long cnt[5]) {
   artp_ctx* c = f->ctx;
-  hipStream_t st = c->stream;
+  hipStream_t st = c->lane->stream;
   const artp::FieldGrid& G = f->grid;
   const uint32_t* nm = new_mask;
   if (!mask_on_device) {  // the columns of sub_rect only, to the same place of a buffer in the field's layout
@@ -1282,11 +1282,11 @@ void field_store_stats(const artp_field_update_stats_t& ps, double passes_ms, St
 // the tiles flagged in d_wacc counted into d_ucnt[6]; cnt[5 .. 5 + n) read from the device (synchronises)
 int field_weight_counts(artp_field* f, unsigned long long* cnt, int n) {
   artp_ctx* c = f->ctx;
-  hipLaunchKernelGGL(artp::field_count_flags_kernel, dim3((unsigned)((f->n_tiles + 255) / 256)), dim3(256), 0, c->stream,
+  hipLaunchKernelGGL(artp::field_count_flags_kernel, dim3((unsigned)((f->n_tiles + 255) / 256)), dim3(256), 0, c->lane->stream,
                      (uint32_t)f->n_tiles, (const unsigned*)f->d_wacc, f->d_ucnt);
   HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, hipMemcpyAsync(cnt + 5, f->d_ucnt + 5, n * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipMemcpyAsync(cnt + 5, f->d_ucnt + 5, n * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->lane->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->lane->stream));
   return ARTP_OK;
 }
 
@@ -1300,7 +1300,7 @@ int field_update_run(artp_field* f, const char* who, const uint32_t* new_mask, i
                      bool refresh, bool adopt, Stats* stored, Middle&& middle) {
   artp_ctx* c = f->ctx;
   HIP_TRY(c, hipSetDevice(c->device));
-  hipStream_t st = c->stream;
+  hipStream_t st = c->lane->stream;
   const bool wtab = artp::field_has_wtab(f->grid);
   ARTP_TRY(field_update_scratch(f, new_mask && !mask_on_device, wtab));
   HIP_TRY(c, hipMemsetAsync(f->d_acc, 0, f->n_tiles * sizeof(unsigned), st));
@@ -1514,8 +1514,8 @@ int artp_field_dist(artp_field* f, double* dist_out) {
   artp_ctx* c = f->ctx;
   std::lock_guard<std::recursive_mutex> lock(c->mu);
   HIP_TRY(c, hipSetDevice(c->device));
-  HIP_TRY(c, hipMemcpyAsync(dist_out, f->d_dist, f->n_nodes * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipMemcpyAsync(dist_out, f->d_dist, f->n_nodes * sizeof(double), hipMemcpyDeviceToHost, c->lane->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->lane->stream));
   return ARTP_OK;
 }
 
@@ -1543,7 +1543,7 @@ int artp_field_path(artp_field* f, const int* target, int* nodes_out, double* se
   }
   if (cap > f->n_nodes) cap = f->n_nodes;
   HIP_TRY(c, hipSetDevice(c->device));
-  hipStream_t st = c->stream;
+  hipStream_t st = c->lane->stream;
   int rc = field_ensure_scratch(f, 3 * cap + 4, 7 * cap + 8);
   if (rc) return rc;
   // d_out: [0] = cost, [1] = the count (as long long), [8 ..] = the poses
@@ -1586,7 +1586,7 @@ int artp_field_edge_costs(artp_field* f, const int* a, const int* b, size_t n, d
   artp_ctx* c = f->ctx;
   std::lock_guard<std::recursive_mutex> lock(c->mu);
   HIP_TRY(c, hipSetDevice(c->device));
-  hipStream_t st = c->stream;
+  hipStream_t st = c->lane->stream;
   int rc = field_ensure_scratch(f, 6 * n, n + 8);
   if (rc) return rc;
   HIP_TRY(c, hipMemcpyAsync(f->d_nodes, a, 3 * n * sizeof(int), hipMemcpyHostToDevice, st));
@@ -1672,7 +1672,7 @@ int artp_field_update_learned(artp_field* f, const uint32_t* new_mask, int mask_
       f, "artp_field_update_learned", new_mask, mask_on_device, sub, false, true, &f->lustats,
       [&](unsigned long long* cnt, artp_field_learned_update_stats_t* us, bool* run) -> int {
         field_adopt_sampler(c, f);
-        hipLaunchKernelGGL(artp::field_heights_kernel, dim3((unsigned)((f->n_cells + 255) / 256)), dim3(256), 0, c->stream,
+        hipLaunchKernelGGL(artp::field_heights_kernel, dim3((unsigned)((f->n_cells + 255) / 256)), dim3(256), 0, c->lane->stream,
                            f->sampler, f->geom, f->rect, f->d_h);
         HIP_TRY(c, hipGetLastError());
         double ms[3] = {0.0, 0.0, 0.0};

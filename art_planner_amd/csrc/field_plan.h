@@ -138,7 +138,7 @@ int field_blocked_alloc(artp_field* f) {
   artp_ctx* c = f->ctx;
   const size_t words = (f->n_nodes + 1) / 2 * 2;  // whole 32-bit words
   HIP_TRY(c, f->mem.alloc(&f->d_blk, words));
-  HIP_TRY(c, hipMemsetAsync(f->d_blk, 0, words * sizeof(uint16_t), c->stream));
+  HIP_TRY(c, hipMemsetAsync(f->d_blk, 0, words * sizeof(uint16_t), c->lane->stream));
   return ARTP_OK;
 }
 
@@ -146,7 +146,7 @@ int field_blocked_alloc(artp_field* f) {
 int field_plan_passes(artp_field* f, artp_field_update_stats_t* ps) {
   const int rc = field_update_passes(f, ps);
   if (rc) {
-    (void)hipStreamSynchronize(f->ctx->stream);
+    (void)hipStreamSynchronize(f->ctx->lane->stream);
     return rc;
   }
   f->stats.reached_nodes = ps->reached_nodes;
@@ -195,7 +195,7 @@ int field_plan_scratch(artp_field* f, size_t targets, size_t states, FieldPlanBu
   if (f->plan_targets < targets || f->plan_states < states) {
     if (targets < f->plan_targets) targets = f->plan_targets;
     if (states < f->plan_states) states = f->plan_states;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->lane->stream));
     f->mem.release(f->d_plan);
     f->d_plan = nullptr;
     f->plan_targets = f->plan_states = 0;
@@ -236,7 +236,7 @@ int artp_field_block_moves(artp_field* f, const int* a, const int* b, size_t n, 
     }
   }
   HIP_TRY(c, hipSetDevice(c->device));
-  hipStream_t st = c->stream;
+  hipStream_t st = c->lane->stream;
   int rc = field_update_scratch(f, false);
   if (rc) return rc;
   rc = field_blocked_alloc(f);
@@ -271,7 +271,7 @@ int artp_field_unblock(artp_field* f, const int* sub_rect, uint64_t* unblocked) 
   ARTP_TRY(field_sub_rect(f, "artp_field_unblock", sub_rect, &sub));
   if (!f->d_blk || !f->n_blocked) return ARTP_OK;
   HIP_TRY(c, hipSetDevice(c->device));
-  hipStream_t st = c->stream;
+  hipStream_t st = c->lane->stream;
   int rc = field_update_scratch(f, false);
   if (rc) return rc;
   HIP_TRY(c, hipMemsetAsync(f->d_acc, 0, f->n_tiles * sizeof(unsigned), st));
@@ -306,8 +306,8 @@ int artp_field_blocked(artp_field* f, uint16_t* words_out) {
     return ARTP_OK;
   }
   HIP_TRY(c, hipSetDevice(c->device));
-  HIP_TRY(c, hipMemcpyAsync(words_out, f->d_blk, f->n_nodes * sizeof(uint16_t), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipMemcpyAsync(words_out, f->d_blk, f->n_nodes * sizeof(uint16_t), hipMemcpyDeviceToHost, c->lane->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->lane->stream));
   return ARTP_OK;
 }
 
@@ -334,7 +334,7 @@ int artp_field_plan(artp_field* f, const int* targets, size_t n_targets, int max
     return ARTP_ERR_NO_MAP;
   }
   HIP_TRY(c, hipSetDevice(c->device));
-  hipStream_t st = c->stream;
+  hipStream_t st = c->lane->stream;
   int rc = field_update_scratch(f, false);
   if (rc) return rc;
   rc = field_blocked_alloc(f);

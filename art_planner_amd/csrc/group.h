@@ -268,7 +268,7 @@ inline int for_each_member(artp_group* g, const std::function<int(int)>& fn) {
 // the context's lane-0 stream (what artp_sample_and_validate_dev runs on); lane 3 carries the side stream
 inline hipStream_t compute_stream(Member& mem) {
   (void)artp_set_lane(mem.ctx, 0);
-  return mem.ctx->stream;
+  return mem.ctx->lane->stream;
 }
 
 inline void free_exchange_buffers(Member& mem) {

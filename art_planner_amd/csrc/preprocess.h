@@ -574,7 +574,7 @@ bool pre_sampling_distribution(artp_ctx* c, artp_preprocessed* pp, const artp_pr
                                const double* d_verts, size_t n_vertices) {
   const int rows = pp->rows, cols = pp->cols, n = rows * cols;
   const double res = pp->len_x / rows;
-  hipStream_t st = c->stream;
+  hipStream_t st = c->lane->stream;
   const dim3 grid((unsigned)((n + 255) / 256)), blk(256);
   auto L = [&](int k) { return pp->layer(k); };
   const artp::PreGeom geom{rows, cols, (float)res, pp->pos_x, pp->pos_y, pp->len_x, pp->len_y};
@@ -715,7 +715,7 @@ int artp_preprocess_map_ex(artp_ctx* c, const artp_preprocess_inputs* in, const 
     c->last_error = "hipMalloc failed in artp_preprocess_map";
     return ARTP_ERR_HIP;
   }
-  hipStream_t st = c->stream;
+  hipStream_t st = c->lane->stream;
   const double res = len_x / rows;
   const dim3 grid((unsigned)((n + 255) / 256)), blk(256);
   auto L = [&](int k) { return pp->layer(k); };
@@ -856,20 +856,20 @@ int artp_preprocessed_change(artp_ctx* c, artp_preprocessed* map_new, const artp
   int* d_rect = reinterpret_cast<int*>(map_new->scalars() + 8);
   unsigned long long* d_cnt = reinterpret_cast<unsigned long long*>(map_new->scalars() + 12);
   const int init[4] = {0x7fffffff, 0x7fffffff, -1, -1};
-  HIP_TRY(c, hipMemcpyAsync(d_rect, init, sizeof(init), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemsetAsync(d_cnt, 0, 8, c->stream));
-  hipLaunchKernelGGL(artp::change_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream,
+  HIP_TRY(c, hipMemcpyAsync(d_rect, init, sizeof(init), hipMemcpyHostToDevice, c->lane->stream));
+  HIP_TRY(c, hipMemsetAsync(d_cnt, 0, 8, c->lane->stream));
+  hipLaunchKernelGGL(artp::change_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->lane->stream,
                      (const float*)map_new->layer(PRE_ELEV), (const float*)map_new->layer(PRE_SAFETY),
                      (const float*)map_old->layer(PRE_ELEV), (const float*)map_old->layer(PRE_SAFETY), rows, cols, si, sj,
                      height_change_for_update, map_new->layer(PRE_UPDATED), d_rect, d_cnt);
   HIP_TRY(c, hipGetLastError());
   int r[4];
   unsigned long long cnt = 0;
-  HIP_TRY(c, hipMemcpyAsync(r, d_rect, sizeof(r), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(&cnt, d_cnt, 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(r, d_rect, sizeof(r), hipMemcpyDeviceToHost, c->lane->stream));
+  HIP_TRY(c, hipMemcpyAsync(&cnt, d_cnt, 8, hipMemcpyDeviceToHost, c->lane->stream));
   if (updated_out)
-    HIP_TRY(c, hipMemcpyAsync(updated_out, map_new->layer(PRE_UPDATED), (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpyAsync(updated_out, map_new->layer(PRE_UPDATED), (size_t)n * 4, hipMemcpyDeviceToHost, c->lane->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->lane->stream));
   if (rect) {
     rect[0] = cnt ? r[0] : 0;
     rect[1] = cnt ? r[1] : 0;
@@ -931,8 +931,8 @@ int artp_preprocessed_reweight_dev(artp_ctx* c, artp_preprocessed* pp, const art
   }
   if (!install_sampler) return ARTP_OK;
   float total = 0.f;
-  HIP_TRY(c, hipMemcpyAsync(&total, pp->scalars(), 4, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipMemcpyAsync(&total, pp->scalars(), 4, hipMemcpyDeviceToHost, c->lane->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->lane->stream));
   if (!(total > 0.f)) {
     c->last_error = "sample_probability is zero everywhere: nothing can be sampled on this map";
     return ARTP_ERR_NO_MAP;
@@ -953,12 +953,12 @@ static int inpaint_dev(artp_ctx* c, const float* d_in, int rows, int cols, int m
   if (rc) return rc;
   std::lock_guard<std::recursive_mutex> lock(c->mu);
   HIP_TRY(c, hipSetDevice(c->device));
-  hipStream_t st = c->stream;
+  hipStream_t st = c->lane->stream;
   unsigned char* buf = nullptr;
   DeviceScratch S;
   HIP_TRY(c, S.alloc(&buf, 4 * n + 64));
   unsigned char *q = buf, *known = buf + n, *q2 = buf + 2 * n, *known2 = buf + 3 * n;
-  unsigned long long* d_holes = reinterpret_cast<unsigned long long*>(c->d_count);
+  unsigned long long* d_holes = reinterpret_cast<unsigned long long*>(c->lane->d_count.get());
   unsigned* d_left = reinterpret_cast<unsigned*>(buf + 4 * n + (8 - (4 * n) % 8) % 8);
   const dim3 grid((unsigned)((n + 255) / 256)), blk(256);
   if (hipMemsetAsync(d_holes, 0, 8, st) != hipSuccess) return ARTP_ERR_HIP;

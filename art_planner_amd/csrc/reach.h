@@ -16,7 +16,7 @@
 namespace artp {
 
 constexpr int ARTP_REACH_MAX_YAW = 32;
-constexpr size_t ARTP_REACH_CHUNK = size_t(1) << 22;  // poses per pipeline call (bounds tmp[7] and the queues)
+constexpr size_t ARTP_REACH_CHUNK = size_t(1) << 22;  // poses per pipeline call (bounds pose_recs and the queues)
 
 struct ReachRect {
   int row0, col0, nrows, ncols;
@@ -178,26 +178,22 @@ int artp_reachability_map_dev(artp_ctx* c, int n_yaw, const int* rect, uint32_t*
   std::lock_guard<std::recursive_mutex> lock(c->mu);
   if (!c->have_field[0] || !c->have_field[1] || !reach_have_lattice(c)) return ARTP_ERR_NO_MAP;
   artp::ReachRect r;
-  int rc = reach_resolve(c, n_yaw, rect, &r);
-  if (rc) return rc;
+  ARTP_TRY(reach_resolve(c, n_yaw, rect, &r));
   HIP_TRY(c, hipSetDevice(c->device));
   const size_t cells = (size_t)r.nrows * r.ncols, per = reach_chunk_cells(n_yaw);
   const size_t chunk_poses = (cells < per ? cells : per) * (size_t)n_yaw;
-  rc = ensure_recs(c, chunk_poses);
-  if (rc) return rc;
-  rc = ensure_tmp(c, 6, chunk_poses);  // the chunk's labels
-  if (rc) return rc;
+  ARTP_TRY(ensure_recs(c, chunk_poses));
+  ARTP_TRY(ensure_scratch(c, c->lane->call_scratch, chunk_poses));  // the chunk's labels
   for (size_t c0 = 0; c0 < cells; c0 += per) {
     const size_t nc = cells - c0 < per ? cells - c0 : per;
     const size_t np = nc * (size_t)n_yaw;
-    uint8_t* labels = static_cast<uint8_t*>(c->tmp[6]);
-    hipLaunchKernelGGL(artp::reach_poses_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, c->stream, c->sampler,
+    uint8_t* labels = c->lane->call_scratch.as<uint8_t>();
+    hipLaunchKernelGGL(artp::reach_poses_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, c->lane->stream, c->sampler,
                        c->geom, r, (uint32_t)(c0 * (size_t)n_yaw), (uint32_t)np, (double*)nullptr, c->field[0],
-                       static_cast<PoseRec*>(c->tmp[7]));
+                       c->lane->pose_recs.as<PoseRec>());
     HIP_TRY(c, hipGetLastError());
-    rc = launch_validate_pipeline(c, nullptr, np, labels, true);
-    if (rc) return rc;
-    hipLaunchKernelGGL(artp::reach_pack_kernel, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, c->stream, c->sampler,
+    ARTP_TRY(launch_validate_pipeline(c, nullptr, np, labels, true));
+    hipLaunchKernelGGL(artp::reach_pack_kernel, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, c->lane->stream, c->sampler,
                        c->geom, r, (uint32_t)c0, (uint32_t)nc, (const uint8_t*)labels, mask);
     HIP_TRY(c, hipGetLastError());
   }
@@ -209,15 +205,12 @@ int artp_reachability_map(artp_ctx* c, int n_yaw, const int* rect, uint32_t* mas
   std::lock_guard<std::recursive_mutex> lock(c->mu);
   if (!c->have_field[0] || !c->have_field[1] || !reach_have_lattice(c)) return ARTP_ERR_NO_MAP;
   artp::ReachRect r;
-  int rc = reach_resolve(c, n_yaw, rect, &r);
-  if (rc) return rc;
+  ARTP_TRY(reach_resolve(c, n_yaw, rect, &r));
   HIP_TRY(c, hipSetDevice(c->device));
   const size_t cells = (size_t)r.nrows * r.ncols;
-  rc = ensure_tmp(c, 0, cells * sizeof(uint32_t));
-  if (rc) return rc;
-  rc = artp_reachability_map_dev(c, n_yaw, rect, static_cast<uint32_t*>(c->tmp[0]));
-  if (rc) return rc;
-  HIP_TRY(c, hipMemcpyAsync(mask, c->tmp[0], cells * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  ARTP_TRY(ensure_scratch(c, c->lane->host_args, cells * sizeof(uint32_t)));
+  ARTP_TRY(artp_reachability_map_dev(c, n_yaw, rect, c->lane->host_args.as<uint32_t>()));
+  HIP_TRY(c, hipMemcpyAsync(mask, c->lane->host_args.get(), cells * sizeof(uint32_t), hipMemcpyDeviceToHost, c->lane->stream));
   return check_error_flag(c);
 }
 
@@ -226,23 +219,21 @@ int artp_reachability_poses(artp_ctx* c, int n_yaw, const int* rect, double* se3
   std::lock_guard<std::recursive_mutex> lock(c->mu);
   if (!reach_have_lattice(c)) return ARTP_ERR_NO_MAP;
   artp::ReachRect r;
-  int rc = reach_resolve(c, n_yaw, rect, &r);
-  if (rc) return rc;
+  ARTP_TRY(reach_resolve(c, n_yaw, rect, &r));
   HIP_TRY(c, hipSetDevice(c->device));
   const size_t cells = (size_t)r.nrows * r.ncols, per = reach_chunk_cells(n_yaw);
   const size_t chunk_poses = (cells < per ? cells : per) * (size_t)n_yaw;
-  rc = ensure_tmp(c, 0, chunk_poses * 7 * sizeof(double));
-  if (rc) return rc;
+  ARTP_TRY(ensure_scratch(c, c->lane->host_args, chunk_poses * 7 * sizeof(double)));
   for (size_t c0 = 0; c0 < cells; c0 += per) {
     const size_t nc = cells - c0 < per ? cells - c0 : per;
     const size_t np = nc * (size_t)n_yaw, first = c0 * (size_t)n_yaw;
-    hipLaunchKernelGGL(artp::reach_poses_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, c->stream, c->sampler,
-                       c->geom, r, (uint32_t)first, (uint32_t)np, static_cast<double*>(c->tmp[0]), c->field[0],
+    hipLaunchKernelGGL(artp::reach_poses_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, c->lane->stream, c->sampler,
+                       c->geom, r, (uint32_t)first, (uint32_t)np, c->lane->host_args.as<double>(), c->field[0],
                        (PoseRec*)nullptr);
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(se3_out + 7 * first, c->tmp[0], np * 7 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(se3_out + 7 * first, c->lane->host_args.get(), np * 7 * sizeof(double), hipMemcpyDeviceToHost, c->lane->stream));
   }
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->lane->stream));
   return ARTP_OK;
 }
 

@@ -584,7 +584,7 @@ bool roadmap_sssp_dev(artp_roadmap* rm, std::vector<uint32_t>* path, double* cos
   const size_t nv = rm->nv(), ne = rm->eu.size();
   *ok = false;
   if (hipSetDevice(c->device) != hipSuccess) return false;
-  hipStream_t st = c->stream;
+  hipStream_t st = c->lane->stream;
   if (rm->d_graph_ne != ne || rm->d_graph_nv != nv || !rm->d_euv) {
     for (void* p : {(void*)rm->d_euv, (void*)rm->d_w, (void*)rm->d_dist, (void*)rm->d_pred})
       if (p) (void)hipFree(p);
@@ -685,7 +685,7 @@ int roadmap_eval_edges_dev(artp_ctx* c, const artp_roadmap_params* prm, const do
                            size_t ne, uint8_t* evalid, uint32_t* einterp, double* ecost, bool direct = false,
                            double segment_cost_step = 0.0) {
   if (ne == 0) return ARTP_OK;
-  hipStream_t st = c->stream;
+  hipStream_t st = c->lane->stream;
   double* d_cost = nullptr;
   uint8_t* d_evalid = nullptr;
   uint32_t *d_einterp = nullptr, *d_rows = nullptr, *d_off = nullptr, *d_ncost = nullptr;
@@ -812,7 +812,7 @@ static int roadmap_connect(artp_ctx* c, const artp_roadmap_params* prm, const do
   double *d_s1 = nullptr, *d_s2 = nullptr;
   void* d_cub = nullptr;
   DeviceScratch S;
-  hipStream_t st = c->stream;
+  hipStream_t st = c->lane->stream;
   HIP_TRY(c, S.alloc(&d_cnt, 1));
   // 2. k nearest neighbours
   int k = (int)prm->k_neighbors;
@@ -992,7 +992,7 @@ static int roadmap_build_impl(artp_ctx* c, const artp_roadmap_params* prm_in, co
   uint64_t* d_cnt = nullptr;
   DeviceScratch S;
   HIP_TRY(c, hipSetDevice(c->device));
-  hipStream_t st = c->stream;
+  hipStream_t st = c->lane->stream;
   HIP_TRY(c, S.alloc(&d_verts, nv * 7));
   HIP_TRY(c, S.alloc(&d_cnt, 1));
 
@@ -1203,7 +1203,7 @@ struct IncrementalGraph {
     std::sort_heap(out.begin(), out.end());
   }
   int eval_tasks(size_t n) {  // tasks -> states, valid
-    hipStream_t st = c->stream;
+    hipStream_t st = c->lane->stream;
     if (hipSetDevice(c->device) != hipSuccess) return ARTP_ERR_HIP;
     if (cap < n) {
       for (void* p : {(void*)d_tasks, (void*)d_states, (void*)d_valid}) staging.release(p);
@@ -1366,7 +1366,7 @@ static int incremental_sample_graph(IncrementalGraph& g, size_t max_vertices, ui
                                     uint64_t* n_reweights, uint64_t* budget_flags) {
   artp_ctx* c = g.c;
   const artp_roadmap_params& prm = g.prm;
-  hipStream_t st = c->stream;
+  hipStream_t st = c->lane->stream;
   const size_t batch = 4096;
   double *d_batch = nullptr, *d_compact = nullptr, *d_verts = nullptr;
   uint8_t* d_valid = nullptr;
@@ -1454,7 +1454,7 @@ static int roadmap_build_incremental(artp_ctx* c, const artp_roadmap_params* prm
     std::memcpy(sg + 7, goal7, 7 * sizeof(double));
     uint8_t ok[2] = {0, 0};
     ARTP_TRY(artp_validate_states(c, sg, 2, ok, nullptr));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->lane->stream));
     if (!ok[0] || !ok[1]) {
       c->last_error = !ok[0] ? "start state is not valid" : "goal state is not valid";
       return ARTP_ERR_INVALID_ARG;
@@ -1497,7 +1497,7 @@ static int roadmap_grow_incremental(artp_roadmap* rm, uint64_t n_more, uint64_t 
   const size_t nv = rm->nv();
   std::vector<uint8_t> vok(nv, 0);
   ARTP_TRY(artp_validate_states(c, rm->verts.data(), nv, vok.data(), nullptr));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->lane->stream));
   if (!vok[0] || !vok[1]) {
     c->last_error = !vok[0] ? "start state is not valid" : "goal state is not valid";
     return ARTP_ERR_INVALID_ARG;
@@ -1643,23 +1643,23 @@ int artp_roadmap_revalidate(artp_roadmap* rm, uint64_t out[4]) {
         rm->d_edge_cap = okk ? ne : 0;
       }
       okk = okk && S.alloc(&d_v, nv * 7) == hipSuccess && S.alloc(&d_uv, 2 * ne) == hipSuccess &&
-            hipMemcpyAsync(d_v, rm->verts.data(), nv * 7 * sizeof(double), hipMemcpyHostToDevice, c->stream) == hipSuccess &&
-            hipMemcpyAsync(d_uv, rm->eu.data(), ne * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream) == hipSuccess &&
-            hipMemcpyAsync(d_uv + ne, rm->ev.data(), ne * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream) == hipSuccess;
+            hipMemcpyAsync(d_v, rm->verts.data(), nv * 7 * sizeof(double), hipMemcpyHostToDevice, c->lane->stream) == hipSuccess &&
+            hipMemcpyAsync(d_uv, rm->eu.data(), ne * sizeof(uint32_t), hipMemcpyHostToDevice, c->lane->stream) == hipSuccess &&
+            hipMemcpyAsync(d_uv + ne, rm->ev.data(), ne * sizeof(uint32_t), hipMemcpyHostToDevice, c->lane->stream) == hipSuccess;
       std::vector<uint32_t> src, dst;  // end points in cost direction (eflip)
       if (okk && !rm->eflip.empty()) {
         src = rm->eu;
         dst = rm->ev;
         for (size_t e = 0; e < ne; ++e)
           if (rm->eflip[e]) std::swap(src[e], dst[e]);
-        okk = hipMemcpyAsync(d_uv, src.data(), ne * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream) == hipSuccess &&
-              hipMemcpyAsync(d_uv + ne, dst.data(), ne * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream) == hipSuccess;
+        okk = hipMemcpyAsync(d_uv, src.data(), ne * sizeof(uint32_t), hipMemcpyHostToDevice, c->lane->stream) == hipSuccess &&
+              hipMemcpyAsync(d_uv + ne, dst.data(), ne * sizeof(uint32_t), hipMemcpyHostToDevice, c->lane->stream) == hipSuccess;
       }
       if (okk) {
-        hipLaunchKernelGGL(artp::gather_edge_states_uv_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, c->stream,
+        hipLaunchKernelGGL(artp::gather_edge_states_uv_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, c->lane->stream,
                            (const double*)d_v, (const uint32_t*)d_uv, (const uint32_t*)(d_uv + ne), ne, rm->d_edge_states,
                            rm->d_edge_states + ne * 7);
-        okk = hipGetLastError() == hipSuccess && hipStreamSynchronize(c->stream) == hipSuccess;
+        okk = hipGetLastError() == hipSuccess && hipStreamSynchronize(c->lane->stream) == hipSuccess;
       }
       if (!okk) {
         c->last_error = "staging the edge states failed";
@@ -1832,7 +1832,7 @@ int roadmap_simplify_path_impl(artp_ctx* c, const artp_roadmap_params* prm, cons
     }
     rc = artp_check_motions(c, s1.data(), s2.data(), ne, ok2.data());
     if (rc != ARTP_OK) return rc;
-    (void)hipStreamSynchronize(c->stream);
+    (void)hipStreamSynchronize(c->lane->stream);
   }
   // DAG shortest path 0 -> n-1 (edges only go forward)
   std::vector<double> best(n, INFINITY);
@@ -2191,21 +2191,21 @@ int roadmap_check_motion_items(artp_roadmap* rm, const std::vector<uint32_t>& sr
     }
     const int rc = artp_check_motions(c, s1.data(), s2.data(), n, ok->data());
     if (rc != ARTP_OK) return rc;
-    return hipStreamSynchronize(c->stream) == hipSuccess ? ARTP_OK : ARTP_ERR_HIP;
+    return hipStreamSynchronize(c->lane->stream) == hipSuccess ? ARTP_OK : ARTP_ERR_HIP;
   }
-  // the context's host-entry staging slots (tmp[0], tmp[1]: the device entry point below does not touch them) instead of
+  // the context's host-entry staging buffers (host_args, host_results: the device entry point below does not touch them) instead of
   // four hipMalloc / hipFree pairs per call -- a hipFree alone waits for the device
   HIP_TRY(c, hipSetDevice(c->device));
-  ARTP_TRY(ensure_tmp(c, 0, nv * 7 * sizeof(double) + 2 * n * sizeof(uint32_t) + 64));
-  ARTP_TRY(ensure_tmp(c, 1, 2 * n * 7 * sizeof(double) + n + 64));
-  double* d_v = static_cast<double*>(c->tmp[0]);
+  ARTP_TRY(ensure_scratch(c, c->lane->host_args, nv * 7 * sizeof(double) + 2 * n * sizeof(uint32_t) + 64));
+  ARTP_TRY(ensure_scratch(c, c->lane->host_results, 2 * n * 7 * sizeof(double) + n + 64));
+  double* d_v = c->lane->host_args.as<double>();
   uint32_t* d_uv = reinterpret_cast<uint32_t*>(d_v + nv * 7);
-  double* d_s = static_cast<double*>(c->tmp[1]);
+  double* d_s = c->lane->host_results.as<double>();
   uint8_t* d_ok = reinterpret_cast<uint8_t*>(d_s + 2 * n * 7);
-  HIP_TRY(c, hipMemcpyAsync(d_v, rm->verts.data(), nv * 7 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(d_uv, src.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(d_uv + n, dst.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-  hipLaunchKernelGGL(artp::gather_edge_states_uv_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream,
+  HIP_TRY(c, hipMemcpyAsync(d_v, rm->verts.data(), nv * 7 * sizeof(double), hipMemcpyHostToDevice, c->lane->stream));
+  HIP_TRY(c, hipMemcpyAsync(d_uv, src.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, c->lane->stream));
+  HIP_TRY(c, hipMemcpyAsync(d_uv + n, dst.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, c->lane->stream));
+  hipLaunchKernelGGL(artp::gather_edge_states_uv_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->lane->stream,
                      (const double*)d_v, (const uint32_t*)d_uv, (const uint32_t*)(d_uv + n), n, d_s, d_s + n * 7);
   HIP_TRY(c, hipGetLastError());
   // in chunks of 2^18 motions (~13 M interior states): the pipeline's scratch (PoseRecs, queues) is sized by the largest
@@ -2214,8 +2214,8 @@ int roadmap_check_motion_items(artp_roadmap* rm, const std::vector<uint32_t>& sr
     const size_t m = std::min(n - at, (size_t)1 << 18);
     ARTP_TRY(artp_check_motions_dev(c, d_s + at * 7, d_s + (n + at) * 7, m, d_ok + at));
   }
-  HIP_TRY(c, hipMemcpyAsync(ok->data(), d_ok, n, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipMemcpyAsync(ok->data(), d_ok, n, hipMemcpyDeviceToHost, c->lane->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->lane->stream));
   return ARTP_OK;
 }
 
@@ -2528,7 +2528,7 @@ int artp_roadmap_solve(artp_roadmap* rm, double* path_se3, size_t cap_states, si
     if (np > 1) {
       const int rc = artp_check_motions(c, s1.data(), s2.data(), np - 1, ok.data());
       if (rc != ARTP_OK) return rc;
-      (void)hipStreamSynchronize(c->stream);
+      (void)hipStreamSynchronize(c->lane->stream);
     }
     size_t bad = np;
     for (size_t i = np - 1; i-- > 0;)  // the reference walks from the goal backwards

@@ -352,7 +352,7 @@ int many_device_solve(artp_roadmap* rm, const double* start7, const double* goal
                       const std::vector<double>& sw, int32_t* status, double* cost,
                       std::vector<std::vector<uint32_t>>* paths, uint64_t stats[4]) {
   artp_ctx* c = rm->ctx;
-  hipStream_t st = c->stream;
+  hipStream_t st = c->lane->stream;
   const int k = rm->k;
   const size_t nv = rm->nv(), ng = gi.size();
   size_t first_keep = 0;
@@ -663,17 +663,17 @@ int artp_roadmap_solve_many(artp_roadmap* rm, const double* start_se3, const dou
       HIP_TRY(c, B.alloc(&d_d, nq * kk));
       HIP_TRY(c, B.alloc(&d_id, nq * kk));
       HIP_TRY(c, B.alloc(&d_pr, nv));
-      HIP_TRY(c, hipMemcpyAsync(d_v, rm->verts.data(), nv * 7 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-      HIP_TRY(c, hipMemcpyAsync(d_q, q.data(), nq * 7 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-      HIP_TRY(c, hipMemcpyAsync(d_pr, pr.data(), nv, hipMemcpyHostToDevice, c->stream));
-      hipLaunchKernelGGL(artp::tree_knn_kernel, dim3(tree_blocks(nq, 4)), dim3(256), 0, c->stream, (const double*)d_v,
+      HIP_TRY(c, hipMemcpyAsync(d_v, rm->verts.data(), nv * 7 * sizeof(double), hipMemcpyHostToDevice, c->lane->stream));
+      HIP_TRY(c, hipMemcpyAsync(d_q, q.data(), nq * 7 * sizeof(double), hipMemcpyHostToDevice, c->lane->stream));
+      HIP_TRY(c, hipMemcpyAsync(d_pr, pr.data(), nv, hipMemcpyHostToDevice, c->lane->stream));
+      hipLaunchKernelGGL(artp::tree_knn_kernel, dim3(tree_blocks(nq, 4)), dim3(256), 0, c->lane->stream, (const double*)d_v,
                          (int)nv, (const uint8_t*)d_pr, (const double*)d_q, (int)nq, kk, d_id, d_d);
       HIP_TRY(c, hipGetLastError());
       sid.resize(nq * kk);
       sd.resize(nq * kk);
-      HIP_TRY(c, hipMemcpyAsync(sid.data(), d_id, nq * kk * 4, hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(c, hipMemcpyAsync(sd.data(), d_d, nq * kk * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(c, hipStreamSynchronize(c->stream));
+      HIP_TRY(c, hipMemcpyAsync(sid.data(), d_id, nq * kk * 4, hipMemcpyDeviceToHost, c->lane->stream));
+      HIP_TRY(c, hipMemcpyAsync(sd.data(), d_d, nq * kk * sizeof(double), hipMemcpyDeviceToHost, c->lane->stream));
+      HIP_TRY(c, hipStreamSynchronize(c->lane->stream));
     }
     for (size_t i = 0; i < pend.size(); ++i) {
       const double* q = goals + (size_t)pend[i] * 7;

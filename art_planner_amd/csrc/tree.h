@@ -546,13 +546,13 @@ int tree_log_reserve(artp_tree* t, size_t need) {
   HIP_TRY(c, S.alloc(&cvu, cap));
   if (t->log_n) {
     const size_t m = t->log_n;
-    HIP_TRY(c, hipMemcpyAsync(lu, t->d_lu, m * 4, hipMemcpyDeviceToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(lv, t->d_lv, m * 4, hipMemcpyDeviceToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(lb, t->d_lbatch, m * 4, hipMemcpyDeviceToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(lval, t->d_lvalid, m, hipMemcpyDeviceToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(cuv, t->d_lcuv, m * 8, hipMemcpyDeviceToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(cvu, t->d_lcvu, m * 8, hipMemcpyDeviceToDevice, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpyAsync(lu, t->d_lu, m * 4, hipMemcpyDeviceToDevice, c->lane->stream));
+    HIP_TRY(c, hipMemcpyAsync(lv, t->d_lv, m * 4, hipMemcpyDeviceToDevice, c->lane->stream));
+    HIP_TRY(c, hipMemcpyAsync(lb, t->d_lbatch, m * 4, hipMemcpyDeviceToDevice, c->lane->stream));
+    HIP_TRY(c, hipMemcpyAsync(lval, t->d_lvalid, m, hipMemcpyDeviceToDevice, c->lane->stream));
+    HIP_TRY(c, hipMemcpyAsync(cuv, t->d_lcuv, m * 8, hipMemcpyDeviceToDevice, c->lane->stream));
+    HIP_TRY(c, hipMemcpyAsync(cvu, t->d_lcvu, m * 8, hipMemcpyDeviceToDevice, c->lane->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->lane->stream));
   }
   for (void* p : {(void*)t->d_lu, (void*)t->d_lv, (void*)t->d_lbatch, (void*)t->d_lvalid, (void*)t->d_lcuv, (void*)t->d_lcvu})
     t->mem.release(p);
@@ -573,7 +573,7 @@ inline unsigned tree_blocks(size_t n, unsigned bs = 256) { return (unsigned)std:
 int tree_batch(artp_tree* t, bool* stop) {
   using namespace artp;
   artp_ctx* c = t->ctx;
-  hipStream_t st = c->stream;
+  hipStream_t st = c->lane->stream;
   const artp_tree_params& p = t->params;
   const int B = (int)p.batch;
   const uint32_t n_pre = t->n;
@@ -720,8 +720,8 @@ int tree_batch(artp_tree* t, bool* stop) {
 int tree_check_err(artp_tree* t) {
   artp_ctx* c = t->ctx;
   int err = 0;
-  HIP_TRY(c, hipMemcpyAsync(&err, t->d_err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipMemcpyAsync(&err, t->d_err, sizeof(int), hipMemcpyDeviceToHost, c->lane->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->lane->stream));
   if (err) {
     c->last_error = err == 1 ? "tree: a parent chain does not reach the root" : "tree: shortest-path sweeps did not settle";
     return ARTP_ERR_INVALID_ARG;
@@ -827,7 +827,7 @@ int artp_tree_create(artp_ctx* c, const artp_tree_params* prm, const double* sta
   HIP_TRY(c, t->mem.alloc(&t->d_err, 1));
   if (prm->profile)
     for (hipEvent_t& e : t->ev) HIP_TRY(c, hipEventCreate(&e));
-  hipStream_t st = c->stream;
+  hipStream_t st = c->lane->stream;
   HIP_TRY(c, hipMemcpyAsync(t->d_sg, t->sg, 14 * 8, hipMemcpyHostToDevice, st));
   HIP_TRY(c, hipMemcpyAsync(t->d_verts, t->sg, 7 * 8, hipMemcpyHostToDevice, st));
   HIP_TRY(c, hipMemsetAsync(t->d_cost, 0, 8, st));
@@ -877,9 +877,9 @@ int artp_tree_stats(const artp_tree* t, uint64_t out[8]) {
   std::lock_guard<std::recursive_mutex> lock(c->mu);
   unsigned long long cnt[2] = {0, 0};
   std::vector<uint8_t> pr(t->n);
-  HIP_TRY(c, hipMemcpyAsync(cnt, t->d_counters, sizeof(cnt), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(pr.data(), t->d_pruned, t->n, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipMemcpyAsync(cnt, t->d_counters, sizeof(cnt), hipMemcpyDeviceToHost, c->lane->stream));
+  HIP_TRY(c, hipMemcpyAsync(pr.data(), t->d_pruned, t->n, hipMemcpyDeviceToHost, c->lane->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->lane->stream));
   uint64_t np = 0;
   for (uint8_t b : pr) np += b ? 1 : 0;
   out[0] = t->n;
@@ -899,7 +899,7 @@ int artp_tree_export(const artp_tree* t, double* verts, uint32_t* parent, double
   artp_ctx* c = t->ctx;
   std::lock_guard<std::recursive_mutex> lock(c->mu);
   const size_t n = t->n;
-  hipStream_t st = c->stream;
+  hipStream_t st = c->lane->stream;
   if (verts) HIP_TRY(c, hipMemcpyAsync(verts, t->d_verts, n * 7 * 8, hipMemcpyDeviceToHost, st));
   if (parent) HIP_TRY(c, hipMemcpyAsync(parent, t->d_parent, n * 4, hipMemcpyDeviceToHost, st));
   if (cost) HIP_TRY(c, hipMemcpyAsync(cost, t->d_cost, n * 8, hipMemcpyDeviceToHost, st));
@@ -918,7 +918,7 @@ int artp_tree_export_checked(const artp_tree* t, uint32_t* u, uint32_t* v, uint8
   const size_t m = t->log_n;
   std::vector<uint32_t> lu(m), lv(m), lb(m);
   std::vector<uint8_t> lval(m);
-  hipStream_t st = c->stream;
+  hipStream_t st = c->lane->stream;
   if (m) {
     HIP_TRY(c, hipMemcpyAsync(lu.data(), t->d_lu, m * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipMemcpyAsync(lv.data(), t->d_lv, m * 4, hipMemcpyDeviceToHost, st));
@@ -955,10 +955,10 @@ int artp_tree_solve(const artp_tree* t, double* path_se3, size_t cap_states, siz
   const size_t n = t->n;
   std::vector<uint32_t> parent(n);
   std::vector<double> verts(n * 7), costs(n);
-  HIP_TRY(c, hipMemcpyAsync(parent.data(), t->d_parent, n * 4, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(verts.data(), t->d_verts, n * 7 * 8, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(costs.data(), t->d_cost, n * 8, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipMemcpyAsync(parent.data(), t->d_parent, n * 4, hipMemcpyDeviceToHost, c->lane->stream));
+  HIP_TRY(c, hipMemcpyAsync(verts.data(), t->d_verts, n * 7 * 8, hipMemcpyDeviceToHost, c->lane->stream));
+  HIP_TRY(c, hipMemcpyAsync(costs.data(), t->d_cost, n * 8, hipMemcpyDeviceToHost, c->lane->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->lane->stream));
   std::vector<uint32_t> chain;
   for (uint32_t v = t->goal_id;; v = parent[v]) {
     chain.push_back(v);

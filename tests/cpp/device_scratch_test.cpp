@@ -3,6 +3,7 @@
 // a leak, a double free or a use after free ends the program with a non-zero status, like a failed CHECK.
 #include "../../include/artp_c.h"
 #include "../../art_planner_amd/csrc/device_scratch.h"
+#include "../../art_planner_amd/csrc/pinned_buffer.h"
 
 #include <cstdint>
 #include <cstdio>
@@ -261,6 +262,87 @@ int main() {
     f->dist[99] = 1.0;  // the others are untouched
     delete f;
     CHECK(hip_stub::live == 0);
+  }
+
+  // DeviceBuffer: the grow-only block of a context or a lane
+  {
+    hip_stub::reset();
+    {
+      DeviceBuffer<int> b;
+      CHECK(b.get() == nullptr && b.capacity() == 0);
+      CHECK(b.reserve(0) == hipSuccess && hip_stub::mallocs == 0);   // nothing asked, nothing done
+      CHECK(b.reserve(64) == hipSuccess && b.get() != nullptr && b.capacity() == 64);
+      int* const first = b.get();
+      first[15] = 1;
+      CHECK(b.reserve(64) == hipSuccess && b.reserve(8) == hipSuccess);   // fits: no allocation, the same block
+      CHECK(b.get() == first && b.capacity() == 64 && hip_stub::mallocs == 1 && hip_stub::frees == 0);
+      CHECK(b.reserve(65) == hipSuccess && b.capacity() == 65);           // exactly what was asked for
+      CHECK(hip_stub::mallocs == 2 && hip_stub::frees == 1 && hip_stub::live == 1);
+      b.as<char>()[64] = 1;
+    }
+    CHECK(hip_stub::live == 0 && hip_stub::frees == 2);   // destruction frees exactly once
+  }
+  // ... a regrow frees the old block BEFORE it allocates: at the failing allocation nothing is live any more
+  {
+    DeviceBuffer<> b;
+    hip_stub::reset();
+    CHECK(b.reserve(100) == hipSuccess && hip_stub::live == 1);
+    hip_stub::reset(1);
+    CHECK(b.reserve(200) == hipErrorOutOfMemory);
+    CHECK(hip_stub::frees == 1 && hip_stub::mallocs == 1 && hip_stub::live == 0);
+    CHECK(b.get() == nullptr && b.capacity() == 0);   // empty, not "null with the old capacity"
+    // the request the open-coded idiom let through with a null pointer: smaller than the block that was lost
+    CHECK(b.reserve(50) == hipSuccess && b.get() != nullptr && b.capacity() == 50);
+    CHECK(hip_stub::mallocs == 2 && hip_stub::live == 1);
+    b.as<char>()[49] = 1;
+    CHECK(b.reset() == hipSuccess && b.get() == nullptr && b.capacity() == 0 && hip_stub::live == 0);
+    CHECK(b.reset() == hipSuccess && hip_stub::frees == 2);   // nothing left to free a second time
+  }
+  CHECK(hip_stub::live == 0);
+  // ... a first reserve that fails, and a block handed over from another allocator call
+  {
+    hip_stub::reset(1);
+    DeviceBuffer<float> b;
+    CHECK(b.reserve(16) == hipErrorOutOfMemory && b.get() == nullptr && b.capacity() == 0);
+    void* p = nullptr;
+    CHECK(hipMalloc(&p, 32) == hipSuccess);
+    b.adopt(p, 32);
+    CHECK(b.get() == p && b.capacity() == 32 && b.reserve(32) == hipSuccess && hip_stub::mallocs == 2);
+  }
+  CHECK(hip_stub::live == 0 && hip_stub::frees == 1);
+
+  // PinnedBuffer: the same rules, freed with the host call and never the device one
+  {
+    hip_stub::reset();
+    {
+      PinnedBuffer<double> m, plain;
+      CHECK(m.reserve(56, hipHostMallocMapped) == hipSuccess && m.host() != nullptr && m.dev() == m.host());
+      CHECK(plain.reserve(56, hipHostMallocDefault) == hipSuccess && plain.host() != nullptr && plain.dev() == nullptr);
+      m.host()[6] = 1.0;
+      double* const first = m.host();
+      CHECK(m.reserve(8, hipHostMallocMapped) == hipSuccess && m.host() == first && hip_stub::host_mallocs == 2);
+      CHECK(m.reserve(112, hipHostMallocMapped) == hipSuccess && m.capacity() == 112 && m.dev() == m.host());
+      CHECK(hip_stub::host_mallocs == 3 && hip_stub::host_frees == 1 && hip_stub::host_live == 2);
+      m.host()[13] = 1.0;
+    }
+    CHECK(hip_stub::host_live == 0 && hip_stub::host_frees == 3);
+    CHECK(hip_stub::mallocs == 0 && hip_stub::frees == 0 && hip_stub::live == 0);   // no device call at all
+  }
+  {
+    PinnedBuffer<> m;
+    hip_stub::reset();
+    CHECK(m.reserve(100, hipHostMallocMapped) == hipSuccess);
+    hip_stub::reset(1);
+    CHECK(m.reserve(200, hipHostMallocMapped) == hipErrorOutOfMemory);
+    CHECK(hip_stub::host_frees == 1 && hip_stub::host_live == 0);
+    CHECK(m.host() == nullptr && m.dev() == nullptr && m.capacity() == 0);
+    CHECK(m.reserve(50, hipHostMallocMapped) == hipSuccess && m.host() != nullptr && m.capacity() == 50);
+    // no device address for a mapped block: the block goes back, the buffer is empty
+    hip_stub::fail_dev_ptr = true;
+    CHECK(m.reserve(400, hipHostMallocMapped) == hipErrorOutOfMemory);
+    CHECK(m.host() == nullptr && m.dev() == nullptr && m.capacity() == 0 && hip_stub::host_live == 0);
+    hip_stub::fail_dev_ptr = false;
+    CHECK(hip_stub::frees == 0);
   }
 
   CHECK(try_passes_code(ARTP_OK) == ARTP_OK);

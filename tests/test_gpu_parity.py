@@ -1146,6 +1146,63 @@ def test_map_writes_are_ordered_against_the_other_lanes(big_map):
     ctx.close()
 
 
+def test_lanes_own_their_scratch_and_tail_history(big_map):
+    """Every lane has its own scratch buffers, counters and tail history.  17 states are one more than the latency path takes
+    (the pipeline runs) and 65 one more than a classify workgroup holds, so the 65-state batch regrows every buffer the
+    17-state batch sized.  Lane 1 regrows its scratch while lane 2's, of the larger size, is live; lane 3 checks a handful of
+    edges; all of it equals what lane 0 computed alone, bit for bit.  artp_last_tail: a lane's first pipeline call takes the
+    full tail whatever the other lanes did, its second the rare one (65 states leave at most 325 boxes behind, on this terrain
+    a handful: below the one wavefront per CU and more of the rare grid), and lane 0's answer is not touched by the others.
+    A second context still comes and goes."""
+    from art_planner_amd.context import Context
+    FULL, RARE = 1, 2
+    gm = big_map
+    se3 = common.random_states(gm, 65, np.random.default_rng(31))
+    few, many = se3[:17], se3
+    ctx = Context(0, "yaml")
+    ctx.upload_map(gm, sampler=False)
+    assert ctx.lane == 0 and ctx.last_tail() == 0
+    ref_few = ctx.validate_states(few)
+    assert ctx.last_tail() == FULL
+    ref_many = ctx.validate_states(many)
+    assert ctx.last_tail() == RARE
+    ok = many[ref_many != 0]
+    s1, s2 = ok[:6].copy(), ok[:6].copy()   # three edges of 0.1 m from a valid state, three across the map
+    s2[:3, 0] += 0.1
+    s2[3:] = ok[6:9]
+    ref_edges = ctx.check_motions(s1, s2)
+    print("valid of 17:", int(ref_few.sum()), "of 65:", int(ref_many.sum()), "edges:", ref_edges.tolist())
+    assert np.array_equal(ref_many, O.OracleMap(gm).states_valid(O.robot("yaml"), many))
+    assert np.array_equal(ref_many[:17], ref_few) and 0 < ref_few.sum() < 17 and 0 < ref_many[17:].sum() < 48
+    assert np.array_equal(ref_edges, O.OracleMap(gm).check_motions(O.robot("yaml"), s1, s2)[0]) and 0 < ref_edges.sum() < 6
+    ctx.set_lane(1)
+    assert ctx.last_tail() == 0
+    got_few = ctx.validate_states(few)
+    assert ctx.last_tail() == FULL
+    ctx.set_lane(2)
+    got_many_2 = ctx.validate_states(many)
+    assert ctx.last_tail() == FULL
+    ctx.set_lane(1)
+    got_many_1 = ctx.validate_states(many)   # lane 1 regrows; lane 2's buffers stay where they are
+    assert ctx.last_tail() == RARE
+    ctx.set_lane(2)
+    got_few_2 = ctx.validate_states(few)     # ... and still work
+    ctx.set_lane(3)
+    got_edges = ctx.check_motions(s1, s2)
+    assert ctx.last_tail() == 0              # six edges take the latency path: still no pipeline call of lane 3's own
+    ctx.set_lane(0)
+    assert ctx.lane == 0 and ctx.last_tail() == RARE
+    again = ctx.validate_states(many)
+    for got, ref in ((got_few, ref_few), (got_many_2, ref_many), (got_many_1, ref_many), (got_few_2, ref_few),
+                     (got_edges, ref_edges), (again, ref_many)):
+        assert got.tobytes() == ref.tobytes()
+    ctx.close()                              # four lanes' streams, counters and scratch go
+    other = Context(0, "yaml")
+    other.upload_map(gm, sampler=False)
+    assert np.array_equal(other.validate_states(few), ref_few)
+    other.close()
+
+
 def test_check_motion_two_pass_equals_one_pass_and_the_oracle(big_map, monkeypatch):
     """artp_check_motions on batches of >= 4096 edges runs in two passes (s2 + every 8th interior state of every edge, then
     the rest of the edges still alive: kernels.h ARTP_COARSE_STRIDE).  An edge is valid iff all its states are, so the
