@@ -24,6 +24,7 @@ SYMBOLS = [
     "artp_field_destroy", "artp_field_learned_params_defaults", "artp_field_compute_learned", "artp_field_learned_stats",
     "artp_field_update_learned", "artp_field_learned_update_stats", "artp_field_block_moves", "artp_field_unblock",
     "artp_field_blocked_count", "artp_field_blocked", "artp_field_plan", "artp_field_plan_stats", "artp_field_plan_round_tile_runs",
+    "artp_field_simplify_paths", "artp_field_simplify_stats",
     "artp_clearance_params_defaults", "artp_clearance_map", "artp_clearance_map_dev",
     "artp_field_clearance_params_defaults", "artp_field_compute_clearance", "artp_field_clearance",
     "artp_field_update_clearance", "artp_field_clearance_update_stats",
@@ -146,6 +147,16 @@ class FieldPlanStats(C.Structure):  # artp_field_plan_stats_t
                 [(n, C.c_double) for n in ("descent_ms", "check_ms", "round_ms", "passes_ms")])
 
 
+class FieldSimplifyParams(C.Structure):  # artp_field_simplify_params
+    _fields_ = [("window", C.c_uint32), ("reserved", C.c_uint32), ("max_batch_pairs", C.c_uint64)]
+
+
+class FieldSimplifyStats(C.Structure):  # artp_field_simplify_stats_t
+    _fields_ = ([(n, C.c_uint64) for n in ("paths", "states_in", "states_kept", "candidates", "usable_candidates",
+                                           "batches")] +
+                [(n, C.c_double) for n in ("eval_ms", "search_ms", "host_ms")])
+
+
 class ClearanceParams(C.Structure):  # artp_clearance_params
     _fields_ = [("radius_cells", C.c_int32), ("yaw_spread", C.c_int32), ("outside_is_obstacle", C.c_int32),
                 ("reserved", C.c_int32)]
@@ -258,6 +269,8 @@ def _load_path(LIB_PATH):
     L.artp_field_plan.argtypes = [vp, vp, sz, i32, vp, vp, vp, vp, vp, sz]
     L.artp_field_plan_stats.argtypes = [vp, C.POINTER(FieldPlanStats)]
     L.artp_field_plan_round_tile_runs.argtypes = [vp, vp, sz, C.POINTER(sz)]
+    L.artp_field_simplify_paths.argtypes = [vp, C.POINTER(FieldSimplifyParams), vp, vp, sz, vp, vp, vp, vp, vp, sz]
+    L.artp_field_simplify_stats.argtypes = [vp, C.POINTER(FieldSimplifyStats)]
     L.artp_clearance_params_defaults.argtypes = [C.POINTER(ClearanceParams)]
     L.artp_clearance_params_defaults.restype = None
     for name in ("artp_clearance_map", "artp_clearance_map_dev"):

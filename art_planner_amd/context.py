@@ -249,7 +249,8 @@ class Context:
         array, or a device tensor in the layout reachability_map_dev writes; sources = (r, c, k) triples local to the
         rectangle.  reverse=False: cost from the nearest source to every node; True: from every node to the nearest
         source.  Returns a CostField (.dist(), .dist_dev(), .path(target), .stats(), .close(); .plan(targets) for
-        paths whose moves passed check_motions, .block_moves(a, b) / .unblock(rect) for the set behind it)."""
+        paths whose moves passed check_motions, .block_moves(a, b) / .unblock(rect) for the set behind it,
+        .simplify(paths, window) for the cheapest chains of checked shortcuts through such paths)."""
         from .field import CostField
         return CostField(self, mask, n_yaw, sources, rect=rect, reverse=reverse, objective=objective,
                          max_lon_vel=max_lon_vel, max_lat_vel=max_lat_vel, max_ang_vel=max_ang_vel,

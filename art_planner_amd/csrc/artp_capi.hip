@@ -3504,6 +3504,7 @@ int artp_cost_get_features(artp_ctx* c, float* out, int* fh, int* fw) {
 #include "field.h"
 #include "clearance.h"
 #include "field_plan.h"
+#include "field_simplify.h"
 #include "preprocess.h"
 #include "group.h"
 

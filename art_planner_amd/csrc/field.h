@@ -855,6 +855,10 @@ struct artp_field {
   // artp_field_plan's scratch: per-target records, path nodes, poses, the move list, the (s1, s2) pairs and verdicts
   void* d_plan = nullptr;
   size_t plan_targets = 0, plan_states = 0;
+  // artp_field_simplify_paths' scratch (field_simplify.h): one block, grown to the largest call
+  char* d_simplify = nullptr;
+  size_t simplify_cap = 0;              // bytes
+  artp_field_simplify_stats_t sstats{};
   DeviceScratch mem;  // owns every d_* above: freed with the field, or earlier by mem.release
 };
 

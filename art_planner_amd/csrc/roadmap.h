@@ -681,20 +681,20 @@ bool roadmap_sssp_dev(artp_roadmap* rm, std::vector<uint32_t>* path, double* cos
 // and LazyPRM*'s edges into their graphs.
 // segment_cost_step > 0 (learned objective only): the edges are path SEGMENTS priced the way
 // MotionCostObjective::motionCost prices a motion -- split by max_query_edge_length, not along the validity chain.
-int roadmap_eval_edges_dev(artp_ctx* c, const artp_roadmap_params* prm, const double* d_s1, const double* d_s2,
-                           size_t ne, uint8_t* evalid, uint32_t* einterp, double* ecost, bool direct = false,
-                           double segment_cost_step = 0.0) {
+//
+// roadmap_eval_edges_into: the launches, with the three results LEFT ON THE DEVICE in the caller's d_evalid (ne bytes),
+// d_einterp and d_cost (ne entries).  Enqueued on the lane's stream and not synchronised at the end; *scratch owns what
+// the learned objective allocates on the way and must outlive the launches (artp_field_simplify_paths keeps the
+// results where they are; roadmap_eval_edges_dev below copies them to the host arrays).
+int roadmap_eval_edges_into(artp_ctx* c, const artp_roadmap_params* prm, const double* d_s1, const double* d_s2,
+                            size_t ne, uint8_t* d_evalid, uint32_t* d_einterp, double* d_cost, DeviceScratch* scratch,
+                            bool direct = false, double segment_cost_step = 0.0) {
   if (ne == 0) return ARTP_OK;
   hipStream_t st = c->lane->stream;
-  double* d_cost = nullptr;
-  uint8_t* d_evalid = nullptr;
-  uint32_t *d_einterp = nullptr, *d_rows = nullptr, *d_off = nullptr, *d_ncost = nullptr;
+  uint32_t *d_rows = nullptr, *d_off = nullptr, *d_ncost = nullptr;
   float *d_em = nullptr, *d_c3 = nullptr;
   void* d_cub2 = nullptr;
-  DeviceScratch S;
-  HIP_TRY(c, S.alloc(&d_cost, ne));
-  HIP_TRY(c, S.alloc(&d_evalid, ne));
-  HIP_TRY(c, S.alloc(&d_einterp, ne));
+  DeviceScratch& S = *scratch;
   if (direct) {
     HIP_TRY(c, hipMemsetAsync(d_evalid, 1, ne, st));
     HIP_TRY(c, hipMemsetAsync(d_einterp, 0, ne * sizeof(uint32_t), st));
@@ -735,6 +735,22 @@ int roadmap_eval_edges_dev(artp_ctx* c, const artp_roadmap_params* prm, const do
                        prm->w_time, prm->w_risk, prm->risk_threshold, d_cost);
   }
   HIP_TRY(c, hipGetLastError());
+  return ARTP_OK;
+}
+
+int roadmap_eval_edges_dev(artp_ctx* c, const artp_roadmap_params* prm, const double* d_s1, const double* d_s2,
+                           size_t ne, uint8_t* evalid, uint32_t* einterp, double* ecost, bool direct = false,
+                           double segment_cost_step = 0.0) {
+  if (ne == 0) return ARTP_OK;
+  hipStream_t st = c->lane->stream;
+  double* d_cost = nullptr;
+  uint8_t* d_evalid = nullptr;
+  uint32_t* d_einterp = nullptr;
+  DeviceScratch S;
+  HIP_TRY(c, S.alloc(&d_cost, ne));
+  HIP_TRY(c, S.alloc(&d_evalid, ne));
+  HIP_TRY(c, S.alloc(&d_einterp, ne));
+  ARTP_TRY(roadmap_eval_edges_into(c, prm, d_s1, d_s2, ne, d_evalid, d_einterp, d_cost, &S, direct, segment_cost_step));
   HIP_TRY(c, hipStreamSynchronize(st));
   HIP_TRY(c, hipMemcpy(evalid, d_evalid, ne, hipMemcpyDeviceToHost));
   HIP_TRY(c, hipMemcpy(einterp, d_einterp, ne * sizeof(uint32_t), hipMemcpyDeviceToHost));

@@ -235,12 +235,21 @@ class CostField:
         self.ctx._chk(self.L.artp_field_blocked_count(self.h, C.byref(n)), "artp_field_blocked_count")
         return int(n.value)
 
-    def plan(self, targets, max_rounds=64) -> list:
+    def plan(self, targets, max_rounds=64, simplify=False, window=64) -> list:
         """Lazily checked paths to (n, 3) target triples (artp_field_plan): per round the field's path of every pending
         target, one batched check_motions of all their moves, the failing moves blocked and the field repaired.
         Returns one (status, nodes, se3, cost) per target: status 0 = every move passed (nodes (n, 3) int32 and se3
         (n, 7) in travel order, cost = dist[target]), 1 = unreachable, 2 = max_rounds exhausted (nodes and se3 None,
-        cost +inf).  The blocks stay on the field: a second call continues."""
+        cost +inf).  The blocks stay on the field: a second call continues.
+        simplify=True: the status-0 paths go through simplify(window=window) in one call, and their tuples gain two
+        members: the simplified states (k, 7) and their cost under simplify()'s pricing."""
+        out = self._plan(targets, max_rounds)
+        if simplify and out:
+            simple = self.simplify(out, window=window)
+            out = [r if s is None else r + (s[2], s[3]) for r, s in zip(out, simple)]
+        return out
+
+    def _plan(self, targets, max_rounds) -> list:
         t = np.ascontiguousarray(targets, np.int32).reshape(-1, 3)
         nt = len(t)
         self._plan_stats = None
@@ -275,6 +284,48 @@ class CostField:
             else:
                 out.append((int(st[i]), None, None, float(cost[i])))
         return out
+
+    def simplify(self, paths, window=64, max_batch_pairs=0) -> list:
+        """Windowed shortcut simplification of many paths in one call (artp_field_simplify_paths).
+        paths: a list of (n, 7) arrays, or the list plan() returns (entries whose status is not 0 pass through as None,
+        and so does a None).  A candidate joins states at most `window` apart along the path (0 = all pairs); it must pass
+        check_edges_interp and check_motions, and is priced by the field's objective and velocities (a clearance-weighted
+        field: unweighted).  Returns one (status, kept_indices, se3, cost) per path: status 0 = simplified, 1 = the input
+        itself does not pass (returned unchanged, cost +inf), 2 = empty.  With a window that covers the path the result
+        is Roadmap.simplify's bit for bit."""
+        idx, arrs = [], []
+        for i, p in enumerate(paths):
+            if p is None:
+                continue
+            if isinstance(p, tuple):            # an entry of plan(): (status, nodes, se3, cost, ...)
+                if p[0] != 0:
+                    continue
+                p = p[2]
+            idx.append(i)
+            arrs.append(np.ascontiguousarray(p, np.float64).reshape(-1, 7))
+        out = [None] * len(paths)
+        if not idx:
+            return out
+        n = len(arrs)
+        off = np.zeros(n + 1, np.uint64)
+        off[1:] = np.cumsum([len(a) for a in arrs])
+        total = int(off[n])
+        se3_in = np.concatenate(arrs) if total else np.zeros((0, 7))
+        prm = _capi.FieldSimplifyParams(int(window), 0, int(max_batch_pairs))
+        st, cost, ooff = np.empty(n, np.int32), np.empty(n, np.float64), np.zeros(n + 1, np.uint64)
+        kept, se3 = np.empty(max(total, 1), np.uint32), np.empty((max(total, 1), 7), np.float64)   # never more than came in
+        self.ctx._chk(self.L.artp_field_simplify_paths(self.h, C.byref(prm), se3_in.ctypes.data, off.ctypes.data, n,
+                                                       st.ctypes.data, cost.ctypes.data, ooff.ctypes.data,
+                                                       kept.ctypes.data, se3.ctypes.data, max(total, 1)),
+                      "artp_field_simplify_paths")
+        for j, i in enumerate(idx):
+            lo, hi = int(ooff[j]), int(ooff[j + 1])
+            out[i] = (int(st[j]), kept[lo:hi].copy(), se3[lo:hi].copy(), float(cost[j]))
+        return out
+
+    def simplify_stats(self) -> dict:
+        """The numbers of the last simplify() (artp_field_simplify_stats)."""
+        return self._stats(_capi.FieldSimplifyStats, self.L.artp_field_simplify_stats, "artp_field_simplify_stats")
 
     def _read_plan_stats(self) -> dict:
         d = self._stats(_capi.FieldPlanStats, self.L.artp_field_plan_stats, "artp_field_plan_stats")

@@ -562,14 +562,40 @@ class Planner {
   // dist[target]); 1: unreachable; 2: rounds exhausted.  The blocks stay on the field: a second call continues.
   // Refreshes the "cost_to_go" layer, since the blocks move the field.  stats (may be null) takes the numbers of the
   // call; should the paths outgrow the buffers, the call is made again with larger ones and stats holds both together.
+  // simplify = true: the status-0 paths go through simplifyCostFieldPaths(window) in one call; `simplified` and
+  // `simplified_cost` take the kept states and their cost under that call's pricing (empty and +inf otherwise).
   struct CostFieldPlan {
     int status = 2;
     std::vector<std::array<int, 3>> nodes;
     std::vector<std::array<double, 7>> states;
     double cost = std::numeric_limits<double>::infinity();
+    std::vector<std::array<double, 7>> simplified;
+    double simplified_cost = std::numeric_limits<double>::infinity();
   };
+  // One path of simplifyCostFieldPaths: status 0 = simplified, 1 = the input itself does not pass (returned unchanged,
+  // cost +inf), 2 = empty; kept = the indices of the kept input states, ascending from 0 to n - 1.
+  struct SimplifiedPath {
+    int status = 2;
+    std::vector<uint32_t> kept;
+    std::vector<std::array<double, 7>> states;
+    double cost = std::numeric_limits<double>::infinity();
+  };
+  // Windowed shortcut simplification of many paths in one device call (artp_field_simplify_paths, include/artp_c.h):
+  // per path the cheapest chain of shortcuts between states at most `window` apart (0 = all pairs) that pass the 0.5 m
+  // interpolation rule and checkMotion, priced by the field's objective and velocities (a clearance-weighted field:
+  // unweighted).  With a window that covers a path: what getSolutionPath(true) makes of it.  The field is not changed.
+  std::vector<SimplifiedPath> simplifyCostFieldPaths(artp_field* kept,
+                                                     const std::vector<std::vector<std::array<double, 7>>>& paths,
+                                                     unsigned window = 64, artp_field_simplify_stats_t* stats = nullptr) {
+    std::lock_guard<std::mutex> lock(map_mutex_);
+    if (!map_) throw std::runtime_error("simplifyCostFieldPaths: the planner does not have a map set");
+    if (!kept) throw std::runtime_error("simplifyCostFieldPaths: no field");
+    return simplifyPathsLocked(kept, paths, window, stats);
+  }
+
   std::vector<CostFieldPlan> planOnCostField(artp_field* kept, const std::vector<std::array<int, 3>>& targets,
-                                             int max_rounds = 64, artp_field_plan_stats_t* stats = nullptr) {
+                                             int max_rounds = 64, artp_field_plan_stats_t* stats = nullptr,
+                                             bool simplify = false, unsigned window = 64) {
     std::lock_guard<std::mutex> lock(map_mutex_);
     if (!map_) throw std::runtime_error("planOnCostField: the planner does not have a map set");
     if (!kept) throw std::runtime_error("planOnCostField: no field");
@@ -630,6 +656,19 @@ class Planner {
     }
     if (stats) *stats = sum;
     refreshCostToGo(kept, cells, st.nodes);
+    if (simplify) {
+      std::vector<std::vector<std::array<double, 7>>> paths;
+      for (const CostFieldPlan& p : out)
+        if (p.status == 0) paths.push_back(p.states);
+      const std::vector<SimplifiedPath> simple = simplifyPathsLocked(kept, paths, window, nullptr);
+      size_t at = 0;
+      for (CostFieldPlan& p : out)
+        if (p.status == 0) {
+          p.simplified = simple[at].states;
+          p.simplified_cost = simple[at].cost;
+          ++at;
+        }
+    }
     return out;
   }
 
@@ -744,6 +783,43 @@ class Planner {
   const std::shared_ptr<BatchTree>& tree() const { return tree_; }
 
  protected:
+  // simplifyCostFieldPaths with map_mutex_ held by the caller (planOnCostField holds it already)
+  std::vector<SimplifiedPath> simplifyPathsLocked(artp_field* kept, const std::vector<std::vector<std::array<double, 7>>>& paths,
+                                                  unsigned window, artp_field_simplify_stats_t* stats) {
+    const size_t n = paths.size();
+    std::vector<SimplifiedPath> out(n);
+    if (stats) *stats = artp_field_simplify_stats_t{};
+    if (!n) return out;
+    std::vector<uint64_t> off(n + 1, 0), ooff(n + 1, 0);
+    std::vector<double> se3_in;
+    for (size_t q = 0; q < n; ++q) {
+      for (const auto& s : paths[q]) se3_in.insert(se3_in.end(), s.begin(), s.end());
+      off[q + 1] = off[q] + paths[q].size();
+    }
+    const size_t total = static_cast<size_t>(off[n]);               // never more states come back than went in
+    std::vector<int32_t> status(n);
+    std::vector<double> cost(n), se3(7 * total + 7);
+    std::vector<uint32_t> kept_idx(total + 1);
+    artp_field_simplify_params sp{};
+    sp.window = window;
+    throwOnError(gpu_->get(),
+                 artp_field_simplify_paths(kept, &sp, se3_in.data(), off.data(), n, status.data(), cost.data(), ooff.data(),
+                                           kept_idx.data(), se3.data(), total + 1),
+                 "artp_field_simplify_paths");
+    if (stats) throwOnError(gpu_->get(), artp_field_simplify_stats(kept, stats), "artp_field_simplify_stats");
+    for (size_t q = 0; q < n; ++q) {
+      out[q].status = status[q];
+      out[q].cost = cost[q];
+      for (uint64_t s = ooff[q]; s < ooff[q + 1]; ++s) {
+        out[q].kept.push_back(kept_idx[s]);
+        std::array<double, 7> x;
+        for (int j = 0; j < 7; ++j) x[j] = se3[7 * s + j];
+        out[q].states.push_back(x);
+      }
+    }
+    return out;
+  }
+
   // the tail of both update calls: dist out of the kept field, the layer refreshed
   std::vector<double> refreshCostToGo(artp_field* kept, size_t cells, size_t nodes) {
     const size_t n_yaw = nodes / cells;

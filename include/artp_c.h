@@ -442,6 +442,54 @@ int artp_field_plan_stats(artp_field* f, artp_field_plan_stats_t* out);
  * form).  *n_rounds = the rounds; runs_out (may be NULL with cap = 0) takes the first cap of them. */
 int artp_field_plan_round_tile_runs(artp_field* f, uint64_t* runs_out, size_t cap, size_t* n_rounds);
 
+/* ---- Simplified paths: windowed shortcuts, many paths a call --------------------------------
+ * What artp_field_plan returns is a lattice staircase, one state per cell or heading step.  This call keeps a subset of
+ * each path's states: the cheapest chain of usable shortcuts from the first to the last state, artp_roadmap_simplify_path's
+ * search with the candidates limited to a window and everything between the upload of the paths and the read of the
+ * result on the device.
+ * Path q = the states [offsets[q], offsets[q + 1]) of se3_in (host, 7 doubles a state, travel order, as artp_field_plan
+ * hands them out; they need not be lattice poses).  A candidate (i, j) of a path has 1 <= j - i <= window (0 = all pairs).
+ * It is usable iff the 0.5 m interpolation rule passes it (artp_check_edges_interp), checkMotion passes it
+ * (artp_check_motions) and its cost is finite; its cost is the chain cost of artp_roadmap_simplify_path under the field's
+ * objective (0 or 1) and velocities: the sub-edges at the interpolation rule's interior states, summed in order.
+ * The search: best[0] = 0; for i ascending, for j ascending, best[j] = best[i] + c(i, j) when that is strictly smaller
+ * (the left fold of the sums; the smallest i wins a tie).  With a window of n - 1 or more, or 0, the result is bit for bit
+ * artp_roadmap_simplify_path's on a roadmap of the same objective and velocities.  A larger window never costs more.
+ * statuses[q]: 0 = simplified; 1 = the input chain itself does not pass: the path comes back unchanged with cost +inf;
+ * 2 = an empty path (cost +inf).  costs[q] = best[n - 1] (0 for a single state).  out_offsets (n_paths + 1 entries):
+ * path q's kept states at [out_offsets[q], out_offsets[q + 1]) of kept_out (indices into the path, ascending, the first
+ * 0 and the last n - 1) and of se3_out (those states); the three may be NULL.  ARTP_ERR_CAPACITY when cap_states <
+ * out_offsets[n_paths]: statuses, costs and offsets are filled, nothing else is missing.
+ * A clearance-weighted field is accepted and its candidates are priced with the UNWEIGHTED base objective: a shortcut may
+ * give back part of the margin the lattice path kept, by at most what a chord over `window` states can cut.
+ * Refused with nothing written (ARTP_ERR_INVALID_ARG): a learned field (artp_last_error says so), offsets that do not
+ * ascend, a changed map, p == NULL, n_paths == 0 or above 2^24, 2^32 - 1 states or more in one call; ARTP_ERR_NO_MAP
+ * without both validity layers and artp_set_z_bounds.
+ * Candidates are evaluated in batches of at most max_batch_pairs, cut anywhere; the result does not depend on it.  The
+ * host reads the statuses, costs and counts once and the kept indices and states once, besides the reads of the two checks.
+ * Synchronous, on the context's current stream; the field itself is not changed. */
+typedef struct artp_field_simplify_params {
+  uint32_t window;           /* a candidate (i, j) has 1 <= j - i <= window; 0 = all pairs */
+  uint32_t reserved;
+  uint64_t max_batch_pairs;  /* candidates evaluated per device batch; 0 = the library's default (2^20) */
+} artp_field_simplify_params;
+typedef struct artp_field_simplify_stats_t {
+  uint64_t paths;              /* of the call */
+  uint64_t states_in;          /* states of all paths */
+  uint64_t states_kept;
+  uint64_t candidates;         /* pairs inside the window */
+  uint64_t usable_candidates;  /* ... that passed both checks with a finite cost */
+  uint64_t batches;
+  double eval_ms;              /* stream time of enumeration, the two checks, costs and weights, all batches */
+  double search_ms;            /* stream time of the search, the scan of the counts and the output gather */
+  double host_ms;              /* host time of the call */
+} artp_field_simplify_stats_t;
+int artp_field_simplify_paths(artp_field* f, const artp_field_simplify_params* p, const double* se3_in,
+                              const uint64_t* offsets, size_t n_paths, int32_t* statuses, double* costs,
+                              uint64_t* out_offsets, uint32_t* kept_out, double* se3_out, size_t cap_states);
+/* the numbers of the last artp_field_simplify_paths that ran (zeros before the first) */
+int artp_field_simplify_stats(artp_field* f, artp_field_simplify_stats_t* out);
+
 /* ---- Clearance maps and clearance-weighted fields -------------------------------------------
  * A cost-to-go field finds the CHEAPEST lattice path, and under PathLengthObjective that path hugs the boundary of the
  * valid set.  A clearance map measures how far every node is from that boundary; a clearance-weighted field prefers to
