@@ -58,7 +58,10 @@
 // and the same table-driven kernels search it (field_has_wtab).  A mask edit moves clearances, and with them weights, up to
 // radius_cells around it: artp_field_update and artp_field_update_learned refuse such a field, artp_field_update_clearance
 // (clearance.h) recomputes both on a window of tiles and runs the passes of artp_field_update.
-// The host side of the three updates is one procedure, field_update_run; an entry point adds its refusals and its own step.
+// artp_field_shift: the map moved by whole cells under the rectangle.  field_shift_nodes_kernel and
+// field_shift_cells_kernel move dist, hops, blocked words, mask words and heights by a constant offset, fill the cells that
+// entered and flag the border through which cells left; then the diff against the whole new mask and the four passes.
+// The host side of the updates and the shift is one procedure, field_update_run; an entry point adds its refusals and its own step.
 #pragma once
 
 #include <cstddef>
@@ -805,6 +808,75 @@ field_hop_reset_kernel(FieldGrid G, const double* __restrict__ dist, const doubl
   field_flag_around(G, (int)(cell % (uint32_t)G.nrows), (int)(cell / (uint32_t)G.nrows), acc);
 }
 
+// ---- artp_field_shift ---------------------------------------------------------------------
+
+// The map moved by (si, sj) whole cells under a rectangle that keeps its map indices: node (r, c, k) becomes node
+// (r + si, c + sj, k).  The node index is (r + c nrows) n_yaw + k, so a destination reads the element a constant number
+// of places in front of it -- (si + sj nrows) n_yaw nodes, si + sj nrows cells -- when its old cell lay inside the
+// rectangle.  One lane per destination element: the lanes of a wave read and write consecutive addresses.  The rows that
+// leave on one side are the rows that enter on the other, so a workgroup would read what another has written already:
+// the kernels write into scratch, and the host copies back.
+struct FieldShift {
+  int si, sj;
+  long long cell_off;  // si + sj nrows
+};
+__device__ __forceinline__ bool field_shift_inside(const FieldGrid& G, int r, int c) {
+  return r >= 0 && r < G.nrows && c >= 0 && c < G.ncols;
+}
+
+// One lane per destination node: dist and hops (+inf / NONE in the cells that entered), and with blk != nullptr the
+// blocked words (0 there).  A blocked word moves with its node and loses the translation slots whose neighbour now lies
+// outside the rectangle; a node that left takes its word with it.  cnt[7] += blocked moves kept, counted as
+// field_unblock_kernel counts them (blocked moves are few: one atomic per word that holds any).
+__global__ void __launch_bounds__(256)
+field_shift_nodes_kernel(FieldGrid G, FieldShift sh, const double* __restrict__ dist, const uint32_t* __restrict__ hops,
+                         const uint16_t* __restrict__ blk, double* __restrict__ dist_o, uint32_t* __restrict__ hops_o,
+                         uint16_t* __restrict__ blk_o, unsigned long long* __restrict__ cnt) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)G.nrows * G.ncols * G.n_yaw) return;
+  const uint32_t cell = (uint32_t)(i / (uint32_t)G.n_yaw);
+  const int r = (int)(cell % (uint32_t)G.nrows), c = (int)(cell / (uint32_t)G.nrows);
+  const bool in = field_shift_inside(G, r - sh.si, c - sh.sj);
+  const size_t s = in ? (size_t)((long long)i - sh.cell_off * G.n_yaw) : 0;
+  dist_o[i] = in ? dist[s] : (double)INFINITY;
+  hops_o[i] = in ? hops[s] : FIELD_NONE;
+  if (!blk) return;
+  uint32_t w = in ? (uint32_t)blk[s] : 0u;
+  if (w) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      if (!field_shift_inside(G, r + field_dr(j), c + field_dc(j))) w &= ~(1u << j);
+    if (w) atomicAdd(&cnt[7], (unsigned long long)(G.n_yaw == 2 ? __popc(w & 0xffu) + ((w & 0x300u) ? 1 : 0) : __popc(w)));
+  }
+  blk_o[i] = (uint16_t)w;
+}
+
+// One lane per destination cell: the mask word (0 in a cell that entered) and the height (there: the sampler layer's, as
+// field_heights_kernel reads it).  cnt[5] += the nodes of the cells that left -- the lane's own old cell when (r + si,
+// c + sj) lies outside -- one atomic per wave.  The rectangle's border row and column on the sides through which cells
+// left flag the tiles around their cells in acc: a kept node there may have had its only support outside.  Its mask word
+// does not change, so no diff would flag it, and the unsupport pass has to look at it.
+__global__ void __launch_bounds__(256)
+field_shift_cells_kernel(FieldGrid G, FieldShift sh, SamplerDev sm, int map_rows, ReachRect rc,
+                         const uint32_t* __restrict__ mask, const float* __restrict__ h, uint32_t* __restrict__ mask_o,
+                         float* __restrict__ h_o, unsigned* acc, unsigned long long* __restrict__ cnt) {
+  const uint32_t cell = blockIdx.x * blockDim.x + threadIdx.x;
+  unsigned left = 0u;
+  if (cell < (uint32_t)G.nrows * (uint32_t)G.ncols) {
+    const int r = (int)(cell % (uint32_t)G.nrows), c = (int)(cell / (uint32_t)G.nrows);
+    const bool in = field_shift_inside(G, r - sh.si, c - sh.sj);
+    const size_t s = in ? (size_t)((long long)cell - sh.cell_off) : 0;
+    mask_o[cell] = in ? mask[s] : 0u;
+    h_o[cell] = in ? h[s] : sm.cells[2 * ((size_t)(rc.row0 + r) + (size_t)(rc.col0 + c) * map_rows)].x;
+    if (!field_shift_inside(G, r + sh.si, c + sh.sj)) left = (unsigned)__popc(mask[cell] & G.yaw_bits);
+    if ((sh.si > 0 && r == G.nrows - 1) || (sh.si < 0 && r == 0) || (sh.sj > 0 && c == G.ncols - 1) || (sh.sj < 0 && c == 0))
+      field_flag_around(G, r, c, acc);
+  }
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) left += __shfl_down(left, d);
+  if ((threadIdx.x & 63) == 0 && left) atomicAdd(&cnt[5], (unsigned long long)left);
+}
+
 }  // namespace artp
 
 struct artp_field {
@@ -859,6 +931,10 @@ struct artp_field {
   char* d_simplify = nullptr;
   size_t simplify_cap = 0;              // bytes
   artp_field_simplify_stats_t sstats{};
+  // artp_field_shift: where the move writes (hops | mask words | heights | blocked words; dist goes through d_snap),
+  // allocated by the first shift
+  char* d_shift = nullptr;
+  artp_field_shift_stats_t shstats{};
   DeviceScratch mem;  // owns every d_* above: freed with the field, or earlier by mem.release
 };
 
@@ -1262,13 +1338,14 @@ void field_adopt_sampler(artp_ctx* c, artp_field* f) {
   f->map_version = c->map_version.load();
 }
 
-// The stats of the two weight-table updates begin with the members of artp_field_update_stats_t, at its offsets.
+// The stats of the two weight-table updates and of the shift begin with the members of artp_field_update_stats_t, at its offsets.
 #define FIELD_STATS_PREFIX(X)                                                                                         \
   X(changed_words) X(removed_nodes) X(added_nodes) X(dead_nodes) X(hop_dead_nodes) X(unsupport_rounds) X(dist_rounds) \
   X(hop_rounds) X(tile_launches) X(reached_nodes)
 #define FIELD_STATS_SAME_OFFSET(m)                                                                              \
   static_assert(offsetof(artp_field_learned_update_stats_t, m) == offsetof(artp_field_update_stats_t, m) &&     \
-                    offsetof(artp_field_clearance_update_stats_t, m) == offsetof(artp_field_update_stats_t, m), \
+                    offsetof(artp_field_clearance_update_stats_t, m) == offsetof(artp_field_update_stats_t, m) && \
+                    offsetof(artp_field_shift_stats_t, m) == offsetof(artp_field_update_stats_t, m),            \
                 "the update stats structs share their first ten members");
 FIELD_STATS_PREFIX(FIELD_STATS_SAME_OFFSET)
 static_assert(sizeof(artp_field_update_stats_t) == 10 * sizeof(uint64_t), "ten members, and FIELD_STATS_PREFIX names them all");
@@ -1299,9 +1376,11 @@ int field_weight_counts(artp_field* f, unsigned long long* cnt, int n) {
 // sampler adopted where it fits the field (adopt), the stats stored.  middle(cnt, us, run) is the kind's step: cnt = the
 // counts of d_ucnt read so far, us = its stats to complete; it sets *run when the passes are to run.  `who` is the entry
 // point in the error.  A refusal writes nothing; a failure later leaves the field undefined.
-template <class Stats, class Middle>
+// before() runs behind the cleared flags and counts and in front of the diff: artp_field_shift's move, which flags tiles
+// in d_acc and counts into d_ucnt[5 ..] as the diff does (its own refusals are behind it by then).
+template <class Stats, class Before, class Middle>
 int field_update_run(artp_field* f, const char* who, const uint32_t* new_mask, int mask_on_device, const artp::FieldSub& sub,
-                     bool refresh, bool adopt, Stats* stored, Middle&& middle) {
+                     bool refresh, bool adopt, Stats* stored, Before&& before, Middle&& middle) {
   artp_ctx* c = f->ctx;
   HIP_TRY(c, hipSetDevice(c->device));
   hipStream_t st = c->lane->stream;
@@ -1311,6 +1390,7 @@ int field_update_run(artp_field* f, const char* who, const uint32_t* new_mask, i
   if (wtab) HIP_TRY(c, hipMemsetAsync(f->d_wacc, 0, f->n_tiles * sizeof(unsigned), st));
   HIP_TRY(c, hipMemsetAsync(f->d_ucnt, 0, 8 * sizeof(unsigned long long), st));
   unsigned long long cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  ARTP_TRY(before());
   if (new_mask) {
     ARTP_TRY(field_update_diff(f, new_mask, mask_on_device, sub, refresh, refresh ? c->sampler : f->sampler, cnt));
     if (cnt[4]) {
@@ -1341,6 +1421,12 @@ int field_update_run(artp_field* f, const char* who, const uint32_t* new_mask, i
   field_store_stats(ps, passes_ms, &us);
   *stored = us;
   return ARTP_OK;
+}
+template <class Stats, class Middle>
+int field_update_run(artp_field* f, const char* who, const uint32_t* new_mask, int mask_on_device, const artp::FieldSub& sub,
+                     bool refresh, bool adopt, Stats* stored, Middle&& middle) {
+  return field_update_run(f, who, new_mask, mask_on_device, sub, refresh, adopt, stored, [] { return (int)ARTP_OK; },
+                          std::forward<Middle>(middle));
 }
 
 int field_check_sources(artp_ctx* c, const artp::ReachRect& r, int n_yaw, const int* sources, size_t n_sources) {
@@ -1644,6 +1730,124 @@ int artp_field_update(artp_field* f, const uint32_t* new_mask, int mask_on_devic
 int artp_field_update_stats(artp_field* f, artp_field_update_stats_t* out) {
   if (!f || !out) return ARTP_ERR_INVALID_ARG;
   *out = f->ustats;
+  return ARTP_OK;
+}
+
+// DESIGN.md section 20.  Every refusal comes in front of the first write: the host's tests, then the moved sources
+// against new_mask on the device (field_update_sources_kernel on a copy of them), then field_update_run with the move in
+// front of its diff.
+int artp_field_shift(artp_field* f, const uint32_t* new_mask, int mask_on_device, int refresh_heights) {
+  if (!f || !new_mask) return ARTP_ERR_INVALID_ARG;
+  artp_ctx* c = f->ctx;
+  std::lock_guard<std::recursive_mutex> lock(c->mu);
+  const artp::FieldGrid& G = f->grid;
+  if (artp::field_has_wtab(G)) {
+    c->last_error = "artp_field_shift: a learned or a clearance-weighted field keeps a weight per node and move, which would "
+                    "have to move too: compute it anew on the new map";
+    return ARTP_ERR_INVALID_ARG;
+  }
+  if (!reach_have_lattice(c)) return ARTP_ERR_NO_MAP;
+  const MapGeom &a = f->geom, &b = c->geom;
+  if (a.rows != b.rows || a.cols != b.cols || a.len_x != b.len_x || a.len_y != b.len_y || a.res != b.res) {
+    c->last_error = "artp_field_shift: the context's map differs from the field's in rows, cols, lengths or resolution";
+    return ARTP_ERR_INVALID_ARG;
+  }
+  // artp_preprocessed_change's convention: cell (i, j) of the new map lies over cell (i - si, j - sj) of the old one
+  const double fi = (b.pos_x - a.pos_x) / b.res, fj = (b.pos_y - a.pos_y) / b.res;
+  const bool overlap = std::fabs(fi) < (double)G.nrows && std::fabs(fj) < (double)G.ncols;  // false for a NaN too
+  const long long si = overlap ? std::lround(fi) : 0, sj = overlap ? std::lround(fj) : 0;
+  std::vector<int> moved(f->h_src);
+  bool inside = overlap;
+  for (size_t i = 0; i + 2 < moved.size() && inside; i += 3) {
+    moved[i] += (int)si;
+    moved[i + 1] += (int)sj;
+    inside = moved[i] >= 0 && moved[i] < G.nrows && moved[i + 1] >= 0 && moved[i + 1] < G.ncols;
+  }
+  if (!inside) {
+    c->last_error = "artp_field_shift: a source leaves the rectangle with the map's move (the field is unchanged)";
+    return ARTP_ERR_INVALID_ARG;
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  hipStream_t st = c->lane->stream;
+  ARTP_TRY(field_update_scratch(f, !mask_on_device));
+  ARTP_TRY(field_ensure_scratch(f, moved.size(), 8));
+  const uint32_t* nm = new_mask;
+  if (!mask_on_device) {
+    HIP_TRY(c, hipMemcpyAsync(f->d_stage, new_mask, f->n_cells * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    nm = f->d_stage;
+  }
+  const artp::FieldSub whole{0, 0, G.nrows, G.ncols};
+  const int n_src = (int)(moved.size() / 3);
+  unsigned long long gone = 0;
+  HIP_TRY(c, hipMemcpyAsync(f->d_nodes, moved.data(), moved.size() * sizeof(int), hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemsetAsync(f->d_ucnt, 0, 8 * sizeof(unsigned long long), st));
+  hipLaunchKernelGGL(artp::field_update_sources_kernel, dim3((unsigned)((n_src + 63) / 64)), dim3(64), 0, st, G, whole,
+                     (const uint32_t*)f->d_mask, nm, (const int*)f->d_nodes, n_src, f->d_ucnt);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(&gone, f->d_ucnt + 4, sizeof(gone), hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipStreamSynchronize(st));  // the host copy of the mask is free from here
+  if (gone) {
+    c->last_error = "artp_field_shift: a moved source is not a node of new_mask (the field is unchanged)";
+    return ARTP_ERR_INVALID_ARG;
+  }
+  const bool moves = si != 0 || sj != 0;
+  const artp::FieldShift sh{(int)si, (int)sj, si + sj * (long long)G.nrows};
+  const size_t blk_words = (f->n_nodes + 1) / 2 * 2;  // field_blocked_alloc's
+  StreamTimer<2> tm(st);
+  return field_update_run(
+      f, "artp_field_shift", nm, 1, whole, refresh_heights != 0, true, &f->shstats,
+      [&]() -> int {
+        f->geom = c->geom;
+        if (!moves) return ARTP_OK;
+        ARTP_TRY(field_lazy(f, &f->d_shift, f->n_nodes * sizeof(uint32_t) + f->n_cells * 8 + blk_words * sizeof(uint16_t)));
+        uint32_t* hops_o = reinterpret_cast<uint32_t*>(f->d_shift);
+        uint32_t* mask_o = hops_o + f->n_nodes;
+        float* h_o = reinterpret_cast<float*>(mask_o + f->n_cells);
+        uint16_t* blk_o = reinterpret_cast<uint16_t*>(h_o + f->n_cells);
+        f->h_src = moved;
+        HIP_TRY(c, hipMemcpyAsync(f->d_src, f->h_src.data(), f->h_src.size() * sizeof(int), hipMemcpyHostToDevice, st));
+        tm.mark(0);
+        hipLaunchKernelGGL(artp::field_shift_nodes_kernel, dim3((unsigned)((f->n_nodes + 255) / 256)), dim3(256), 0, st, G, sh,
+                           (const double*)f->d_dist, (const uint32_t*)f->d_hops, (const uint16_t*)f->d_blk, f->d_snap, hops_o,
+                           blk_o, f->d_ucnt);
+        hipLaunchKernelGGL(artp::field_shift_cells_kernel, dim3((unsigned)((f->n_cells + 255) / 256)), dim3(256), 0, st, G, sh,
+                           c->sampler, c->geom.rows, f->rect, (const uint32_t*)f->d_mask, (const float*)f->d_h, mask_o, h_o,
+                           f->d_acc, f->d_ucnt);
+        HIP_TRY(c, hipGetLastError());
+        // dist stays the buffer artp_field_dist_dev handed out
+        HIP_TRY(c, hipMemcpyAsync(f->d_dist, f->d_snap, f->n_nodes * sizeof(double), hipMemcpyDeviceToDevice, st));
+        HIP_TRY(c, hipMemcpyAsync(f->d_hops, hops_o, f->n_nodes * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+        HIP_TRY(c, hipMemcpyAsync(f->d_mask, mask_o, f->n_cells * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+        HIP_TRY(c, hipMemcpyAsync(f->d_h, h_o, f->n_cells * sizeof(float), hipMemcpyDeviceToDevice, st));
+        if (f->d_blk)
+          HIP_TRY(c, hipMemcpyAsync(f->d_blk, blk_o, f->n_nodes * sizeof(uint16_t), hipMemcpyDeviceToDevice, st));
+        tm.mark(1);
+        return ARTP_OK;
+      },
+      // the kind's step: the move's counts.  After a move the passes always run: the border may have lost its support.
+      [&](unsigned long long* cnt, artp_field_shift_stats_t* us, bool* run) -> int {
+        if (moves) {
+          HIP_TRY(c, hipMemcpyAsync(cnt + 5, f->d_ucnt + 5, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+          HIP_TRY(c, hipStreamSynchronize(st));
+          if (f->d_blk) {
+            us->dropped_blocked = f->n_blocked - cnt[7];
+            f->n_blocked = cnt[7];
+          }
+        }
+        const long long ai = si < 0 ? -si : si, aj = sj < 0 ? -sj : sj;
+        us->shift_rows = si;
+        us->shift_cols = sj;
+        us->kept_cells = (uint64_t)(G.nrows - ai) * (uint64_t)(G.ncols - aj);
+        us->left_nodes = cnt[5];
+        us->move_ms = tm.ms(0, 1, moves);
+        *run = moves || cnt[0] || cnt[3];
+        return ARTP_OK;
+      });
+}
+
+int artp_field_shift_stats(artp_field* f, artp_field_shift_stats_t* out) {
+  if (!f || !out) return ARTP_ERR_INVALID_ARG;
+  *out = f->shstats;
   return ARTP_OK;
 }
 

@@ -188,6 +188,23 @@ class CostField:
         return self._stats(_capi.FieldClearanceUpdateStats, self.L.artp_field_clearance_update_stats,
                            "artp_field_clearance_update_stats")
 
+    def shift(self, mask, refresh_heights=True) -> dict:
+        """Carry the field across a move of the map by whole cells (artp_field_shift).  The
+        context's installed map is the new one; node (r, c, k) becomes (r + shift_rows, c + shift_cols, k), with the
+        shift taken from the two map positions as artp_preprocessed_change takes it.  mask: the field's whole rectangle
+        on the new map, as in the constructor.  The same bits as a new cost_field on the new map with that mask, the
+        moved sources and the blocked moves that stayed inside.  refresh_heights re-reads every height; without it the
+        kept cells keep theirs.  A learned or clearance-weighted field is refused.  Returns the shift's stats: add
+        shift_rows and shift_cols to your own node coordinates."""
+        mask_ptr, on_device, keep = self._mask_arg(mask, "CostField.shift")
+        self.ctx._chk(self.L.artp_field_shift(self.h, mask_ptr, on_device, int(bool(refresh_heights))), "artp_field_shift")
+        del keep
+        return self.shift_stats()
+
+    def shift_stats(self) -> dict:
+        """The numbers of the last shift that succeeded (zeros before the first)."""
+        return self._stats(_capi.FieldShiftStats, self.L.artp_field_shift_stats, "artp_field_shift_stats")
+
     def _update(self, call, name, mask, rect, *extra):
         """The mask and rect handling the three updates share; call = the C entry point artp_field_<name>.  mask None
         (update_learned only): no mask and no rect go down."""

@@ -494,6 +494,19 @@ class Planner {
     });
   }
 
+  // The field a computeCostField call kept, carried across a move of the map by whole cells (artp_field_shift,
+  // include/artp_c.h): setMap has installed the new map, whose position differs from the old one's by whole cells; node
+  // (r, c, k) becomes (r + si, c + sj, k) with si = lround((pos_x_new - pos_x_old) / res), sj likewise.  mask = rows *
+  // cols words on the NEW map (computeReachability, or an edited copy); every word is read.  The same bits as
+  // computeCostField on the new map with the sources moved.  refresh_heights re-reads every height; without it the kept
+  // cells keep theirs.  Throws, with the field unchanged, when a moved source leaves the map or is no node of mask, when
+  // the new map has another size or resolution, and for a learned or clearance-weighted field (compute those anew).
+  // Returns dist and refreshes the "cost_to_go" layer.
+  std::vector<double> shiftCostField(artp_field* kept, const std::vector<uint32_t>& mask, bool refresh_heights = true) {
+    return updateKeptField("shiftCostField", "artp_field_shift", kept, mask, false,
+                           [&] { return artp_field_shift(kept, mask.data(), 0, refresh_heights ? 1 : 0); });
+  }
+
   // The field a computeClearanceCostField call kept, brought in place to an edited mask (artp_field_update_clearance,
   // include/artp_c.h): the clearance map and the move costs computed again around rect, then updateCostField's passes.
   // mask, rect and refresh_heights as updateCostField takes them.  The same bits as computeClearanceCostField with the

@@ -585,6 +585,44 @@ int artp_field_update_clearance(artp_field* f, const uint32_t* new_mask, int mas
  * no change: zeros apart from reached_nodes) */
 int artp_field_clearance_update_stats(artp_field* f, artp_field_clearance_update_stats_t* out);
 
+/* ---- A field carried across a map move ---------------------------------------------------
+ * A robot-centric map moves with the robot by whole cells.  The context's installed sampler layers are the NEW map; the
+ * field still holds the geometry it was computed on.  With si = lround((pos_x_new - pos_x_old) / res) and sj likewise
+ * from pos_y -- artp_preprocessed_change's convention: cell (i, j) of the new map lies over cell (i - si, j - sj) of the
+ * old one -- node (r, c, k) of the field's rectangle becomes node (r + si, c + sj, k).  The rectangle keeps its map
+ * indices {row0, col0, nrows, ncols}: it moves with the map.  new_mask: nrows x ncols words of the rectangle ON THE NEW
+ * MAP, the layout artp_reachability_map writes, host (mask_on_device = 0) or device (1); every word is read (after a
+ * move a real map's validity changes within the reachability halo of all four borders, not only in the entered strips).
+ * After ARTP_OK dist, hops (artp_field_path), artp_field_edge_costs and reached_nodes are bit for bit those of
+ * artp_field_compute on the new map with new_mask, the field's own params, n_yaw, rectangle and reverse, its sources
+ * moved by (si, sj) and the blocked moves it kept.  Heights (objective 0) move with their cells; the cells that entered
+ * take the current sampler layer's; refresh_heights != 0 re-reads the whole rectangle.  The field adopts the context's
+ * sampler layers, map version and geometry: artp_field_path's poses, artp_field_plan and artp_field_simplify_paths work
+ * as on a new field.  Blocked moves move with their nodes; a slot is cleared when its node left or its neighbour now lies
+ * outside the rectangle (artp_field_blocked and _blocked_count report what was kept).  si = sj = 0 is artp_field_update
+ * with sub_rect = NULL: the same result and the same counts.
+ * Refused with NOTHING written (dist, hops, mask, heights, blocked moves, geometry, sources and all stats stay):
+ * ARTP_ERR_INVALID_ARG, with a text in artp_last_error, when the context's map differs from the field's in rows, cols,
+ * lengths or resolution, for a learned or a clearance-weighted field (their per-field tables would have to move too:
+ * compute them anew), when a moved source lies outside the rectangle (no overlap at all included) or is not a node of
+ * new_mask, when f or new_mask is NULL; ARTP_ERR_NO_MAP without sampler layers.  A failure after those checks
+ * (ARTP_ERR_HIP, ARTP_ERR_CAPACITY) leaves the field UNDEFINED: destroy it.  The first shift allocates its scratch (12
+ * bytes a node, 8 a cell) and keeps it.  Synchronous, on the context's current stream. */
+typedef struct artp_field_shift_stats_t {
+  uint64_t changed_words, removed_nodes, added_nodes, dead_nodes, hop_dead_nodes, unsupport_rounds, dist_rounds,
+      hop_rounds, tile_launches, reached_nodes; /* as artp_field_update_stats_t; the first three count the diff between
+                                                   the moved mask (0 in the cells that entered) and new_mask */
+  int64_t shift_rows, shift_cols; /* si, sj: what the caller adds to its own node coordinates */
+  uint64_t kept_cells;            /* cells of the overlap */
+  uint64_t left_nodes;            /* nodes of the cells that left the rectangle */
+  uint64_t dropped_blocked;       /* blocked moves cleared by the move */
+  double move_ms;                 /* stream time of the move */
+  double passes_ms;               /* host time of the four passes */
+} artp_field_shift_stats_t;
+int artp_field_shift(artp_field* f, const uint32_t* new_mask, int mask_on_device, int refresh_heights);
+/* the numbers of the last artp_field_shift that returned ARTP_OK (zeros before the first) */
+int artp_field_shift_stats(artp_field* f, artp_field_shift_stats_t* out);
+
 /* ---- ob::MotionValidator::checkMotion (OMPL DiscreteMotionValidator; call sites
  *      prm_motion_cost.cpp:652, lazy_prm_star_min_update.cpp:725), batched -----------------------
  * valid[i] = isValid(s2_i) && all interior states of the discretised segment are valid.
