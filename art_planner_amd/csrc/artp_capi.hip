@@ -240,8 +240,11 @@ int order_after_other_lanes(artp_ctx* c) {
   return ARTP_OK;
 }
 
-// Behind a map write that returns before the device is done (rectangle updates, same-geometry re-install): the other
-// lanes' next launches wait for it.  The host-synchronous writers (full upload, sampler layers) call it too: free.
+// Behind the last device write of every writer of state the lanes share (the height layers and their tables, the sampler
+// tables, the motion-cost activations and features: DESIGN.md section 21): the other lanes' next launches wait for it.
+// That matters for the writers that return before the device is done (rectangle updates, same-geometry re-install,
+// artp_cost_update_map_dev); for the host-synchronous ones (full upload, sampler layers, artp_cost_update_map) the wait
+// is over before it is asked for.
 int publish_map_write(artp_ctx* c) {
   if (!c->map_written) HIP_TRY(c, hipEventCreateWithFlags(&c->map_written, hipEventDisableTiming));
   HIP_TRY(c, hipEventRecord(c->map_written, c->lane->stream));
@@ -1530,6 +1533,7 @@ int artp_upload_sampler_layers(artp_ctx* c, const float* cum_prob, const float* 
   const size_t e = (size_t)rows * cols;
   c->map_version.fetch_add(1, std::memory_order_release);
   ARTP_TRY(ensure_sampler_storage(c, rows, cols));
+  ARTP_TRY(order_after_other_lanes(c));  // lanes that still sample or build lattice poses from the old tables
   float* p = c->sampler_buf.get();
   const float* src[6] = {cum_prob, elevation, normal_x, normal_y, normal_z, plane_fit_std_dev};
   const float** dst[6] = {&c->sampler.cum_prob, &c->sampler.elevation, &c->sampler.normal_x,
@@ -1550,7 +1554,7 @@ int artp_upload_sampler_layers(artp_ctx* c, const float* cum_prob, const float* 
   }
   c->sampler.from_distribution = c->params.sample_from_distribution;
   c->have_sampler = true;
-  return ARTP_OK;
+  return publish_map_write(c);
 }
 
 // The derived sampler tables (SamplerDev::cum_prob_t / pivots / cells) from the six layers in c->sampler_buf.
@@ -1586,6 +1590,7 @@ static int upload_sampler_layers_from_device(artp_ctx* c, const float* cum_prob,
   const size_t e = (size_t)rows * cols;
   c->map_version.fetch_add(1, std::memory_order_release);
   ARTP_TRY(ensure_sampler_storage(c, rows, cols));
+  ARTP_TRY(order_after_other_lanes(c));  // lanes that still sample or build lattice poses from the old tables
   float* p = c->sampler_buf.get();
   const float* src[6] = {cum_prob, elevation, normal_x, normal_y, normal_z, plane_fit_std_dev};
   const float** dst[6] = {&c->sampler.cum_prob, &c->sampler.elevation, &c->sampler.normal_x,
@@ -1606,7 +1611,7 @@ static int upload_sampler_layers_from_device(artp_ctx* c, const float* cum_prob,
   }
   c->sampler.from_distribution = c->params.sample_from_distribution;
   c->have_sampler = true;
-  return ARTP_OK;
+  return publish_map_write(c);
 }
 
 // min / max of the finite samples of a device layer (host result); false if there is none
@@ -3290,6 +3295,9 @@ static int cost_update_map_impl(artp_ctx* c, const float* elev_xy, bool on_devic
   HIP_TRY(c, hipSetDevice(c->device));
   const size_t n = (size_t)rows * cols;
   const float* d_map = elev_xy;  // a device array is read where it lies (stream-ordered, like every _dev argument)
+  // d_map_f32, d_act and d_feat are the context's: cost queries and learned fields still queued on the other lanes read
+  // the old features, and their next ones must see the new (the lane rule of the layer writers)
+  ARTP_TRY(order_after_other_lanes(c));
   if (!on_device) {
     HIP_TRY(c, c->d_map_f32.reserve(n * sizeof(float)));
     HIP_TRY(c, hipMemcpyAsync(c->d_map_f32.get(), elev_xy, n * sizeof(float), hipMemcpyHostToDevice, c->lane->stream));
@@ -3305,6 +3313,7 @@ static int cost_update_map_impl(artp_ctx* c, const float* elev_xy, bool on_devic
   g.col_bias = (int)((len_y / res - 2 * 24) / 2 * 0.5);
   g.cx = cx;
   g.cy = cy;
+  ARTP_TRY(publish_map_write(c));
   if (!on_device) HIP_TRY(c, hipStreamSynchronize(c->lane->stream));  // the caller's host buffer is free again
   c->have_features = true;
   return ARTP_OK;

@@ -85,8 +85,16 @@ int artp_synchronize(artp_ctx* ctx); /* every lane's stream */
  * different lanes overlap on the GPU: a planner thread that validates a batch as two halves on two lanes hides the
  * pipeline's short serial kernels and pairs kernels with different bottlenecks (bench.py: 1.77 -> 1.66 ms per 2^22
  * states).  Every call works on the CURRENT lane (0 after artp_create); artp_set_lane switches it (first use of a
- * lane creates its stream).  Work on different lanes is unordered: the caller orders map / layer updates against the
- * lanes that still read the old map (artp_synchronize, or stream events).  The current lane is state of the
+ * lane creates its stream).  Calls that only read the shared state are unordered across lanes.  Every call that WRITES
+ * state the lanes share orders itself, on the device: the height layers and their tables (artp_upload_layer,
+ * artp_update_layer_rect(s), artp_preprocessed_install), the sampler tables (artp_upload_sampler_layers,
+ * artp_preprocessed_install, artp_preprocessed_reweight_dev with install_sampler, the roadmap's density rounds) and the
+ * motion-cost feature map (artp_cost_update_map, _dev, _layer; artp_cost_load_weights waits for the whole device).  Such a
+ * call, issued on the current lane, runs behind everything the other lanes were given before it (they still see the old
+ * state), and whatever any lane is given after it runs behind the write (it sees the new state), whether or not the
+ * call returns before the device is done.  One thing is left to the caller: a _dev RESULT produced on one lane and passed
+ * as an argument to a call on another lane is ordered by the caller (artp_synchronize, or stream events); the library
+ * orders its own state, not the caller's buffers.  The current lane is state of the
  * context, not of the calling thread: lanes are for ONE host thread that keeps several batches in flight (threads
  * that share a context would switch each other's lane; give each thread its own context).  No equivalent in the
  * reference (it validates one state at a time on the calling thread). */
