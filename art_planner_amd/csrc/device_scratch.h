@@ -29,6 +29,7 @@
 // Owner of device allocations: what it still holds when it goes out of scope is freed, on every way out.  Declared at
 // the top of the scope that owns the buffers (a function's temporaries) or as a member (an object's buffers).  Plain
 // hipMalloc / hipFree: a hipFree waits for the device, so where and how often memory is freed is part of a step's time.
+// (DeviceBuffer below and PinnedBuffer can be moved; a DeviceScratch hands single buffers over with take / adopt.)
 class DeviceScratch {
  public:
   DeviceScratch() = default;
@@ -74,14 +75,24 @@ class DeviceScratch {
   std::vector<void*> ptrs_;
 };
 
-// One grow-only block of device memory with its owner: a member of whatever keeps the block (artp_ctx, a lane).  The
-// caller decides how much to ask for (padding is its policy); the block is freed with its owner.
+// One grow-only block of device memory with its owner: a member of whatever keeps the block (artp_ctx, a lane, a
+// roadmap).  The caller decides how much to ask for (padding is its policy); the block is freed with its owner.
+// Movable, not copyable, so that an object made of such members can be swapped whole: the moved-from buffer is empty,
+// the assigned-to buffer frees what it held first, a move onto itself changes nothing.
 template <class T = void>
 class DeviceBuffer {
  public:
   DeviceBuffer() = default;
   DeviceBuffer(const DeviceBuffer&) = delete;
   DeviceBuffer& operator=(const DeviceBuffer&) = delete;
+  DeviceBuffer(DeviceBuffer&& o) noexcept : p_(o.p_), cap_(o.cap_) { o.p_ = nullptr, o.cap_ = 0; }
+  DeviceBuffer& operator=(DeviceBuffer&& o) noexcept {
+    if (this != &o) {
+      adopt(o.p_, o.cap_);
+      o.p_ = nullptr, o.cap_ = 0;
+    }
+    return *this;
+  }
   ~DeviceBuffer() { (void)reset(); }
   // Nothing if `bytes` fit; else the old block is freed FIRST (peak memory: one block), then exactly `bytes` are
   // allocated.  After a failure the buffer is empty -- null and capacity 0 -- so the next request allocates again.
@@ -99,7 +110,8 @@ class DeviceBuffer {
     cap_ = 0;
     return p ? hipFree(p) : hipSuccess;
   }
-  // a block that hipFree frees but hipMalloc did not make (hipExtMallocWithFlags) is freed here from now on
+  // a block from another owner (DeviceScratch::take), or one that hipFree frees but hipMalloc did not make
+  // (hipExtMallocWithFlags), is freed here from now on; what the buffer held is freed first
   void adopt(void* p, size_t bytes) {
     (void)reset();
     p_ = p;

@@ -8,13 +8,22 @@
 
 // One grow-only block of pinned host memory (hipHostMalloc with `flags`) with its owner, by DeviceBuffer's rules.
 // host() is the block, dev() its device address where the flags ask for a mapped block (null otherwise).  Freed with
-// hipHostFree.  (A header of its own: device_scratch.h keeps to hipMalloc / hipFree.)
+// hipHostFree.  Movable like DeviceBuffer.  (A header of its own: device_scratch.h keeps to hipMalloc / hipFree.)
 template <class T = void>
 class PinnedBuffer {
  public:
   PinnedBuffer() = default;
   PinnedBuffer(const PinnedBuffer&) = delete;
   PinnedBuffer& operator=(const PinnedBuffer&) = delete;
+  PinnedBuffer(PinnedBuffer&& o) noexcept : p_(o.p_), dev_(o.dev_), cap_(o.cap_) { o.p_ = o.dev_ = nullptr, o.cap_ = 0; }
+  PinnedBuffer& operator=(PinnedBuffer&& o) noexcept {
+    if (this != &o) {
+      (void)reset();
+      p_ = o.p_, dev_ = o.dev_, cap_ = o.cap_;
+      o.p_ = o.dev_ = nullptr, o.cap_ = 0;
+    }
+    return *this;
+  }
   ~PinnedBuffer() { (void)reset(); }
   hipError_t reserve(size_t bytes, unsigned flags) {
     if (cap_ >= bytes) return hipSuccess;

@@ -516,11 +516,11 @@ const char* const kPreLayerNames[] = {"elevation", "traversability", "normal_x",
 struct artp_preprocessed {
   int rows = 0, cols = 0;
   double len_x = 0, len_y = 0, pos_x = 0, pos_y = 0;
-  float* buf = nullptr;          // PRE_COUNT layers + cum_prob_rowwise (rows) + 1 scalar
-  float* layer(int k) const { return buf + (size_t)k * rows * cols; }
-  float* rowwise() const { return buf + (size_t)PRE_COUNT * rows * cols; }
+  DeviceBuffer<float> buf;       // PRE_COUNT layers + cum_prob_rowwise (rows) + 1 scalar
+  float* layer(int k) const { return buf.get() + (size_t)k * rows * cols; }
+  float* rowwise() const { return buf.get() + (size_t)PRE_COUNT * rows * cols; }
   // scalars behind the row CDF: [0] total probability, [1] max of the blurred density (bits), [2..5] two doubles
-  float* scalars() const { return buf + ((((size_t)PRE_COUNT * rows * cols) + rows + 1) & ~(size_t)1); }
+  float* scalars() const { return buf.get() + ((((size_t)PRE_COUNT * rows * cols) + rows + 1) & ~(size_t)1); }
 };
 
 
@@ -570,7 +570,7 @@ std::vector<int> circular_footprint(int size, int* fsize) {
 // [capped unknown share], then the CDF -- the part of the processor chain that depends on the roadmap's vertices
 // and that Map::reApplyPreprocessing() (map.cpp:94-96) re-runs while PRMMotionCostMaintainer::sampleGraph grows
 // the roadmap (prm_motion_cost.cpp:190-193).  d_verts: n_vertices x 7 doubles in HBM (may be null).  Asynchronous.
-bool pre_sampling_distribution(artp_ctx* c, artp_preprocessed* pp, const artp_preprocess_params* prm,
+int pre_sampling_distribution(artp_ctx* c, artp_preprocessed* pp, const artp_preprocess_params* prm,
                                const double* d_verts, size_t n_vertices) {
   const int rows = pp->rows, cols = pp->cols, n = rows * cols;
   const double res = pp->len_x / rows;
@@ -582,7 +582,7 @@ bool pre_sampling_distribution(artp_ctx* c, artp_preprocessed* pp, const artp_pr
   DeviceScratch S;
   unsigned* max_bits = reinterpret_cast<unsigned*>(pp->scalars() + 1);
   double* mass = reinterpret_cast<double*>(pp->scalars() + 2);  // 8-byte aligned (even offset, see scalars())
-  bool ok = hipMemsetAsync(pp->scalars(), 0, 8 * sizeof(float), st) == hipSuccess;
+  HIP_TRY(c, hipMemsetAsync(pp->scalars(), 0, 8 * sizeof(float), st));
   const bool density = prm->use_inverse_vertex_density && n_vertices > 0 && d_verts;
   if (density) {
     const double blur_radius = (c->params.torso_length + c->params.torso_width) * 0.25;  // planner.cpp:48
@@ -598,20 +598,18 @@ bool pre_sampling_distribution(artp_ctx* c, artp_preprocessed* pp, const artp_pr
       sum += taps[i];
     }
     for (int i = 0; i < k; ++i) taps[i] = (float)(taps[i] * (1.0 / sum));
-    ok = ok && S.alloc(&d_taps, (size_t)k) == hipSuccess &&
-         hipMemcpyAsync(d_taps, taps.data(), k * sizeof(float), hipMemcpyHostToDevice, st) == hipSuccess &&
-         hipMemsetAsync(L(PRE_T0), 0, (size_t)n * 4, st) == hipSuccess;
-    if (ok) {
-      hipLaunchKernelGGL(artp::vertex_histogram_kernel, dim3((unsigned)((n_vertices + 255) / 256)), blk, 0, st,
-                         d_verts, n_vertices, geom, L(PRE_T0));
-      hipLaunchKernelGGL(artp::gauss_pass_kernel<true>, grid, blk, 0, st, (const float*)L(PRE_T0), rows, cols,
-                         (const float*)d_taps, k, L(PRE_T1));
-      hipLaunchKernelGGL(artp::gauss_pass_kernel<false>, grid, blk, 0, st, (const float*)L(PRE_T1), rows, cols,
-                         (const float*)d_taps, k, L(PRE_NSAMPLES));
-      hipLaunchKernelGGL(artp::nonneg_max_kernel, grid, blk, 0, st, (const float*)L(PRE_NSAMPLES), n, max_bits);
-    }
+    HIP_TRY(c, S.alloc(&d_taps, (size_t)k));
+    HIP_TRY(c, hipMemcpyAsync(d_taps, taps.data(), k * sizeof(float), hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemsetAsync(L(PRE_T0), 0, (size_t)n * 4, st));
+    hipLaunchKernelGGL(artp::vertex_histogram_kernel, dim3((unsigned)((n_vertices + 255) / 256)), blk, 0, st,
+                       d_verts, n_vertices, geom, L(PRE_T0));
+    hipLaunchKernelGGL(artp::gauss_pass_kernel<true>, grid, blk, 0, st, (const float*)L(PRE_T0), rows, cols,
+                       (const float*)d_taps, k, L(PRE_T1));
+    hipLaunchKernelGGL(artp::gauss_pass_kernel<false>, grid, blk, 0, st, (const float*)L(PRE_T1), rows, cols,
+                       (const float*)d_taps, k, L(PRE_NSAMPLES));
+    hipLaunchKernelGGL(artp::nonneg_max_kernel, grid, blk, 0, st, (const float*)L(PRE_NSAMPLES), n, max_bits);
   } else {
-    ok = ok && hipMemsetAsync(L(PRE_NSAMPLES), 0, (size_t)n * 4, st) == hipSuccess;
+    HIP_TRY(c, hipMemsetAsync(L(PRE_NSAMPLES), 0, (size_t)n * 4, st));
   }
   hipLaunchKernelGGL(artp::base_distribution_kernel, grid, blk, 0, st,
                      density ? (const float*)L(PRE_NSAMPLES) : (const float*)nullptr, (const unsigned*)max_bits,
@@ -635,99 +633,33 @@ bool pre_sampling_distribution(artp_ctx* c, artp_preprocessed* pp, const artp_pr
                      (const float*)L(PRE_SAMPLE_PROB), rows, cols, L(PRE_CUM_PROB), row_sum);
   hipLaunchKernelGGL(artp::cdf_rowwise_kernel, dim3(1), dim3(256), 0, st, (const float*)row_sum, rows, pp->rowwise(),
                      total);
-  ok = ok && hipGetLastError() == hipSuccess;
-  if (d_taps) ok = hipStreamSynchronize(st) == hipSuccess && ok;  // the taps are read by the kernels above
-  return ok;
-}
-}  // namespace
-
-extern "C" {
-
-void artp_preprocess_params_defaults(artp_preprocess_params* p) {
-  if (!p) return;
-  std::memset(p, 0, sizeof(*p));
-  p->traversability_thres = 0.5f;  // Params::planner.traversability_thres (params.h:24)
-  // Params::planner.safety defaults are all zero (params.h:27-34): no morphology
-  p->use_inverse_vertex_density = 0;      // params.h:82-84
-  p->use_max_prob_unknown_samples = 0;
-  p->max_prob_unknown_samples = 0.1;
+  HIP_TRY(c, hipGetLastError());
+  if (d_taps) HIP_TRY(c, hipStreamSynchronize(st));  // the taps are read by the kernels above
+  return ARTP_OK;
 }
 
-void artp_preprocess_params_yaml(artp_preprocess_params* p) {  // art_planner_ros/config/params.yaml
-  artp_preprocess_params_defaults(p);
-  if (!p) return;
-  p->traversability_thres = 0.15f;
-  p->foothold_margin = 0.3;
-  p->foothold_margin_max_hole_size = 0.3;
-  p->foothold_margin_max_drop = 0.3;
-  p->foothold_margin_max_drop_search_radius = 0.16;
-  p->foothold_margin_min_step = 0.3;
-  p->foothold_size = 0.1;
-  p->use_inverse_vertex_density = 1;      // params.yaml:49-51
-  p->use_max_prob_unknown_samples = 1;
-  p->max_prob_unknown_samples = 0.1;
-}
-
-void artp_preprocessed_destroy(artp_preprocessed* pp) {
-  if (!pp) return;
-  if (pp->buf) (void)hipFree(pp->buf);
-  delete pp;
-}
-
-int artp_preprocess_map(artp_ctx* c, const float* elevation, const float* traversability, int rows, int cols,
-                        double len_x, double len_y, double pos_x, double pos_y, const artp_preprocess_params* prm,
-                        artp_preprocessed** out) {
-  artp_preprocess_inputs in;
-  std::memset(&in, 0, sizeof(in));
-  in.elevation = elevation;
-  in.traversability = traversability;
-  in.rows = rows;
-  in.cols = cols;
-  in.len_x = len_x;
-  in.len_y = len_y;
-  in.pos_x = pos_x;
-  in.pos_y = pos_y;
-  return artp_preprocess_map_ex(c, &in, prm, out);
-}
-
-int artp_preprocess_map_ex(artp_ctx* c, const artp_preprocess_inputs* in, const artp_preprocess_params* prm,
-                           artp_preprocessed** out) {
-  if (!c || !in || !in->elevation || !prm || !out || in->rows < 2 || in->cols < 2 ||
-      (in->n_vertices && !in->vertex_se3))
-    return ARTP_ERR_INVALID_ARG;
+// The processor chain of artp_preprocess_map_ex on a new object (its geometry set, its lock held): the block of layers
+// is allocated, filled and synchronised.  A failure leaves the half-made object to the caller.
+int pre_fill_layers(artp_ctx* c, const artp_preprocess_inputs* in, const artp_preprocess_params* prm,
+                    artp_preprocessed* pp) {
   const float* elevation = in->elevation;
   const float* traversability = in->traversability;
-  const int rows = in->rows, cols = in->cols;
-  const double len_x = in->len_x, len_y = in->len_y, pos_x = in->pos_x, pos_y = in->pos_y;
-  *out = nullptr;
-  std::unique_lock<std::recursive_mutex> lock(c->mu);
-  HIP_TRY(c, hipSetDevice(c->device));
-  const int n = rows * cols;
-  auto pp = new artp_preprocessed();
-  pp->rows = rows;
-  pp->cols = cols;
-  pp->len_x = len_x;
-  pp->len_y = len_y;
-  pp->pos_x = pos_x;
-  pp->pos_y = pos_y;
-  if (hipMalloc(reinterpret_cast<void**>(&pp->buf), ((size_t)PRE_COUNT * n + rows + 2 + 16) * sizeof(float)) != hipSuccess) {
-    delete pp;
-    c->last_error = "hipMalloc failed in artp_preprocess_map";
-    return ARTP_ERR_HIP;
-  }
+  const int rows = pp->rows, cols = pp->cols, n = rows * cols;
+  const double len_x = pp->len_x, len_y = pp->len_y, pos_x = pp->pos_x, pos_y = pp->pos_y;
+  HIP_TRY(c, pp->buf.reserve(((size_t)PRE_COUNT * n + rows + 2 + 16) * sizeof(float)));
   hipStream_t st = c->lane->stream;
   const double res = len_x / rows;
   const dim3 grid((unsigned)((n + 255) / 256)), blk(256);
   auto L = [&](int k) { return pp->layer(k); };
-  bool ok = hipMemcpyAsync(L(PRE_ELEV), elevation, (size_t)n * 4, hipMemcpyHostToDevice, st) == hipSuccess;
+  HIP_TRY(c, hipMemcpyAsync(L(PRE_ELEV), elevation, (size_t)n * 4, hipMemcpyHostToDevice, st));
   if (traversability)
-    ok = ok && hipMemcpyAsync(L(PRE_TRAV), traversability, (size_t)n * 4, hipMemcpyHostToDevice, st) == hipSuccess;
+    HIP_TRY(c, hipMemcpyAsync(L(PRE_TRAV), traversability, (size_t)n * 4, hipMemcpyHostToDevice, st));
   else
     hipLaunchKernelGGL(artp::pre_fill_kernel, grid, blk, 0, st, L(PRE_TRAV), n, 1.0f);  // checkTraversability
 
   // addKnownCells (basic.cpp:26-38): "observed" = the cells that were valid before inpainting
   if (in->observed)
-    ok = ok && hipMemcpyAsync(L(PRE_OBSERVED), in->observed, (size_t)n * 4, hipMemcpyHostToDevice, st) == hipSuccess;
+    HIP_TRY(c, hipMemcpyAsync(L(PRE_OBSERVED), in->observed, (size_t)n * 4, hipMemcpyHostToDevice, st));
   else
     hipLaunchKernelGGL(artp::pre_fill_kernel, grid, blk, 0, st, L(PRE_OBSERVED), n, 1.0f);
   if (c->params.unknown_space_untraversable)
@@ -762,9 +694,9 @@ int artp_preprocess_map_ex(artp_ctx* c, const artp_preprocess_inputs* in, const 
   }
   int* d_fp = nullptr;
   DeviceScratch S;
-  ok = ok && S.alloc(&d_fp, fp_host.size()) == hipSuccess &&
-       hipMemcpyAsync(d_fp, fp_host.data(), fp_host.size() * sizeof(int), hipMemcpyHostToDevice, st) == hipSuccess &&
-       hipStreamSynchronize(st) == hipSuccess;  // fp_host dies with this call
+  HIP_TRY(c, S.alloc(&d_fp, fp_host.size()));
+  HIP_TRY(c, hipMemcpyAsync(d_fp, fp_host.data(), fp_host.size() * sizeof(int), hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipStreamSynchronize(st));  // fp_host dies with this call
   auto footprint = [&](int size, int* fsize) -> const int* {
     int q = 0;
     while (q < 5 && fp_sizes[q] != size) ++q;
@@ -774,12 +706,12 @@ int artp_preprocess_map_ex(artp_ctx* c, const artp_preprocess_inputs* in, const 
   auto erode = [&](const float* in, int size, float* o) {
     int fs = 0;
     const int* fp = footprint(size, &fs);
-    if (ok) hipLaunchKernelGGL(artp::morph_kernel<false>, grid, blk, 0, st, in, rows, cols, fs, fp, o);
+    hipLaunchKernelGGL(artp::morph_kernel<false>, grid, blk, 0, st, in, rows, cols, fs, fp, o);
   };
   auto dilate = [&](const float* in, int size, float* o) {
     int fs = 0;
     const int* fp = footprint(size, &fs);
-    if (ok) hipLaunchKernelGGL(artp::morph_kernel<true>, grid, blk, 0, st, in, rows, cols, fs, fp, o);
+    hipLaunchKernelGGL(artp::morph_kernel<true>, grid, blk, 0, st, in, rows, cols, fs, fp, o);
   };
   hipLaunchKernelGGL(artp::pre_threshold_kernel, grid, blk, 0, st, (const float*)L(PRE_TRAV), n,
                      prm->traversability_thres, L(PRE_TRAV_FILTER));
@@ -806,17 +738,82 @@ int artp_preprocess_map_ex(artp_ctx* c, const artp_preprocess_inputs* in, const 
   erode(L(PRE_T1), wall, L(PRE_SAMPLE_FILTER));
   // the sampling distribution (planner.cpp:43-56): [inverse vertex density] * sample filter [capped unknown share]
   double* d_verts = nullptr;
-  if (prm->use_inverse_vertex_density && in->n_vertices > 0)
-    ok = ok && S.alloc(&d_verts, (size_t)in->n_vertices * 7) == hipSuccess &&
-         hipMemcpyAsync(d_verts, in->vertex_se3, in->n_vertices * 7 * sizeof(double), hipMemcpyHostToDevice, st) ==
-             hipSuccess;
-  ok = ok && pre_sampling_distribution(c, pp, prm, d_verts, d_verts ? in->n_vertices : 0);
-  ok = ok && hipGetLastError() == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
-  if (!ok) {
-    c->last_error = "device preprocessing failed";
+  if (prm->use_inverse_vertex_density && in->n_vertices > 0) {
+    HIP_TRY(c, S.alloc(&d_verts, (size_t)in->n_vertices * 7));
+    HIP_TRY(c, hipMemcpyAsync(d_verts, in->vertex_se3, in->n_vertices * 7 * sizeof(double), hipMemcpyHostToDevice, st));
+  }
+  ARTP_TRY(pre_sampling_distribution(c, pp, prm, d_verts, d_verts ? in->n_vertices : 0));
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipStreamSynchronize(st));
+  return ARTP_OK;
+}
+}  // namespace
+
+extern "C" {
+
+void artp_preprocess_params_defaults(artp_preprocess_params* p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof(*p));
+  p->traversability_thres = 0.5f;  // Params::planner.traversability_thres (params.h:24)
+  // Params::planner.safety defaults are all zero (params.h:27-34): no morphology
+  p->use_inverse_vertex_density = 0;      // params.h:82-84
+  p->use_max_prob_unknown_samples = 0;
+  p->max_prob_unknown_samples = 0.1;
+}
+
+void artp_preprocess_params_yaml(artp_preprocess_params* p) {  // art_planner_ros/config/params.yaml
+  artp_preprocess_params_defaults(p);
+  if (!p) return;
+  p->traversability_thres = 0.15f;
+  p->foothold_margin = 0.3;
+  p->foothold_margin_max_hole_size = 0.3;
+  p->foothold_margin_max_drop = 0.3;
+  p->foothold_margin_max_drop_search_radius = 0.16;
+  p->foothold_margin_min_step = 0.3;
+  p->foothold_size = 0.1;
+  p->use_inverse_vertex_density = 1;      // params.yaml:49-51
+  p->use_max_prob_unknown_samples = 1;
+  p->max_prob_unknown_samples = 0.1;
+}
+
+void artp_preprocessed_destroy(artp_preprocessed* pp) { delete pp; }
+
+int artp_preprocess_map(artp_ctx* c, const float* elevation, const float* traversability, int rows, int cols,
+                        double len_x, double len_y, double pos_x, double pos_y, const artp_preprocess_params* prm,
+                        artp_preprocessed** out) {
+  artp_preprocess_inputs in;
+  std::memset(&in, 0, sizeof(in));
+  in.elevation = elevation;
+  in.traversability = traversability;
+  in.rows = rows;
+  in.cols = cols;
+  in.len_x = len_x;
+  in.len_y = len_y;
+  in.pos_x = pos_x;
+  in.pos_y = pos_y;
+  return artp_preprocess_map_ex(c, &in, prm, out);
+}
+
+int artp_preprocess_map_ex(artp_ctx* c, const artp_preprocess_inputs* in, const artp_preprocess_params* prm,
+                           artp_preprocessed** out) {
+  if (!c || !in || !in->elevation || !prm || !out || in->rows < 2 || in->cols < 2 ||
+      (in->n_vertices && !in->vertex_se3))
+    return ARTP_ERR_INVALID_ARG;
+  *out = nullptr;
+  std::unique_lock<std::recursive_mutex> lock(c->mu);
+  HIP_TRY(c, hipSetDevice(c->device));
+  auto pp = new artp_preprocessed();
+  pp->rows = in->rows;
+  pp->cols = in->cols;
+  pp->len_x = in->len_x;
+  pp->len_y = in->len_y;
+  pp->pos_x = in->pos_x;
+  pp->pos_y = in->pos_y;
+  const int rc = pre_fill_layers(c, in, prm, pp);
+  if (rc != ARTP_OK) {  // undo, in the order it always had: the lock is dropped, then the half-made object destroyed
     lock.unlock();
     artp_preprocessed_destroy(pp);
-    return ARTP_ERR_HIP;
+    return rc;
   }
   *out = pp;
   return ARTP_OK;
@@ -896,21 +893,17 @@ int artp_preprocessed_install(artp_ctx* c, const artp_preprocessed* pp) {
     return ARTP_ERR_NO_MAP;
   }
   // everything stays in HBM: layout flips, copies and the z-bound reduction run on the device
-  int rc = upload_layer_from_device(c, ARTP_SLOT_BODY, pp->layer(PRE_ELEV), pp->rows, pp->cols, pp->len_x, pp->len_y,
-                                    pp->pos_x, pp->pos_y);
-  if (rc) return rc;
-  rc = upload_layer_from_device(c, ARTP_SLOT_FEET, pp->layer(PRE_MASKED), pp->rows, pp->cols, pp->len_x, pp->len_y,
-                                pp->pos_x, pp->pos_y);
-  if (rc) return rc;
-  rc = upload_sampler_layers_from_device(c, pp->layer(PRE_CUM_PROB), pp->rowwise(), pp->layer(PRE_ELEV),
-                                         pp->layer(PRE_NX), pp->layer(PRE_NY), pp->layer(PRE_NZ), pp->layer(PRE_STD),
-                                         pp->rows, pp->cols, pp->len_x, pp->len_y, pp->pos_x, pp->pos_y);
-  if (rc) return rc;
+  ARTP_TRY(upload_layer_from_device(c, ARTP_SLOT_BODY, pp->layer(PRE_ELEV), pp->rows, pp->cols, pp->len_x, pp->len_y,
+                                    pp->pos_x, pp->pos_y));
+  ARTP_TRY(upload_layer_from_device(c, ARTP_SLOT_FEET, pp->layer(PRE_MASKED), pp->rows, pp->cols, pp->len_x, pp->len_y,
+                                    pp->pos_x, pp->pos_y));
+  ARTP_TRY(upload_sampler_layers_from_device(c, pp->layer(PRE_CUM_PROB), pp->rowwise(), pp->layer(PRE_ELEV),
+                                             pp->layer(PRE_NX), pp->layer(PRE_NY), pp->layer(PRE_NZ), pp->layer(PRE_STD),
+                                             pp->rows, pp->cols, pp->len_x, pp->len_y, pp->pos_x, pp->pos_y));
   // bounds.low[2] / high[2] = min / max finite elevation -/+ reach.z / 2 (planner.cpp:146-156)
   float lo = 0.f, hi = 0.f;
   bool any = false;
-  rc = finite_min_max_dev(c, pp->layer(PRE_ELEV), n, &lo, &hi, &any);
-  if (rc) return rc;
+  ARTP_TRY(finite_min_max_dev(c, pp->layer(PRE_ELEV), n, &lo, &hi, &any));
   if (!any) lo = hi = 0.f;
   return artp_set_z_bounds(c, (double)lo - c->params.reach_z / 2, (double)hi + c->params.reach_z / 2);
 }
@@ -925,10 +918,7 @@ int artp_preprocessed_reweight_dev(artp_ctx* c, artp_preprocessed* pp, const art
   if (!c || !pp || !prm || (n_vertices && !vertex_se3_dev)) return ARTP_ERR_INVALID_ARG;
   std::lock_guard<std::recursive_mutex> lock(c->mu);
   HIP_TRY(c, hipSetDevice(c->device));
-  if (!pre_sampling_distribution(c, pp, prm, vertex_se3_dev, n_vertices)) {
-    c->last_error = "re-weighting the sampling distribution failed";
-    return ARTP_ERR_HIP;
-  }
+  ARTP_TRY(pre_sampling_distribution(c, pp, prm, vertex_se3_dev, n_vertices));
   if (!install_sampler) return ARTP_OK;
   float total = 0.f;
   HIP_TRY(c, hipMemcpyAsync(&total, pp->scalars(), 4, hipMemcpyDeviceToHost, c->lane->stream));
@@ -949,8 +939,7 @@ static int inpaint_dev(artp_ctx* c, const float* d_in, int rows, int cols, int m
   const size_t n = (size_t)rows * cols;
   float lo = 0.f, hi = 0.f;
   bool any = false;
-  int rc = finite_min_max_dev(c, d_in, n, &lo, &hi, &any);
-  if (rc) return rc;
+  ARTP_TRY(finite_min_max_dev(c, d_in, n, &lo, &hi, &any));
   std::lock_guard<std::recursive_mutex> lock(c->mu);
   HIP_TRY(c, hipSetDevice(c->device));
   hipStream_t st = c->lane->stream;
@@ -961,21 +950,21 @@ static int inpaint_dev(artp_ctx* c, const float* d_in, int rows, int cols, int m
   unsigned long long* d_holes = reinterpret_cast<unsigned long long*>(c->lane->d_count.get());
   unsigned* d_left = reinterpret_cast<unsigned*>(buf + 4 * n + (8 - (4 * n) % 8) % 8);
   const dim3 grid((unsigned)((n + 255) / 256)), blk(256);
-  if (hipMemsetAsync(d_holes, 0, 8, st) != hipSuccess) return ARTP_ERR_HIP;
+  HIP_TRY(c, hipMemsetAsync(d_holes, 0, 8, st));
   if (!any || !(hi > lo)) {
     mode &= 1;
     // no valid cell at all, or a constant layer (the reference divides by max - min = 0 here): holes take the
     // constant, nothing is quantised
     hipLaunchKernelGGL(artp::inpaint_quantise_kernel, grid, blk, 0, st, d_in, (int)n, mode, 0.0f, 1.0f, q, known, d_holes);
     unsigned long long h = 0;
-    if (hipMemcpyAsync(&h, d_holes, 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-      return ARTP_ERR_HIP;
+    HIP_TRY(c, hipMemcpyAsync(&h, d_holes, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
     if (n_holes) *n_holes = h;
     std::vector<float> tmp(n);
-    if (hipMemcpy(tmp.data(), d_in, n * 4, hipMemcpyDeviceToHost) != hipSuccess) return ARTP_ERR_HIP;
+    HIP_TRY(c, hipMemcpy(tmp.data(), d_in, n * 4, hipMemcpyDeviceToHost));
     for (float& v : tmp)
       if (!std::isfinite(v)) v = any ? lo : 0.0f;
-    if (hipMemcpy(d_out, tmp.data(), n * 4, hipMemcpyHostToDevice) != hipSuccess) return ARTP_ERR_HIP;
+    HIP_TRY(c, hipMemcpy(d_out, tmp.data(), n * 4, hipMemcpyHostToDevice));
     return ARTP_OK;
   }
   // Telea's march reads a 3 x 3 neighbourhood around every band pixel with cv::inpaint's border index rule: it needs at
@@ -984,13 +973,12 @@ static int inpaint_dev(artp_ctx* c, const float* d_in, int rows, int cols, int m
   mode &= 1;
   hipLaunchKernelGGL(artp::inpaint_quantise_kernel, grid, blk, 0, st, d_in, (int)n, mode, lo, hi, q, known, d_holes);
   unsigned long long h = 0;
-  if (hipMemcpyAsync(&h, d_holes, 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-    return ARTP_ERR_HIP;
+  HIP_TRY(c, hipMemcpyAsync(&h, d_holes, 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipStreamSynchronize(st));
   if (n_holes) *n_holes = h;
   if (h == 0) {
-    if (d_out != d_in && hipMemcpyAsync(d_out, d_in, n * 4, hipMemcpyDeviceToDevice, st) != hipSuccess)
-      return ARTP_ERR_HIP;
-    if (hipStreamSynchronize(st) != hipSuccess) return ARTP_ERR_HIP;
+    if (d_out != d_in) HIP_TRY(c, hipMemcpyAsync(d_out, d_in, n * 4, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
     return ARTP_OK;
   }
   if (telea) {
@@ -998,9 +986,9 @@ static int inpaint_dev(artp_ctx* c, const float* d_in, int rows, int cols, int m
     // wraps the column-major layer as a cv::Mat(cols, rows) (utils.cpp:16-19: the buffer read row-major), the cost node
     // works on a[r][c] = layer(rows - 1 - r, cols - 1 - c) (cost_query_server.py:74)
     std::vector<unsigned char> hq(n), hk(n), img(n), msk(n);
-    if (hipMemcpyAsync(hq.data(), q, n, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipMemcpyAsync(hk.data(), known, n, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-      return ARTP_ERR_HIP;
+    HIP_TRY(c, hipMemcpyAsync(hq.data(), q, n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(hk.data(), known, n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
     auto src_of = [&](size_t i) {   // image index -> layer index
       if (mode == 0) return i;
       const size_t r = i / (size_t)cols, cc = i % (size_t)cols;
@@ -1013,11 +1001,11 @@ static int inpaint_dev(artp_ctx* c, const float* d_in, int rows, int cols, int m
     if (mode == 0) artp_telea::inpaint_u8(cols, rows, img.data(), msk.data(), 3);
     else artp_telea::inpaint_u8(rows, cols, img.data(), msk.data(), 3);
     for (size_t i = 0; i < n; ++i) hq[src_of(i)] = img[i];
-    if (hipMemcpyAsync(q, hq.data(), n, hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-      return ARTP_ERR_HIP;
+    HIP_TRY(c, hipMemcpyAsync(q, hq.data(), n, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
   }
   for (int group = 0; !telea && group < (rows + cols) / 3 + 2; ++group) {
-    if (hipMemsetAsync(d_left, 0, 4, st) != hipSuccess) return ARTP_ERR_HIP;
+    HIP_TRY(c, hipMemsetAsync(d_left, 0, 4, st));
     for (int p = 0; p < 4; ++p) {  // an even number of passes: the result is back in (q, known)
       hipLaunchKernelGGL(artp::inpaint_fill_pass_kernel, grid, blk, 0, st, (const unsigned char*)q,
                          (const unsigned char*)known, rows, cols, q2, known2, d_left);
@@ -1025,13 +1013,14 @@ static int inpaint_dev(artp_ctx* c, const float* d_in, int rows, int cols, int m
                          (const unsigned char*)known2, rows, cols, q, known, d_left);
     }
     unsigned left = 0;
-    if (hipMemcpyAsync(&left, d_left, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-      return ARTP_ERR_HIP;
+    HIP_TRY(c, hipMemcpyAsync(&left, d_left, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
     if (!left) break;
   }
   hipLaunchKernelGGL(artp::inpaint_dequantise_kernel, grid, blk, 0, st, (const unsigned char*)q, rows, cols, mode, lo, hi,
                      d_out);
-  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return ARTP_ERR_HIP;
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipStreamSynchronize(st));
   return ARTP_OK;
 }
 
@@ -1043,10 +1032,10 @@ int artp_inpaint_layer(artp_ctx* c, const float* layer, int rows, int cols, int 
   float* d = nullptr;
   DeviceScratch S;
   HIP_TRY(c, S.alloc(&d, n));
-  int rc = hipMemcpy(d, layer, n * 4, hipMemcpyHostToDevice) == hipSuccess ? ARTP_OK : ARTP_ERR_HIP;
-  if (rc == ARTP_OK) rc = inpaint_dev(c, d, rows, cols, mode, d, n_holes);
-  if (rc == ARTP_OK && hipMemcpy(out, d, n * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = ARTP_ERR_HIP;
-  return rc;
+  HIP_TRY(c, hipMemcpy(d, layer, n * 4, hipMemcpyHostToDevice));
+  ARTP_TRY(inpaint_dev(c, d, rows, cols, mode, d, n_holes));
+  HIP_TRY(c, hipMemcpy(out, d, n * 4, hipMemcpyDeviceToHost));
+  return ARTP_OK;
 }
 
 int artp_telea_inpaint_u8(const uint8_t* img, const uint8_t* mask, int h, int w, int range, uint8_t* out) {
@@ -1069,9 +1058,8 @@ int cost_update_map_layer_filled(artp_ctx* c, const float* layer, int rows, int 
                                  double len_y, double pos_x, double pos_y) {
   std::vector<float> filled((size_t)rows * cols);
   uint64_t holes = 0;
-  const int rc = artp_inpaint_layer(c, layer, rows, cols, ARTP_INPAINT_COST_NODE | (c->cost_fill_telea ? ARTP_INPAINT_TELEA : 0),
-                                    filled.data(), &holes);
-  if (rc != ARTP_OK) return rc;
+  ARTP_TRY(artp_inpaint_layer(c, layer, rows, cols, ARTP_INPAINT_COST_NODE | (c->cost_fill_telea ? ARTP_INPAINT_TELEA : 0),
+                              filled.data(), &holes));
   c->cost_fill_holes = false;  // the filled layer has no holes; avoid recursion
   const int rc2 = artp_cost_update_map_layer(c, filled.data(), rows, cols, res, len_x, len_y, pos_x, pos_y);
   c->cost_fill_holes = true;

@@ -447,13 +447,13 @@ struct artp_roadmap {
   artp_preprocess_params density_params_copy{};  // params.density_params points here (see roadmap_fix_params)
   uint64_t n_reweights = 0;        // density re-weightings during the build
   uint64_t budget_flags = 0;       // bit 0: max_sample_time ended the sampling, bit 1: max_n_edges cut the graph
-  // device copies for the label-correcting search of large roadmaps (roadmap_sssp_dev)
-  uint32_t* d_euv = nullptr;       // eu | ev
-  double* d_w = nullptr;           // edge weight, +inf = not usable
-  unsigned long long* d_dist = nullptr;
-  uint32_t* d_pred = nullptr;
-  size_t d_graph_ne = 0, d_graph_nv = 0;
-  bool d_graph_dirty = true;
+  // device copies for the label-correcting search of large roadmaps (roadmap_sssp_dev), grown to the current graph
+  DeviceBuffer<uint32_t> d_euv;              // eu | ev
+  DeviceBuffer<double> d_w;                  // edge weight, +inf = not usable
+  DeviceBuffer<unsigned long long> d_dist;   // nv distances, then the word that counts a sweep group's changes
+  DeviceBuffer<uint32_t> d_pred;             // pred | stamp
+  bool d_graph_stale = true;                 // d_euv is not the current edge list
+  bool d_w_stale = true;                     // d_w is not the current weights
   std::vector<double> verts;       // nv x 7; vertex 0 = start, 1 = goal
   std::vector<uint32_t> knn;       // nv x k (0xffffffff = none)
   std::vector<double> knn_dist;    // nv x k
@@ -482,11 +482,48 @@ struct artp_roadmap {
   bool emotion_dirty = true;
   // resident in HBM for artp_roadmap_revalidate: the endpoint states of all edges (s1 rows, then s2 rows), and
   // what they are gathered from after a re-query replaced the first edges (vertex states, edge end points)
-  double* d_edge_states = nullptr;
-  size_t d_edge_cap = 0;
+  DeviceBuffer<double> d_edge_states;
   bool d_edge_states_stale = true;
   size_t nv() const { return verts.size() / 7; }
 };
+
+// ---- derived state ----------------------------------------------------------------------------------------------------
+// The CSR, the verdict cache, the device graph and the resident edge states are all computed from the edge arrays and
+// rebuilt by their consumers when marked.  Whoever changes the edge arrays says WHAT changed through one of these three;
+// nobody else writes the marks.  (A roadmap swapped in whole -- roadmap_replace -- brings its own marks along.)
+
+// The edge LIST changed (set_query's new prefix, a finished incremental graph, a restored query prefix): edge ids mean
+// other edges now, so everything indexed by them goes -- CSR, verdict cache, device graph (eu | ev are uploaded again,
+// and the weights with them), resident endpoint states.
+static inline void roadmap_edges_changed(artp_roadmap* rm) {
+  rm->csr_dirty = rm->emotion_dirty = rm->d_graph_stale = rm->d_w_stale = rm->d_edge_states_stale = true;
+}
+
+// Edge verdicts or costs changed under an unchanged list (revalidate after a map change): the weights of the CSR and of
+// the device graph, and the motion verdicts of the old map; end points and their resident states stand.
+static inline void roadmap_weights_changed(artp_roadmap* rm) {
+  rm->csr_dirty = rm->emotion_dirty = rm->d_w_stale = true;
+}
+
+// The lazy path check removed edge e: marked, and not usable in the device weights.  The CSR stays usable -- the edge's
+// two slots get weight +inf (what the tree search reads; roadmap_astar skips removed edges itself) -- because a lazy
+// solve removes hundreds of edges one at a time and must not rebuild 265 000 edges' adjacency for each.
+static inline void roadmap_remove_edge(artp_roadmap* rm, size_t e) {
+  rm->eremoved[e] = 1;
+  rm->d_w_stale = true;
+  if (rm->csr_dirty) return;
+  for (const uint32_t v : {rm->eu[e], rm->ev[e]})
+    for (uint32_t a = rm->row[v]; a < rm->row[v + 1]; ++a)
+      if (rm->adj_edge[a] == e) rm->adjw[a] = INFINITY;
+}
+
+// The weight every search gives edge e: its cost while the edge is valid, not removed, and the cost finite and not
+// negative, else +inf.  (A negative weight -- a learned cost below 0 -- would break the atomicMin on the bit pattern of the
+// device distances, which orders non-negative doubles only; the reference's costs are >= 0.)
+static inline double roadmap_edge_weight(const artp_roadmap* rm, size_t e) {
+  const double w = rm->ecost[e];
+  return (rm->evalid[e] && !rm->eremoved[e] && std::isfinite(w) && w >= 0.0) ? w : INFINITY;
+}
 
 namespace {
 
@@ -518,7 +555,7 @@ void roadmap_build_csr(artp_roadmap* rm) {
   for (size_t e = 0; e < ne; ++e)
     if (rm->evalid[e] && !rm->eremoved[e]) {
       const uint32_t u = rm->eu[e], v = rm->ev[e];
-      const double w = (std::isfinite(rm->ecost[e]) && rm->ecost[e] >= 0.0) ? rm->ecost[e] : INFINITY;
+      const double w = roadmap_edge_weight(rm, e);
       rm->adj[fill[u]] = v;
       rm->adjw[fill[u]] = w;
       rm->adj_edge[fill[u]++] = (uint32_t)e;
@@ -577,101 +614,105 @@ bool roadmap_astar(artp_roadmap* rm, std::vector<uint32_t>* path, double* cost) 
   return true;
 }
 
+// Label-correcting sweeps driven to their fixed point: launch(s) enqueues sweep number s (1, 2, ...) on the lane's
+// stream; after every group of sweeps the host reads *d_changed (zeroed before the group) and stops at zero, i.e. after
+// one whole group that changed nothing.  The first group has `group` sweeps, every later one twice its predecessor's up
+// to group_max: a sweep behind the wavefront costs two reads per edge, a host read a synchronisation.
+template <class Launch>
+int roadmap_sweep_to_fixed_point(artp_ctx* c, unsigned* d_changed, unsigned group, unsigned group_max, Launch launch) {
+  hipStream_t st = c->lane->stream;
+  for (unsigned sweep = 1; sweep < 1000000u; sweep += group, group = std::min(2 * group, group_max)) {
+    HIP_TRY(c, hipMemsetAsync(d_changed, 0, 4, st));
+    for (unsigned r = 0; r < group; ++r) launch(sweep + r);
+    unsigned changed = 0;
+    HIP_TRY(c, hipMemcpyAsync(&changed, d_changed, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    if (!changed) break;
+  }
+  return ARTP_OK;
+}
+
+enum class DevSearch {
+  Found,        // *path and *cost hold the answer
+  Unreachable,  // no path from vertex 0 to vertex 1
+  UseHost       // the predecessor chain closed a cycle through zero-weight edges: the host A* cannot cycle
+};
+
 // The same search on the device for large roadmaps (see sssp_relax_kernel).  Same result as roadmap_astar up to the
-// choice among equal-cost paths.
-bool roadmap_sssp_dev(artp_roadmap* rm, std::vector<uint32_t>* path, double* cost, bool* ok) {
+// choice among equal-cost paths.  A failing HIP call is the caller's error (ARTP_ERR_HIP), not a reason to search on
+// the host.
+int roadmap_sssp_dev(artp_roadmap* rm, std::vector<uint32_t>* path, double* cost, DevSearch* outcome) {
   artp_ctx* c = rm->ctx;
   const size_t nv = rm->nv(), ne = rm->eu.size();
-  *ok = false;
-  if (hipSetDevice(c->device) != hipSuccess) return false;
+  HIP_TRY(c, hipSetDevice(c->device));
   hipStream_t st = c->lane->stream;
-  if (rm->d_graph_ne != ne || rm->d_graph_nv != nv || !rm->d_euv) {
-    for (void* p : {(void*)rm->d_euv, (void*)rm->d_w, (void*)rm->d_dist, (void*)rm->d_pred})
-      if (p) (void)hipFree(p);
-    rm->d_euv = nullptr; rm->d_w = nullptr; rm->d_dist = nullptr; rm->d_pred = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&rm->d_euv), 2 * ne * sizeof(uint32_t)) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&rm->d_w), ne * sizeof(double)) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&rm->d_dist), nv * sizeof(unsigned long long) + 16) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&rm->d_pred), 2 * nv * sizeof(uint32_t)) != hipSuccess)  // pred | stamp
-      return false;
-    rm->d_graph_ne = ne;
-    rm->d_graph_nv = nv;
-    rm->d_graph_dirty = true;
-    if (hipMemcpyAsync(rm->d_euv, rm->eu.data(), ne * 4, hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipMemcpyAsync(rm->d_euv + ne, rm->ev.data(), ne * 4, hipMemcpyHostToDevice, st) != hipSuccess)
-      return false;
+  if (rm->d_graph_stale) {
+    HIP_TRY(c, rm->d_euv.reserve(2 * ne * sizeof(uint32_t)));
+    HIP_TRY(c, rm->d_w.reserve(ne * sizeof(double)));
+    HIP_TRY(c, rm->d_dist.reserve(nv * sizeof(unsigned long long) + 16));
+    HIP_TRY(c, rm->d_pred.reserve(2 * nv * sizeof(uint32_t)));
+    HIP_TRY(c, hipMemcpyAsync(rm->d_euv.get(), rm->eu.data(), ne * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(rm->d_euv.get() + ne, rm->ev.data(), ne * 4, hipMemcpyHostToDevice, st));
+    rm->d_graph_stale = false;
+    rm->d_w_stale = true;
   }
-  if (rm->d_graph_dirty) {
+  const uint32_t *d_eu = rm->d_euv.get(), *d_ev = rm->d_euv.get() + ne;
+  const double* d_w = rm->d_w.get();
+  unsigned long long* d_dist = rm->d_dist.get();
+  uint32_t* d_pred = rm->d_pred.get();
+  if (rm->d_w_stale) {
     std::vector<double> w(ne);
-    for (size_t e = 0; e < ne; ++e)
-      // negative weights (a learned cost below 0) would break the atomicMin on the bit pattern of the distances, which
-      // orders non-negative doubles only: such an edge is not traversable here (the reference's costs are >= 0)
-      w[e] = (rm->evalid[e] && !rm->eremoved[e] && std::isfinite(rm->ecost[e]) && rm->ecost[e] >= 0.0) ? rm->ecost[e]
-                                                                                                           : INFINITY;
-    if (hipMemcpyAsync(rm->d_w, w.data(), ne * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess)
-      return false;
-    rm->d_graph_dirty = false;
+    for (size_t e = 0; e < ne; ++e) w[e] = roadmap_edge_weight(rm, e);
+    HIP_TRY(c, hipMemcpyAsync(rm->d_w.get(), w.data(), ne * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    rm->d_w_stale = false;
   }
-  unsigned* d_changed = reinterpret_cast<unsigned*>(rm->d_dist + nv);
+  unsigned* d_changed = reinterpret_cast<unsigned*>(d_dist + nv);
   // dist = +inf (0x7ff0...), dist[0] = 0
   std::vector<unsigned long long> init(nv, 0x7ff0000000000000ull);
   init[0] = 0ull;
-  if (hipMemcpyAsync(rm->d_dist, init.data(), nv * 8, hipMemcpyHostToDevice, st) != hipSuccess) return false;
+  HIP_TRY(c, hipMemcpyAsync(d_dist, init.data(), nv * 8, hipMemcpyHostToDevice, st));
   // stamps: the source "moved" in sweep 0, nobody else yet (0xfefefefe + 1 never equals a sweep number)
-  unsigned* d_stamp = rm->d_pred + nv;
+  unsigned* d_stamp = d_pred + nv;
   const unsigned zero = 0;
-  if (hipMemsetAsync(d_stamp, 0xfe, nv * 4, st) != hipSuccess ||
-      hipMemcpyAsync(d_stamp, &zero, 4, hipMemcpyHostToDevice, st) != hipSuccess)
-    return false;
+  HIP_TRY(c, hipMemsetAsync(d_stamp, 0xfe, nv * 4, st));
+  HIP_TRY(c, hipMemcpyAsync(d_stamp, &zero, 4, hipMemcpyHostToDevice, st));
   size_t blocks = (ne + 255) / 256;
   if (blocks > (size_t)c->n_cus * 8) blocks = (size_t)c->n_cus * 8;
-  for (unsigned sweep = 1; sweep < 1000000u; sweep += 16) {
-    if (hipMemsetAsync(d_changed, 0, 4, st) != hipSuccess) return false;
-    for (unsigned r = 0; r < 16; ++r)
-      hipLaunchKernelGGL(artp::sssp_relax_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const uint32_t*)rm->d_euv,
-                         (const uint32_t*)(rm->d_euv + ne), (const double*)rm->d_w, ne, rm->d_dist, d_stamp, sweep + r,
-                         d_changed);
-    unsigned changed = 0;
-    if (hipMemcpyAsync(&changed, d_changed, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess)
-      return false;
-    if (!changed) break;
-  }
+  ARTP_TRY(roadmap_sweep_to_fixed_point(c, d_changed, 16, 16, [&](unsigned sweep) {
+    hipLaunchKernelGGL(artp::sssp_relax_kernel, dim3((unsigned)blocks), dim3(256), 0, st, d_eu, d_ev, d_w, ne, d_dist,
+                       d_stamp, sweep, d_changed);
+  }));
   // one more sweep group proved the fixed point (changed == 0 over 16 sweeps); predecessors
-  if (hipMemsetAsync(rm->d_pred, 0xff, nv * 4, st) != hipSuccess) return false;
-  hipLaunchKernelGGL(artp::sssp_pred_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const uint32_t*)rm->d_euv,
-                     (const uint32_t*)(rm->d_euv + ne), (const double*)rm->d_w, ne,
-                     (const unsigned long long*)rm->d_dist, rm->d_pred);
+  HIP_TRY(c, hipMemsetAsync(d_pred, 0xff, nv * 4, st));
+  hipLaunchKernelGGL(artp::sssp_pred_kernel, dim3((unsigned)blocks), dim3(256), 0, st, d_eu, d_ev, d_w, ne,
+                     (const unsigned long long*)d_dist, d_pred);
   std::vector<uint32_t> pred(nv);
-  unsigned long long dgoal = 0;
-  if (hipMemcpyAsync(pred.data(), rm->d_pred, nv * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipMemcpyAsync(&dgoal, rm->d_dist + 1, 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipStreamSynchronize(st) != hipSuccess)
-    return false;
-  *ok = true;
-  double dg;
-  std::memcpy(&dg, &dgoal, 8);
-  if (!(dg < INFINITY)) return false;
+  double dg = INFINITY;
+  HIP_TRY(c, hipMemcpyAsync(pred.data(), d_pred, nv * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(&dg, d_dist + 1, 8, hipMemcpyDeviceToHost, st));  // the distance's own bits
+  HIP_TRY(c, hipStreamSynchronize(st));
+  *outcome = DevSearch::Unreachable;
+  if (!(dg < INFINITY)) return ARTP_OK;
   path->clear();
   uint32_t v = 1;
   for (size_t guard = 0; guard <= nv; ++guard) {
     path->push_back(v);
     if (v == 0) break;
     v = pred[v];
-    if (v == 0xffffffffu) return false;  // cannot happen at the fixed point
+    if (v == 0xffffffffu) return ARTP_OK;  // cannot happen at the fixed point
   }
   if (path->back() != 0) {
     // zero-weight edges (coincident vertices, a learned cost of 0) make dist[u] + 0 == dist[v] true in both
-    // directions, so the predecessor chain can close a cycle that never reaches the start: no path from here --
-    // the caller falls back to the host A*, which cannot cycle
+    // directions, so the predecessor chain can close a cycle that never reaches the start: no path from here
     path->clear();
-    *ok = false;
-    return false;
+    *outcome = DevSearch::UseHost;
+    return ARTP_OK;
   }
   std::reverse(path->begin(), path->end());
   *cost = dg;
-  return true;
+  *outcome = DevSearch::Found;
+  return ARTP_OK;
 }
 
 // Verdict (0.5 m interpolation rule), interior-state count and chain cost of ne edges whose endpoint states
@@ -808,12 +849,31 @@ void artp_roadmap_params_defaults(artp_roadmap_params* p) {
   p->max_query_edge_length = 0.5;  // params.h:54
 }
 
-void artp_roadmap_destroy(artp_roadmap* rm) {
-  if (!rm) return;
-  if (rm->d_edge_states) (void)hipFree(rm->d_edge_states);
-  for (void* p : {(void*)rm->d_euv, (void*)rm->d_w, (void*)rm->d_dist, (void*)rm->d_pred})
-    if (p) (void)hipFree(p);
-  delete rm;
+void artp_roadmap_destroy(artp_roadmap* rm) { delete rm; }
+
+// rm becomes what `fresh` is (a regrown graph) and the old roadmap goes, its device memory with it; each keeps its own
+// derived state, so nothing is invalidated here
+static void roadmap_replace(artp_roadmap* rm, artp_roadmap* fresh) {
+  std::swap(*rm, *fresh);
+  roadmap_fix_params(rm);
+  roadmap_fix_params(fresh);
+  delete fresh;
+}
+
+// start and goal must be valid states (baseSolve: INVALID_START / INVALID_GOAL, prm_motion_cost.cpp:452-476)
+static int roadmap_require_valid_query(artp_ctx* c, bool start_ok, bool goal_ok) {
+  if (start_ok && goal_ok) return ARTP_OK;
+  c->last_error = !start_ok ? "start state is not valid" : "goal state is not valid";
+  return ARTP_ERR_INVALID_ARG;
+}
+
+// ... checked for a new pair: sg = start | goal
+static int roadmap_validate_query(artp_ctx* c, const double* start7, const double* goal7, double sg[14]) {
+  std::memcpy(sg, start7, 7 * sizeof(double));
+  std::memcpy(sg + 7, goal7, 7 * sizeof(double));
+  uint8_t ok[2] = {0, 0};
+  ARTP_TRY(artp_validate_states(c, sg, 2, ok, nullptr));
+  return roadmap_require_valid_query(c, ok[0], ok[1]);
 }
 
 // Connection + evaluation of a vertex set that is already in HBM (d_verts: nv x 7; vertex 0 = start, 1 = goal):
@@ -848,15 +908,11 @@ static int roadmap_connect(artp_ctx* c, const artp_roadmap_params* prm, const do
       if (ki > (int)i) ki = (int)i;
       k_of[i] = ki > k ? k : ki;
     }
-    if (S.alloc(&d_k_of, nv) != hipSuccess ||
-        hipMemcpy(d_k_of, k_of.data(), nv * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
-      c->last_error = "k table upload failed";
-      return ARTP_ERR_HIP;
-    }
+    HIP_TRY(c, S.alloc(&d_k_of, nv));
+    HIP_TRY(c, hipMemcpy(d_k_of, k_of.data(), nv * sizeof(int), hipMemcpyHostToDevice));
   }
   HIP_TRY(c, S.alloc(&d_knn, nv * k));
   HIP_TRY(c, S.alloc(&d_knn_dist, nv * k));
-  bool okk;
   {
     DeviceScratch G;  // the grid's buffers: gone before the key buffers are allocated
     // grid over the map: about three vertices per cell
@@ -878,39 +934,30 @@ static int roadmap_connect(artp_ctx* c, const artp_roadmap_params* prm, const do
     double* d_vs = nullptr;
     void* d_cub1 = nullptr;
     size_t need = 0;
-    okk = G.alloc(&d_cell, nv) == hipSuccess && G.alloc(&d_id, nv) == hipSuccess &&
-          G.alloc(&d_cell_s, nv) == hipSuccess && G.alloc(&d_id_s, nv) == hipSuccess &&
-          G.alloc(&d_start, (size_t)ncell + 1) == hipSuccess && G.alloc(&d_vs, nv * 7) == hipSuccess &&
-          hipcub::DeviceRadixSort::SortPairs(nullptr, need, d_cell, d_cell_s, d_id, d_id_s, (int)nv, 0, 32, st) ==
-              hipSuccess &&
-          G.alloc(&d_cub1, need + 256) == hipSuccess;
-    if (okk) {
-      hipLaunchKernelGGL(artp::knn_cell_ids_kernel, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, st,
-                         (const double*)d_verts, (int)nv, g, d_cell, d_id);
-      size_t cap1 = need + 256;
-      okk = hipcub::DeviceRadixSort::SortPairs(d_cub1, cap1, d_cell, d_cell_s, d_id, d_id_s, (int)nv, 0, 32, st) ==
-            hipSuccess;
-    }
-    if (okk) {
-      hipLaunchKernelGGL(artp::knn_permute_kernel, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, st,
-                         (const double*)d_verts, (const uint32_t*)d_cell_s, (const uint32_t*)d_id_s, (int)nv, ncell,
-                         d_vs, d_start);
-      const size_t lds = (size_t)k * 64 * 12;
-      okk = hipFuncSetAttribute(reinterpret_cast<const void*>(artp::knn_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
-      if (okk) {
-        hipLaunchKernelGGL(artp::knn_kernel, dim3((unsigned)((nv + 63) / 64)), dim3(64), lds, st, (const double*)d_vs,
-                           (const uint32_t*)d_id_s, (const uint32_t*)d_start, g, (int)nv, k, (const int*)d_k_of,
-                           pred_only ? 1 : 0, d_knn, d_knn_dist);
-        okk = hipGetLastError() == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
-      }
-    }
+    HIP_TRY(c, G.alloc(&d_cell, nv));
+    HIP_TRY(c, G.alloc(&d_id, nv));
+    HIP_TRY(c, G.alloc(&d_cell_s, nv));
+    HIP_TRY(c, G.alloc(&d_id_s, nv));
+    HIP_TRY(c, G.alloc(&d_start, (size_t)ncell + 1));
+    HIP_TRY(c, G.alloc(&d_vs, nv * 7));
+    HIP_TRY(c, hipcub::DeviceRadixSort::SortPairs(nullptr, need, d_cell, d_cell_s, d_id, d_id_s, (int)nv, 0, 32, st));
+    HIP_TRY(c, G.alloc(&d_cub1, need + 256));
+    hipLaunchKernelGGL(artp::knn_cell_ids_kernel, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, st,
+                       (const double*)d_verts, (int)nv, g, d_cell, d_id);
+    size_t cap1 = need + 256;
+    HIP_TRY(c, hipcub::DeviceRadixSort::SortPairs(d_cub1, cap1, d_cell, d_cell_s, d_id, d_id_s, (int)nv, 0, 32, st));
+    hipLaunchKernelGGL(artp::knn_permute_kernel, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, st,
+                       (const double*)d_verts, (const uint32_t*)d_cell_s, (const uint32_t*)d_id_s, (int)nv, ncell,
+                       d_vs, d_start);
+    const size_t lds = (size_t)k * 64 * 12;
+    ARTP_OPT_IN(c, artp::knn_kernel, lds);  // only ever raised: a smaller k does not lower it under another roadmap
+    hipLaunchKernelGGL(artp::knn_kernel, dim3((unsigned)((nv + 63) / 64)), dim3(64), lds, st, (const double*)d_vs,
+                       (const uint32_t*)d_id_s, (const uint32_t*)d_start, g, (int)nv, k, (const int*)d_k_of,
+                       pred_only ? 1 : 0, d_knn, d_knn_dist);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(st));
   }
   S.release(d_k_of);
-  if (!okk) {
-    c->last_error = "k-NN stage failed";
-    return ARTP_ERR_HIP;
-  }
 
   // 3. candidate edges: symmetrised, unique
   const size_t nk = nv * (size_t)k;
@@ -945,7 +992,7 @@ static int roadmap_connect(artp_ctx* c, const artp_roadmap_params* prm, const do
     }
   }
 
-  std::unique_ptr<artp_roadmap, void (*)(artp_roadmap*)> rm(new artp_roadmap(), artp_roadmap_destroy);
+  std::unique_ptr<artp_roadmap> rm(new artp_roadmap());
   rm->ctx = c;
   rm->params = *prm;
   roadmap_fix_params(rm.get());
@@ -953,10 +1000,9 @@ static int roadmap_connect(artp_ctx* c, const artp_roadmap_params* prm, const do
   rm->verts.resize(nv * 7);
   rm->knn.resize(nk);
   rm->knn_dist.resize(nk);
-  if (hipMemcpy(rm->verts.data(), d_verts, nv * 7 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
-      hipMemcpy(rm->knn.data(), d_knn, nk * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess ||
-      hipMemcpy(rm->knn_dist.data(), d_knn_dist, nk * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
-    return ARTP_ERR_HIP;
+  HIP_TRY(c, hipMemcpy(rm->verts.data(), d_verts, nv * 7 * sizeof(double), hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(rm->knn.data(), d_knn, nk * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(rm->knn_dist.data(), d_knn_dist, nk * sizeof(double), hipMemcpyDeviceToHost));
 
   // 4. edge verdicts (0.5 m interpolation rule) and chain costs
   rm->eu.resize(ne);
@@ -966,23 +1012,21 @@ static int roadmap_connect(artp_ctx* c, const artp_roadmap_params* prm, const do
   rm->ecost.assign(ne, 0.0);
   rm->eremoved.assign(ne, 0);
   if (ne) {
-    if (S.alloc(&d_s1, 2 * ne * 7) != hipSuccess) return ARTP_ERR_HIP;
+    HIP_TRY(c, S.alloc(&d_s1, 2 * ne * 7));
     d_s2 = d_s1 + ne * 7;
     hipLaunchKernelGGL(artp::gather_edge_states_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st,
                        (const double*)d_verts, (const unsigned long long*)d_keys_unique, ne, d_s1, d_s2, pred_only ? 1 : 0);
     if (pred_only) rm->eflip.assign(ne, 1);
     // construction 2: the lazy planner puts DIRECT edges of unknown validity into its graph (no interpolation rule)
-    const int rc = roadmap_eval_edges_dev(c, prm, d_s1, d_s2, ne, rm->evalid.data(), rm->einterp.data(),
-                                          rm->ecost.data(), pred_only);
-    if (rc != ARTP_OK) return rc;
+    ARTP_TRY(roadmap_eval_edges_dev(c, prm, d_s1, d_s2, ne, rm->evalid.data(), rm->einterp.data(), rm->ecost.data(),
+                                    pred_only));
     std::vector<unsigned long long> keys(ne);
-    if (hipMemcpy(keys.data(), d_keys_unique, ne * 8, hipMemcpyDeviceToHost) != hipSuccess) return ARTP_ERR_HIP;
+    HIP_TRY(c, hipMemcpy(keys.data(), d_keys_unique, ne * 8, hipMemcpyDeviceToHost));
     for (size_t e = 0; e < ne; ++e) {
       rm->eu[e] = (uint32_t)(keys[e] >> 32);
       rm->ev[e] = (uint32_t)(keys[e] & 0xffffffffu);
     }
-    rm->d_edge_states = S.take(d_s1);  // stays resident (freed by artp_roadmap_destroy)
-    rm->d_edge_cap = ne;
+    rm->d_edge_states.adopt(S.take(d_s1), 2 * ne * 7 * sizeof(double));  // stays resident, the roadmap's from here on
     rm->d_edge_states_stale = false;
   }
   *out = rm.release();
@@ -1012,19 +1056,9 @@ static int roadmap_build_impl(artp_ctx* c, const artp_roadmap_params* prm_in, co
   HIP_TRY(c, S.alloc(&d_verts, nv * 7));
   HIP_TRY(c, S.alloc(&d_cnt, 1));
 
-  // start and goal must be valid states (baseSolve: INVALID_START / INVALID_GOAL, prm_motion_cost.cpp:452-476)
-  {
-    double sg[14];
-    std::memcpy(sg, start7, 7 * sizeof(double));
-    std::memcpy(sg + 7, goal7, 7 * sizeof(double));
-    uint8_t ok[2] = {0, 0};
-    ARTP_TRY(artp_validate_states(c, sg, 2, ok, nullptr));
-    if (!ok[0] || !ok[1]) {
-      c->last_error = !ok[0] ? "start state is not valid" : "goal state is not valid";
-      return ARTP_ERR_INVALID_ARG;
-    }
-    HIP_TRY(c, hipMemcpyAsync(d_verts, sg, sizeof(sg), hipMemcpyHostToDevice, st));
-  }
+  double sg[14];
+  ARTP_TRY(roadmap_validate_query(c, start7, goal7, sg));
+  HIP_TRY(c, hipMemcpyAsync(d_verts, sg, sizeof(sg), hipMemcpyHostToDevice, st));
 
   // 1. milestones: the kept ones, then accepted states of the sample stream, in index order
   size_t have = n_keep;
@@ -1105,8 +1139,7 @@ static int roadmap_build_impl(artp_ctx* c, const artp_roadmap_params* prm_in, co
   for (int attempt = 0;; ++attempt) {
     artp_roadmap_params p_use = *prm;
     p_use.n_milestones = (uint32_t)(nv_use - 2);
-    const int rc = roadmap_connect(c, &p_use, d_verts, nv_use, &rm);
-    if (rc != ARTP_OK) return rc;
+    ARTP_TRY(roadmap_connect(c, &p_use, d_verts, nv_use, &rm));
     if (!prm->max_n_edges || rm->eu.size() <= prm->max_n_edges || nv_use <= 3 || attempt >= 12) break;
     std::vector<uint32_t> per_v(nv_use, 0);
     for (uint32_t v : rm->ev) ++per_v[v];
@@ -1220,31 +1253,27 @@ struct IncrementalGraph {
   }
   int eval_tasks(size_t n) {  // tasks -> states, valid
     hipStream_t st = c->lane->stream;
-    if (hipSetDevice(c->device) != hipSuccess) return ARTP_ERR_HIP;
+    HIP_TRY(c, hipSetDevice(c->device));
     if (cap < n) {
       for (void* p : {(void*)d_tasks, (void*)d_states, (void*)d_valid}) staging.release(p);
       d_tasks = d_states = nullptr;
       d_valid = nullptr;
-      cap = std::max<size_t>(2 * n, 1024);
-      if (staging.alloc(&d_tasks, cap * 15) != hipSuccess || staging.alloc(&d_states, cap * 7) != hipSuccess ||
-          staging.alloc(&d_valid, cap) != hipSuccess) {
-        cap = 0;
-        c->last_error = "chain staging allocation failed";
-        return ARTP_ERR_HIP;
-      }
+      cap = 0;  // until all three are there
+      const size_t want = std::max<size_t>(2 * n, 1024);
+      HIP_TRY(c, staging.alloc(&d_tasks, want * 15));
+      HIP_TRY(c, staging.alloc(&d_states, want * 7));
+      HIP_TRY(c, staging.alloc(&d_valid, want));
+      cap = want;
     }
     states.resize(n * 7);
     valid.resize(n);
-    if (hipMemcpyAsync(d_tasks, tasks.data(), n * 15 * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess)
-      return ARTP_ERR_HIP;
+    HIP_TRY(c, hipMemcpyAsync(d_tasks, tasks.data(), n * 15 * sizeof(double), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(artp::chain_states_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st,
                        (const double*)d_tasks, (int)n, d_states);
-    const int rc = artp_validate_states_dev(c, d_states, n, d_valid, nullptr);
-    if (rc != ARTP_OK) return rc;
-    if (hipMemcpyAsync(states.data(), d_states, n * 7 * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipMemcpyAsync(valid.data(), d_valid, n, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess)
-      return ARTP_ERR_HIP;
+    ARTP_TRY(artp_validate_states_dev(c, d_states, n, d_valid, nullptr));
+    HIP_TRY(c, hipMemcpyAsync(states.data(), d_states, n * 7 * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(valid.data(), d_valid, n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
     states_checked += n;
     return check_error_flag(c);
   }
@@ -1281,10 +1310,7 @@ struct IncrementalGraph {
       }
     }
     const size_t n_tasks = tasks.size() / 15;
-    if (n_tasks) {
-      const int rc = eval_tasks(n_tasks);
-      if (rc != ARTP_OK) return rc;
-    }
+    if (n_tasks) ARTP_TRY(eval_tasks(n_tasks));
     size_t at = 0;
     for (size_t t = 0; t < nbrs.size(); ++t) {
       const uint32_t nb = nbrs[t].second;
@@ -1359,19 +1385,15 @@ static int incremental_finish(IncrementalGraph& g, artp_roadmap* rm, const std::
   rm->einterp.assign(n, 0);
   rm->ecost.assign(n, 0.0);
   rm->eremoved.assign(n, 0);
-  const int rc = roadmap_eval_edges_host(g.c, &rm->params, rm->verts, rm->eu.data(), rm->ev.data(), n, rm->evalid.data(),
-                                         rm->einterp.data(), rm->ecost.data(), true, rm->eflip.data());
-  if (rc != ARTP_OK) return rc;
+  ARTP_TRY(roadmap_eval_edges_host(g.c, &rm->params, rm->verts, rm->eu.data(), rm->ev.data(), n, rm->evalid.data(),
+                                   rm->einterp.data(), rm->ecost.data(), true, rm->eflip.data()));
   if (vertex_ok)
     for (size_t i = 0; i < n; ++i)
       if (!(*vertex_ok)[rm->eu[i]] || !(*vertex_ok)[rm->ev[i]]) rm->evalid[i] = 0;
   // the adjacency is part of the graph: built with it (OMPL's boost graph has it from the insertion on), not at the first
   // search -- 2 ms of the first solve at 10^4 vertices / 2.6 10^5 edges (round 5)
+  roadmap_edges_changed(rm);
   roadmap_build_csr(rm);
-  rm->emotion_dirty = true;
-  rm->d_graph_dirty = true;
-  rm->d_graph_ne = 0;
-  rm->d_edge_states_stale = true;
   return ARTP_OK;
 }
 
@@ -1464,18 +1486,9 @@ static int incremental_sample_graph(IncrementalGraph& g, size_t max_vertices, ui
 static int roadmap_build_incremental(artp_ctx* c, const artp_roadmap_params* prm, const double* start7,
                                      const double* goal7, artp_roadmap** out) {
   *out = nullptr;
-  {
-    double sg[14];
-    std::memcpy(sg, start7, 7 * sizeof(double));
-    std::memcpy(sg + 7, goal7, 7 * sizeof(double));
-    uint8_t ok[2] = {0, 0};
-    ARTP_TRY(artp_validate_states(c, sg, 2, ok, nullptr));
-    HIP_TRY(c, hipStreamSynchronize(c->lane->stream));
-    if (!ok[0] || !ok[1]) {
-      c->last_error = !ok[0] ? "start state is not valid" : "goal state is not valid";
-      return ARTP_ERR_INVALID_ARG;
-    }
-  }
+  double sg[14];
+  ARTP_TRY(roadmap_validate_query(c, start7, goal7, sg));
+  HIP_TRY(c, hipStreamSynchronize(c->lane->stream));
   IncrementalGraph g;
   g.c = c;
   g.prm = *prm;
@@ -1492,16 +1505,12 @@ static int roadmap_build_incremental(artp_ctx* c, const artp_roadmap_params* prm
   // baseSolve: start and goal become milestones of the finished roadmap (:447-470)
   ARTP_TRY(g.add_valid_milestone(0));
   ARTP_TRY(g.add_valid_milestone(1));
-  auto rm = new artp_roadmap();
-  const int rc = incremental_finish(g, rm, nullptr);
-  if (rc != ARTP_OK) {
-    delete rm;
-    return rc;
-  }
+  std::unique_ptr<artp_roadmap> rm(new artp_roadmap());
+  ARTP_TRY(incremental_finish(g, rm.get(), nullptr));
   rm->samples_drawn = next - prm->first_index;
   rm->n_reweights = n_reweights;
   rm->budget_flags = budget_flags;
-  *out = rm;
+  *out = rm.release();
   return ARTP_OK;
 }
 
@@ -1514,10 +1523,7 @@ static int roadmap_grow_incremental(artp_roadmap* rm, uint64_t n_more, uint64_t 
   std::vector<uint8_t> vok(nv, 0);
   ARTP_TRY(artp_validate_states(c, rm->verts.data(), nv, vok.data(), nullptr));
   HIP_TRY(c, hipStreamSynchronize(c->lane->stream));
-  if (!vok[0] || !vok[1]) {
-    c->last_error = !vok[0] ? "start state is not valid" : "goal state is not valid";
-    return ARTP_ERR_INVALID_ARG;
-  }
+  ARTP_TRY(roadmap_require_valid_query(c, vok[0], vok[1]));
   IncrementalGraph g;
   g.c = c;
   g.prm = rm->params;
@@ -1547,14 +1553,12 @@ static int roadmap_grow_incremental(artp_roadmap* rm, uint64_t n_more, uint64_t 
   uint64_t next = rm->params.first_index + rm->samples_drawn, n_reweights = 0, budget_flags = 0;
   ARTP_TRY(incremental_sample_graph(g, nv + (size_t)n_more, next, &next, &n_reweights, &budget_flags));
   vok.resize(g.nv(), 1);
-  auto fresh = new artp_roadmap();
-  const int rc = incremental_finish(g, fresh, &vok);
-  if (rc != ARTP_OK) {
-    delete fresh;
-    return rc;
-  }
+  std::unique_ptr<artp_roadmap> fresh(new artp_roadmap());
+  ARTP_TRY(incremental_finish(g, fresh.get(), &vok));
   // The reference removes an edge the lazy path check rejected from g_ for good (prm_motion_cost.cpp:652-660): the
   // removals of the graph so far carry over.  Edge identity is stable -- (min, max) vertex ids, both lists sorted.
+  // (Plain data of a graph not yet in use, not a lazy removal: the adjacency built above keeps these edges' slots, and
+  // a path that takes one has its motion checked and the edge removed again.)
   {
     size_t o = 0;
     const size_t no = rm->eu.size();
@@ -1569,10 +1573,7 @@ static int roadmap_grow_incremental(artp_roadmap* rm, uint64_t n_more, uint64_t 
   fresh->n_reweights = rm->n_reweights + n_reweights;
   fresh->budget_flags = budget_flags;
   fresh->params.n_milestones = (uint32_t)std::min<size_t>(nv + (size_t)n_more, 0xffffffffu);
-  std::swap(*rm, *fresh);
-  roadmap_fix_params(rm);
-  roadmap_fix_params(fresh);
-  artp_roadmap_destroy(fresh);
+  roadmap_replace(rm, fresh.release());
   if (out) {
     out[0] = kept;
     out[1] = nv - kept;
@@ -1601,12 +1602,8 @@ int artp_roadmap_grow(artp_roadmap* rm, uint64_t n_more, uint64_t out[2]) {
   artp_ctx* c = rm->ctx;
   const size_t nv = rm->nv();
   std::vector<uint8_t> vok(nv, 0);
-  int rc = artp_validate_states(c, rm->verts.data(), nv, vok.data(), nullptr);
-  if (rc != ARTP_OK) return rc;
-  if (!vok[0] || !vok[1]) {
-    c->last_error = !vok[0] ? "start state is not valid" : "goal state is not valid";
-    return ARTP_ERR_INVALID_ARG;
-  }
+  ARTP_TRY(artp_validate_states(c, rm->verts.data(), nv, vok.data(), nullptr));
+  ARTP_TRY(roadmap_require_valid_query(c, vok[0], vok[1]));
   std::vector<double> keep;
   keep.reserve((nv - 2) * 7);
   for (size_t v = 2; v < nv; ++v)
@@ -1615,15 +1612,11 @@ int artp_roadmap_grow(artp_roadmap* rm, uint64_t n_more, uint64_t out[2]) {
   if (n_keep + n_more < 1) return ARTP_ERR_INVALID_ARG;
   artp_roadmap* fresh = nullptr;
   const uint64_t drawn_before = rm->samples_drawn;
-  rc = roadmap_build_impl(c, &rm->params, rm->verts.data(), rm->verts.data() + 7, keep.data(), n_keep, (size_t)n_more,
-                          rm->params.first_index + drawn_before, &fresh);
-  if (rc != ARTP_OK) return rc;
+  ARTP_TRY(roadmap_build_impl(c, &rm->params, rm->verts.data(), rm->verts.data() + 7, keep.data(), n_keep, (size_t)n_more,
+                              rm->params.first_index + drawn_before, &fresh));
   fresh->samples_drawn += drawn_before;
   fresh->n_reweights += rm->n_reweights;
-  std::swap(*rm, *fresh);
-  roadmap_fix_params(rm);
-  roadmap_fix_params(fresh);
-  artp_roadmap_destroy(fresh);
+  roadmap_replace(rm, fresh);
   if (out) {
     out[0] = n_keep;
     out[1] = (nv - 2) - n_keep;  // milestones the current map invalidated
@@ -1635,13 +1628,28 @@ int artp_roadmap_grow(artp_roadmap* rm, uint64_t n_more, uint64_t out[2]) {
 // (lazy_prm_star_min_update.cpp:18-217).  Batched: after the map changed, re-validate EVERY vertex and
 // re-evaluate EVERY edge against the current layers (10^4 vertices + 10^5 edges are one small batch);
 // edges with an invalid endpoint go, earlier lazy removals are forgotten.
+// Endpoint states of n (src, dst) vertex pairs, gathered on the device: the vertex states and the two index lists go up
+// into the caller's d_v (nv x 7) and d_uv (2 n), gather_edge_states_uv_kernel writes d_s1 / d_s2 (n x 7 each) -- 56 bytes
+// per state never cross PCIe.  Enqueued on the lane's stream; src and dst must live until it has been synchronised.
+static int roadmap_gather_endpoints(artp_roadmap* rm, const uint32_t* src, const uint32_t* dst, size_t n, double* d_v,
+                                    uint32_t* d_uv, double* d_s1, double* d_s2) {
+  artp_ctx* c = rm->ctx;
+  hipStream_t st = c->lane->stream;
+  HIP_TRY(c, hipMemcpyAsync(d_v, rm->verts.data(), rm->nv() * 7 * sizeof(double), hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemcpyAsync(d_uv, src, n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemcpyAsync(d_uv + n, dst, n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(artp::gather_edge_states_uv_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
+                     (const double*)d_v, (const uint32_t*)d_uv, (const uint32_t*)(d_uv + n), n, d_s1, d_s2);
+  HIP_TRY(c, hipGetLastError());
+  return ARTP_OK;
+}
+
 int artp_roadmap_revalidate(artp_roadmap* rm, uint64_t out[4]) {
   if (!rm) return ARTP_ERR_INVALID_ARG;
   artp_ctx* c = rm->ctx;
   const size_t nv = rm->nv(), ne = rm->eu.size();
   std::vector<uint8_t> vok(nv, 0);
-  int rc = artp_validate_states(c, rm->verts.data(), nv, vok.data(), nullptr);
-  if (rc != ARTP_OK) return rc;
+  ARTP_TRY(artp_validate_states(c, rm->verts.data(), nv, vok.data(), nullptr));
   uint64_t before = 0, after = 0, vbad = 0;
   for (size_t e = 0; e < ne; ++e) before += rm->evalid[e] ? 1 : 0;
   if (ne) {
@@ -1651,43 +1659,26 @@ int artp_roadmap_revalidate(artp_roadmap* rm, uint64_t out[4]) {
       double* d_v = nullptr;
       uint32_t* d_uv = nullptr;
       DeviceScratch S;
-      bool okk = hipSetDevice(c->device) == hipSuccess;
-      if (okk && rm->d_edge_cap < ne) {
-        if (rm->d_edge_states) (void)hipFree(rm->d_edge_states);
-        rm->d_edge_states = nullptr;
-        okk = hipMalloc(reinterpret_cast<void**>(&rm->d_edge_states), 2 * ne * 7 * sizeof(double)) == hipSuccess;
-        rm->d_edge_cap = okk ? ne : 0;
-      }
-      okk = okk && S.alloc(&d_v, nv * 7) == hipSuccess && S.alloc(&d_uv, 2 * ne) == hipSuccess &&
-            hipMemcpyAsync(d_v, rm->verts.data(), nv * 7 * sizeof(double), hipMemcpyHostToDevice, c->lane->stream) == hipSuccess &&
-            hipMemcpyAsync(d_uv, rm->eu.data(), ne * sizeof(uint32_t), hipMemcpyHostToDevice, c->lane->stream) == hipSuccess &&
-            hipMemcpyAsync(d_uv + ne, rm->ev.data(), ne * sizeof(uint32_t), hipMemcpyHostToDevice, c->lane->stream) == hipSuccess;
+      HIP_TRY(c, hipSetDevice(c->device));
+      HIP_TRY(c, rm->d_edge_states.reserve(2 * ne * 7 * sizeof(double)));
+      HIP_TRY(c, S.alloc(&d_v, nv * 7));
+      HIP_TRY(c, S.alloc(&d_uv, 2 * ne));
       std::vector<uint32_t> src, dst;  // end points in cost direction (eflip)
-      if (okk && !rm->eflip.empty()) {
+      if (!rm->eflip.empty()) {
         src = rm->eu;
         dst = rm->ev;
         for (size_t e = 0; e < ne; ++e)
           if (rm->eflip[e]) std::swap(src[e], dst[e]);
-        okk = hipMemcpyAsync(d_uv, src.data(), ne * sizeof(uint32_t), hipMemcpyHostToDevice, c->lane->stream) == hipSuccess &&
-              hipMemcpyAsync(d_uv + ne, dst.data(), ne * sizeof(uint32_t), hipMemcpyHostToDevice, c->lane->stream) == hipSuccess;
       }
-      if (okk) {
-        hipLaunchKernelGGL(artp::gather_edge_states_uv_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, c->lane->stream,
-                           (const double*)d_v, (const uint32_t*)d_uv, (const uint32_t*)(d_uv + ne), ne, rm->d_edge_states,
-                           rm->d_edge_states + ne * 7);
-        okk = hipGetLastError() == hipSuccess && hipStreamSynchronize(c->lane->stream) == hipSuccess;
-      }
-      if (!okk) {
-        c->last_error = "staging the edge states failed";
-        return ARTP_ERR_HIP;
-      }
+      ARTP_TRY(roadmap_gather_endpoints(rm, src.empty() ? rm->eu.data() : src.data(), src.empty() ? rm->ev.data() : dst.data(),
+                                        ne, d_v, d_uv, rm->d_edge_states.get(), rm->d_edge_states.get() + ne * 7));
+      HIP_TRY(c, hipStreamSynchronize(c->lane->stream));
       rm->d_edge_states_stale = false;
     }
     // construction 2 holds direct edges of unknown validity (the lazy path check's business); the sub-edges of
     // construction 1 are shorter than 0.5 m, so the rule passes them as they are and only applies to query edges
-    rc = roadmap_eval_edges_dev(c, &rm->params, rm->d_edge_states, rm->d_edge_states + ne * 7, ne, rm->evalid.data(),
-                                rm->einterp.data(), rm->ecost.data(), rm->params.construction == 2);
-    if (rc != ARTP_OK) return rc;
+    ARTP_TRY(roadmap_eval_edges_dev(c, &rm->params, rm->d_edge_states.get(), rm->d_edge_states.get() + ne * 7, ne,
+                                    rm->evalid.data(), rm->einterp.data(), rm->ecost.data(), rm->params.construction == 2));
   }
   for (size_t v = 0; v < nv; ++v) vbad += vok[v] ? 0 : 1;
   for (size_t e = 0; e < ne; ++e) {
@@ -1697,9 +1688,7 @@ int artp_roadmap_revalidate(artp_roadmap* rm, uint64_t out[4]) {
   std::fill(rm->eremoved.begin(), rm->eremoved.end(), 0);
   rm->vinvalid.assign(nv, 0);
   for (size_t v = 0; v < nv; ++v) rm->vinvalid[v] = vok[v] ? 0 : 1;
-  rm->csr_dirty = true;
-  rm->emotion_dirty = true;
-  rm->d_graph_dirty = true;
+  roadmap_weights_changed(rm);
   if (out) {
     out[0] = vbad;
     out[1] = before;
@@ -1714,21 +1703,10 @@ int artp_roadmap_revalidate(artp_roadmap* rm, uint64_t out[4]) {
 int artp_roadmap_set_query(artp_roadmap* rm, const double* start7, const double* goal7) {
   if (!rm || !start7 || !goal7) return ARTP_ERR_INVALID_ARG;
   artp_ctx* c = rm->ctx;
-  double old_sg[14];
-  {
-    double sg[14];
-    std::memcpy(sg, start7, 7 * sizeof(double));
-    std::memcpy(sg + 7, goal7, 7 * sizeof(double));
-    uint8_t ok[2] = {0, 0};
-    const int rc = artp_validate_states(c, sg, 2, ok, nullptr);
-    if (rc != ARTP_OK) return rc;
-    if (!ok[0] || !ok[1]) {
-      c->last_error = !ok[0] ? "start state is not valid" : "goal state is not valid";
-      return ARTP_ERR_INVALID_ARG;
-    }
-    std::memcpy(old_sg, &rm->verts[0], sizeof(old_sg));
-    std::memcpy(&rm->verts[0], sg, sizeof(sg));
-  }
+  double sg[14], old_sg[14];
+  ARTP_TRY(roadmap_validate_query(c, start7, goal7, sg));
+  std::memcpy(old_sg, &rm->verts[0], sizeof(old_sg));
+  std::memcpy(&rm->verts[0], sg, sizeof(sg));
   const size_t nv = rm->nv();
   const int k = rm->k;
   // everything below either commits completely or leaves the roadmap as it was (a failing edge evaluation must
@@ -1783,7 +1761,7 @@ int artp_roadmap_set_query(artp_roadmap* rm, const double* start7, const double*
   }
   const int rc = roadmap_eval_edges_host(c, &rm->params, rm->verts, pu.data(), pv.data(), np, pvalid.data(),
                                          pinterp.data(), pcost.data(), rm->params.construction == 2);
-  if (rc != ARTP_OK) {
+  if (rc != ARTP_OK) {  // undo: the old query states and their neighbour rows; the edge arrays were not touched yet
     std::memcpy(&rm->verts[0], old_sg, sizeof(old_sg));
     std::copy(old_knn.begin(), old_knn.end(), rm->knn.begin());
     std::copy(old_knn_dist.begin(), old_knn_dist.end(), rm->knn_dist.begin());
@@ -1801,10 +1779,7 @@ int artp_roadmap_set_query(artp_roadmap* rm, const double* start7, const double*
   std::vector<uint8_t> zeros(np, 0);
   splice(rm->eremoved, zeros);
   if (!rm->eflip.empty()) splice(rm->eflip, zeros);  // query vertex (the smaller id) -> neighbour: the order it is added in
-  rm->csr_dirty = true;
-  rm->emotion_dirty = true;
-  rm->d_edge_states_stale = true;
-  rm->d_graph_ne = 0;  // the edge list changed: the device copy is rebuilt at the next search
+  roadmap_edges_changed(rm);
   return ARTP_OK;
 }
 
@@ -1838,17 +1813,15 @@ int roadmap_simplify_path_impl(artp_ctx* c, const artp_roadmap_params* prm, cons
     // shortcut candidates are path segments: the learned objective prices them the way motionCost does
     // (max_query_edge_length, motion_cost_objective.cpp:41-42); the 0.5 m rule still decides their validity
     const double mq = prm->max_query_edge_length > 0.0 ? prm->max_query_edge_length : 0.5;
-    int rc = roadmap_eval_edges_host(c, prm, verts, eu.data(), ev.data(), ne, ok1.data(), ni.data(), ec.data(), false,
-                                     nullptr, prm->objective == 2 ? mq : 0.0);
-    if (rc != ARTP_OK) return rc;
+    ARTP_TRY(roadmap_eval_edges_host(c, prm, verts, eu.data(), ev.data(), ne, ok1.data(), ni.data(), ec.data(), false,
+                                     nullptr, prm->objective == 2 ? mq : 0.0));
     std::vector<double> s1(ne * 7), s2(ne * 7);
     for (size_t e = 0; e < ne; ++e) {
       std::memcpy(&s1[e * 7], &verts[(size_t)eu[e] * 7], 7 * sizeof(double));
       std::memcpy(&s2[e * 7], &verts[(size_t)ev[e] * 7], 7 * sizeof(double));
     }
-    rc = artp_check_motions(c, s1.data(), s2.data(), ne, ok2.data());
-    if (rc != ARTP_OK) return rc;
-    (void)hipStreamSynchronize(c->lane->stream);
+    ARTP_TRY(artp_check_motions(c, s1.data(), s2.data(), ne, ok2.data()));
+    HIP_TRY(c, hipStreamSynchronize(c->lane->stream));
   }
   // DAG shortest path 0 -> n-1 (edges only go forward)
   std::vector<double> best(n, INFINITY);
@@ -1959,15 +1932,6 @@ struct LazyTree {
   using Item = std::pair<double, uint32_t>;
   // everything the searches touch per adjacency slot is contiguous (adj, adjw); dist / pred of 10^4 vertices stay in
   // the host's L1 / L2 (three random reads per slot into the per-edge arrays made a repair 10x slower)
-  bool usable(uint32_t e) const {
-    const double w = rm->ecost[e];
-    return rm->evalid[e] && !rm->eremoved[e] && std::isfinite(w) && w >= 0.0;
-  }
-  void drop_edge(uint32_t e) {  // the slots of a removed edge stop being usable
-    for (const uint32_t v : {rm->eu[e], rm->ev[e]})
-      for (uint32_t a = rm->row[v]; a < rm->row[v + 1]; ++a)
-        if (rm->adj_edge[a] == e) rm->adjw[a] = INFINITY;
-  }
   void full(uint32_t new_root) {
     const size_t nv = rm->nv();
     root = new_root;
@@ -2205,9 +2169,9 @@ int roadmap_check_motion_items(artp_roadmap* rm, const std::vector<uint32_t>& sr
       std::memcpy(&s1[i * 7], &rm->verts[(size_t)src[i] * 7], 7 * sizeof(double));
       std::memcpy(&s2[i * 7], &rm->verts[(size_t)dst[i] * 7], 7 * sizeof(double));
     }
-    const int rc = artp_check_motions(c, s1.data(), s2.data(), n, ok->data());
-    if (rc != ARTP_OK) return rc;
-    return hipStreamSynchronize(c->lane->stream) == hipSuccess ? ARTP_OK : ARTP_ERR_HIP;
+    ARTP_TRY(artp_check_motions(c, s1.data(), s2.data(), n, ok->data()));
+    HIP_TRY(c, hipStreamSynchronize(c->lane->stream));
+    return ARTP_OK;
   }
   // the context's host-entry staging buffers (host_args, host_results: the device entry point below does not touch them) instead of
   // four hipMalloc / hipFree pairs per call -- a hipFree alone waits for the device
@@ -2218,12 +2182,7 @@ int roadmap_check_motion_items(artp_roadmap* rm, const std::vector<uint32_t>& sr
   uint32_t* d_uv = reinterpret_cast<uint32_t*>(d_v + nv * 7);
   double* d_s = c->lane->host_results.as<double>();
   uint8_t* d_ok = reinterpret_cast<uint8_t*>(d_s + 2 * n * 7);
-  HIP_TRY(c, hipMemcpyAsync(d_v, rm->verts.data(), nv * 7 * sizeof(double), hipMemcpyHostToDevice, c->lane->stream));
-  HIP_TRY(c, hipMemcpyAsync(d_uv, src.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, c->lane->stream));
-  HIP_TRY(c, hipMemcpyAsync(d_uv + n, dst.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, c->lane->stream));
-  hipLaunchKernelGGL(artp::gather_edge_states_uv_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->lane->stream,
-                     (const double*)d_v, (const uint32_t*)d_uv, (const uint32_t*)(d_uv + n), n, d_s, d_s + n * 7);
-  HIP_TRY(c, hipGetLastError());
+  ARTP_TRY(roadmap_gather_endpoints(rm, src.data(), dst.data(), n, d_v, d_uv, d_s, d_s + n * 7));
   // in chunks of 2^18 motions (~13 M interior states): the pipeline's scratch (PoseRecs, queues) is sized by the largest
   // batch a context has seen, and a 10^6-motion batch would make it allocate tens of GB once
   for (size_t at = 0; at < n; at += (size_t)1 << 18) {
@@ -2238,16 +2197,79 @@ int roadmap_check_motion_items(artp_roadmap* rm, const std::vector<uint32_t>& sr
 #define ARTP_LAZY_PRECHECK_AFTER 3          // lazy removals before the whole graph is checked in one batch
 #define ARTP_LAZY_PRECHECK_MAX (1u << 22)   // ... unless that is more motions than this
 
+// A lazy solve's answer: the path's states (when the caller gave a buffer), its length, cost and the removals it took
+int roadmap_write_path(artp_roadmap* rm, const std::vector<uint32_t>& path, double path_cost, int replans,
+                       double* path_se3, size_t cap_states, size_t* n_path, double* cost, int* n_replans) {
+  const size_t np = path.size();
+  *n_path = np;
+  if (path_se3) {
+    if (cap_states < np) {
+      rm->ctx->last_error = "path buffer too small";
+      return ARTP_ERR_CAPACITY;
+    }
+    for (size_t i = 0; i < np; ++i) std::memcpy(path_se3 + i * 7, &rm->verts[(size_t)path[i] * 7], 7 * sizeof(double));
+  }
+  *cost = path_cost;
+  if (n_replans) *n_replans = replans;
+  return ARTP_OK;
+}
+
+// one more lazy removal: max_replans of them is the limit of a solve
+int roadmap_count_replan(artp_roadmap* rm, int* replans, int* n_replans) {
+  if (++*replans <= (int)rm->params.max_replans) return ARTP_OK;
+  rm->ctx->last_error = "too many lazy edge removals";
+  if (n_replans) *n_replans = *replans;
+  return ARTP_ERR_CAPACITY;
+}
+
+// Where a lazy solve's time went ($ARTP_SOLVE_TIMING, $ARTP_SOLVE_SEQUENCE: the variants build).  The product's
+// variant_env is a constant null, so `on` is false, the clock is never read and report() prints nothing.
+struct SolveTrace {
+  const bool on = variant_env("ARTP_SOLVE_TIMING") != nullptr;
+  double t_csr = 0, t_full = 0, t_check = 0, t_repair = 0, t_pre = 0, t_informed = 0;
+  double c_star = INFINITY, c_pre = 0;  // C* of the informed set, the path cost at the precheck
+  size_t n_check_calls = 0, n_checked = 0, n_pre = 0, sub_total = 0, n_rel = 0;
+  int n_switch = 0;
+  struct SubStat { uint32_t n, bad, np; float ms; };
+  std::vector<SubStat> sub_sizes;
+  double now() const {
+    return on ? std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count() : 0.0;
+  }
+  void repaired(size_t sub, size_t bad, size_t np, double ms) {
+    t_repair += ms;
+    sub_total += sub;
+    if (on) sub_sizes.push_back({(uint32_t)sub, (uint32_t)bad, (uint32_t)np, (float)ms});
+  }
+  void report(const artp_roadmap* rm, int replans, int informed_round, uint32_t root) const {
+    if (!on) return;
+    if (!sub_sizes.empty()) {
+      std::vector<SubStat> ss = sub_sizes;
+      std::sort(ss.begin(), ss.end(), [](const SubStat& a, const SubStat& b) { return a.n > b.n; });
+      std::fprintf(stderr, "[solve] largest repairs (vertices @ position/path states, ms):");
+      for (size_t i = 0; i < ss.size() && i < 12; ++i) std::fprintf(stderr, " %u@%u/%u %.3f", ss[i].n, ss[i].bad, ss[i].np, ss[i].ms);
+      std::fprintf(stderr, "; median %u\n", ss[ss.size() / 2].n);
+      if (variant_env("ARTP_SOLVE_SEQUENCE")) {
+        std::fprintf(stderr, "[solve] sequence (position/states:vertices):");
+        for (const SubStat& q : sub_sizes) std::fprintf(stderr, " %u/%u:%u", q.bad, q.np, q.n);
+        std::fprintf(stderr, "\n");
+      }
+    }
+    std::fprintf(stderr, "[solve] nv %zu ne %zu: csr %.2f ms, full tree %.2f ms, %zu check calls (%zu motions) %.2f ms of which "
+                 "precheck %zu motions %.2f ms, %d repairs %.2f ms (subtree vertices %zu); informed set %zu vertices "
+                 "(C* %.4f, cost at the precheck %.4f, shell %d) %.2f ms; root %u after %d switches\n", rm->nv(), rm->eu.size(),
+                 t_csr, t_full, n_check_calls, n_checked, t_check, n_pre, t_pre, replans, t_repair, sub_total, n_rel, c_star,
+                 c_pre, informed_round, t_informed, root, n_switch);
+  }
+};
+
 int roadmap_solve_tree(artp_roadmap* rm, double* path_se3, size_t cap_states, size_t* n_path, double* cost,
                        int* n_replans) {
   artp_ctx* c = rm->ctx;
   const size_t ne = rm->eu.size();
-  const bool timing = variant_env("ARTP_SOLVE_TIMING") != nullptr;
-  auto now = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  double t_csr = now(), t_full = 0, t_check = 0, t_repair = 0, t_pre = 0;
-  size_t n_check_calls = 0, n_checked = 0, sub_total = 0, n_pre = 0;
+  SolveTrace tr;
+  tr.t_csr = tr.now();
   if (rm->csr_dirty) roadmap_build_csr(rm);
-  t_csr = now() - t_csr;
+  tr.t_csr = tr.now() - tr.t_csr;
   const uint64_t mv = artp_map_version(c);
   if (rm->emotion_dirty || rm->emotion.size() != 2 * ne || rm->emotion_map_version != mv) {
     rm->emotion.assign(2 * ne, 0);
@@ -2263,37 +2285,15 @@ int roadmap_solve_tree(artp_roadmap* rm, double* path_se3, size_t cap_states, si
   const char* env_inf = variant_env("ARTP_LAZY_INFORMED");
   bool informed = env_inf ? std::atoi(env_inf) != 0 : true;
   const double informed_beta[5] = {1.06, 1.25, 1.6, 2.5, INFINITY};
-  int informed_round = 0, wrong_side = 0, since_switch = 0, n_switch = 0, pinned_root = -1;
-  double bound = INFINITY, c_star = INFINITY, c_pre = 0, t_informed = 0;
-  size_t n_rel = 0;
+  int informed_round = 0, wrong_side = 0, since_switch = 0, pinned_root = -1;
+  double bound = INFINITY;
   std::vector<double> to_other;
   std::vector<uint8_t> within;
-  struct SubStat { uint32_t n, bad, np; float ms; };
-  std::vector<SubStat> sub_sizes;
-  auto report = [&]() {
-    if (timing && !sub_sizes.empty()) {
-      std::vector<SubStat> ss = sub_sizes;
-      std::sort(ss.begin(), ss.end(), [](const SubStat& a, const SubStat& b) { return a.n > b.n; });
-      std::fprintf(stderr, "[solve] largest repairs (vertices @ position/path states, ms):");
-      for (size_t i = 0; i < ss.size() && i < 12; ++i) std::fprintf(stderr, " %u@%u/%u %.3f", ss[i].n, ss[i].bad, ss[i].np, ss[i].ms);
-      std::fprintf(stderr, "; median %u\n", ss[ss.size() / 2].n);
-      if (variant_env("ARTP_SOLVE_SEQUENCE")) {
-        std::fprintf(stderr, "[solve] sequence (position/states:vertices):");
-        for (const SubStat& q : sub_sizes) std::fprintf(stderr, " %u/%u:%u", q.bad, q.np, q.n);
-        std::fprintf(stderr, "\n");
-      }
-    }
-    if (timing)
-      std::fprintf(stderr, "[solve] nv %zu ne %zu: csr %.2f ms, full tree %.2f ms, %zu check calls (%zu motions) %.2f ms of which "
-                   "precheck %zu motions %.2f ms, %d repairs %.2f ms (subtree vertices %zu); informed set %zu vertices "
-                   "(C* %.4f, cost at the precheck %.4f, shell %d) %.2f ms; root %u after %d switches\n", rm->nv(), ne, t_csr, t_full,
-                   n_check_calls, n_checked, t_check, n_pre, t_pre, replans, t_repair, sub_total, n_rel, c_star, c_pre,
-                   informed_round, t_informed, t.root, n_switch);
-  };
   bool prechecked = false, precheck_batch = false;
   std::vector<uint32_t> path, pedge, src, dst, item;
   std::vector<uint8_t> ok;
   for (;;) {
+    // ---- the cheapest path of the current graph: the first A*, then read off the tree ----
     double path_cost = INFINITY;
     pedge.clear();
     if (!have_tree) {
@@ -2323,7 +2323,7 @@ int roadmap_solve_tree(artp_roadmap* rm, double* path_se3, size_t cap_states, si
       }
       if (!std::isfinite(t.dist[far])) {
         if (n_replans) *n_replans = replans;
-        report();
+        tr.report(rm, replans, informed_round, t.root);
         return ARTP_OK;
       }
       path.clear();
@@ -2346,8 +2346,8 @@ int roadmap_solve_tree(artp_roadmap* rm, double* path_se3, size_t cap_states, si
     }
     const size_t np = path.size();
     auto slot = [&](size_t i) { return 2 * (size_t)pedge[i] + (path[i] == rm->eu[pedge[i]] ? 0u : 1u); };
-    // verdicts the table does not hold yet: this path's, or -- once the graph has shown that it needs its lazy checks
-    // -- every usable edge's, both directions, in one batch
+    // ---- verdicts the table does not hold yet: this path's, or -- once the graph has shown that it needs its lazy
+    // checks -- every usable edge's, both directions, in one batch ----
     src.clear();
     dst.clear();
     item.clear();
@@ -2356,17 +2356,17 @@ int roadmap_solve_tree(artp_roadmap* rm, double* path_se3, size_t cap_states, si
       // are all valid; a vertex v with d(start, v) + d(v, goal) > C* (distances in TODAY's graph: they only grow as
       // edges go) can lie on none of them.  C* needs verdicts, so: guess C* <= beta c, check the motions among the
       // vertices within beta c in one batch, find C* among them, widen beta if it was not there.
-      const double t0 = now();
+      const double t0 = tr.now();
       if (informed && to_other.empty()) t.distances_from(t.root == 0u ? 1u : 0u, &to_other);
-      t_informed += now() - t0;
+      tr.t_informed += tr.now() - t0;
       double beta = informed ? informed_beta[informed_round] : INFINITY;
       bound = std::isfinite(beta) ? beta * path_cost * (1.0 + 1e-9) : INFINITY;
-      c_pre = path_cost;
+      tr.c_pre = path_cost;
       within.assign(rm->nv(), 1);
       if (std::isfinite(bound))
         for (size_t v = 0; v < rm->nv(); ++v) within[v] = t.dist[v] + to_other[v] <= bound;
       for (size_t e = 0; e < ne && item.size() <= ARTP_LAZY_PRECHECK_MAX; ++e) {
-        if (!within[rm->eu[e]] || !within[rm->ev[e]] || !t.usable((uint32_t)e)) continue;
+        if (!within[rm->eu[e]] || !within[rm->ev[e]] || !std::isfinite(roadmap_edge_weight(rm, e))) continue;
         for (unsigned d = 0; d < 2; ++d)
           if (rm->emotion[2 * e + d] == 0) {
             src.push_back(d ? rm->ev[e] : rm->eu[e]);
@@ -2392,66 +2392,54 @@ int roadmap_solve_tree(artp_roadmap* rm, double* path_se3, size_t cap_states, si
           item.push_back((uint32_t)slot(i));
         }
     if (!item.empty()) {
-      const double t0 = now();
-      const int rc = roadmap_check_motion_items(rm, src, dst, &ok);
-      if (rc != ARTP_OK) return rc;
+      const double t0 = tr.now();
+      ARTP_TRY(roadmap_check_motion_items(rm, src, dst, &ok));
       for (size_t k = 0; k < item.size(); ++k) rm->emotion[item[k]] = ok[k] ? 1 : 2;
-      t_check += now() - t0;
-      ++n_check_calls;
-      n_checked += item.size();
+      tr.t_check += tr.now() - t0;
+      ++tr.n_check_calls;
+      tr.n_checked += item.size();
       if (precheck_batch) {
-        t_pre += now() - t0;
-        n_pre += item.size();
+        tr.t_pre += tr.now() - t0;
+        tr.n_pre += item.size();
       }
     }
     if (precheck_batch) {
       precheck_batch = false;
       if (informed && t.rel.empty()) {
-        const double t0 = now();
+        const double t0 = tr.now();
         const double cstar = t.valid_only_cost(within, t.root == 1u ? t.dist : to_other);  // heuristic: distance to the goal
         if (cstar <= bound) {  // the true C*: a cheaper all-valid path would lie within the bound as well
           std::vector<uint8_t> keep(rm->nv());
           size_t kept = 0;
           for (size_t v = 0; v < rm->nv(); ++v) kept += keep[v] = t.dist[v] + to_other[v] <= cstar * (1.0 + 1e-9);
           t.restrict(std::move(keep), to_other.data(), cstar * (1.0 + 1e-9));
-          n_rel = kept;
-          c_star = cstar;
+          tr.n_rel = kept;
+          tr.c_star = cstar;
         } else if (std::isfinite(bound)) {  // not within beta c: the next shell (the verdicts so far stay)
           ++informed_round;
           prechecked = false;
         }
-        t_informed += now() - t0;
+        tr.t_informed += tr.now() - t0;
       }
     }
+    // ---- the first invalid edge from the goal backwards (the reference's walk) goes; none: this path is the answer ----
     size_t bad = np;
-    for (size_t i = np - 1; i-- > 0;)  // the reference walks from the goal backwards
+    for (size_t i = np - 1; i-- > 0;)
       if (rm->emotion[slot(i)] == 2) {
         bad = i;
         break;
       }
     if (bad == np) {
-      if (path_se3) {
-        if (cap_states < np) {
-          c->last_error = "path buffer too small";
-          *n_path = np;
-          return ARTP_ERR_CAPACITY;
-        }
-        for (size_t i = 0; i < np; ++i)
-          std::memcpy(path_se3 + i * 7, &rm->verts[(size_t)path[i] * 7], 7 * sizeof(double));
-      }
-      *n_path = np;
-      *cost = path_cost;
-      if (n_replans) *n_replans = replans;
-      report();
-      return ARTP_OK;
+      const int rc = roadmap_write_path(rm, path, path_cost, replans, path_se3, cap_states, n_path, cost, n_replans);
+      if (rc == ARTP_OK) tr.report(rm, replans, informed_round, t.root);
+      return rc;
     }
-    rm->eremoved[pedge[bad]] = 1;
-    rm->d_graph_dirty = true;
-    t.drop_edge(pedge[bad]);
+    roadmap_remove_edge(rm, pedge[bad]);
+    // ---- the tree follows: built at the first removal, repaired at every later one ----
     // where along the path the edge failed: 0 = at the start, 1 = at the goal
     const double where = np > 2 ? (double)bad / (double)(np - 2) : 0.5;
     if (!have_tree) {
-      const double t0 = now();
+      const double t0 = tr.now();
       // the order among equal-cost paths is that of a search from the START (LazyTree::before): with the directional
       // objective, where equal sums are real, the tree stays there
       if (rm->params.objective == 1) pinned_root = 0;
@@ -2469,35 +2457,27 @@ int roadmap_solve_tree(artp_roadmap* rm, double* path_se3, size_t cap_states, si
       }
       t.full(new_root);
       if (side.joinable()) side.join();
-      t_full = now() - t0;
+      tr.t_full = tr.now() - t0;
       have_tree = true;
     } else {
-      const double t0 = now();
+      const double t0 = tr.now();
       t.repair(t.root == 0u ? path[bad + 1] : path[bad]);  // the tree edge into that vertex is gone
-      t_repair += now() - t0;
-      sub_total += t.sub.size();
-      if (timing) sub_sizes.push_back({(uint32_t)t.sub.size(), (uint32_t)bad, (uint32_t)np, (float)(now() - t0)});
+      tr.repaired(t.sub.size(), bad, np, tr.now() - t0);
       // the edges keep failing on the root's side of the path: hang the tree from the other end (a search over the
       // vertices still in reach; the old root's exact distances become the bound towards it)
       const bool root_side = t.root == 0u ? where < 0.35 : where > 0.65;
       wrong_side = root_side ? wrong_side + 1 : 0;
       if (++since_switch >= 12 && wrong_side >= 6 && t.to_other && pinned_root < 0) {
-        const double t1 = now();
-        if (t.to_other) {
-          to_other = t.dist;
-          t.to_other = to_other.data();
-        }
+        const double t1 = tr.now();
+        to_other = t.dist;
+        t.to_other = to_other.data();
         t.full(t.root == 0u ? 1u : 0u);
-        t_full += now() - t1;
-        ++n_switch;
+        tr.t_full += tr.now() - t1;
+        ++tr.n_switch;
         wrong_side = since_switch = 0;
       }
     }
-    if (++replans > (int)rm->params.max_replans) {
-      c->last_error = "too many lazy edge removals";
-      if (n_replans) *n_replans = replans;
-      return ARTP_ERR_CAPACITY;
-    }
+    ARTP_TRY(roadmap_count_replan(rm, &replans, n_replans));
   }
 }
 
@@ -2518,16 +2498,10 @@ int artp_roadmap_solve(artp_roadmap* rm, double* path_se3, size_t cap_states, si
   std::vector<uint8_t> ok;
   for (;;) {
     double cst = INFINITY;
-    bool found;
-    const bool on_device = rm->nv() >= ARTP_SSSP_MIN_VERTICES;
-    if (on_device) {
-      bool dev_ok = false;
-      found = roadmap_sssp_dev(rm, &path, &cst, &dev_ok);
-      if (!dev_ok) found = roadmap_astar(rm, &path, &cst);
-    } else {
-      found = roadmap_astar(rm, &path, &cst);
-    }
-    if (!found) {
+    DevSearch found = DevSearch::UseHost;
+    if (rm->nv() >= ARTP_SSSP_MIN_VERTICES) ARTP_TRY(roadmap_sssp_dev(rm, &path, &cst, &found));
+    if (found == DevSearch::UseHost) found = roadmap_astar(rm, &path, &cst) ? DevSearch::Found : DevSearch::Unreachable;
+    if (found == DevSearch::Unreachable) {
       if (n_replans) *n_replans = replans;
       return ARTP_OK;  // *n_path == 0: start and goal are not connected (PlannerStatus::TIMEOUT)
     }
@@ -2542,9 +2516,8 @@ int artp_roadmap_solve(artp_roadmap* rm, double* path_se3, size_t cap_states, si
       std::memcpy(&s2[i * 7], &rm->verts[(size_t)path[i + 1] * 7], 7 * sizeof(double));
     }
     if (np > 1) {
-      const int rc = artp_check_motions(c, s1.data(), s2.data(), np - 1, ok.data());
-      if (rc != ARTP_OK) return rc;
-      (void)hipStreamSynchronize(c->lane->stream);
+      ARTP_TRY(artp_check_motions(c, s1.data(), s2.data(), np - 1, ok.data()));
+      HIP_TRY(c, hipStreamSynchronize(c->lane->stream));
     }
     size_t bad = np;
     for (size_t i = np - 1; i-- > 0;)  // the reference walks from the goal backwards
@@ -2552,44 +2525,18 @@ int artp_roadmap_solve(artp_roadmap* rm, double* path_se3, size_t cap_states, si
         bad = i;
         break;
       }
-    if (bad == np) {
-      if (path_se3) {
-        if (cap_states < np) {
-          c->last_error = "path buffer too small";
-          *n_path = np;
-          return ARTP_ERR_CAPACITY;
-        }
-        for (size_t i = 0; i < np; ++i)
-          std::memcpy(path_se3 + i * 7, &rm->verts[(size_t)path[i] * 7], 7 * sizeof(double));
-      }
-      *n_path = np;
-      *cost = cst;
-      if (n_replans) *n_replans = replans;
-      return ARTP_OK;
-    }
-    // remove edge (path[bad], path[bad+1])
+    if (bad == np) return roadmap_write_path(rm, path, cst, replans, path_se3, cap_states, n_path, cost, n_replans);
+    // remove edge (path[bad], path[bad+1]): the edge list is sorted by (u, v), u < v
     const uint32_t a = std::min(path[bad], path[bad + 1]), b = std::max(path[bad], path[bad + 1]);
-    if (!rm->csr_dirty) {
-      for (uint32_t t = rm->row[a]; t < rm->row[a + 1]; ++t)
-        if (rm->adj[t] == b) rm->eremoved[rm->adj_edge[t]] = 1;  // the search skips removed edges
-    } else {
-      // no CSR (device search): the edge list is sorted by (u, v), u < v
-      size_t lo = 0, hi = rm->eu.size();
-      while (lo < hi) {
-        const size_t mid = (lo + hi) / 2;
-        if (rm->eu[mid] < a || (rm->eu[mid] == a && rm->ev[mid] < b)) lo = mid + 1; else hi = mid;
-      }
-      if (lo < rm->eu.size() && rm->eu[lo] == a && rm->ev[lo] == b) rm->eremoved[lo] = 1;
+    size_t lo = 0, hi = rm->eu.size();
+    while (lo < hi) {
+      const size_t mid = (lo + hi) / 2;
+      if (rm->eu[mid] < a || (rm->eu[mid] == a && rm->ev[mid] < b)) lo = mid + 1; else hi = mid;
     }
-    rm->d_graph_dirty = true;
-    if (++replans > (int)rm->params.max_replans) {
-      c->last_error = "too many lazy edge removals";
-      if (n_replans) *n_replans = replans;
-      return ARTP_ERR_CAPACITY;
-    }
+    if (lo < rm->eu.size() && rm->eu[lo] == a && rm->ev[lo] == b) roadmap_remove_edge(rm, lo);
+    ARTP_TRY(roadmap_count_replan(rm, &replans, n_replans));
   }
 }
-
 
 int artp_roadmap_set_density_map(artp_roadmap* rm, artp_preprocessed* pp, const artp_preprocess_params* prm) {
   if (!rm || (pp && !prm)) return ARTP_ERR_INVALID_ARG;
@@ -2613,20 +2560,17 @@ int artp_roadmap_solve_until(artp_roadmap* rm, double plan_time, uint32_t grow_s
     size_t n = 0;
     double cst = INFINITY;
     int replans = 0;
-    int rc = artp_roadmap_solve(rm, nullptr, 0, &n, &cst, &replans);  // length first
-    if (rc != ARTP_OK) return rc;
+    ARTP_TRY(artp_roadmap_solve(rm, nullptr, 0, &n, &cst, &replans));  // length first
     if (n > 0 && cst < best_cost) {  // opt_->isCostBetterThan(c, bestCost_)
       cur.resize(n * 7);
-      rc = artp_roadmap_solve(rm, cur.data(), n, &n, &cst, &replans);
-      if (rc != ARTP_OK) return rc;
+      ARTP_TRY(artp_roadmap_solve(rm, cur.data(), n, &n, &cst, &replans));
       best.assign(cur.begin(), cur.begin() + n * 7);
       best_cost = cst;
       ++improved;
     }
     if (elapsed() >= plan_time || grow_step == 0) break;  // ptc
     uint64_t g[2];
-    rc = artp_roadmap_grow(rm, grow_step, g);  // `do sampleUniform while !isValid; addValidMilestone` in batches
-    if (rc != ARTP_OK) return rc;
+    ARTP_TRY(artp_roadmap_grow(rm, grow_step, g));  // `do sampleUniform while !isValid; addValidMilestone` in batches
     ++rounds;
   }
   if (stats) {

@@ -335,12 +335,10 @@ struct QuerySnapshot {
     put(rm->ecost, ecost);
     put(rm->eremoved, eremoved);
     if (!rm->eflip.empty()) put(rm->eflip, eflip);
-    rm->emotion = emotion;
+    roadmap_edges_changed(rm);  // derived state: rebuilt from the restored arrays when next needed ...
+    rm->emotion = emotion;      // ... but for the verdict cache, which comes back with the list it was taken for
     rm->emotion_map_version = emotion_map_version;
     rm->emotion_dirty = emotion_dirty;
-    rm->csr_dirty = true;  // derived caches: rebuilt from the restored arrays when next needed
-    rm->d_edge_states_stale = true;
-    rm->d_graph_ne = 0;
   }
 };
 
@@ -365,8 +363,7 @@ int many_device_solve(artp_roadmap* rm, const double* start7, const double* goal
     const size_t r = first_keep + e;
     heu[e] = rm->eu[r];
     hev[e] = rm->ev[r];
-    hw[e] = (rm->evalid[r] && !rm->eremoved[r] && std::isfinite(rm->ecost[r]) && rm->ecost[r] >= 0.0) ? rm->ecost[r]
-                                                                                                         : INFINITY;
+    hw[e] = roadmap_edge_weight(rm, r);
   }
   for (size_t t = 0; t < ns; ++t) {
     heu[nr + t] = 0;
@@ -456,27 +453,16 @@ int many_device_solve(artp_roadmap* rm, const double* start7, const double* goal
     hipLaunchKernelGGL(artp::roadmap_many_init_kernel, dim3(tree_blocks(nv)), dim3(256), 0, st, (int)nv, d_dist, d_stamp,
                        d_hops, d_hstamp, d_pkey);
     unsigned cnt[8];
-    // sweep groups of 16, 32, 64 between host reads: a sweep behind the wavefront costs two reads per edge, a read
-    // a synchronisation (the sparse construction-1 graphs take hundreds of sweeps)
-    for (unsigned sweep = 1, group = 16; sweep < 1000000u; sweep += group, group = std::min(2 * group, 64u)) {
-      HIP_TRY(c, hipMemsetAsync(d_cnt, 0, 4, st));
-      for (unsigned r = 0; r < group; ++r)
-        hipLaunchKernelGGL(artp::sssp_relax_kernel, dim3((unsigned)blocks), dim3(256), 0, st, d_eu, d_ev,
-                           (const double*)d_w, ne, d_dist, d_stamp, sweep + r, d_cnt);
-      HIP_TRY(c, hipMemcpyAsync(cnt, d_cnt, 4, hipMemcpyDeviceToHost, st));
-      HIP_TRY(c, hipStreamSynchronize(st));
-      if (!cnt[0]) break;
-    }
+    // sweep groups of 16, 32, 64, 64, ... between host reads (the sparse construction-1 graphs take hundreds of sweeps)
+    ARTP_TRY(roadmap_sweep_to_fixed_point(c, d_cnt, 16, 64, [&](unsigned sweep) {
+      hipLaunchKernelGGL(artp::sssp_relax_kernel, dim3((unsigned)blocks), dim3(256), 0, st, d_eu, d_ev, (const double*)d_w,
+                         ne, d_dist, d_stamp, sweep, d_cnt);
+    }));
     // 2. hop counts over the tight edges, predecessors one hop closer
-    for (unsigned sweep = 1, group = 16; sweep < 1000000u; sweep += group, group = std::min(2 * group, 64u)) {
-      HIP_TRY(c, hipMemsetAsync(d_cnt + 1, 0, 4, st));
-      for (unsigned r = 0; r < group; ++r)
-        hipLaunchKernelGGL(artp::roadmap_many_hops_kernel, dim3((unsigned)blocks), dim3(256), 0, st, d_eu, d_ev,
-                           (const double*)d_w, ne, (const unsigned long long*)d_dist, d_hops, d_hstamp, sweep + r, d_cnt + 1);
-      HIP_TRY(c, hipMemcpyAsync(cnt + 1, d_cnt + 1, 4, hipMemcpyDeviceToHost, st));
-      HIP_TRY(c, hipStreamSynchronize(st));
-      if (!cnt[1]) break;
-    }
+    ARTP_TRY(roadmap_sweep_to_fixed_point(c, d_cnt + 1, 16, 64, [&](unsigned sweep) {
+      hipLaunchKernelGGL(artp::roadmap_many_hops_kernel, dim3((unsigned)blocks), dim3(256), 0, st, d_eu, d_ev,
+                         (const double*)d_w, ne, (const unsigned long long*)d_dist, d_hops, d_hstamp, sweep, d_cnt + 1);
+    }));
     hipLaunchKernelGGL(artp::roadmap_many_pred_kernel, dim3((unsigned)blocks), dim3(256), 0, st, d_eu, d_ev,
                        (const double*)d_w, ne, (const unsigned long long*)d_dist, (const uint32_t*)d_hops, d_pkey);
     // 3. best attachment per pending goal, 4. path lengths -> offsets
@@ -573,17 +559,9 @@ int many_device_solve(artp_roadmap* rm, const double* start7, const double* goal
     if (status[g] == 0) (*paths)[g].assign(rpv[fr[i]].begin() + fo[i], rpv[fr[i]].begin() + fo[i] + fl[i]);
     for (int a = 0; a < k; ++a) n_removed += hav[i * k + a] == 2u;
   }
-  bool any_removed = false;
   for (size_t e = 0; e < ne; ++e) {
     n_removed += hrem[e];
-    if (e < nr && hrem[e]) {
-      rm->eremoved[first_keep + e] = 1;
-      any_removed = true;
-    }
-  }
-  if (any_removed) {
-    rm->csr_dirty = true;
-    rm->d_graph_dirty = true;
+    if (e < nr && hrem[e]) roadmap_remove_edge(rm, first_keep + e);
   }
   if (!cache_ok) {  // the solve loop's rule: a stale table is cleared for this map and edge list first
     rm->emotion.assign(2 * rm->eu.size(), 0);
@@ -615,14 +593,8 @@ int artp_roadmap_solve_many(artp_roadmap* rm, const double* start_se3, const dou
   std::memcpy(sg.data(), start_se3, 7 * sizeof(double));
   if (ng) std::memcpy(sg.data() + 7, goals_se3, ng * 7 * sizeof(double));
   std::vector<uint8_t> ok(ng + 1, 0);
-  {
-    const int rc = artp_validate_states(c, sg.data(), ng + 1, ok.data(), nullptr);
-    if (rc != ARTP_OK) return rc;
-  }
-  if (!ok[0]) {
-    c->last_error = "start state is not valid";
-    return ARTP_ERR_INVALID_ARG;
-  }
+  ARTP_TRY(artp_validate_states(c, sg.data(), ng + 1, ok.data(), nullptr));
+  ARTP_TRY(roadmap_require_valid_query(c, ok[0], true));  // an invalid goal is that goal's status, not an error
   if (path_offsets) path_offsets[0] = 0;
   if (ng == 0) {
     if (stats_out) std::memset(stats_out, 0, 4 * sizeof(uint64_t));

@@ -496,7 +496,7 @@ struct artp_tree {
   uint32_t *d_nn = nullptr, *d_idx1 = nullptr, *d_idx2 = nullptr, *d_rank = nullptr, *d_par0 = nullptr, *d_near = nullptr;
   uint8_t *d_alive = nullptr, *d_valid1 = nullptr, *d_validk = nullptr;
   uint32_t* d_cnt = nullptr;     // 4 words: compaction results
-  uint32_t* h_cnt = nullptr;     // pinned twin
+  PinnedBuffer<uint32_t> h_cnt;  // pinned twin
   unsigned long long* d_counters = nullptr;  // [0] near motions checked, [1] rewires
   int* d_err = nullptr;
   unsigned long long* d_best_bits = nullptr;  // rewire: cap; rrt_sharp: dist
@@ -521,9 +521,8 @@ inline int tree_k(double rewire_factor, size_t n) {
   return (int)std::ceil(rewire_factor * (2.718281828459045 + 2.718281828459045 / 6.0) * std::log((double)n + 1.0));
 }
 
-// what artp_tree::mem does not own: the pinned host block and the events
+// what the tree's members do not own themselves: the events
 void tree_free(artp_tree* t) {
-  if (t->h_cnt) (void)hipHostFree(t->h_cnt);
   for (hipEvent_t& e : t->ev)
     if (e) (void)hipEventDestroy(e);
 }
@@ -603,9 +602,9 @@ int tree_batch(artp_tree* t, bool* stop) {
                      t->d_xnew, t->d_alive, t->d_cnt + 2);
   hipLaunchKernelGGL(tree_compact_kernel, dim3(1), dim3(1024), 0, st, (const uint8_t*)t->d_alive, B, t->d_idx1,
                      (uint32_t*)nullptr, (const uint32_t*)nullptr, t->d_cnt);
-  HIP_TRY(c, hipMemcpyAsync(t->h_cnt, t->d_cnt, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(t->h_cnt.host(), t->d_cnt, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   HIP_TRY(c, hipStreamSynchronize(st));
-  const int m1 = (int)t->h_cnt[0];
+  const int m1 = (int)t->h_cnt.host()[0];
   // 4. first motion checkMotion(nearest, x_new) (host read 2: survivors, and whether slot 0 -- the goal -- is one)
   ARTP_TRY(mark(3));
   int m2 = 0;
@@ -616,10 +615,10 @@ int tree_batch(artp_tree* t, bool* stop) {
     ARTP_TRY(artp_check_motions_dev(c, t->d_s1, t->d_s2, (size_t)m1, t->d_valid1));
     hipLaunchKernelGGL(tree_compact_kernel, dim3(1), dim3(1024), 0, st, (const uint8_t*)t->d_valid1, m1, t->d_idx2,
                        t->d_rank, (const uint32_t*)t->d_idx1, t->d_cnt);
-    HIP_TRY(c, hipMemcpyAsync(t->h_cnt, t->d_cnt, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(t->h_cnt.host(), t->d_cnt, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
-    m2 = (int)std::min<uint32_t>(t->h_cnt[0], t->cap - n_pre);
-    first_slot = t->h_cnt[2] ? t->h_cnt[1] : TREE_NONE;  // a goal steered short of the goal is not the goal
+    m2 = (int)std::min<uint32_t>(t->h_cnt.host()[0], t->cap - n_pre);
+    first_slot = t->h_cnt.host()[2] ? t->h_cnt.host()[1] : TREE_NONE;  // a goal steered short of the goal is not the goal
   }
   t->first_checked += (uint64_t)m1;
   const int k = std::max(1, std::min(tree_k(p.rewire_factor, n_pre), t->kmax));
@@ -822,7 +821,7 @@ int artp_tree_create(artp_ctx* c, const artp_tree_params* prm, const double* sta
   HIP_TRY(c, t->mem.alloc(&t->d_valid1, B));
   HIP_TRY(c, t->mem.alloc(&t->d_validk, BK));
   HIP_TRY(c, t->mem.alloc(&t->d_cnt, 4));
-  HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&t->h_cnt), 4 * 4, hipHostMallocDefault));
+  HIP_TRY(c, t->h_cnt.reserve(4 * 4, hipHostMallocDefault));
   HIP_TRY(c, t->mem.alloc(&t->d_counters, 2));
   HIP_TRY(c, t->mem.alloc(&t->d_err, 1));
   if (prm->profile)

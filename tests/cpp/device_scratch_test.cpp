@@ -8,6 +8,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <utility>
 
 struct FakeCtx {
   std::string last_error;
@@ -310,6 +311,43 @@ int main() {
     CHECK(b.get() == p && b.capacity() == 32 && b.reserve(32) == hipSuccess && hip_stub::mallocs == 2);
   }
   CHECK(hip_stub::live == 0 && hip_stub::frees == 1);
+  // ... moved: the block changes owner without a malloc or a free, the moved-from buffer is empty and can be used again
+  {
+    hip_stub::reset();
+    {
+      DeviceBuffer<int> a;
+      CHECK(a.reserve(64) == hipSuccess);
+      int* const block = a.get();
+      block[15] = 7;
+      DeviceBuffer<int> b(std::move(a));                                  // move construction
+      CHECK(b.get() == block && b.capacity() == 64 && a.get() == nullptr && a.capacity() == 0);
+      CHECK(hip_stub::mallocs == 1 && hip_stub::frees == 0 && hip_stub::live == 1);
+      DeviceBuffer<int> e;
+      e = std::move(b);                                                   // move assignment onto an empty buffer
+      CHECK(e.get() == block && e.capacity() == 64 && b.get() == nullptr && b.capacity() == 0 && hip_stub::frees == 0);
+      DeviceBuffer<int>& self = e;
+      e = std::move(self);                                                // onto itself: nothing changes, nothing freed
+      CHECK(e.get() == block && e.capacity() == 64 && e.get()[15] == 7 && hip_stub::frees == 0 && hip_stub::live == 1);
+      DeviceBuffer<int> full;
+      CHECK(full.reserve(32) == hipSuccess && hip_stub::live == 2);
+      full = std::move(e);                                                // onto a non-empty buffer: its block goes first
+      CHECK(full.get() == block && full.capacity() == 64 && e.get() == nullptr && e.capacity() == 0);
+      CHECK(hip_stub::frees == 1 && hip_stub::live == 1 && full.get()[15] == 7);
+      CHECK(a.reserve(8) == hipSuccess && a.get() != nullptr && hip_stub::live == 2);  // a moved-from buffer grows again
+      // a struct of such members swaps whole (the roadmap's std::swap): three moves, no malloc, no free
+      struct Pair { DeviceBuffer<int> x; DeviceBuffer<> y; int tag; };
+      Pair p, q;
+      p.tag = 1, q.tag = 2;
+      CHECK(p.x.reserve(16) == hipSuccess && q.y.reserve(24) == hipSuccess);
+      int* const px = p.x.get();
+      void* const qy = q.y.get();
+      const int m = hip_stub::mallocs, f = hip_stub::frees;
+      std::swap(p, q);
+      CHECK(q.x.get() == px && p.y.get() == qy && p.x.get() == nullptr && q.y.get() == nullptr && p.tag == 2);
+      CHECK(hip_stub::mallocs == m && hip_stub::frees == f && hip_stub::live == 4);
+    }
+    CHECK(hip_stub::live == 0 && hip_stub::mallocs == hip_stub::frees);   // every block freed exactly once
+  }
 
   // PinnedBuffer: the same rules, freed with the host call and never the device one
   {
@@ -343,6 +381,30 @@ int main() {
     CHECK(m.host() == nullptr && m.dev() == nullptr && m.capacity() == 0 && hip_stub::host_live == 0);
     hip_stub::fail_dev_ptr = false;
     CHECK(hip_stub::frees == 0);
+  }
+  // ... moved: host and device address travel together
+  {
+    hip_stub::reset();
+    {
+      PinnedBuffer<double> a;
+      CHECK(a.reserve(56, hipHostMallocMapped) == hipSuccess);
+      double* const block = a.host();
+      block[6] = 3.0;
+      PinnedBuffer<double> b(std::move(a));
+      CHECK(b.host() == block && b.dev() == block && b.capacity() == 56);
+      CHECK(a.host() == nullptr && a.dev() == nullptr && a.capacity() == 0 && hip_stub::host_frees == 0);
+      PinnedBuffer<double>& self = b;
+      b = std::move(self);
+      CHECK(b.host() == block && b.dev() == block && b.capacity() == 56 && hip_stub::host_frees == 0);
+      PinnedBuffer<double> full;
+      CHECK(full.reserve(16, hipHostMallocDefault) == hipSuccess && hip_stub::host_live == 2);
+      full = std::move(b);
+      CHECK(full.host() == block && full.dev() == block && full.capacity() == 56 && full.host()[6] == 3.0);
+      CHECK(b.host() == nullptr && b.dev() == nullptr && b.capacity() == 0);
+      CHECK(hip_stub::host_frees == 1 && hip_stub::host_live == 1);
+      CHECK(a.reserve(8, hipHostMallocDefault) == hipSuccess && a.host() != nullptr && a.dev() == nullptr);
+    }
+    CHECK(hip_stub::host_live == 0 && hip_stub::host_mallocs == hip_stub::host_frees && hip_stub::frees == 0);
   }
 
   CHECK(try_passes_code(ARTP_OK) == ARTP_OK);
