@@ -28,6 +28,7 @@ SYMBOLS = [
     "artp_clearance_params_defaults", "artp_clearance_map", "artp_clearance_map_dev",
     "artp_field_clearance_params_defaults", "artp_field_compute_clearance", "artp_field_clearance",
     "artp_field_update_clearance", "artp_field_clearance_update_stats", "artp_field_shift", "artp_field_shift_stats",
+    "artp_field_shift_clearance", "artp_field_clearance_shift_stats",
     "artp_check_motions_last_valid", "artp_check_motions_last_valid_dev",
     "artp_set_z_bounds", "artp_set_few_edges", "artp_set_tail_mode", "artp_last_tail", "artp_set_edge_passes", "artp_cost_set_fc_path", "artp_check_motions", "artp_check_motions_dev", "artp_check_edges_interp",
     "artp_check_edges_interp_dev", "artp_compact_valid_dev", "artp_compact_valid_indices_dev", "artp_sample_states_at_dev",
@@ -179,6 +180,13 @@ class FieldShiftStats(C.Structure):  # artp_field_shift_stats_t
                 [(n, C.c_double) for n in ("move_ms", "passes_ms")])
 
 
+class FieldClearanceShiftStats(C.Structure):  # artp_field_clearance_shift_stats_t
+    _fields_ = (list(FieldUpdateStats._fields_) +
+                [(n, C.c_int64) for n in ("shift_rows", "shift_cols")] +
+                [(n, C.c_uint64) for n in ("kept_cells", "left_nodes", "dropped_blocked", "changed_slots", "weight_tiles")] +
+                [(n, C.c_double) for n in ("move_ms", "clearance_ms", "table_ms", "passes_ms")])
+
+
 class TreeParams(C.Structure):  # artp_tree_params (include/artp_c.h)
     _fields_ = [("seed", C.c_uint64), ("first_index", C.c_uint64), ("variant", C.c_int32), ("objective", C.c_int32),
                 ("max_lon_vel", C.c_double), ("max_lat_vel", C.c_double), ("max_ang_vel", C.c_double),
@@ -291,6 +299,8 @@ def _load_path(LIB_PATH):
     L.artp_field_clearance_update_stats.argtypes = [vp, C.POINTER(FieldClearanceUpdateStats)]
     L.artp_field_shift.argtypes = [vp, vp, i32, i32]
     L.artp_field_shift_stats.argtypes = [vp, C.POINTER(FieldShiftStats)]
+    L.artp_field_shift_clearance.argtypes = [vp, vp, i32, i32]
+    L.artp_field_clearance_shift_stats.argtypes = [vp, C.POINTER(FieldClearanceShiftStats)]
     L.artp_map_version.argtypes = [vp]
     L.artp_map_version.restype = C.c_uint64
     L.artp_set_z_bounds.argtypes = [vp, dbl, dbl]

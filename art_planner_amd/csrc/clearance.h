@@ -26,6 +26,12 @@
 //                                    slot that differs is written and flags its tile, as field_learned_reprice_kernel does
 // and the four passes of artp_field_update from the flagged tiles.  artp_field_update and artp_field_update_learned
 // refuse the field.
+// artp_field_shift_clearance carries such a field across a map move: the move and the diff of
+// artp_field_shift, clearance_map_kernel over the whole rectangle, then
+//   field_clearance_shift_table_kernel   every slot priced on the new state into a second table, against the weight its own
+//                                        node carried for the same move in the old table (+inf where that node entered)
+// and the same passes.  The second table is allocated by the first call that moves and kept until artp_field_destroy;
+// the two tables swap roles after every move (d_tab never leaves the library).
 #pragma once
 
 namespace artp {
@@ -203,6 +209,38 @@ field_clearance_reprice_kernel(FieldGrid G, ClearWindow w, const uint32_t* __res
   const bool ch = __double_as_longlong(price) != __double_as_longlong(wtab[s]);
   if (ch) wtab[s] = price;
   const unsigned long long b = __ballot(ch);
+  if (b && (threadIdx.x & 63) == 0) {
+    acc[tile] = 1u;
+    wacc[tile] = 1u;
+    atomicAdd(&cnt[5], (unsigned long long)__popcll(b));
+  }
+}
+
+// artp_field_shift_clearance: the map moved by (sh.si, sh.sj) cells, mask, h and d2 hold the new state, old_tab the table
+// of the state before the move.  field_clearance_reprice_kernel's mapping over all tiles: workgroup b prices run
+// b % (10 n_yaw) = (k, j) of tile b / (10 n_yaw), one slot a lane.  The slot's own node (r, c, k) was node (r - si, c - sj, k):
+// its old weight is that node's slot of the same move when the old cell lay inside the rectangle, +inf otherwise (an entered
+// cell had no edge; a padded slot of a last tile prices to +inf and had +inf: nothing is read for it).  The 16 lanes of a
+// tile column read 16 consecutive slots of an old tile's row, split over at most two tiles.  Every slot of wtab is
+// written; a slot whose bit pattern differs from its old one flags its tile in acc and wacc, cnt[5] += their number, one
+// atomic per wave.
+__global__ void __launch_bounds__(256)
+field_clearance_shift_table_kernel(FieldGrid G, FieldShift sh, const uint32_t* __restrict__ mask, const float* __restrict__ h,
+                                   const double* __restrict__ tab, const uint16_t* __restrict__ d2, ClearWeight p,
+                                   const double* __restrict__ old_tab, double* __restrict__ wtab, unsigned* __restrict__ acc,
+                                   unsigned* __restrict__ wacc, unsigned long long* __restrict__ cnt) {
+  const uint32_t runs = 10u * (uint32_t)G.n_yaw;
+  const uint32_t tile = blockIdx.x / runs, run = blockIdx.x - tile * runs;
+  const size_t s = ((size_t)tile * runs + run) * (FIELD_T * FIELD_T) + threadIdx.x;
+  const double price = field_clearance_price(G, mask, h, tab, d2, p, s);
+  const int r = (int)(tile % (uint32_t)G.tiles_r) * FIELD_T + (int)(threadIdx.x & (FIELD_T - 1));
+  const int c = (int)(tile / (uint32_t)G.tiles_r) * FIELD_T + (int)(threadIdx.x >> 4);
+  const int k = (int)(run / 10u), j = (int)(run - 10u * (uint32_t)k);
+  double old = INFINITY;
+  if (r < G.nrows && c < G.ncols && field_shift_inside(G, r - sh.si, c - sh.sj))
+    old = old_tab[field_wtab_index(G, r - sh.si, c - sh.sj, k, j)];
+  wtab[s] = price;
+  const unsigned long long b = __ballot(__double_as_longlong(price) != __double_as_longlong(old));
   if (b && (threadIdx.x & 63) == 0) {
     acc[tile] = 1u;
     wacc[tile] = 1u;
@@ -488,6 +526,90 @@ int artp_field_update_clearance(artp_field* f, const uint32_t* new_mask, int mas
 int artp_field_clearance_update_stats(artp_field* f, artp_field_clearance_update_stats_t* out) {
   if (!f || !out) return ARTP_ERR_INVALID_ARG;
   *out = f->custats;
+  return ARTP_OK;
+}
+
+int artp_field_shift_clearance(artp_field* f, const uint32_t* new_mask, int mask_on_device, int refresh_heights) {
+  if (!f || !new_mask) return ARTP_ERR_INVALID_ARG;
+  artp_ctx* c = f->ctx;
+  std::lock_guard<std::recursive_mutex> lock(c->mu);
+  const artp::FieldGrid& G = f->grid;
+  if (G.objective != 3) {
+    c->last_error = "artp_field_shift_clearance: not a field of artp_field_compute_clearance (artp_field_shift takes a plain "
+                    "field; a learned field is computed anew)";
+    return ARTP_ERR_INVALID_ARG;
+  }
+  FieldMove mv;
+  ARTP_TRY(field_shift_checks(f, "artp_field_shift_clearance", new_mask, mask_on_device, &mv));
+  hipStream_t st = c->lane->stream;
+  if (!mv.moves()) {
+    // artp_field_update_clearance over the whole rectangle, on the geometry a shift adopts; its own stats stay
+    const artp_field_clearance_update_stats_t kept = f->custats;
+    f->geom = c->geom;
+    const int rc = artp_field_update_clearance(f, mv.nm, 1, nullptr, refresh_heights);
+    const artp_field_clearance_update_stats_t cu = f->custats;
+    f->custats = kept;
+    if (rc) return rc;
+    artp_field_clearance_shift_stats_t us{};
+    artp_field_update_stats_t ps;
+    std::memcpy(&ps, &cu, sizeof(ps));  // the ten shared members, at their offsets
+    field_store_stats(ps, cu.passes_ms, &us);
+    us.kept_cells = f->n_cells;
+    us.changed_slots = cu.changed_slots;
+    us.weight_tiles = cu.weight_tiles;
+    us.clearance_ms = cu.clearance_ms;
+    us.table_ms = cu.reprice_ms;
+    f->clshstats = us;
+    return ARTP_OK;
+  }
+  const artp::FieldSub whole{0, 0, G.nrows, G.ncols};
+  const size_t slots = artp::field_wtab_slots(G);
+  StreamTimer<2> tm(st);
+  // The kind's step: the move's counts, then d2 of the whole rectangle and the table priced into d_tab2 against the moved
+  // old slots; cnt[5] counts the changed slots from zero again.  After a move the passes always run.
+  return field_update_run(
+      f, "artp_field_shift_clearance", mv.nm, 1, whole, refresh_heights != 0, true, &f->clshstats,
+      [&]() -> int {
+        ARTP_TRY(field_lazy(f, &f->d_tab2, slots));
+        return field_shift_move(f, mv, tm);
+      },
+      [&](unsigned long long* cnt, artp_field_clearance_shift_stats_t* us, bool* run) -> int {
+        ARTP_TRY(field_shift_counts(f, mv, tm, cnt, us));
+        HIP_TRY(c, hipMemsetAsync(f->d_ucnt + 5, 0, sizeof(unsigned long long), st));
+        const artp::FieldShift sh{(int)mv.si, (int)mv.sj, mv.si + mv.sj * (long long)G.nrows};
+        StreamTimer<3> tc(st);
+        tc.mark(0);
+        int rc = clearance_run(c, f->cparams.clearance, G.n_yaw, G.nrows, G.ncols, f->d_mask, f->d_d2);
+        tc.mark(1);
+        if (rc == ARTP_OK) {
+          artp::FieldGrid Gb = G;
+          Gb.objective = f->params.objective;
+          const artp::ClearWeight w{f->geom.res, f->cparams.margin, f->cparams.gain};
+          hipLaunchKernelGGL(artp::field_clearance_shift_table_kernel, dim3((unsigned)(f->n_tiles * 10 * (size_t)G.n_yaw)), dim3(256), 0,
+                             st, Gb, sh, (const uint32_t*)f->d_mask, (const float*)f->d_h, (const double*)f->d_btab,
+                             (const uint16_t*)f->d_d2, w, (const double*)f->d_tab, f->d_tab2, f->d_acc, f->d_wacc, f->d_ucnt);
+          if (hipGetLastError() != hipSuccess) rc = ARTP_ERR_HIP;
+        }
+        tc.mark(2);
+        if (rc == ARTP_OK) rc = field_weight_counts(f, cnt, 2);
+        if (rc) {
+          (void)hipStreamSynchronize(st);
+          if (rc == ARTP_ERR_HIP && c->last_error.empty()) c->last_error = "artp_field_shift_clearance: pricing the weight table failed";
+          return rc;
+        }
+        std::swap(f->d_tab, f->d_tab2);  // the kernel has run: the searches read the new table, the next move writes the other
+        us->clearance_ms = tc.ms(0, 1, true);
+        us->table_ms = tc.ms(1, 2, true);
+        us->changed_slots = cnt[5];
+        us->weight_tiles = cnt[6];
+        *run = true;
+        return ARTP_OK;
+      });
+}
+
+int artp_field_clearance_shift_stats(artp_field* f, artp_field_clearance_shift_stats_t* out) {
+  if (!f || !out) return ARTP_ERR_INVALID_ARG;
+  *out = f->clshstats;
   return ARTP_OK;
 }
 

@@ -935,6 +935,10 @@ struct artp_field {
   // allocated by the first shift
   char* d_shift = nullptr;
   artp_field_shift_stats_t shstats{};
+  // artp_field_shift_clearance (clearance.h): the second weight table, allocated by the first call that moves and kept;
+  // a move prices into it and swaps it with d_tab, which never leaves the library
+  double* d_tab2 = nullptr;
+  artp_field_clearance_shift_stats_t clshstats{};
   DeviceScratch mem;  // owns every d_* above: freed with the field, or earlier by mem.release
 };
 
@@ -1345,7 +1349,8 @@ void field_adopt_sampler(artp_ctx* c, artp_field* f) {
 #define FIELD_STATS_SAME_OFFSET(m)                                                                              \
   static_assert(offsetof(artp_field_learned_update_stats_t, m) == offsetof(artp_field_update_stats_t, m) &&     \
                     offsetof(artp_field_clearance_update_stats_t, m) == offsetof(artp_field_update_stats_t, m) && \
-                    offsetof(artp_field_shift_stats_t, m) == offsetof(artp_field_update_stats_t, m),            \
+                    offsetof(artp_field_shift_stats_t, m) == offsetof(artp_field_update_stats_t, m) &&          \
+                    offsetof(artp_field_clearance_shift_stats_t, m) == offsetof(artp_field_update_stats_t, m),  \
                 "the update stats structs share their first ten members");
 FIELD_STATS_PREFIX(FIELD_STATS_SAME_OFFSET)
 static_assert(sizeof(artp_field_update_stats_t) == 10 * sizeof(uint64_t), "ten members, and FIELD_STATS_PREFIX names them all");
@@ -1733,23 +1738,28 @@ int artp_field_update_stats(artp_field* f, artp_field_update_stats_t* out) {
   return ARTP_OK;
 }
 
-// DESIGN.md section 20.  Every refusal comes in front of the first write: the host's tests, then the moved sources
-// against new_mask on the device (field_update_sources_kernel on a copy of them), then field_update_run with the move in
-// front of its diff.
-int artp_field_shift(artp_field* f, const uint32_t* new_mask, int mask_on_device, int refresh_heights) {
-  if (!f || !new_mask) return ARTP_ERR_INVALID_ARG;
+}  // extern "C"
+
+namespace {
+
+// A move that passed field_shift_checks: (si, sj), the sources at their new places, new_mask on the device.
+struct FieldMove {
+  long long si = 0, sj = 0;
+  std::vector<int> moved;
+  const uint32_t* nm = nullptr;
+  bool moves() const { return si != 0 || sj != 0; }
+};
+
+// What artp_field_shift and artp_field_shift_clearance refuse behind the test of the field's kind, in front of the first
+// write: the host's tests, then the moved sources against new_mask on the device (field_update_sources_kernel on a copy of
+// them).  `who` is the entry point in the error.
+int field_shift_checks(artp_field* f, const char* who, const uint32_t* new_mask, int mask_on_device, FieldMove* mv) {
   artp_ctx* c = f->ctx;
-  std::lock_guard<std::recursive_mutex> lock(c->mu);
   const artp::FieldGrid& G = f->grid;
-  if (artp::field_has_wtab(G)) {
-    c->last_error = "artp_field_shift: a learned or a clearance-weighted field keeps a weight per node and move, which would "
-                    "have to move too: compute it anew on the new map";
-    return ARTP_ERR_INVALID_ARG;
-  }
   if (!reach_have_lattice(c)) return ARTP_ERR_NO_MAP;
   const MapGeom &a = f->geom, &b = c->geom;
   if (a.rows != b.rows || a.cols != b.cols || a.len_x != b.len_x || a.len_y != b.len_y || a.res != b.res) {
-    c->last_error = "artp_field_shift: the context's map differs from the field's in rows, cols, lengths or resolution";
+    c->last_error = std::string(who) + ": the context's map differs from the field's in rows, cols, lengths or resolution";
     return ARTP_ERR_INVALID_ARG;
   }
   // artp_preprocessed_change's convention: cell (i, j) of the new map lies over cell (i - si, j - sj) of the old one
@@ -1764,7 +1774,7 @@ int artp_field_shift(artp_field* f, const uint32_t* new_mask, int mask_on_device
     inside = moved[i] >= 0 && moved[i] < G.nrows && moved[i + 1] >= 0 && moved[i + 1] < G.ncols;
   }
   if (!inside) {
-    c->last_error = "artp_field_shift: a source leaves the rectangle with the map's move (the field is unchanged)";
+    c->last_error = std::string(who) + ": a source leaves the rectangle with the map's move (the field is unchanged)";
     return ARTP_ERR_INVALID_ARG;
   }
   HIP_TRY(c, hipSetDevice(c->device));
@@ -1787,60 +1797,103 @@ int artp_field_shift(artp_field* f, const uint32_t* new_mask, int mask_on_device
   HIP_TRY(c, hipMemcpyAsync(&gone, f->d_ucnt + 4, sizeof(gone), hipMemcpyDeviceToHost, st));
   HIP_TRY(c, hipStreamSynchronize(st));  // the host copy of the mask is free from here
   if (gone) {
-    c->last_error = "artp_field_shift: a moved source is not a node of new_mask (the field is unchanged)";
+    c->last_error = std::string(who) + ": a moved source is not a node of new_mask (the field is unchanged)";
     return ARTP_ERR_INVALID_ARG;
   }
-  const bool moves = si != 0 || sj != 0;
-  const artp::FieldShift sh{(int)si, (int)sj, si + sj * (long long)G.nrows};
+  mv->si = si;
+  mv->sj = sj;
+  mv->moved = std::move(moved);
+  mv->nm = nm;
+  return ARTP_OK;
+}
+
+// The move itself, as field_update_run's before(): the geometry and the sources adopted, then dist, hops, mask words,
+// heights and blocked words moved through scratch and copied back.  tm marks 0 and 1 around the device work of a move.
+int field_shift_move(artp_field* f, const FieldMove& mv, StreamTimer<2>& tm) {
+  artp_ctx* c = f->ctx;
+  hipStream_t st = c->lane->stream;
+  const artp::FieldGrid& G = f->grid;
+  f->geom = c->geom;
+  if (!mv.moves()) return ARTP_OK;
+  const artp::FieldShift sh{(int)mv.si, (int)mv.sj, mv.si + mv.sj * (long long)G.nrows};
   const size_t blk_words = (f->n_nodes + 1) / 2 * 2;  // field_blocked_alloc's
-  StreamTimer<2> tm(st);
+  ARTP_TRY(field_lazy(f, &f->d_shift, f->n_nodes * sizeof(uint32_t) + f->n_cells * 8 + blk_words * sizeof(uint16_t)));
+  uint32_t* hops_o = reinterpret_cast<uint32_t*>(f->d_shift);
+  uint32_t* mask_o = hops_o + f->n_nodes;
+  float* h_o = reinterpret_cast<float*>(mask_o + f->n_cells);
+  uint16_t* blk_o = reinterpret_cast<uint16_t*>(h_o + f->n_cells);
+  f->h_src = mv.moved;
+  HIP_TRY(c, hipMemcpyAsync(f->d_src, f->h_src.data(), f->h_src.size() * sizeof(int), hipMemcpyHostToDevice, st));
+  tm.mark(0);
+  hipLaunchKernelGGL(artp::field_shift_nodes_kernel, dim3((unsigned)((f->n_nodes + 255) / 256)), dim3(256), 0, st, G, sh,
+                     (const double*)f->d_dist, (const uint32_t*)f->d_hops, (const uint16_t*)f->d_blk, f->d_snap, hops_o,
+                     blk_o, f->d_ucnt);
+  hipLaunchKernelGGL(artp::field_shift_cells_kernel, dim3((unsigned)((f->n_cells + 255) / 256)), dim3(256), 0, st, G, sh,
+                     c->sampler, c->geom.rows, f->rect, (const uint32_t*)f->d_mask, (const float*)f->d_h, mask_o, h_o,
+                     f->d_acc, f->d_ucnt);
+  HIP_TRY(c, hipGetLastError());
+  // dist stays the buffer artp_field_dist_dev handed out
+  HIP_TRY(c, hipMemcpyAsync(f->d_dist, f->d_snap, f->n_nodes * sizeof(double), hipMemcpyDeviceToDevice, st));
+  HIP_TRY(c, hipMemcpyAsync(f->d_hops, hops_o, f->n_nodes * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+  HIP_TRY(c, hipMemcpyAsync(f->d_mask, mask_o, f->n_cells * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+  HIP_TRY(c, hipMemcpyAsync(f->d_h, h_o, f->n_cells * sizeof(float), hipMemcpyDeviceToDevice, st));
+  if (f->d_blk)
+    HIP_TRY(c, hipMemcpyAsync(f->d_blk, blk_o, f->n_nodes * sizeof(uint16_t), hipMemcpyDeviceToDevice, st));
+  tm.mark(1);
+  return ARTP_OK;
+}
+
+// The move's counts, in the kind's step: d_ucnt[5 .. 7] read into cnt (synchronises), the blocked moves that stayed
+// adopted, the shift's members of the stats filled.
+template <class Stats>
+int field_shift_counts(artp_field* f, const FieldMove& mv, StreamTimer<2>& tm, unsigned long long* cnt, Stats* us) {
+  artp_ctx* c = f->ctx;
+  hipStream_t st = c->lane->stream;
+  const artp::FieldGrid& G = f->grid;
+  if (mv.moves()) {
+    HIP_TRY(c, hipMemcpyAsync(cnt + 5, f->d_ucnt + 5, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    if (f->d_blk) {
+      us->dropped_blocked = f->n_blocked - cnt[7];
+      f->n_blocked = cnt[7];
+    }
+  }
+  const long long ai = mv.si < 0 ? -mv.si : mv.si, aj = mv.sj < 0 ? -mv.sj : mv.sj;
+  us->shift_rows = mv.si;
+  us->shift_cols = mv.sj;
+  us->kept_cells = (uint64_t)(G.nrows - ai) * (uint64_t)(G.ncols - aj);
+  us->left_nodes = cnt[5];
+  us->move_ms = tm.ms(0, 1, mv.moves());
+  return ARTP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// DESIGN.md section 20.  Every refusal comes in front of the first write (field_shift_checks), then field_update_run with
+// the move in front of its diff.
+int artp_field_shift(artp_field* f, const uint32_t* new_mask, int mask_on_device, int refresh_heights) {
+  if (!f || !new_mask) return ARTP_ERR_INVALID_ARG;
+  artp_ctx* c = f->ctx;
+  std::lock_guard<std::recursive_mutex> lock(c->mu);
+  const artp::FieldGrid& G = f->grid;
+  if (artp::field_has_wtab(G)) {
+    c->last_error = "artp_field_shift: a learned or a clearance-weighted field keeps a weight per node and move, which would "
+                    "have to move too: compute it anew on the new map (a clearance-weighted field: artp_field_shift_clearance)";
+    return ARTP_ERR_INVALID_ARG;
+  }
+  FieldMove mv;
+  ARTP_TRY(field_shift_checks(f, "artp_field_shift", new_mask, mask_on_device, &mv));
+  const artp::FieldSub whole{0, 0, G.nrows, G.ncols};
+  StreamTimer<2> tm(c->lane->stream);
   return field_update_run(
-      f, "artp_field_shift", nm, 1, whole, refresh_heights != 0, true, &f->shstats,
-      [&]() -> int {
-        f->geom = c->geom;
-        if (!moves) return ARTP_OK;
-        ARTP_TRY(field_lazy(f, &f->d_shift, f->n_nodes * sizeof(uint32_t) + f->n_cells * 8 + blk_words * sizeof(uint16_t)));
-        uint32_t* hops_o = reinterpret_cast<uint32_t*>(f->d_shift);
-        uint32_t* mask_o = hops_o + f->n_nodes;
-        float* h_o = reinterpret_cast<float*>(mask_o + f->n_cells);
-        uint16_t* blk_o = reinterpret_cast<uint16_t*>(h_o + f->n_cells);
-        f->h_src = moved;
-        HIP_TRY(c, hipMemcpyAsync(f->d_src, f->h_src.data(), f->h_src.size() * sizeof(int), hipMemcpyHostToDevice, st));
-        tm.mark(0);
-        hipLaunchKernelGGL(artp::field_shift_nodes_kernel, dim3((unsigned)((f->n_nodes + 255) / 256)), dim3(256), 0, st, G, sh,
-                           (const double*)f->d_dist, (const uint32_t*)f->d_hops, (const uint16_t*)f->d_blk, f->d_snap, hops_o,
-                           blk_o, f->d_ucnt);
-        hipLaunchKernelGGL(artp::field_shift_cells_kernel, dim3((unsigned)((f->n_cells + 255) / 256)), dim3(256), 0, st, G, sh,
-                           c->sampler, c->geom.rows, f->rect, (const uint32_t*)f->d_mask, (const float*)f->d_h, mask_o, h_o,
-                           f->d_acc, f->d_ucnt);
-        HIP_TRY(c, hipGetLastError());
-        // dist stays the buffer artp_field_dist_dev handed out
-        HIP_TRY(c, hipMemcpyAsync(f->d_dist, f->d_snap, f->n_nodes * sizeof(double), hipMemcpyDeviceToDevice, st));
-        HIP_TRY(c, hipMemcpyAsync(f->d_hops, hops_o, f->n_nodes * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
-        HIP_TRY(c, hipMemcpyAsync(f->d_mask, mask_o, f->n_cells * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
-        HIP_TRY(c, hipMemcpyAsync(f->d_h, h_o, f->n_cells * sizeof(float), hipMemcpyDeviceToDevice, st));
-        if (f->d_blk)
-          HIP_TRY(c, hipMemcpyAsync(f->d_blk, blk_o, f->n_nodes * sizeof(uint16_t), hipMemcpyDeviceToDevice, st));
-        tm.mark(1);
-        return ARTP_OK;
-      },
+      f, "artp_field_shift", mv.nm, 1, whole, refresh_heights != 0, true, &f->shstats,
+      [&]() -> int { return field_shift_move(f, mv, tm); },
       // the kind's step: the move's counts.  After a move the passes always run: the border may have lost its support.
       [&](unsigned long long* cnt, artp_field_shift_stats_t* us, bool* run) -> int {
-        if (moves) {
-          HIP_TRY(c, hipMemcpyAsync(cnt + 5, f->d_ucnt + 5, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-          HIP_TRY(c, hipStreamSynchronize(st));
-          if (f->d_blk) {
-            us->dropped_blocked = f->n_blocked - cnt[7];
-            f->n_blocked = cnt[7];
-          }
-        }
-        const long long ai = si < 0 ? -si : si, aj = sj < 0 ? -sj : sj;
-        us->shift_rows = si;
-        us->shift_cols = sj;
-        us->kept_cells = (uint64_t)(G.nrows - ai) * (uint64_t)(G.ncols - aj);
-        us->left_nodes = cnt[5];
-        us->move_ms = tm.ms(0, 1, moves);
-        *run = moves || cnt[0] || cnt[3];
+        ARTP_TRY(field_shift_counts(f, mv, tm, cnt, us));
+        *run = mv.moves() || cnt[0] || cnt[3];
         return ARTP_OK;
       });
 }

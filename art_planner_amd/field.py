@@ -205,6 +205,25 @@ class CostField:
         """The numbers of the last shift that succeeded (zeros before the first)."""
         return self._stats(_capi.FieldShiftStats, self.L.artp_field_shift_stats, "artp_field_shift_stats")
 
+    def shift_clearance(self, mask, refresh_heights=True) -> dict:
+        """shift() for a clearance-weighted field (artp_field_shift_clearance): the move of shift(),
+        the clearance map computed again over the whole rectangle, every weight priced again against the one its node
+        carried across the move, then the passes from the tiles where a weight or the mask changed.  mask and
+        refresh_heights as in shift().  The same bits -- dist, paths, clearance(), edge_costs -- as a new
+        clearance_cost_field on the new map with the field's own parameters, the moved sources and the blocked moves that
+        stayed inside.  The first call that moves allocates a second weight table and keeps it.  Any other field is
+        refused.  Returns the shift's stats."""
+        mask_ptr, on_device, keep = self._mask_arg(mask, "CostField.shift_clearance")
+        self.ctx._chk(self.L.artp_field_shift_clearance(self.h, mask_ptr, on_device, int(bool(refresh_heights))),
+                      "artp_field_shift_clearance")
+        del keep
+        return self.clearance_shift_stats()
+
+    def clearance_shift_stats(self) -> dict:
+        """The numbers of the last shift_clearance that succeeded (zeros before the first)."""
+        return self._stats(_capi.FieldClearanceShiftStats, self.L.artp_field_clearance_shift_stats,
+                           "artp_field_clearance_shift_stats")
+
     def _update(self, call, name, mask, rect, *extra):
         """The mask and rect handling the three updates share; call = the C entry point artp_field_<name>.  mask None
         (update_learned only): no mask and no rect go down."""

@@ -518,6 +518,19 @@ class Planner {
     });
   }
 
+  // The field a computeClearanceCostField call kept, carried across a move of the map by whole cells
+  // (artp_field_shift_clearance, include/artp_c.h): shiftCostField for the clearance-weighted field.  The clearance map is
+  // computed again on the new map and every move priced again against the weight its node carried across the move.  mask
+  // and refresh_heights as shiftCostField takes them.  The same bits as computeClearanceCostField with the field's own
+  // parameters on the new map with the sources moved.  Throws, with the field unchanged, where shiftCostField throws and
+  // for any field that is not clearance-weighted.  The first call that moves keeps a second weight table as large as the
+  // field's own.  Returns dist and refreshes the "cost_to_go" layer.
+  std::vector<double> shiftClearanceCostField(artp_field* kept, const std::vector<uint32_t>& mask,
+                                              bool refresh_heights = true) {
+    return updateKeptField("shiftClearanceCostField", "artp_field_shift_clearance", kept, mask, false,
+                           [&] { return artp_field_shift_clearance(kept, mask.data(), 0, refresh_heights ? 1 : 0); });
+  }
+
   // The field a computeLearnedCostField call kept, brought in place to the device's current state
   // (artp_field_update_learned, include/artp_c.h): every move priced again by the loaded network on the cost map of the
   // last artp_cost_update_map*, and the mask edited as updateCostField edits it (an empty mask = the mask did not change;

@@ -612,7 +612,7 @@ int artp_field_clearance_update_stats(artp_field* f, artp_field_clearance_update
  * Refused with NOTHING written (dist, hops, mask, heights, blocked moves, geometry, sources and all stats stay):
  * ARTP_ERR_INVALID_ARG, with a text in artp_last_error, when the context's map differs from the field's in rows, cols,
  * lengths or resolution, for a learned or a clearance-weighted field (their per-field tables would have to move too:
- * compute them anew), when a moved source lies outside the rectangle (no overlap at all included) or is not a node of
+ * compute a learned field anew, artp_field_shift_clearance below takes the other), when a moved source lies outside the rectangle (no overlap at all included) or is not a node of
  * new_mask, when f or new_mask is NULL; ARTP_ERR_NO_MAP without sampler layers.  A failure after those checks
  * (ARTP_ERR_HIP, ARTP_ERR_CAPACITY) leaves the field UNDEFINED: destroy it.  The first shift allocates its scratch (12
  * bytes a node, 8 a cell) and keeps it.  Synchronous, on the context's current stream. */
@@ -630,6 +630,44 @@ typedef struct artp_field_shift_stats_t {
 int artp_field_shift(artp_field* f, const uint32_t* new_mask, int mask_on_device, int refresh_heights);
 /* the numbers of the last artp_field_shift that returned ARTP_OK (zeros before the first) */
 int artp_field_shift_stats(artp_field* f, artp_field_shift_stats_t* out);
+
+/* ---- A clearance-weighted field carried across a map move ---------------------------------
+ * artp_field_shift for a field of artp_field_compute_clearance.  Everything said above holds: the shift convention (si, sj),
+ * new_mask, the heights and refresh_heights, the blocked moves, and the adoption of the context's sampler layers, map
+ * version and geometry.  Behind the move and the diff against new_mask, d2 is computed again over the whole rectangle (after
+ * a move the mask changes all round the border), and every slot of the weight table is priced on the new state into a
+ * SECOND table, against the weight its own node carried for the same move before the move (+inf where that node's old cell
+ * lay outside the rectangle: an entered cell had no edge).  A slot whose bit pattern differs flags its tile, and the passes
+ * of artp_field_update run from the flagged tiles.
+ * After ARTP_OK dist, hops (artp_field_path), artp_field_clearance, artp_field_edge_costs (every slot) and reached_nodes are
+ * bit for bit those of artp_field_compute_clearance on the new map with new_mask, the field's own params, n_yaw, rectangle
+ * and reverse, its sources moved by (si, sj) and the blocked moves it kept.  artp_field_dist_dev keeps its buffer.
+ * si = sj = 0 is artp_field_update_clearance with sub_rect = NULL: the same result and the same shared counts, and no new
+ * allocation.  The first call that moves allocates the second table (80 n_yaw bytes a cell of the padded rectangle, as
+ * large as the first) next to the scratch of artp_field_shift, and keeps both until artp_field_destroy; the two tables
+ * change roles with every move.
+ * Refused with NOTHING written: ARTP_ERR_INVALID_ARG, with a text in artp_last_error, for a field that is not
+ * clearance-weighted, and for everything artp_field_shift refuses, for the same reasons (another map size, lengths or
+ * resolution; a moved source outside the rectangle or not a node of new_mask; f or new_mask NULL); ARTP_ERR_NO_MAP without
+ * sampler layers.  A failure after those checks leaves the field UNDEFINED: destroy it.  Synchronous, on the context's
+ * current stream. */
+typedef struct artp_field_clearance_shift_stats_t {
+  uint64_t changed_words, removed_nodes, added_nodes, dead_nodes, hop_dead_nodes, unsupport_rounds, dist_rounds,
+      hop_rounds, tile_launches, reached_nodes; /* as artp_field_shift_stats_t */
+  int64_t shift_rows, shift_cols;
+  uint64_t kept_cells, left_nodes, dropped_blocked; /* as artp_field_shift_stats_t */
+  uint64_t changed_slots; /* slots of the new table whose bit pattern differs from the slot of the same node (the slot's own
+                             node: the move's target in a forward field, its origin in a reverse one) and move before the
+                             move; a slot whose old cell lay outside the rectangle had +inf */
+  uint64_t weight_tiles;  /* tiles flagged by such a slot */
+  double move_ms;         /* stream time of the move */
+  double clearance_ms;    /* stream time of d2 over the whole rectangle */
+  double table_ms;        /* stream time of the table kernel */
+  double passes_ms;       /* host time of the four passes */
+} artp_field_clearance_shift_stats_t;
+int artp_field_shift_clearance(artp_field* f, const uint32_t* new_mask, int mask_on_device, int refresh_heights);
+/* the numbers of the last artp_field_shift_clearance that returned ARTP_OK (zeros before the first) */
+int artp_field_clearance_shift_stats(artp_field* f, artp_field_clearance_shift_stats_t* out);
 
 /* ---- ob::MotionValidator::checkMotion (OMPL DiscreteMotionValidator; call sites
  *      prm_motion_cost.cpp:652, lazy_prm_star_min_update.cpp:725), batched -----------------------
