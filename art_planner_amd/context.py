@@ -256,6 +256,30 @@ class Context:
                          max_lon_vel=max_lon_vel, max_lat_vel=max_lat_vel, max_ang_vel=max_ang_vel,
                          plain_sweeps=plain_sweeps, inner_sweeps=inner_sweeps)
 
+    def cost_fields(self, mask, n_yaw, sources_list, *, rect=None, reverse=False, objective=1, max_lon_vel=0.5,
+                    max_lat_vel=0.1, max_ang_vel=0.5, plain_sweeps=False, inner_sweeps=64) -> list:
+        """One cost_field per source set of sources_list, all searched side by side in one batched call
+        (artp_field_compute_many): every round is one launch over all the fields and one read of
+        their counters.  Field b holds the bits of cost_field(mask, n_yaw, sources_list[b], ...).  Returns a list of
+        CostField; each is updated, shifted, planned on and closed on its own.  Objectives 0 and 1 in the tiled form only
+        (plain_sweeps=True is refused); one bad source refuses the whole call and names its set."""
+        from .field import CostField
+        return CostField.many(self, mask, n_yaw, sources_list, rect=rect, reverse=reverse, objective=objective,
+                              max_lon_vel=max_lon_vel, max_lat_vel=max_lat_vel, max_ang_vel=max_ang_vel,
+                              plain_sweeps=plain_sweeps, inner_sweeps=inner_sweeps)
+
+    def cost_matrix(self, mask, n_yaw, poses, batch=None, *, rect=None, objective=1, max_lon_vel=0.5, max_lat_vel=0.1,
+                    max_ang_vel=0.5, inner_sweeps=64, return_stats=False):
+        """(N, N) float64: M[i, j] = the cost from pose i to pose j ((r, c, k) triples), the forward cost_field of pose i
+        read at pose j: +inf where unreachable, 0 on the diagonal (artp_field_cost_matrix).  The N fields are computed in
+        batched groups of at most `batch` (None: as many as fit in half of the free device memory) and freed group by
+        group.  M is not symmetric bit for bit.  return_stats=True: (M, the call's stats)."""
+        from .field import CostField
+        m, st = CostField.matrix(self, mask, n_yaw, poses, batch=batch, rect=rect, objective=objective,
+                                 max_lon_vel=max_lon_vel, max_lat_vel=max_lat_vel, max_ang_vel=max_ang_vel,
+                                 inner_sweeps=inner_sweeps)
+        return (m, st) if return_stats else m
+
     def learned_cost_field(self, mask, n_yaw, sources, *, rect=None, reverse=False, w_energy=None, w_time=None,
                            w_risk=None, risk_threshold=None, plain_sweeps=False, inner_sweeps=64):
         """cost_field under the learned motion cost (artp_field_compute_learned): every lattice

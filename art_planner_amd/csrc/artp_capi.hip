@@ -3511,6 +3511,7 @@ int artp_cost_get_features(artp_ctx* c, float* out, int* fh, int* fw) {
 #include "roadmap_many.h"
 #include "reach.h"
 #include "field.h"
+#include "field_many.h"
 #include "clearance.h"
 #include "field_plan.h"
 #include "field_simplify.h"

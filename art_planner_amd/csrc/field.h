@@ -29,7 +29,10 @@
 //                through field_tile_walk) until nothing changes or inner_sweeps are spent; the tile writes its own
 //                cells back (plain vector stores; the halo is read-only), flags the neighbouring tiles whose halo it
 //                changed for the next launch, and itself when it ran out of sweeps.  A launch covers every tile; the
-//                ones nobody flagged leave at once.
+//                ones nobody flagged leave at once.  The skeleton's body is one function, field_tile_body, of the tile
+//                index and the per-field pointers; field_tile_many_kernel<PHASE> runs it (relax, (m, k) table) on a grid of
+//                (tiles, fields) for a batch of fields that share mask, heights and table (field_many.h, DESIGN.md
+//                section 23).
 // field_rounds is the host loop of both forms: launch, read the counters, stop when nothing was flagged, refuse after
 // n_nodes + 2 rounds.  No launch waits for another workgroup and no kernel stays resident.
 //
@@ -387,14 +390,15 @@ __device__ __forceinline__ bool field_tile_rule(const FieldGrid& G, const FieldL
 // LEARNED (objectives 2 and 3): tabg is the weight table.  It is streamed from global memory, not staged: at 16 headings a tile's
 // weights are 328 KB.  The ten loads of a heading are issued in front of that heading's LDS reads.
 // blk (may be nullptr): the blocked words, streamed the same way: one 16-bit load per lane and heading in front of the rule.
-template <int PHASE, bool UNSUP, bool LEARNED = false>
-__global__ void __launch_bounds__(256)
-field_tile_kernel(FieldGrid G, const uint32_t* __restrict__ mask, const float* __restrict__ h,
-                  const double* __restrict__ tabg, const uint16_t* __restrict__ blk, double* dist, uint32_t* hops,
-                  unsigned* act_cur, unsigned* act_nxt, unsigned* acc, unsigned* __restrict__ counters, int inner_max) {
+// The body is one function, field_tile_body, of the tile index and the per-field pointers; two kernels call it:
+// field_tile_kernel (one field, grid = its tiles) and field_tile_many_kernel (a batch of fields).
+template <int PHASE, bool UNSUP, bool LEARNED>
+__device__ __forceinline__ void
+field_tile_body(const FieldGrid& G, const int tile, const uint32_t* __restrict__ mask, const float* __restrict__ h,
+                const double* __restrict__ tabg, const uint16_t* __restrict__ blk, double* dist, uint32_t* hops,
+                unsigned* act_cur, unsigned* act_nxt, unsigned* acc, unsigned* __restrict__ counters, int inner_max) {
   constexpr bool HOPS = PHASE == 1 || UNSUP;  // hop planes in LDS
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tile = blockIdx.x;
   if (!act_cur[tile]) return;  // nobody writes act_cur in this launch before the barrier below: uniform
   const int ny = G.n_yaw;
   double* sd = reinterpret_cast<double*>(smem);
@@ -502,6 +506,47 @@ field_tile_kernel(FieldGrid G, const uint32_t* __restrict__ mask, const float* _
     if (UNSUP && sflag[1]) atomicAdd(&counters[2], sflag[1]);
     act_cur[tile] = 0u;  // every lane read it in front of the first barrier
   }
+}
+
+template <int PHASE, bool UNSUP, bool LEARNED = false>
+__global__ void __launch_bounds__(256)
+field_tile_kernel(FieldGrid G, const uint32_t* __restrict__ mask, const float* __restrict__ h,
+                  const double* __restrict__ tabg, const uint16_t* __restrict__ blk, double* dist, uint32_t* hops,
+                  unsigned* act_cur, unsigned* act_nxt, unsigned* acc, unsigned* __restrict__ counters, int inner_max) {
+  field_tile_body<PHASE, UNSUP, LEARNED>(G, (int)blockIdx.x, mask, h, tabg, blk, dist, hops, act_cur, act_nxt, acc, counters,
+                                         inner_max);
+}
+
+// What a field of a batch brings of its own (artp_field_compute_many): the mask, the heights, the (m, k) table and the
+// grid are the batch's.  flags: the field's two arrays of n_tiles words; counters: its four words of the call's block.
+struct FieldSlot {
+  double* dist;
+  uint32_t* hops;
+  unsigned* flags;
+  unsigned* counters;
+};
+
+// The relax rule of PHASE on a batch of fields: grid (n_tiles, n_sets), blockIdx.y picks the slot.  parity: which of the
+// slot's two flag arrays is this round's (the other collects the next round's).  A tile flags tiles of its own field only:
+// every flag it writes goes through its slot's pointers.
+template <int PHASE>
+__global__ void __launch_bounds__(256)
+field_tile_many_kernel(FieldGrid G, const uint32_t* __restrict__ mask, const float* __restrict__ h,
+                       const double* __restrict__ tabg, const FieldSlot* __restrict__ slots, int parity, int inner_max) {
+  const FieldSlot s = slots[blockIdx.y];
+  const size_t n_tiles = (size_t)G.tiles_r * (size_t)G.tiles_c;
+  field_tile_body<PHASE, false, false>(G, (int)blockIdx.x, mask, h, tabg, nullptr, s.dist, s.hops,
+                                       s.flags + (parity ? n_tiles : 0), s.flags + (parity ? 0 : n_tiles), nullptr, s.counters,
+                                       inner_max);
+}
+
+// out[b n + j] = the distance of field b at node nodes[j] (artp_field_cost_matrix): grid (ceil(n / 256), n_sets)
+__global__ void __launch_bounds__(256)
+field_gather_kernel(const FieldSlot* __restrict__ slots, const uint32_t* __restrict__ nodes, uint32_t n,
+                    double* __restrict__ out) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  out[(size_t)blockIdx.y * n + j] = slots[blockIdx.y].dist[nodes[j]];
 }
 
 __global__ void __launch_bounds__(256)
@@ -1462,6 +1507,8 @@ int field_check_params(artp_ctx* c, const artp_field_params& p) {
 int field_create(artp_ctx* c, const artp_field_params& params, const artp_field_learned_params* lp,
                  const artp_field_clearance_params* cp, const artp::ReachRect& r, const uint32_t* mask, int mask_on_device,
                  const int* sources, size_t n_sources, int reverse, artp_field** out);
+artp_field* field_new(artp_ctx* c, const artp_field_params& params, const artp_field_learned_params* lp,
+                      const artp_field_clearance_params* cp, const artp::ReachRect& r, int reverse);
 
 }  // namespace
 
@@ -1560,12 +1607,25 @@ int artp_field_learned_stats(artp_field* f, artp_field_learned_stats_t* out) {
 namespace {
 
 // the part of artp_field_compute, _learned and _clearance behind their checks (lp: objective 2 only; cp: the clearance
-// field, params = its base objective's)
+// field, params = its base objective's); artp_field_compute_many (field_many.h) makes its fields with field_new
 int field_create(artp_ctx* c, const artp_field_params& params, const artp_field_learned_params* lp,
                  const artp_field_clearance_params* cp, const artp::ReachRect& r, const uint32_t* mask, int mask_on_device,
                  const int* sources, size_t n_sources, int reverse, artp_field** out) {
-  const int n_yaw = r.n_yaw;
   HIP_TRY(c, hipSetDevice(c->device));
+  artp_field* f = field_new(c, params, lp, cp, r, reverse);
+  const int rc = field_compute_impl(c, f, mask, mask_on_device, sources, n_sources);
+  if (rc) {
+    field_free(f);
+    return rc;
+  }
+  *out = f;
+  return ARTP_OK;
+}
+
+// a field of the rectangle with its grid and sizes, and no device memory yet
+artp_field* field_new(artp_ctx* c, const artp_field_params& params, const artp_field_learned_params* lp,
+                      const artp_field_clearance_params* cp, const artp::ReachRect& r, int reverse) {
+  const int n_yaw = r.n_yaw;
   artp_field* f = new artp_field;
   f->ctx = c;
   f->params = params;
@@ -1591,13 +1651,7 @@ int field_create(artp_ctx* c, const artp_field_params& params, const artp_field_
   f->n_tiles = (size_t)G.tiles_r * G.tiles_c;
   f->stats.nodes = f->n_nodes;
   f->stats.tiles = f->n_tiles;
-  const int rc = field_compute_impl(c, f, mask, mask_on_device, sources, n_sources);
-  if (rc) {
-    field_free(f);
-    return rc;
-  }
-  *out = f;
-  return ARTP_OK;
+  return f;
 }
 
 }  // namespace

@@ -8,15 +8,34 @@ import numpy as np
 from . import _capi
 
 
+def _field_params(ctx, objective, plain_sweeps, inner_sweeps, max_lon_vel, max_lat_vel, max_ang_vel):
+    """artp_field_params from the keywords cost_field, cost_fields and cost_matrix share."""
+    p = _capi.FieldParams()
+    ctx.L.artp_field_params_defaults(C.byref(p))
+    p.objective, p.plain_sweeps, p.inner_sweeps = int(objective), int(bool(plain_sweeps)), int(inner_sweeps)
+    p.max_lon_vel, p.max_lat_vel, p.max_ang_vel = max_lon_vel, max_lat_vel, max_ang_vel
+    return p
+
+
+def _mask_arg(mask, nr, nc, what):
+    """(pointer, on_device, the object that owns the memory) of a mask of an nr x nc rectangle."""
+    if hasattr(mask, "data_ptr"):   # a device tensor of nrows * ncols 32-bit words, column-major
+        if mask.numel() * mask.element_size() < nr * nc * 4:
+            raise _capi.ArtpError(f"{what}: the mask tensor holds fewer than nrows * ncols words")
+        return mask.data_ptr(), 1, mask
+    m = np.asarray(mask)
+    if m.shape != (nr, nc):
+        raise _capi.ArtpError(f"{what}: the mask is {m.shape}, the rectangle ({nr}, {nc})")
+    keep = np.asfortranarray(m, dtype=np.uint32)
+    return keep.ctypes.data, 0, keep
+
+
 class CostField:
     """One computed field.  Nodes are (r, c, k) triples, r and c local to the rectangle."""
 
     def __init__(self, ctx, mask, n_yaw, sources, rect=None, reverse=False, objective=1, max_lon_vel=0.5,
                  max_lat_vel=0.1, max_ang_vel=0.5, plain_sweeps=False, inner_sweeps=64):
-        p = _capi.FieldParams()
-        ctx.L.artp_field_params_defaults(C.byref(p))
-        p.objective, p.plain_sweeps, p.inner_sweeps = int(objective), int(bool(plain_sweeps)), int(inner_sweeps)
-        p.max_lon_vel, p.max_lat_vel, p.max_ang_vel = max_lon_vel, max_lat_vel, max_ang_vel
+        p = _field_params(ctx, objective, plain_sweeps, inner_sweeps, max_lon_vel, max_lat_vel, max_ang_vel)
         self._compute(ctx, ctx.L.artp_field_compute, "artp_field_compute", p, mask, n_yaw, sources, rect, reverse)
 
     @classmethod
@@ -53,6 +72,50 @@ class CostField:
                       reverse)
         return self
 
+    @classmethod
+    def adopt(cls, ctx, handle, nrows, ncols, n_yaw, reverse=False):
+        """The CostField of a handle the library gave out already (a field of artp_field_compute_many): the object owns
+        it from here on and closes it like any other."""
+        self = cls.__new__(cls)
+        self.ctx, self.L = ctx, ctx.L
+        self.nrows, self.ncols, self.n_yaw, self.reverse = int(nrows), int(ncols), int(n_yaw), bool(reverse)
+        self.h = handle if isinstance(handle, C.c_void_p) else C.c_void_p(handle)
+        return self
+
+    @classmethod
+    def many(cls, ctx, mask, n_yaw, sources_list, rect=None, reverse=False, objective=1, max_lon_vel=0.5,
+             max_lat_vel=0.1, max_ang_vel=0.5, plain_sweeps=False, inner_sweeps=64) -> list:
+        """One CostField per source set, computed in one batched search (artp_field_compute_many)."""
+        p = _field_params(ctx, objective, plain_sweeps, inner_sweeps, max_lon_vel, max_lat_vel, max_ang_vel)
+        r, nr, nc = ctx._reach_rect(rect)
+        mask_ptr, on_device, keep = _mask_arg(mask, nr, nc, "cost_fields")
+        sets = [np.ascontiguousarray(s, np.int32).reshape(-1, 3) for s in sources_list]
+        off = np.zeros(len(sets) + 1, np.uint64)
+        off[1:] = np.cumsum([len(s) for s in sets])
+        src = np.concatenate(sets) if sets and int(off[-1]) else np.zeros((1, 3), np.int32)
+        handles = (C.c_void_p * max(len(sets), 1))()
+        ctx._chk(ctx.L.artp_field_compute_many(ctx.h, C.byref(p), int(n_yaw), r.ctypes.data if r is not None else None,
+                                               mask_ptr, on_device, src.ctypes.data, off.ctypes.data, len(sets),
+                                               int(bool(reverse)), handles), "artp_field_compute_many")
+        del keep
+        return [cls.adopt(ctx, handles[b], nr, nc, n_yaw, reverse) for b in range(len(sets))]
+
+    @staticmethod
+    def matrix(ctx, mask, n_yaw, poses, batch=None, rect=None, objective=1, max_lon_vel=0.5, max_lat_vel=0.1,
+               max_ang_vel=0.5, inner_sweeps=64):
+        """((n, n) float64 costs from pose i to pose j, the call's stats) of artp_field_cost_matrix."""
+        p = _field_params(ctx, objective, False, inner_sweeps, max_lon_vel, max_lat_vel, max_ang_vel)
+        r, nr, nc = ctx._reach_rect(rect)
+        mask_ptr, on_device, keep = _mask_arg(mask, nr, nc, "cost_matrix")
+        t = np.ascontiguousarray(poses, np.int32).reshape(-1, 3)
+        out = np.empty((len(t), len(t)), np.float64)
+        st = _capi.FieldManyStats()
+        ctx._chk(ctx.L.artp_field_cost_matrix(ctx.h, C.byref(p), int(n_yaw), r.ctypes.data if r is not None else None,
+                                              mask_ptr, on_device, t.ctypes.data, len(t), int(batch or 0),
+                                              out.ctypes.data, C.byref(st)), "artp_field_cost_matrix")
+        del keep
+        return out, {n: int(getattr(st, n)) for n, _ in _capi.FieldManyStats._fields_}
+
     def _compute(self, ctx, call, name, params, mask, n_yaw, sources, rect, reverse):
         """The mask and source handling both constructors share; call = the C entry point, params = its struct."""
         self.ctx = ctx
@@ -70,16 +133,7 @@ class CostField:
 
     def _mask_arg(self, mask, what):
         """(pointer, on_device, the object that owns the memory) of a mask of the field's rectangle."""
-        nr, nc = self.nrows, self.ncols
-        if hasattr(mask, "data_ptr"):   # a device tensor of nrows * ncols 32-bit words, column-major
-            if mask.numel() * mask.element_size() < nr * nc * 4:
-                raise _capi.ArtpError(f"{what}: the mask tensor holds fewer than nrows * ncols words")
-            return mask.data_ptr(), 1, mask
-        m = np.asarray(mask)
-        if m.shape != (nr, nc):
-            raise _capi.ArtpError(f"{what}: the mask is {m.shape}, the rectangle ({nr}, {nc})")
-        keep = np.asfortranarray(m, dtype=np.uint32)
-        return keep.ctypes.data, 0, keep
+        return _mask_arg(mask, self.nrows, self.ncols, what)
 
     def close(self):
         if self.h:

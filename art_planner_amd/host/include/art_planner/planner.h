@@ -374,13 +374,7 @@ class Planner {
     const auto g = map_->getGeometry();
     const size_t cells = static_cast<size_t>(g.rows) * g.cols;
     if (mask.size() != cells) throw std::runtime_error("computeCostField: the mask does not have rows * cols words");
-    artp_field_params fp;
-    artp_field_params_defaults(&fp);
-    const auto& cpl = params_->objectives.custom_path_length;
-    fp.objective = cpl.use_directional_cost ? 1 : 0;
-    fp.max_lon_vel = cpl.max_lon_vel;
-    fp.max_lat_vel = cpl.max_lat_vel;
-    fp.max_ang_vel = cpl.max_ang_vel;
+    const artp_field_params fp = costFieldParams();
     std::vector<int> src;
     for (const auto& s : sources) src.insert(src.end(), s.begin(), s.end());
     artp_field* f = nullptr;
@@ -389,6 +383,62 @@ class Planner {
                                     sources.size(), reverse ? 1 : 0, &f),
                  "artp_field_compute");
     return finishCostField(f, cells, n_yaw, keep);
+  }
+
+  // computeCostField for many source sets at once (artp_field_compute_many, include/artp_c.h): one field per set, all
+  // searched side by side in one batched call; field b holds the bits of computeCostField(mask, n_yaw, source_sets[b]).
+  // Returns the kept fields, one per set: each works with artp_field_dist, artp_field_path, updateCostField,
+  // planOnCostField and the rest on its own, and the caller destroys each (artp_field_destroy).  One bad source refuses
+  // the whole call (the exception names its set) and leaves nothing allocated.  The "cost_to_go" layer is not touched:
+  // it holds one field.
+  std::vector<artp_field*> computeCostFields(const std::vector<uint32_t>& mask, unsigned n_yaw,
+                                             const std::vector<std::vector<std::array<int, 3>>>& source_sets,
+                                             bool reverse = false) {
+    std::lock_guard<std::mutex> lock(map_mutex_);
+    if (!map_) throw std::runtime_error("computeCostFields: the planner does not have a map set");
+    const auto g = map_->getGeometry();
+    if (mask.size() != static_cast<size_t>(g.rows) * g.cols)
+      throw std::runtime_error("computeCostFields: the mask does not have rows * cols words");
+    const artp_field_params fp = costFieldParams();
+    std::vector<int> src;
+    std::vector<uint64_t> off(1, 0);
+    for (const auto& set : source_sets) {
+      for (const auto& s : set) src.insert(src.end(), s.begin(), s.end());
+      off.push_back(src.size() / 3);
+    }
+    if (src.empty()) src.resize(3, 0);   // a pointer the library can refuse the empty call behind
+    std::vector<artp_field*> fields(std::max<size_t>(source_sets.size(), 1), nullptr);
+    throwOnError(gpu_->get(),
+                 artp_field_compute_many(gpu_->get(), &fp, static_cast<int>(n_yaw), nullptr, mask.data(), 0, src.data(),
+                                         off.data(), source_sets.size(), reverse ? 1 : 0, fields.data()),
+                 "artp_field_compute_many");
+    fields.resize(source_sets.size());
+    return fields;
+  }
+
+  // Pose-to-pose costs (artp_field_cost_matrix, include/artp_c.h): entry i * n + j = the cost from poses[i] to poses[j],
+  // the forward field of pose i read at pose j; +inf where unreachable, 0 on the diagonal, bit for bit
+  // computeCostField's values.  The n fields are computed in batched groups of at most `batch` (0: as many as fit in
+  // half of the free device memory) and freed group by group.  stats (may be null): groups, fields, rounds, tile runs.
+  std::vector<double> computeCostMatrix(const std::vector<uint32_t>& mask, unsigned n_yaw,
+                                        const std::vector<std::array<int, 3>>& poses, size_t batch = 0,
+                                        artp_field_many_stats_t* stats = nullptr) {
+    std::lock_guard<std::mutex> lock(map_mutex_);
+    if (!map_) throw std::runtime_error("computeCostMatrix: the planner does not have a map set");
+    const auto g = map_->getGeometry();
+    if (mask.size() != static_cast<size_t>(g.rows) * g.cols)
+      throw std::runtime_error("computeCostMatrix: the mask does not have rows * cols words");
+    const artp_field_params fp = costFieldParams();
+    std::vector<int> p;
+    for (const auto& s : poses) p.insert(p.end(), s.begin(), s.end());
+    if (p.empty()) p.resize(3, 0);
+    std::vector<double> matrix(std::max<size_t>(poses.size() * poses.size(), 1));
+    throwOnError(gpu_->get(),
+                 artp_field_cost_matrix(gpu_->get(), &fp, static_cast<int>(n_yaw), nullptr, mask.data(), 0, p.data(),
+                                        poses.size(), batch, matrix.data(), stats),
+                 "artp_field_cost_matrix");
+    matrix.resize(poses.size() * poses.size());
+    return matrix;
   }
 
   // computeCostField under the learned motion cost (artp_field_compute_learned, include/artp_c.h): every lattice move is
@@ -859,6 +909,18 @@ class Planner {
     }
     map_->addLayer("cost_to_go", best.data());
     return dist;
+  }
+
+  // artp_field_params of Params::objectives.custom_path_length (computeCostField, computeCostFields, computeCostMatrix)
+  artp_field_params costFieldParams() const {
+    artp_field_params fp;
+    artp_field_params_defaults(&fp);
+    const auto& cpl = params_->objectives.custom_path_length;
+    fp.objective = cpl.use_directional_cost ? 1 : 0;
+    fp.max_lon_vel = cpl.max_lon_vel;
+    fp.max_lat_vel = cpl.max_lat_vel;
+    fp.max_ang_vel = cpl.max_ang_vel;
+    return fp;
   }
 
   // the tail of both computeCostField calls: dist out of the field, the field kept or destroyed, the layer refreshed

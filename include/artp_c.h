@@ -669,6 +669,45 @@ int artp_field_shift_clearance(artp_field* f, const uint32_t* new_mask, int mask
 /* the numbers of the last artp_field_shift_clearance that returned ARTP_OK (zeros before the first) */
 int artp_field_clearance_shift_stats(artp_field* f, artp_field_clearance_shift_stats_t* out);
 
+/* ---- Many fields in one batched search; pose-to-pose cost matrices -------------
+ * artp_field_compute_many: n_sets fields over ONE mask, rectangle, params and direction, one per source set, searched
+ * side by side: every round is one launch over (tiles, fields) and one host read of all the fields' counters.  sources
+ * holds the triples of all sets one after the other; set b is triples set_offsets[b] .. set_offsets[b + 1] - 1
+ * (set_offsets: n_sets + 1 entries, set_offsets[0] = 0, strictly increasing).  out_fields receives n_sets ordinary fields:
+ * field b is bit for bit -- dist, hop counts (so paths), edge costs, reached_nodes -- what artp_field_compute gives for
+ * set b alone.  Each owns its own copies of the mask, the heights, the table and the flags: artp_field_update, _shift,
+ * _block_moves, _plan, _simplify_paths, _path and _destroy work on each one alone, and each is destroyed by the caller.
+ * artp_field_stats of field b: outer_rounds / hop_rounds = the rounds of the batch until that field went quiet,
+ * tile_launches / hop_tile_launches = its own tile runs, reached_nodes its own.
+ * ARTP_ERR_INVALID_ARG, with a text in artp_last_error, every out_fields[b] = NULL and nothing left allocated: everything
+ * artp_field_compute refuses (objective 2 included: learned and clearance-weighted fields have no batched form); n_sets
+ * of 0 or above 65535; an empty set; offsets that do not increase; plain_sweeps != 0 (the batch runs in the tiled form
+ * only); a source that is no node of the mask (the text names the index of its set), before any search runs.
+ * ARTP_ERR_CAPACITY, with a text, when hipMemGetInfo shows less free memory than the n_sets fields need (12 bytes per
+ * node and cell-sized arrays each).  The round cap is artp_field_compute's.  Synchronous, on the current lane's stream;
+ * the call writes no state of the context.
+ * artp_field_cost_matrix: matrix_out[i n + j] (n * n doubles on the host) = the cost from pose i to pose j (n triples
+ * (r, c, k)), i.e. dist of the forward field of pose i read at pose j: +inf where j cannot be reached from i, 0 on the
+ * diagonal, bit for bit artp_field_compute's value.  Not symmetric bit for bit: the two folds run from opposite ends.
+ * The fields are computed in groups of at most `batch` (0: the largest group that fits in half of the free device
+ * memory), each group's n values per field gathered on the device and read back in one copy, its fields freed before
+ * the next group starts.  Both passes run (distances and hop counts).  Refusals as above (a pose that is no node of the
+ * mask: the text names the pose), and n of 0 or above 65536.  stats_out may be NULL. */
+typedef struct artp_field_many_stats_t {
+  uint64_t groups;        /* batched searches */
+  uint64_t fields;        /* fields computed: n */
+  uint64_t dist_rounds;   /* launches of the distance search, summed over the groups */
+  uint64_t hop_rounds;    /* launches of the hop-count search, summed over the groups */
+  uint64_t tile_runs;     /* tiles that ran in the distance searches, all fields */
+  uint64_t hop_tile_runs; /* tiles that ran in the hop-count searches, all fields */
+} artp_field_many_stats_t;
+int artp_field_compute_many(artp_ctx* ctx, const artp_field_params* params, int n_yaw, const int rect[4],
+                            const uint32_t* mask, int mask_on_device, const int* sources, const uint64_t* set_offsets,
+                            size_t n_sets, int reverse, artp_field** out_fields);
+int artp_field_cost_matrix(artp_ctx* ctx, const artp_field_params* params, int n_yaw, const int rect[4],
+                           const uint32_t* mask, int mask_on_device, const int* poses, size_t n, size_t batch,
+                           double* matrix_out, artp_field_many_stats_t* stats_out);
+
 /* ---- ob::MotionValidator::checkMotion (OMPL DiscreteMotionValidator; call sites
  *      prm_motion_cost.cpp:652, lazy_prm_star_min_update.cpp:725), batched -----------------------
  * valid[i] = isValid(s2_i) && all interior states of the discretised segment are valid.
