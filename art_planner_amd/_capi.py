@@ -29,6 +29,8 @@ SYMBOLS = [
     "artp_field_clearance_params_defaults", "artp_field_compute_clearance", "artp_field_clearance",
     "artp_field_update_clearance", "artp_field_clearance_update_stats", "artp_field_shift", "artp_field_shift_stats",
     "artp_field_shift_clearance", "artp_field_clearance_shift_stats", "artp_field_compute_many", "artp_field_cost_matrix",
+    "artp_field_compute_many_learned", "artp_field_compute_many_clearance", "artp_field_cost_matrix_learned",
+    "artp_field_cost_matrix_clearance",
     "artp_check_motions_last_valid", "artp_check_motions_last_valid_dev",
     "artp_set_z_bounds", "artp_set_few_edges", "artp_set_tail_mode", "artp_last_tail", "artp_set_edge_passes", "artp_cost_set_fc_path", "artp_check_motions", "artp_check_motions_dev", "artp_check_edges_interp",
     "artp_check_edges_interp_dev", "artp_compact_valid_dev", "artp_compact_valid_indices_dev", "artp_sample_states_at_dev",
@@ -191,6 +193,11 @@ class FieldManyStats(C.Structure):  # artp_field_many_stats_t
     _fields_ = [(n, C.c_uint64) for n in ("groups", "fields", "dist_rounds", "hop_rounds", "tile_runs", "hop_tile_runs")]
 
 
+class FieldManyTableStats(C.Structure):  # artp_field_many_table_stats_t
+    _fields_ = ([(n, C.c_uint64) for n in ("table_builds", "table_rows", "table_bytes", "table_copies")] +
+                [("build_ms", C.c_double)])
+
+
 class TreeParams(C.Structure):  # artp_tree_params (include/artp_c.h)
     _fields_ = [("seed", C.c_uint64), ("first_index", C.c_uint64), ("variant", C.c_int32), ("objective", C.c_int32),
                 ("max_lon_vel", C.c_double), ("max_lat_vel", C.c_double), ("max_ang_vel", C.c_double),
@@ -308,6 +315,13 @@ def _load_path(LIB_PATH):
     L.artp_field_compute_many.argtypes = [vp, C.POINTER(FieldParams), i32, vp, vp, i32, vp, vp, sz, i32, vp]
     L.artp_field_cost_matrix.argtypes = [vp, C.POINTER(FieldParams), i32, vp, vp, i32, vp, sz, sz, vp,
                                          C.POINTER(FieldManyStats)]
+    L.artp_field_compute_many_learned.argtypes = [vp, C.POINTER(FieldLearnedParams), i32, vp, vp, i32, vp, vp, sz, i32, vp]
+    L.artp_field_compute_many_clearance.argtypes = [vp, C.POINTER(FieldClearanceParams), i32, vp, vp, i32, vp, vp, sz, i32,
+                                                    vp]
+    L.artp_field_cost_matrix_learned.argtypes = [vp, C.POINTER(FieldLearnedParams), i32, vp, vp, i32, vp, sz, sz, vp,
+                                                 C.POINTER(FieldManyStats), C.POINTER(FieldManyTableStats)]
+    L.artp_field_cost_matrix_clearance.argtypes = [vp, C.POINTER(FieldClearanceParams), i32, vp, vp, i32, vp, sz, sz, vp,
+                                                   C.POINTER(FieldManyStats), C.POINTER(FieldManyTableStats)]
     L.artp_map_version.argtypes = [vp]
     L.artp_map_version.restype = C.c_uint64
     L.artp_set_z_bounds.argtypes = [vp, dbl, dbl]

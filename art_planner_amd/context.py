@@ -351,6 +351,57 @@ class Context:
                                             max_lat_vel=max_lat_vel, max_ang_vel=max_ang_vel, plain_sweeps=plain_sweeps,
                                             inner_sweeps=inner_sweeps)
 
+    def learned_cost_fields(self, mask, n_yaw, sources_list, *, rect=None, reverse=False, w_energy=None, w_time=None,
+                            w_risk=None, risk_threshold=None, plain_sweeps=False, inner_sweeps=64) -> list:
+        """One learned_cost_field per source set of sources_list in one batched call (artp_field_compute_many_learned,
+        DESIGN.md section 24): the weight table is priced once through the network and every field searches it side by
+        side.  Field b holds the bits of learned_cost_field(mask, n_yaw, sources_list[b], ...) and owns its own copy of
+        the table: each is updated (update_learned), blocked, planned on and closed on its own.  learned_stats() of
+        every field describes the shared build.  plain_sweeps=True is refused; a bad source names its set."""
+        from .field import CostField
+        return CostField.many_learned(self, mask, n_yaw, sources_list, rect=rect, reverse=reverse, w_energy=w_energy,
+                                      w_time=w_time, w_risk=w_risk, risk_threshold=risk_threshold,
+                                      plain_sweeps=plain_sweeps, inner_sweeps=inner_sweeps)
+
+    def clearance_cost_fields(self, mask, n_yaw, sources_list, *, margin=0.2, gain=2.0, radius_cells=12, yaw_spread=0,
+                              outside_is_obstacle=False, rect=None, reverse=False, objective=1, max_lon_vel=0.5,
+                              max_lat_vel=0.1, max_ang_vel=0.5, plain_sweeps=False, inner_sweeps=64) -> list:
+        """One clearance_cost_field per source set in one batched call (artp_field_compute_many_clearance): one clearance
+        map and one weight table for the batch, a copy of both for every field.  Field b holds the bits of
+        clearance_cost_field(mask, n_yaw, sources_list[b], ...); update_clearance, shift_clearance, plan and clearance()
+        work on each one alone."""
+        from .field import CostField
+        return CostField.many_clearance_weighted(self, mask, n_yaw, sources_list, margin=margin, gain=gain,
+                                                 radius_cells=radius_cells, yaw_spread=yaw_spread,
+                                                 outside_is_obstacle=outside_is_obstacle, rect=rect, reverse=reverse,
+                                                 objective=objective, max_lon_vel=max_lon_vel, max_lat_vel=max_lat_vel,
+                                                 max_ang_vel=max_ang_vel, plain_sweeps=plain_sweeps,
+                                                 inner_sweeps=inner_sweeps)
+
+    def learned_cost_matrix(self, mask, n_yaw, poses, batch=None, *, rect=None, w_energy=None, w_time=None, w_risk=None,
+                            risk_threshold=None, inner_sweeps=64, return_stats=False):
+        """cost_matrix under the learned motion cost (artp_field_cost_matrix_learned): M[i, j] = the forward
+        learned_cost_field of pose i read at pose j.  The learned cost is not symmetric, and neither is M.  The weight
+        table is priced once for all groups and freed with the call.  return_stats=True: (M, stats), the stats of
+        cost_matrix plus table_builds, table_rows, table_bytes, table_copies and build_ms."""
+        from .field import CostField
+        m, st = CostField.matrix_learned(self, mask, n_yaw, poses, batch=batch, rect=rect, w_energy=w_energy, w_time=w_time,
+                                         w_risk=w_risk, risk_threshold=risk_threshold, inner_sweeps=inner_sweeps)
+        return (m, st) if return_stats else m
+
+    def clearance_cost_matrix(self, mask, n_yaw, poses, batch=None, *, margin=0.2, gain=2.0, radius_cells=12, yaw_spread=0,
+                              outside_is_obstacle=False, rect=None, objective=1, max_lon_vel=0.5, max_lat_vel=0.1,
+                              max_ang_vel=0.5, inner_sweeps=64, return_stats=False):
+        """cost_matrix under the clearance-weighted cost (artp_field_cost_matrix_clearance): one clearance map and one
+        weight table for all groups.  return_stats as for learned_cost_matrix."""
+        from .field import CostField
+        m, st = CostField.matrix_clearance_weighted(self, mask, n_yaw, poses, batch=batch, margin=margin, gain=gain,
+                                                    radius_cells=radius_cells, yaw_spread=yaw_spread,
+                                                    outside_is_obstacle=outside_is_obstacle, rect=rect,
+                                                    objective=objective, max_lon_vel=max_lon_vel, max_lat_vel=max_lat_vel,
+                                                    max_ang_vel=max_ang_vel, inner_sweeps=inner_sweeps)
+        return (m, st) if return_stats else m
+
     def check_edges_interp(self, s1, s2):
         s1 = np.ascontiguousarray(s1, np.float64).reshape(-1, 7)
         s2 = np.ascontiguousarray(s2, np.float64).reshape(-1, 7)

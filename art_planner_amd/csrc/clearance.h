@@ -370,6 +370,29 @@ int field_clearance_build(artp_ctx* c, artp_field* f, const double* tab) {
   return rc;
 }
 
+// What a clearance-weighted entry point (who: artp_field_compute_clearance, or a batched one below) refuses about the
+// context, the rectangle and its params, behind the context's lock.
+int field_clearance_checks(artp_ctx* c, const char* who, const artp_field_clearance_params& p, int n_yaw, const int* rect,
+                           size_t n_sources, artp::ReachRect* r) {
+  if (!reach_have_lattice(c)) return ARTP_ERR_NO_MAP;
+  ARTP_TRY(reach_resolve(c, n_yaw, rect, r));
+  ARTP_TRY(field_check_params(c, p.base));
+  if (n_sources > (size_t)1 << 24) {
+    c->last_error = std::string(who) + ": n_sources <= 2^24";
+    return ARTP_ERR_INVALID_ARG;
+  }
+  ARTP_TRY(clearance_check(c, p.clearance, n_yaw));
+  if (!(p.margin > 0.0) || !std::isfinite(p.margin) || !(p.gain >= 0.0) || !std::isfinite(p.gain)) {
+    c->last_error = std::string(who) + ": margin must be positive and finite, gain non-negative and finite";
+    return ARTP_ERR_INVALID_ARG;
+  }
+  if (p.margin > (double)p.clearance.radius_cells * c->geom.res) {
+    c->last_error = std::string(who) + ": margin exceeds radius_cells * resolution (clearance beyond the cap is unknown)";
+    return ARTP_ERR_INVALID_ARG;
+  }
+  return ARTP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -428,25 +451,46 @@ int artp_field_compute_clearance(artp_ctx* c, const artp_field_clearance_params*
   if (out) *out = nullptr;
   if (!c || !params || !mask || !sources || !out || n_sources < 1) return ARTP_ERR_INVALID_ARG;
   std::lock_guard<std::recursive_mutex> lock(c->mu);
-  if (!reach_have_lattice(c)) return ARTP_ERR_NO_MAP;
   artp::ReachRect r;
-  ARTP_TRY(reach_resolve(c, n_yaw, rect, &r));
-  ARTP_TRY(field_check_params(c, params->base));
-  if (n_sources > (size_t)1 << 24) {
-    c->last_error = "artp_field_compute_clearance: n_sources <= 2^24";
-    return ARTP_ERR_INVALID_ARG;
-  }
-  ARTP_TRY(clearance_check(c, params->clearance, n_yaw));
-  if (!(params->margin > 0.0) || !std::isfinite(params->margin) || !(params->gain >= 0.0) || !std::isfinite(params->gain)) {
-    c->last_error = "artp_field_compute_clearance: margin must be positive and finite, gain non-negative and finite";
-    return ARTP_ERR_INVALID_ARG;
-  }
-  if (params->margin > (double)params->clearance.radius_cells * c->geom.res) {
-    c->last_error = "artp_field_compute_clearance: margin exceeds radius_cells * resolution (clearance beyond the cap is unknown)";
-    return ARTP_ERR_INVALID_ARG;
-  }
+  ARTP_TRY(field_clearance_checks(c, "artp_field_compute_clearance", *params, n_yaw, rect, n_sources, &r));
   ARTP_TRY(field_check_sources(c, r, n_yaw, sources, n_sources));
   return field_create(c, params->base, nullptr, params, r, mask, mask_on_device, sources, n_sources, reverse, out);
+}
+
+// The batched forms (field_many.h): one clearance map and one weight table for the whole batch.
+int artp_field_compute_many_clearance(artp_ctx* c, const artp_field_clearance_params* params, int n_yaw, const int* rect,
+                                      const uint32_t* mask, int mask_on_device, const int* sources,
+                                      const uint64_t* set_offsets, size_t n_sets, int reverse, artp_field** out_fields) {
+  if (out_fields)
+    for (size_t b = 0; b < n_sets && b < 65536; ++b) out_fields[b] = nullptr;
+  if (!c || !params || !mask || !sources || !set_offsets || !out_fields) return ARTP_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> lock(c->mu);
+  const char* who = "artp_field_compute_many_clearance";
+  ARTP_TRY(field_many_check_count(c, who, n_sets));
+  artp::ReachRect r;
+  ARTP_TRY(field_clearance_checks(c, who, *params, n_yaw, rect, 1, &r));
+  ARTP_TRY(field_many_tiled_only(c, who, params->base.plain_sweeps));
+  FieldManyTable wt;
+  wt.cp = params;
+  return field_many_run(c, who, params->base, r, mask, mask_on_device, sources, set_offsets, n_sets, reverse, out_fields, &wt);
+}
+
+int artp_field_cost_matrix_clearance(artp_ctx* c, const artp_field_clearance_params* params, int n_yaw, const int* rect,
+                                     const uint32_t* mask, int mask_on_device, const int* poses, size_t n, size_t batch,
+                                     double* matrix_out, artp_field_many_stats_t* stats_out,
+                                     artp_field_many_table_stats_t* table_out) {
+  if (stats_out) std::memset(stats_out, 0, sizeof(*stats_out));
+  if (table_out) std::memset(table_out, 0, sizeof(*table_out));
+  if (!c || !params || !mask || !poses || !matrix_out) return ARTP_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> lock(c->mu);
+  const char* who = "artp_field_cost_matrix_clearance";
+  ARTP_TRY(field_matrix_check_count(c, who, n));
+  artp::ReachRect r;
+  ARTP_TRY(field_clearance_checks(c, who, *params, n_yaw, rect, 1, &r));
+  ARTP_TRY(field_many_tiled_only(c, who, params->base.plain_sweeps));
+  FieldManyTable wt;
+  wt.cp = params;
+  return field_matrix_run(c, who, params->base, r, mask, mask_on_device, poses, n, batch, matrix_out, stats_out, &wt, table_out);
 }
 
 int artp_field_clearance(artp_field* f, uint16_t* d2_out) {

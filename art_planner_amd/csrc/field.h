@@ -30,9 +30,10 @@
 //                cells back (plain vector stores; the halo is read-only), flags the neighbouring tiles whose halo it
 //                changed for the next launch, and itself when it ran out of sweeps.  A launch covers every tile; the
 //                ones nobody flagged leave at once.  The skeleton's body is one function, field_tile_body, of the tile
-//                index and the per-field pointers; field_tile_many_kernel<PHASE> runs it (relax, (m, k) table) on a grid of
+//                index and the per-field pointers; field_tile_many_kernel<PHASE, LEARNED> runs it (relax, (m, k) table) on a grid of
 //                (tiles, fields) for a batch of fields that share mask, heights and table (field_many.h, DESIGN.md
-//                section 23).
+//                section 23); with LEARNED it runs on the ONE streamed weight table of a batch of learned or
+//                clearance-weighted fields.
 // field_rounds is the host loop of both forms: launch, read the counters, stop when nothing was flagged, refuse after
 // n_nodes + 2 rounds.  No launch waits for another workgroup and no kernel stays resident.
 //
@@ -529,15 +530,28 @@ struct FieldSlot {
 // The relax rule of PHASE on a batch of fields: grid (n_tiles, n_sets), blockIdx.y picks the slot.  parity: which of the
 // slot's two flag arrays is this round's (the other collects the next round's).  A tile flags tiles of its own field only:
 // every flag it writes goes through its slot's pointers.
-template <int PHASE>
+// LEARNED (objectives 2 and 3): tabg is the batch's ONE weight table, streamed by every field.  The
+// grid stays (n_tiles, n_sets): a 1-D grid decoded so that all fields of a tile share linear id % 8 (one XCD's L2, as the
+// chip deals workgroups today) was measured and lost, 103.0 against 99.2 ms and 91.4 against 84.8 ms at eight fields.
+template <int PHASE, bool LEARNED = false>
 __global__ void __launch_bounds__(256)
 field_tile_many_kernel(FieldGrid G, const uint32_t* __restrict__ mask, const float* __restrict__ h,
                        const double* __restrict__ tabg, const FieldSlot* __restrict__ slots, int parity, int inner_max) {
   const FieldSlot s = slots[blockIdx.y];
   const size_t n_tiles = (size_t)G.tiles_r * (size_t)G.tiles_c;
-  field_tile_body<PHASE, false, false>(G, (int)blockIdx.x, mask, h, tabg, nullptr, s.dist, s.hops,
-                                       s.flags + (parity ? n_tiles : 0), s.flags + (parity ? 0 : n_tiles), nullptr, s.counters,
-                                       inner_max);
+  field_tile_body<PHASE, false, LEARNED>(G, (int)blockIdx.x, mask, h, tabg, nullptr, s.dist, s.hops,
+                                         s.flags + (parity ? n_tiles : 0), s.flags + (parity ? 0 : n_tiles), nullptr, s.counters,
+                                         inner_max);
+}
+
+// bad[i] = 1 where pose i (a triple inside the rectangle) is no node of the mask (the weighted cost matrices check every
+// pose in front of the table build)
+__global__ void __launch_bounds__(64)
+field_pose_check_kernel(FieldGrid G, const uint32_t* __restrict__ mask, const int* __restrict__ poses, int n,
+                        unsigned* __restrict__ bad) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  bad[i] = ((mask[(size_t)poses[3 * i] + (size_t)poses[3 * i + 1] * G.nrows] >> poses[3 * i + 2]) & 1u) ? 0u : 1u;
 }
 
 // out[b n + j] = the distance of field b at node nodes[j] (artp_field_cost_matrix): grid (ceil(n / 256), n_sets)
@@ -1510,6 +1524,37 @@ int field_create(artp_ctx* c, const artp_field_params& params, const artp_field_
 artp_field* field_new(artp_ctx* c, const artp_field_params& params, const artp_field_learned_params* lp,
                       const artp_field_clearance_params* cp, const artp::ReachRect& r, int reverse);
 
+// What a learned entry point (who: artp_field_compute_learned, or a batched one of field_many.h) refuses about the context,
+// the rectangle and its params, behind the context's lock; *fp = the field params a learned field carries.
+int field_learned_checks(artp_ctx* c, const char* who, const artp_field_learned_params& p, int n_yaw, const int* rect,
+                         size_t n_sources, artp::ReachRect* r, artp_field_params* fp) {
+  if (!c->have_weights) {
+    c->last_error = std::string(who) + ": artp_cost_load_weights has not been called";
+    return ARTP_ERR_NO_WEIGHTS;
+  }
+  if (!c->have_features) {
+    c->last_error = std::string(who) + ": artp_cost_update_map has not been called";
+    return ARTP_ERR_NO_MAP;
+  }
+  if (!reach_have_lattice(c)) return ARTP_ERR_NO_MAP;
+  ARTP_TRY(reach_resolve(c, n_yaw, rect, r));
+  const float wt[4] = {p.w_energy, p.w_time, p.w_risk, p.risk_threshold};
+  for (float v : wt)
+    if (!(v >= 0.0f) || !std::isfinite(v)) {
+      c->last_error = std::string(who) + ": the weights and the risk threshold must be non-negative and finite";
+      return ARTP_ERR_INVALID_ARG;
+    }
+  if (p.inner_sweeps < 1 || n_sources > (size_t)1 << 24) {
+    c->last_error = std::string(who) + ": inner_sweeps >= 1, n_sources <= 2^24";
+    return ARTP_ERR_INVALID_ARG;
+  }
+  artp_field_params_defaults(fp);  // the velocities are not used
+  fp->objective = 2;
+  fp->plain_sweeps = p.plain_sweeps;
+  fp->inner_sweeps = p.inner_sweeps;
+  return ARTP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1564,35 +1609,12 @@ int artp_field_compute_learned(artp_ctx* c, const artp_field_learned_params* par
   if (out) *out = nullptr;
   if (!c || !params || !mask || !sources || !out || n_sources < 1) return ARTP_ERR_INVALID_ARG;
   std::lock_guard<std::recursive_mutex> lock(c->mu);
-  if (!c->have_weights) {
-    c->last_error = "artp_field_compute_learned: artp_cost_load_weights has not been called";
-    return ARTP_ERR_NO_WEIGHTS;
-  }
-  if (!c->have_features) {
-    c->last_error = "artp_field_compute_learned: artp_cost_update_map has not been called";
-    return ARTP_ERR_NO_MAP;
-  }
-  if (!reach_have_lattice(c)) return ARTP_ERR_NO_MAP;
   artp::ReachRect r;
-  int rc = reach_resolve(c, n_yaw, rect, &r);
+  artp_field_params fp;
+  int rc = field_learned_checks(c, "artp_field_compute_learned", *params, n_yaw, rect, n_sources, &r, &fp);
   if (rc) return rc;
-  const float wt[4] = {params->w_energy, params->w_time, params->w_risk, params->risk_threshold};
-  for (float v : wt)
-    if (!(v >= 0.0f) || !std::isfinite(v)) {
-      c->last_error = "artp_field_compute_learned: the weights and the risk threshold must be non-negative and finite";
-      return ARTP_ERR_INVALID_ARG;
-    }
-  if (params->inner_sweeps < 1 || n_sources > (size_t)1 << 24) {
-    c->last_error = "artp_field_compute_learned: inner_sweeps >= 1, n_sources <= 2^24";
-    return ARTP_ERR_INVALID_ARG;
-  }
   rc = field_check_sources(c, r, n_yaw, sources, n_sources);
   if (rc) return rc;
-  artp_field_params fp;
-  artp_field_params_defaults(&fp);  // the velocities are not used
-  fp.objective = 2;
-  fp.plain_sweeps = params->plain_sweeps;
-  fp.inner_sweeps = params->inner_sweeps;
   return field_create(c, fp, params, nullptr, r, mask, mask_on_device, sources, n_sources, reverse, out);
 }
 

@@ -17,6 +17,38 @@ def _field_params(ctx, objective, plain_sweeps, inner_sweeps, max_lon_vel, max_l
     return p
 
 
+def _learned_params(ctx, w_energy, w_time, w_risk, risk_threshold, plain_sweeps, inner_sweeps):
+    """artp_field_learned_params from the keywords the learned fields share; None keeps a default of the library."""
+    p = _capi.FieldLearnedParams()
+    ctx.L.artp_field_learned_params_defaults(C.byref(p))
+    for name, v in (("w_energy", w_energy), ("w_time", w_time), ("w_risk", w_risk), ("risk_threshold", risk_threshold)):
+        if v is not None:
+            setattr(p, name, v)
+    p.plain_sweeps, p.inner_sweeps = int(bool(plain_sweeps)), int(inner_sweeps)
+    return p
+
+
+def _clearance_params(ctx, margin, gain, radius_cells, yaw_spread, outside_is_obstacle, objective, max_lon_vel, max_lat_vel,
+                      max_ang_vel, plain_sweeps, inner_sweeps):
+    """artp_field_clearance_params from the keywords the clearance-weighted fields share."""
+    p = _capi.FieldClearanceParams()
+    ctx.L.artp_field_clearance_params_defaults(C.byref(p))
+    b = p.base
+    b.objective, b.plain_sweeps, b.inner_sweeps = int(objective), int(bool(plain_sweeps)), int(inner_sweeps)
+    b.max_lon_vel, b.max_lat_vel, b.max_ang_vel = max_lon_vel, max_lat_vel, max_ang_vel
+    p.clearance.radius_cells, p.clearance.yaw_spread = int(radius_cells), int(yaw_spread)
+    p.clearance.outside_is_obstacle = int(bool(outside_is_obstacle))
+    p.margin, p.gain = float(margin), float(gain)
+    return p
+
+
+# the Context method behind each batched entry point: what a refused mask is reported under
+_METHOD = {"artp_field_compute_many": "cost_fields", "artp_field_compute_many_learned": "learned_cost_fields",
+           "artp_field_compute_many_clearance": "clearance_cost_fields", "artp_field_cost_matrix": "cost_matrix",
+           "artp_field_cost_matrix_learned": "learned_cost_matrix",
+           "artp_field_cost_matrix_clearance": "clearance_cost_matrix"}
+
+
 def _mask_arg(mask, nr, nc, what):
     """(pointer, on_device, the object that owns the memory) of a mask of an nr x nc rectangle."""
     if hasattr(mask, "data_ptr"):   # a device tensor of nrows * ncols 32-bit words, column-major
@@ -43,12 +75,7 @@ class CostField:
                 risk_threshold=None, plain_sweeps=False, inner_sweeps=64):
         """The field under the motion-cost network (artp_field_compute_learned); None keeps a default of the library."""
         self = cls.__new__(cls)
-        p = _capi.FieldLearnedParams()
-        ctx.L.artp_field_learned_params_defaults(C.byref(p))
-        for name, v in (("w_energy", w_energy), ("w_time", w_time), ("w_risk", w_risk), ("risk_threshold", risk_threshold)):
-            if v is not None:
-                setattr(p, name, v)
-        p.plain_sweeps, p.inner_sweeps = int(bool(plain_sweeps)), int(inner_sweeps)
+        p = _learned_params(ctx, w_energy, w_time, w_risk, risk_threshold, plain_sweeps, inner_sweeps)
         self._compute(ctx, ctx.L.artp_field_compute_learned, "artp_field_compute_learned", p, mask, n_yaw, sources, rect,
                       reverse)
         return self
@@ -60,14 +87,8 @@ class CostField:
         """The field whose move costs are the objective's, inflated near obstacles (artp_field_compute_clearance,
         DESIGN.md section 17)."""
         self = cls.__new__(cls)
-        p = _capi.FieldClearanceParams()
-        ctx.L.artp_field_clearance_params_defaults(C.byref(p))
-        b = p.base
-        b.objective, b.plain_sweeps, b.inner_sweeps = int(objective), int(bool(plain_sweeps)), int(inner_sweeps)
-        b.max_lon_vel, b.max_lat_vel, b.max_ang_vel = max_lon_vel, max_lat_vel, max_ang_vel
-        p.clearance.radius_cells, p.clearance.yaw_spread = int(radius_cells), int(yaw_spread)
-        p.clearance.outside_is_obstacle = int(bool(outside_is_obstacle))
-        p.margin, p.gain = float(margin), float(gain)
+        p = _clearance_params(ctx, margin, gain, radius_cells, yaw_spread, outside_is_obstacle, objective, max_lon_vel,
+                              max_lat_vel, max_ang_vel, plain_sweeps, inner_sweeps)
         self._compute(ctx, ctx.L.artp_field_compute_clearance, "artp_field_compute_clearance", p, mask, n_yaw, sources, rect,
                       reverse)
         return self
@@ -87,16 +108,39 @@ class CostField:
              max_lat_vel=0.1, max_ang_vel=0.5, plain_sweeps=False, inner_sweeps=64) -> list:
         """One CostField per source set, computed in one batched search (artp_field_compute_many)."""
         p = _field_params(ctx, objective, plain_sweeps, inner_sweeps, max_lon_vel, max_lat_vel, max_ang_vel)
+        return cls._many(ctx, "artp_field_compute_many", p, mask, n_yaw, sources_list, rect, reverse)
+
+    @classmethod
+    def many_learned(cls, ctx, mask, n_yaw, sources_list, rect=None, reverse=False, w_energy=None, w_time=None, w_risk=None,
+                     risk_threshold=None, plain_sweeps=False, inner_sweeps=64) -> list:
+        """One learned CostField per source set on one shared build of the weight table
+        (artp_field_compute_many_learned)."""
+        p = _learned_params(ctx, w_energy, w_time, w_risk, risk_threshold, plain_sweeps, inner_sweeps)
+        return cls._many(ctx, "artp_field_compute_many_learned", p, mask, n_yaw, sources_list, rect, reverse)
+
+    @classmethod
+    def many_clearance_weighted(cls, ctx, mask, n_yaw, sources_list, margin=0.2, gain=2.0, radius_cells=12, yaw_spread=0,
+                                outside_is_obstacle=False, rect=None, reverse=False, objective=1, max_lon_vel=0.5,
+                                max_lat_vel=0.1, max_ang_vel=0.5, plain_sweeps=False, inner_sweeps=64) -> list:
+        """One clearance-weighted CostField per source set on one clearance map and one weight table
+        (artp_field_compute_many_clearance)."""
+        p = _clearance_params(ctx, margin, gain, radius_cells, yaw_spread, outside_is_obstacle, objective, max_lon_vel,
+                              max_lat_vel, max_ang_vel, plain_sweeps, inner_sweeps)
+        return cls._many(ctx, "artp_field_compute_many_clearance", p, mask, n_yaw, sources_list, rect, reverse)
+
+    @classmethod
+    def _many(cls, ctx, name, p, mask, n_yaw, sources_list, rect, reverse) -> list:
+        """The mask and set handling of the three batched constructors; name = the C entry point, p = its params."""
         r, nr, nc = ctx._reach_rect(rect)
-        mask_ptr, on_device, keep = _mask_arg(mask, nr, nc, "cost_fields")
+        mask_ptr, on_device, keep = _mask_arg(mask, nr, nc, _METHOD[name])
         sets = [np.ascontiguousarray(s, np.int32).reshape(-1, 3) for s in sources_list]
         off = np.zeros(len(sets) + 1, np.uint64)
         off[1:] = np.cumsum([len(s) for s in sets])
         src = np.concatenate(sets) if sets and int(off[-1]) else np.zeros((1, 3), np.int32)
         handles = (C.c_void_p * max(len(sets), 1))()
-        ctx._chk(ctx.L.artp_field_compute_many(ctx.h, C.byref(p), int(n_yaw), r.ctypes.data if r is not None else None,
-                                               mask_ptr, on_device, src.ctypes.data, off.ctypes.data, len(sets),
-                                               int(bool(reverse)), handles), "artp_field_compute_many")
+        ctx._chk(getattr(ctx.L, name)(ctx.h, C.byref(p), int(n_yaw), r.ctypes.data if r is not None else None, mask_ptr,
+                                      on_device, src.ctypes.data, off.ctypes.data, len(sets), int(bool(reverse)), handles),
+                 name)
         del keep
         return [cls.adopt(ctx, handles[b], nr, nc, n_yaw, reverse) for b in range(len(sets))]
 
@@ -105,16 +149,40 @@ class CostField:
                max_ang_vel=0.5, inner_sweeps=64):
         """((n, n) float64 costs from pose i to pose j, the call's stats) of artp_field_cost_matrix."""
         p = _field_params(ctx, objective, False, inner_sweeps, max_lon_vel, max_lat_vel, max_ang_vel)
+        return CostField._matrix(ctx, "artp_field_cost_matrix", p, mask, n_yaw, poses, batch, rect, False)
+
+    @staticmethod
+    def matrix_learned(ctx, mask, n_yaw, poses, batch=None, rect=None, w_energy=None, w_time=None, w_risk=None,
+                       risk_threshold=None, inner_sweeps=64):
+        """The same under the learned cost (artp_field_cost_matrix_learned): the stats carry the table's as well."""
+        p = _learned_params(ctx, w_energy, w_time, w_risk, risk_threshold, False, inner_sweeps)
+        return CostField._matrix(ctx, "artp_field_cost_matrix_learned", p, mask, n_yaw, poses, batch, rect, True)
+
+    @staticmethod
+    def matrix_clearance_weighted(ctx, mask, n_yaw, poses, batch=None, margin=0.2, gain=2.0, radius_cells=12, yaw_spread=0,
+                                  outside_is_obstacle=False, rect=None, objective=1, max_lon_vel=0.5, max_lat_vel=0.1,
+                                  max_ang_vel=0.5, inner_sweeps=64):
+        """The same under the clearance-weighted cost (artp_field_cost_matrix_clearance)."""
+        p = _clearance_params(ctx, margin, gain, radius_cells, yaw_spread, outside_is_obstacle, objective, max_lon_vel,
+                              max_lat_vel, max_ang_vel, False, inner_sweeps)
+        return CostField._matrix(ctx, "artp_field_cost_matrix_clearance", p, mask, n_yaw, poses, batch, rect, True)
+
+    @staticmethod
+    def _matrix(ctx, name, p, mask, n_yaw, poses, batch, rect, table):
+        """The mask and pose handling of the three matrices; table: the entry point also fills the table's stats."""
         r, nr, nc = ctx._reach_rect(rect)
-        mask_ptr, on_device, keep = _mask_arg(mask, nr, nc, "cost_matrix")
+        mask_ptr, on_device, keep = _mask_arg(mask, nr, nc, _METHOD[name])
         t = np.ascontiguousarray(poses, np.int32).reshape(-1, 3)
         out = np.empty((len(t), len(t)), np.float64)
-        st = _capi.FieldManyStats()
-        ctx._chk(ctx.L.artp_field_cost_matrix(ctx.h, C.byref(p), int(n_yaw), r.ctypes.data if r is not None else None,
-                                              mask_ptr, on_device, t.ctypes.data, len(t), int(batch or 0),
-                                              out.ctypes.data, C.byref(st)), "artp_field_cost_matrix")
+        st, ts = _capi.FieldManyStats(), _capi.FieldManyTableStats()
+        args = [ctx.h, C.byref(p), int(n_yaw), r.ctypes.data if r is not None else None, mask_ptr, on_device, t.ctypes.data,
+                len(t), int(batch or 0), out.ctypes.data, C.byref(st)] + ([C.byref(ts)] if table else [])
+        ctx._chk(getattr(ctx.L, name)(*args), name)
         del keep
-        return out, {n: int(getattr(st, n)) for n, _ in _capi.FieldManyStats._fields_}
+        stats = {n: int(getattr(st, n)) for n, _ in _capi.FieldManyStats._fields_}
+        if table:
+            stats.update({n: (float if t_ is C.c_double else int)(getattr(ts, n)) for n, t_ in _capi.FieldManyTableStats._fields_})
+        return out, stats
 
     def _compute(self, ctx, call, name, params, mask, n_yaw, sources, rect, reverse):
         """The mask and source handling both constructors share; call = the C entry point, params = its struct."""

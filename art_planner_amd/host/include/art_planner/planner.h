@@ -533,6 +533,139 @@ class Planner {
     return finishCostField(f, cells, n_yaw, keep);
   }
 
+  // computeLearnedCostField / computeClearanceCostField for many source sets at once, and the pose-to-pose matrices under
+  // the two costs (artp_field_compute_many_learned / _clearance, artp_field_cost_matrix_learned / _clearance,
+  // include/artp_c.h): the weight table is priced once per call and every field searches it side by side.  Field b holds
+  // the bits of the single call on source_sets[b] and owns its own copy of the table: each works with
+  // updateLearnedCostField / updateClearanceCostField, planOnCostField and the rest alone, and the caller destroys each.
+  // The learned cost is not symmetric, and neither is its matrix.  A matrix's table is freed with the call; table (may be
+  // null) receives its numbers.  The "cost_to_go" layer is not touched.
+  std::vector<artp_field*> computeLearnedCostFields(const std::vector<uint32_t>& mask, unsigned n_yaw,
+                                                    const std::vector<std::vector<std::array<int, 3>>>& source_sets,
+                                                    bool reverse = false) {
+    const artp_field_learned_params lp = learnedFieldParams();
+    return manyWeightedFields("computeLearnedCostFields", "artp_field_compute_many_learned", mask, source_sets,
+                              [&](const int* src, const uint64_t* off, artp_field** out) {
+                                return artp_field_compute_many_learned(gpu_->get(), &lp, static_cast<int>(n_yaw), nullptr,
+                                                                       mask.data(), 0, src, off, source_sets.size(),
+                                                                       reverse ? 1 : 0, out);
+                              });
+  }
+
+  std::vector<artp_field*> computeClearanceCostFields(const std::vector<uint32_t>& mask, unsigned n_yaw,
+                                                      const std::vector<std::vector<std::array<int, 3>>>& source_sets,
+                                                      double margin = 0.2, double gain = 2.0, int radius_cells = 12,
+                                                      int yaw_spread = 0, bool outside_is_obstacle = false,
+                                                      bool reverse = false) {
+    const artp_field_clearance_params fp = clearanceFieldParams(margin, gain, radius_cells, yaw_spread, outside_is_obstacle);
+    return manyWeightedFields("computeClearanceCostFields", "artp_field_compute_many_clearance", mask, source_sets,
+                              [&](const int* src, const uint64_t* off, artp_field** out) {
+                                return artp_field_compute_many_clearance(gpu_->get(), &fp, static_cast<int>(n_yaw), nullptr,
+                                                                         mask.data(), 0, src, off, source_sets.size(),
+                                                                         reverse ? 1 : 0, out);
+                              });
+  }
+
+  std::vector<double> computeLearnedCostMatrix(const std::vector<uint32_t>& mask, unsigned n_yaw,
+                                               const std::vector<std::array<int, 3>>& poses, size_t batch = 0,
+                                               artp_field_many_stats_t* stats = nullptr,
+                                               artp_field_many_table_stats_t* table = nullptr) {
+    const artp_field_learned_params lp = learnedFieldParams();
+    return weightedCostMatrix("computeLearnedCostMatrix", "artp_field_cost_matrix_learned", mask, poses,
+                              [&](const int* p, double* m) {
+                                return artp_field_cost_matrix_learned(gpu_->get(), &lp, static_cast<int>(n_yaw), nullptr,
+                                                                      mask.data(), 0, p, poses.size(), batch, m, stats, table);
+                              });
+  }
+
+  std::vector<double> computeClearanceCostMatrix(const std::vector<uint32_t>& mask, unsigned n_yaw,
+                                                 const std::vector<std::array<int, 3>>& poses, size_t batch = 0,
+                                                 double margin = 0.2, double gain = 2.0, int radius_cells = 12,
+                                                 int yaw_spread = 0, bool outside_is_obstacle = false,
+                                                 artp_field_many_stats_t* stats = nullptr,
+                                                 artp_field_many_table_stats_t* table = nullptr) {
+    const artp_field_clearance_params fp = clearanceFieldParams(margin, gain, radius_cells, yaw_spread, outside_is_obstacle);
+    return weightedCostMatrix("computeClearanceCostMatrix", "artp_field_cost_matrix_clearance", mask, poses,
+                              [&](const int* p, double* m) {
+                                return artp_field_cost_matrix_clearance(gpu_->get(), &fp, static_cast<int>(n_yaw), nullptr,
+                                                                        mask.data(), 0, p, poses.size(), batch, m, stats,
+                                                                        table);
+                              });
+  }
+
+ private:
+  // Params::planner.prm_motion_cost's weights and threshold, as computeLearnedCostField passes them
+  artp_field_learned_params learnedFieldParams() const {
+    artp_field_learned_params lp;
+    artp_field_learned_params_defaults(&lp);
+    const auto& pmc = params_->planner.prm_motion_cost;
+    lp.w_energy = pmc.cost_weights.energy;
+    lp.w_time = pmc.cost_weights.time;
+    lp.w_risk = pmc.cost_weights.risk;
+    lp.risk_threshold = pmc.risk_threshold;
+    return lp;
+  }
+
+  // Params::objectives.custom_path_length's base objective with the clearance weighting, as computeClearanceCostField
+  artp_field_clearance_params clearanceFieldParams(double margin, double gain, int radius_cells, int yaw_spread,
+                                                   bool outside_is_obstacle) const {
+    artp_field_clearance_params fp;
+    artp_field_clearance_params_defaults(&fp);
+    const auto& cpl = params_->objectives.custom_path_length;
+    fp.base.objective = cpl.use_directional_cost ? 1 : 0;
+    fp.base.max_lon_vel = cpl.max_lon_vel;
+    fp.base.max_lat_vel = cpl.max_lat_vel;
+    fp.base.max_ang_vel = cpl.max_ang_vel;
+    fp.clearance.radius_cells = radius_cells;
+    fp.clearance.yaw_spread = yaw_spread;
+    fp.clearance.outside_is_obstacle = outside_is_obstacle ? 1 : 0;
+    fp.margin = margin;
+    fp.gain = gain;
+    return fp;
+  }
+
+  // the map check, the flattened sets and the handles of a batched weighted call; call(sources, offsets, out_fields)
+  template <class Call>
+  std::vector<artp_field*> manyWeightedFields(const char* who, const char* entry, const std::vector<uint32_t>& mask,
+                                              const std::vector<std::vector<std::array<int, 3>>>& source_sets, Call&& call) {
+    std::lock_guard<std::mutex> lock(map_mutex_);
+    if (!map_) throw std::runtime_error(std::string(who) + ": the planner does not have a map set");
+    const auto g = map_->getGeometry();
+    if (mask.size() != static_cast<size_t>(g.rows) * g.cols)
+      throw std::runtime_error(std::string(who) + ": the mask does not have rows * cols words");
+    std::vector<int> src;
+    std::vector<uint64_t> off(1, 0);
+    for (const auto& set : source_sets) {
+      for (const auto& s : set) src.insert(src.end(), s.begin(), s.end());
+      off.push_back(src.size() / 3);
+    }
+    if (src.empty()) src.resize(3, 0);   // a pointer the library can refuse the empty call behind
+    std::vector<artp_field*> fields(std::max<size_t>(source_sets.size(), 1), nullptr);
+    throwOnError(gpu_->get(), call(src.data(), off.data(), fields.data()), entry);
+    fields.resize(source_sets.size());
+    return fields;
+  }
+
+  // the same for a weighted matrix; call(poses, matrix_out)
+  template <class Call>
+  std::vector<double> weightedCostMatrix(const char* who, const char* entry, const std::vector<uint32_t>& mask,
+                                         const std::vector<std::array<int, 3>>& poses, Call&& call) {
+    std::lock_guard<std::mutex> lock(map_mutex_);
+    if (!map_) throw std::runtime_error(std::string(who) + ": the planner does not have a map set");
+    const auto g = map_->getGeometry();
+    if (mask.size() != static_cast<size_t>(g.rows) * g.cols)
+      throw std::runtime_error(std::string(who) + ": the mask does not have rows * cols words");
+    std::vector<int> p;
+    for (const auto& s : poses) p.insert(p.end(), s.begin(), s.end());
+    if (p.empty()) p.resize(3, 0);
+    std::vector<double> matrix(std::max<size_t>(poses.size() * poses.size(), 1));
+    throwOnError(gpu_->get(), call(p.data(), matrix.data()), entry);
+    matrix.resize(poses.size() * poses.size());
+    return matrix;
+  }
+
+ public:
+
   // The field a computeCostField call kept, brought in place to an edited mask (artp_field_update, include/artp_c.h):
   // the same bits as computeCostField on it, at the price of the region whose costs change.  mask = rows * cols words;
   // rect = (row0, col0, nrows, ncols) of the words that may differ (nullptr = all of them; the others are not read).

@@ -708,6 +708,53 @@ int artp_field_cost_matrix(artp_ctx* ctx, const artp_field_params* params, int n
                            const uint32_t* mask, int mask_on_device, const int* poses, size_t n, size_t batch,
                            double* matrix_out, artp_field_many_stats_t* stats_out);
 
+/* ---- Batched learned and clearance-weighted fields on one weight table ------------------------
+ * The two calls above for the fields of artp_field_compute_learned and artp_field_compute_clearance, whose pull weights
+ * sit in a table of 80 bytes per node that does not depend on the sources.  The table is priced ONCE per call, by the
+ * single field's own build (learned: rows -> the context's device network -> combine, in its chunks, whatever
+ * artp_cost_set_external_query installed; clearance: the clearance map of the mask, then the table kernel), and every
+ * field of the batch searches that one table side by side.
+ * artp_field_compute_many_*: field b is bit for bit -- dist, hop counts (so paths), edge costs, reached_nodes,
+ * artp_field_clearance -- what artp_field_compute_learned / _clearance gives for set b alone on the same context state.
+ * Every returned field owns its own copy of the table (a clearance field also of its clearance map and base table),
+ * copied device to device in front of the search: artp_field_update_learned, _update_clearance, _shift_clearance,
+ * _block_moves, _plan, _path, _edge_costs, _clearance and _destroy work on each one alone.  artp_field_learned_stats of
+ * every field describes the shared build (table_rows, table_bytes, chunks and the three build times, the same numbers
+ * in every field) and the batch's dist_ms / hop_ms: the host's time for the two batched passes as a whole, not a field's
+ * share of them (inside a matrix, each group's own two passes).  artp_field_stats as for artp_field_compute_many.
+ * artp_field_cost_matrix_*: matrix_out[i n + j] = that forward field of pose i read at pose j.  Under the learned cost
+ * w(a -> b) != w(b -> a): the matrix is not symmetric.  The call owns the one table for all its groups and frees it
+ * before it returns; `batch` = 0 sizes the groups by half of the memory that is free once the table stands.
+ * table_out (may be NULL): table_builds = 1 however many groups ran, table_copies = 0 (no field of a matrix outlives
+ * the call, so none gets a copy), table_rows / table_bytes of the one table, build_ms its stream time.
+ * Refused with nothing left allocated, every out_fields[b] = NULL and both stats structs zeroed: everything the single
+ * entry point refuses (ARTP_ERR_NO_WEIGHTS, ARTP_ERR_NO_MAP included), everything artp_field_compute_many refuses about
+ * sets, offsets and plain_sweeps, a source that is no node of the mask (the text names its set; a matrix checks every
+ * pose before it prices anything and names the pose).  ARTP_ERR_CAPACITY, with a text, when hipMemGetInfo shows less free
+ * memory than the table, its copies (compute_many only), the build's scratch and the fields need.  Synchronous, on the
+ * current lane's stream; no context state is written beyond what artp_field_compute_learned writes. */
+typedef struct artp_field_many_table_stats_t {
+  uint64_t table_builds;  /* times the weight table was priced: 1 */
+  uint64_t table_rows;    /* slots of one table */
+  uint64_t table_bytes;   /* bytes of one table */
+  uint64_t table_copies;  /* device-to-device copies made for fields that outlive the call */
+  double build_ms;        /* stream time of the build */
+} artp_field_many_table_stats_t;
+int artp_field_compute_many_learned(artp_ctx* ctx, const artp_field_learned_params* params, int n_yaw, const int rect[4],
+                                    const uint32_t* mask, int mask_on_device, const int* sources,
+                                    const uint64_t* set_offsets, size_t n_sets, int reverse, artp_field** out_fields);
+int artp_field_compute_many_clearance(artp_ctx* ctx, const artp_field_clearance_params* params, int n_yaw, const int rect[4],
+                                      const uint32_t* mask, int mask_on_device, const int* sources,
+                                      const uint64_t* set_offsets, size_t n_sets, int reverse, artp_field** out_fields);
+int artp_field_cost_matrix_learned(artp_ctx* ctx, const artp_field_learned_params* params, int n_yaw, const int rect[4],
+                                   const uint32_t* mask, int mask_on_device, const int* poses, size_t n, size_t batch,
+                                   double* matrix_out, artp_field_many_stats_t* stats_out,
+                                   artp_field_many_table_stats_t* table_out);
+int artp_field_cost_matrix_clearance(artp_ctx* ctx, const artp_field_clearance_params* params, int n_yaw, const int rect[4],
+                                     const uint32_t* mask, int mask_on_device, const int* poses, size_t n, size_t batch,
+                                     double* matrix_out, artp_field_many_stats_t* stats_out,
+                                     artp_field_many_table_stats_t* table_out);
+
 /* ---- ob::MotionValidator::checkMotion (OMPL DiscreteMotionValidator; call sites
  *      prm_motion_cost.cpp:652, lazy_prm_star_min_update.cpp:725), batched -----------------------
  * valid[i] = isValid(s2_i) && all interior states of the discretised segment are valid.
